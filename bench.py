@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json's metric on MI355X: Mpixels/s (and concurrent 1080p30 streams) of MixtureOfGaussianV2BGS.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--input sat|surv]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--input sat|surv] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...     (one rank per GPU, RCCL)
 
 A step = one frame of every stream on this rank's GPU through bgs_process_batch_device (ONE kernel launch over
 streams x pixels, frames already resident in HBM).  Streams shard across ranks with no data-path collective;
 with N > 1 the bit-packed masks are gathered to rank 0 every step (the one real exchange step),
 overlapped with the next step's kernel.  Rank 0 prints ONE JSON line.
+
+A plain run sets up and ages the model, warms up, times the K steps and prints the line.  --full adds every other leg:
+the host path, this box's copy calibration and clocks, the sustained launches, clips, the placement witness, one
+stream alone, the S_surv / S_dense scenes, BASELINE's other configs, the CPU baseline and the live PMC traffic passes.
+--dump-outputs DIR writes what the last timed step computed as float32 .npy files: rank 0's masks (and backgrounds with
+--with-bg), stream 0 whole and a fixed, seeded sample over all streams, and a fixed sample of stream 0's model state.
 """
 import argparse
 import json
@@ -382,6 +388,30 @@ def clip_leg(eng, pool, period, S, T, launches=40, warm=10):
             "bytes_model_per_pixel_frame": round(model, 1), "added_latency_frames": T - 1}
 
 
+DUMP_SAMPLE = 1 << 20   # sampled entries per dumped mask / background array (4 MiB of float32)
+STATE_SAMPLE = 1 << 17  # stream-0 pixels whose model state is dumped (13 MiB for w, var, mu, nmodes); all files together stay below 64 MB
+
+
+def dump_outputs(path, eng, fg, bg):
+    """What the last timed step computed, as float32 .npy files under `path`: the masks (and backgrounds) a caller of
+    bgs_process_batch_device receives - stream 0 whole, and DUMP_SAMPLE entries of the whole batch at positions drawn from a fixed
+    seed - and the model state it left (bgs_get_state, stream 0, STATE_SAMPLE pixels from a fixed seed).  On S_sat the aged model
+    calls every pixel background, so the masks alone cannot tell two builds apart; the state can."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("mask", fg), ("background", bg)):
+        if t is None:
+            continue
+        np.save(os.path.join(path, name + "_stream0.npy"), t[0].cpu().numpy().astype(np.float32))
+        idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE))
+        sample = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + "_sample.npy"), sample.cpu().numpy().astype(np.float32))
+    n = ROWS * COLS
+    px = np.sort(np.random.default_rng(1).choice(n, STATE_SAMPLE, replace=False))
+    for plane, shape, dt in (("w", (5, n), np.float32), ("var", (5, n), np.float32), ("mu", (5, 3, n), np.float32), ("nmodes", (n,), np.uint8)):
+        a = eng.get_state(plane, shape, dt, stream=0)
+        np.save(os.path.join(path, "model_%s_stream0_sample.npy" % plane), a[..., px].astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -391,12 +421,15 @@ def main():
     ap.add_argument("--input", choices=["sat", "surv", "dense"], default="sat")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--with-bg", action="store_true", help="also produce the background image every frame (+3 B/px)")
-    ap.add_argument("--main-only", action="store_true", help="only the timed leg (used under rocprofv3 so the last K launches are the timed ones)")
+    ap.add_argument("--full", action="store_true", help="every leg beside the headline (host path, calibration, sustained launches, clips, placement witness, single stream, "
+                    "scenes, BASELINE configs, CPU baseline, live PMC traffic); without it the run only sets up, warms up and times the K steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed into DIR/<name>.npy (float32)")
+    ap.add_argument("--main-only", action="store_true", help="with --full: only the timed leg, the calibration and the sustained launches (used under rocprofv3 so the last K launches are the timed ones)")
     ap.add_argument("--pmc-child", default="", metavar="MARKS.json", help="what the counter passes run: the timed leg, a few clip launches of 4 and 8 frames, short S_surv and S_dense legs; "
                     "writes which update-kernel dispatches belong to which leg into MARKS.json")
     ap.add_argument("--no-configs", action="store_true", help="skip the BASELINE configs[2] / configs[3] block")
     ap.add_argument("--settle", type=int, default=340, help="untimed launches after model saturation and before the W warm-up steps: they age the model until the weights have equalised and every frame re-orders the modes (steady-state traffic)")
-    ap.add_argument("--sustain", type=int, default=200, help="further launches after the timed K, reported as roofline.sustained")
+    ap.add_argument("--sustain", type=int, default=None, help="further launches after the timed K, reported as roofline.sustained (default: 200 with --full, else 0)")
     ap.add_argument("--series", default="", help="write the per-launch kernel durations (settle, warmup, timed, sustain) to this CSV")
     ap.add_argument("--rehearse", action="store_true", help="N > 1 control flow on one GPU: all ranks on cuda:0, gloo, masks via host (not a benchmark)")
     ap.add_argument("--rccl-selftest", action="store_true", help="one rank, but through the N > 1 code path: RCCL process group, packed-mask gather every step (to itself), barrier and max-reduce of the time - the collective calls on real hardware where only one GPU is available (not a scaling result)")
@@ -406,10 +439,17 @@ def main():
     ap.add_argument("--pool-frames", type=int, default=240, help="cap on the DISTINCT frames kept resident for the warm-up + timed steps (32 streams: 199 MB per frame); beyond it the pool is cycled")
     ap.add_argument("--px", type=int, default=0, help="MOG2 pixels per lane (tuning; 0 = default = 1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.native_node:
+        ap.error("--dump-outputs reads the byte masks of bgs_process_batch_device; --native-node produces packed words only")
 
     pmc_child = bool(args.pmc_child)
     if pmc_child:
         args.main_only = True
+    legs = args.full and not args.main_only  # the legs beside the timed one (--full)
+    if args.sustain is None:
+        args.sustain = 200 if args.full else 0
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -447,11 +487,11 @@ def main():
     # is unaffected; a property of the runtime's DMA path, not of the engine.  The same camera legs run AGAIN at the end of this process
     # (`host_path.after_large_allocations`) so that the line shows both.
     host = None
-    if rank == 0 and world == 1 and not args.main_only and not selftest:
+    if rank == 0 and world == 1 and legs and not selftest:
         hclip = make_source("sat", 1, dev, 1234).pool(25)[:, 0].cpu().numpy()
         host = host_leg(local, hclip)
         del hclip
-    calibration = calibrate(local, S) if (rank == 0 and not pmc_child) else None  # before the model exists
+    calibration = calibrate(local, S) if (rank == 0 and args.full and not pmc_child) else None  # before the model exists
 
     nd = None
     if native:
@@ -547,8 +587,10 @@ def main():
         gather_wait_ms = nd.step_stats()[0] / max(1, args.steps)      # host ms per step inside bgs_node_step_device (it never blocks on the device)
     else:
         gather_wait_ms = 0.0
+    if rank == 0 and args.dump_outputs:  # before the sustained launches overwrite fg / bg
+        dump_outputs(args.dump_outputs, eng, fg, bg)
     # sustained leg (untimed by the contract's clock, reported beside it): SUSTAIN further launches of the same step
-    clocks = ClockSampler(local) if rank == 0 else None
+    clocks = ClockSampler(local) if (rank == 0 and args.full) else None
     if clocks:
         clocks.start()
     for _ in range(SUSTAIN):
@@ -622,15 +664,15 @@ def main():
                  "note": "the model is one virtual range backed by separately created physical chunks (hipMemCreate / hipMemMap; DESIGN.md 6.2; chunk_MiB 0 = one plain hipMalloc). "
                          "`dense_launch` = the placement witness: the same model streamed whole (BGS_OPT_MOG2_SPARSE = 0: every weight, summary, record and meta word read and "
                          "written back, 228 B/pixel) - its rate against calibration.copy_GBps_chunked says whether this model's placement is as good as a fresh chunked range's"}
-        clip0 = pool[:25, 0].cpu().numpy()  # stream 0's frames for the host-path and CPU legs
+        clip0 = pool[:25, 0].cpu().numpy() if legs else None  # stream 0's frames for the host-path and CPU legs
     if rank == 0 and pmc_child:
         for T in (4, 8):
             clip_leg(eng, pool, period, S, T, launches=CLIP_PMC_LAUNCHES, warm=4)
-    if rank == 0 and not args.main_only and not rehearse and nd is None:
+    if rank == 0 and legs and not rehearse and nd is None:
         clip = {"note": "supplementary, never `value`: bgs_process_clip_device on the same engine and saturated model - T consecutive frames per launch, model kept in "
                         "registers across them, bit-identical results; for file-fed video or deployments that accept T-1 frame times of latency",
                 "T4": clip_leg(eng, pool, period, S, 4), "T8": clip_leg(eng, pool, period, S, 8)}
-    if rank == 0 and not args.main_only and not rehearse and nd is None and args.input == "sat":
+    if rank == 0 and legs and not rehearse and nd is None and args.input == "sat":
         # placement witness: the whole model streamed (results unchanged: dense only writes back what it read)
         eng.set_option(capi.OPT_MOG2_SPARSE, 0)
         for i in range(3):
@@ -646,7 +688,7 @@ def main():
         dense_bytes = (2 * MODEL_BYTES_PER_PIXEL + 4) * S * ROWS * COLS
         probe["dense_launch"] = {"kernel_ms": round(dms, 4), "bytes_per_pixel": 2 * MODEL_BYTES_PER_PIXEL + 4, "GBps": round(dense_bytes / (dms * 1e-3) / 1e9, 1) if dms > 0 else None,
                                  "frac_of_box_copy": round(dense_bytes / (dms * 1e-3) / 1e9 / calibration["copy_GBps_chunked"], 4) if (dms > 0 and calibration and calibration.get("copy_GBps_chunked")) else None}
-    if rank == 0 and not args.main_only:
+    if rank == 0 and legs:
         # BASELINE configs[1] literally: ONE 1080p stream.  Its 253 MB model fits the 256 MiB Infinity Cache, so this
         # number is not an HBM measurement; it is reported beside the batched one, never as `value`.
         e1 = Engine(capi.MOG2, device=local, n_streams=1)
@@ -667,7 +709,7 @@ def main():
                   "kernel_GBps_moved": round(BYTES_PER_PIXEL * ROWS * COLS / (ms1 * 1e-3) / 1e9, 1),
                   "note": "single stream: 253 MB of model state fits the 256 MiB Infinity Cache (not an HBM figure)"}
         e1.close()
-    if rank == 0 and (not args.main_only or pmc_child) and args.input == "sat":
+    if rank == 0 and (legs or pmc_child) and args.input == "sat":
         n_leg = PMC_LEG_LAUNCHES if pmc_child else 100
         del pool  # the scene legs bring their own frames
         pool = None
@@ -684,7 +726,7 @@ def main():
     if pmc_child and rank == 0:
         with open(args.pmc_child, "w") as f:
             json.dump(marks, f)
-    if rank == 0 and not args.main_only:
+    if rank == 0 and legs:
         if world == 1 and not selftest and host is not None:
             late = host_leg(local, clip0, cameras_only=True)
             late.pop("pcie_calibration", None)
@@ -711,7 +753,7 @@ def main():
         achieved = algo_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
         traffic, traffic_source, traffic_detail = None, "none", None
         pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if world == 1 and not args.main_only and not args.no_pmc and not args.with_bg and not selftest:
+        if world == 1 and legs and not args.no_pmc and not args.with_bg and not selftest:
             pmc_all, why = pmc_traffic_live(S, args.steps, args.warmup, args.input, SETTLE)
             if pmc_all and "update" in pmc_all:
                 traffic_detail = pmc_all["update"]

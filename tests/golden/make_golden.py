@@ -10,12 +10,18 @@ Outputs :
                         (oracle/_ref/ref_sdlama_cli), default parameters and (ampFactor 3, minVar 2, maxVar 200) -> pinned
   lbsp_ref.npz          LBSP descriptors of frames[0] produced by THE REFERENCE'S OWN pattern files
                         (oracle/_ref/libref_lbsp.so, built from package_bgs/pl/LBSP_16bits_dbcross_*.i) -> pinned
+  lbsp_ref_random.npz   LBSP descriptors of seeded random images from THE REFERENCE'S OWN pattern files, for the cases of
+                        tests/test_oracle_cpu.py::test_lbsp_oracle_matches_live_reference_build -> pinned
+  sigmadelta_ref_adversarial.npz  SigmaDeltaBGS masks of the seeded adversarial clips of
+                        tests/test_oracle_cpu.py::test_sigmadelta_oracle_matches_live_reference_build from THE REFERENCE'S OWN
+                        sdLaMa091.cpp, with a CRC-32 of every clip so that the test can tell whether it regenerated the same input -> pinned
   framediff_indep.npz   FrameDifference masks computed by an independent numpy formula (integer only)
   oracle_regress.npz    masks / backgrounds / MOG2 state from the CPU oracle for every algorithm.  These pin the
                         oracle against accidental change; they are NOT reference outputs (OpenCV absent -> unpinned).
 """
 import os
 import sys
+import zlib
 
 import numpy as np
 from PIL import Image
@@ -27,6 +33,39 @@ from oracle import pyoracle as po  # noqa: E402
 from tracking_amd import capi  # noqa: E402
 
 REF = "/root/reference/frames"
+
+
+# the seeded inputs of the two live-reference tests in tests/test_oracle_cpu.py (kept identical to the generation there)
+LBSP_CASES = [(ch, rel, off) for ch in (1, 3) for rel, off in ((0.333, 0), (0.05, 9), (1.0, 0))]
+SD_CASES = [(1, 15, 255), (2, 2, 255), (4, 10, 100), (1, 0, 255), (7, 3, 40), (2, 20, 300)]
+
+
+def lbsp_images():
+    rng = np.random.default_rng(1)
+    return {ch: rng.integers(0, 256, (40, 56) + ((3,) if ch == 3 else ()), dtype=np.uint8) for ch in (1, 3)}
+
+
+def sd_clip(amp, vmin):
+    rng = np.random.default_rng(amp * 100 + vmin)
+    frames = rng.integers(0, 256, (30, 40, 52, 3), dtype=np.uint8)
+    frames[10:20] = (frames[10:20].astype(np.int32) // 8 + 200).astype(np.uint8)  # a long bright stretch
+    return frames
+
+
+def live_reference_cases():
+    """lbsp_ref_random.npz and sigmadelta_ref_adversarial.npz: the live-reference tests' expected outputs, from oracle/_ref."""
+    assert po.ref_lbsp_available() and po.ref_sdlama_available(), "oracle/_ref not built (needs the reference sources)"
+    imgs, lb = lbsp_images(), {}
+    for ch, rel, off in LBSP_CASES:
+        lb["img%d" % ch] = imgs[ch]
+        lb["desc_%d_%g_%d" % (ch, rel, off)] = po.ref_lbsp_describe(imgs[ch], po.lbsp_lut(rel, off, ch))
+    np.savez_compressed(os.path.join(HERE, "lbsp_ref_random.npz"), **lb)
+    sd = {}
+    for amp, vmin, vmax in SD_CASES:
+        frames = sd_clip(amp, vmin)
+        sd["masks_%d_%d_%d" % (amp, vmin, vmax)] = po.ref_sigmadelta_clip(frames, amp, vmin, vmax)
+        sd["crc_%d_%d_%d" % (amp, vmin, vmax)] = np.uint32(zlib.crc32(frames.tobytes()))
+    np.savez_compressed(os.path.join(HERE, "sigmadelta_ref_adversarial.npz"), **sd)
 
 
 def load(i):
@@ -52,6 +91,7 @@ def main():
     for tag, (amp, vmin, vmax) in {"default": (1, 15, 255), "amp3": (3, 2, 200)}.items():
         sd[tag] = po.ref_sigmadelta_clip(frames, amp, vmin, vmax)
     np.savez_compressed(os.path.join(HERE, "sigmadelta_ref.npz"), **sd)
+    live_reference_cases()
 
     # --- independent integer formula for FrameDifference (FrameDifferenceBGS.cpp:45-51 with P1/P2 of DESIGN.md §5)
     masks = []
@@ -88,4 +128,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    live_reference_cases() if sys.argv[1:] == ["--live-reference-cases"] else main()

@@ -5,17 +5,19 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*extra):
+def _bench(*extra, sustain=4):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--streams", "2", "--settle", "4", "--sustain", "4", *extra],
+    sus = ["--sustain", str(sustain)] if sustain is not None else []
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--streams", "2", "--settle", "4", *sus, *extra],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -24,7 +26,7 @@ def _bench(*extra):
 
 
 def test_bench_line_contract():
-    d = _bench("--no-pmc")
+    d = _bench("--full", "--no-pmc")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2 and d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None
@@ -51,6 +53,33 @@ def test_bench_line_contract():
     assert hp["submit_wait_8_cameras_registered_buffers"]["diag"]["pinned_input"] == 8 and hp["submit_wait_8_cameras_registered_buffers"]["diag"]["register_calls_inside_timed_rounds"] == 0
     assert hp["submit_wait_8_cameras_registered_arena"]["diag"]["arenas"] == 2 and hp["submit_wait_8_cameras_registered_arena"]["diag"]["register_calls"] == 2
     assert hp["submit_wait_8_cameras_registered_arena"]["diag"]["cpu_ms_staging_per_frame"] == 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs_every_run(tmp_path):
+    """Without --full the run only times the K steps; --dump-outputs writes the last timed step's masks and backgrounds, identical
+    from run to run with the same arguments."""
+    runs = []
+    for name in ("a", "b"):
+        out = tmp_path / name
+        d = _bench("--with-bg", "--dump-outputs", str(out), sustain=None)
+        assert d["steps"] == 4 and d["roofline"]["kernel_launches"] == 4 and d["value"] > 0
+        assert abs(d["value"] - 2 * 1920 * 1080 / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 0.01
+        for k in ("cpu_baseline", "host_path", "single_stream", "s_surv", "s_dense", "clip", "configs"):
+            assert d[k] is None, k
+        assert d["calibration"] == {"clocks": None} and d["roofline"]["sustained"] is None and "dense_launch" not in d["model_placement"]
+        files = {f.name: np.load(f) for f in out.iterdir()}
+        assert sorted(files) == ["background_sample.npy", "background_stream0.npy", "mask_sample.npy", "mask_stream0.npy",
+                                 "model_mu_stream0_sample.npy", "model_nmodes_stream0_sample.npy", "model_var_stream0_sample.npy", "model_w_stream0_sample.npy"]
+        assert all(a.dtype == np.float32 for a in files.values()) and sum(f.stat().st_size for f in out.iterdir()) <= 64e6
+        assert files["mask_stream0.npy"].shape == (1080, 1920) and files["background_stream0.npy"].shape == (1080, 1920, 3)
+        idx = np.sort(np.random.default_rng(0).integers(0, 2 * 1080 * 1920, files["mask_sample.npy"].size))  # the documented sample
+        s0 = idx < 1080 * 1920
+        assert s0.any() and np.array_equal(files["mask_sample.npy"][s0], files["mask_stream0.npy"].reshape(-1)[idx[s0]])
+        w, nm = files["model_w_stream0_sample.npy"], files["model_nmodes_stream0_sample.npy"]
+        assert w.shape == (5, 1 << 17) and files["model_mu_stream0_sample.npy"].shape == (5, 3, 1 << 17) and nm.min() >= 1 and nm.max() <= 5
+        runs.append(files)
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), k
 
 
 def test_bench_rccl_selftest_gathers_what_the_kernel_wrote():

@@ -6,6 +6,7 @@ What pins what:
   * everything else    — regression vectors of the oracle (OpenCV is absent: parity unpinned), plus properties
 """
 import os
+import zlib
 
 import numpy as np
 import pytest
@@ -27,14 +28,20 @@ def test_lbsp_oracle_matches_reference_built_fixture(golden_frames, golden_gray)
     assert np.array_equal(pyoracle.lbsp_describe(golden_gray[0], g["lut1"])[:, :, 0], g["desc1"])
 
 
-@pytest.mark.skipif(not pyoracle.ref_lbsp_available(), reason="oracle/_ref is built only where /root/reference exists")
 def test_lbsp_oracle_matches_live_reference_build():
+    """Seeded random images against the reference's own pattern files: the descriptors that build produced are stored in
+    tests/golden/lbsp_ref_random.npz (make_golden.py); where oracle/_ref exists the live build is asked as well."""
+    g = np.load(os.path.join(GOLDEN, "lbsp_ref_random.npz"))
     rng = np.random.default_rng(1)
     for ch in (1, 3):
         img = rng.integers(0, 256, (40, 56) + ((3,) if ch == 3 else ()), dtype=np.uint8)
+        assert np.array_equal(img, g["img%d" % ch]), "the seeded input differs from the one the fixture was made from"
         for rel, off in ((0.333, 0), (0.05, 9), (1.0, 0)):
             lut = pyoracle.lbsp_lut(rel, off, ch)
-            assert np.array_equal(pyoracle.lbsp_describe(img, lut), pyoracle.ref_lbsp_describe(img, lut))
+            got = pyoracle.lbsp_describe(img, lut)
+            assert np.array_equal(got, g["desc_%d_%g_%d" % (ch, rel, off)]), (ch, rel, off)
+            if pyoracle.ref_lbsp_available():
+                assert np.array_equal(got, pyoracle.ref_lbsp_describe(img, lut)), (ch, rel, off)
 
 
 def test_sigmadelta_oracle_matches_reference_built_fixture(golden_frames):
@@ -50,15 +57,21 @@ def test_sigmadelta_oracle_matches_reference_built_fixture(golden_frames):
             assert bg is None and np.array_equal(fg, g[tag][t - 1]), (tag, t)
 
 
-@pytest.mark.skipif(not pyoracle.ref_sdlama_available(), reason="oracle/_ref is built only where /root/reference exists")
 @pytest.mark.parametrize("amp,vmin,vmax", [(1, 15, 255), (2, 2, 255), (4, 10, 100), (1, 0, 255), (7, 3, 40), (2, 20, 300)])
 def test_sigmadelta_oracle_matches_live_reference_build(amp, vmin, vmax):
     """Restatement vs the reference's own C file on adversarial clips: big jumps (int8 wrap of Mt - I), amplified
-    differences above 255 (uint8 wrap of ++Vt), maxVar > 255 (truncated to uint8 by sdLaMa091's min/max)."""
+    differences above 255 (uint8 wrap of ++Vt), maxVar > 255 (truncated to uint8 by sdLaMa091's min/max).  The masks that
+    file produced are stored in tests/golden/sigmadelta_ref_adversarial.npz (make_golden.py); where oracle/_ref exists the
+    live build is asked as well."""
     rng = np.random.default_rng(amp * 100 + vmin)
     frames = rng.integers(0, 256, (30, 40, 52, 3), dtype=np.uint8)
     frames[10:20] = (frames[10:20].astype(np.int32) // 8 + 200).astype(np.uint8)  # a long bright stretch
-    want_all = pyoracle.ref_sigmadelta_clip(frames, amp, vmin, vmax)
+    g = np.load(os.path.join(GOLDEN, "sigmadelta_ref_adversarial.npz"))
+    case = "%d_%d_%d" % (amp, vmin, vmax)
+    assert zlib.crc32(frames.tobytes()) == int(g["crc_" + case]), "the seeded clip differs from the one the fixture was made from"
+    want_all = g["masks_" + case]
+    if pyoracle.ref_sdlama_available():
+        assert np.array_equal(want_all, pyoracle.ref_sigmadelta_clip(frames, amp, vmin, vmax))
     p = capi.default_params(capi.SIGMA_DELTA)
     p.sd_amp_factor, p.sd_min_var, p.sd_max_var = amp, vmin, vmax
     o = pyoracle.Oracle(capi.SIGMA_DELTA, params=p)

@@ -9,7 +9,7 @@ if [ -n "$PMC_SET" ]; then SETS=("$PMC_SET"); else SETS=("SQ_INSTS_VALU SQ_INSTS
 : > $OUT/summary.txt
 for ctrs in "${SETS[@]}"; do
   tag=$(echo $ctrs | tr ' ' '_' | cut -c1-40)
-  timeout -k 5 240 rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $OUT/raw_$tag -o pmc -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --main-only --no-pmc --no-cpu-baseline > $OUT/run_$tag.log 2>&1
+  timeout -k 5 240 rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $OUT/raw_$tag -o pmc -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --main-only --no-pmc --no-cpu-baseline > $OUT/run_$tag.log 2>&1
   python3 - "$OUT/raw_$tag" "$ctrs" <<'PY' | tee -a $OUT/summary.txt
 import csv, glob, sys, collections
 out, ctrs = sys.argv[1], sys.argv[2].split()

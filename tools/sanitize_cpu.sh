@@ -3,7 +3,7 @@
 # the host-side C++ mirror (bgs_demo) up to the point where it needs a GPU.  usage: bash tools/sanitize_cpu.sh
 set -e
 cd "$(dirname "$0")/.."
-OUT=/tmp/bgs_sanitize; mkdir -p $OUT
+OUT=$(mktemp -d -t bgs_sanitize.XXXXXX); trap 'rm -rf "$OUT"' EXIT
 gcc -O1 -g -std=c11 -fPIC -ffp-contract=off -fno-fast-math -fopenmp -fsanitize=address,undefined -fno-omit-frame-pointer -shared -Iinclude \
     -o $OUT/libbgs_oracle_asan.so oracle/bgs_oracle.c oracle/subsense_oracle.c oracle/dp_oracle.c oracle/ingest_oracle.c -lm
 ASAN=$(gcc -print-file-name=libasan.so)
