@@ -51,6 +51,7 @@ typedef enum bgs_algo {
   BGS_DP_MEAN = 15,          /* DPMeanBGS::process                 package_bgs/dp/DPMeanBGS.cpp:29-82 */
   BGS_DP_ADAPTIVE_MEDIAN = 16, /* DPAdaptiveMedianBGS::process     package_bgs/dp/DPAdaptiveMedianBGS.cpp:29-81 */
   BGS_LOBSTER = 17,          /* LOBSTERBGS::process                package_bgs/pl/LOBSTER.cpp:20-45 */
+  BGS_KDE = 18,              /* KDE::process (USTC_BGS type 32)    package_bgs/ae/KDE.cpp:34-96 */
   BGS_ALGO_COUNT
 } bgs_algo;
 
@@ -150,6 +151,21 @@ typedef struct bgs_params {
   float dp_threshold;   /* Zivkovic 25, Grimson 9, WrenGA 12.25, Mean 2700, AdaptiveMedian 40 */
   float dp_alpha;       /* Zivkovic 0.001, Grimson 0.01, WrenGA 0.005, Mean 1e-6 */
   int32_t dp_gaussians; /* 3 */
+
+  /* KDE (package_bgs/ae/KDE.cpp:19-20, :114-126).  bgs_default_params fills these for BGS_KDE only (zero for every other
+   * algorithm).  Like the wrapper, which hands them to its model once, on the first frame, every kde_* field except
+   * kde_frames_to_learn and kde_update_model is fixed once the geometry is set: later bgs_set_params values are ignored.
+   * kde_frames_to_learn is re-read every frame (loadConfig), kde_update_model too.
+   * Limits: sequence_length 3..255, frames_to_learn >= 1, time_window >= 1 with time_window / sequence_length <= 255
+   * (BGS_ERR_INVALID otherwise); colour ratios need 3-channel frames (BGS_ERR_UNSUPPORTED for gray with ratios on). */
+  int32_t kde_frames_to_learn;  /* 10  framesToLearn: learning frames before the first mask */
+  int32_t kde_sequence_length;  /* 50  SequenceLength: samples per pixel */
+  int32_t kde_time_window;      /* 100 TimeWindowSize: samples are drawn from this many frames */
+  int32_t kde_sd_estimation;    /* 1   SDEstimationFlag: per-pixel kernel bandwidth (0: every bin 1) */
+  int32_t kde_color_ratios;     /* 1   lUseColorRatiosFlag: compare in (brightness, g/s, r/s) */
+  int32_t kde_update_model;     /* 1   NPBGSubtractor::UpdateBGFlag (never initialised by the reference) */
+  double kde_threshold;         /* 10e-8 th: probability threshold */
+  double kde_alpha;             /* 0.3   alpha: brightness band of the colour-ratio gate */
 } bgs_params;
 
 int bgs_abi_version(void);

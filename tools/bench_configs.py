@@ -3,6 +3,7 @@
 Not the driver's bench line (bench.py is); the numbers go to DESIGN.md §6.
   configs[2]: WeightedMovingVarianceBGS + AdaptiveBackgroundLearning, 3840x2160 (HBM-bound stress)
   configs[3]: LBSP descriptor path, 1920x1080
+  --only kde: KDE (package_bgs/ae) young / aged model, static and ~10 % foreground scenes, 8 x 1080p
 usage: bench_configs.py [--streams S] [--swizzle 0|1]"""
 import argparse
 import os
@@ -516,12 +517,85 @@ def configs_block(device=0, S=8, steps=40, cpu=True):
     return out
 
 
+def kde_scene(T, S, rows, cols, fg_frac, device):
+    """T frames of S streams: a static textured scene with fresh +-3 sensor noise in every frame and, when fg_frac > 0, a moving
+    saturated box covering fg_frac of the frame (foreground: run_kde learns from box-free frames)."""
+    g = torch.Generator(device=device)
+    g.manual_seed(77)
+    base = torch.randint(30, 200, (S, rows, cols, 3), generator=g, device=device, dtype=torch.int16)
+    out = torch.empty((T, S, rows, cols, 3), dtype=torch.uint8, device=device)
+    bh, bw = int(rows * fg_frac ** 0.5), int(cols * fg_frac ** 0.5)
+    for t in range(T):
+        f = base + torch.randint(-3, 4, base.shape, generator=g, device=device, dtype=torch.int16)
+        if fg_frac > 0:
+            y, x = (t * 37) % (rows - bh), (t * 53) % (cols - bw)
+            f[:, y:y + bh, x:x + bw] = torch.tensor([230, 40, 90], device=device, dtype=torch.int16)
+        out[t] = f.clamp(0, 255).to(torch.uint8)
+    return out
+
+
+def run_kde(S=8, rows=1080, cols=1920, steps=30, scenes=((("static + noise", 0.0), ("~10 % foreground", 0.1))), count_trips=True):
+    """KDE (BGS_KDE) with the reference defaults (50 samples, 10 learning frames, colour ratios): ms per step of S x 1080p for a young
+    model (frames 11-40) and one aged ~100 frames, on a static noisy scene and on one with ~10 % foreground; mean density-loop trips
+    per pixel from a second, untimed engine with the trip counter on (BGS_KDE_TRIPS=1: one atomic per wave)."""
+    dev = torch.device("cuda", 0)
+    T = 16
+    learn = kde_scene(11, S, rows, cols, 0.0, dev)  # the 10 learning frames + the estimation frame see the empty scene
+    for label, frac in scenes:
+        pool = kde_scene(T, S, rows, cols, frac, dev)
+        fg = torch.empty((S, rows, cols), dtype=torch.uint8, device=dev)
+        bits = torch.empty((S, rows * cols // 64), dtype=torch.int64, device=dev)
+        res = {}
+        for counted in ((False, True) if count_trips else (False,)):
+            os.environ["BGS_KDE_TRIPS"] = "1" if counted else "0"
+            e = Engine(capi.KDE, n_streams=S)
+            os.environ.pop("BGS_KDE_TRIPS")
+            e.set_geometry(rows, cols, 3)
+            t = 0
+            for age, upto in (("young", 11), ("aged", 100)):
+                while t < upto:
+                    e.process_batch_device(learn[t] if t < 11 else pool[t % T], fg, None, bits)
+                    t += 1
+                torch.cuda.synchronize()
+                if counted:
+                    t0 = e.get_state("trips", (2,), np.uint64)
+                else:
+                    e.enable_kernel_timing(True)
+                w0 = time.perf_counter()
+                for _ in range(steps):
+                    e.process_batch_device(pool[t % T], fg, None, bits)
+                    t += 1
+                torch.cuda.synchronize()
+                wall = (time.perf_counter() - w0) / steps * 1e3
+                if counted:
+                    t1 = e.get_state("trips", (2,), np.uint64)
+                    res[age]["mean_trips"] = float(t1[0] - t0[0]) / float(t1[1] - t0[1])
+                else:
+                    ms, _, kname = e.kernel_timing()
+                    e.enable_kernel_timing(False)
+                    res[age] = {"wall_ms": wall, "kernel_ms": ms, "fg": float((fg != 0).float().mean())}
+            e.close()
+        for age, r in res.items():
+            print("KDE %-17s %-5s %dx%d x%d streams: %.3f ms/step wall, kde_frame_kernel %.3f ms -> %8.1f Mpix/s; mean trips %s of 50; fg ratio %.3f"
+                  % (label, age, cols, rows, S, r["wall_ms"], r["kernel_ms"], S * rows * cols / r["kernel_ms"] / 1e3,
+                     "%.2f" % r["mean_trips"] if "mean_trips" in r else "-", r["fg"]))
+        del pool
+    del learn
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=8)
     ap.add_argument("--only", default="", help="subsense: just the SuBSENSE lines")
     args = ap.parse_args()
     S = args.streams
+    if args.only == "kde":
+        run_kde(S)
+        return
+    if args.only in ("kde_static", "kde_fg"):  # one scene, short legs, no trip counter: for counter passes
+        run_kde(S, steps=5, scenes=((("static + noise", 0.0),) if args.only == "kde_static" else (("~10 % foreground", 0.1),)), count_trips=False)
+        return
     if args.only == "subsense":
         run_subsense(2)
         run_subsense(2, kind="smooth")

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("BGS_LIB_PATH") or os.path.join(_HERE, "lib", "libbgs_
 FRAME_DIFF, STATIC_FRAME_DIFF, WMM, WMV, ABL, ASBL, MOG2, MOG1, GMG, SUBSENSE, LBSP_DESC, SIGMA_DELTA = range(12)
 DP_ZIVKOVIC_AGMM, DP_GRIMSON_GMM, DP_WREN_GA, DP_MEAN, DP_ADAPTIVE_MEDIAN = range(12, 17)
 LOBSTER = 17
+KDE = 18
 FG_VALID, BG_VALID = 1, 2
 OPT_BORROW_FRAMES, OPT_MOG2_PIXELS_PER_LANE, OPT_MOG2_TILED, OPT_XCD_SWIZZLE, OPT_PLACEMENT_PROBE, OPT_MOG2_SPARSE, OPT_CLIP_FUSE, OPT_HOST_REGISTER, OPT_MODEL_CHUNK_MB, OPT_MODEL_CHUNK_MIN_MB = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 
@@ -71,6 +72,14 @@ class BgsParams(C.Structure):
         ("dp_threshold", C.c_float),
         ("dp_alpha", C.c_float),
         ("dp_gaussians", C.c_int32),
+        ("kde_frames_to_learn", C.c_int32),
+        ("kde_sequence_length", C.c_int32),
+        ("kde_time_window", C.c_int32),
+        ("kde_sd_estimation", C.c_int32),
+        ("kde_color_ratios", C.c_int32),
+        ("kde_update_model", C.c_int32),
+        ("kde_threshold", C.c_double),
+        ("kde_alpha", C.c_double),
     ]
 
 

@@ -24,6 +24,7 @@
 
 #include "kernel_gmg.h"
 #include "kernel_ingest.h"
+#include "kernel_kde.h"
 #include "kernel_cc.h"
 #include "kernel_dp.h"
 #include "kernel_mog1.h"
@@ -128,6 +129,17 @@ struct bgs_engine {
   SsDevice* ss = nullptr;       // SuBSENSE model (engine_subsense.h)
   int2* gmg_rec = nullptr;        // GMG histograms (kernel_gmg.h): {colour, weight} records [F][P]
   uint8_t* gmg_nfeat = nullptr;
+  // KDE model (kernel_kde.h / engine_kde.h): stream-major planes of 4-byte records, the kernel table and the colour-ratio gate
+  uint32_t *kde_samples = nullptr, *kde_tb = nullptr, *kde_meta = nullptr, *kde_acc = nullptr;
+  double* kde_lut = nullptr;
+  int2* kde_gate = nullptr;
+  unsigned long long* kde_trips = nullptr;  // diagnostics: density-loop trips (BGS_KDE_TRIPS=1)
+  uint64_t kde_lanes = 0;                   // lanes the counted launches covered
+  bool kde_count_trips = false;
+  struct KdeStream {                        // the reference object's counters, one set per stream (engine_kde.h)
+    int64_t fn = 0, top = 0, tidx = 0, tbc = 0, tbtop = 0;
+  };
+  std::vector<KdeStream> kde;
   // MOG2 model (kernel_mog2.h: tiles of ranked weights + fixed-slot records + rank->slot meta words)
   uint8_t* mog2_state = nullptr;
   int xcd_swizzle = 1;             // XCD-aware block order (kernel_mog2.h): 0 off, 1 model kernels (MOG2, MOG1, dp), 2 also the byte-stream kernels
@@ -200,6 +212,8 @@ struct bgs_engine {
 namespace {
 
 void ss_free(bgs_engine* e);  // engine_subsense.h
+void kde_free(bgs_engine* e);  // engine_kde.h
+int kde_check(const bgs_params& p);
 void vmm_free(VmmRange& v);  // below
 
 void lane_release(bgs_engine::Lane& ln) {  // whatever of a lane came to be (bgs_submit's set-up may have failed half-way)
@@ -242,6 +256,7 @@ void free_all(bgs_engine* e) {
   for (auto& ev : e->events) (void)hipEventDestroy(ev.first), (void)hipEventDestroy(ev.second);
   e->events.clear();
   ss_free(e);
+  kde_free(e);
   if (e->d_stat) (void)hipFree(e->d_stat), e->d_stat = nullptr;
   if (e->h_stat) (void)hipHostFree(e->h_stat), e->h_stat = nullptr;
   for (int i = 0; i < bgs_engine::kStatSlots; ++i) {
@@ -268,6 +283,7 @@ int check_params(bgs_algo algo, const bgs_params& p) {
   if ((algo == BGS_DP_ZIVKOVIC_AGMM || algo == BGS_DP_GRIMSON_GMM) && (p.dp_gaussians < 1 || p.dp_gaussians > 5))
     return fail(BGS_ERR_UNSUPPORTED, "dp GMM kernels are built for 1..5 gaussians, got %d", p.dp_gaussians);
   if (algo == BGS_DP_ADAPTIVE_MEDIAN && p.dp_sampling_rate == 0) return fail(BGS_ERR_UNSUPPORTED, "AdaptiveMedian samplingRate 0 (frame_num %% 0)");
+  if (algo == BGS_KDE) return kde_check(p);
   return BGS_OK;
 }
 
@@ -513,6 +529,7 @@ int mog2_allocate(bgs_engine* e) {
 
 #include "engine_subsense.h"
 #include "engine_dp.h"
+#include "engine_kde.h"
 
 // (Re)build ABL's lookup table for the current alpha on e->stream.  Called when the geometry is set and when bgs_set_params
 // changes alpha; both drain the device first / the stream after, so no launch on any stream sees a half-written table.
@@ -569,6 +586,7 @@ int allocate(bgs_engine* e, int rows, int cols, int ch) {
     case BGS_DP_WREN_GA:
     case BGS_DP_MEAN: break;
     case BGS_DP_ADAPTIVE_MEDIAN: e->state_ch = 3; break;  // bgstate = the median image
+    case BGS_KDE: break;
     default: return fail(BGS_ERR_UNSUPPORTED, "algorithm %d is not implemented in this build", (int)e->algo);
   }
   for (int i = 0; i < e->nring; ++i) DMALLOC(e->ring[i], fb);
@@ -613,6 +631,10 @@ int allocate(bgs_engine* e, int rows, int cols, int ch) {
   }
   if (e->algo == BGS_LOBSTER) {
     int rc = lob_allocate(e);
+    if (rc) return rc;
+  }
+  if (e->algo == BGS_KDE) {
+    int rc = kde_allocate(e);
     if (rc) return rc;
   }
   // Whatever allocation enqueued on e->stream (statistics counters, poison fills) is complete before the caller's first
@@ -739,6 +761,7 @@ uint64_t launch_key(const bgs_engine* e, int i) {
     case BGS_DP_ADAPTIVE_MEDIAN: return (uint64_t)(t == 0) | (uint64_t)((t % p.dp_sampling_rate) == 1) << 1;
     case BGS_MOG1: return lr_key(p.alpha, p.mog1_history, 1);
     case BGS_MOG2: return lr_key(p.alpha, p.mog2_history, 2);
+    case BGS_KDE: return kde_key(e, i);
     default: return (uint64_t)t | (uint64_t)(e->ss ? e->ss->pp[i] & 1 : 0) << 62;  // SuBSENSE / LOBSTER: the frame index itself goes into the kernels (counter-based random draws); + which half of the ping-pong maps is current
   }
 }
@@ -1077,6 +1100,11 @@ int process_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, ui
       flags = BGS_FG_VALID | BGS_BG_VALID;
       break;
     }
+    case BGS_KDE: {
+      int rc = kde_run(e, first, count, d_frames, d_fg, d_bits, s, &flags);
+      if (rc) return rc;
+      break;
+    }
     default: return fail(BGS_ERR_UNSUPPORTED, "algorithm %d is not implemented in this build", (int)e->algo);
   }
   HIP_TRY(hipGetLastError());
@@ -1354,6 +1382,11 @@ int bgs_default_params(bgs_algo algo, bgs_params* p) {
       p->lbsp_rel_threshold = 0.365f, p->subsense_desc_dist_threshold_offset = 4, p->subsense_min_color_dist_threshold = 30;
       p->subsense_n_samples = 35, p->subsense_n_required = 2;
       break;
+    case BGS_KDE:  // KDE.cpp:19-20, :114-126 (the kde_* fields stay zero for every other algorithm)
+      p->kde_frames_to_learn = 10, p->kde_sequence_length = 50, p->kde_time_window = 100;
+      p->kde_sd_estimation = 1, p->kde_color_ratios = 1, p->kde_update_model = 1;
+      p->kde_threshold = 10e-8, p->kde_alpha = 0.3;
+      break;
     default: break;
   }
   return BGS_OK;
@@ -1395,6 +1428,8 @@ int bgs_create(bgs_algo algo, const bgs_params* params, int hip_device, int n_st
   e->last_flags.assign(n_streams, 0);
   e->counter.assign(n_streams, 0);
   e->flip.assign(n_streams, 0);
+  e->kde.assign(n_streams, bgs_engine::KdeStream());
+  if (const char* env = getenv("BGS_KDE_TRIPS")) e->kde_count_trips = atoi(env) != 0;
   if (const char* env = getenv("BGS_MOG2_COMPLETE")) e->mog2_complete = atoi(env) != 0;
   if (const char* env = getenv("BGS_XCD_SWIZZLE")) e->xcd_swizzle = atoi(env);
   if (const char* env = getenv("BGS_MOG2_SPARSE")) e->mog2_sparse = atoi(env);
@@ -1430,6 +1465,10 @@ int bgs_set_params(bgs_engine* e, const bgs_params* params) {
       p.dp_sampling_rate = old.dp_sampling_rate, p.learning_frames = old.learning_frames;
     }
     if (e->algo == BGS_GMG) p.gmg_max_features = old.gmg_max_features;  // sizes the histogram planes
+    if (e->algo == BGS_KDE) {  // KDE.cpp:40-66: Intialize / SetThresholds once; framesToLearn is re-read every frame (and update_model is live)
+      p.kde_sequence_length = old.kde_sequence_length, p.kde_time_window = old.kde_time_window, p.kde_sd_estimation = old.kde_sd_estimation;
+      p.kde_color_ratios = old.kde_color_ratios, p.kde_threshold = old.kde_threshold, p.kde_alpha = old.kde_alpha;
+    }
     if (e->algo == BGS_ASBL && (!e->abl_lut_valid || p.alpha_learn != e->asbl_lut_alpha[0] || p.alpha_detection != e->asbl_lut_alpha[1])) {
       if (hipSetDevice(e->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(BGS_ERR_HIP, "device sync failed");
       rc = asbl_build_lut(e);
@@ -1828,6 +1867,7 @@ int64_t bgs_get_state(bgs_engine* e, int stream, const char* plane, void* dst, s
     }
   }
   if ((e->algo == BGS_SUBSENSE || e->algo == BGS_LOBSTER) && e->ss) return ss_get_state(e, stream, plane, dst, cap);
+  if (e->algo == BGS_KDE && e->kde_samples) return kde_get_state(e, stream, plane, dst, cap);
   if (is_dp(e->algo)) {  // planes are stored canonically: [stream][plane][n]
     const int planes = dp_planes_of(e);
     const char* fname = (e->algo == BGS_DP_WREN_GA) ? "gauss" : (e->algo == BGS_DP_MEAN) ? "mean" : "modes";
@@ -1913,6 +1953,7 @@ int bgs_reset_stream(bgs_engine* e, int stream) {
   if (!e) return fail(BGS_ERR_INVALID, "engine is NULL");
   if (stream < 0 || stream >= e->S) return fail(BGS_ERR_INVALID, "stream %d outside 0..%d", stream, e->S - 1);
   e->seen[stream] = 0, e->counter[stream] = 0, e->last_flags[stream] = 0;
+  if (!e->kde.empty()) e->kde[stream] = bgs_engine::KdeStream();
   if (e->last_fg_stream == stream) e->last_fg_stream = -1;
   return BGS_OK;
 }

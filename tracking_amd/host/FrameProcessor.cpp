@@ -18,6 +18,7 @@ FrameProcessor::FrameProcessor()
   zivkovicAGMM = nullptr, enableDPZivkovicAGMMBGS = false;
   temporalMean = nullptr, enableDPMeanBGS = false;
   wrenGA = nullptr, enableDPWrenGABGS = false;
+  kde = nullptr, enableKDE = false;
   sdbgs = nullptr, enableSigmaDeltaBGS = false;
   ssbgs = nullptr, enableSuBSENSEBGS = false;
   lobgs = nullptr, enableLOBSTERBGS = false;
@@ -44,6 +45,7 @@ void FrameProcessor::init() {  // FrameProcessor.cpp:35-155
   if (enableDPZivkovicAGMMBGS) zivkovicAGMM = new DPZivkovicAGMMBGS;
   if (enableDPMeanBGS) temporalMean = new DPMeanBGS;
   if (enableDPWrenGABGS) wrenGA = new DPWrenGABGS;
+  if (enableKDE) kde = new KDE;  // after VuMeter, before IMBS (:135)
   if (enableSigmaDeltaBGS) sdbgs = new SigmaDeltaBGS;
   if (enableSuBSENSEBGS) ssbgs = new SuBSENSEBGS;
   if (enableLOBSTERBGS) lobgs = new LOBSTERBGS;
@@ -109,6 +111,7 @@ void FrameProcessor::process(const Image& img_input) {  // :169-340
   if (enableDPZivkovicAGMMBGS) process("DPZivkovicAGMMBGS", zivkovicAGMM, img_prep, img_zivgmm);
   if (enableDPMeanBGS) process("DPMeanBGS", temporalMean, img_prep, img_tmpmean);
   if (enableDPWrenGABGS) process("DPWrenGABGS", wrenGA, img_prep, img_wrenga);
+  if (enableKDE) process("KDE", kde, img_prep, img_kde);  // :275
   if (enableSigmaDeltaBGS) process("SigmaDeltaBGS", sdbgs, img_prep, img_sdbgs);
   if (enableSuBSENSEBGS) process("SuBSENSEBGS", ssbgs, img_prep, img_ssbgs);
   if (enableLOBSTERBGS) process("LOBSTERBGS", lobgs, img_prep, img_lobgs);
@@ -122,6 +125,7 @@ void FrameProcessor::finish() {  // :342-482 (reverse order of init)
   delete lobgs, lobgs = nullptr;
   delete ssbgs, ssbgs = nullptr;
   delete sdbgs, sdbgs = nullptr;
+  delete kde, kde = nullptr;
   delete wrenGA, wrenGA = nullptr;
   delete temporalMean, temporalMean = nullptr;
   delete zivkovicAGMM, zivkovicAGMM = nullptr;
@@ -168,6 +172,7 @@ void FrameProcessor::saveConfig() {  // :496-552 (keys of the classes this build
   fs.writeInt("enableDPZivkovicAGMMBGS", enableDPZivkovicAGMMBGS);
   fs.writeInt("enableDPMeanBGS", enableDPMeanBGS);
   fs.writeInt("enableDPWrenGABGS", enableDPWrenGABGS);
+  fs.writeInt("enableKDE", enableKDE);  // :544
   fs.writeInt("enableSigmaDeltaBGS", enableSigmaDeltaBGS);
   fs.writeInt("enableSuBSENSEBGS", enableSuBSENSEBGS);
   fs.writeInt("enableLOBSTERBGS", enableLOBSTERBGS);
@@ -193,6 +198,7 @@ void FrameProcessor::loadConfig() {  // :554-610 (defaults: PreProcessor and Fra
   enableDPZivkovicAGMMBGS = fs.readInt("enableDPZivkovicAGMMBGS", false);
   enableDPMeanBGS = fs.readInt("enableDPMeanBGS", false);
   enableDPWrenGABGS = fs.readInt("enableDPWrenGABGS", false);
+  enableKDE = fs.readInt("enableKDE", false);  // :602
   enableSigmaDeltaBGS = fs.readInt("enableSigmaDeltaBGS", false);
   enableSuBSENSEBGS = fs.readInt("enableSuBSENSEBGS", false);
   enableLOBSTERBGS = fs.readInt("enableLOBSTERBGS", false);

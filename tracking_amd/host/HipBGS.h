@@ -3,9 +3,9 @@
 // One IBGS class per reference class on the hot path, all in namespace hipbgs so that nothing clashes with the CPU classes:
 //   hipbgs::FrameDifferenceBGS, StaticFrameDifferenceBGS, WeightedMovingMeanBGS, WeightedMovingVarianceBGS,
 //   AdaptiveBackgroundLearning, AdaptiveSelectiveBackgroundLearning, MixtureOfGaussianV1BGS, MixtureOfGaussianV2BGS, GMG,
-//   SigmaDeltaBGS, SuBSENSEBGS, LOBSTERBGS, DPZivkovicAGMMBGS, DPGrimsonGMMBGS, DPWrenGABGS, DPMeanBGS, DPAdaptiveMedianBGS
+//   SigmaDeltaBGS, SuBSENSEBGS, LOBSTERBGS, DPZivkovicAGMMBGS, DPGrimsonGMMBGS, DPWrenGABGS, DPMeanBGS, DPAdaptiveMedianBGS, KDE
 // Each reads / writes the same ./config/<Class>.xml with the same keys and defaults as the class it stands in for
-// (the list is bgs_classes.inc, shared verbatim with this repository's tested host mirror, tracking_amd/host/bgs_host.h).
+// (the list is bgs_classes.inc + bgs_classes_kde.inc, shared verbatim with this repository's tested host mirror, tracking_amd/host/bgs_host.h).
 //
 // Use:   mixtureOfGaussianV2BGS = new hipbgs::MixtureOfGaussianV2BGS;      // FrameProcessor.cpp:59-60
 //        if(i==36) bgs = new hipbgs::SuBSENSEBGS();                          // ustc_src/ustc_bgs.cpp:68
@@ -141,6 +141,7 @@ class HipBGSBase : public IBGS {
 #define override  /* the reference builds as C++03 */
 #endif
 #include "bgs_classes.inc"
+#include "bgs_classes_kde.inc"
 #ifdef BGS_HIP_DEFINED_OVERRIDE
 #undef override
 #undef BGS_HIP_DEFINED_OVERRIDE

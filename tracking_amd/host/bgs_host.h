@@ -268,6 +268,7 @@ class HipBGSBase : public IBGS {
   ~Class() override { std::cout << "~" #Class "()" << std::endl; }
 
 #include "bgs_classes.inc"
+#include "bgs_classes_kde.inc"
 
 #undef BGS_HIP_BANNER_DTOR
 
