@@ -52,6 +52,8 @@ typedef enum bgs_algo {
   BGS_DP_ADAPTIVE_MEDIAN = 16, /* DPAdaptiveMedianBGS::process     package_bgs/dp/DPAdaptiveMedianBGS.cpp:29-81 */
   BGS_LOBSTER = 17,          /* LOBSTERBGS::process                package_bgs/pl/LOBSTER.cpp:20-45 */
   BGS_KDE = 18,              /* KDE::process (USTC_BGS type 32)    package_bgs/ae/KDE.cpp:34-96 */
+  BGS_DP_PRATI_MEDIOD = 19,  /* DPPratiMediodBGS::process (USTC_BGS type 14) package_bgs/dp/DPPratiMediodBGS.cpp:29-81 */
+  BGS_DP_TEXTURE = 20,       /* DPTextureBGS::process (USTC_BGS type 16)     package_bgs/dp/DPTextureBGS.cpp:39-134 */
   BGS_ALGO_COUNT
 } bgs_algo;
 
@@ -166,7 +168,19 @@ typedef struct bgs_params {
   int32_t kde_update_model;     /* 1   NPBGSubtractor::UpdateBGFlag (never initialised by the reference) */
   double kde_threshold;         /* 10e-8 th: probability threshold */
   double kde_alpha;             /* 0.3   alpha: brightness band of the colour-ratio gate */
+
+  /* DPPratiMediodBGS (package_bgs/dp/DPPratiMediodBGS.cpp:19, :83-107).  bgs_default_params fills these for
+   * BGS_DP_PRATI_MEDIOD only (zero for every other algorithm); it also sets dp_threshold = 30 (LowThreshold, truncated to an
+   * integer; the returned mask uses HighThreshold = 2 x LowThreshold) and dp_sampling_rate = 5.  Like the wrapper, which copies
+   * them into its model once, on the first frame, all four are fixed once the geometry is set.
+   * Refused (BGS_ERR_UNSUPPORTED): dp_sampling_rate 0, dp_history_size outside 1..BGS_PRATI_MAX_HISTORY, a negative
+   * dp_threshold (the reference's unsigned int wraps it), 1-channel frames.  BGS_DP_TEXTURE has no run-time parameters. */
+  int32_t dp_history_size;      /* 16  historySize: samples in the circular buffer */
+  int32_t dp_weight;            /* 5   weight: stored and saved by the reference, never read */
 } bgs_params;
+
+/* Largest dp_history_size the PratiMediod kernel is built for (every dist entry then fits in 16 bits: 64 x 255 < 65536). */
+#define BGS_PRATI_MAX_HISTORY 64
 
 int bgs_abi_version(void);
 
@@ -390,7 +404,12 @@ const char* bgs_last_error(void);
 
 /* State planes of the dp/ models (bgs_get_state): "modes" f32 [K*F][n] with F = 5 (sigma, mu0, mu1, mu2, weight) for
  * Zivkovic and 6 (variance, mu0, mu1, mu2, weight, significants) for Grimson, plane index k*F + f; "nmodes" u8 [n];
- * WrenGA "gauss" f32 [4][n] (mu0..2, var); Mean "mean" f32 [3][n]; AdaptiveMedian "median" u8 [n*3]. */
+ * WrenGA "gauss" f32 [4][n] (mu0..2, var); Mean "mean" f32 [3][n]; AdaptiveMedian "median" u8 [n*3].
+ * PratiMediod: "samples" u8 [historySize][n][3] in slot order (slots not yet filled hold 0), "dist" u16 [historySize][n] (the
+ * L-inf sums, 0 for slots not yet filled), "median" u8 [n][3] (the medoid of the last sampled frame; 0 before the first);
+ * bgs_get_state also answers "count" int64 [2] = {samples in the buffer, next slot to replace}.
+ * Texture: "hist" u8 [n][3][64], the background histograms in the reference's r, g, b order (TextureHistogram); pixels outside
+ * the processed interior (7 <= x < cols-7, 7 <= y < rows-7) hold 0. */
 
 /* LBSP 16-bit double-cross descriptors of a whole 8UC3 / 8UC1 image (LBSP.h:50-95,
  * LBSP_16bits_dbcross_{3ch3t,1ch}.i).  d_desc: [rows][cols][channels] uint16; the

@@ -4,6 +4,7 @@ Not the driver's bench line (bench.py is); the numbers go to DESIGN.md §6.
   configs[2]: WeightedMovingVarianceBGS + AdaptiveBackgroundLearning, 3840x2160 (HBM-bound stress)
   configs[3]: LBSP descriptor path, 1920x1080
   --only kde: KDE (package_bgs/ae) young / aged model, static and ~10 % foreground scenes, 8 x 1080p
+  --only dp2: DPPratiMediodBGS (sampled / other frames) and DPTextureBGS, 8 x 1080p
 usage: bench_configs.py [--streams S] [--swizzle 0|1]"""
 import argparse
 import os
@@ -584,6 +585,68 @@ def run_kde(S=8, rows=1080, cols=1920, steps=30, scenes=((("static + noise", 0.0
     torch.cuda.empty_cache()
 
 
+def run_dp2(S=8, rows=1080, cols=1920, steps=40, texture_only=False):
+    """DPPratiMediodBGS (defaults: history 16, rate 5, threshold 30) and DPTextureBGS at S x 1080p: ms per step by HIP events around
+    each step's launches, PratiMediod split into sampled frames (medoid update) and the others (mask only), with a full buffer.
+    Bytes per pixel are counted from the layouts of kernel_dp2.h (DRAM traffic if nothing is reused beyond the 3x3 / 15x15
+    neighbourhood, which L2 serves); `copy_frac` is the achieved rate over this box's float4 copy rate (bench.py's calibration)."""
+    dev = torch.device("cuda", 0)
+    px = S * rows * cols
+    T = 10
+    g = torch.Generator(device=dev)
+    g.manual_seed(5)
+    base = torch.randint(30, 220, (S, rows, cols, 3), generator=g, device=dev, dtype=torch.int16)
+    pool = torch.empty((T, S, rows, cols, 3), dtype=torch.uint8, device=dev)
+    bh, bw = rows // 3, cols // 3
+    for t in range(T):
+        f = base + torch.randint(-4, 5, base.shape, generator=g, device=dev, dtype=torch.int16)
+        y, x = (t * 37) % (rows - bh), (t * 53) % (cols - bw)
+        f[:, y:y + bh, x:x + bw] = 255 - f[:, y:y + bh, x:x + bw]
+        pool[t] = f.clamp(0, 255).to(torch.uint8)
+    del base
+    copy = capi.calibrate_copy(0, 2 << 30, 0) if not texture_only else float("nan")
+    fg = torch.empty((S, rows, cols), dtype=torch.uint8, device=dev)
+    bits = torch.empty((S, rows * cols // 64), dtype=torch.int64, device=dev)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+
+    def timed(e, t0, n):
+        for i in range(n):
+            ev[i][0].record()
+            e.process_batch_device(pool[(t0 + i) % T], fg, None, bits)
+            ev[i][1].record()
+        torch.cuda.synchronize()
+        return [a.elapsed_time(b) for a, b in ev[:n]]
+
+    H, rate = 16, 5
+    bpp = {"PratiMediod sampled": 16 * 4 + 16 * 2 * 2 + 4 + 4 + 4 + 3 + 1, "PratiMediod other": 4 + 3 + 1, "Texture": 192 + 3 + 2 + 3 + 1 + 64 + 64 + 1}
+    legs = {}
+    if not texture_only:
+        e = Engine(capi.DP_PRATI_MEDIOD, n_streams=S)
+        e.set_geometry(rows, cols, 3)
+        t = 0
+        while t < H * rate + 1:  # fill the buffer
+            e.process_batch_device(pool[t % T], fg, None, bits)
+            t += 1
+        torch.cuda.synchronize()
+        t0 = t
+        ms = timed(e, t0, steps)
+        e.close()
+        legs = {"PratiMediod sampled": [m for i, m in enumerate(ms) if (t0 + i) % rate == 0],
+                "PratiMediod other": [m for i, m in enumerate(ms) if (t0 + i) % rate != 0]}
+    e = Engine(capi.DP_TEXTURE, n_streams=S)
+    e.set_geometry(rows, cols, 3)
+    timed(e, 0, 3)
+    legs["Texture"] = timed(e, 3, steps)
+    e.close()
+    for label, v in legs.items():
+        m = float(np.median(v))
+        gbps = bpp[label] * px / (m * 1e-3) / 1e9
+        print("%-20s %dx%d x%d streams: %.3f ms/step (median of %d, min %.3f); %d B/px counted -> %.0f GB/s = %.2f of copy %.0f GB/s"
+              % (label, cols, rows, S, m, len(v), min(v), bpp[label], gbps, gbps / copy, copy))
+    del pool
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=8)
@@ -592,6 +655,12 @@ def main():
     S = args.streams
     if args.only == "kde":
         run_kde(S)
+        return
+    if args.only == "dp2":
+        run_dp2(S)
+        return
+    if args.only == "dp2_tex":  # Texture only, short leg, no calibration: for counter passes
+        run_dp2(S, steps=5, texture_only=True)
         return
     if args.only in ("kde_static", "kde_fg"):  # one scene, short legs, no trip counter: for counter passes
         run_kde(S, steps=5, scenes=((("static + noise", 0.0),) if args.only == "kde_static" else (("~10 % foreground", 0.1),)), count_trips=False)

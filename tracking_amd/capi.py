@@ -15,6 +15,8 @@ FRAME_DIFF, STATIC_FRAME_DIFF, WMM, WMV, ABL, ASBL, MOG2, MOG1, GMG, SUBSENSE, L
 DP_ZIVKOVIC_AGMM, DP_GRIMSON_GMM, DP_WREN_GA, DP_MEAN, DP_ADAPTIVE_MEDIAN = range(12, 17)
 LOBSTER = 17
 KDE = 18
+DP_PRATI_MEDIOD, DP_TEXTURE = 19, 20
+PRATI_MAX_HISTORY = 64  # BGS_PRATI_MAX_HISTORY
 FG_VALID, BG_VALID = 1, 2
 OPT_BORROW_FRAMES, OPT_MOG2_PIXELS_PER_LANE, OPT_MOG2_TILED, OPT_XCD_SWIZZLE, OPT_PLACEMENT_PROBE, OPT_MOG2_SPARSE, OPT_CLIP_FUSE, OPT_HOST_REGISTER, OPT_MODEL_CHUNK_MB, OPT_MODEL_CHUNK_MIN_MB = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 
@@ -80,6 +82,8 @@ class BgsParams(C.Structure):
         ("kde_update_model", C.c_int32),
         ("kde_threshold", C.c_double),
         ("kde_alpha", C.c_double),
+        ("dp_history_size", C.c_int32),
+        ("dp_weight", C.c_int32),
     ]
 
 

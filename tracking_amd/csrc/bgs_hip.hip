@@ -25,6 +25,7 @@
 #include "kernel_gmg.h"
 #include "kernel_ingest.h"
 #include "kernel_kde.h"
+#include "kernel_dp2.h"
 #include "kernel_cc.h"
 #include "kernel_dp.h"
 #include "kernel_mog1.h"
@@ -140,6 +141,11 @@ struct bgs_engine {
     int64_t fn = 0, top = 0, tidx = 0, tbc = 0, tbtop = 0;
   };
   std::vector<KdeStream> kde;
+  // DPPratiMediodBGS / DPTextureBGS models (kernel_dp2.h / engine_dp2.h): stream-major planes
+  uint32_t *pm_samples = nullptr, *pm_med = nullptr;  // samples [S][H][n], medoid ping-pong [2][S][n]
+  uint16_t* pm_dist = nullptr;                        // [S][H][n]
+  uint32_t *tex_r = nullptr, *tex_gb = nullptr;       // histogram planes [S][16][n], [S][32][n]
+  uint8_t* tex_mask = nullptr;                        // the last frame's mask [S][n] (the transposed update gate)
   // MOG2 model (kernel_mog2.h: tiles of ranked weights + fixed-slot records + rank->slot meta words)
   uint8_t* mog2_state = nullptr;
   int xcd_swizzle = 1;             // XCD-aware block order (kernel_mog2.h): 0 off, 1 model kernels (MOG2, MOG1, dp), 2 also the byte-stream kernels
@@ -214,6 +220,8 @@ namespace {
 void ss_free(bgs_engine* e);  // engine_subsense.h
 void kde_free(bgs_engine* e);  // engine_kde.h
 int kde_check(const bgs_params& p);
+void dp2_free(bgs_engine* e);  // engine_dp2.h
+int dp2_check(bgs_algo algo, const bgs_params& p);
 void vmm_free(VmmRange& v);  // below
 
 void lane_release(bgs_engine::Lane& ln) {  // whatever of a lane came to be (bgs_submit's set-up may have failed half-way)
@@ -257,6 +265,7 @@ void free_all(bgs_engine* e) {
   e->events.clear();
   ss_free(e);
   kde_free(e);
+  dp2_free(e);
   if (e->d_stat) (void)hipFree(e->d_stat), e->d_stat = nullptr;
   if (e->h_stat) (void)hipHostFree(e->h_stat), e->h_stat = nullptr;
   for (int i = 0; i < bgs_engine::kStatSlots; ++i) {
@@ -284,6 +293,7 @@ int check_params(bgs_algo algo, const bgs_params& p) {
     return fail(BGS_ERR_UNSUPPORTED, "dp GMM kernels are built for 1..5 gaussians, got %d", p.dp_gaussians);
   if (algo == BGS_DP_ADAPTIVE_MEDIAN && p.dp_sampling_rate == 0) return fail(BGS_ERR_UNSUPPORTED, "AdaptiveMedian samplingRate 0 (frame_num %% 0)");
   if (algo == BGS_KDE) return kde_check(p);
+  if (algo == BGS_DP_PRATI_MEDIOD || algo == BGS_DP_TEXTURE) return dp2_check(algo, p);
   return BGS_OK;
 }
 
@@ -530,6 +540,7 @@ int mog2_allocate(bgs_engine* e) {
 #include "engine_subsense.h"
 #include "engine_dp.h"
 #include "engine_kde.h"
+#include "engine_dp2.h"
 
 // (Re)build ABL's lookup table for the current alpha on e->stream.  Called when the geometry is set and when bgs_set_params
 // changes alpha; both drain the device first / the stream after, so no launch on any stream sees a half-written table.
@@ -586,7 +597,9 @@ int allocate(bgs_engine* e, int rows, int cols, int ch) {
     case BGS_DP_WREN_GA:
     case BGS_DP_MEAN: break;
     case BGS_DP_ADAPTIVE_MEDIAN: e->state_ch = 3; break;  // bgstate = the median image
-    case BGS_KDE: break;
+    case BGS_KDE:
+    case BGS_DP_PRATI_MEDIOD:
+    case BGS_DP_TEXTURE: break;
     default: return fail(BGS_ERR_UNSUPPORTED, "algorithm %d is not implemented in this build", (int)e->algo);
   }
   for (int i = 0; i < e->nring; ++i) DMALLOC(e->ring[i], fb);
@@ -635,6 +648,10 @@ int allocate(bgs_engine* e, int rows, int cols, int ch) {
   }
   if (e->algo == BGS_KDE) {
     int rc = kde_allocate(e);
+    if (rc) return rc;
+  }
+  if (is_dp2(e->algo)) {
+    int rc = dp2_allocate(e);
     if (rc) return rc;
   }
   // Whatever allocation enqueued on e->stream (statistics counters, poison fills) is complete before the caller's first
@@ -762,6 +779,8 @@ uint64_t launch_key(const bgs_engine* e, int i) {
     case BGS_MOG1: return lr_key(p.alpha, p.mog1_history, 1);
     case BGS_MOG2: return lr_key(p.alpha, p.mog2_history, 2);
     case BGS_KDE: return kde_key(e, i);
+    case BGS_DP_PRATI_MEDIOD:
+    case BGS_DP_TEXTURE: return dp2_key(e, i);
     default: return (uint64_t)t | (uint64_t)(e->ss ? e->ss->pp[i] & 1 : 0) << 62;  // SuBSENSE / LOBSTER: the frame index itself goes into the kernels (counter-based random draws); + which half of the ping-pong maps is current
   }
 }
@@ -1105,6 +1124,12 @@ int process_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, ui
       if (rc) return rc;
       break;
     }
+    case BGS_DP_PRATI_MEDIOD:
+    case BGS_DP_TEXTURE: {
+      int rc = dp2_run(e, first, count, d_frames, d_fg, d_bits, s, &flags);
+      if (rc) return rc;
+      break;
+    }
     default: return fail(BGS_ERR_UNSUPPORTED, "algorithm %d is not implemented in this build", (int)e->algo);
   }
   HIP_TRY(hipGetLastError());
@@ -1387,6 +1412,9 @@ int bgs_default_params(bgs_algo algo, bgs_params* p) {
       p->kde_sd_estimation = 1, p->kde_color_ratios = 1, p->kde_update_model = 1;
       p->kde_threshold = 10e-8, p->kde_alpha = 0.3;
       break;
+    case BGS_DP_PRATI_MEDIOD:  // DPPratiMediodBGS.cpp:19, :98-104 (dp_history_size / dp_weight stay zero for every other algorithm)
+      p->dp_threshold = 30.0f, p->dp_sampling_rate = 5, p->dp_history_size = 16, p->dp_weight = 5;
+      break;
     default: break;
   }
   return BGS_OK;
@@ -1468,6 +1496,10 @@ int bgs_set_params(bgs_engine* e, const bgs_params* params) {
     if (e->algo == BGS_KDE) {  // KDE.cpp:40-66: Intialize / SetThresholds once; framesToLearn is re-read every frame (and update_model is live)
       p.kde_sequence_length = old.kde_sequence_length, p.kde_time_window = old.kde_time_window, p.kde_sd_estimation = old.kde_sd_estimation;
       p.kde_color_ratios = old.kde_color_ratios, p.kde_threshold = old.kde_threshold, p.kde_alpha = old.kde_alpha;
+    }
+    if (e->algo == BGS_DP_PRATI_MEDIOD) {  // PratiMediodBGS::Initalize copies m_params once (DPPratiMediodBGS.cpp:55-64)
+      p.dp_threshold = old.dp_threshold, p.dp_sampling_rate = old.dp_sampling_rate;
+      p.dp_history_size = old.dp_history_size, p.dp_weight = old.dp_weight;
     }
     if (e->algo == BGS_ASBL && (!e->abl_lut_valid || p.alpha_learn != e->asbl_lut_alpha[0] || p.alpha_detection != e->asbl_lut_alpha[1])) {
       if (hipSetDevice(e->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(BGS_ERR_HIP, "device sync failed");
@@ -1868,6 +1900,7 @@ int64_t bgs_get_state(bgs_engine* e, int stream, const char* plane, void* dst, s
   }
   if ((e->algo == BGS_SUBSENSE || e->algo == BGS_LOBSTER) && e->ss) return ss_get_state(e, stream, plane, dst, cap);
   if (e->algo == BGS_KDE && e->kde_samples) return kde_get_state(e, stream, plane, dst, cap);
+  if ((e->algo == BGS_DP_PRATI_MEDIOD && e->pm_samples) || (e->algo == BGS_DP_TEXTURE && e->tex_r)) return dp2_get_state(e, stream, plane, dst, cap);
   if (is_dp(e->algo)) {  // planes are stored canonically: [stream][plane][n]
     const int planes = dp_planes_of(e);
     const char* fname = (e->algo == BGS_DP_WREN_GA) ? "gauss" : (e->algo == BGS_DP_MEAN) ? "mean" : "modes";

@@ -18,6 +18,8 @@ FrameProcessor::FrameProcessor()
   zivkovicAGMM = nullptr, enableDPZivkovicAGMMBGS = false;
   temporalMean = nullptr, enableDPMeanBGS = false;
   wrenGA = nullptr, enableDPWrenGABGS = false;
+  pratiMediod = nullptr, enableDPPratiMediodBGS = false;
+  textureBGS = nullptr, enableDPTextureBGS = false;
   kde = nullptr, enableKDE = false;
   sdbgs = nullptr, enableSigmaDeltaBGS = false;
   ssbgs = nullptr, enableSuBSENSEBGS = false;
@@ -45,6 +47,8 @@ void FrameProcessor::init() {  // FrameProcessor.cpp:35-155
   if (enableDPZivkovicAGMMBGS) zivkovicAGMM = new DPZivkovicAGMMBGS;
   if (enableDPMeanBGS) temporalMean = new DPMeanBGS;
   if (enableDPWrenGABGS) wrenGA = new DPWrenGABGS;
+  if (enableDPPratiMediodBGS) pratiMediod = new DPPratiMediodBGS;  // :81-88 (DPEigenbackgroundBGS between them is not built)
+  if (enableDPTextureBGS) textureBGS = new DPTextureBGS;
   if (enableKDE) kde = new KDE;  // after VuMeter, before IMBS (:135)
   if (enableSigmaDeltaBGS) sdbgs = new SigmaDeltaBGS;
   if (enableSuBSENSEBGS) ssbgs = new SuBSENSEBGS;
@@ -111,6 +115,8 @@ void FrameProcessor::process(const Image& img_input) {  // :169-340
   if (enableDPZivkovicAGMMBGS) process("DPZivkovicAGMMBGS", zivkovicAGMM, img_prep, img_zivgmm);
   if (enableDPMeanBGS) process("DPMeanBGS", temporalMean, img_prep, img_tmpmean);
   if (enableDPWrenGABGS) process("DPWrenGABGS", wrenGA, img_prep, img_wrenga);
+  if (enableDPPratiMediodBGS) process("DPPratiMediodBGS", pratiMediod, img_prep, img_pramed);  // :217-224
+  if (enableDPTextureBGS) process("DPTextureBGS", textureBGS, img_prep, img_texbgs);
   if (enableKDE) process("KDE", kde, img_prep, img_kde);  // :275
   if (enableSigmaDeltaBGS) process("SigmaDeltaBGS", sdbgs, img_prep, img_sdbgs);
   if (enableSuBSENSEBGS) process("SuBSENSEBGS", ssbgs, img_prep, img_ssbgs);
@@ -126,6 +132,8 @@ void FrameProcessor::finish() {  // :342-482 (reverse order of init)
   delete ssbgs, ssbgs = nullptr;
   delete sdbgs, sdbgs = nullptr;
   delete kde, kde = nullptr;
+  delete textureBGS, textureBGS = nullptr;
+  delete pratiMediod, pratiMediod = nullptr;
   delete wrenGA, wrenGA = nullptr;
   delete temporalMean, temporalMean = nullptr;
   delete zivkovicAGMM, zivkovicAGMM = nullptr;
@@ -172,6 +180,8 @@ void FrameProcessor::saveConfig() {  // :496-552 (keys of the classes this build
   fs.writeInt("enableDPZivkovicAGMMBGS", enableDPZivkovicAGMMBGS);
   fs.writeInt("enableDPMeanBGS", enableDPMeanBGS);
   fs.writeInt("enableDPWrenGABGS", enableDPWrenGABGS);
+  fs.writeInt("enableDPPratiMediodBGS", enableDPPratiMediodBGS);  // :522-524
+  fs.writeInt("enableDPTextureBGS", enableDPTextureBGS);
   fs.writeInt("enableKDE", enableKDE);  // :544
   fs.writeInt("enableSigmaDeltaBGS", enableSigmaDeltaBGS);
   fs.writeInt("enableSuBSENSEBGS", enableSuBSENSEBGS);
@@ -198,6 +208,8 @@ void FrameProcessor::loadConfig() {  // :554-610 (defaults: PreProcessor and Fra
   enableDPZivkovicAGMMBGS = fs.readInt("enableDPZivkovicAGMMBGS", false);
   enableDPMeanBGS = fs.readInt("enableDPMeanBGS", false);
   enableDPWrenGABGS = fs.readInt("enableDPWrenGABGS", false);
+  enableDPPratiMediodBGS = fs.readInt("enableDPPratiMediodBGS", false);  // :580-582
+  enableDPTextureBGS = fs.readInt("enableDPTextureBGS", false);
   enableKDE = fs.readInt("enableKDE", false);  // :602
   enableSigmaDeltaBGS = fs.readInt("enableSigmaDeltaBGS", false);
   enableSuBSENSEBGS = fs.readInt("enableSuBSENSEBGS", false);

@@ -3,9 +3,10 @@
 // One IBGS class per reference class on the hot path, all in namespace hipbgs so that nothing clashes with the CPU classes:
 //   hipbgs::FrameDifferenceBGS, StaticFrameDifferenceBGS, WeightedMovingMeanBGS, WeightedMovingVarianceBGS,
 //   AdaptiveBackgroundLearning, AdaptiveSelectiveBackgroundLearning, MixtureOfGaussianV1BGS, MixtureOfGaussianV2BGS, GMG,
-//   SigmaDeltaBGS, SuBSENSEBGS, LOBSTERBGS, DPZivkovicAGMMBGS, DPGrimsonGMMBGS, DPWrenGABGS, DPMeanBGS, DPAdaptiveMedianBGS, KDE
+//   SigmaDeltaBGS, SuBSENSEBGS, LOBSTERBGS, DPZivkovicAGMMBGS, DPGrimsonGMMBGS, DPWrenGABGS, DPMeanBGS, DPAdaptiveMedianBGS, KDE,
+//   DPPratiMediodBGS, DPTextureBGS
 // Each reads / writes the same ./config/<Class>.xml with the same keys and defaults as the class it stands in for
-// (the list is bgs_classes.inc + bgs_classes_kde.inc, shared verbatim with this repository's tested host mirror, tracking_amd/host/bgs_host.h).
+// (the list is bgs_classes.inc + bgs_classes_kde.inc + bgs_classes_dp2.inc, shared verbatim with this repository's tested host mirror, tracking_amd/host/bgs_host.h).
 //
 // Use:   mixtureOfGaussianV2BGS = new hipbgs::MixtureOfGaussianV2BGS;      // FrameProcessor.cpp:59-60
 //        if(i==36) bgs = new hipbgs::SuBSENSEBGS();                          // ustc_src/ustc_bgs.cpp:68
@@ -142,6 +143,7 @@ class HipBGSBase : public IBGS {
 #endif
 #include "bgs_classes.inc"
 #include "bgs_classes_kde.inc"
+#include "bgs_classes_dp2.inc"
 #ifdef BGS_HIP_DEFINED_OVERRIDE
 #undef override
 #undef BGS_HIP_DEFINED_OVERRIDE

@@ -50,6 +50,8 @@ class HipFGDetector : public CvFGDetector {
     if (i == 11) bgs = new hipbgs::DPZivkovicAGMMBGS;
     if (i == 12) bgs = new hipbgs::DPMeanBGS;
     if (i == 13) bgs = new hipbgs::DPWrenGABGS;
+    if (i == 14) bgs = new hipbgs::DPPratiMediodBGS;
+    if (i == 16) bgs = new hipbgs::DPTextureBGS;
     if (i == 32) bgs = new hipbgs::KDE;
     if (i == 35) bgs = new hipbgs::SigmaDeltaBGS;
     if (i == 36) bgs = new hipbgs::SuBSENSEBGS();

@@ -269,6 +269,7 @@ class HipBGSBase : public IBGS {
 
 #include "bgs_classes.inc"
 #include "bgs_classes_kde.inc"
+#include "bgs_classes_dp2.inc"
 
 #undef BGS_HIP_BANNER_DTOR
 

@@ -2,7 +2,7 @@
 // cvCreateBlobTrackerAuto1 (ustc_src/trackingMain.cpp:33-35, :613-618; the shipped build uses type 36 = SuBSENSE).
 // Same type table, same Process / GetMask / Release protocol; OpenCV-legacy's CvFGDetector base and IplImage are not in this
 // image, so the mask is handed out as a bgs_hip::Image (INTEGRATION.md shows the IplImage-returning version for the reference).
-// Types whose class is outside the hot path (ustc_bgs.cpp:23-58: dp Prati/Eigen/Texture, tb/, jmo/, lb/, ck/, av/, db/, sjn/; of
+// Types whose class is outside the hot path (ustc_bgs.cpp:23-58: dp Eigenbackground, tb/, jmo/, lb/, ck/, av/, db/, sjn/; of
 // ae/ only KDE, type 32, is built) throw instead of silently running something else.
 #pragma once
 #include "bgs_host.h"
@@ -33,6 +33,8 @@ class USTC_BGS {
     if (i == 11) bgs = new DPZivkovicAGMMBGS;
     if (i == 12) bgs = new DPMeanBGS;
     if (i == 13) bgs = new DPWrenGABGS;
+    if (i == 14) bgs = new DPPratiMediodBGS;
+    if (i == 16) bgs = new DPTextureBGS;
     if (i == 32) bgs = new KDE;
     if (i == 35) bgs = new SigmaDeltaBGS;
     if (i == 36) bgs = new SuBSENSEBGS();
