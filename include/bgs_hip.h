@@ -54,7 +54,17 @@ typedef enum bgs_algo {
   BGS_KDE = 18,              /* KDE::process (USTC_BGS type 32)    package_bgs/ae/KDE.cpp:34-96 */
   BGS_DP_PRATI_MEDIOD = 19,  /* DPPratiMediodBGS::process (USTC_BGS type 14) package_bgs/dp/DPPratiMediodBGS.cpp:29-81 */
   BGS_DP_TEXTURE = 20,       /* DPTextureBGS::process (USTC_BGS type 16)     package_bgs/dp/DPTextureBGS.cpp:39-134 */
-  BGS_ALGO_COUNT
+  /* BGS_ALGO_COUNT is FROZEN at 21: the CPU restatement the tests compare with bounds its defaults table with it, and the tests
+   * compile this header and pin its value, so it no longer counts the classes.  Ids added later are declared after it with explicit values
+   * (the first repeats the count's value, which C allows) and BGS_ALGO_END is the end marker every range check uses. */
+  BGS_ALGO_COUNT,
+  /* Laurence Bender's package_bgs/lb/ models (3-channel frames only; double-precision per-pixel models; FG and BG from frame 1) */
+  BGS_LB_SIMPLE_GAUSSIAN = 21,    /* LBSimpleGaussian::process (USTC_BGS type 25)     package_bgs/lb/LBSimpleGaussian.cpp:31-73 */
+  BGS_LB_FUZZY_GAUSSIAN = 22,     /* LBFuzzyGaussian::process (USTC_BGS type 26)      package_bgs/lb/LBFuzzyGaussian.cpp:31-74 */
+  BGS_LB_MOG = 23,                /* LBMixtureOfGaussians::process (USTC_BGS type 27) package_bgs/lb/LBMixtureOfGaussians.cpp:31-74 */
+  BGS_LB_ADAPTIVE_SOM = 24,       /* LBAdaptiveSOM::process (USTC_BGS type 28)        package_bgs/lb/LBAdaptiveSOM.cpp:31-74 */
+  BGS_LB_FUZZY_ADAPTIVE_SOM = 25, /* LBFuzzyAdaptiveSOM::process (USTC_BGS type 29)   package_bgs/lb/LBFuzzyAdaptiveSOM.cpp:31-74 */
+  BGS_ALGO_END
 } bgs_algo;
 
 typedef enum bgs_status {
@@ -177,6 +187,28 @@ typedef struct bgs_params {
    * dp_threshold (the reference's unsigned int wraps it), 1-channel frames.  BGS_DP_TEXTURE has no run-time parameters. */
   int32_t dp_history_size;      /* 16  historySize: samples in the circular buffer */
   int32_t dp_weight;            /* 5   weight: stored and saved by the reference, never read */
+
+  /* package_bgs/lb/ wrappers (LB*.cpp:19-20 constructors).  bgs_default_params fills these for the five BGS_LB_* ids only (zero for
+   * every other algorithm).  Each is the wrapper's 0..255 integer; the wrappers re-read their XML and call setBGModelParameter
+   * with it on EVERY frame, so all seven are live through bgs_set_params.  The engine maps them to the model's doubles on the
+   * host, in the reference's order of operations (value / 255.0, then squared / cubed / 100 x / 255^2 v^4 / over Wmax).
+   *                                     SimpleGaussian FuzzyGaussian MixtureOfGaussians AdaptiveSOM FuzzyAdaptiveSOM
+   *   lb_sensitivity                         66             72             81              75            90
+   *   lb_bg_threshold                         -            162             83               -             -
+   *   lb_learning_rate                       18             49             59              62            38
+   *   lb_noise_variance                     162            195            206               -             -
+   *   lb_training_sensitivity                 -              -              -             245           240
+   *   lb_training_learning_rate               -              -              -             255           255
+   *   lb_training_steps                       -              -              -              55            81
+   * Refused (BGS_ERR_UNSUPPORTED): any value outside 0..255, 1-channel frames, lb_noise_variance 0 (Gaussians,
+   * MoG), lb_bg_threshold 255 (MoG), lb_training_steps 0 (SOMs). */
+  int32_t lb_sensitivity;
+  int32_t lb_bg_threshold;
+  int32_t lb_learning_rate;
+  int32_t lb_noise_variance;
+  int32_t lb_training_sensitivity;
+  int32_t lb_training_learning_rate;
+  int32_t lb_training_steps;
 } bgs_params;
 
 /* Largest dp_history_size the PratiMediod kernel is built for (every dist entry then fits in 16 bits: 64 x 255 < 65536). */
@@ -409,7 +441,11 @@ const char* bgs_last_error(void);
  * L-inf sums, 0 for slots not yet filled), "median" u8 [n][3] (the medoid of the last sampled frame; 0 before the first);
  * bgs_get_state also answers "count" int64 [2] = {samples in the buffer, next slot to replace}.
  * Texture: "hist" u8 [n][3][64], the background histograms in the reference's r, g, b order (TextureHistogram); pixels outside
- * the processed interior (7 <= x < cols-7, 7 <= y < rows-7) hold 0. */
+ * the processed interior (7 <= x < cols-7, 7 <= y < rows-7) hold 0.
+ * lb/ models, all f64 in the reference's memory order, colour fields in the byte order of the input pixel (B, G, R):
+ * SimpleGaussian / FuzzyGaussian "mu", "var" f64 [n][3]; MixtureOfGaussians "w" f64 [n][3], "mu", "var" f64 [n][3][3] (pixel, slot,
+ * colour), "sortkey" f64 [n][3], "k" int32 [n] (slots >= k read 0); AdaptiveSOM / FuzzyAdaptiveSOM "som" f64 [n][3][3][3] (pixel,
+ * neuron row, neuron column, colour), "bg" u8 [n][3], "count" int64 [1] = the stream's training counter m_K. */
 
 /* LBSP 16-bit double-cross descriptors of a whole 8UC3 / 8UC1 image (LBSP.h:50-95,
  * LBSP_16bits_dbcross_{3ch3t,1ch}.i).  d_desc: [rows][cols][channels] uint16; the

@@ -5,6 +5,8 @@ Not the driver's bench line (bench.py is); the numbers go to DESIGN.md §6.
   configs[3]: LBSP descriptor path, 1920x1080
   --only kde: KDE (package_bgs/ae) young / aged model, static and ~10 % foreground scenes, 8 x 1080p
   --only dp2: DPPratiMediodBGS (sampled / other frames) and DPTextureBGS, 8 x 1080p
+  --only lb: the five package_bgs/lb models (double-precision planes), static and ~10 % foreground scenes, SOMs inside and past their
+             calibration phase, the Gaussian pair with one and two pixels per lane, 8 x 1080p  (lb_<class>: one class, short legs)
 usage: bench_configs.py [--streams S] [--swizzle 0|1]"""
 import argparse
 import os
@@ -646,6 +648,60 @@ def run_dp2(S=8, rows=1080, cols=1920, steps=40, texture_only=False):
     del pool
     torch.cuda.empty_cache()
 
+LB_CLASSES = {"sg": ("LBSimpleGaussian", "LB_SIMPLE_GAUSSIAN"), "fg": ("LBFuzzyGaussian", "LB_FUZZY_GAUSSIAN"), "mog": ("LBMixtureOfGaussians", "LB_MOG"),
+              "som": ("LBAdaptiveSOM", "LB_ADAPTIVE_SOM"), "fsom": ("LBFuzzyAdaptiveSOM", "LB_FUZZY_ADAPTIVE_SOM")}
+
+
+def run_lb(S=8, rows=1080, cols=1920, steps=30, only=None, px_variants=(2, 1), calibrate=True, scenes=(("static + noise", 0.0), ("~10 % foreground", 0.1))):
+    """The five package_bgs/lb classes (reference defaults) at S x 1080p, byte mask + background image out: kernel ms per step (HIP
+    events around the launch, mean of `steps`) on a static scene with sensor noise and on one with ~10 % foreground, the model aged
+    past the SOMs' calibration phase (frame 100 on; for the SOMs also inside it, frames 11 on) - the Gaussian pair with two pixels
+    per lane (16 B per lane and plane) and with one (BGS_LB_PX).  Bytes per pixel are the algorithmic ones of kernel_lb.h: frame 3 +
+    model read + model written + mask 1 + background 3 (SOMs: + the 3 kept background bytes each way); for MoG and the SOMs the
+    dense bound (every slot / all nine neurons) and the least a pixel can move; `copy_frac` is the dense figure's rate over this
+    process's float4 copy rate (bench.py's calibration)."""
+    dev = torch.device("cuda", 0)
+    px = S * rows * cols
+    T = 12
+    copy = capi.calibrate_copy(0, 2 << 30, 0) if calibrate else float("nan")
+    fg = torch.empty((S, rows, cols), dtype=torch.uint8, device=dev)
+    bg = torch.empty((S, rows, cols, 3), dtype=torch.uint8, device=dev)
+    dense = {"sg": 3 + 48 + 48 + 1 + 3, "fg": 3 + 48 + 48 + 1 + 3, "mog": 3 + 172 + 172 + 4, "som": 3 + 216 + 216 + 7 + 3, "fsom": 3 + 216 + 216 + 7 + 3}
+    least = {"sg": 103, "fg": 103, "mog": 3 + 60 + 12 + 4, "som": 3 + 216 + 3 + 4, "fsom": 3 + 216 + 96 + 4}
+    for label, frac in scenes:
+        pool = kde_scene(T, S, rows, cols, frac, dev)
+        learn = kde_scene(11, S, rows, cols, 0.0, dev) if frac > 0 else pool
+        for key, (name, algo) in LB_CLASSES.items():
+            if only and key != only:
+                continue
+            som = key in ("som", "fsom")
+            for pxl in (px_variants if key in ("sg", "fg") else (0,)):
+                if pxl:
+                    os.environ["BGS_LB_PX"] = str(pxl)
+                e = Engine(getattr(capi, algo), n_streams=S)
+                os.environ.pop("BGS_LB_PX", None)
+                e.set_geometry(rows, cols, 3)
+                t = 0
+                for phase, upto in ((("calibration", 11), ("online", 100)) if som else (("aged", 100),)):
+                    while t < upto:
+                        e.process_batch_device(learn[t] if t < 11 else pool[t % T], fg, bg, None)
+                        t += 1
+                    torch.cuda.synchronize()
+                    e.enable_kernel_timing(True)
+                    for _ in range(steps):
+                        e.process_batch_device(pool[t % T], fg, bg, None)
+                        t += 1
+                    torch.cuda.synchronize()
+                    ms, n, kname = e.kernel_timing()
+                    e.enable_kernel_timing(False)
+                    gbps = dense[key] * px / (ms * 1e-3) / 1e9
+                    print("%-20s %-17s %-11s %s%dx%d x%d streams: %s %.3f ms/step (mean of %d) -> %7.1f Mpix/s; %d B/px dense (least %d) -> %.0f GB/s = %.2f of copy %.0f GB/s; fg ratio %.3f"
+                          % (name, label, phase, "%d px/lane " % pxl if pxl else "", cols, rows, S, kname, ms, n, px / ms / 1e3, dense[key], least[key], gbps,
+                             gbps / copy, copy, float((fg != 0).float().mean())))
+                e.close()
+        del pool, learn
+        torch.cuda.empty_cache()
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -658,6 +714,12 @@ def main():
         return
     if args.only == "dp2":
         run_dp2(S)
+        return
+    if args.only == "lb":
+        run_lb(S)
+        return
+    if args.only.startswith("lb_") and args.only[3:] in LB_CLASSES:  # one class, the foreground scene, short legs, no calibration: for counter passes
+        run_lb(S, steps=5, only=args.only[3:], px_variants=(0,), calibrate=False, scenes=(("~10 % foreground", 0.1),))
         return
     if args.only == "dp2_tex":  # Texture only, short leg, no calibration: for counter passes
         run_dp2(S, steps=5, texture_only=True)

@@ -26,6 +26,7 @@
 #include "kernel_ingest.h"
 #include "kernel_kde.h"
 #include "kernel_dp2.h"
+#include "kernel_lb.h"
 #include "kernel_cc.h"
 #include "kernel_dp.h"
 #include "kernel_mog1.h"
@@ -146,6 +147,12 @@ struct bgs_engine {
   uint16_t* pm_dist = nullptr;                        // [S][H][n]
   uint32_t *tex_r = nullptr, *tex_gb = nullptr;       // histogram planes [S][16][n], [S][32][n]
   uint8_t* tex_mask = nullptr;                        // the last frame's mask [S][n] (the transposed update gate)
+  // package_bgs/lb/ models (kernel_lb.h / engine_lb.h): planar doubles [S][P][n], MoG mode counts, the SOMs' background bytes
+  double* lb_model = nullptr;
+  int32_t* lb_k = nullptr;
+  uint8_t* lb_bg = nullptr;
+  std::vector<int> lb_mk;          // the SOMs' training counter m_K, one per stream
+  int lb_px = 1;                   // pixels per lane of the two Gaussian kernels (BGS_LB_PX=2: the double2 form, A/B; identical results)
   // MOG2 model (kernel_mog2.h: tiles of ranked weights + fixed-slot records + rank->slot meta words)
   uint8_t* mog2_state = nullptr;
   int xcd_swizzle = 1;             // XCD-aware block order (kernel_mog2.h): 0 off, 1 model kernels (MOG2, MOG1, dp), 2 also the byte-stream kernels
@@ -222,6 +229,8 @@ void kde_free(bgs_engine* e);  // engine_kde.h
 int kde_check(const bgs_params& p);
 void dp2_free(bgs_engine* e);  // engine_dp2.h
 int dp2_check(bgs_algo algo, const bgs_params& p);
+void lb_free(bgs_engine* e);  // engine_lb.h
+int lb_check(bgs_algo algo, const bgs_params& p);
 void vmm_free(VmmRange& v);  // below
 
 void lane_release(bgs_engine::Lane& ln) {  // whatever of a lane came to be (bgs_submit's set-up may have failed half-way)
@@ -251,6 +260,7 @@ void free_all(bgs_engine* e) {
     if ((void*)e->mog2_state == e->vmm.base) e->mog2_state = nullptr;
     if ((void*)e->mog1_state == e->vmm.base) e->mog1_state = nullptr;
     if ((void*)e->dp_state == e->vmm.base) e->dp_state = nullptr;
+    if ((void*)e->lb_model == e->vmm.base) e->lb_model = nullptr;
     vmm_free(e->vmm);
   }
   void* dev[] = {e->dp_state, e->gmg_rec, e->gmg_nfeat, e->bgstate, e->bgstate2, e->mog1_state, e->mog2_state, e->d_in, e->d_fg, e->d_bg};
@@ -266,6 +276,7 @@ void free_all(bgs_engine* e) {
   ss_free(e);
   kde_free(e);
   dp2_free(e);
+  lb_free(e);
   if (e->d_stat) (void)hipFree(e->d_stat), e->d_stat = nullptr;
   if (e->h_stat) (void)hipHostFree(e->h_stat), e->h_stat = nullptr;
   for (int i = 0; i < bgs_engine::kStatSlots; ++i) {
@@ -294,6 +305,7 @@ int check_params(bgs_algo algo, const bgs_params& p) {
   if (algo == BGS_DP_ADAPTIVE_MEDIAN && p.dp_sampling_rate == 0) return fail(BGS_ERR_UNSUPPORTED, "AdaptiveMedian samplingRate 0 (frame_num %% 0)");
   if (algo == BGS_KDE) return kde_check(p);
   if (algo == BGS_DP_PRATI_MEDIOD || algo == BGS_DP_TEXTURE) return dp2_check(algo, p);
+  if (algo >= BGS_LB_SIMPLE_GAUSSIAN && algo <= BGS_LB_FUZZY_ADAPTIVE_SOM) return lb_check(algo, p);
   return BGS_OK;
 }
 
@@ -541,6 +553,7 @@ int mog2_allocate(bgs_engine* e) {
 #include "engine_dp.h"
 #include "engine_kde.h"
 #include "engine_dp2.h"
+#include "engine_lb.h"
 
 // (Re)build ABL's lookup table for the current alpha on e->stream.  Called when the geometry is set and when bgs_set_params
 // changes alpha; both drain the device first / the stream after, so no launch on any stream sees a half-written table.
@@ -599,7 +612,12 @@ int allocate(bgs_engine* e, int rows, int cols, int ch) {
     case BGS_DP_ADAPTIVE_MEDIAN: e->state_ch = 3; break;  // bgstate = the median image
     case BGS_KDE:
     case BGS_DP_PRATI_MEDIOD:
-    case BGS_DP_TEXTURE: break;
+    case BGS_DP_TEXTURE:
+    case BGS_LB_SIMPLE_GAUSSIAN:
+    case BGS_LB_FUZZY_GAUSSIAN:
+    case BGS_LB_MOG:
+    case BGS_LB_ADAPTIVE_SOM:
+    case BGS_LB_FUZZY_ADAPTIVE_SOM: break;
     default: return fail(BGS_ERR_UNSUPPORTED, "algorithm %d is not implemented in this build", (int)e->algo);
   }
   for (int i = 0; i < e->nring; ++i) DMALLOC(e->ring[i], fb);
@@ -652,6 +670,10 @@ int allocate(bgs_engine* e, int rows, int cols, int ch) {
   }
   if (is_dp2(e->algo)) {
     int rc = dp2_allocate(e);
+    if (rc) return rc;
+  }
+  if (is_lb(e->algo)) {
+    int rc = lb_allocate(e);
     if (rc) return rc;
   }
   // Whatever allocation enqueued on e->stream (statistics counters, poison fills) is complete before the caller's first
@@ -781,6 +803,11 @@ uint64_t launch_key(const bgs_engine* e, int i) {
     case BGS_KDE: return kde_key(e, i);
     case BGS_DP_PRATI_MEDIOD:
     case BGS_DP_TEXTURE: return dp2_key(e, i);
+    case BGS_LB_SIMPLE_GAUSSIAN:
+    case BGS_LB_FUZZY_GAUSSIAN:
+    case BGS_LB_MOG:
+    case BGS_LB_ADAPTIVE_SOM:
+    case BGS_LB_FUZZY_ADAPTIVE_SOM: return lb_key(e, i);
     default: return (uint64_t)t | (uint64_t)(e->ss ? e->ss->pp[i] & 1 : 0) << 62;  // SuBSENSE / LOBSTER: the frame index itself goes into the kernels (counter-based random draws); + which half of the ping-pong maps is current
   }
 }
@@ -1130,6 +1157,15 @@ int process_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, ui
       if (rc) return rc;
       break;
     }
+    case BGS_LB_SIMPLE_GAUSSIAN:
+    case BGS_LB_FUZZY_GAUSSIAN:
+    case BGS_LB_MOG:
+    case BGS_LB_ADAPTIVE_SOM:
+    case BGS_LB_FUZZY_ADAPTIVE_SOM: {
+      int rc = lb_run(e, first, count, d_frames, d_fg, d_bg, d_bits, s, &flags);
+      if (rc) return rc;
+      break;
+    }
     default: return fail(BGS_ERR_UNSUPPORTED, "algorithm %d is not implemented in this build", (int)e->algo);
   }
   HIP_TRY(hipGetLastError());
@@ -1348,7 +1384,7 @@ const char* bgs_last_error(void) { return g_err.c_str(); }
 
 int bgs_default_params(bgs_algo algo, bgs_params* p) {
   if (!p) return fail(BGS_ERR_INVALID, "params is NULL");
-  if ((int)algo < 0 || algo >= BGS_ALGO_COUNT) return fail(BGS_ERR_INVALID, "unknown algorithm %d", (int)algo);
+  if ((int)algo < 0 || algo >= BGS_ALGO_END) return fail(BGS_ERR_INVALID, "unknown algorithm %d", (int)algo);
   std::memset(p, 0, sizeof(*p));
   p->struct_size = (uint32_t)sizeof(*p);
   p->enable_threshold = 1;
@@ -1415,6 +1451,16 @@ int bgs_default_params(bgs_algo algo, bgs_params* p) {
     case BGS_DP_PRATI_MEDIOD:  // DPPratiMediodBGS.cpp:19, :98-104 (dp_history_size / dp_weight stay zero for every other algorithm)
       p->dp_threshold = 30.0f, p->dp_sampling_rate = 5, p->dp_history_size = 16, p->dp_weight = 5;
       break;
+    // package_bgs/lb wrappers, LB*.cpp:19-20 (the lb_* fields stay zero for every other algorithm)
+    case BGS_LB_SIMPLE_GAUSSIAN: p->lb_sensitivity = 66, p->lb_noise_variance = 162, p->lb_learning_rate = 18; break;
+    case BGS_LB_FUZZY_GAUSSIAN: p->lb_sensitivity = 72, p->lb_bg_threshold = 162, p->lb_learning_rate = 49, p->lb_noise_variance = 195; break;
+    case BGS_LB_MOG: p->lb_sensitivity = 81, p->lb_bg_threshold = 83, p->lb_learning_rate = 59, p->lb_noise_variance = 206; break;
+    case BGS_LB_ADAPTIVE_SOM:
+      p->lb_sensitivity = 75, p->lb_training_sensitivity = 245, p->lb_learning_rate = 62, p->lb_training_learning_rate = 255, p->lb_training_steps = 55;
+      break;
+    case BGS_LB_FUZZY_ADAPTIVE_SOM:
+      p->lb_sensitivity = 90, p->lb_training_sensitivity = 240, p->lb_learning_rate = 38, p->lb_training_learning_rate = 255, p->lb_training_steps = 81;
+      break;
     default: break;
   }
   return BGS_OK;
@@ -1423,7 +1469,7 @@ int bgs_default_params(bgs_algo algo, bgs_params* p) {
 int bgs_create(bgs_algo algo, const bgs_params* params, int hip_device, int n_streams, bgs_engine** out) {
   if (!out) return fail(BGS_ERR_INVALID, "out is NULL");
   *out = nullptr;
-  if ((int)algo < 0 || algo >= BGS_ALGO_COUNT) return fail(BGS_ERR_INVALID, "unknown algorithm %d", (int)algo);
+  if ((int)algo < 0 || algo >= BGS_ALGO_END) return fail(BGS_ERR_INVALID, "unknown algorithm %d", (int)algo);
   if (n_streams < 1) return fail(BGS_ERR_INVALID, "n_streams must be >= 1");
   if (params && params->struct_size != sizeof(bgs_params)) return fail(BGS_ERR_INVALID, "bgs_params.struct_size %u != %zu (ABI mismatch)", params->struct_size, sizeof(bgs_params));
   bgs_engine* e = new (std::nothrow) bgs_engine();
@@ -1459,6 +1505,7 @@ int bgs_create(bgs_algo algo, const bgs_params* params, int hip_device, int n_st
   e->kde.assign(n_streams, bgs_engine::KdeStream());
   if (const char* env = getenv("BGS_KDE_TRIPS")) e->kde_count_trips = atoi(env) != 0;
   if (const char* env = getenv("BGS_MOG2_COMPLETE")) e->mog2_complete = atoi(env) != 0;
+  if (const char* env = getenv("BGS_LB_PX")) e->lb_px = atoi(env) == 2 ? 2 : 1;
   if (const char* env = getenv("BGS_XCD_SWIZZLE")) e->xcd_swizzle = atoi(env);
   if (const char* env = getenv("BGS_MOG2_SPARSE")) e->mog2_sparse = atoi(env);
   if (const char* env = getenv("BGS_MODEL_CHUNK_MB")) e->model_chunk_mb = atoi(env);
@@ -1900,6 +1947,7 @@ int64_t bgs_get_state(bgs_engine* e, int stream, const char* plane, void* dst, s
   }
   if ((e->algo == BGS_SUBSENSE || e->algo == BGS_LOBSTER) && e->ss) return ss_get_state(e, stream, plane, dst, cap);
   if (e->algo == BGS_KDE && e->kde_samples) return kde_get_state(e, stream, plane, dst, cap);
+  if (is_lb(e->algo) && e->lb_model) return lb_get_state(e, stream, plane, dst, cap);
   if ((e->algo == BGS_DP_PRATI_MEDIOD && e->pm_samples) || (e->algo == BGS_DP_TEXTURE && e->tex_r)) return dp2_get_state(e, stream, plane, dst, cap);
   if (is_dp(e->algo)) {  // planes are stored canonically: [stream][plane][n]
     const int planes = dp_planes_of(e);
@@ -1987,6 +2035,7 @@ int bgs_reset_stream(bgs_engine* e, int stream) {
   if (stream < 0 || stream >= e->S) return fail(BGS_ERR_INVALID, "stream %d outside 0..%d", stream, e->S - 1);
   e->seen[stream] = 0, e->counter[stream] = 0, e->last_flags[stream] = 0;
   if (!e->kde.empty()) e->kde[stream] = bgs_engine::KdeStream();
+  if (!e->lb_mk.empty()) e->lb_mk[stream] = 0;
   if (e->last_fg_stream == stream) e->last_fg_stream = -1;
   return BGS_OK;
 }

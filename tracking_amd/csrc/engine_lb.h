@@ -1,0 +1,228 @@
+// engine_lb.h — host side of the five package_bgs/lb/ classes (BGS_LB_*): checks, the 0..255 -> double parameter mapping, model
+// allocation, the per-stream schedule and the state export.  Included by bgs_hip.hip inside its anonymous namespace; kernels in
+// kernel_lb.h.
+//
+// The wrappers (LB*.cpp:31-74) re-read their XML and call setBGModelParameter(id, 0..255) on every frame, after InitModel on the
+// first one: Init() therefore sees the constructor's m_noise (50), and every Update() - the first included - the XML's values.
+// The SOMs' training counter m_K is the model object's own state (restarted by Init, advanced by Update while m_K <= m_TSteps, and
+// m_TSteps may change between frames), so it is kept per stream here and not derived from bgs_engine::seen.
+
+bool is_lb(bgs_algo a) { return a >= BGS_LB_SIMPLE_GAUSSIAN && a <= BGS_LB_FUZZY_ADAPTIVE_SOM; }
+bool is_lb_som(bgs_algo a) { return a == BGS_LB_ADAPTIVE_SOM || a == BGS_LB_FUZZY_ADAPTIVE_SOM; }
+
+const char* lb_name(bgs_algo a) {
+  switch (a) {
+    case BGS_LB_SIMPLE_GAUSSIAN: return "LBSimpleGaussian";
+    case BGS_LB_FUZZY_GAUSSIAN: return "LBFuzzyGaussian";
+    case BGS_LB_MOG: return "LBMixtureOfGaussians";
+    case BGS_LB_ADAPTIVE_SOM: return "LBAdaptiveSOM";
+    default: return "LBFuzzyAdaptiveSOM";
+  }
+}
+
+int lb_planes_of(bgs_algo a) { return is_lb_som(a) ? bgs::kLbSomPlanes : a == BGS_LB_MOG ? bgs::kLbMogPlanes : bgs::kLbGaussPlanes; }
+
+// What the reference leaves undefined or order-dependent is refused.
+int lb_check(bgs_algo algo, const bgs_params& p) {
+  const char* nm = lb_name(algo);
+  const struct { const char* key; int v; } all[] = {{"sensitivity", p.lb_sensitivity}, {"bgThreshold", p.lb_bg_threshold}, {"learningRate", p.lb_learning_rate},
+      {"noiseVariance", p.lb_noise_variance}, {"trainingSensitivity", p.lb_training_sensitivity}, {"trainingLearningRate", p.lb_training_learning_rate},
+      {"trainingSteps", p.lb_training_steps}};
+  for (const auto& f : all)
+    if (f.v < 0 || f.v > 255) return fail(BGS_ERR_UNSUPPORTED, "%s %s must be 0..255 (setBGModelParameter's range), got %d", nm, f.key, f.v);
+  if (!is_lb_som(algo) && p.lb_noise_variance == 0) return fail(BGS_ERR_UNSUPPORTED, "%s noiseVariance 0: the variances reach 0 and the Mahalanobis distance divides by them", nm);
+  if (algo == BGS_LB_MOG && p.lb_bg_threshold == 255)
+    return fail(BGS_ERR_UNSUPPORTED, "%s bgThreshold 255: m_T = 1 may never be exceeded and the reference then reads kBG uninitialised (BGModelMog.cpp:146)", nm);
+  if (is_lb_som(algo) && p.lb_training_steps == 0) return fail(BGS_ERR_UNSUPPORTED, "%s trainingSteps 0: alpha is 0 / 0 at m_K = 0 (BGModelSom.cpp:194)", nm);
+  return BGS_OK;
+}
+
+// setBGModelParameter of the five models, in double and in the reference's order of operations
+struct LbModelParams {
+  double threshold, noise, alpha, bg_threshold;            // Gaussians, MoG
+  double eps1, eps2, alpha1, alpha2;                       // SOMs
+  int tsteps;
+};
+
+LbModelParams lb_model_params(bgs_algo algo, const bgs_params& p) {
+  auto dv = [](int v) { return (double)v / 255.0; };
+  LbModelParams m{};
+  double d = dv(p.lb_sensitivity);
+  m.threshold = 100.0 * d * d;
+  m.eps2 = 255.0 * 255.0 * d * d * d * d;
+  d = dv(p.lb_training_sensitivity);
+  m.eps1 = 255.0 * 255.0 * d * d * d * d;
+  d = dv(p.lb_noise_variance);
+  m.noise = 100.0 * d;
+  d = dv(p.lb_learning_rate);
+  m.alpha = d * d * d;
+  const double wmax = 4.0;  // the largest entry of the 3 x 3 Pascal kernel (BGModelSom.cpp:77-99)
+  m.alpha2 = d * d * d / wmax;
+  d = dv(p.lb_training_learning_rate);
+  m.alpha1 = d * d * d / wmax;
+  m.bg_threshold = dv(p.lb_bg_threshold);
+  d = dv(p.lb_training_steps);
+  m.tsteps = (int)(255.0 * d);
+  (void)algo;
+  return m;
+}
+
+uint64_t lb_key(const bgs_engine* e, int i) { return e->seen[i] == 0; }
+
+int lb_allocate(bgs_engine* e) {
+  if (e->ch != 3) return fail(BGS_ERR_UNSUPPORTED, "%s reads 3-channel frames only (BGModel::InitModel copies into an 8UC3 image, lb/BGModel.cpp:72)", lb_name(e->algo));
+  const size_t n = e->n, S = (size_t)e->S;
+  if (n * S >= (size_t)1 << 31) return fail(BGS_ERR_INVALID, "lb: streams x pixels must stay below 2^31");
+  int rc = model_allocate(e, (void**)&e->lb_model, S * n * lb_planes_of(e->algo) * sizeof(double));
+  if (rc) return rc;
+  if (e->algo == BGS_LB_MOG) DMALLOC(e->lb_k, S * n * sizeof(int32_t));
+  if (is_lb_som(e->algo)) DMALLOC(e->lb_bg, S * n * 3);
+  e->lb_mk.assign(S, 0);
+  // Nothing is initialised here: a stream's first frame builds its model inside the launch (LbArgs::init)
+  return BGS_OK;
+}
+
+void lb_free(bgs_engine* e) {
+  if (e->lb_model) (void)hipFree(e->lb_model);  // free_all has already dropped a model built from chunks
+  if (e->lb_k) (void)hipFree(e->lb_k);
+  if (e->lb_bg) (void)hipFree(e->lb_bg);
+  e->lb_model = nullptr, e->lb_k = nullptr, e->lb_bg = nullptr;
+}
+
+// One frame of LB*::process for streams [first, first+count), which share lb_key.
+int lb_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
+  const size_t n = e->n;
+  const int P = lb_planes_of(e->algo);
+  const LbModelParams mp = lb_model_params(e->algo, e->p);
+  bgs::LbArgs a{};
+  a.n = (uint32_t)n, a.init = e->seen[first] == 0;
+  a.threshold = mp.threshold, a.noise = mp.noise, a.noise0 = 50.0, a.alpha = mp.alpha, a.bg_threshold = mp.bg_threshold;
+  auto slab = [&](int f, int c) {  // arguments of streams [f, f + c)
+    const size_t o = (size_t)(f - first) * n;
+    a.cur = d_frames + o * 3, a.fg = d_fg ? d_fg + o : nullptr, a.bg = d_bg ? d_bg + o * 3 : nullptr;
+    a.fg_bits = d_bits ? d_bits + o / 64 : nullptr;
+    a.model = e->lb_model + (size_t)f * P * n;
+    a.k = e->lb_k ? e->lb_k + (size_t)f * n : nullptr, a.bgplane = e->lb_bg ? e->lb_bg + (size_t)f * n * 3 : nullptr;
+    a.npix = (uint32_t)(n * c);
+  };
+  if (!is_lb_som(e->algo)) {
+    slab(first, count);
+    const size_t npix = a.npix;
+    if (e->algo == BGS_LB_MOG) {
+      Timed tm(e, s, "lb_mog_kernel");
+      hipLaunchKernelGGL(bgs::lb_mog_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, a);
+    } else {
+      const bool fuzzy = e->algo == BGS_LB_FUZZY_GAUSSIAN;
+      const bool two = e->lb_px == 2 && n % 2 == 0;  // pairs of pixels never straddle two streams then, and every double2 is aligned
+      Timed tm(e, s, fuzzy ? "lb_fuzzy_gauss_kernel" : "lb_gauss_kernel");
+      if (two) {
+        if (fuzzy)
+          hipLaunchKernelGGL((bgs::lb_gauss_kernel<true, 2>), dim3(blocks_for(npix / 2)), dim3(bgs::kBlock), 0, s, a);
+        else
+          hipLaunchKernelGGL((bgs::lb_gauss_kernel<false, 2>), dim3(blocks_for(npix / 2)), dim3(bgs::kBlock), 0, s, a);
+      } else {
+        if (fuzzy)
+          hipLaunchKernelGGL((bgs::lb_gauss_kernel<true, 1>), dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, a);
+        else
+          hipLaunchKernelGGL((bgs::lb_gauss_kernel<false, 1>), dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, a);
+      }
+    }
+  } else {
+    // BGModelSom::Update's phase test, per stream: calibration while m_K <= m_TSteps (frame 1 counts), alpha with the integers
+    // promoted to double.  Streams whose counters differ get their own table entry in the same launch.
+    std::vector<double> al(count), ep(count);
+    bool same = true;
+    for (int i = 0; i < count; ++i) {
+      int& mk = e->lb_mk[first + i];
+      if (a.init) mk = 0;
+      if (mk <= mp.tsteps) {
+        ep[i] = mp.eps1, al[i] = mp.alpha1 - (double)mk * (mp.alpha1 - mp.alpha2) / (double)mp.tsteps;
+        ++mk;
+      } else {
+        ep[i] = mp.eps2, al[i] = mp.alpha2;
+      }
+      same = same && al[i] == al[0] && ep[i] == ep[0];
+    }
+    const bool fuzzy = e->algo == BGS_LB_FUZZY_ADAPTIVE_SOM;
+    for (int f = 0; f < count; f += same ? count : bgs::kLbTable) {
+      const int c = same ? count : std::min(bgs::kLbTable, count - f);
+      slab(first + f, c);
+      a.uniform = same, a.bps = (uint32_t)blocks_for(n);
+      const dim3 grid(a.bps * (unsigned)c);
+      for (int i = 0; i < (same ? 1 : c); ++i) a.alpha_s[i] = al[f + i], a.eps_s[i] = ep[f + i];
+      Timed tm(e, s, fuzzy ? "lb_fuzzy_som_kernel" : "lb_som_kernel");
+      if (fuzzy)
+        hipLaunchKernelGGL(bgs::lb_som_kernel<true>, grid, dim3(bgs::kBlock), 0, s, a);
+      else
+        hipLaunchKernelGGL(bgs::lb_som_kernel<false>, grid, dim3(bgs::kBlock), 0, s, a);
+    }
+  }
+  *flags = BGS_FG_VALID | BGS_BG_VALID;
+  return BGS_OK;
+}
+
+// bgs_get_state planes (include/bgs_hip.h), in the reference's memory order.
+int64_t lb_get_state(bgs_engine* e, int stream, const char* plane, void* dst, size_t cap) {
+  const size_t n = e->n;
+  const int P = lb_planes_of(e->algo);
+  auto need = [&](size_t bytes) { return cap < bytes ? fail(BGS_ERR_STATE, "buffer too small for plane %s", plane) : 0; };
+  if (is_lb_som(e->algo) && !strcmp(plane, "count")) {
+    if (need(8)) return BGS_ERR_STATE;
+    const int64_t v = e->lb_mk[stream];
+    memcpy(dst, &v, 8);
+    return 8;
+  }
+  if (is_lb_som(e->algo) && !strcmp(plane, "bg")) {
+    if (need(n * 3)) return BGS_ERR_STATE;
+    if (d2h_staged(dst, e->lb_bg + (size_t)stream * n * 3, n * 3)) return fail(BGS_ERR_HIP, "hipMemcpy failed");
+    return (int64_t)(n * 3);
+  }
+  std::vector<int32_t> K;
+  if (e->algo == BGS_LB_MOG) {
+    K.resize(n);
+    if (d2h_staged(K.data(), e->lb_k + (size_t)stream * n, n * 4)) return fail(BGS_ERR_HIP, "hipMemcpy failed");
+    if (!strcmp(plane, "k")) {
+      if (need(n * 4)) return BGS_ERR_STATE;
+      memcpy(dst, K.data(), n * 4);
+      return (int64_t)(n * 4);
+    }
+  }
+  std::vector<double> m((size_t)P * n);
+  if (d2h_staged(m.data(), e->lb_model + (size_t)stream * P * n, m.size() * 8)) return fail(BGS_ERR_HIP, "hipMemcpy failed");
+  double* o = (double*)dst;
+  if (is_lb_som(e->algo) && !strcmp(plane, "som")) {
+    if (need(n * 27 * 8)) return BGS_ERR_STATE;
+    for (size_t i = 0; i < n; ++i)
+      for (int j = 0; j < 27; ++j) o[i * 27 + j] = m[(size_t)j * n + i];
+    return (int64_t)(n * 27 * 8);
+  }
+  const bool mu = !strcmp(plane, "mu"), var = !strcmp(plane, "var");
+  if ((e->algo == BGS_LB_SIMPLE_GAUSSIAN || e->algo == BGS_LB_FUZZY_GAUSSIAN) && (mu || var)) {
+    if (need(n * 24)) return BGS_ERR_STATE;
+    for (size_t i = 0; i < n; ++i)
+      for (int c = 0; c < 3; ++c) o[i * 3 + c] = m[(size_t)((mu ? 0 : 3) + c) * n + i];
+    return (int64_t)(n * 24);
+  }
+  if (e->algo == BGS_LB_MOG) {
+    auto at = [&](int k, int f, size_t i) { return k < K[i] ? m[(size_t)(7 * k + f) * n + i] : 0.0; };  // slots >= K: the constructor's zeros
+    if (mu || var) {
+      if (need(n * 72)) return BGS_ERR_STATE;
+      for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 3; ++k)
+          for (int c = 0; c < 3; ++c) o[(i * 3 + k) * 3 + c] = at(k, (mu ? 1 : 4) + c, i);
+      return (int64_t)(n * 72);
+    }
+    const bool w = !strcmp(plane, "w"), key = !strcmp(plane, "sortkey");
+    if (w || key) {
+      if (need(n * 24)) return BGS_ERR_STATE;
+      for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 3; ++k) {
+          double v = at(k, 0, i);
+          if (key && k < K[i]) v = v / std::sqrt(at(k, 6, i) + at(k, 5, i) + at(k, 4, i));  // Red + Green + Blue
+          o[i * 3 + k] = v;
+        }
+      return (int64_t)(n * 24);
+    }
+  }
+  return fail(BGS_ERR_STATE, "unknown state plane '%s' for algorithm %d", plane, (int)e->algo);
+}

@@ -20,6 +20,11 @@ FrameProcessor::FrameProcessor()
   wrenGA = nullptr, enableDPWrenGABGS = false;
   pratiMediod = nullptr, enableDPPratiMediodBGS = false;
   textureBGS = nullptr, enableDPTextureBGS = false;
+  lbSimpleGaussian = nullptr, enableLBSimpleGaussian = false;
+  lbFuzzyGaussian = nullptr, enableLBFuzzyGaussian = false;
+  lbMixtureOfGaussians = nullptr, enableLBMixtureOfGaussians = false;
+  lbAdaptiveSOM = nullptr, enableLBAdaptiveSOM = false;
+  lbFuzzyAdaptiveSOM = nullptr, enableLBFuzzyAdaptiveSOM = false;
   kde = nullptr, enableKDE = false;
   sdbgs = nullptr, enableSigmaDeltaBGS = false;
   ssbgs = nullptr, enableSuBSENSEBGS = false;
@@ -49,6 +54,11 @@ void FrameProcessor::init() {  // FrameProcessor.cpp:35-155
   if (enableDPWrenGABGS) wrenGA = new DPWrenGABGS;
   if (enableDPPratiMediodBGS) pratiMediod = new DPPratiMediodBGS;  // :81-88 (DPEigenbackgroundBGS between them is not built)
   if (enableDPTextureBGS) textureBGS = new DPTextureBGS;
+  if (enableLBSimpleGaussian) lbSimpleGaussian = new LBSimpleGaussian;  // :108-122
+  if (enableLBFuzzyGaussian) lbFuzzyGaussian = new LBFuzzyGaussian;
+  if (enableLBMixtureOfGaussians) lbMixtureOfGaussians = new LBMixtureOfGaussians;
+  if (enableLBAdaptiveSOM) lbAdaptiveSOM = new LBAdaptiveSOM;
+  if (enableLBFuzzyAdaptiveSOM) lbFuzzyAdaptiveSOM = new LBFuzzyAdaptiveSOM;
   if (enableKDE) kde = new KDE;  // after VuMeter, before IMBS (:135)
   if (enableSigmaDeltaBGS) sdbgs = new SigmaDeltaBGS;
   if (enableSuBSENSEBGS) ssbgs = new SuBSENSEBGS;
@@ -117,6 +127,11 @@ void FrameProcessor::process(const Image& img_input) {  // :169-340
   if (enableDPWrenGABGS) process("DPWrenGABGS", wrenGA, img_prep, img_wrenga);
   if (enableDPPratiMediodBGS) process("DPPratiMediodBGS", pratiMediod, img_prep, img_pramed);  // :217-224
   if (enableDPTextureBGS) process("DPTextureBGS", textureBGS, img_prep, img_texbgs);
+  if (enableLBSimpleGaussian) process("LBSimpleGaussian", lbSimpleGaussian, img_prep, img_lb_sg);  // :244-257
+  if (enableLBFuzzyGaussian) process("LBFuzzyGaussian", lbFuzzyGaussian, img_prep, img_lb_fg);
+  if (enableLBMixtureOfGaussians) process("LBMixtureOfGaussians", lbMixtureOfGaussians, img_prep, img_lb_mog);
+  if (enableLBAdaptiveSOM) process("LBAdaptiveSOM", lbAdaptiveSOM, img_prep, img_lb_som);
+  if (enableLBFuzzyAdaptiveSOM) process("LBFuzzyAdaptiveSOM", lbFuzzyAdaptiveSOM, img_prep, img_lb_fsom);
   if (enableKDE) process("KDE", kde, img_prep, img_kde);  // :275
   if (enableSigmaDeltaBGS) process("SigmaDeltaBGS", sdbgs, img_prep, img_sdbgs);
   if (enableSuBSENSEBGS) process("SuBSENSEBGS", ssbgs, img_prep, img_ssbgs);
@@ -132,6 +147,11 @@ void FrameProcessor::finish() {  // :342-482 (reverse order of init)
   delete ssbgs, ssbgs = nullptr;
   delete sdbgs, sdbgs = nullptr;
   delete kde, kde = nullptr;
+  delete lbFuzzyAdaptiveSOM, lbFuzzyAdaptiveSOM = nullptr;
+  delete lbAdaptiveSOM, lbAdaptiveSOM = nullptr;
+  delete lbMixtureOfGaussians, lbMixtureOfGaussians = nullptr;
+  delete lbFuzzyGaussian, lbFuzzyGaussian = nullptr;
+  delete lbSimpleGaussian, lbSimpleGaussian = nullptr;
   delete textureBGS, textureBGS = nullptr;
   delete pratiMediod, pratiMediod = nullptr;
   delete wrenGA, wrenGA = nullptr;
@@ -182,6 +202,11 @@ void FrameProcessor::saveConfig() {  // :496-552 (keys of the classes this build
   fs.writeInt("enableDPWrenGABGS", enableDPWrenGABGS);
   fs.writeInt("enableDPPratiMediodBGS", enableDPPratiMediodBGS);  // :522-524
   fs.writeInt("enableDPTextureBGS", enableDPTextureBGS);
+  fs.writeInt("enableLBSimpleGaussian", enableLBSimpleGaussian);  // :533-537
+  fs.writeInt("enableLBFuzzyGaussian", enableLBFuzzyGaussian);
+  fs.writeInt("enableLBMixtureOfGaussians", enableLBMixtureOfGaussians);
+  fs.writeInt("enableLBAdaptiveSOM", enableLBAdaptiveSOM);
+  fs.writeInt("enableLBFuzzyAdaptiveSOM", enableLBFuzzyAdaptiveSOM);
   fs.writeInt("enableKDE", enableKDE);  // :544
   fs.writeInt("enableSigmaDeltaBGS", enableSigmaDeltaBGS);
   fs.writeInt("enableSuBSENSEBGS", enableSuBSENSEBGS);
@@ -210,6 +235,11 @@ void FrameProcessor::loadConfig() {  // :554-610 (defaults: PreProcessor and Fra
   enableDPWrenGABGS = fs.readInt("enableDPWrenGABGS", false);
   enableDPPratiMediodBGS = fs.readInt("enableDPPratiMediodBGS", false);  // :580-582
   enableDPTextureBGS = fs.readInt("enableDPTextureBGS", false);
+  enableLBSimpleGaussian = fs.readInt("enableLBSimpleGaussian", false);  // :591-595
+  enableLBFuzzyGaussian = fs.readInt("enableLBFuzzyGaussian", false);
+  enableLBMixtureOfGaussians = fs.readInt("enableLBMixtureOfGaussians", false);
+  enableLBAdaptiveSOM = fs.readInt("enableLBAdaptiveSOM", false);
+  enableLBFuzzyAdaptiveSOM = fs.readInt("enableLBFuzzyAdaptiveSOM", false);
   enableKDE = fs.readInt("enableKDE", false);  // :602
   enableSigmaDeltaBGS = fs.readInt("enableSigmaDeltaBGS", false);
   enableSuBSENSEBGS = fs.readInt("enableSuBSENSEBGS", false);

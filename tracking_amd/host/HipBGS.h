@@ -4,9 +4,9 @@
 //   hipbgs::FrameDifferenceBGS, StaticFrameDifferenceBGS, WeightedMovingMeanBGS, WeightedMovingVarianceBGS,
 //   AdaptiveBackgroundLearning, AdaptiveSelectiveBackgroundLearning, MixtureOfGaussianV1BGS, MixtureOfGaussianV2BGS, GMG,
 //   SigmaDeltaBGS, SuBSENSEBGS, LOBSTERBGS, DPZivkovicAGMMBGS, DPGrimsonGMMBGS, DPWrenGABGS, DPMeanBGS, DPAdaptiveMedianBGS, KDE,
-//   DPPratiMediodBGS, DPTextureBGS
+//   DPPratiMediodBGS, DPTextureBGS, LBSimpleGaussian, LBFuzzyGaussian, LBMixtureOfGaussians, LBAdaptiveSOM, LBFuzzyAdaptiveSOM
 // Each reads / writes the same ./config/<Class>.xml with the same keys and defaults as the class it stands in for
-// (the list is bgs_classes.inc + bgs_classes_kde.inc + bgs_classes_dp2.inc, shared verbatim with this repository's tested host mirror, tracking_amd/host/bgs_host.h).
+// (the list is bgs_classes.inc + bgs_classes_kde.inc + bgs_classes_dp2.inc + bgs_classes_lb.inc, shared verbatim with this repository's tested host mirror, tracking_amd/host/bgs_host.h).
 //
 // Use:   mixtureOfGaussianV2BGS = new hipbgs::MixtureOfGaussianV2BGS;      // FrameProcessor.cpp:59-60
 //        if(i==36) bgs = new hipbgs::SuBSENSEBGS();                          // ustc_src/ustc_bgs.cpp:68
@@ -89,7 +89,16 @@ class HipBGSBase : public IBGS {
     uint32_t flags = 0;
     if (bgs_process(engine_, 0, img_input.data, img_input.rows, img_input.cols, img_input.channels(), img_input.step, fg_.data, fg_.step, bg_.data, bg_.step, &flags))
       fail();
-    if (flags & BGS_FG_VALID) fg_.copyTo(img_output);  // img_foreground.copyTo(img_output)
+    if ((flags & BGS_FG_VALID) && fg_channels_ == 3) {  // the lb/ wrappers return cv::Mat(m_pBGModel->GetFG()): 8UC3, equal channels
+      img_output.create(fg_.size(), CV_8UC3);
+      for (int y = 0; y < fg_.rows; ++y) {
+        const uchar* s = fg_.data + (size_t)y * fg_.step;
+        uchar* d = img_output.data + (size_t)y * img_output.step;
+        for (int x = 0; x < fg_.cols; ++x) d[3 * x] = d[3 * x + 1] = d[3 * x + 2] = s[x];
+      }
+    } else if (flags & BGS_FG_VALID) {
+      fg_.copyTo(img_output);  // img_foreground.copyTo(img_output)
+    }
     if (flags & BGS_BG_VALID)
       bg_.copyTo(img_bgmodel);  // img_background.copyTo(img_bgmodel)
     else if (clears_bg_)
@@ -113,7 +122,7 @@ class HipBGSBase : public IBGS {
   }
 
  protected:
-  HipBGSBase(bgs_algo algo, const char* name, bool clears_bg = false) : firstTime(true), algo_(algo), name_(name), clears_bg_(clears_bg), device_(0), engine_(0) {
+  HipBGSBase(bgs_algo algo, const char* name, bool clears_bg = false) : firstTime(true), fg_channels_(1), algo_(algo), name_(name), clears_bg_(clears_bg), device_(0), engine_(0) {
     params_ = bgs_params();
     params_.struct_size = sizeof(params_);
     bgs_default_params(algo, &params_);
@@ -122,6 +131,7 @@ class HipBGSBase : public IBGS {
   std::string configPath() const { return std::string("./config/") + name_ + ".xml"; }
   bool firstTime;
   bgs_params params_;
+  int fg_channels_;  // 3: the class hands its caller an 8UC3 mask with equal channels (bgs_classes_lb.inc)
 
  private:
   virtual void saveConfig() = 0;  // private pure virtuals of IBGS, re-declared so process() above may call them
@@ -144,6 +154,7 @@ class HipBGSBase : public IBGS {
 #include "bgs_classes.inc"
 #include "bgs_classes_kde.inc"
 #include "bgs_classes_dp2.inc"
+#include "bgs_classes_lb.inc"
 #ifdef BGS_HIP_DEFINED_OVERRIDE
 #undef override
 #undef BGS_HIP_DEFINED_OVERRIDE

@@ -52,6 +52,11 @@ class HipFGDetector : public CvFGDetector {
     if (i == 13) bgs = new hipbgs::DPWrenGABGS;
     if (i == 14) bgs = new hipbgs::DPPratiMediodBGS;
     if (i == 16) bgs = new hipbgs::DPTextureBGS;
+    if (i == 25) bgs = new hipbgs::LBSimpleGaussian;
+    if (i == 26) bgs = new hipbgs::LBFuzzyGaussian;
+    if (i == 27) bgs = new hipbgs::LBMixtureOfGaussians;
+    if (i == 28) bgs = new hipbgs::LBAdaptiveSOM;
+    if (i == 29) bgs = new hipbgs::LBFuzzyAdaptiveSOM;
     if (i == 32) bgs = new hipbgs::KDE;
     if (i == 35) bgs = new hipbgs::SigmaDeltaBGS;
     if (i == 36) bgs = new hipbgs::SuBSENSEBGS();

@@ -240,6 +240,7 @@ class HipBGSBase : public IBGS {
   std::string configPath() const { return std::string("./config/") + name_ + ".xml"; }
   bool firstTime;
   bgs_params params_;
+  int fg_channels_ = 1;  // 3: the class hands its caller an 8UC3 mask with equal channels, like the reference's lb/ wrappers (bgs_classes_lb.inc)
 
  private:
   void saveConfig() override = 0;  // private pure virtuals of IBGS, re-declared so process() above may call them
@@ -255,7 +256,16 @@ class HipBGSBase : public IBGS {
   bool group_ready_ = false;
   uint32_t group_flags_ = 0;
   void deliver(uint32_t flags, Image& img_output, Image& img_bgmodel) {
-    if (flags & BGS_FG_VALID) fg_.copyTo(img_output);  // img_foreground.copyTo(img_output)
+    if ((flags & BGS_FG_VALID) && fg_channels_ == 3) {  // cv::Mat(m_pBGModel->GetFG()).copyTo(img_output): 8UC3, the mask byte in every channel
+      img_output.create(fg_.rows, fg_.cols, 3);
+      for (int y = 0; y < fg_.rows; ++y) {
+        const uint8_t* s = fg_.data + (size_t)y * fg_.step;
+        uint8_t* d = img_output.data + (size_t)y * img_output.step;
+        for (int x = 0; x < fg_.cols; ++x) d[3 * x] = d[3 * x + 1] = d[3 * x + 2] = s[x];
+      }
+    } else if (flags & BGS_FG_VALID) {
+      fg_.copyTo(img_output);  // img_foreground.copyTo(img_output)
+    }
     if (flags & BGS_BG_VALID)
       bg_.copyTo(img_bgmodel);  // img_background.copyTo(img_bgmodel)
     else if (clears_bg_)
@@ -270,6 +280,7 @@ class HipBGSBase : public IBGS {
 #include "bgs_classes.inc"
 #include "bgs_classes_kde.inc"
 #include "bgs_classes_dp2.inc"
+#include "bgs_classes_lb.inc"
 
 #undef BGS_HIP_BANNER_DTOR
 
