@@ -54,9 +54,12 @@ typedef enum bgs_algo {
   BGS_KDE = 18,              /* KDE::process (USTC_BGS type 32)    package_bgs/ae/KDE.cpp:34-96 */
   BGS_DP_PRATI_MEDIOD = 19,  /* DPPratiMediodBGS::process (USTC_BGS type 14) package_bgs/dp/DPPratiMediodBGS.cpp:29-81 */
   BGS_DP_TEXTURE = 20,       /* DPTextureBGS::process (USTC_BGS type 16)     package_bgs/dp/DPTextureBGS.cpp:39-134 */
-  /* BGS_ALGO_COUNT is FROZEN at 21: the CPU restatement the tests compare with bounds its defaults table with it, and the tests
-   * compile this header and pin its value, so it no longer counts the classes.  Ids added later are declared after it with explicit values
-   * (the first repeats the count's value, which C allows) and BGS_ALGO_END is the end marker every range check uses. */
+  /* THE ID SPACE.  Three names below are pinned by the tests with the values they had when they were introduced, and none of them may
+   * move again: BGS_ALGO_COUNT == 21 (the CPU restatement bounds its defaults table with it), BGS_ALGO_END == 26 (the end marker of
+   * the lb/ round) and "id 26 is not an algorithm".  So neither counts the classes, id 26 is a permanent hole, and the end marker
+   * every range check uses is BGS_ALGO_LIMIT, through BGS_ALGO_KNOWN() below.
+   * TO ADD A CLASS: declare it after the last one with an explicit value (the old BGS_ALGO_LIMIT), raise BGS_ALGO_LIMIT by one,
+   * and touch nothing else here - not BGS_ALGO_COUNT, not BGS_ALGO_END, not the hole. */
   BGS_ALGO_COUNT,
   /* Laurence Bender's package_bgs/lb/ models (3-channel frames only; double-precision per-pixel models; FG and BG from frame 1) */
   BGS_LB_SIMPLE_GAUSSIAN = 21,    /* LBSimpleGaussian::process (USTC_BGS type 25)     package_bgs/lb/LBSimpleGaussian.cpp:31-73 */
@@ -64,8 +67,13 @@ typedef enum bgs_algo {
   BGS_LB_MOG = 23,                /* LBMixtureOfGaussians::process (USTC_BGS type 27) package_bgs/lb/LBMixtureOfGaussians.cpp:31-74 */
   BGS_LB_ADAPTIVE_SOM = 24,       /* LBAdaptiveSOM::process (USTC_BGS type 28)        package_bgs/lb/LBAdaptiveSOM.cpp:31-74 */
   BGS_LB_FUZZY_ADAPTIVE_SOM = 25, /* LBFuzzyAdaptiveSOM::process (USTC_BGS type 29)   package_bgs/lb/LBFuzzyAdaptiveSOM.cpp:31-74 */
-  BGS_ALGO_END
+  BGS_ALGO_END,                   /* FROZEN at 26 (see above); id 26 itself is a hole */
+  BGS_VUMETER = 27,               /* VuMeter::process (USTC_BGS type 31)              package_bgs/av/VuMeter.cpp:33-86 */
+  BGS_ALGO_LIMIT = 28             /* one past the last id */
 } bgs_algo;
+
+/* "id is an algorithm": the one range check (bgs_default_params, bgs_create, bgs_node_create) */
+#define BGS_ALGO_KNOWN(id) (((int)(id) >= 0 && (int)(id) < 26) || ((int)(id) >= 27 && (int)(id) < (int)BGS_ALGO_LIMIT))
 
 typedef enum bgs_status {
   BGS_OK = 0,
@@ -209,6 +217,17 @@ typedef struct bgs_params {
   int32_t lb_training_sensitivity;
   int32_t lb_training_learning_rate;
   int32_t lb_training_steps;
+
+  /* VuMeter (package_bgs/av/VuMeter.cpp:19, :103-116).  bgs_default_params fills these for BGS_VUMETER only (zero for every other
+   * algorithm).  The wrapper hands binSize, alpha and threshold to its model once, on the first frame, through setters that REPLACE
+   * an out-of-range value instead of failing (binSize outside 1..254 -> 8, alpha / threshold outside (0,1) -> 0.995 / 0.03,
+   * TBackgroundVuMeter.h:47-54); the engine applies the same rules and keeps the three once the geometry is set.  vu_enable_filter
+   * (cv::erode 3x3 then cv::medianBlur 5 of the mask) is re-read every frame.  Mask and background image (1 channel: the gray
+   * background) are valid from frame 1; the mask of a stream's first four frames is zero.  1-channel frames: BGS_ERR_UNSUPPORTED. */
+  int32_t vu_bin_size;        /* 8     binSize: gray levels per histogram bin (binCount = 256 / binSize) */
+  int32_t vu_enable_filter;   /* 1     enableFilter */
+  double vu_alpha;            /* 0.995 alpha: every bin is scaled by it every frame */
+  double vu_threshold;        /* 0.03  threshold: a pixel whose bin is below it is foreground */
 } bgs_params;
 
 /* Largest dp_history_size the PratiMediod kernel is built for (every dist entry then fits in 16 bits: 64 x 255 < 65536). */
@@ -276,7 +295,7 @@ int bgs_set_geometry(bgs_engine* e, int rows, int cols, int channels);
  * One frame of one stream, host buffers (the IBGS::process call).
  *   in       rows x cols x channels uint8, interleaved (BGR), row stride in_step bytes (>= cols*channels)
  *   fg       rows x cols uint8 mask or NULL; written only if BGS_FG_VALID is reported
- *   bg       rows x cols x channels (ASBL: x1) uint8 or NULL; written only if BGS_BG_VALID
+ *   bg       rows x cols x channels (ASBL, VuMeter: x1) uint8 or NULL; written only if BGS_BG_VALID
  * in == NULL or rows*cols == 0 is the reference's `if(img_input.empty()) return;`:
  * returns BGS_OK with *out_flags = 0 and no state change.
  * Synchronous: the outputs are complete on return.
@@ -290,7 +309,7 @@ int bgs_process(bgs_engine* e, int stream, const uint8_t* in, int rows, int cols
  * roofline path: no PCIe traffic, one launch over streams x pixels.
  *   d_frames  [n_streams][rows][cols][channels] uint8, contiguous
  *   d_fg      [n_streams][rows][cols] uint8 or NULL
- *   d_bg      [n_streams][rows][cols][channels] uint8 or NULL
+ *   d_bg      [n_streams][rows][cols][channels] uint8 or NULL (ASBL, VuMeter: one channel)
  *   d_fg_bits [n_streams][W] uint64, W = ceil(rows*cols/64): bit i of word j of a stream = its pixel 64j+i is foreground; the bits of
  *             a stream's last word past pixel rows*cols-1 are zero; or NULL.  (rows*cols a multiple of 64 - 1080p, 4K, 720p, VGA,
  *             320x176 ... - is the fast case: the update kernels write the words from wave ballots; for any other size the words are
@@ -445,7 +464,9 @@ const char* bgs_last_error(void);
  * lb/ models, all f64 in the reference's memory order, colour fields in the byte order of the input pixel (B, G, R):
  * SimpleGaussian / FuzzyGaussian "mu", "var" f64 [n][3]; MixtureOfGaussians "w" f64 [n][3], "mu", "var" f64 [n][3][3] (pixel, slot,
  * colour), "sortkey" f64 [n][3], "k" int32 [n] (slots >= k read 0); AdaptiveSOM / FuzzyAdaptiveSOM "som" f64 [n][3][3][3] (pixel,
- * neuron row, neuron column, colour), "bg" u8 [n][3], "count" int64 [1] = the stream's training counter m_K. */
+ * neuron row, neuron column, colour), "bg" u8 [n][3], "count" int64 [1] = the stream's training counter m_K.
+ * VuMeter: "hist" f32 [binCount][n], the reference's dense histogram planes (whatever the engine keeps internally), "background"
+ * u8 [n], "count" int64 [1] = the stream's m_nCount. */
 
 /* LBSP 16-bit double-cross descriptors of a whole 8UC3 / 8UC1 image (LBSP.h:50-95,
  * LBSP_16bits_dbcross_{3ch3t,1ch}.i).  d_desc: [rows][cols][channels] uint16; the

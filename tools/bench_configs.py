@@ -7,6 +7,8 @@ Not the driver's bench line (bench.py is); the numbers go to DESIGN.md §6.
   --only dp2: DPPratiMediodBGS (sampled / other frames) and DPTextureBGS, 8 x 1080p
   --only lb: the five package_bgs/lb models (double-precision planes), static and ~10 % foreground scenes, SOMs inside and past their
              calibration phase, the Gaussian pair with one and two pixels per lane, 8 x 1080p  (lb_<class>: one class, short legs)
+  --only vumeter: VuMeter (package_bgs/av), dense and live-bin kernels (BGS_VU_SPARSE 0 / 1 / 2), filter on and off, on S_surv and on
+             fresh uniform noise (every bin live: the live-bin kernels' worst case), 8 x 1080p
 usage: bench_configs.py [--streams S] [--swizzle 0|1]"""
 import argparse
 import os
@@ -703,6 +705,73 @@ def run_lb(S=8, rows=1080, cols=1920, steps=30, only=None, px_variants=(2, 1), c
         torch.cuda.empty_cache()
 
 
+def run_vumeter(S=8, rows=1080, cols=1920, steps=30, age=60):
+    """VuMeter (reference defaults: 32 bins, alpha 0.995) at S x 1080p, byte mask + background image out, for the three kernel variants
+    in one process on the same frames: the model kernel's ms per step (HIP events around the launch, mean of `steps`) and the wall ms
+    per step with the post-filter off and on (erode + median: two more launches), after `age` frames.  Scenes: S_surv (tools/synth.py),
+    fresh uniform noise, where every bin of every pixel becomes live, and S_smooth (S_surv's boxes over a low-frequency background).  Bytes per pixel are the model's own accounting from the
+    histograms of stream 0 after the run: L = live bins per pixel, U = bins live in at least one of a wave's 64 pixels (U16: of
+    16 consecutive pixels, one 64-byte sector of a plane);
+      dense 3 + 128 + 128 + 4;  live-bin 3 + 4 L + 4 U + 8 (bitmap) + 4;  live-bin, masked stores 3 + 4 L + 4 L + 8 + 4
+    (the 4: background byte read and written, background image, mask).  `copy_frac` is that figure's rate over this process's
+    float4 copy rate."""
+    dev = torch.device("cuda", 0)
+    px = S * rows * cols
+    T = 12
+    copy = capi.calibrate_copy(0, 2 << 30, 0)
+    fg = torch.empty((S, rows, cols), dtype=torch.uint8, device=dev)
+    bg = torch.empty((S, rows, cols), dtype=torch.uint8, device=dev)
+    g = torch.Generator(device=dev)
+    g.manual_seed(5)
+    for label in ("S_surv", "uniform noise", "S_smooth"):
+        if label == "S_surv":
+            pool = synth.SurvStreams(S, rows, cols, seed0=4321, device=dev).pool(T)
+        elif label == "S_smooth":  # not asked of the class; shows what the live-bin kernels gain when neighbours share bins
+            pool = torch.stack([synth.s_smooth(T, rows, cols, seed=777 + k, device=dev) for k in range(S)], 1)
+        else:
+            pool = torch.randint(0, 256, (T, S, rows, cols, 3), generator=g, device=dev, dtype=torch.uint8)
+        for mode, name in ((0, "dense"), (1, "live-bin"), (2, "live-bin, masked stores")):
+            os.environ["BGS_VU_SPARSE"] = str(mode)
+            e = Engine(capi.VUMETER, n_streams=S)
+            os.environ.pop("BGS_VU_SPARSE", None)
+            e.set_geometry(rows, cols, 3)
+            t = 0
+            res = {}
+            for filt in (0, 1):
+                p = capi.default_params(capi.VUMETER)
+                p.vu_enable_filter = filt
+                e.set_params(p)
+                while t < age * (filt + 1):  # the noise scene ages on frames of its own, so that every bin of every pixel gets hit
+                    e.process_batch_device(pool[t % T] if label != "uniform noise" else torch.randint(0, 256, pool[0].shape, generator=g, device=dev, dtype=torch.uint8), fg, bg, None)
+                    t += 1
+                torch.cuda.synchronize()
+                e.enable_kernel_timing(True)
+                w0 = time.perf_counter()
+                for _ in range(steps):
+                    e.process_batch_device(pool[t % T], fg, bg, None)
+                    t += 1
+                torch.cuda.synchronize()
+                wall = (time.perf_counter() - w0) / steps * 1e3
+                ms, n, kname = e.kernel_timing()
+                e.enable_kernel_timing(False)
+                res[filt] = (ms, wall, n, kname)
+            h = torch.from_numpy(e.get_state("hist", (32, rows * cols), np.float32)) != 0
+            L = float(h.sum(0).float().mean())
+            U = float(h.reshape(32, -1, 64).any(2).sum(0).float().mean())
+            U16 = float(h.reshape(32, -1, 16).any(2).sum(0).float().mean())
+            bpp = {0: 3 + 128 + 128 + 4, 1: 3 + 4 * L + 4 * U + 8 + 4, 2: 3 + 8 * L + 8 + 4}[mode]
+            sect = {0: bpp, 1: 3 + 4 * U16 + 4 * U + 8 + 4, 2: 3 + 8 * U16 + 8 + 4}[mode]  # memory moves 64-byte sectors, not lanes' dwords
+            ms = res[0][0]
+            gbps = bpp * px / (ms * 1e-3) / 1e9
+            print("VuMeter %-14s %-24s %dx%d x%d streams: %s %.3f ms/step filter off (%.3f with the filter on; mean of %d) -> %7.1f Mpix/s; wall %.3f / %.3f ms/step; "
+                  "L %.2f live bins/px, U16 %.2f per 16 px, U %.2f per wave; %.1f B/px requested (%.1f in 64-byte sectors) -> %.0f GB/s = %.2f of copy %.0f GB/s (sectors: %.2f); fg ratio %.3f"
+                  % (label, name, cols, rows, S, res[0][3], ms, res[1][0], res[0][2], px / ms / 1e3, res[0][1], res[1][1], L, U16, U, bpp, sect, gbps, gbps / copy, copy, sect * px / (ms * 1e-3) / 1e9 / copy,
+                     float((fg != 0).float().mean())))
+            e.close()
+        del pool
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=8)
@@ -717,6 +786,9 @@ def main():
         return
     if args.only == "lb":
         run_lb(S)
+        return
+    if args.only == "vumeter":
+        run_vumeter(S)
         return
     if args.only.startswith("lb_") and args.only[3:] in LB_CLASSES:  # one class, the foreground scene, short legs, no calibration: for counter passes
         run_lb(S, steps=5, only=args.only[3:], px_variants=(0,), calibrate=False, scenes=(("~10 % foreground", 0.1),))

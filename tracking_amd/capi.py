@@ -17,6 +17,8 @@ LOBSTER = 17
 KDE = 18
 DP_PRATI_MEDIOD, DP_TEXTURE = 19, 20
 LB_SIMPLE_GAUSSIAN, LB_FUZZY_GAUSSIAN, LB_MOG, LB_ADAPTIVE_SOM, LB_FUZZY_ADAPTIVE_SOM = range(21, 26)
+VUMETER = 27  # id 26 is a permanent hole (BGS_ALGO_END is frozen there); BGS_ALGO_LIMIT = 28
+ALGO_LIMIT = 28
 PRATI_MAX_HISTORY = 64  # BGS_PRATI_MAX_HISTORY
 FG_VALID, BG_VALID = 1, 2
 OPT_BORROW_FRAMES, OPT_MOG2_PIXELS_PER_LANE, OPT_MOG2_TILED, OPT_XCD_SWIZZLE, OPT_PLACEMENT_PROBE, OPT_MOG2_SPARSE, OPT_CLIP_FUSE, OPT_HOST_REGISTER, OPT_MODEL_CHUNK_MB, OPT_MODEL_CHUNK_MIN_MB = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
@@ -92,6 +94,10 @@ class BgsParams(C.Structure):
         ("lb_training_sensitivity", C.c_int32),
         ("lb_training_learning_rate", C.c_int32),
         ("lb_training_steps", C.c_int32),
+        ("vu_bin_size", C.c_int32),
+        ("vu_enable_filter", C.c_int32),
+        ("vu_alpha", C.c_double),
+        ("vu_threshold", C.c_double),
     ]
 
 

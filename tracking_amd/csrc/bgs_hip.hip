@@ -27,6 +27,7 @@
 #include "kernel_kde.h"
 #include "kernel_dp2.h"
 #include "kernel_lb.h"
+#include "kernel_vumeter.h"
 #include "kernel_cc.h"
 #include "kernel_dp.h"
 #include "kernel_mog1.h"
@@ -152,6 +153,13 @@ struct bgs_engine {
   int32_t* lb_k = nullptr;
   uint8_t* lb_bg = nullptr;
   std::vector<int> lb_mk;          // the SOMs' training counter m_K, one per stream
+  // VuMeter (kernel_vumeter.h / engine_vumeter.h): histogram planes [bin][S][n], background bytes and live-bin bitmaps [S][n], the
+  // unfiltered and the eroded mask [S][n]
+  float* vu_hist = nullptr;
+  uint8_t *vu_bg = nullptr, *vu_raw = nullptr, *vu_tmp = nullptr;
+  uint32_t* vu_live = nullptr;
+  std::vector<int> vu_count;       // m_nCount of each stream's model object
+  int vu_sparse = 1;               // BGS_VU_SPARSE: 0 dense, 1 live-bin with whole-line stores, 2 live-bin with masked stores (identical results)
   int lb_px = 1;                   // pixels per lane of the two Gaussian kernels (BGS_LB_PX=2: the double2 form, A/B; identical results)
   // MOG2 model (kernel_mog2.h: tiles of ranked weights + fixed-slot records + rank->slot meta words)
   uint8_t* mog2_state = nullptr;
@@ -231,7 +239,11 @@ void dp2_free(bgs_engine* e);  // engine_dp2.h
 int dp2_check(bgs_algo algo, const bgs_params& p);
 void lb_free(bgs_engine* e);  // engine_lb.h
 int lb_check(bgs_algo algo, const bgs_params& p);
+void vu_free(bgs_engine* e);  // engine_vumeter.h
 void vmm_free(VmmRange& v);  // below
+
+// channels of the background image a class hands out: ASBL's and VuMeter's are gray
+int bg_channels(const bgs_engine* e) { return (e->algo == BGS_ASBL || e->algo == BGS_VUMETER) ? 1 : e->ch; }
 
 void lane_release(bgs_engine::Lane& ln) {  // whatever of a lane came to be (bgs_submit's set-up may have failed half-way)
   if (ln.hs) (void)hipStreamSynchronize(ln.hs);
@@ -261,6 +273,7 @@ void free_all(bgs_engine* e) {
     if ((void*)e->mog1_state == e->vmm.base) e->mog1_state = nullptr;
     if ((void*)e->dp_state == e->vmm.base) e->dp_state = nullptr;
     if ((void*)e->lb_model == e->vmm.base) e->lb_model = nullptr;
+    if ((void*)e->vu_hist == e->vmm.base) e->vu_hist = nullptr;
     vmm_free(e->vmm);
   }
   void* dev[] = {e->dp_state, e->gmg_rec, e->gmg_nfeat, e->bgstate, e->bgstate2, e->mog1_state, e->mog2_state, e->d_in, e->d_fg, e->d_bg};
@@ -277,6 +290,7 @@ void free_all(bgs_engine* e) {
   kde_free(e);
   dp2_free(e);
   lb_free(e);
+  vu_free(e);
   if (e->d_stat) (void)hipFree(e->d_stat), e->d_stat = nullptr;
   if (e->h_stat) (void)hipHostFree(e->h_stat), e->h_stat = nullptr;
   for (int i = 0; i < bgs_engine::kStatSlots; ++i) {
@@ -554,6 +568,7 @@ int mog2_allocate(bgs_engine* e) {
 #include "engine_kde.h"
 #include "engine_dp2.h"
 #include "engine_lb.h"
+#include "engine_vumeter.h"
 
 // (Re)build ABL's lookup table for the current alpha on e->stream.  Called when the geometry is set and when bgs_set_params
 // changes alpha; both drain the device first / the stream after, so no launch on any stream sees a half-written table.
@@ -585,6 +600,8 @@ int allocate(bgs_engine* e, int rows, int cols, int ch) {
   if (ch != 1 && ch != 3) return fail(BGS_ERR_UNSUPPORTED, "channels must be 1 or 3, got %d", ch);
   if (e->algo == BGS_MOG2 && ch != 3)
     return fail(BGS_ERR_UNSUPPORTED, "MixtureOfGaussianV2BGS needs 3 channels: getBackgroundImage asserts nchannels == 3 (MixtureOfGaussianV2BGS.cpp:59)");
+  if (e->algo == BGS_VUMETER && ch != 3)
+    return fail(BGS_ERR_UNSUPPORTED, "VuMeter reads 3-channel frames only (cvCvtColor(frame, gray, CV_RGB2GRAY) asserts, VuMeter.cpp:49)");
   HIP_TRY(hipSetDevice(e->device));
   e->rows = rows, e->cols = cols, e->ch = ch, e->n = (size_t)rows * cols;
   const size_t P = e->n * e->S, fb = P * ch;
@@ -617,7 +634,8 @@ int allocate(bgs_engine* e, int rows, int cols, int ch) {
     case BGS_LB_FUZZY_GAUSSIAN:
     case BGS_LB_MOG:
     case BGS_LB_ADAPTIVE_SOM:
-    case BGS_LB_FUZZY_ADAPTIVE_SOM: break;
+    case BGS_LB_FUZZY_ADAPTIVE_SOM:
+    case BGS_VUMETER: break;
     default: return fail(BGS_ERR_UNSUPPORTED, "algorithm %d is not implemented in this build", (int)e->algo);
   }
   for (int i = 0; i < e->nring; ++i) DMALLOC(e->ring[i], fb);
@@ -674,6 +692,10 @@ int allocate(bgs_engine* e, int rows, int cols, int ch) {
   }
   if (is_lb(e->algo)) {
     int rc = lb_allocate(e);
+    if (rc) return rc;
+  }
+  if (e->algo == BGS_VUMETER) {
+    int rc = vu_allocate(e);
     if (rc) return rc;
   }
   // Whatever allocation enqueued on e->stream (statistics counters, poison fills) is complete before the caller's first
@@ -808,6 +830,7 @@ uint64_t launch_key(const bgs_engine* e, int i) {
     case BGS_LB_MOG:
     case BGS_LB_ADAPTIVE_SOM:
     case BGS_LB_FUZZY_ADAPTIVE_SOM: return lb_key(e, i);
+    case BGS_VUMETER: return vu_key(e, i);
     default: return (uint64_t)t | (uint64_t)(e->ss ? e->ss->pp[i] & 1 : 0) << 62;  // SuBSENSE / LOBSTER: the frame index itself goes into the kernels (counter-based random draws); + which half of the ping-pong maps is current
   }
 }
@@ -844,14 +867,14 @@ int process_range(bgs_engine* e, int first, int count, const uint8_t* d_frames, 
   // buffer when it passed none - and mask_pack_ragged_kernel makes the words from them, tail bits zero.
   const size_t W = (e->n + 63) / 64;
   const bool ragged = d_bits && (e->n % 64) != 0;
-  const bool via_bytes = e->algo == BGS_GMG || e->algo == BGS_ASBL;  // their packed mask is always made from the finished byte mask (median after the pixel loop)
+  const bool via_bytes = e->algo == BGS_GMG || e->algo == BGS_ASBL || (e->algo == BGS_VUMETER && e->p.vu_enable_filter);  // their packed mask is always made from the finished byte mask (median after the pixel loop)
   if (d_bits && !d_fg && (ragged || via_bytes)) {
     int rc = pack_scratch(e, (size_t)count * e->n, s);
     if (rc) return rc;
     d_fg = e->pack_fg;
   }
   uint32_t all = ~0u;
-  const size_t C = (size_t)e->ch, bgC = e->algo == BGS_ASBL ? 1 : C;
+  const size_t C = (size_t)e->ch, bgC = (size_t)bg_channels(e);
   for (int a = first; a < first + count;) {
     int b = a + 1;
     const uint64_t key = launch_key(e, a);
@@ -1166,6 +1189,11 @@ int process_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, ui
       if (rc) return rc;
       break;
     }
+    case BGS_VUMETER: {
+      int rc = vu_run(e, first, count, d_frames, d_fg, d_bg, d_bits, s, &flags);
+      if (rc) return rc;
+      break;
+    }
     default: return fail(BGS_ERR_UNSUPPORTED, "algorithm %d is not implemented in this build", (int)e->algo);
   }
   HIP_TRY(hipGetLastError());
@@ -1191,12 +1219,12 @@ int process_clip(bgs_engine* e, int first, int count, int nframes, const uint8_t
   if (!d_frames) return fail(BGS_ERR_INVALID, "d_frames is NULL");
   const size_t W = (e->n + 63) / 64;
   const bool ragged = d_bits && (e->n % 64) != 0;  // as in process_range: byte masks first, then mask_pack_ragged_kernel
-  if (d_bits && !d_fg && (ragged || e->algo == BGS_GMG || e->algo == BGS_ASBL)) {
+  if (d_bits && !d_fg && (ragged || e->algo == BGS_GMG || e->algo == BGS_ASBL || (e->algo == BGS_VUMETER && e->p.vu_enable_filter))) {
     int rc = pack_scratch(e, (size_t)nframes * count * e->n, s);
     if (rc) return rc;
     d_fg = e->pack_fg;
   }
-  const size_t C = (size_t)e->ch, bgC = e->algo == BGS_ASBL ? 1 : C;
+  const size_t C = (size_t)e->ch, bgC = (size_t)bg_channels(e);
   std::vector<uint32_t> fl((size_t)nframes), all((size_t)nframes, ~0u);
   for (int a = first; a < first + count;) {
     int b = a + 1;
@@ -1256,7 +1284,7 @@ int process_clip_run(bgs_engine* e, int first, int count, int slab_count, int nf
     const int fuse = !fuse_ok ? 1 : left >= 8 ? 8 : left >= 4 ? 4 : left >= 2 ? 2 : 1;
     const uint8_t* fr = d_frames + (size_t)t * slab * C;
     uint8_t* fg = d_fg ? d_fg + (size_t)t * slab : nullptr;
-    uint8_t* bg = d_bg ? d_bg + (size_t)t * slab * (e->algo == BGS_ASBL ? 1 : C) : nullptr;
+    uint8_t* bg = d_bg ? d_bg + (size_t)t * slab * (size_t)bg_channels(e) : nullptr;
     uint64_t* bits = d_bits ? d_bits + (size_t)t * words : nullptr;
     if (fuse == 1) {
       int rc = process_range(e, first, count, fr, fg, bg, bits, s, out_flags ? out_flags + t : nullptr);
@@ -1384,7 +1412,7 @@ const char* bgs_last_error(void) { return g_err.c_str(); }
 
 int bgs_default_params(bgs_algo algo, bgs_params* p) {
   if (!p) return fail(BGS_ERR_INVALID, "params is NULL");
-  if ((int)algo < 0 || algo >= BGS_ALGO_END) return fail(BGS_ERR_INVALID, "unknown algorithm %d", (int)algo);
+  if (!BGS_ALGO_KNOWN(algo)) return fail(BGS_ERR_INVALID, "unknown algorithm %d", (int)algo);
   std::memset(p, 0, sizeof(*p));
   p->struct_size = (uint32_t)sizeof(*p);
   p->enable_threshold = 1;
@@ -1461,6 +1489,9 @@ int bgs_default_params(bgs_algo algo, bgs_params* p) {
     case BGS_LB_FUZZY_ADAPTIVE_SOM:
       p->lb_sensitivity = 90, p->lb_training_sensitivity = 240, p->lb_learning_rate = 38, p->lb_training_learning_rate = 255, p->lb_training_steps = 81;
       break;
+    case BGS_VUMETER:  // VuMeter.cpp:19, :103-116 (the vu_* fields stay zero for every other algorithm)
+      p->vu_bin_size = 8, p->vu_enable_filter = 1, p->vu_alpha = 0.995, p->vu_threshold = 0.03;
+      break;
     default: break;
   }
   return BGS_OK;
@@ -1469,7 +1500,7 @@ int bgs_default_params(bgs_algo algo, bgs_params* p) {
 int bgs_create(bgs_algo algo, const bgs_params* params, int hip_device, int n_streams, bgs_engine** out) {
   if (!out) return fail(BGS_ERR_INVALID, "out is NULL");
   *out = nullptr;
-  if ((int)algo < 0 || algo >= BGS_ALGO_END) return fail(BGS_ERR_INVALID, "unknown algorithm %d", (int)algo);
+  if (!BGS_ALGO_KNOWN(algo)) return fail(BGS_ERR_INVALID, "unknown algorithm %d", (int)algo);
   if (n_streams < 1) return fail(BGS_ERR_INVALID, "n_streams must be >= 1");
   if (params && params->struct_size != sizeof(bgs_params)) return fail(BGS_ERR_INVALID, "bgs_params.struct_size %u != %zu (ABI mismatch)", params->struct_size, sizeof(bgs_params));
   bgs_engine* e = new (std::nothrow) bgs_engine();
@@ -1506,6 +1537,7 @@ int bgs_create(bgs_algo algo, const bgs_params* params, int hip_device, int n_st
   if (const char* env = getenv("BGS_KDE_TRIPS")) e->kde_count_trips = atoi(env) != 0;
   if (const char* env = getenv("BGS_MOG2_COMPLETE")) e->mog2_complete = atoi(env) != 0;
   if (const char* env = getenv("BGS_LB_PX")) e->lb_px = atoi(env) == 2 ? 2 : 1;
+  if (const char* env = getenv("BGS_VU_SPARSE")) e->vu_sparse = std::min(std::max(atoi(env), 0), 2);
   if (const char* env = getenv("BGS_XCD_SWIZZLE")) e->xcd_swizzle = atoi(env);
   if (const char* env = getenv("BGS_MOG2_SPARSE")) e->mog2_sparse = atoi(env);
   if (const char* env = getenv("BGS_MODEL_CHUNK_MB")) e->model_chunk_mb = atoi(env);
@@ -1544,6 +1576,8 @@ int bgs_set_params(bgs_engine* e, const bgs_params* params) {
       p.kde_sequence_length = old.kde_sequence_length, p.kde_time_window = old.kde_time_window, p.kde_sd_estimation = old.kde_sd_estimation;
       p.kde_color_ratios = old.kde_color_ratios, p.kde_threshold = old.kde_threshold, p.kde_alpha = old.kde_alpha;
     }
+    if (e->algo == BGS_VUMETER)  // VuMeter.cpp:42-47: SetAlpha / SetBinSize / SetThreshold on the first frame only; enableFilter is live
+      p.vu_bin_size = old.vu_bin_size, p.vu_alpha = old.vu_alpha, p.vu_threshold = old.vu_threshold;
     if (e->algo == BGS_DP_PRATI_MEDIOD) {  // PratiMediodBGS::Initalize copies m_params once (DPPratiMediodBGS.cpp:55-64)
       p.dp_threshold = old.dp_threshold, p.dp_sampling_rate = old.dp_sampling_rate;
       p.dp_history_size = old.dp_history_size, p.dp_weight = old.dp_weight;
@@ -1719,7 +1753,7 @@ int bgs_process(bgs_engine* e, int stream, const uint8_t* in, int rows, int cols
   e->borrow = saved_borrow;
   if (rc) return rc;
   if (flags & BGS_FG_VALID) e->last_fg_stream = stream;
-  const int bg_ch = e->algo == BGS_ASBL ? 1 : channels;
+  const int bg_ch = bg_channels(e);
   // the way back is pipelined the same way when there is a background image to return (6 MB at 1080p): band k is copied out to
   // the caller's image while band k+1 is still on the bus; a mask alone (2 MB) is not worth the events
   bool out_fg = fg && (flags & BGS_FG_VALID), out_bg = bg && (flags & BGS_BG_VALID);
@@ -1768,7 +1802,7 @@ static int lane_wait(bgs_engine* e, int stream, uint32_t* out_flags) {
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipEventSynchronize(ln.done));
   ln.pending = false;
-  const int bg_ch = e->algo == BGS_ASBL ? 1 : e->ch;
+  const int bg_ch = bg_channels(e);
   const bool copy_fg = ln.fg && !ln.fg_direct && (ln.flags & BGS_FG_VALID), copy_bg = ln.bg && !ln.bg_direct && (ln.flags & BGS_BG_VALID);
   const auto st0 = std::chrono::steady_clock::now();
   if (copy_fg)
@@ -1794,7 +1828,7 @@ int bgs_submit(bgs_engine* e, int stream, const uint8_t* in, int rows, int cols,
   HIP_TRY(hipSetDevice(e->device));
   bgs_engine::Lane& ln = e->lanes[stream];
   const size_t rb = (size_t)cols * channels, fb = e->n * channels;
-  const int bg_ch = e->algo == BGS_ASBL ? 1 : channels;
+  const int bg_ch = bg_channels(e);
   if (!ln.hs) {
     // all or nothing: a lane whose stream exists but whose buffers do not would send the next submission through null pointers
     hipError_t er = hipStreamCreateWithFlags(&ln.hs, hipStreamNonBlocking);
@@ -1948,6 +1982,7 @@ int64_t bgs_get_state(bgs_engine* e, int stream, const char* plane, void* dst, s
   if ((e->algo == BGS_SUBSENSE || e->algo == BGS_LOBSTER) && e->ss) return ss_get_state(e, stream, plane, dst, cap);
   if (e->algo == BGS_KDE && e->kde_samples) return kde_get_state(e, stream, plane, dst, cap);
   if (is_lb(e->algo) && e->lb_model) return lb_get_state(e, stream, plane, dst, cap);
+  if (e->algo == BGS_VUMETER && e->vu_hist) return vu_get_state(e, stream, plane, dst, cap);
   if ((e->algo == BGS_DP_PRATI_MEDIOD && e->pm_samples) || (e->algo == BGS_DP_TEXTURE && e->tex_r)) return dp2_get_state(e, stream, plane, dst, cap);
   if (is_dp(e->algo)) {  // planes are stored canonically: [stream][plane][n]
     const int planes = dp_planes_of(e);
@@ -2036,6 +2071,7 @@ int bgs_reset_stream(bgs_engine* e, int stream) {
   e->seen[stream] = 0, e->counter[stream] = 0, e->last_flags[stream] = 0;
   if (!e->kde.empty()) e->kde[stream] = bgs_engine::KdeStream();
   if (!e->lb_mk.empty()) e->lb_mk[stream] = 0;
+  if (!e->vu_count.empty()) e->vu_count[stream] = 0;
   if (e->last_fg_stream == stream) e->last_fg_stream = -1;
   return BGS_OK;
 }

@@ -238,7 +238,7 @@ int dev_setup(bgs_node* n, Dev* d, const bgs_params* params) {
 int check_common(bgs_algo algo, int total, bgs_node** out) {
   if (!out) return nfail(BGS_ERR_INVALID, "out is NULL");
   *out = nullptr;
-  if ((int)algo < 0 || algo >= BGS_ALGO_END) return nfail(BGS_ERR_INVALID, "unknown algorithm %d", (int)algo);
+  if (!BGS_ALGO_KNOWN(algo)) return nfail(BGS_ERR_INVALID, "unknown algorithm %d", (int)algo);
   if (total < 1) return nfail(BGS_ERR_INVALID, "total_streams must be >= 1");
   return BGS_OK;
 }

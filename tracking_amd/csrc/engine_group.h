@@ -270,6 +270,7 @@ int bgs_group_create(const bgs_algo* algos, const bgs_params* const* params, int
       if (params[i]->struct_size != sizeof(bgs_params)) rc = fail(BGS_ERR_INVALID, "bgs_params.struct_size mismatch (class %d)", i);
       else p = *params[i];
     }
+    if (!rc && algos[i] == BGS_VUMETER) rc = fail(BGS_ERR_UNSUPPORTED, "VuMeter is not built for class groups (its background image is gray)");
     unsigned bit = fan_bit_of(algos[i]);
     if (bit & g->fused) bit = 0;  // a second instance of a fused class runs as a member engine
     bgs_engine* m = nullptr;

@@ -82,7 +82,7 @@ class Engine:
             capi.check(capi.lib().bgs_ingest_size(C.byref(self._ingest), rows, cols, C.byref(r), C.byref(c)))
             rows, cols = r.value, c.value
         fg = np.empty((rows, cols), np.uint8)
-        bg_ch = 1 if self.algo == capi.ASBL else ch
+        bg_ch = 1 if self.algo in (capi.ASBL, capi.VUMETER) else ch
         bg = np.empty((rows, cols, bg_ch), np.uint8) if want_bg else None
         flags = C.c_uint32(0)
         capi.check(capi.lib().bgs_process(

@@ -25,6 +25,7 @@ FrameProcessor::FrameProcessor()
   lbMixtureOfGaussians = nullptr, enableLBMixtureOfGaussians = false;
   lbAdaptiveSOM = nullptr, enableLBAdaptiveSOM = false;
   lbFuzzyAdaptiveSOM = nullptr, enableLBFuzzyAdaptiveSOM = false;
+  vuMeter = nullptr, enableVuMeter = false;
   kde = nullptr, enableKDE = false;
   sdbgs = nullptr, enableSigmaDeltaBGS = false;
   ssbgs = nullptr, enableSuBSENSEBGS = false;
@@ -59,6 +60,7 @@ void FrameProcessor::init() {  // FrameProcessor.cpp:35-155
   if (enableLBMixtureOfGaussians) lbMixtureOfGaussians = new LBMixtureOfGaussians;
   if (enableLBAdaptiveSOM) lbAdaptiveSOM = new LBAdaptiveSOM;
   if (enableLBFuzzyAdaptiveSOM) lbFuzzyAdaptiveSOM = new LBFuzzyAdaptiveSOM;
+  if (enableVuMeter) vuMeter = new VuMeter;  // :132
   if (enableKDE) kde = new KDE;  // after VuMeter, before IMBS (:135)
   if (enableSigmaDeltaBGS) sdbgs = new SigmaDeltaBGS;
   if (enableSuBSENSEBGS) ssbgs = new SuBSENSEBGS;
@@ -132,6 +134,7 @@ void FrameProcessor::process(const Image& img_input) {  // :169-340
   if (enableLBMixtureOfGaussians) process("LBMixtureOfGaussians", lbMixtureOfGaussians, img_prep, img_lb_mog);
   if (enableLBAdaptiveSOM) process("LBAdaptiveSOM", lbAdaptiveSOM, img_prep, img_lb_som);
   if (enableLBFuzzyAdaptiveSOM) process("LBFuzzyAdaptiveSOM", lbFuzzyAdaptiveSOM, img_prep, img_lb_fsom);
+  if (enableVuMeter) process("VuMeter", vuMeter, img_prep, img_vumeter);  // :272
   if (enableKDE) process("KDE", kde, img_prep, img_kde);  // :275
   if (enableSigmaDeltaBGS) process("SigmaDeltaBGS", sdbgs, img_prep, img_sdbgs);
   if (enableSuBSENSEBGS) process("SuBSENSEBGS", ssbgs, img_prep, img_ssbgs);
@@ -147,6 +150,7 @@ void FrameProcessor::finish() {  // :342-482 (reverse order of init)
   delete ssbgs, ssbgs = nullptr;
   delete sdbgs, sdbgs = nullptr;
   delete kde, kde = nullptr;
+  delete vuMeter, vuMeter = nullptr;
   delete lbFuzzyAdaptiveSOM, lbFuzzyAdaptiveSOM = nullptr;
   delete lbAdaptiveSOM, lbAdaptiveSOM = nullptr;
   delete lbMixtureOfGaussians, lbMixtureOfGaussians = nullptr;
@@ -207,6 +211,7 @@ void FrameProcessor::saveConfig() {  // :496-552 (keys of the classes this build
   fs.writeInt("enableLBMixtureOfGaussians", enableLBMixtureOfGaussians);
   fs.writeInt("enableLBAdaptiveSOM", enableLBAdaptiveSOM);
   fs.writeInt("enableLBFuzzyAdaptiveSOM", enableLBFuzzyAdaptiveSOM);
+  fs.writeInt("enableVuMeter", enableVuMeter);  // :543
   fs.writeInt("enableKDE", enableKDE);  // :544
   fs.writeInt("enableSigmaDeltaBGS", enableSigmaDeltaBGS);
   fs.writeInt("enableSuBSENSEBGS", enableSuBSENSEBGS);
@@ -240,6 +245,7 @@ void FrameProcessor::loadConfig() {  // :554-610 (defaults: PreProcessor and Fra
   enableLBMixtureOfGaussians = fs.readInt("enableLBMixtureOfGaussians", false);
   enableLBAdaptiveSOM = fs.readInt("enableLBAdaptiveSOM", false);
   enableLBFuzzyAdaptiveSOM = fs.readInt("enableLBFuzzyAdaptiveSOM", false);
+  enableVuMeter = fs.readInt("enableVuMeter", false);  // :601
   enableKDE = fs.readInt("enableKDE", false);  // :602
   enableSigmaDeltaBGS = fs.readInt("enableSigmaDeltaBGS", false);
   enableSuBSENSEBGS = fs.readInt("enableSuBSENSEBGS", false);

@@ -4,9 +4,9 @@
 //   hipbgs::FrameDifferenceBGS, StaticFrameDifferenceBGS, WeightedMovingMeanBGS, WeightedMovingVarianceBGS,
 //   AdaptiveBackgroundLearning, AdaptiveSelectiveBackgroundLearning, MixtureOfGaussianV1BGS, MixtureOfGaussianV2BGS, GMG,
 //   SigmaDeltaBGS, SuBSENSEBGS, LOBSTERBGS, DPZivkovicAGMMBGS, DPGrimsonGMMBGS, DPWrenGABGS, DPMeanBGS, DPAdaptiveMedianBGS, KDE,
-//   DPPratiMediodBGS, DPTextureBGS, LBSimpleGaussian, LBFuzzyGaussian, LBMixtureOfGaussians, LBAdaptiveSOM, LBFuzzyAdaptiveSOM
+//   DPPratiMediodBGS, DPTextureBGS, LBSimpleGaussian, LBFuzzyGaussian, LBMixtureOfGaussians, LBAdaptiveSOM, LBFuzzyAdaptiveSOM, VuMeter
 // Each reads / writes the same ./config/<Class>.xml with the same keys and defaults as the class it stands in for
-// (the list is bgs_classes.inc + bgs_classes_kde.inc + bgs_classes_dp2.inc + bgs_classes_lb.inc, shared verbatim with this repository's tested host mirror, tracking_amd/host/bgs_host.h).
+// (the list is bgs_classes.inc + bgs_classes_kde.inc + bgs_classes_dp2.inc + bgs_classes_lb.inc + bgs_classes_vumeter.inc, shared verbatim with this repository's tested host mirror, tracking_amd/host/bgs_host.h).
 //
 // Use:   mixtureOfGaussianV2BGS = new hipbgs::MixtureOfGaussianV2BGS;      // FrameProcessor.cpp:59-60
 //        if(i==36) bgs = new hipbgs::SuBSENSEBGS();                          // ustc_src/ustc_bgs.cpp:68
@@ -83,7 +83,7 @@ class HipBGSBase : public IBGS {
     } else if (bgs_set_params(engine_, &params_)) {
       fail();
     }
-    const int bg_ch = (algo_ == BGS_ASBL) ? 1 : img_input.channels();
+    const int bg_ch = (algo_ == BGS_ASBL || algo_ == BGS_VUMETER) ? 1 : img_input.channels();
     fg_.create(img_input.size(), CV_8UC1);
     bg_.create(img_input.size(), CV_MAKETYPE(CV_8U, bg_ch));
     uint32_t flags = 0;
@@ -155,6 +155,7 @@ class HipBGSBase : public IBGS {
 #include "bgs_classes_kde.inc"
 #include "bgs_classes_dp2.inc"
 #include "bgs_classes_lb.inc"
+#include "bgs_classes_vumeter.inc"
 #ifdef BGS_HIP_DEFINED_OVERRIDE
 #undef override
 #undef BGS_HIP_DEFINED_OVERRIDE

@@ -57,6 +57,7 @@ class HipFGDetector : public CvFGDetector {
     if (i == 27) bgs = new hipbgs::LBMixtureOfGaussians;
     if (i == 28) bgs = new hipbgs::LBAdaptiveSOM;
     if (i == 29) bgs = new hipbgs::LBFuzzyAdaptiveSOM;
+    if (i == 31) bgs = new hipbgs::VuMeter;
     if (i == 32) bgs = new hipbgs::KDE;
     if (i == 35) bgs = new hipbgs::SigmaDeltaBGS;
     if (i == 36) bgs = new hipbgs::SuBSENSEBGS();

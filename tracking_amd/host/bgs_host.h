@@ -187,7 +187,7 @@ class HipBGSBase : public IBGS {
       int rc = bgs_set_params(engine_, &params_);
       if (rc) throw Exception(rc, std::string(name_) + ": " + bgs_last_error());
     }
-    const int bg_ch = (algo_ == BGS_ASBL) ? 1 : img_input.channels();
+    const int bg_ch = (algo_ == BGS_ASBL || algo_ == BGS_VUMETER) ? 1 : img_input.channels();
     fg_.create(img_input.rows, img_input.cols, 1);
     bg_.create(img_input.rows, img_input.cols, bg_ch);
     uint32_t flags = 0;
@@ -281,6 +281,7 @@ class HipBGSBase : public IBGS {
 #include "bgs_classes_kde.inc"
 #include "bgs_classes_dp2.inc"
 #include "bgs_classes_lb.inc"
+#include "bgs_classes_vumeter.inc"
 
 #undef BGS_HIP_BANNER_DTOR
 

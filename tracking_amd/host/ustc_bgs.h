@@ -2,8 +2,9 @@
 // cvCreateBlobTrackerAuto1 (ustc_src/trackingMain.cpp:33-35, :613-618; the shipped build uses type 36 = SuBSENSE).
 // Same type table, same Process / GetMask / Release protocol; OpenCV-legacy's CvFGDetector base and IplImage are not in this
 // image, so the mask is handed out as a bgs_hip::Image (INTEGRATION.md shows the IplImage-returning version for the reference).
-// Types whose class is outside the hot path (ustc_bgs.cpp:23-58: dp Eigenbackground, tb/, jmo/, LbpMrf, ck/, av/, db/, sjn/; of
-// ae/ only KDE, type 32, and of lb/ the five per-pixel models, types 25-29, are built) throw instead of silently running something else.
+// Types whose class is outside the hot path (ustc_bgs.cpp:23-58: dp Eigenbackground, tb/, jmo/, LbpMrf, ck/, db/, sjn/; of
+// ae/ only KDE, type 32, of lb/ the five per-pixel models, types 25-29, and av/'s VuMeter, type 31, are built) throw instead of
+// silently running something else.
 #pragma once
 #include "bgs_host.h"
 #include "blob.h"
@@ -40,6 +41,7 @@ class USTC_BGS {
     if (i == 27) bgs = new LBMixtureOfGaussians;
     if (i == 28) bgs = new LBAdaptiveSOM;
     if (i == 29) bgs = new LBFuzzyAdaptiveSOM;
+    if (i == 31) bgs = new VuMeter;
     if (i == 32) bgs = new KDE;
     if (i == 35) bgs = new SigmaDeltaBGS;
     if (i == 36) bgs = new SuBSENSEBGS();
