@@ -54,12 +54,16 @@ typedef enum bgs_algo {
   BGS_KDE = 18,              /* KDE::process (USTC_BGS type 32)    package_bgs/ae/KDE.cpp:34-96 */
   BGS_DP_PRATI_MEDIOD = 19,  /* DPPratiMediodBGS::process (USTC_BGS type 14) package_bgs/dp/DPPratiMediodBGS.cpp:29-81 */
   BGS_DP_TEXTURE = 20,       /* DPTextureBGS::process (USTC_BGS type 16)     package_bgs/dp/DPTextureBGS.cpp:39-134 */
-  /* THE ID SPACE.  Three names below are pinned by the tests with the values they had when they were introduced, and none of them may
+  /* THE ID SPACE.  Four names below are pinned by the tests with the values they had when they were introduced, and none of them may
    * move again: BGS_ALGO_COUNT == 21 (the CPU restatement bounds its defaults table with it), BGS_ALGO_END == 26 (the end marker of
-   * the lb/ round) and "id 26 is not an algorithm".  So neither counts the classes, id 26 is a permanent hole, and the end marker
-   * every range check uses is BGS_ALGO_LIMIT, through BGS_ALGO_KNOWN() below.
-   * TO ADD A CLASS: declare it after the last one with an explicit value (the old BGS_ALGO_LIMIT), raise BGS_ALGO_LIMIT by one,
-   * and touch nothing else here - not BGS_ALGO_COUNT, not BGS_ALGO_END, not the hole. */
+   * the lb/ round), BGS_ALGO_LIMIT == 28 (the end marker of the VuMeter round) and "ids 26 and 28 are not algorithms".  So none of
+   * the three counts the classes, ids 26 and 28 are permanent holes, and the end marker every range check uses is BGS_ALGO_LAST,
+   * through BGS_ALGO_KNOWN() below.
+   * TO ADD A CLASS: declare it after the last one with an explicit value (the old BGS_ALGO_LAST), raise BGS_ALGO_LAST by one, and
+   * touch nothing else here - not BGS_ALGO_COUNT, not BGS_ALGO_END, not BGS_ALGO_LIMIT, not the holes.  The tests of the round that
+   * adds the class must pin "id BGS_ALGO_LAST is unknown" through BGS_ALGO_KNOWN() and bgs_create ONLY, never the marker's value: a
+   * pinned marker value is what made the two holes.  Parameters of a new class go into a struct of their own with its own
+   * default / set / get calls (bgs_fuzzy_params below): tests pin sizeof(bgs_params) and its last fields. */
   BGS_ALGO_COUNT,
   /* Laurence Bender's package_bgs/lb/ models (3-channel frames only; double-precision per-pixel models; FG and BG from frame 1) */
   BGS_LB_SIMPLE_GAUSSIAN = 21,    /* LBSimpleGaussian::process (USTC_BGS type 25)     package_bgs/lb/LBSimpleGaussian.cpp:31-73 */
@@ -69,11 +73,16 @@ typedef enum bgs_algo {
   BGS_LB_FUZZY_ADAPTIVE_SOM = 25, /* LBFuzzyAdaptiveSOM::process (USTC_BGS type 29)   package_bgs/lb/LBFuzzyAdaptiveSOM.cpp:31-74 */
   BGS_ALGO_END,                   /* FROZEN at 26 (see above); id 26 itself is a hole */
   BGS_VUMETER = 27,               /* VuMeter::process (USTC_BGS type 31)              package_bgs/av/VuMeter.cpp:33-86 */
-  BGS_ALGO_LIMIT = 28             /* one past the last id */
+  BGS_ALGO_LIMIT = 28,            /* FROZEN at 28 (see above); id 28 itself is a hole */
+  /* package_bgs/tb fuzzy integrals (3-channel frames; float BGR background; no mask during the framesToLearn + 1 learning frames).
+   * Their parameters are bgs_fuzzy_params, not bgs_params. */
+  BGS_FUZZY_SUGENO = 29,          /* FuzzySugenoIntegral::process (USTC_BGS type 21)  package_bgs/tb/FuzzySugenoIntegral.cpp:31-173 */
+  BGS_FUZZY_CHOQUET = 30,         /* FuzzyChoquetIntegral::process (USTC_BGS type 22) package_bgs/tb/FuzzyChoquetIntegral.cpp:31-173 */
+  BGS_ALGO_LAST = 31              /* one past the last id; moves with every class added */
 } bgs_algo;
 
 /* "id is an algorithm": the one range check (bgs_default_params, bgs_create, bgs_node_create) */
-#define BGS_ALGO_KNOWN(id) (((int)(id) >= 0 && (int)(id) < 26) || ((int)(id) >= 27 && (int)(id) < (int)BGS_ALGO_LIMIT))
+#define BGS_ALGO_KNOWN(id) (((int)(id) >= 0 && (int)(id) < 26) || (int)(id) == 27 || ((int)(id) >= 29 && (int)(id) < (int)BGS_ALGO_LAST))
 
 typedef enum bgs_status {
   BGS_OK = 0,
@@ -230,6 +239,26 @@ typedef struct bgs_params {
   double vu_threshold;        /* 0.03  threshold: a pixel whose bin is below it is foreground */
 } bgs_params;
 
+/* FuzzySugenoIntegral / FuzzyChoquetIntegral (package_bgs/tb/Fuzzy*Integral.cpp:20-21, :191-205).  A struct of its own: bgs_params does
+ * not grow any more (see THE ID SPACE).  bgs_create gives a fuzzy engine these defaults whatever bgs_params it was handed;
+ * bgs_set_fuzzy_params may be called between any two frames and acts from the next frame on, as the wrapper's per-frame loadConfig
+ * does: all seven values are live.  A stream learns while its own frame counter is <= frames_to_learn (frames_to_learn + 1 frames:
+ * no mask, no background image, out_flags 0), then detects: mask (0 / 255) and the 3-channel background image, both valid.
+ * Refused with BGS_ERR_UNSUPPORTED: color_space 2 (Ohta: a pixel with R == B gives -inf and a NaN background on the first detecting
+ * frame), 3 and 4 (OpenCV's float cvCvtColor), option outside {1,2} (the reference's integral image is uninitialised then),
+ * 1-channel frames, frames narrower or lower than 2 pixels; BGS_ERR_INVALID: frames_to_learn < 0. */
+typedef struct bgs_fuzzy_params {
+  uint32_t struct_size;     /* sizeof(bgs_fuzzy_params) */
+  int32_t frames_to_learn;  /* 10   framesToLearn */
+  double alpha_learn;       /* 0.1  alphaLearn: bg = alphaLearn * in + (1 - alphaLearn) * bg while learning */
+  double alpha_update;      /* 0.01 alphaUpdate */
+  int32_t color_space;      /* 1    colorSpace: 1 = RGB (the only one built) */
+  int32_t option;           /* 2    1: three colour components, 2: texture + two colour components */
+  int32_t smooth;           /* 1    smooth: medianBlur 3 of the integral image */
+  int32_t reserved_;        /* 0 */
+  double threshold;         /* 0.67 threshold */
+} bgs_fuzzy_params;
+
 /* Largest dp_history_size the PratiMediod kernel is built for (every dist entry then fits in 16 bits: 64 x 255 < 65536). */
 #define BGS_PRATI_MAX_HISTORY 64
 
@@ -248,6 +277,14 @@ int bgs_create(bgs_algo algo, const bgs_params* params, int hip_device, int n_st
  * so thresholds / alpha may change mid-stream; structural fields (nmixtures, n_samples)
  * must stay what they were at bgs_create. */
 int bgs_set_params(bgs_engine* e, const bgs_params* params);
+
+/* The fuzzy-integral classes' own parameters (bgs_fuzzy_params above); BGS_ERR_INVALID for an engine of any other class. */
+int bgs_fuzzy_default_params(bgs_fuzzy_params* p);
+int bgs_set_fuzzy_params(bgs_engine* e, const bgs_fuzzy_params* p);
+int bgs_get_fuzzy_params(const bgs_engine* e, bgs_fuzzy_params* p);
+/* Every refusal of the two classes without an engine and without a device: parameters (p == NULL: the defaults) and, where rows > 0,
+ * the frame geometry.  bgs_set_fuzzy_params and bgs_set_geometry run the same checks.  The message names the class. */
+int bgs_fuzzy_check(bgs_algo algo, const bgs_fuzzy_params* p, int rows, int cols, int channels);
 
 /* Engine options.
  *   BGS_OPT_BORROW_FRAMES  device path of the history-keeping classes (FrameDifference, WeightedMovingMean/Variance):
@@ -466,7 +503,9 @@ const char* bgs_last_error(void);
  * colour), "sortkey" f64 [n][3], "k" int32 [n] (slots >= k read 0); AdaptiveSOM / FuzzyAdaptiveSOM "som" f64 [n][3][3][3] (pixel,
  * neuron row, neuron column, colour), "bg" u8 [n][3], "count" int64 [1] = the stream's training counter m_K.
  * VuMeter: "hist" f32 [binCount][n], the reference's dense histogram planes (whatever the engine keeps internally), "background"
- * u8 [n], "count" int64 [1] = the stream's m_nCount. */
+ * u8 [n], "count" int64 [1] = the stream's m_nCount.
+ * Fuzzy integrals: "background" f32 [n][3] (BGR), "integral" f32 [n] = the (blurred) integral image of the stream's last detecting
+ * frame, "minmax" f32 [2] of that image, "count" int64 [1] = the stream's frameNumber. */
 
 /* LBSP 16-bit double-cross descriptors of a whole 8UC3 / 8UC1 image (LBSP.h:50-95,
  * LBSP_16bits_dbcross_{3ch3t,1ch}.i).  d_desc: [rows][cols][channels] uint16; the

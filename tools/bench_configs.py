@@ -9,6 +9,8 @@ Not the driver's bench line (bench.py is); the numbers go to DESIGN.md §6.
              calibration phase, the Gaussian pair with one and two pixels per lane, 8 x 1080p  (lb_<class>: one class, short legs)
   --only vumeter: VuMeter (package_bgs/av), dense and live-bin kernels (BGS_VU_SPARSE 0 / 1 / 2), filter on and off, on S_surv and on
              fresh uniform noise (every bin live: the live-bin kernels' worst case), 8 x 1080p
+  --only fuzzy: FuzzySugenoIntegral and FuzzyChoquetIntegral (package_bgs/tb), ms per learning step and per detecting step on S_surv,
+             8 x 1080p  (fuzzy_choquet / fuzzy_sugeno: one class, short legs, no calibration: for kernel-trace passes)
 usage: bench_configs.py [--streams S] [--swizzle 0|1]"""
 import argparse
 import os
@@ -772,6 +774,48 @@ def run_vumeter(S=8, rows=1080, cols=1920, steps=30, age=60):
         torch.cuda.empty_cache()
 
 
+def run_fuzzy(S=8, rows=1080, cols=1920, steps=20, only=None, calibrate=True):
+    """The two fuzzy integrals (reference defaults) at S x 1080p on S_surv, byte mask + background image out: ms per learning step (one
+    launch) and per detecting step (seven launches: HIP events around the whole step, mean of `steps`) and the wall ms per step.
+    Bytes per pixel are the kernels' own accounting of what a detecting step requests (kernel_fuzzy.h): prep 3 + 12 in, 8 out; pixel
+    3 + 12 + 8 in, 12 + 1 out; scan 1 in; apply 1 + 12 in, 4 out; median 4 in, 4 + 1 out; update 4 + 3 + 12 in, 12 + 3 out = 120; a
+    learning step 3 + 12 in, 12 out = 27.  `copy_frac` is that figure's rate over this process's float4 copy rate."""
+    dev = torch.device("cuda", 0)
+    px = S * rows * cols
+    T = 8
+    copy = capi.calibrate_copy(0, 2 << 30, 0) if calibrate else float("nan")
+    pool = synth.SurvStreams(S, rows, cols, seed0=4321, device=dev).pool(T)
+    fg = torch.empty((S, rows, cols), dtype=torch.uint8, device=dev)
+    bg = torch.empty((S, rows, cols, 3), dtype=torch.uint8, device=dev)
+    for algo, name in ((capi.FUZZY_SUGENO, "FuzzySugenoIntegral"), (capi.FUZZY_CHOQUET, "FuzzyChoquetIntegral")):
+        if only and name != only:
+            continue
+        e = Engine(algo, n_streams=S)
+        e.set_geometry(rows, cols, 3)
+        res = {}
+        t = 0
+        for phase, ftl, bpp in (("learning", 1 << 30, 27.0), ("detecting", 0, 120.0)):
+            e.set_fuzzy_params(frames_to_learn=ftl)
+            for _ in range(4):
+                e.process_batch_device(pool[t % T], fg, bg, None)
+                t += 1
+            torch.cuda.synchronize()
+            e.enable_kernel_timing(True)
+            w0 = time.perf_counter()
+            for _ in range(steps):
+                e.process_batch_device(pool[t % T], fg, bg, None)
+                t += 1
+            torch.cuda.synchronize()
+            wall = (time.perf_counter() - w0) / steps * 1e3
+            ms, n, kname = e.kernel_timing()
+            e.enable_kernel_timing(False)
+            gbps = bpp * px / (ms * 1e-3) / 1e9
+            res[phase] = (ms, wall, n, gbps)
+            print("%-20s %-9s %dx%d x%d streams: %.3f ms/step (%s; mean of %d) -> %7.1f Mpix/s; wall %.3f ms/step; %.0f B/px requested -> %.0f GB/s = %.2f of copy %.0f GB/s; fg ratio %.3f"
+                  % (name, phase, cols, rows, S, ms, kname, n, px / ms / 1e3, wall, bpp, gbps, gbps / copy, copy, float((fg != 0).float().mean()) if ftl == 0 else 0.0))
+        e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=8)
@@ -789,6 +833,12 @@ def main():
         return
     if args.only == "vumeter":
         run_vumeter(S)
+        return
+    if args.only == "fuzzy":
+        run_fuzzy(S)
+        return
+    if args.only in ("fuzzy_choquet", "fuzzy_sugeno"):
+        run_fuzzy(S, steps=5, only="FuzzyChoquetIntegral" if args.only == "fuzzy_choquet" else "FuzzySugenoIntegral", calibrate=False)
         return
     if args.only.startswith("lb_") and args.only[3:] in LB_CLASSES:  # one class, the foreground scene, short legs, no calibration: for counter passes
         run_lb(S, steps=5, only=args.only[3:], px_variants=(0,), calibrate=False, scenes=(("~10 % foreground", 0.1),))

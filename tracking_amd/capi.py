@@ -17,8 +17,12 @@ LOBSTER = 17
 KDE = 18
 DP_PRATI_MEDIOD, DP_TEXTURE = 19, 20
 LB_SIMPLE_GAUSSIAN, LB_FUZZY_GAUSSIAN, LB_MOG, LB_ADAPTIVE_SOM, LB_FUZZY_ADAPTIVE_SOM = range(21, 26)
-VUMETER = 27  # id 26 is a permanent hole (BGS_ALGO_END is frozen there); BGS_ALGO_LIMIT = 28
-ALGO_LIMIT = 28
+VUMETER = 27  # id 26 is a permanent hole (BGS_ALGO_END is frozen there); BGS_ALGO_LIMIT = 28  # frozen, and id 28 is the second permanent hole
+FUZZY_SUGENO, FUZZY_CHOQUET = 29, 30  # package_bgs/tb fuzzy integrals; their parameters are BgsFuzzyParams, not BgsParams
+ALGO_LAST = 31  # one past the last id
+ALGO_LIMIT = 28  # frozen, and id 28 is the second permanent hole
+FUZZY_SUGENO, FUZZY_CHOQUET = 29, 30  # package_bgs/tb fuzzy integrals; their parameters are BgsFuzzyParams, not BgsParams
+ALGO_LAST = 31  # one past the last id
 PRATI_MAX_HISTORY = 64  # BGS_PRATI_MAX_HISTORY
 FG_VALID, BG_VALID = 1, 2
 OPT_BORROW_FRAMES, OPT_MOG2_PIXELS_PER_LANE, OPT_MOG2_TILED, OPT_XCD_SWIZZLE, OPT_PLACEMENT_PROBE, OPT_MOG2_SPARSE, OPT_CLIP_FUSE, OPT_HOST_REGISTER, OPT_MODEL_CHUNK_MB, OPT_MODEL_CHUNK_MIN_MB = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
@@ -101,6 +105,12 @@ class BgsParams(C.Structure):
     ]
 
 
+class BgsFuzzyParams(C.Structure):
+    """struct bgs_fuzzy_params, field for field (FuzzySugenoIntegral / FuzzyChoquetIntegral)."""
+    _fields_ = [("struct_size", C.c_uint32), ("frames_to_learn", C.c_int32), ("alpha_learn", C.c_double), ("alpha_update", C.c_double),
+                ("color_space", C.c_int32), ("option", C.c_int32), ("smooth", C.c_int32), ("reserved_", C.c_int32), ("threshold", C.c_double)]
+
+
 class BgsError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("libbgs_hip error %d: %s" % (code, text))
@@ -114,6 +124,10 @@ SYMBOLS = [
     ("bgs_default_params", C.c_int, [C.c_int, C.POINTER(BgsParams)]),
     ("bgs_create", C.c_int, [C.c_int, C.POINTER(BgsParams), C.c_int, C.c_int, C.POINTER(_P)]),
     ("bgs_set_params", C.c_int, [_P, C.POINTER(BgsParams)]),
+    ("bgs_fuzzy_default_params", C.c_int, [C.POINTER(BgsFuzzyParams)]),
+    ("bgs_set_fuzzy_params", C.c_int, [_P, C.POINTER(BgsFuzzyParams)]),
+    ("bgs_get_fuzzy_params", C.c_int, [_P, C.POINTER(BgsFuzzyParams)]),
+    ("bgs_fuzzy_check", C.c_int, [C.c_int, C.POINTER(BgsFuzzyParams), C.c_int, C.c_int, C.c_int]),
     ("bgs_set_option", C.c_int, [_P, C.c_int, C.c_int64]),
     ("bgs_set_geometry", C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     ("bgs_process", C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_uint32)]),
@@ -220,6 +234,14 @@ def default_params(algo):
     p = BgsParams()
     p.struct_size = C.sizeof(BgsParams)
     check(lib().bgs_default_params(algo, C.byref(p)))
+    return p
+
+
+def fuzzy_default_params(**kw):
+    p = BgsFuzzyParams()
+    check(lib().bgs_fuzzy_default_params(C.byref(p)))
+    for k, v in kw.items():
+        setattr(p, k, v)
     return p
 
 

@@ -28,6 +28,7 @@
 #include "kernel_dp2.h"
 #include "kernel_lb.h"
 #include "kernel_vumeter.h"
+#include "kernel_fuzzy.h"
 #include "kernel_cc.h"
 #include "kernel_dp.h"
 #include "kernel_mog1.h"
@@ -160,6 +161,17 @@ struct bgs_engine {
   uint32_t* vu_live = nullptr;
   std::vector<int> vu_count;       // m_nCount of each stream's model object
   int vu_sparse = 1;               // BGS_VU_SPARSE: 0 dense, 1 live-bin with whole-line stores, 2 live-bin with masked stores (identical results)
+  // Fuzzy integrals (kernel_fuzzy.h / engine_fuzzy.h): the float BGR background [S][n][3]; per-frame scratch: seven float planes
+  // [S][n] (gray of input and background, hs[3], integral column-major, blurred integral row-major), pi codes, scan block products,
+  // per-stream min / max keys; the LBP table
+  bgs_fuzzy_params fz;
+  float *fz_bg = nullptr, *fz_f = nullptr, *fz_tab = nullptr;
+  uint8_t *fz_code = nullptr, *fz_bprod = nullptr;
+  uint32_t* fz_minmax = nullptr;
+  std::vector<int64_t> fz_fn;        // frameNumber of each stream's object
+  std::vector<uint32_t> fz_flags;    // out_flags of each stream's last frame (streams of one launch differ)
+  std::vector<uint8_t> fz_detected;  // the stream has an integral image
+  bool fz_any_valid = false;         // the last run held a detecting stream
   int lb_px = 1;                   // pixels per lane of the two Gaussian kernels (BGS_LB_PX=2: the double2 form, A/B; identical results)
   // MOG2 model (kernel_mog2.h: tiles of ranked weights + fixed-slot records + rank->slot meta words)
   uint8_t* mog2_state = nullptr;
@@ -240,6 +252,8 @@ int dp2_check(bgs_algo algo, const bgs_params& p);
 void lb_free(bgs_engine* e);  // engine_lb.h
 int lb_check(bgs_algo algo, const bgs_params& p);
 void vu_free(bgs_engine* e);  // engine_vumeter.h
+void fz_free(bgs_engine* e);  // engine_fuzzy.h
+bool is_fuzzy(bgs_algo a);
 void vmm_free(VmmRange& v);  // below
 
 // channels of the background image a class hands out: ASBL's and VuMeter's are gray
@@ -291,6 +305,7 @@ void free_all(bgs_engine* e) {
   dp2_free(e);
   lb_free(e);
   vu_free(e);
+  fz_free(e);
   if (e->d_stat) (void)hipFree(e->d_stat), e->d_stat = nullptr;
   if (e->h_stat) (void)hipHostFree(e->h_stat), e->h_stat = nullptr;
   for (int i = 0; i < bgs_engine::kStatSlots; ++i) {
@@ -569,6 +584,7 @@ int mog2_allocate(bgs_engine* e) {
 #include "engine_dp2.h"
 #include "engine_lb.h"
 #include "engine_vumeter.h"
+#include "engine_fuzzy.h"
 
 // (Re)build ABL's lookup table for the current alpha on e->stream.  Called when the geometry is set and when bgs_set_params
 // changes alpha; both drain the device first / the stream after, so no launch on any stream sees a half-written table.
@@ -602,6 +618,10 @@ int allocate(bgs_engine* e, int rows, int cols, int ch) {
     return fail(BGS_ERR_UNSUPPORTED, "MixtureOfGaussianV2BGS needs 3 channels: getBackgroundImage asserts nchannels == 3 (MixtureOfGaussianV2BGS.cpp:59)");
   if (e->algo == BGS_VUMETER && ch != 3)
     return fail(BGS_ERR_UNSUPPORTED, "VuMeter reads 3-channel frames only (cvCvtColor(frame, gray, CV_RGB2GRAY) asserts, VuMeter.cpp:49)");
+  if (is_fuzzy(e->algo)) {
+    int rc = fz_check_geometry(e->algo, rows, cols, ch);
+    if (rc) return rc;
+  }
   HIP_TRY(hipSetDevice(e->device));
   e->rows = rows, e->cols = cols, e->ch = ch, e->n = (size_t)rows * cols;
   const size_t P = e->n * e->S, fb = P * ch;
@@ -635,7 +655,9 @@ int allocate(bgs_engine* e, int rows, int cols, int ch) {
     case BGS_LB_MOG:
     case BGS_LB_ADAPTIVE_SOM:
     case BGS_LB_FUZZY_ADAPTIVE_SOM:
-    case BGS_VUMETER: break;
+    case BGS_VUMETER:
+    case BGS_FUZZY_SUGENO:
+    case BGS_FUZZY_CHOQUET: break;
     default: return fail(BGS_ERR_UNSUPPORTED, "algorithm %d is not implemented in this build", (int)e->algo);
   }
   for (int i = 0; i < e->nring; ++i) DMALLOC(e->ring[i], fb);
@@ -696,6 +718,10 @@ int allocate(bgs_engine* e, int rows, int cols, int ch) {
   }
   if (e->algo == BGS_VUMETER) {
     int rc = vu_allocate(e);
+    if (rc) return rc;
+  }
+  if (is_fuzzy(e->algo)) {
+    int rc = fz_allocate(e);
     if (rc) return rc;
   }
   // Whatever allocation enqueued on e->stream (statistics counters, poison fills) is complete before the caller's first
@@ -831,6 +857,8 @@ uint64_t launch_key(const bgs_engine* e, int i) {
     case BGS_LB_ADAPTIVE_SOM:
     case BGS_LB_FUZZY_ADAPTIVE_SOM: return lb_key(e, i);
     case BGS_VUMETER: return vu_key(e, i);
+    case BGS_FUZZY_SUGENO:
+    case BGS_FUZZY_CHOQUET: return fz_key(e, i);
     default: return (uint64_t)t | (uint64_t)(e->ss ? e->ss->pp[i] & 1 : 0) << 62;  // SuBSENSE / LOBSTER: the frame index itself goes into the kernels (counter-based random draws); + which half of the ping-pong maps is current
   }
 }
@@ -867,7 +895,7 @@ int process_range(bgs_engine* e, int first, int count, const uint8_t* d_frames, 
   // buffer when it passed none - and mask_pack_ragged_kernel makes the words from them, tail bits zero.
   const size_t W = (e->n + 63) / 64;
   const bool ragged = d_bits && (e->n % 64) != 0;
-  const bool via_bytes = e->algo == BGS_GMG || e->algo == BGS_ASBL || (e->algo == BGS_VUMETER && e->p.vu_enable_filter);  // their packed mask is always made from the finished byte mask (median after the pixel loop)
+  const bool via_bytes = e->algo == BGS_GMG || e->algo == BGS_ASBL || (e->algo == BGS_VUMETER && e->p.vu_enable_filter) || is_fuzzy(e->algo);  // their packed mask is always made from the finished byte mask (median after the pixel loop)
   if (d_bits && !d_fg && (ragged || via_bytes)) {
     int rc = pack_scratch(e, (size_t)count * e->n, s);
     if (rc) return rc;
@@ -885,7 +913,7 @@ int process_range(bgs_engine* e, int first, int count, const uint8_t* d_frames, 
     uint32_t fl = 0;
     int rc = process_run(e, a, b - a, d_frames + o * C, d_fg ? d_fg + o : nullptr, d_bg ? d_bg + o * bgC : nullptr, (d_bits && !ragged) ? d_bits + (size_t)(a - first) * W : nullptr, s, &fl);
     if (rc) return rc;
-    if (ragged && (fl & BGS_FG_VALID)) pack_ragged(e, d_fg + o, d_bits + (size_t)(a - first) * W, (size_t)(b - a), s);
+    if (ragged && ((fl & BGS_FG_VALID) || (is_fuzzy(e->algo) && e->fz_any_valid))) pack_ragged(e, d_fg + o, d_bits + (size_t)(a - first) * W, (size_t)(b - a), s);
     all &= fl;
     a = b;
   }
@@ -1194,10 +1222,18 @@ int process_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, ui
       if (rc) return rc;
       break;
     }
+    case BGS_FUZZY_SUGENO:
+    case BGS_FUZZY_CHOQUET: {
+      int rc = fz_run(e, first, count, d_frames, d_fg, d_bg, d_bits, s, &flags);
+      if (rc) return rc;
+      break;
+    }
     default: return fail(BGS_ERR_UNSUPPORTED, "algorithm %d is not implemented in this build", (int)e->algo);
   }
   HIP_TRY(hipGetLastError());
   for (int i = first; i < first + count; ++i) e->seen[i]++, e->rpos[i]++, e->last_flags[i] = flags;
+  if (is_fuzzy(e->algo))  // learning and detecting streams share the run: the flags are per stream
+    for (int i = first; i < first + count; ++i) e->last_flags[i] = e->fz_flags[i];
   if (out_flags) *out_flags = flags;
   return BGS_OK;
 }
@@ -1219,7 +1255,7 @@ int process_clip(bgs_engine* e, int first, int count, int nframes, const uint8_t
   if (!d_frames) return fail(BGS_ERR_INVALID, "d_frames is NULL");
   const size_t W = (e->n + 63) / 64;
   const bool ragged = d_bits && (e->n % 64) != 0;  // as in process_range: byte masks first, then mask_pack_ragged_kernel
-  if (d_bits && !d_fg && (ragged || e->algo == BGS_GMG || e->algo == BGS_ASBL || (e->algo == BGS_VUMETER && e->p.vu_enable_filter))) {
+  if (d_bits && !d_fg && (ragged || e->algo == BGS_GMG || e->algo == BGS_ASBL || (e->algo == BGS_VUMETER && e->p.vu_enable_filter) || is_fuzzy(e->algo))) {
     int rc = pack_scratch(e, (size_t)nframes * count * e->n, s);
     if (rc) return rc;
     d_fg = e->pack_fg;
@@ -1534,6 +1570,7 @@ int bgs_create(bgs_algo algo, const bgs_params* params, int hip_device, int n_st
   e->counter.assign(n_streams, 0);
   e->flip.assign(n_streams, 0);
   e->kde.assign(n_streams, bgs_engine::KdeStream());
+  fz_defaults(&e->fz);  // a fuzzy engine starts from the constructor's values whatever bgs_params it was handed (bgs_set_fuzzy_params)
   if (const char* env = getenv("BGS_KDE_TRIPS")) e->kde_count_trips = atoi(env) != 0;
   if (const char* env = getenv("BGS_MOG2_COMPLETE")) e->mog2_complete = atoi(env) != 0;
   if (const char* env = getenv("BGS_LB_PX")) e->lb_px = atoi(env) == 2 ? 2 : 1;
@@ -1594,6 +1631,39 @@ int bgs_set_params(bgs_engine* e, const bgs_params* params) {
       if (rc) return rc;
     }
   }
+  return BGS_OK;
+}
+
+int bgs_fuzzy_default_params(bgs_fuzzy_params* p) {
+  if (!p) return fail(BGS_ERR_INVALID, "params is NULL");
+  fz_defaults(p);
+  return BGS_OK;
+}
+
+int bgs_set_fuzzy_params(bgs_engine* e, const bgs_fuzzy_params* p) {
+  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
+  if (!is_fuzzy(e->algo)) return fail(BGS_ERR_INVALID, "bgs_set_fuzzy_params: algorithm %d is not a fuzzy integral", (int)e->algo);
+  if (p->struct_size != sizeof(bgs_fuzzy_params)) return fail(BGS_ERR_INVALID, "bgs_fuzzy_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_fuzzy_params));
+  int rc = fz_check(e->algo, *p);
+  if (rc) return rc;
+  e->fz = *p;  // all seven are live: the host fills the launch arguments of the next frame from them
+  return BGS_OK;
+}
+
+int bgs_fuzzy_check(bgs_algo algo, const bgs_fuzzy_params* p, int rows, int cols, int channels) {
+  if (!is_fuzzy(algo)) return fail(BGS_ERR_INVALID, "bgs_fuzzy_check: algorithm %d is not a fuzzy integral", (int)algo);
+  bgs_fuzzy_params d;
+  fz_defaults(&d);
+  if (p && p->struct_size != sizeof(bgs_fuzzy_params)) return fail(BGS_ERR_INVALID, "bgs_fuzzy_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_fuzzy_params));
+  int rc = fz_check(algo, p ? *p : d);
+  if (rc || rows <= 0) return rc;
+  return fz_check_geometry(algo, rows, cols, channels);
+}
+
+int bgs_get_fuzzy_params(const bgs_engine* e, bgs_fuzzy_params* p) {
+  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
+  if (!is_fuzzy(e->algo)) return fail(BGS_ERR_INVALID, "bgs_get_fuzzy_params: algorithm %d is not a fuzzy integral", (int)e->algo);
+  *p = e->fz;
   return BGS_OK;
 }
 
@@ -1983,6 +2053,7 @@ int64_t bgs_get_state(bgs_engine* e, int stream, const char* plane, void* dst, s
   if (e->algo == BGS_KDE && e->kde_samples) return kde_get_state(e, stream, plane, dst, cap);
   if (is_lb(e->algo) && e->lb_model) return lb_get_state(e, stream, plane, dst, cap);
   if (e->algo == BGS_VUMETER && e->vu_hist) return vu_get_state(e, stream, plane, dst, cap);
+  if (is_fuzzy(e->algo) && e->fz_bg) return fz_get_state(e, stream, plane, dst, cap);
   if ((e->algo == BGS_DP_PRATI_MEDIOD && e->pm_samples) || (e->algo == BGS_DP_TEXTURE && e->tex_r)) return dp2_get_state(e, stream, plane, dst, cap);
   if (is_dp(e->algo)) {  // planes are stored canonically: [stream][plane][n]
     const int planes = dp_planes_of(e);
@@ -2072,6 +2143,7 @@ int bgs_reset_stream(bgs_engine* e, int stream) {
   if (!e->kde.empty()) e->kde[stream] = bgs_engine::KdeStream();
   if (!e->lb_mk.empty()) e->lb_mk[stream] = 0;
   if (!e->vu_count.empty()) e->vu_count[stream] = 0;
+  if (!e->fz_fn.empty()) e->fz_fn[stream] = 0, e->fz_flags[stream] = 0, e->fz_detected[stream] = 0;
   if (e->last_fg_stream == stream) e->last_fg_stream = -1;
   return BGS_OK;
 }

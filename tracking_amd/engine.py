@@ -51,6 +51,20 @@ class Engine:
         capi.check(capi.lib().bgs_set_params(self._h, C.byref(params)))
         self.params = params
 
+    def set_fuzzy_params(self, params=None, **kw):
+        """bgs_set_fuzzy_params (FUZZY_SUGENO / FUZZY_CHOQUET): acts from the next frame on.  Keywords change single fields of the
+        engine's current values."""
+        if params is None:
+            params = self.get_fuzzy_params()
+        for k, v in kw.items():
+            setattr(params, k, v)
+        capi.check(capi.lib().bgs_set_fuzzy_params(self._h, C.byref(params)))
+
+    def get_fuzzy_params(self):
+        p = capi.BgsFuzzyParams()
+        capi.check(capi.lib().bgs_get_fuzzy_params(self._h, C.byref(p)))
+        return p
+
     def set_option(self, option, value):
         capi.check(capi.lib().bgs_set_option(self._h, option, int(value)))
 

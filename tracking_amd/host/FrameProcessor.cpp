@@ -20,6 +20,8 @@ FrameProcessor::FrameProcessor()
   wrenGA = nullptr, enableDPWrenGABGS = false;
   pratiMediod = nullptr, enableDPPratiMediodBGS = false;
   textureBGS = nullptr, enableDPTextureBGS = false;
+  fuzzySugenoIntegral = nullptr, enableFuzzySugenoIntegral = false;
+  fuzzyChoquetIntegral = nullptr, enableFuzzyChoquetIntegral = false;
   lbSimpleGaussian = nullptr, enableLBSimpleGaussian = false;
   lbFuzzyGaussian = nullptr, enableLBFuzzyGaussian = false;
   lbMixtureOfGaussians = nullptr, enableLBMixtureOfGaussians = false;
@@ -55,6 +57,8 @@ void FrameProcessor::init() {  // FrameProcessor.cpp:35-155
   if (enableDPWrenGABGS) wrenGA = new DPWrenGABGS;
   if (enableDPPratiMediodBGS) pratiMediod = new DPPratiMediodBGS;  // :81-88 (DPEigenbackgroundBGS between them is not built)
   if (enableDPTextureBGS) textureBGS = new DPTextureBGS;
+  if (enableFuzzySugenoIntegral) fuzzySugenoIntegral = new FuzzySugenoIntegral;  // :102-106
+  if (enableFuzzyChoquetIntegral) fuzzyChoquetIntegral = new FuzzyChoquetIntegral;
   if (enableLBSimpleGaussian) lbSimpleGaussian = new LBSimpleGaussian;  // :108-122
   if (enableLBFuzzyGaussian) lbFuzzyGaussian = new LBFuzzyGaussian;
   if (enableLBMixtureOfGaussians) lbMixtureOfGaussians = new LBMixtureOfGaussians;
@@ -129,6 +133,8 @@ void FrameProcessor::process(const Image& img_input) {  // :169-340
   if (enableDPWrenGABGS) process("DPWrenGABGS", wrenGA, img_prep, img_wrenga);
   if (enableDPPratiMediodBGS) process("DPPratiMediodBGS", pratiMediod, img_prep, img_pramed);  // :217-224
   if (enableDPTextureBGS) process("DPTextureBGS", textureBGS, img_prep, img_texbgs);
+  if (enableFuzzySugenoIntegral) process("FuzzySugenoIntegral", fuzzySugenoIntegral, img_prep, img_fsi);  // :238-242
+  if (enableFuzzyChoquetIntegral) process("FuzzyChoquetIntegral", fuzzyChoquetIntegral, img_prep, img_fci);
   if (enableLBSimpleGaussian) process("LBSimpleGaussian", lbSimpleGaussian, img_prep, img_lb_sg);  // :244-257
   if (enableLBFuzzyGaussian) process("LBFuzzyGaussian", lbFuzzyGaussian, img_prep, img_lb_fg);
   if (enableLBMixtureOfGaussians) process("LBMixtureOfGaussians", lbMixtureOfGaussians, img_prep, img_lb_mog);
@@ -156,6 +162,8 @@ void FrameProcessor::finish() {  // :342-482 (reverse order of init)
   delete lbMixtureOfGaussians, lbMixtureOfGaussians = nullptr;
   delete lbFuzzyGaussian, lbFuzzyGaussian = nullptr;
   delete lbSimpleGaussian, lbSimpleGaussian = nullptr;
+  delete fuzzyChoquetIntegral, fuzzyChoquetIntegral = nullptr;  // :412-416
+  delete fuzzySugenoIntegral, fuzzySugenoIntegral = nullptr;
   delete textureBGS, textureBGS = nullptr;
   delete pratiMediod, pratiMediod = nullptr;
   delete wrenGA, wrenGA = nullptr;
@@ -206,6 +214,8 @@ void FrameProcessor::saveConfig() {  // :496-552 (keys of the classes this build
   fs.writeInt("enableDPWrenGABGS", enableDPWrenGABGS);
   fs.writeInt("enableDPPratiMediodBGS", enableDPPratiMediodBGS);  // :522-524
   fs.writeInt("enableDPTextureBGS", enableDPTextureBGS);
+  fs.writeInt("enableFuzzySugenoIntegral", enableFuzzySugenoIntegral);  // :530-531
+  fs.writeInt("enableFuzzyChoquetIntegral", enableFuzzyChoquetIntegral);
   fs.writeInt("enableLBSimpleGaussian", enableLBSimpleGaussian);  // :533-537
   fs.writeInt("enableLBFuzzyGaussian", enableLBFuzzyGaussian);
   fs.writeInt("enableLBMixtureOfGaussians", enableLBMixtureOfGaussians);
@@ -240,6 +250,8 @@ void FrameProcessor::loadConfig() {  // :554-610 (defaults: PreProcessor and Fra
   enableDPWrenGABGS = fs.readInt("enableDPWrenGABGS", false);
   enableDPPratiMediodBGS = fs.readInt("enableDPPratiMediodBGS", false);  // :580-582
   enableDPTextureBGS = fs.readInt("enableDPTextureBGS", false);
+  enableFuzzySugenoIntegral = fs.readInt("enableFuzzySugenoIntegral", false);  // :588-589
+  enableFuzzyChoquetIntegral = fs.readInt("enableFuzzyChoquetIntegral", false);
   enableLBSimpleGaussian = fs.readInt("enableLBSimpleGaussian", false);  // :591-595
   enableLBFuzzyGaussian = fs.readInt("enableLBFuzzyGaussian", false);
   enableLBMixtureOfGaussians = fs.readInt("enableLBMixtureOfGaussians", false);

@@ -4,9 +4,10 @@
 //   hipbgs::FrameDifferenceBGS, StaticFrameDifferenceBGS, WeightedMovingMeanBGS, WeightedMovingVarianceBGS,
 //   AdaptiveBackgroundLearning, AdaptiveSelectiveBackgroundLearning, MixtureOfGaussianV1BGS, MixtureOfGaussianV2BGS, GMG,
 //   SigmaDeltaBGS, SuBSENSEBGS, LOBSTERBGS, DPZivkovicAGMMBGS, DPGrimsonGMMBGS, DPWrenGABGS, DPMeanBGS, DPAdaptiveMedianBGS, KDE,
-//   DPPratiMediodBGS, DPTextureBGS, LBSimpleGaussian, LBFuzzyGaussian, LBMixtureOfGaussians, LBAdaptiveSOM, LBFuzzyAdaptiveSOM, VuMeter
+//   DPPratiMediodBGS, DPTextureBGS, LBSimpleGaussian, LBFuzzyGaussian, LBMixtureOfGaussians, LBAdaptiveSOM, LBFuzzyAdaptiveSOM, VuMeter,
+//   FuzzySugenoIntegral, FuzzyChoquetIntegral
 // Each reads / writes the same ./config/<Class>.xml with the same keys and defaults as the class it stands in for
-// (the list is bgs_classes.inc + bgs_classes_kde.inc + bgs_classes_dp2.inc + bgs_classes_lb.inc + bgs_classes_vumeter.inc, shared verbatim with this repository's tested host mirror, tracking_amd/host/bgs_host.h).
+// (the list is bgs_classes.inc + bgs_classes_kde.inc + bgs_classes_dp2.inc + bgs_classes_lb.inc + bgs_classes_vumeter.inc + bgs_classes_fuzzy.inc, shared verbatim with this repository's tested host mirror, tracking_amd/host/bgs_host.h).
 //
 // Use:   mixtureOfGaussianV2BGS = new hipbgs::MixtureOfGaussianV2BGS;      // FrameProcessor.cpp:59-60
 //        if(i==36) bgs = new hipbgs::SuBSENSEBGS();                          // ustc_src/ustc_bgs.cpp:68
@@ -83,6 +84,7 @@ class HipBGSBase : public IBGS {
     } else if (bgs_set_params(engine_, &params_)) {
       fail();
     }
+    if (applyClassParams(engine_)) fail();
     const int bg_ch = (algo_ == BGS_ASBL || algo_ == BGS_VUMETER) ? 1 : img_input.channels();
     fg_.create(img_input.size(), CV_8UC1);
     bg_.create(img_input.size(), CV_MAKETYPE(CV_8U, bg_ch));
@@ -131,6 +133,7 @@ class HipBGSBase : public IBGS {
   std::string configPath() const { return std::string("./config/") + name_ + ".xml"; }
   bool firstTime;
   bgs_params params_;
+  virtual int applyClassParams(bgs_engine*) { return 0; }  // parameters outside bgs_params (bgs_classes_fuzzy.inc), before every frame
   int fg_channels_;  // 3: the class hands its caller an 8UC3 mask with equal channels (bgs_classes_lb.inc)
 
  private:
@@ -156,6 +159,7 @@ class HipBGSBase : public IBGS {
 #include "bgs_classes_dp2.inc"
 #include "bgs_classes_lb.inc"
 #include "bgs_classes_vumeter.inc"
+#include "bgs_classes_fuzzy.inc"
 #ifdef BGS_HIP_DEFINED_OVERRIDE
 #undef override
 #undef BGS_HIP_DEFINED_OVERRIDE

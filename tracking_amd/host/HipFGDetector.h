@@ -52,6 +52,8 @@ class HipFGDetector : public CvFGDetector {
     if (i == 13) bgs = new hipbgs::DPWrenGABGS;
     if (i == 14) bgs = new hipbgs::DPPratiMediodBGS;
     if (i == 16) bgs = new hipbgs::DPTextureBGS;
+    if (i == 21) bgs = new hipbgs::FuzzySugenoIntegral;
+    if (i == 22) bgs = new hipbgs::FuzzyChoquetIntegral;
     if (i == 25) bgs = new hipbgs::LBSimpleGaussian;
     if (i == 26) bgs = new hipbgs::LBFuzzyGaussian;
     if (i == 27) bgs = new hipbgs::LBMixtureOfGaussians;

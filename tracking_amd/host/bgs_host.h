@@ -187,6 +187,7 @@ class HipBGSBase : public IBGS {
       int rc = bgs_set_params(engine_, &params_);
       if (rc) throw Exception(rc, std::string(name_) + ": " + bgs_last_error());
     }
+    if (int rc = applyClassParams(engine_)) throw Exception(rc, std::string(name_) + ": " + bgs_last_error());
     const int bg_ch = (algo_ == BGS_ASBL || algo_ == BGS_VUMETER) ? 1 : img_input.channels();
     fg_.create(img_input.rows, img_input.cols, 1);
     bg_.create(img_input.rows, img_input.cols, bg_ch);
@@ -240,6 +241,8 @@ class HipBGSBase : public IBGS {
   std::string configPath() const { return std::string("./config/") + name_ + ".xml"; }
   bool firstTime;
   bgs_params params_;
+  // parameters that do not travel in bgs_params (bgs_classes_fuzzy.inc): handed over before every frame, after bgs_set_params
+  virtual int applyClassParams(bgs_engine*) { return 0; }
   int fg_channels_ = 1;  // 3: the class hands its caller an 8UC3 mask with equal channels, like the reference's lb/ wrappers (bgs_classes_lb.inc)
 
  private:
@@ -282,6 +285,7 @@ class HipBGSBase : public IBGS {
 #include "bgs_classes_dp2.inc"
 #include "bgs_classes_lb.inc"
 #include "bgs_classes_vumeter.inc"
+#include "bgs_classes_fuzzy.inc"
 
 #undef BGS_HIP_BANNER_DTOR
 

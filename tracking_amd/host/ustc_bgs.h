@@ -2,9 +2,9 @@
 // cvCreateBlobTrackerAuto1 (ustc_src/trackingMain.cpp:33-35, :613-618; the shipped build uses type 36 = SuBSENSE).
 // Same type table, same Process / GetMask / Release protocol; OpenCV-legacy's CvFGDetector base and IplImage are not in this
 // image, so the mask is handed out as a bgs_hip::Image (INTEGRATION.md shows the IplImage-returning version for the reference).
-// Types whose class is outside the hot path (ustc_bgs.cpp:23-58: dp Eigenbackground, tb/, jmo/, LbpMrf, ck/, db/, sjn/; of
-// ae/ only KDE, type 32, of lb/ the five per-pixel models, types 25-29, and av/'s VuMeter, type 31, are built) throw instead of
-// silently running something else.
+// Types whose class is outside the hot path (ustc_bgs.cpp:23-58: dp Eigenbackground, tb/'s T2FGMM and T2FMRF pairs, jmo/, LbpMrf,
+// ck/, db/, sjn/; of ae/ only KDE, type 32, of lb/ the five per-pixel models, types 25-29, av/'s VuMeter, type 31, and of tb/ the two
+// fuzzy integrals, types 21 and 22, are built) throw instead of silently running something else.
 #pragma once
 #include "bgs_host.h"
 #include "blob.h"
@@ -36,6 +36,8 @@ class USTC_BGS {
     if (i == 13) bgs = new DPWrenGABGS;
     if (i == 14) bgs = new DPPratiMediodBGS;
     if (i == 16) bgs = new DPTextureBGS;
+    if (i == 21) bgs = new FuzzySugenoIntegral;
+    if (i == 22) bgs = new FuzzyChoquetIntegral;
     if (i == 25) bgs = new LBSimpleGaussian;
     if (i == 26) bgs = new LBFuzzyGaussian;
     if (i == 27) bgs = new LBMixtureOfGaussians;
