@@ -235,3 +235,65 @@ def test_host_arena_cameras_dma_in_place_equal_the_oracle():
     ofg, _ = orcs[0].process(clips[0, 0])
     assert np.array_equal(fgs[0], ofg)
     eng.close()
+
+
+def _known_ids():
+    """Every id for which the header's own BGS_ALGO_KNOWN holds: the macro's expression, read from include/bgs_hip.h and evaluated."""
+    import os
+    import re
+    text = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), os.pardir, "include", "bgs_hip.h")).read()
+    expr = re.search(r"#define BGS_ALGO_KNOWN\(id\) (.*)", text).group(1)
+    last = int(re.search(r"BGS_ALGO_LAST = (\d+)", text).group(1))
+    expr = expr.replace("(int)(id)", "i").replace("(int)BGS_ALGO_LAST", str(last)).replace("&&", " and ").replace("||", " or ")
+    assert re.fullmatch(r"[\di<>=()andor ]+", expr), expr
+    return [i for i in range(-1, last + 2) if eval(expr, {"i": i})]
+
+
+KNOWN_IDS = _known_ids()
+
+
+@pytest.mark.parametrize("algo", KNOWN_IDS)
+def test_packed_only_call_equals_byte_mask_call_for_every_algorithm(algo):
+    """Two engines of one class, default parameters, 3 streams of 3-channel frames, 34 frames (past the largest default warm-up),
+    stream 1 reset at step 20: one engine is asked for byte masks only, the other for packed masks only.  Wherever a stream's flags
+    say BGS_FG_VALID the words are the byte mask's bits (tail bits zero), and the flags of the two engines agree on every stream at
+    every step - at 16x64 (pixels % 64 == 0: the kernels write the words) and at 10x13 (ragged, cols % 4 != 0: packed from bytes).
+    Every family's key, byte-mask need, per-stream flags, reset, state refusal and release in one place.  Id 10 (BGS_LBSP_DESC) is
+    known but is no engine class: its geometry is refused."""
+    torch = _torch()
+    S, T = 3, 34
+    if algo == capi.LBSP_DESC:
+        eng = Engine(algo, n_streams=S)
+        with pytest.raises(capi.BgsError) as ei:
+            eng.set_geometry(16, 64, 3)
+        assert ei.value.code == capi.ERR_UNSUPPORTED and "not implemented in this build" in str(ei.value)
+        eng.close()
+        return
+    for H, W in ((16, 64), (10, 13)):
+        n, Wd = H * W, (H * W + 63) // 64
+        clips = torch.from_numpy(np.stack([synth.random_frames(T, H, W, 3, seed=700 + s) for s in range(S)], axis=1)).cuda()  # [T][S][H][W][3]
+        a, b = Engine(algo, n_streams=S), Engine(algo, n_streams=S)
+        a.set_geometry(H, W, 3), b.set_geometry(H, W, 3)
+        for step in range(T):
+            if step == 20:
+                a.reset_stream(1), b.reset_stream(1)
+            d_fg = torch.full((S, H, W), 9, dtype=torch.uint8, device="cuda")
+            d_bits = torch.full((S, Wd), -1, dtype=torch.int64, device="cuda")
+            a.process_batch_device(clips[step], d_fg, None, None)
+            b.process_batch_device(clips[step], None, None, d_bits)
+            torch.cuda.synchronize()
+            fg, bits = d_fg.cpu().numpy().reshape(S, n), d_bits.cpu().numpy().view(np.uint64)
+            for s in range(S):
+                fl = a.stream_flags(s)
+                assert fl == b.stream_flags(s), (algo, H, W, step, s)
+                if fl & capi.FG_VALID:
+                    want = np.zeros(Wd * 8, np.uint8)
+                    want[:(n + 7) // 8] = np.packbits(fg[s] != 0, bitorder="little")  # the tail bits of the last word stay zero
+                    assert np.array_equal(bits[s], want.view(np.uint64)), (algo, H, W, step, s)
+        for s in (0, 2):
+            assert a.stream_flags(s) & capi.FG_VALID, (algo, H, W, s, "no mask by frame %d: nothing was compared" % T)
+        for eng in (a, b):
+            with pytest.raises(capi.BgsError) as ei:
+                eng.get_state("no_such_plane", (1,), np.uint8, stream=0)
+            assert ei.value.code == capi.ERR_STATE and "unknown state plane" in str(ei.value)
+            eng.close()

@@ -5,6 +5,11 @@
 // (package_bgs/IBGS.h:24) into ONE fused kernel launch.  Host entry points stage through pinned memory;
 // device entry points take HBM pointers and launch over streams x pixels.  There is no CPU fallback: if HIP
 // is unavailable every compute entry point fails with BGS_ERR_HIP.
+//
+// This file holds what every class shares: the engine's members, allocation helpers, the split of a call into runs of streams
+// (launch_key), the packed-mask plumbing, clip calls, the host path and the C entry points.  What a class does - checks, model
+// allocation, the launch key, one frame, a fused clip, the state export - lives in its engine_*.h and is reached only through
+// that file's `Family` of entry points, looked up once per engine by family_of() below.
 #include "../../include/bgs_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -90,19 +95,21 @@ inline unsigned blocks_for(size_t groups) { return (unsigned)((groups + bgs::kBl
 
 namespace {
 struct SsDevice;  // engine_subsense.h
+struct Family;    // below
 }
-
 
 // One virtual address range backed by separately created physical chunks (hipMemAddressReserve + hipMemCreate x n + hipMemMap): how
 // the big models are placed (model_allocate) and what bgs_calibrate_copy measures beside a plain hipMalloc.
 struct VmmRange {
   std::vector<hipMemGenericAllocationHandle_t> handles;
   void* base = nullptr;
+  void** owner = nullptr;  // the engine member model_allocate filled with `base` (free_all nulls it: the range is not hipFree's to release)
   size_t bytes = 0, chunk = 0, mapped = 0;  // mapped: chunks actually mapped (a failure half-way leaves fewer than handles)
 };
 
 struct bgs_engine {
   bgs_algo algo;
+  const Family* fam = nullptr;  // the class's entry points (family_of)
   bgs_params p;
   int device = 0;
   int S = 1;
@@ -169,9 +176,7 @@ struct bgs_engine {
   uint8_t *fz_code = nullptr, *fz_bprod = nullptr;
   uint32_t* fz_minmax = nullptr;
   std::vector<int64_t> fz_fn;        // frameNumber of each stream's object
-  std::vector<uint32_t> fz_flags;    // out_flags of each stream's last frame (streams of one launch differ)
   std::vector<uint8_t> fz_detected;  // the stream has an integral image
-  bool fz_any_valid = false;         // the last run held a detecting stream
   int lb_px = 1;                   // pixels per lane of the two Gaussian kernels (BGS_LB_PX=2: the double2 form, A/B; identical results)
   // MOG2 model (kernel_mog2.h: tiles of ranked weights + fixed-slot records + rank->slot meta words)
   uint8_t* mog2_state = nullptr;
@@ -244,20 +249,55 @@ struct bgs_engine {
 
 namespace {
 
-void ss_free(bgs_engine* e);  // engine_subsense.h
-void kde_free(bgs_engine* e);  // engine_kde.h
-int kde_check(const bgs_params& p);
-void dp2_free(bgs_engine* e);  // engine_dp2.h
-int dp2_check(bgs_algo algo, const bgs_params& p);
-void lb_free(bgs_engine* e);  // engine_lb.h
-int lb_check(bgs_algo algo, const bgs_params& p);
-void vu_free(bgs_engine* e);  // engine_vumeter.h
-void fz_free(bgs_engine* e);  // engine_fuzzy.h
-bool is_fuzzy(bgs_algo a);
+// What a class of background model plugs into the engine: one constant of this per family at the end of its engine_*.h, found by
+// family_of().  `first`, `count`: a run of streams that share every kernel argument (launch_key); d_* point at the run's first
+// stream.  Entries marked nullable may stay null.
+struct Family {
+  int (*check)(bgs_algo, const bgs_params&);                      // nullable; needs no device (bgs_create, bgs_set_params)
+  int (*check_geometry)(bgs_algo, int rows, int cols, int ch);    // nullable; refusals made before the device is opened
+  int (*allocate)(bgs_engine*);                                   // rows / cols / ch / n are set, e->stream exists; a failure is followed by release
+  void (*release)(bgs_engine*);                                   // frees whatever allocate made (possibly part of it) and nulls the pointers
+  uint64_t (*key)(const bgs_engine*, int stream);                 // streams whose next frame has the same key share a launch
+  // one frame: launches on s, advances the family's own per-stream counters, *flags = BGS_FG_VALID / BGS_BG_VALID of the run
+  int (*run)(bgs_engine*, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s, uint32_t* flags);
+  int64_t (*get_state)(bgs_engine*, int stream, const char* plane, void* dst, size_t cap);
+  void (*reset_stream)(bgs_engine*, int stream);                  // nullable; per-stream counters beyond seen / counter / last_flags
+  void (*keep_frozen)(bgs_params& p, const bgs_params& old);      // nullable; what bgs_set_params restores once the geometry is set
+  int (*apply_params)(bgs_engine*);                               // nullable; device tables that follow live parameters (bgs_set_params)
+  bool (*needs_byte_mask)(const bgs_engine*);                     // nullable (no); the packed mask is made from the finished byte mask
+  // nullable; `fuse` = 2, 4 or 8 consecutive frames of a clip in one launch that keeps the model in registers; slab: pixels from one
+  // frame of the clip to the next.  Taken when clip_fusable (nullable: always) agrees.
+  int (*clip_fused)(bgs_engine*, int first, int count, int fuse, size_t slab, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s, uint32_t* flags);
+  bool (*clip_fusable)(const bgs_engine*);
+  int bg_channels;        // channels of the background image the class hands out: 0 = as the frames, 1 = gray
+  bool per_stream_flags;  // run writes e->last_flags[first..first+count) itself and returns their AND (streams of one launch differ)
+};
+
 void vmm_free(VmmRange& v);  // below
 
-// channels of the background image a class hands out: ASBL's and VuMeter's are gray
-int bg_channels(const bgs_engine* e) { return (e->algo == BGS_ASBL || e->algo == BGS_VUMETER) ? 1 : e->ch; }
+int bg_channels(const bgs_engine* e) { return e->fam->bg_channels ? e->fam->bg_channels : e->ch; }
+
+// OR of the flags of the last frame of streams [first, first+count): did any of them produce a mask
+uint32_t any_flags(const bgs_engine* e, int first, int count) {
+  uint32_t any = 0;
+  for (int i = first; i < first + count; ++i) any |= e->last_flags[i];
+  return any;
+}
+
+bool always(const bgs_engine*) { return true; }  // needs_byte_mask of the classes whose mask is finished by a stencil pass
+
+template <class T>
+void dfree(T*& p) {
+  if (p) (void)hipFree(p), p = nullptr;
+}
+
+// bgs_get_state: `nb` device bytes at src are plane `plane`
+int64_t copy_plane(const char* plane, void* dst, size_t cap, const uint8_t* src, size_t nb) {
+  if (cap < nb) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
+  if (d2h_staged(dst, src, nb) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
+  return (int64_t)nb;
+}
+int64_t unknown_plane(const bgs_engine* e, const char* plane) { return fail(BGS_ERR_STATE, "unknown state plane '%s' for algorithm %d", plane, (int)e->algo); }
 
 void lane_release(bgs_engine::Lane& ln) {  // whatever of a lane came to be (bgs_submit's set-up may have failed half-way)
   if (ln.hs) (void)hipStreamSynchronize(ln.hs);
@@ -270,72 +310,6 @@ void lane_release(bgs_engine::Lane& ln) {  // whatever of a lane came to be (bgs
   if (ln.done) (void)hipEventDestroy(ln.done);
   if (ln.hs) (void)hipStreamDestroy(ln.hs);
   ln = bgs_engine::Lane();
-}
-
-void free_all(bgs_engine* e) {
-  for (auto& r : e->ring)
-    if (r) (void)hipFree(r), r = nullptr;
-  if (e->abl_lut) (void)hipFree(e->abl_lut), e->abl_lut = nullptr, e->abl_lut_valid = false;
-  if (e->cc_work) (void)hipFree(e->cc_work), e->cc_work = nullptr, e->cc_cap = 0;
-  if (e->pack_fg) (void)hipFree(e->pack_fg), e->pack_fg = nullptr, e->pack_fg_bytes = 0;
-  if (e->h_raw) (void)hipHostFree(e->h_raw), e->h_raw = nullptr;
-  if (e->d_raw) (void)hipFree(e->d_raw), e->d_raw = nullptr;
-  if (e->d_ingest_ws) (void)hipFree(e->d_ingest_ws), e->d_ingest_ws = nullptr;
-  e->last_fg_stream = -1;
-  if (e->vmm.base) {  // a model built by model_allocate from physical chunks: not hipFree's to release
-    if ((void*)e->mog2_state == e->vmm.base) e->mog2_state = nullptr;
-    if ((void*)e->mog1_state == e->vmm.base) e->mog1_state = nullptr;
-    if ((void*)e->dp_state == e->vmm.base) e->dp_state = nullptr;
-    if ((void*)e->lb_model == e->vmm.base) e->lb_model = nullptr;
-    if ((void*)e->vu_hist == e->vmm.base) e->vu_hist = nullptr;
-    vmm_free(e->vmm);
-  }
-  void* dev[] = {e->dp_state, e->gmg_rec, e->gmg_nfeat, e->bgstate, e->bgstate2, e->mog1_state, e->mog2_state, e->d_in, e->d_fg, e->d_bg};
-  for (void* d : dev)
-    if (d) (void)hipFree(d);
-  e->dp_state = nullptr, e->gmg_rec = nullptr, e->gmg_nfeat = nullptr, e->bgstate = e->bgstate2 = nullptr, e->mog1_state = nullptr, e->mog2_state = nullptr, e->d_in = e->d_fg = e->d_bg = nullptr;
-  void* host[] = {e->h_in, e->h_fg, e->h_bg};
-  for (void* h : host)
-    if (h) (void)hipHostFree(h);
-  e->h_in = e->h_fg = e->h_bg = nullptr;
-  for (auto& ev : e->events) (void)hipEventDestroy(ev.first), (void)hipEventDestroy(ev.second);
-  e->events.clear();
-  ss_free(e);
-  kde_free(e);
-  dp2_free(e);
-  lb_free(e);
-  vu_free(e);
-  fz_free(e);
-  if (e->d_stat) (void)hipFree(e->d_stat), e->d_stat = nullptr;
-  if (e->h_stat) (void)hipHostFree(e->h_stat), e->h_stat = nullptr;
-  for (int i = 0; i < bgs_engine::kStatSlots; ++i) {
-    if (e->stat_ev[i]) (void)hipEventDestroy(e->stat_ev[i]), e->stat_ev[i] = nullptr;
-    e->stat_posted[i] = false;
-  }
-  for (auto& ev : e->band_ev)
-    if (ev) (void)hipEventDestroy(ev), ev = nullptr;
-  for (auto& hp : e->pin) {
-    if (hp.pinned) (void)hipHostUnregister(const_cast<void*>(hp.ptr));
-    hp = bgs_engine::HostPin();
-  }
-  for (auto& a : e->arenas) (void)hipHostUnregister(const_cast<uint8_t*>(a.first));
-  e->arenas.clear();
-  for (auto& ln : e->lanes) lane_release(ln);
-}
-
-int check_params(bgs_algo algo, const bgs_params& p) {
-  if (algo == BGS_GMG && (p.gmg_max_features < 1 || p.gmg_max_features > 64)) return fail(BGS_ERR_UNSUPPORTED, "GMG maxFeatures must be 1..64, got %d", p.gmg_max_features);
-  if (algo == BGS_GMG && p.gmg_smoothing_radius != 0 && (p.gmg_smoothing_radius < 3 || p.gmg_smoothing_radius > 15 || p.gmg_smoothing_radius % 2 == 0))
-    return fail(BGS_ERR_UNSUPPORTED, "GMG smoothingRadius (cv::medianBlur kernel) must be 0 or odd 3..15, got %d", p.gmg_smoothing_radius);
-  if (algo == BGS_MOG2 && p.mog2_nmixtures != bgs::kMog2K) return fail(BGS_ERR_UNSUPPORTED, "MOG2 kernel is built for K=%d mixtures, got %d", bgs::kMog2K, p.mog2_nmixtures);
-  if (algo == BGS_MOG1 && p.mog1_nmixtures != bgs::kMog1K) return fail(BGS_ERR_UNSUPPORTED, "MOG1 kernel is built for K=%d mixtures, got %d", bgs::kMog1K, p.mog1_nmixtures);
-  if ((algo == BGS_DP_ZIVKOVIC_AGMM || algo == BGS_DP_GRIMSON_GMM) && (p.dp_gaussians < 1 || p.dp_gaussians > 5))
-    return fail(BGS_ERR_UNSUPPORTED, "dp GMM kernels are built for 1..5 gaussians, got %d", p.dp_gaussians);
-  if (algo == BGS_DP_ADAPTIVE_MEDIAN && p.dp_sampling_rate == 0) return fail(BGS_ERR_UNSUPPORTED, "AdaptiveMedian samplingRate 0 (frame_num %% 0)");
-  if (algo == BGS_KDE) return kde_check(p);
-  if (algo == BGS_DP_PRATI_MEDIOD || algo == BGS_DP_TEXTURE) return dp2_check(algo, p);
-  if (algo >= BGS_LB_SIMPLE_GAUSSIAN && algo <= BGS_LB_FUZZY_ADAPTIVE_SOM) return lb_check(algo, p);
-  return BGS_OK;
 }
 
 // Every model / history / staging buffer of an engine comes from here.  Nothing may rely on what a fresh allocation holds:
@@ -369,136 +343,6 @@ struct Timed {
     }
   }
 };
-
-// Automatic choice of how a per-frame launch loads a pixel's model (kernel_mog2.h; results are identical, only speed differs):
-//   1 eager   everything at once, no dependent loads: right when most pixels have most modes and need them;
-//   2 count   only the modes a pixel has (one dependent round): quiet scenes, one or two modes per pixel;
-//   4 filter  summaries first, then only the records they cannot rule out (one dependent round, +4 B per mode for the
-//             summaries): pays when at least half of a pixel's records are ruled out (modes far apart).
-// About 256 sampled workgroups of every filter-kernel launch count, per pixel, the modes it has and the records that kernel loads
-// or would load (when another kernel is current, every 16th launch - every 4th of a stream's first 64 - is a filter launch for
-// that purpose).  The host never blocks: the counters come back through a pinned buffer and an event that is queried before
-// every launch; it switches at once on clear evidence, else when two samples in a row ask for the same other mode.
-void mog2_stat_read(bgs_engine* e) {
-  // the newest post whose copy has completed; everything older is dropped with it
-  int slot = -1;
-  for (unsigned back = 1; back <= (unsigned)bgs_engine::kStatSlots && back <= e->stat_seq; ++back) {
-    const int i = (int)((e->stat_seq - back) % bgs_engine::kStatSlots);
-    if (!e->stat_posted[i]) break;  // already consumed (and so is everything older)
-    if (slot < 0 && hipEventQuery(e->stat_ev[i]) == hipSuccess) slot = i;
-    if (slot >= 0) e->stat_posted[i] = false;
-  }
-  if (slot < 0) return;
-  const unsigned* hs = e->h_stat + 3 * slot;
-  const unsigned total = hs[0], live = hs[1], need = hs[2];
-  if (total < 64 * 5) return;
-  const float lf = (float)live / (float)total, nf = (float)need / (float)total;
-  const int want = (nf < 0.5f * lf && lf - nf > 0.1f) ? 4 : lf < 0.7f ? 2 : 1;
-  const bool clear = (want == 4 && nf < 0.35f * lf) || (want != 4 && e->mog2_sparse_now == 4 && nf > 0.8f * lf);
-  static const bool debug = getenv("BGS_DEBUG_STAT") != nullptr;
-  if (debug)
-    fprintf(stderr, "[bgs] mog2 auto: %u record slots sampled, %.3f live, %.3f needed after the summaries -> mode %d (now %d)\n", total, lf, nf, want, e->mog2_sparse_now);
-  if (want != e->mog2_sparse_now && (clear || want == e->mog2_sparse_want)) e->mog2_sparse_now = want;
-  e->mog2_sparse_want = want;
-}
-void mog2_stat_post(bgs_engine* e, hipStream_t s) {
-  const int i = (int)(e->stat_seq % bgs_engine::kStatSlots);  // the oldest slot is reused (its event re-recorded) if nobody read it
-  (void)hipMemcpyAsync(e->h_stat + 3 * i, e->d_stat, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, s);
-  (void)hipMemsetAsync(e->d_stat, 0, 3 * sizeof(unsigned), s);
-  (void)hipEventRecord(e->stat_ev[i], s);
-  e->stat_posted[i] = true;
-  e->stat_seq++;
-}
-
-int launch_mog2(bgs_engine* e, bgs::Mog2Args& a, hipStream_t s, bool timed = true) {
-  const bgs_params& p = e->p;
-  // shadow test only when it can change the delivered mask: not thresholded, or the threshold separates shadow from foreground
-  a.shadow = p.mog2_detect_shadows && (!p.enable_threshold || ((p.mog2_shadow_value > p.threshold) != (255 > p.threshold)));
-  a.want_bg = a.bgimg != nullptr, a.packed = a.fg_bits != nullptr;
-  a.xcd_swizzle = e->xcd_swizzle, a.complete = e->mog2_complete;
-  const bool autom = timed && e->mog2_sparse == 3;
-  if (autom) mog2_stat_read(e);
-  int mode = e->mog2_sparse == 3 ? e->mog2_sparse_now : e->mog2_sparse;
-  if (mode >= 4 && (a.shadow || a.want_bg)) mode = 2;  // shadow test and background image read every mode's mean: nothing to rule out
-  // auto mode: the filter kernel's sampled workgroups count what each way of loading would read; when another kernel is current,
-  // every 16th launch (every 4th of the first 64) goes through the filter kernel anyway so that the choice keeps following the scene
-  if (autom && mode != 4) {
-    const unsigned n = e->mog2_launches++;
-    if ((n & (n < 64 ? 3u : 15u)) == 0) mode = 4;
-  }
-  a.sparse = mode;
-  a.stat = (autom && mode == 4) ? e->d_stat : nullptr;
-  if (a.packed && a.npix % 64) return fail(BGS_ERR_UNSUPPORTED, "packed mask needs pixels %% 64 == 0");
-  Timed t(e, s, "mog2_update_kernel", timed);
-  const dim3 grid(blocks_for(a.npix)), block(bgs::kBlock);  // one pixel per lane (round 2's 1 / 2 / 4 comparison: equal or better everywhere)
-  unsigned every = 1;  // sample about 256 workgroups per launch whatever the grid: enough to decide, few enough atomics not to show
-  while (grid.x / every > 256) every <<= 1;
-  a.stat_mask = every - 1;
-  // BGS_MOG2_LDS_PAD=bytes: unused dynamic LDS per workgroup - fewer workgroups fit a CU (160 KB): the occupancy study of DESIGN.md 6.1
-  // (round 4: 2 / 3 / 4 / 5 waves per SIMD 2.15 / 1.50 / 1.22 / 1.09 ms; a build of the filter kernel without the shadow and background
-  // code - 66 instead of 91 VGPRs, 7 waves - ran no faster than this one's 5: profiles/r04_mog2_occupancy_ab.txt)
-  static const unsigned lds_pad = getenv("BGS_MOG2_LDS_PAD") ? (unsigned)std::max(0, std::min(65536, atoi(getenv("BGS_MOG2_LDS_PAD")))) : 0u;
-  if (mode >= 4)
-    hipLaunchKernelGGL((bgs::mog2_update_kernel<bgs::kMog2Filter>), grid, block, lds_pad, s, a);
-  else if (mode >= 2)
-    hipLaunchKernelGGL((bgs::mog2_update_kernel<bgs::kMog2Count>), grid, block, lds_pad, s, a);
-  else
-    hipLaunchKernelGGL((bgs::mog2_update_kernel<bgs::kMog2Eager>), grid, block, lds_pad, s, a);
-  if (a.stat) mog2_stat_post(e, s);
-  return BGS_OK;
-}
-
-void mog1_fill_args(const bgs_engine* e, bgs::Mog1Args& m, double lr) {
-  const bgs_params& p = e->p;
-  const int C = e->ch;
-  const double defaultNoiseSigma = 30 * 0.5;
-  m.alpha = (float)lr, m.T = (float)p.mog1_background_ratio, m.vT = (float)p.mog1_var_threshold;
-  m.w0 = (float)0.05;
-  m.sk0 = C == 3 ? (float)(m.w0 / (defaultNoiseSigma * 2 * std::sqrt(3.))) : (float)(m.w0 / (defaultNoiseSigma * 2));
-  m.var0 = (float)(defaultNoiseSigma * defaultNoiseSigma * 4);
-  m.minVar = (float)(p.mog1_noise_sigma * p.mog1_noise_sigma);
-  m.thr = p.threshold, m.enable_thr = p.enable_threshold, m.packed = m.fg_bits != nullptr, m.xcd_swizzle = e->xcd_swizzle;
-}
-
-void mog2_fill_args(const bgs_engine* e, bgs::Mog2Args& m, double lr) {
-  const bgs_params& p = e->p;
-  m.state = e->mog2_state;
-  m.alphaT = (float)lr, m.alpha1 = 1.f - m.alphaT, m.prune = (float)(-lr * (double)p.mog2_ct);
-  m.Tb = p.mog2_var_threshold, m.TB = p.mog2_background_ratio, m.Tg = p.mog2_var_threshold_gen;
-  m.varInit = p.mog2_var_init, m.varMin = p.mog2_var_min, m.varMax = p.mog2_var_max, m.tau = p.mog2_tau;
-  m.thr = p.threshold, m.enable_thr = p.enable_threshold, m.shadow_val = p.mog2_shadow_value;
-}
-
-void mog2_clear(bgs_engine* e, const bgs::Mog2Args& m, hipStream_t s) {
-  hipLaunchKernelGGL(bgs::mog2_clear_kernel, dim3(blocks_for(m.npix)), dim3(bgs::kBlock), 0, s, m);
-}
-
-// One launch over `fuse` (2, 4 or 8) consecutive frames of streams whose model starts at c.m.state_off (kernel_mog2.h, clip launches)
-int launch_mog2_clip(bgs_engine* e, bgs::Mog2ClipArgs& c, int fuse, hipStream_t s) {
-  const bgs_params& p = e->p;
-  bgs::Mog2Args& a = c.m;
-  a.shadow = p.mog2_detect_shadows && (!p.enable_threshold || ((p.mog2_shadow_value > p.threshold) != (255 > p.threshold)));
-  a.want_bg = a.bgimg != nullptr, a.packed = a.fg_bits != nullptr;
-  a.xcd_swizzle = e->xcd_swizzle, a.complete = e->mog2_complete;
-  a.sparse = e->mog2_sparse == 0 ? 0 : 1;  // clip launches load every record at once (kernel_mog2.h)
-  a.stat = nullptr;
-  if (a.packed && a.npix % 64) return fail(BGS_ERR_UNSUPPORTED, "packed mask needs pixels %% 64 == 0");
-  Timed t(e, s, "mog2_clip_kernel");
-  const dim3 grid(blocks_for(a.npix)), block(bgs::kBlock);
-  unsigned every = 1;
-  while (grid.x / every > 256) every <<= 1;
-  a.stat_mask = every - 1;
-#define MOG2_CLIP_CASE(TV) \
-  if (fuse == TV) hipLaunchKernelGGL((bgs::mog2_clip_kernel<TV>), grid, block, 0, s, c);
-  MOG2_CLIP_CASE(2) MOG2_CLIP_CASE(4) MOG2_CLIP_CASE(8)
-#undef MOG2_CLIP_CASE
-  return BGS_OK;
-}
-
-size_t mog2_state_bytes(const bgs_engine* e) {
-  const size_t P = e->n * e->S;
-  return (P + bgs::kMog2Tile - 1) / bgs::kMog2Tile * bgs::kMog2TileBytes;
-}
 
 // Model allocation for the big, long-lived models (MOG2, MOG1, dp): ONE virtual range backed by separately created physical chunks.
 // Measured on MI355X in rounds 1-3 (profiles/r02_placement_probe.txt, profiles/r03_placement.txt): the same kernel on
@@ -551,7 +395,7 @@ void vmm_free(VmmRange& v) {
   for (size_t i = 0; i < v.mapped; ++i) warn("hipMemUnmap", hipMemUnmap((char*)v.base + i * v.chunk, v.chunk));
   for (auto& h : v.handles) warn("hipMemRelease", hipMemRelease(h));
   warn("hipMemAddressFree", hipMemAddressFree(v.base, v.bytes));
-  v.handles.clear(), v.base = nullptr, v.bytes = 0, v.mapped = 0;
+  v.handles.clear(), v.base = nullptr, v.owner = nullptr, v.bytes = 0, v.mapped = 0;
 }
 
 // A model of `bytes`: chunked (see above) from 768 MB up - smaller ones sit in the 256 MiB Infinity Cache for a good part and are
@@ -559,6 +403,7 @@ void vmm_free(VmmRange& v) {
 int model_allocate(bgs_engine* e, void** out, size_t bytes) {
   if (e->model_chunk_mb > 0 && bytes >= e->model_chunk_min_bytes && !e->vmm.base) {
     if (vmm_allocate(e->vmm, e->device, out, bytes, (size_t)e->model_chunk_mb << 20) == BGS_OK) {
+      e->vmm.owner = out;
       if (e->poison) HIP_TRY(hipMemsetAsync(*out, 0xA5, e->vmm.bytes, e->stream));
       return BGS_OK;
     }
@@ -569,15 +414,13 @@ int model_allocate(bgs_engine* e, void** out, size_t bytes) {
   return dmalloc(e, out, bytes);
 }
 
-int mog2_allocate(bgs_engine* e) {
-  const size_t bytes = mog2_state_bytes(e);
-  HIP_TRY(hipMalloc((void**)&e->d_stat, 3 * sizeof(unsigned)));
-  HIP_TRY(hipMemsetAsync(e->d_stat, 0, 3 * sizeof(unsigned), e->stream));  // ordered: allocate() drains e->stream before it returns
-  HIP_TRY(hipHostMalloc((void**)&e->h_stat, 3 * bgs_engine::kStatSlots * sizeof(unsigned), hipHostMallocDefault));
-  for (int i = 0; i < bgs_engine::kStatSlots; ++i) HIP_TRY(hipEventCreateWithFlags(&e->stat_ev[i], hipEventDisableTiming));
-  return model_allocate(e, (void**)&e->mog2_state, bytes);
-}
-
+// The families.  Order matters where one borrows from another: engine_asbl.h and engine_gmg.h use engine_pointwise.h's launch macro
+// and "bg" export, engine_mog2.h uses engine_mog1.h's launch key.
+#include "engine_pointwise.h"
+#include "engine_asbl.h"
+#include "engine_gmg.h"
+#include "engine_mog1.h"
+#include "engine_mog2.h"
 #include "engine_subsense.h"
 #include "engine_dp.h"
 #include "engine_kde.h"
@@ -586,144 +429,99 @@ int mog2_allocate(bgs_engine* e) {
 #include "engine_vumeter.h"
 #include "engine_fuzzy.h"
 
-// (Re)build ABL's lookup table for the current alpha on e->stream.  Called when the geometry is set and when bgs_set_params
-// changes alpha; both drain the device first / the stream after, so no launch on any stream sees a half-written table.
-int abl_build_lut(bgs_engine* e) {
-  if (!e->abl_lut) HIP_TRY(hipMalloc((void**)&e->abl_lut, 256 * 256));
-  hipLaunchKernelGGL(bgs::abl_lut_kernel, dim3(256), dim3(bgs::kBlock), 0, e->stream, e->abl_lut, e->p.alpha, 1 - e->p.alpha);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  e->abl_lut_alpha = e->p.alpha, e->abl_lut_valid = true;
-  return BGS_OK;
+// an id that BGS_ALGO_KNOWN accepts but no engine class stands behind (BGS_LBSP_DESC is a stand-alone entry point): refused when the geometry is set
+constexpr Family kUnbuilt = [] {
+  Family f{};
+  f.allocate = [](bgs_engine* e) -> int { return fail(BGS_ERR_UNSUPPORTED, "algorithm %d is not implemented in this build", (int)e->algo); };
+  f.release = [](bgs_engine*) {};
+  return f;
+}();
+
+// THE table: which family stands behind an id.  No default: an enumerator nobody wired in is -Wall's switch warning.
+const Family* family_of(bgs_algo algo) {
+  switch (algo) {
+    case BGS_FRAME_DIFF:
+    case BGS_WMM:
+    case BGS_WMV: return &kFrameHistory;
+    case BGS_STATIC_FRAME_DIFF: return &kStaticFrameDiff;
+    case BGS_ABL: return &kAbl;
+    case BGS_ASBL: return &kAsbl;
+    case BGS_SIGMA_DELTA: return &kSigmaDelta;
+    case BGS_GMG: return &kGmg;
+    case BGS_MOG1: return &kMog1;
+    case BGS_MOG2: return &kMog2;
+    case BGS_SUBSENSE: return &kSubsense;
+    case BGS_LOBSTER: return &kLobster;
+    case BGS_DP_ZIVKOVIC_AGMM:
+    case BGS_DP_GRIMSON_GMM:
+    case BGS_DP_WREN_GA:
+    case BGS_DP_MEAN:
+    case BGS_DP_ADAPTIVE_MEDIAN: return &kDp;
+    case BGS_KDE: return &kKde;
+    case BGS_DP_PRATI_MEDIOD: return &kDpPratiMediod;
+    case BGS_DP_TEXTURE: return &kDpTexture;
+    case BGS_LB_SIMPLE_GAUSSIAN:
+    case BGS_LB_FUZZY_GAUSSIAN:
+    case BGS_LB_MOG:
+    case BGS_LB_ADAPTIVE_SOM:
+    case BGS_LB_FUZZY_ADAPTIVE_SOM: return &kLb;
+    case BGS_VUMETER: return &kVuMeter;
+    case BGS_FUZZY_SUGENO:
+    case BGS_FUZZY_CHOQUET: return &kFuzzy;
+    case BGS_LBSP_DESC:
+    case BGS_ALGO_END:
+    case BGS_ALGO_LIMIT:
+    case BGS_ALGO_LAST: break;
+  }
+  return &kUnbuilt;
 }
 
-// ASBL's two tables (learning / detection phase), same rules
-int asbl_build_lut(bgs_engine* e) {
-  const size_t one = (size_t)bgs::kAsblLutRows * 256;
-  if (!e->abl_lut) HIP_TRY(hipMalloc((void**)&e->abl_lut, 2 * one));
-  const bgs_params& p = e->p;
-  for (int learn = 1; learn >= 0; --learn)
-    hipLaunchKernelGGL(bgs::asbl_lut_kernel, dim3(bgs::kAsblLutRows), dim3(bgs::kBlock), 0, e->stream, e->abl_lut + (learn ? 0 : one), learn, p.alpha_learn, 1 - p.alpha_learn,
-                       p.alpha_detection, 1 - p.alpha_detection);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  e->asbl_lut_alpha[0] = p.alpha_learn, e->asbl_lut_alpha[1] = p.alpha_detection, e->abl_lut_valid = true;
-  return BGS_OK;
+void free_all(bgs_engine* e) {
+  if (e->vmm.base) {  // a model built by model_allocate from physical chunks: not hipFree's to release
+    if (e->vmm.owner) *e->vmm.owner = nullptr;
+    vmm_free(e->vmm);
+  }
+  e->fam->release(e);
+  dfree(e->cc_work), e->cc_cap = 0;
+  dfree(e->pack_fg), e->pack_fg_bytes = 0;
+  if (e->h_raw) (void)hipHostFree(e->h_raw), e->h_raw = nullptr;
+  dfree(e->d_raw), dfree(e->d_ingest_ws);
+  e->last_fg_stream = -1;
+  dfree(e->d_in), dfree(e->d_fg), dfree(e->d_bg);
+  void* host[] = {e->h_in, e->h_fg, e->h_bg};
+  for (void* h : host)
+    if (h) (void)hipHostFree(h);
+  e->h_in = e->h_fg = e->h_bg = nullptr;
+  for (auto& ev : e->events) (void)hipEventDestroy(ev.first), (void)hipEventDestroy(ev.second);
+  e->events.clear();
+  for (auto& ev : e->band_ev)
+    if (ev) (void)hipEventDestroy(ev), ev = nullptr;
+  for (auto& hp : e->pin) {
+    if (hp.pinned) (void)hipHostUnregister(const_cast<void*>(hp.ptr));
+    hp = bgs_engine::HostPin();
+  }
+  for (auto& a : e->arenas) (void)hipHostUnregister(const_cast<uint8_t*>(a.first));
+  e->arenas.clear();
+  for (auto& ln : e->lanes) lane_release(ln);
+}
+
+int check_params(bgs_algo algo, const bgs_params& p) {
+  const Family* f = family_of(algo);
+  return f->check ? f->check(algo, p) : BGS_OK;
 }
 
 int allocate(bgs_engine* e, int rows, int cols, int ch) {
   if (rows <= 0 || cols <= 0) return fail(BGS_ERR_INVALID, "bad geometry %dx%d", rows, cols);
   if (ch != 1 && ch != 3) return fail(BGS_ERR_UNSUPPORTED, "channels must be 1 or 3, got %d", ch);
-  if (e->algo == BGS_MOG2 && ch != 3)
-    return fail(BGS_ERR_UNSUPPORTED, "MixtureOfGaussianV2BGS needs 3 channels: getBackgroundImage asserts nchannels == 3 (MixtureOfGaussianV2BGS.cpp:59)");
-  if (e->algo == BGS_VUMETER && ch != 3)
-    return fail(BGS_ERR_UNSUPPORTED, "VuMeter reads 3-channel frames only (cvCvtColor(frame, gray, CV_RGB2GRAY) asserts, VuMeter.cpp:49)");
-  if (is_fuzzy(e->algo)) {
-    int rc = fz_check_geometry(e->algo, rows, cols, ch);
+  if (e->fam->check_geometry) {
+    int rc = e->fam->check_geometry(e->algo, rows, cols, ch);
     if (rc) return rc;
   }
   HIP_TRY(hipSetDevice(e->device));
   e->rows = rows, e->cols = cols, e->ch = ch, e->n = (size_t)rows * cols;
-  const size_t P = e->n * e->S, fb = P * ch;
   if (!e->stream) HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-  switch (e->algo) {
-    case BGS_FRAME_DIFF: e->nring = 2; break;
-    case BGS_WMM:
-    case BGS_WMV: e->nring = 3; break;
-    case BGS_STATIC_FRAME_DIFF:
-    case BGS_ABL: e->state_ch = ch; break;
-    case BGS_ASBL: e->state_ch = 1; break;
-    case BGS_SIGMA_DELTA:
-      if (ch != 3) return fail(BGS_ERR_UNSUPPORTED, "SigmaDeltaBGS is 3-channel only (sdLaMa091AllocInit_8u_C3R, SigmaDeltaBGS.cpp:35)");
-      e->state_ch = 3;
-      break;
-    case BGS_GMG: e->state_ch = 1; break;  // bgstate = the unsmoothed mask
-    case BGS_MOG1:
-    case BGS_MOG2:
-    case BGS_SUBSENSE:
-    case BGS_LOBSTER: break;
-    case BGS_DP_ZIVKOVIC_AGMM:
-    case BGS_DP_GRIMSON_GMM: e->state_ch = 1; break;  // bgstate = modes per pixel
-    case BGS_DP_WREN_GA:
-    case BGS_DP_MEAN: break;
-    case BGS_DP_ADAPTIVE_MEDIAN: e->state_ch = 3; break;  // bgstate = the median image
-    case BGS_KDE:
-    case BGS_DP_PRATI_MEDIOD:
-    case BGS_DP_TEXTURE:
-    case BGS_LB_SIMPLE_GAUSSIAN:
-    case BGS_LB_FUZZY_GAUSSIAN:
-    case BGS_LB_MOG:
-    case BGS_LB_ADAPTIVE_SOM:
-    case BGS_LB_FUZZY_ADAPTIVE_SOM:
-    case BGS_VUMETER:
-    case BGS_FUZZY_SUGENO:
-    case BGS_FUZZY_CHOQUET: break;
-    default: return fail(BGS_ERR_UNSUPPORTED, "algorithm %d is not implemented in this build", (int)e->algo);
-  }
-  for (int i = 0; i < e->nring; ++i) DMALLOC(e->ring[i], fb);
-  if (e->state_ch) DMALLOC(e->bgstate, P * e->state_ch);
-  if (e->algo == BGS_ABL) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, e->device) == hipSuccess && prop.multiProcessorCount > 0) e->n_cu = prop.multiProcessorCount;
-    int rc = abl_build_lut(e);
-    if (rc) return rc;
-  }
-  if (e->algo == BGS_ASBL) {
-    DMALLOC(e->bgstate2, P);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, e->device) == hipSuccess && prop.multiProcessorCount > 0) e->n_cu = prop.multiProcessorCount;
-    int rc = asbl_build_lut(e);
-    if (rc) return rc;
-  }
-  if (e->algo == BGS_SIGMA_DELTA) DMALLOC(e->bgstate2, P * 3);  // Vt
-  if (e->algo == BGS_GMG) {
-    const size_t F = (size_t)e->p.gmg_max_features;
-    DMALLOC(e->gmg_rec, P * F * sizeof(int2));
-    DMALLOC(e->gmg_nfeat, P);
-  }
-  if (e->algo == BGS_MOG1) {
-    const size_t tile_floats = ch == 3 ? bgs::mog1_tile_floats<3>() : bgs::mog1_tile_floats<1>();
-    const size_t tiles = (P + bgs::kMog1Tile - 1) / bgs::kMog1Tile;
-    const size_t bytes = tiles * tile_floats * sizeof(float);
-    int rc = model_allocate(e, (void**)&e->mog1_state, bytes);
-    if (rc) return rc;
-  }
-  if (e->algo == BGS_MOG2) {
-    int rc = mog2_allocate(e);
-    if (rc) return rc;
-  }
-  if (e->algo == BGS_SUBSENSE) {
-    int rc = ss_allocate(e);
-    if (rc) return rc;
-  }
-  if (is_dp(e->algo)) {
-    int rc = dp_allocate(e);
-    if (rc) return rc;
-  }
-  if (e->algo == BGS_LOBSTER) {
-    int rc = lob_allocate(e);
-    if (rc) return rc;
-  }
-  if (e->algo == BGS_KDE) {
-    int rc = kde_allocate(e);
-    if (rc) return rc;
-  }
-  if (is_dp2(e->algo)) {
-    int rc = dp2_allocate(e);
-    if (rc) return rc;
-  }
-  if (is_lb(e->algo)) {
-    int rc = lb_allocate(e);
-    if (rc) return rc;
-  }
-  if (e->algo == BGS_VUMETER) {
-    int rc = vu_allocate(e);
-    if (rc) return rc;
-  }
-  if (is_fuzzy(e->algo)) {
-    int rc = fz_allocate(e);
-    if (rc) return rc;
-  }
+  int rc = e->fam->allocate(e);
+  if (rc) return rc;
   // Whatever allocation enqueued on e->stream (statistics counters, poison fills) is complete before the caller's first
   // launch - which may come on ANOTHER stream (device path) that nothing else orders against this one.
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -778,90 +576,16 @@ int ensure_staging(bgs_engine* e) {
   return BGS_OK;
 }
 
-#define LAUNCH_FRAME_KERNEL(KERNEL, name)                                                             \
-  do {                                                                                                \
-    Timed t__(e, s, name);                                                                            \
-    if (C == 3) {                                                                                     \
-      if (G == 16)                                                                                    \
-        hipLaunchKernelGGL((bgs::KERNEL<16, 3>), dim3(blocks_for(a.npix / 16)), dim3(bgs::kBlock), 0, s, a); \
-      else if (G == 4)                                                                                \
-        hipLaunchKernelGGL((bgs::KERNEL<4, 3>), dim3(blocks_for(a.npix / 4)), dim3(bgs::kBlock), 0, s, a);   \
-      else                                                                                            \
-        hipLaunchKernelGGL((bgs::KERNEL<1, 3>), dim3(blocks_for(a.npix)), dim3(bgs::kBlock), 0, s, a);       \
-    } else {                                                                                          \
-      if (G == 16)                                                                                    \
-        hipLaunchKernelGGL((bgs::KERNEL<16, 1>), dim3(blocks_for(a.npix / 16)), dim3(bgs::kBlock), 0, s, a); \
-      else if (G == 4)                                                                                \
-        hipLaunchKernelGGL((bgs::KERNEL<4, 1>), dim3(blocks_for(a.npix / 4)), dim3(bgs::kBlock), 0, s, a);   \
-      else                                                                                            \
-        hipLaunchKernelGGL((bgs::KERNEL<1, 1>), dim3(blocks_for(a.npix)), dim3(bgs::kBlock), 0, s, a);       \
-    }                                                                                                 \
-  } while (0)
-
-// widest pixel group every pointer and the pixel count allow
-// (`cap`: measured optimum of the kernel: wmm / wmv run ~10 % faster with 4 pixels per lane than with 16, abl the other way round)
-int pick_group(const bgs::FrameArgs& a, int C, int cap = 16) {
-  const void* ptrs[] = {a.cur, a.p1, a.p2, a.state_out, a.fg, a.bg};
-  int G = 16;
-  if (a.npix % 16) G = (a.npix % 4) ? 1 : 4;
-  if (G > cap) G = cap;
-  for (const void* p : ptrs) {
-    if (!p) continue;
-    if (G == 16 && !aligned(p, 16)) G = 4;
-    if (G == 4 && !aligned(p, 4)) G = 1;
-  }
-  if (const char* env = getenv("BGS_FRAME_GROUP")) {
-    const int want = atoi(env);
-    if ((want == 1 || want == 4 || want == 16) && want <= G) G = want;
-  }
-  (void)C;
-  return G;
-}
-
 // What one launch can cover: streams whose next frame needs the same kernel arguments share a RUN.  Cameras come and go
 // independently (the reference creates and deletes one IBGS object per stream whenever it likes: FrameProcessor.cpp:35-155,
 // :342-482; ustc_src/ustc_bgs.cpp:75-77), so the streams of a batch may have seen different numbers of frames; what a launch
 // depends on is far less than the age - e.g. for MOG2 only "first frame?" and the learning rate, which with the wrapper's fixed
 // alpha is the same from a stream's second frame on.  Streams in lock-step (the benchmark, any batch fed by whole-batch calls) are
 // one run = one launch, exactly as before.
-uint64_t launch_key(const bgs_engine* e, int i) {
-  const bgs_params& p = e->p;
-  const int64_t t = e->seen[i];
-  auto lr_key = [&](double alpha, int64_t cap, int64_t mult) -> uint64_t {  // MOG1 / MOG2: needToInitialize + the learning rate of frame t
-    if (t == 0 || alpha >= 1) return 1;
-    if (alpha >= 0) return 2;
-    return 3 + (uint64_t)std::min<int64_t>(mult * (t + 1), cap);
-  };
-  switch (e->algo) {
-    case BGS_FRAME_DIFF:
-    case BGS_WMM:
-    case BGS_WMV: return (uint64_t)(e->rpos[i] % e->nring) | (uint64_t)std::min<int64_t>(t, e->nring - 1) << 8;  // ring slot + warm-up level
-    case BGS_STATIC_FRAME_DIFF:
-    case BGS_SIGMA_DELTA:
-    case BGS_DP_ZIVKOVIC_AGMM:
-    case BGS_DP_GRIMSON_GMM:
-    case BGS_DP_WREN_GA:
-    case BGS_DP_MEAN: return t == 0;
-    case BGS_ABL: return (uint64_t)(t == 0) | (uint64_t)(((p.limit > 0 && p.limit < e->counter[i]) || p.limit == -1) ? 2 : 0) | (uint64_t)(p.limit > 0 ? std::min<int64_t>(e->counter[i], (int64_t)p.limit + 1) : 0) << 2;
-    case BGS_GMG: return (uint64_t)(t == 0) | (uint64_t)(t >= p.gmg_init_frames) << 1 | (uint64_t)(t == (int64_t)p.gmg_init_frames - 1) << 2;
-    case BGS_ASBL: return (uint64_t)(t == 0) | (uint64_t)e->flip[i] << 1 | (uint64_t)((p.learning_frames > 0 && e->counter[i] <= p.learning_frames) ? 4 : 0);
-    case BGS_DP_ADAPTIVE_MEDIAN: return (uint64_t)(t == 0) | (uint64_t)((t % p.dp_sampling_rate) == 1) << 1;
-    case BGS_MOG1: return lr_key(p.alpha, p.mog1_history, 1);
-    case BGS_MOG2: return lr_key(p.alpha, p.mog2_history, 2);
-    case BGS_KDE: return kde_key(e, i);
-    case BGS_DP_PRATI_MEDIOD:
-    case BGS_DP_TEXTURE: return dp2_key(e, i);
-    case BGS_LB_SIMPLE_GAUSSIAN:
-    case BGS_LB_FUZZY_GAUSSIAN:
-    case BGS_LB_MOG:
-    case BGS_LB_ADAPTIVE_SOM:
-    case BGS_LB_FUZZY_ADAPTIVE_SOM: return lb_key(e, i);
-    case BGS_VUMETER: return vu_key(e, i);
-    case BGS_FUZZY_SUGENO:
-    case BGS_FUZZY_CHOQUET: return fz_key(e, i);
-    default: return (uint64_t)t | (uint64_t)(e->ss ? e->ss->pp[i] & 1 : 0) << 62;  // SuBSENSE / LOBSTER: the frame index itself goes into the kernels (counter-based random draws); + which half of the ping-pong maps is current
-  }
-}
+uint64_t launch_key(const bgs_engine* e, int i) { return e->fam->key(e, i); }
+
+// their packed mask is always made from the finished byte mask (median after the pixel loop)
+bool needs_byte_mask(const bgs_engine* e) { return e->fam->needs_byte_mask && e->fam->needs_byte_mask(e); }
 
 int process_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s, uint32_t* out_flags);
 
@@ -895,8 +619,7 @@ int process_range(bgs_engine* e, int first, int count, const uint8_t* d_frames, 
   // buffer when it passed none - and mask_pack_ragged_kernel makes the words from them, tail bits zero.
   const size_t W = (e->n + 63) / 64;
   const bool ragged = d_bits && (e->n % 64) != 0;
-  const bool via_bytes = e->algo == BGS_GMG || e->algo == BGS_ASBL || (e->algo == BGS_VUMETER && e->p.vu_enable_filter) || is_fuzzy(e->algo);  // their packed mask is always made from the finished byte mask (median after the pixel loop)
-  if (d_bits && !d_fg && (ragged || via_bytes)) {
+  if (d_bits && !d_fg && (ragged || needs_byte_mask(e))) {
     int rc = pack_scratch(e, (size_t)count * e->n, s);
     if (rc) return rc;
     d_fg = e->pack_fg;
@@ -913,7 +636,7 @@ int process_range(bgs_engine* e, int first, int count, const uint8_t* d_frames, 
     uint32_t fl = 0;
     int rc = process_run(e, a, b - a, d_frames + o * C, d_fg ? d_fg + o : nullptr, d_bg ? d_bg + o * bgC : nullptr, (d_bits && !ragged) ? d_bits + (size_t)(a - first) * W : nullptr, s, &fl);
     if (rc) return rc;
-    if (ragged && ((fl & BGS_FG_VALID) || (is_fuzzy(e->algo) && e->fz_any_valid))) pack_ragged(e, d_fg + o, d_bits + (size_t)(a - first) * W, (size_t)(b - a), s);
+    if (ragged && (any_flags(e, a, b - a) & BGS_FG_VALID)) pack_ragged(e, d_fg + o, d_bits + (size_t)(a - first) * W, (size_t)(b - a), s);
     all &= fl;
     a = b;
   }
@@ -925,323 +648,24 @@ int process_range(bgs_engine* e, int first, int count, const uint8_t* d_frames, 
 int process_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s,
                 uint32_t* out_flags) {
   if (out_flags) *out_flags = 0;
-  const int64_t t = e->seen[first];
   HIP_TRY(hipSetDevice(e->device));
-  const bgs_params& p = e->p;
-  const int C = e->ch;
-  const size_t npix = e->n * count, off = e->n * first, fb = npix * C;
-  if (d_bits && npix % 64) return fail(BGS_ERR_INVALID, "internal: a ragged packed mask reached process_run");  // process_range packs those itself
+  if (d_bits && (e->n * count) % 64) return fail(BGS_ERR_INVALID, "internal: a ragged packed mask reached process_run");  // process_range packs those itself
   uint32_t flags = 0;
-
-  bgs::FrameArgs a{};
-  a.cur = d_frames, a.fg = d_fg, a.bg = d_bg, a.fg_bits = d_bits, a.npix = npix;
-  a.thr = p.threshold, a.enable_thr = p.enable_threshold, a.enable_weight = p.enable_weight;
-  // The XCD-aware block order pays where a workgroup's working set is a multi-plane tile (MOG2, MOG1, dp); the byte-stream
-  // kernels run 2-5 % faster in plain block order (tools/ab_pointwise.py), so they only use it at level 2 (for A/B runs).
-  a.xcd_swizzle = e->xcd_swizzle >= 2;
-
-  const bool whole = (first == 0 && count == e->S);
-  if (e->borrow && !whole && e->nring && !e->borrow_in_clip) return fail(BGS_ERR_INVALID, "borrowed frame history needs whole-batch calls");
-
-  switch (e->algo) {
-    case BGS_FRAME_DIFF:
-    case BGS_WMM:
-    case BGS_WMV: {
-      const int R = e->nring, warm = R - 1;
-      const int64_t rp = e->rpos[first];  // the same for every stream of the run (launch_key)
-      const uint8_t *cur = d_frames, *h1 = nullptr, *h2 = nullptr;
-      if (e->borrow) {
-        h1 = e->borrowed[0], h2 = e->borrowed[1];
-      } else {
-        uint8_t* slot = e->ring[rp % R] + off * C;
-        if (cur != slot) HIP_TRY(hipMemcpyAsync(slot, cur, fb, hipMemcpyDeviceToDevice, s));  // keep a private copy as history
-        cur = slot;
-        if (t >= 1) h1 = e->ring[(rp + R - 1) % R] + off * C;
-        if (t >= 2 && R == 3) h2 = e->ring[(rp + R - 2) % R] + off * C;
-      }
-      if (t >= warm) {
-        a.cur = cur, a.p1 = h1, a.p2 = h2;
-        const int G = pick_group(a, C, e->algo == BGS_FRAME_DIFF ? 16 : 4);
-        if (e->algo == BGS_FRAME_DIFF)
-          LAUNCH_FRAME_KERNEL(framediff_kernel, "framediff_kernel");
-        else if (e->algo == BGS_WMM)
-          LAUNCH_FRAME_KERNEL(wmm_kernel, "wmm_kernel");
-        else
-          LAUNCH_FRAME_KERNEL(wmv_kernel, "wmv_kernel");
-        flags = BGS_FG_VALID | (e->algo == BGS_WMM ? BGS_BG_VALID : 0u);
-      }
-      if (e->borrow) e->borrowed[1] = e->borrowed[0], e->borrowed[0] = d_frames;
-      break;
-    }
-    case BGS_STATIC_FRAME_DIFF:
-    case BGS_ABL: {
-      uint8_t* st = e->bgstate + off * C;
-      if (t == 0) HIP_TRY(hipMemcpyAsync(st, d_frames, fb, hipMemcpyDeviceToDevice, s));  // img_input.copyTo(img_background)
-      a.p1 = st;
-      if (e->algo == BGS_STATIC_FRAME_DIFF) {
-        a.bg = nullptr;
-        const int G = pick_group(a, C);
-        LAUNCH_FRAME_KERNEL(framediff_kernel, "framediff_kernel");
-        if (d_bg) HIP_TRY(hipMemcpyAsync(d_bg, st, fb, hipMemcpyDeviceToDevice, s));
-      } else {
-        a.state_out = st;
-        a.alpha = p.alpha, a.beta = 1 - p.alpha;
-        const int64_t cnt = e->counter[first];
-        a.update = ((p.limit > 0 && p.limit < cnt) || p.limit == -1) ? 1 : 0;
-        const int G = pick_group(a, C, 4);  // 4 pixels per lane: 42 VGPRs -> two 1024-lane workgroups per CU (16: 128 VGPRs, one); measured 0.126 vs 0.134 ms
-        {
-          Timed t__(e, s, "abl_kernel");
-          const size_t per_tile = (size_t)bgs::kAblBlock * G, ntiles = (npix + per_tile - 1) / per_tile;
-          // persistent: exactly as many workgroups as are resident at once (1 or 2 per CU, by registers), each walking its share of the tiles
-          const dim3 block(bgs::kAblBlock);
-#define ABL_CASE(GV, CV, UV)                                                                                                               \
-  if (G == GV && C == CV && (a.update != 0) == UV) {                                                                                       \
-    /* resident workgroups per CU of this instantiation: a property of the code object (the library is gfx950-only), cached per   \
-       process; atomic because engines may be driven from several host threads */                                                  \
-    static std::atomic<int> per_cu_cache{0};                                                                                               \
-    int per_cu = per_cu_cache.load(std::memory_order_relaxed);                                                                             \
-    if (!per_cu) {                                                                                                                         \
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bgs::abl_kernel<GV, CV, UV>, bgs::kAblBlock, 0) != hipSuccess || per_cu < 1) per_cu = 1; \
-      per_cu_cache.store(per_cu, std::memory_order_relaxed);                                                                               \
-    }                                                                                                                                      \
-    const dim3 grid((unsigned)std::min<size_t>(ntiles, (size_t)per_cu * e->n_cu));                                                        \
-    hipLaunchKernelGGL((bgs::abl_kernel<GV, CV, UV>), grid, block, 0, s, a, (const uint8_t*)e->abl_lut);                                   \
-  }
-          ABL_CASE(16, 3, true) ABL_CASE(4, 3, true) ABL_CASE(1, 3, true) ABL_CASE(16, 1, true) ABL_CASE(4, 1, true) ABL_CASE(1, 1, true)
-          ABL_CASE(16, 3, false) ABL_CASE(4, 3, false) ABL_CASE(1, 3, false) ABL_CASE(16, 1, false) ABL_CASE(4, 1, false) ABL_CASE(1, 1, false)
-#undef ABL_CASE
-        }
-        if (a.update && p.limit > 0 && p.limit < cnt)
-          for (int i = first; i < first + count; ++i) e->counter[i]++;
-      }
-      flags = BGS_FG_VALID | BGS_BG_VALID;
-      break;
-    }
-    case BGS_GMG: {
-      if (d_bits && !d_fg) return fail(BGS_ERR_UNSUPPORTED, "GMG: the packed mask is made from the byte mask, pass d_fg too");
-      const size_t P = e->n * e->S;
-      if (t == 0) hipLaunchKernelGGL(bgs::gmg_clear_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, e->gmg_nfeat + off, npix);  // initialize(): nfeatures = 0
-      bgs::GmgArgs g{};
-      g.frame = d_frames, g.raw = e->bgstate + off, g.rec = e->gmg_rec, g.nfeat = e->gmg_nfeat;
-      g.plane = P, g.state_off = off, g.npix = npix, g.F = p.gmg_max_features, g.C = C, g.levels = p.gmg_quantization_levels;
-      g.typical = t >= p.gmg_init_frames, g.update = p.gmg_update_background_model != 0, g.normalize_now = t == (int64_t)p.gmg_init_frames - 1;
-      // a decayed weight goes back as the whole 8-byte record (512 contiguous bytes per wave) rather than as a 4-byte store into it
-      // (every other dword of the line: partial sectors): 0.294 -> 0.281 ms per 8 x 1080p, same box, alternating; BGS_GMG_FULL_STORE=0: the 4-byte stores
-      static const bool gmg_full = !(getenv("BGS_GMG_FULL_STORE") && atoi(getenv("BGS_GMG_FULL_STORE")) == 0);
-      g.fullStore = gmg_full ? 1 : 0;
-      g.lr = p.gmg_learning_rate, g.prior = p.gmg_background_prior, g.thr = p.gmg_decision_threshold;
-      {
-        Timed tm(e, s, "gmg_kernel");
-        hipLaunchKernelGGL(bgs::gmg_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, g);
-      }
-      if (d_fg) {
-        if (p.gmg_smoothing_radius > 0) {  // cv::medianBlur(fgmask, smoothingRadius) of a {0,255} mask
-          bgs::MorphArgs m{e->bgstate + off, d_fg, e->rows, e->cols, 3, p.gmg_smoothing_radius};
-          bgs::morph_launch(m, (int)count, s);
-        } else {
-          HIP_TRY(hipMemcpyAsync(d_fg, e->bgstate + off, npix, hipMemcpyDeviceToDevice, s));
-        }
-        if (d_bits) hipLaunchKernelGGL(bgs::mask_pack_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, (const uint8_t*)d_fg, d_bits, npix);
-      }
-      flags = BGS_FG_VALID;  // no getBackgroundImage for GMG (GMG.cpp:59): img_bgmodel ends up empty
-      break;
-    }
-    case BGS_SUBSENSE: {
-      int rc = ss_process(e, first, count, d_frames, d_fg, d_bg, s, t);
-      if (rc) return rc;
-      if (d_bits)  // the mask is also model state (m_oLastFGMask): pack it from there
-        hipLaunchKernelGGL(bgs::mask_pack_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, (const uint8_t*)(e->ss->u8[SS_LASTFG] + off), d_bits, npix);
-      flags = BGS_FG_VALID | BGS_BG_VALID;
-      break;
-    }
-    case BGS_LOBSTER: {
-      int rc = lob_process(e, first, count, d_frames, d_fg, d_bg, s, t);
-      if (rc) return rc;
-      if (d_bits)
-        hipLaunchKernelGGL(bgs::mask_pack_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, (const uint8_t*)(e->ss->u8[SS_LASTFG] + off), d_bits, npix);
-      flags = BGS_FG_VALID | BGS_BG_VALID;
-      break;
-    }
-    case BGS_SIGMA_DELTA: {
-      uint8_t *mt = e->bgstate + off * 3, *vt = e->bgstate2 + off * 3;
-      if (t == 0) {  // SigmaDeltaBGS.cpp:33-39: allocate + initialise, return without output
-        HIP_TRY(hipMemcpyAsync(mt, d_frames, fb, hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(bgs::sigmadelta_init_vt_kernel, dim3(blocks_for(fb)), dim3(bgs::kBlock), 0, s, vt, fb, e->cols, (int)(uint8_t)p.sd_min_var);
-        break;
-      }
-      bgs::SigmaDeltaArgs q{};
-      q.cur = d_frames, q.mt = mt, q.vt = vt, q.fg = d_fg, q.fg_bits = d_bits, q.npix = npix;
-      q.N = (uint32_t)p.sd_amp_factor, q.vmin = (uint8_t)p.sd_min_var, q.vmax = (uint8_t)p.sd_max_var, q.xcd_swizzle = e->xcd_swizzle >= 2;
-      int G = 16;
-      if (npix % 16 || !aligned(d_frames, 16) || !aligned(mt, 16) || !aligned(vt, 16) || (d_fg && !aligned(d_fg, 16))) G = (npix % 4 || !aligned(d_frames, 4) || !aligned(mt, 4) || (d_fg && !aligned(d_fg, 4))) ? 1 : 4;
-      {
-        Timed tm(e, s, "sigmadelta_kernel");
-        if (G == 16) hipLaunchKernelGGL((bgs::sigmadelta_kernel<16>), dim3(blocks_for(npix / 16)), dim3(bgs::kBlock), 0, s, q);
-        if (G == 4) hipLaunchKernelGGL((bgs::sigmadelta_kernel<4>), dim3(blocks_for(npix / 4)), dim3(bgs::kBlock), 0, s, q);
-        if (G == 1) hipLaunchKernelGGL((bgs::sigmadelta_kernel<1>), dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, q);
-      }
-      flags = BGS_FG_VALID;
-      break;
-    }
-    case BGS_DP_ZIVKOVIC_AGMM:
-    case BGS_DP_GRIMSON_GMM:
-    case BGS_DP_WREN_GA:
-    case BGS_DP_MEAN:
-    case BGS_DP_ADAPTIVE_MEDIAN: {
-      int rc = dp_process(e, first, count, t, d_frames, d_fg, d_bits, s, &flags);
-      if (rc) return rc;
-      break;
-    }
-    case BGS_ASBL: {
-      const int cur = e->flip[first];
-      for (int i = first; i < first + count; ++i)
-        if (e->flip[i] != cur) return fail(BGS_ERR_INVALID, "streams %d and %d are not in lock-step", first, i);
-      uint8_t* bufs[2] = {e->bgstate, e->bgstate2};
-      if (t == 0) {  // img_input(gray).copyTo(img_background): a frame of threshold -1 ... simplest exact way is a tiny gray kernel
-        bgs::FrameArgs g{};
-        g.cur = d_frames, g.fg = bufs[cur] + off, g.npix = npix, g.enable_thr = 0;
-        const int G = 1;
-        bgs::FrameArgs a = g;  // LAUNCH_FRAME_KERNEL reads `a`
-        LAUNCH_FRAME_KERNEL(gray_kernel, "gray_kernel");
-      }
-      bgs::AsblArgs q{};
-      q.frame = d_frames, q.bg_in = bufs[cur] + off, q.bg_out = bufs[cur ^ 1] + off, q.fg = d_fg, q.bg_img = d_bg;
-      q.rows = e->rows, q.cols = e->cols, q.thr = p.threshold;
-      const int64_t cnt = e->counter[first];
-      q.learn = (p.learning_frames > 0 && cnt <= p.learning_frames) ? 1 : 0;
-      q.aL = p.alpha_learn, q.bL = 1 - p.alpha_learn, q.aD = p.alpha_detection, q.bD = 1 - p.alpha_detection;
-      {
-        Timed tm(e, s, "asbl_kernel");
-        static const bool table = !(getenv("BGS_ASBL_TABLE") && atoi(getenv("BGS_ASBL_TABLE")) == 0);
-        const uintptr_t ptrs = (uintptr_t)q.frame | (uintptr_t)q.bg_in | (uintptr_t)q.bg_out | (uintptr_t)q.fg | (uintptr_t)q.bg_img;
-        // the table kernel moves whole dwords: rows of 4n pixels, aligned images (also the stream offset inside them: n % 4 == 0 then)
-        if (table && e->cols % 4 == 0 && e->cols >= 4 && ptrs % 4 == 0) {
-          // one wave per strip of 256 columns x R rows; 2 resident workgroups of 16 waves per CU (67 KB of LDS each): R such that the
-          // strips of this launch fill them once, at least 8 rows (each strip re-reads the rows above and below it)
-          const size_t waves = (size_t)2 * e->n_cu * (bgs::kAsbl2Block / bgs::kWave), nsx = (e->cols + bgs::kAsblSW - 1) / bgs::kAsblSW;
-          const size_t blocks_y = std::max<size_t>(1, waves / ((size_t)count * nsx));
-          const int R = (int)std::max<size_t>(8, (e->rows + blocks_y - 1) / blocks_y);
-          const size_t nstrips = (size_t)count * nsx * ((e->rows + R - 1) / R), per_wg = bgs::kAsbl2Block / bgs::kWave;
-          if (nstrips >= (1u << 31)) return fail(BGS_ERR_UNSUPPORTED, "AdaptiveSelectiveBackgroundLearning: launch too large");
-          const dim3 grid((unsigned)std::min<size_t>((nstrips + per_wg - 1) / per_wg, (size_t)2 * e->n_cu));
-          const uint8_t* lut = e->abl_lut + (q.learn ? 0 : (size_t)bgs::kAsblLutRows * 256);
-          if (C == 3)
-            hipLaunchKernelGGL((bgs::asbl_stream_kernel<3>), grid, dim3(bgs::kAsbl2Block), 0, s, q, lut, count, R);
-          else
-            hipLaunchKernelGGL((bgs::asbl_stream_kernel<1>), grid, dim3(bgs::kAsbl2Block), 0, s, q, lut, count, R);
-        } else {
-          const dim3 grid((e->cols + bgs::kAsblTW - 1) / bgs::kAsblTW, (e->rows + bgs::kAsblTH - 1) / bgs::kAsblTH, count);
-          if (C == 3)
-            hipLaunchKernelGGL((bgs::asbl_kernel<3>), grid, dim3(bgs::kBlock), 0, s, q);
-          else
-            hipLaunchKernelGGL((bgs::asbl_kernel<1>), grid, dim3(bgs::kBlock), 0, s, q);
-        }
-      }
-      if (d_bits) {
-        if (!d_fg) return fail(BGS_ERR_UNSUPPORTED, "AdaptiveSelectiveBackgroundLearning: the packed mask is made from the byte mask, pass d_fg too");
-        hipLaunchKernelGGL(bgs::mask_pack_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, (const uint8_t*)d_fg, d_bits, npix);
-      }
-      for (int i = first; i < first + count; ++i) {
-        e->flip[i] = (uint8_t)(cur ^ 1);
-        if (q.learn) e->counter[i]++;
-      }
-      flags = BGS_FG_VALID | BGS_BG_VALID;
-      break;
-    }
-    case BGS_MOG1: {
-      double lr = p.alpha;
-      int64_t nframes = t;
-      bgs::Mog1Args m{};
-      m.state = e->mog1_state, m.state_off = off, m.npix = npix;
-      if (nframes == 0 || lr >= 1) {  // needToInitialize: bgmodel = zeros
-        if (C == 3)
-          hipLaunchKernelGGL((bgs::mog1_clear_kernel<3>), dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, m);
-        else
-          hipLaunchKernelGGL((bgs::mog1_clear_kernel<1>), dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, m);
-        nframes = 0;
-      }
-      ++nframes;
-      lr = (lr >= 0 && nframes > 1) ? lr : 1. / (double)std::min<int64_t>(nframes, p.mog1_history);
-      m.frame = d_frames, m.fg = d_fg, m.fg_bits = d_bits;
-      mog1_fill_args(e, m, lr);
-      {
-        Timed tm(e, s, "mog1_update_kernel");
-        const dim3 grid(blocks_for(npix)), block(bgs::kBlock);
-        if (C == 3) hipLaunchKernelGGL((bgs::mog1_update_kernel<3>), grid, block, 0, s, m);
-        if (C == 1) hipLaunchKernelGGL((bgs::mog1_update_kernel<1>), grid, block, 0, s, m);
-      }
-      if (nframes == 1)  // re-initialisation restarts the count (the streams of a run may otherwise have different ages: launch_key)
-        for (int i = first; i < first + count; ++i) e->seen[i] = 0;
-      flags = BGS_FG_VALID;  // BackgroundSubtractorMOG has no getBackgroundImage (MixtureOfGaussianV1BGS.cpp:53)
-      break;
-    }
-    case BGS_MOG2: {
-      double lr = p.alpha;
-      int64_t nframes = t;
-      bgs::Mog2Args m{};
-      m.state_off = off, m.npix = npix;
-      mog2_fill_args(e, m, 0.0);
-      if (nframes == 0 || lr >= 1) {  // needToInitialize: bgmodel = zeros, modesUsed = 0
-        mog2_clear(e, m, s);
-        nframes = 0;
-      }
-      ++nframes;
-      const int64_t n2 = 2 * nframes;
-      lr = (lr >= 0 && nframes > 1) ? lr : 1. / (double)std::min<int64_t>(n2, p.mog2_history);
-      mog2_fill_args(e, m, lr);
-      m.frame = d_frames, m.fg = d_fg, m.bgimg = d_bg, m.fg_bits = d_bits;
-      int rc = launch_mog2(e, m, s);
-      if (rc) return rc;
-      if (nframes == 1)  // re-initialisation restarts the count (the streams of a run may otherwise have different ages: launch_key)
-        for (int i = first; i < first + count; ++i) e->seen[i] = 0;
-      flags = BGS_FG_VALID | BGS_BG_VALID;
-      break;
-    }
-    case BGS_KDE: {
-      int rc = kde_run(e, first, count, d_frames, d_fg, d_bits, s, &flags);
-      if (rc) return rc;
-      break;
-    }
-    case BGS_DP_PRATI_MEDIOD:
-    case BGS_DP_TEXTURE: {
-      int rc = dp2_run(e, first, count, d_frames, d_fg, d_bits, s, &flags);
-      if (rc) return rc;
-      break;
-    }
-    case BGS_LB_SIMPLE_GAUSSIAN:
-    case BGS_LB_FUZZY_GAUSSIAN:
-    case BGS_LB_MOG:
-    case BGS_LB_ADAPTIVE_SOM:
-    case BGS_LB_FUZZY_ADAPTIVE_SOM: {
-      int rc = lb_run(e, first, count, d_frames, d_fg, d_bg, d_bits, s, &flags);
-      if (rc) return rc;
-      break;
-    }
-    case BGS_VUMETER: {
-      int rc = vu_run(e, first, count, d_frames, d_fg, d_bg, d_bits, s, &flags);
-      if (rc) return rc;
-      break;
-    }
-    case BGS_FUZZY_SUGENO:
-    case BGS_FUZZY_CHOQUET: {
-      int rc = fz_run(e, first, count, d_frames, d_fg, d_bg, d_bits, s, &flags);
-      if (rc) return rc;
-      break;
-    }
-    default: return fail(BGS_ERR_UNSUPPORTED, "algorithm %d is not implemented in this build", (int)e->algo);
-  }
+  int rc = e->fam->run(e, first, count, d_frames, d_fg, d_bg, d_bits, s, &flags);
+  if (rc) return rc;
   HIP_TRY(hipGetLastError());
-  for (int i = first; i < first + count; ++i) e->seen[i]++, e->rpos[i]++, e->last_flags[i] = flags;
-  if (is_fuzzy(e->algo))  // learning and detecting streams share the run: the flags are per stream
-    for (int i = first; i < first + count; ++i) e->last_flags[i] = e->fz_flags[i];
+  for (int i = first; i < first + count; ++i) {
+    e->seen[i]++, e->rpos[i]++;
+    if (!e->fam->per_stream_flags) e->last_flags[i] = flags;
+  }
   if (out_flags) *out_flags = flags;
   return BGS_OK;
 }
 
 
 // bgs_process_clip_device: `nframes` consecutive frames of streams [first, first+count).  Every algorithm: frame by frame
-// through process_range (the same launches as nframes range calls).  MOG2: runs of 8 / 4 / 2 frames go through ONE launch
-// that keeps the model in registers (kernel_mog2.h); what is left over takes the single-frame kernel.
+// through process_range (the same launches as nframes range calls).  Families with a clip_fused entry (MOG2, MOG1, the dp GMMs): runs
+// of 8 / 4 / 2 frames go through ONE launch that keeps the model in registers; what is left over takes the single-frame kernel.
 int process_clip_run(bgs_engine* e, int first, int count, int slab_count, int nframes, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits,
                      hipStream_t s, uint32_t* out_flags);
 
@@ -1255,7 +679,7 @@ int process_clip(bgs_engine* e, int first, int count, int nframes, const uint8_t
   if (!d_frames) return fail(BGS_ERR_INVALID, "d_frames is NULL");
   const size_t W = (e->n + 63) / 64;
   const bool ragged = d_bits && (e->n % 64) != 0;  // as in process_range: byte masks first, then mask_pack_ragged_kernel
-  if (d_bits && !d_fg && (ragged || e->algo == BGS_GMG || e->algo == BGS_ASBL || (e->algo == BGS_VUMETER && e->p.vu_enable_filter) || is_fuzzy(e->algo))) {
+  if (d_bits && !d_fg && (ragged || needs_byte_mask(e))) {
     int rc = pack_scratch(e, (size_t)nframes * count * e->n, s);
     if (rc) return rc;
     d_fg = e->pack_fg;
@@ -1268,7 +692,7 @@ int process_clip(bgs_engine* e, int first, int count, int nframes, const uint8_t
     const size_t o = (size_t)(a - first) * e->n;
     int rc = process_clip_run(e, a, b - a, count, nframes, d_frames + o * C, d_fg ? d_fg + o : nullptr, d_bg ? d_bg + o * bgC : nullptr, (d_bits && !ragged) ? d_bits + (size_t)(a - first) * W : nullptr, s, fl.data());
     if (rc) return rc;
-    if (ragged)
+    if (ragged)  // per frame only the AND over the run is known here (last_flags holds the clip's last frame): as before, a run that mixes learning and detecting streams of a per_stream_flags family gets no words
       for (int t = 0; t < nframes; ++t)
         if (fl[t] & BGS_FG_VALID) pack_ragged(e, d_fg + (size_t)t * count * e->n + o, d_bits + ((size_t)t * count + (size_t)(a - first)) * W, (size_t)(b - a), s);
     for (int t = 0; t < nframes; ++t) all[t] &= fl[t];
@@ -1282,13 +706,11 @@ int process_clip(bgs_engine* e, int first, int count, int nframes, const uint8_t
 // `count` streams of one age starting at `first`, inside a slab of `slab_count` streams per frame
 int process_clip_run(bgs_engine* e, int first, int count, int slab_count, int nframes, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits,
                      hipStream_t s, uint32_t* out_flags) {
-  const bgs_params& p = e->p;
   const size_t npix = e->n * count, C = (size_t)e->ch;
   const size_t slab = e->n * slab_count;  // pixels from one frame of the clip to the next
   const size_t words = slab / 64;
-  // lr >= 1 re-initialises the model on every frame (needToInitialize): nothing to keep in registers
-  const bool dp_gmm = e->algo == BGS_DP_ZIVKOVIC_AGMM || e->algo == BGS_DP_GRIMSON_GMM;
-  const bool fuse_ok = e->clip_fuse && (dp_gmm || ((e->algo == BGS_MOG2 || e->algo == BGS_MOG1) && p.alpha < 1));
+  const Family& fam = *e->fam;
+  const bool fuse_ok = e->clip_fuse && fam.clip_fused && (!fam.clip_fusable || fam.clip_fusable(e));
   // FrameDifference / WeightedMoving*: frame t needs frames t-1 (t-2).  A per-frame call copies its frame into the engine's ring; inside
   // a clip the earlier frames of the clip ARE that history, so only the last one (two) are copied into the ring, once, at the end.
   const bool ring_clip = e->nring > 0 && !e->borrow && nframes >= 2;
@@ -1333,65 +755,13 @@ int process_clip_run(bgs_engine* e, int first, int count, int slab_count, int nf
       for (int i = first; i < first + count; ++i)
         if (e->seen[i] != seen) return fail(BGS_ERR_INVALID, "streams %d and %d are not in lock-step (%lld vs %lld frames)", first, i, (long long)seen, (long long)e->seen[i]);
       HIP_TRY(hipSetDevice(e->device));
-      if (dp_gmm) {  // package_bgs/dp GMMs: the same kernel with a frame loop (kernel_dp.h)
-        uint32_t fl = 0;
-        int rc = dp_process(e, first, count, seen, fr, fg, bits, s, &fl, fuse, slab);
-        if (rc) return rc;
-        HIP_TRY(hipGetLastError());
-        for (int i = first; i < first + count; ++i) e->seen[i] += fuse, e->rpos[i] += fuse, e->last_flags[i] = fl;
-        if (out_flags)
-          for (int j = 0; j < fuse; ++j) out_flags[t + j] = fl;
-        t += fuse;
-        continue;
-      }
-      if (e->algo == BGS_MOG1) {
-        bgs::Mog1ClipArgs c{};
-        c.m.state = e->mog1_state, c.m.state_off = e->n * first, c.m.npix = npix;
-        if (seen == 0) {  // needToInitialize on a stream's first frame
-          if (C == 3)
-            hipLaunchKernelGGL((bgs::mog1_clear_kernel<3>), dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, c.m);
-          else
-            hipLaunchKernelGGL((bgs::mog1_clear_kernel<1>), dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, c.m);
-        }
-        c.m.frame = fr, c.m.fg = fg, c.m.fg_bits = bits;
-        mog1_fill_args(e, c.m, 0.0);
-        for (int j = 0; j < fuse; ++j) {
-          const int64_t nf = seen + j + 1;
-          c.alpha[j] = (float)((p.alpha >= 0 && nf > 1) ? p.alpha : 1. / (double)std::min<int64_t>(nf, p.mog1_history));
-        }
-        c.frame_stride = slab * C, c.fg_stride = slab, c.bits_stride = words;
-        {
-          Timed tm(e, s, "mog1_clip_kernel");
-          const dim3 grid(blocks_for(npix)), block(bgs::kBlock);
-#define MOG1_CLIP_CASE(CV, TV) \
-  if (C == CV && fuse == TV) hipLaunchKernelGGL((bgs::mog1_clip_kernel<CV, TV>), grid, block, 0, s, c);
-          MOG1_CLIP_CASE(3, 2) MOG1_CLIP_CASE(3, 4) MOG1_CLIP_CASE(3, 8) MOG1_CLIP_CASE(1, 2) MOG1_CLIP_CASE(1, 4) MOG1_CLIP_CASE(1, 8)
-#undef MOG1_CLIP_CASE
-        }
-        HIP_TRY(hipGetLastError());
-        for (int i = first; i < first + count; ++i) e->seen[i] += fuse, e->rpos[i] += fuse, e->last_flags[i] = BGS_FG_VALID;
-        if (out_flags)
-          for (int j = 0; j < fuse; ++j) out_flags[t + j] = BGS_FG_VALID;
-        t += fuse;
-        continue;
-      }
-      bgs::Mog2ClipArgs c{};
-      c.m.state_off = e->n * first, c.m.npix = npix;
-      mog2_fill_args(e, c.m, 0.0);
-      if (seen == 0) mog2_clear(e, c.m, s);  // needToInitialize on a stream's first frame
-      for (int j = 0; j < fuse; ++j) {       // the learning rate of each frame, as the single-frame path computes it
-        const int64_t nf = seen + j + 1;
-        const double lr = (p.alpha >= 0 && nf > 1) ? p.alpha : 1. / (double)std::min<int64_t>(2 * nf, p.mog2_history);
-        c.alphaT[j] = (float)lr, c.alpha1[j] = 1.f - c.alphaT[j], c.prune[j] = (float)(-lr * (double)p.mog2_ct);
-      }
-      c.m.frame = fr, c.m.fg = fg, c.m.bgimg = bg, c.m.fg_bits = bits;
-      c.frame_stride = slab * 3, c.fg_stride = slab, c.bg_stride = slab * 3, c.bits_stride = words;
-      int rc = launch_mog2_clip(e, c, fuse, s);
+      uint32_t fl = 0;
+      int rc = fam.clip_fused(e, first, count, fuse, slab, fr, fg, bg, bits, s, &fl);
       if (rc) return rc;
       HIP_TRY(hipGetLastError());
-      for (int i = first; i < first + count; ++i) e->seen[i] += fuse, e->rpos[i] += fuse, e->last_flags[i] = BGS_FG_VALID | BGS_BG_VALID;
+      for (int i = first; i < first + count; ++i) e->seen[i] += fuse, e->rpos[i] += fuse, e->last_flags[i] = fl;
       if (out_flags)
-        for (int j = 0; j < fuse; ++j) out_flags[t + j] = BGS_FG_VALID | BGS_BG_VALID;
+        for (int j = 0; j < fuse; ++j) out_flags[t + j] = fl;
     }
     t += fuse;
   }
@@ -1541,7 +911,7 @@ int bgs_create(bgs_algo algo, const bgs_params* params, int hip_device, int n_st
   if (params && params->struct_size != sizeof(bgs_params)) return fail(BGS_ERR_INVALID, "bgs_params.struct_size %u != %zu (ABI mismatch)", params->struct_size, sizeof(bgs_params));
   bgs_engine* e = new (std::nothrow) bgs_engine();
   if (!e) return fail(BGS_ERR_NOMEM, "out of host memory");
-  e->algo = algo;
+  e->algo = algo, e->fam = family_of(algo);
   if (params)
     e->p = *params;
   else
@@ -1597,39 +967,8 @@ int bgs_set_params(bgs_engine* e, const bgs_params* params) {
     // Parameters the reference hands to its model object once, when it is built on the first frame, stay as they were:
     // later values are ignored there too (SuBSENSE.cpp:27-36, LOBSTER.cpp:27-34, DP*BGS.cpp `if(firstTime)`), and here they
     // also size the device buffers.
-    bgs_params& p = e->p;
-    if (e->algo == BGS_SUBSENSE || e->algo == BGS_LOBSTER) {
-      p.lbsp_rel_threshold = old.lbsp_rel_threshold, p.lbsp_threshold_offset = old.lbsp_threshold_offset;
-      p.subsense_min_color_dist_threshold = old.subsense_min_color_dist_threshold, p.subsense_n_samples = old.subsense_n_samples;
-      p.subsense_n_required = old.subsense_n_required, p.subsense_samples_for_moving_avgs = old.subsense_samples_for_moving_avgs;
-      p.subsense_desc_dist_threshold_offset = old.subsense_desc_dist_threshold_offset;
-    }
-    if (is_dp(e->algo)) {
-      p.dp_threshold = old.dp_threshold, p.dp_alpha = old.dp_alpha, p.dp_gaussians = old.dp_gaussians;
-      p.dp_sampling_rate = old.dp_sampling_rate, p.learning_frames = old.learning_frames;
-    }
-    if (e->algo == BGS_GMG) p.gmg_max_features = old.gmg_max_features;  // sizes the histogram planes
-    if (e->algo == BGS_KDE) {  // KDE.cpp:40-66: Intialize / SetThresholds once; framesToLearn is re-read every frame (and update_model is live)
-      p.kde_sequence_length = old.kde_sequence_length, p.kde_time_window = old.kde_time_window, p.kde_sd_estimation = old.kde_sd_estimation;
-      p.kde_color_ratios = old.kde_color_ratios, p.kde_threshold = old.kde_threshold, p.kde_alpha = old.kde_alpha;
-    }
-    if (e->algo == BGS_VUMETER)  // VuMeter.cpp:42-47: SetAlpha / SetBinSize / SetThreshold on the first frame only; enableFilter is live
-      p.vu_bin_size = old.vu_bin_size, p.vu_alpha = old.vu_alpha, p.vu_threshold = old.vu_threshold;
-    if (e->algo == BGS_DP_PRATI_MEDIOD) {  // PratiMediodBGS::Initalize copies m_params once (DPPratiMediodBGS.cpp:55-64)
-      p.dp_threshold = old.dp_threshold, p.dp_sampling_rate = old.dp_sampling_rate;
-      p.dp_history_size = old.dp_history_size, p.dp_weight = old.dp_weight;
-    }
-    if (e->algo == BGS_ASBL && (!e->abl_lut_valid || p.alpha_learn != e->asbl_lut_alpha[0] || p.alpha_detection != e->asbl_lut_alpha[1])) {
-      if (hipSetDevice(e->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(BGS_ERR_HIP, "device sync failed");
-      rc = asbl_build_lut(e);
-      if (rc) return rc;
-    }
-    if (e->algo == BGS_ABL && (!e->abl_lut_valid || p.alpha != e->abl_lut_alpha)) {
-      // a launch still in flight on some stream may be reading the table: let the device drain before it is rewritten
-      if (hipSetDevice(e->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(BGS_ERR_HIP, "device sync failed");
-      rc = abl_build_lut(e);
-      if (rc) return rc;
-    }
+    if (e->fam->keep_frozen) e->fam->keep_frozen(e->p, old);
+    if (e->fam->apply_params) return e->fam->apply_params(e);
   }
   return BGS_OK;
 }
@@ -1985,13 +1324,6 @@ int64_t bgs_get_state(bgs_engine* e, int stream, const char* plane, void* dst, s
   if (!e->n) return fail(BGS_ERR_STATE, "no model yet");
   if (stream < 0 || stream >= e->S) return fail(BGS_ERR_INVALID, "stream %d outside 0..%d", stream, e->S - 1);
   if (hipSetDevice(e->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(BGS_ERR_HIP, "device sync failed");
-  const size_t n = e->n, P = n * e->S, off = n * stream;
-  const int C = e->ch;
-  auto copy_bytes = [&](const uint8_t* src, size_t nb) -> int64_t {
-    if (cap < nb) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
-    if (d2h_staged(dst, src, nb) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-    return (int64_t)nb;
-  };
   if (!strcmp(plane, "hostpath")) {  // diagnostics of bgs_process / bgs_submit since creation: 15 doubles (see bench.py host_path)
     double rec[15] = {0};
     for (size_t i = 0; i < e->pin.size(); ++i) rec[i % 3] += e->pin[i].pinned, rec[3 + i % 3] += e->pin[i].refused;  // per role: input, mask, background
@@ -2007,123 +1339,7 @@ int64_t bgs_get_state(bgs_engine* e, int stream, const char* plane, void* dst, s
     memcpy(dst, rec, sizeof(rec));
     return (int64_t)sizeof(rec);
   }
-  if (e->algo == BGS_MOG2) {
-    // canonical export: "w" [K][n], "var" [K][n], "mu" [K][3][n] floats, "nmodes" [n] bytes — whatever the device layout
-    int p0 = -1, np = 0;
-    if (!strcmp(plane, "w")) p0 = 0, np = 5;
-    if (!strcmp(plane, "var")) p0 = 5, np = 5;
-    if (!strcmp(plane, "mu")) p0 = 10, np = 15;
-    if (!strcmp(plane, "summary")) p0 = 100, np = 5;  // uint32 [K][n] by rank: the 16-bit word q0 | q1 << 5 | q2 << 10 | class << 15 (kernel_mog2.h; for the invariant test)
-    const bool nm = !strcmp(plane, "nmodes") || !strcmp(plane, "summary_valid");  // bytes [n]; summary_valid: bit 15 of the meta word
-    const bool want_valid = !strcmp(plane, "summary_valid");
-    if (p0 >= 0 || nm) {
-      // device layout (kernel_mog2.h): weights by rank, {var, mean} records in fixed slots, meta = rank -> slot.  Exported in the
-      // reference's array order (rank); entries past a pixel's mode count are zero, as in the reference's zero-initialised bgmodel.
-      const size_t need = nm ? n : (size_t)np * n * 4;
-      if (cap < need) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
-      const size_t T = bgs::kMog2Tile, TB = bgs::kMog2TileBytes;
-      const size_t t0 = off / T, t1 = (off + n + T - 1) / T;
-      std::vector<uint8_t> tiles((t1 - t0) * TB);
-      if (d2h_staged(tiles.data(), e->mog2_state + t0 * TB, tiles.size()) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-      for (size_t i = 0; i < n; ++i) {
-        const size_t sp = off + i, in = sp % T;
-        const uint8_t* tb = tiles.data() + (sp / T - t0) * TB;
-        const float* w = reinterpret_cast<const float*>(tb) + in;
-        const float* rec = reinterpret_cast<const float*>(tb + bgs::kMog2RecOff) + in * 4;
-        const uint16_t* sum = reinterpret_cast<const uint16_t*>(tb + bgs::kMog2SumOff) + in;
-        const unsigned meta = reinterpret_cast<const uint16_t*>(tb + bgs::kMog2MetaOff)[in];
-        if (nm) {
-          ((uint8_t*)dst)[i] = want_valid ? (uint8_t)((meta >> 15) & 1u) : (uint8_t)bgs::mog2_meta_count(meta);
-          continue;
-        }
-        for (int r = 0; r < bgs::kMog2K; ++r) {
-          const unsigned f = (meta >> (3 * r)) & 7u;
-          const float* rc = f ? rec + (size_t)(f - 1) * T * 4 : nullptr;
-          if (p0 == 100) ((uint32_t*)dst)[(size_t)r * n + i] = f ? sum[(size_t)(f - 1) * T] : 0u;
-          if (p0 == 0) ((float*)dst)[(size_t)r * n + i] = f ? w[(size_t)r * T] : 0.f;
-          if (p0 == 5) ((float*)dst)[(size_t)r * n + i] = f ? rc[0] : 0.f;
-          if (p0 == 10)
-            for (int c = 0; c < 3; ++c) ((float*)dst)[((size_t)r * 3 + c) * n + i] = f ? rc[1 + c] : 0.f;
-        }
-      }
-      return (int64_t)need;
-    }
-  }
-  if ((e->algo == BGS_SUBSENSE || e->algo == BGS_LOBSTER) && e->ss) return ss_get_state(e, stream, plane, dst, cap);
-  if (e->algo == BGS_KDE && e->kde_samples) return kde_get_state(e, stream, plane, dst, cap);
-  if (is_lb(e->algo) && e->lb_model) return lb_get_state(e, stream, plane, dst, cap);
-  if (e->algo == BGS_VUMETER && e->vu_hist) return vu_get_state(e, stream, plane, dst, cap);
-  if (is_fuzzy(e->algo) && e->fz_bg) return fz_get_state(e, stream, plane, dst, cap);
-  if ((e->algo == BGS_DP_PRATI_MEDIOD && e->pm_samples) || (e->algo == BGS_DP_TEXTURE && e->tex_r)) return dp2_get_state(e, stream, plane, dst, cap);
-  if (is_dp(e->algo)) {  // planes are stored canonically: [stream][plane][n]
-    const int planes = dp_planes_of(e);
-    const char* fname = (e->algo == BGS_DP_WREN_GA) ? "gauss" : (e->algo == BGS_DP_MEAN) ? "mean" : "modes";
-    if (planes && !strcmp(plane, fname)) return dp_export_planes(e, stream, planes, dst, cap);
-    if (e->state_ch == 1 && !strcmp(plane, "nmodes")) return copy_bytes(e->bgstate + off, n);
-    if (e->state_ch == 3 && !strcmp(plane, "median")) return copy_bytes(e->bgstate + off * 3, n * 3);
-    return fail(BGS_ERR_STATE, "unknown state plane '%s' for algorithm %d", plane, (int)e->algo);
-  }
-  if (e->algo == BGS_GMG && e->gmg_rec) {  // canonical: colors int32 [F][n], weights f32 [F][n] (entries past the count exported as 0), nfeatures int32 [n]
-    const size_t F = (size_t)e->p.gmg_max_features;
-    std::vector<uint8_t> nf(n);
-    if (d2h_staged(nf.data(), e->gmg_nfeat + off, n) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-    if (!strcmp(plane, "nfeatures")) {
-      if (cap < n * 4) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
-      for (size_t i = 0; i < n; ++i) ((int32_t*)dst)[i] = nf[i];
-      return (int64_t)(n * 4);
-    }
-    if (!strcmp(plane, "colors") || !strcmp(plane, "weights")) {
-      if (cap < n * F * 4) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
-      const int which = !strcmp(plane, "colors") ? 0 : 1;  // the device holds {colour, weight} records (kernel_gmg.h)
-      std::vector<uint32_t> recs(n * 2);
-      for (size_t f = 0; f < F; ++f) {
-        if (d2h_staged(recs.data(), e->gmg_rec + f * P + off, n * 8) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-        for (size_t i = 0; i < n; ++i) ((uint32_t*)dst)[f * n + i] = f >= nf[i] ? 0u : recs[2 * i + which];
-      }
-      return (int64_t)(n * F * 4);
-    }
-  }
-  if (e->algo == BGS_MOG1) {  // exported in the reference's order: [rank][channel][pixel] (kernel_mog1.h keeps records by slot)
-    const int K = bgs::kMog1K;
-    int kind = -1, nf = 0;
-    if (!strcmp(plane, "sortkey")) kind = 0, nf = 1;
-    if (!strcmp(plane, "w")) kind = 1, nf = 1;
-    if (!strcmp(plane, "mu")) kind = 2, nf = C;
-    if (!strcmp(plane, "var")) kind = 3, nf = C;
-    if (kind >= 0) {
-      const size_t need = (size_t)K * nf * n * 4;
-      if (cap < need) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
-      const size_t T = bgs::kMog1Tile, TF = C == 3 ? bgs::mog1_tile_floats<3>() : bgs::mog1_tile_floats<1>(), t0 = off / T, t1 = (off + n + T - 1) / T;
-      std::vector<float> tiles((t1 - t0) * TF);
-      if (d2h_staged(tiles.data(), e->mog1_state + t0 * TF, tiles.size() * 4) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-      for (size_t i = 0; i < n; ++i) {
-        const size_t sp = off + i, l = sp % T;
-        const float* tb = tiles.data() + (sp / T - t0) * TF;
-        const unsigned meta = reinterpret_cast<const uint16_t*>(tb + 2 * K * T + K * T * 2 * C)[l];
-        for (int k = 0; k < K; ++k) {
-          const int slot = (int)((meta >> (3 * k)) & 7u) - 1;  // -1: this rank never held a mode (all zeros in the reference)
-          for (int c = 0; c < nf; ++c) {
-            float v;
-            if (kind <= 1)
-              v = tb[(size_t)(kind * K + k) * T + l];
-            else
-              v = slot < 0 ? 0.f : tb[2 * K * T + (size_t)slot * T * 2 * C + l * 2 * C + (kind == 3 ? C : 0) + c];
-            ((float*)dst)[((size_t)k * nf + c) * n + i] = v;
-          }
-        }
-      }
-      return (int64_t)need;
-    }
-  }
-  if (e->algo == BGS_SIGMA_DELTA && e->seen[stream] >= 1 && (!strcmp(plane, "mt") || !strcmp(plane, "vt")))
-    return copy_bytes((!strcmp(plane, "mt") ? e->bgstate : e->bgstate2) + off * 3, n * 3);
-  if (!strcmp(plane, "bg") && e->algo == BGS_ASBL) return copy_bytes((e->flip[stream] ? e->bgstate2 : e->bgstate) + off, n);
-  if (!strcmp(plane, "bg") && e->bgstate) return copy_bytes(e->bgstate + off * e->state_ch, n * e->state_ch);
-  const int64_t t = e->seen[stream];
-  const int64_t rp = e->rpos[stream];
-  if (!strcmp(plane, "prev1") && e->nring && t >= 1) return copy_bytes(e->ring[(rp + e->nring - 1) % e->nring] + off * C, n * C);
-  if (!strcmp(plane, "prev2") && e->nring == 3 && t >= 2) return copy_bytes(e->ring[(rp + e->nring - 2) % e->nring] + off * C, n * C);
-  return fail(BGS_ERR_STATE, "unknown state plane '%s' for algorithm %d", plane, (int)e->algo);
+  return e->fam->get_state(e, stream, plane, dst, cap);
 }
 
 int64_t bgs_frames_seen(const bgs_engine* e, int stream) {
@@ -2140,10 +1356,7 @@ int bgs_reset_stream(bgs_engine* e, int stream) {
   if (!e) return fail(BGS_ERR_INVALID, "engine is NULL");
   if (stream < 0 || stream >= e->S) return fail(BGS_ERR_INVALID, "stream %d outside 0..%d", stream, e->S - 1);
   e->seen[stream] = 0, e->counter[stream] = 0, e->last_flags[stream] = 0;
-  if (!e->kde.empty()) e->kde[stream] = bgs_engine::KdeStream();
-  if (!e->lb_mk.empty()) e->lb_mk[stream] = 0;
-  if (!e->vu_count.empty()) e->vu_count[stream] = 0;
-  if (!e->fz_fn.empty()) e->fz_fn[stream] = 0, e->fz_flags[stream] = 0, e->fz_detected[stream] = 0;
+  if (e->fam->reset_stream) e->fam->reset_stream(e, stream);
   if (e->last_fg_stream == stream) e->last_fg_stream = -1;
   return BGS_OK;
 }

@@ -2,8 +2,6 @@
 // State: `dp_planes` float planes, tiled over the global pixel index (kernel_dp.h), plus e->bgstate (mode count per pixel,
 // or the AdaptiveMedian byte image).
 
-bool is_dp(bgs_algo a) { return a >= BGS_DP_ZIVKOVIC_AGMM && a <= BGS_DP_ADAPTIVE_MEDIAN; }
-
 int dp_planes_of(const bgs_engine* e) {
   switch (e->algo) {
     case BGS_DP_ZIVKOVIC_AGMM: return e->p.dp_gaussians * 5;
@@ -25,10 +23,21 @@ void dp_launch_gmm(int K, unsigned blocks, hipStream_t s, const bgs::DpArgs& a) 
   }
 }
 
+int dp_check(bgs_algo algo, const bgs_params& p) {
+  if ((algo == BGS_DP_ZIVKOVIC_AGMM || algo == BGS_DP_GRIMSON_GMM) && (p.dp_gaussians < 1 || p.dp_gaussians > 5))
+    return fail(BGS_ERR_UNSUPPORTED, "dp GMM kernels are built for 1..5 gaussians, got %d", p.dp_gaussians);
+  if (algo == BGS_DP_ADAPTIVE_MEDIAN && p.dp_sampling_rate == 0) return fail(BGS_ERR_UNSUPPORTED, "AdaptiveMedian samplingRate 0 (frame_num %% 0)");
+  return BGS_OK;
+}
+
+bool dp_is_gmm(const bgs_engine* e) { return e->algo == BGS_DP_ZIVKOVIC_AGMM || e->algo == BGS_DP_GRIMSON_GMM; }
+
 int dp_allocate(bgs_engine* e) {
   if (e->ch != 3) return fail(BGS_ERR_UNSUPPORTED, "the dp/ models read RgbImage pixels: 3-channel frames only (dp/Image.h:257-265)");
   const size_t P = e->n * e->S;
   const int planes = dp_planes_of(e);
+  e->state_ch = dp_is_gmm(e) ? 1 : e->algo == BGS_DP_ADAPTIVE_MEDIAN ? 3 : 0;  // bgstate = modes per pixel / the median image
+  if (e->state_ch) DMALLOC(e->bgstate, P * e->state_ch);
   if (planes) {
     const size_t tiles = (P + bgs::kDpTile - 1) / bgs::kDpTile, bytes = tiles * planes * bgs::kDpTile * sizeof(float);
     if (!e->stream) HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
@@ -40,14 +49,21 @@ int dp_allocate(bgs_engine* e) {
   return BGS_OK;
 }
 
-// one frame (number t, 0-based = the wrappers' frameNumber) for streams [first, first+count)
+void dp_release(bgs_engine* e) { dfree(e->dp_state), dfree(e->bgstate); }
+
+uint64_t dp_key(const bgs_engine* e, int i) {
+  const int64_t t = e->seen[i];
+  if (e->algo == BGS_DP_ADAPTIVE_MEDIAN) return (uint64_t)(t == 0) | (uint64_t)((t % e->p.dp_sampling_rate) == 1) << 1;
+  return t == 0;
+}
+
+// `frames` frames for streams [first, first+count), the first one number e->seen[first] (0-based = the wrappers' frameNumber)
 // frames > 1 (Zivkovic / Grimson only, from process_clip): that many consecutive frames in one launch, d_* point at the first
-// slab: pixels from one frame of a clip to the next (0: the run is the whole slab)
-int dp_process(bgs_engine* e, int first, int count, int64_t t, const uint8_t* d_frames, uint8_t* d_fg, uint64_t* d_bits, hipStream_t s, uint32_t* flags,
-               int frames = 1, size_t slab = 0) {
+// slab: pixels from one frame of a clip to the next (a single frame: the run is the whole slab)
+int dp_process(bgs_engine* e, int first, int count, int frames, size_t slab, const uint8_t* d_frames, uint8_t* d_fg, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
   const bgs_params& p = e->p;
+  const int64_t t = e->seen[first];
   bgs::DpArgs a{};
-  if (!slab) slab = e->n * count;
   a.frames = frames, a.frame_stride = slab * 3, a.fg_stride = slab, a.bits_stride = slab / 64;
   a.frame = d_frames, a.state = e->dp_state, a.bstate = e->bgstate, a.fg = d_fg, a.fg_bits = d_bits;
   a.n = e->n, a.npix = e->n * count, a.first = first;
@@ -96,6 +112,15 @@ int dp_process(bgs_engine* e, int first, int count, int64_t t, const uint8_t* d_
   return BGS_OK;
 }
 
+int dp_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t*, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
+  return dp_process(e, first, count, 1, e->n * count, d_frames, d_fg, d_bits, s, flags);
+}
+
+// package_bgs/dp GMMs: the same kernel with a frame loop (kernel_dp.h)
+int dp_clip_fused(bgs_engine* e, int first, int count, int fuse, size_t slab, const uint8_t* fr, uint8_t* fg, uint8_t*, uint64_t* bits, hipStream_t s, uint32_t* flags) {
+  return dp_process(e, first, count, fuse, slab, fr, fg, bits, s, flags);
+}
+
 // canonical export [plane][n] of one stream from the tiled device layout
 int64_t dp_export_planes(bgs_engine* e, int stream, int planes, void* dst, size_t cap) {
   const size_t n = e->n, g0 = (size_t)stream * n, T = bgs::kDpTile;
@@ -110,3 +135,27 @@ int64_t dp_export_planes(bgs_engine* e, int stream, int planes, void* dst, size_
     }
   return (int64_t)planes * n * 4;
 }
+
+// planes are stored canonically: [stream][plane][n]
+int64_t dp_get_state(bgs_engine* e, int stream, const char* plane, void* dst, size_t cap) {
+  const size_t n = e->n, off = n * stream;
+  const int planes = dp_planes_of(e);
+  const char* fname = (e->algo == BGS_DP_WREN_GA) ? "gauss" : (e->algo == BGS_DP_MEAN) ? "mean" : "modes";
+  if (planes && !strcmp(plane, fname)) return dp_export_planes(e, stream, planes, dst, cap);
+  if (e->state_ch == 1 && !strcmp(plane, "nmodes")) return copy_plane(plane, dst, cap, e->bgstate + off, n);
+  if (e->state_ch == 3 && !strcmp(plane, "median")) return copy_plane(plane, dst, cap, e->bgstate + off * 3, n * 3);
+  return unknown_plane(e, plane);
+}
+
+// handed to the model object once, when it is built on the first frame (DP*BGS.cpp `if(firstTime)`)
+void dp_keep_frozen(bgs_params& p, const bgs_params& old) {
+  p.dp_threshold = old.dp_threshold, p.dp_alpha = old.dp_alpha, p.dp_gaussians = old.dp_gaussians;
+  p.dp_sampling_rate = old.dp_sampling_rate, p.learning_frames = old.learning_frames;
+}
+
+constexpr Family kDp = [] {
+  Family f{};
+  f.check = dp_check, f.allocate = dp_allocate, f.release = dp_release, f.key = dp_key, f.run = dp_run, f.get_state = dp_get_state;
+  f.keep_frozen = dp_keep_frozen, f.clip_fused = dp_clip_fused, f.clip_fusable = dp_is_gmm;
+  return f;
+}();

@@ -6,8 +6,6 @@
 // bgs_reset_stream): frames 0, r, 2r, ... are sampled, so k = ceil(t / |r|) samples were offered before frame t, the buffer holds
 // min(k, H) and a full one replaces slot (k - H) mod H next.  C's `t % r == 0` is the same test for a negative rate.
 
-bool is_dp2(bgs_algo a) { return a == BGS_DP_PRATI_MEDIOD || a == BGS_DP_TEXTURE; }
-
 int dp2_check(bgs_algo algo, const bgs_params& p) {
   if (algo != BGS_DP_PRATI_MEDIOD) return BGS_OK;
   if (p.dp_sampling_rate == 0) return fail(BGS_ERR_UNSUPPORTED, "PratiMediod samplingRate 0 (frame_num %% 0)");
@@ -63,7 +61,7 @@ void dp2_free(bgs_engine* e) {
 }
 
 // One frame of DPPratiMediodBGS::process / DPTextureBGS::process for streams [first, first+count), which share dp2_key.
-int dp2_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
+int dp2_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t*, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
   const size_t n = e->n, npix = n * count, S = (size_t)e->S;
   const bool fresh = e->seen[first] == 0;
   if (e->algo == BGS_DP_PRATI_MEDIOD) {
@@ -158,3 +156,21 @@ int64_t dp2_get_state(bgs_engine* e, int stream, const char* plane, void* dst, s
   }
   return fail(BGS_ERR_STATE, "unknown state plane '%s' for algorithm %d", plane, (int)e->algo);
 }
+
+// PratiMediodBGS::Initalize copies m_params once (DPPratiMediodBGS.cpp:55-64)
+void prati_keep_frozen(bgs_params& p, const bgs_params& old) {
+  p.dp_threshold = old.dp_threshold, p.dp_sampling_rate = old.dp_sampling_rate;
+  p.dp_history_size = old.dp_history_size, p.dp_weight = old.dp_weight;
+}
+
+constexpr Family kDpTexture = [] {
+  Family f{};
+  f.check = dp2_check, f.allocate = dp2_allocate, f.release = dp2_free, f.key = dp2_key, f.run = dp2_run, f.get_state = dp2_get_state;
+  return f;
+}();
+
+constexpr Family kDpPratiMediod = [] {
+  Family f = kDpTexture;
+  f.keep_frozen = prati_keep_frozen;
+  return f;
+}();

@@ -66,7 +66,6 @@ int fz_allocate(bgs_engine* e) {
   HIP_TRY(hipMemcpyAsync(e->fz_tab, tab, sizeof(tab), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));  // `tab` leaves scope
   e->fz_fn.assign(S, 0);
-  e->fz_flags.assign(S, 0);
   e->fz_detected.assign(S, 0);
   return BGS_OK;
 }
@@ -85,7 +84,6 @@ int fz_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t
   const uint32_t nb = (uint32_t)((n + bgs::kFzScan - 1) / bgs::kFzScan);
   if (d_bits && !d_fg) return fail(BGS_ERR_INVALID, "internal: the fuzzy integrals' packed mask needs a byte mask");  // process_range provides one
   uint32_t all = BGS_FG_VALID | BGS_BG_VALID;
-  e->fz_any_valid = false;
   for (int f = 0; f < count; f += bgs::kFzStreams) {
     const int c = std::min(bgs::kFzStreams, count - f);
     const size_t o = (size_t)f * n, so = (size_t)(first + f) * n;
@@ -107,15 +105,14 @@ int fz_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t
       const bool learn = e->fz_fn[st] <= (int64_t)p.frames_to_learn;            // if(frameNumber <= framesToLearn)
       if (learn) a.learn_mask |= (uint64_t)1 << i;
       else ++detecting, e->fz_detected[st] = 1;
-      e->fz_flags[st] = learn ? 0u : (uint32_t)(BGS_FG_VALID | BGS_BG_VALID);
-      all &= e->fz_flags[st];
+      e->last_flags[st] = learn ? 0u : (uint32_t)(BGS_FG_VALID | BGS_BG_VALID);  // per_stream_flags: learning and detecting streams share the run
+      all &= e->last_flags[st];
       e->fz_fn[st]++;
     }
     const uint32_t npix = (uint32_t)(n * c);
     Timed tm(e, s, detecting ? "fuzzy_frame (prep, pixel, scan block / top / apply, median, update)" : "fuzzy_prep_kernel (learning)");
     hipLaunchKernelGGL(bgs::fuzzy_prep_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, a, npix);
     if (!detecting) continue;
-    e->fz_any_valid = true;
     const dim3 tiles((e->cols + bgs::kFzTile - 1) / bgs::kFzTile, (e->rows + bgs::kFzTile - 1) / bgs::kFzTile, c), tile(bgs::kFzTile, bgs::kFzTile);
     hipLaunchKernelGGL(bgs::fuzzy_pixel_kernel, tiles, tile, 0, s, a);
     hipLaunchKernelGGL(bgs::fuzzy_scan_block_kernel, dim3(nb, c), dim3(bgs::kBlock), 0, s, a);
@@ -124,7 +121,7 @@ int fz_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t
     hipLaunchKernelGGL(bgs::fuzzy_median_kernel, tiles, tile, 0, s, a);
     hipLaunchKernelGGL(bgs::fuzzy_update_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, a, npix);
   }
-  if (d_bits && e->fz_any_valid)  // n % 64 == 0 here; the words of a learning stream are as undefined as its byte mask
+  if (d_bits && (any_flags(e, first, count) & BGS_FG_VALID))  // n % 64 == 0 here; the words of a learning stream are as undefined as its byte mask
     hipLaunchKernelGGL(bgs::mask_pack_kernel, dim3(blocks_for(n * count)), dim3(bgs::kBlock), 0, s, (const uint8_t*)d_fg, d_bits, n * count);
   *flags = all;
   return BGS_OK;
@@ -163,3 +160,14 @@ int64_t fz_get_state(bgs_engine* e, int stream, const char* plane, void* dst, si
   }
   return 8;
 }
+
+void fz_reset_stream(bgs_engine* e, int stream) {
+  if (!e->fz_fn.empty()) e->fz_fn[stream] = 0, e->fz_detected[stream] = 0;
+}
+
+constexpr Family kFuzzy = [] {
+  Family f{};
+  f.check_geometry = fz_check_geometry, f.allocate = fz_allocate, f.release = fz_free, f.key = fz_key, f.run = fz_run, f.get_state = fz_get_state;
+  f.reset_stream = fz_reset_stream, f.needs_byte_mask = always, f.per_stream_flags = true;
+  return f;
+}();

@@ -13,7 +13,7 @@
 int kde_tbl(const bgs_params& p) { return std::max(p.kde_time_window / p.kde_sequence_length, 2); }    // TemporalBufferLength
 int kde_rate(const bgs_params& p) { return std::max(p.kde_time_window / p.kde_sequence_length, 2); }   // sampling period (same expression)
 
-int kde_check(const bgs_params& p) {
+int kde_check(bgs_algo, const bgs_params& p) {
   if (p.kde_sequence_length < 3 || p.kde_sequence_length > 255)
     return fail(BGS_ERR_INVALID, "KDE SequenceLength must be 3..255 (PixelQTop and the histogram counts are bytes; below 3 medianCount is 0), got %d", p.kde_sequence_length);
   if (p.kde_frames_to_learn < 1) return fail(BGS_ERR_INVALID, "KDE framesToLearn must be >= 1, got %d", p.kde_frames_to_learn);
@@ -62,7 +62,7 @@ void kde_gate_table(double alpha, int2* out) {
 
 int kde_allocate(bgs_engine* e) {
   const bgs_params& p = e->p;
-  int rc = kde_check(p);
+  int rc = kde_check(e->algo, p);
   if (rc) return rc;
   if (e->ch == 1 && p.kde_color_ratios)
     return fail(BGS_ERR_UNSUPPORTED, "KDE colour ratios need 3-channel frames (BGR2SnGnRn reads 3 bytes per pixel of a gray frame: NPBGSubtractor.cpp:1141)");
@@ -110,7 +110,7 @@ uint64_t kde_key(const bgs_engine* e, int i) {
 }
 
 // One frame of KDE::process for streams [first, first+count), which share kde_key.
-int kde_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
+int kde_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t*, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
   const bgs_params& p = e->p;
   const size_t n = e->n, npix = n * count, SL = (size_t)p.kde_sequence_length, TBL = (size_t)kde_tbl(p);
   if (e->seen[first] == 0) {  // a new model (NPBGmodel's constructor: Sequence zero-filled); every plane cleared, run-contiguous
@@ -201,3 +201,18 @@ int64_t kde_get_state(bgs_engine* e, int stream, const char* plane, void* dst, s
   }
   return fail(BGS_ERR_STATE, "unknown state plane '%s' for algorithm %d", plane, (int)e->algo);
 }
+
+void kde_reset_stream(bgs_engine* e, int stream) { e->kde[stream] = bgs_engine::KdeStream(); }  // sized by bgs_create, unlike lb_mk / vu_count / fz_fn (sized by allocate): no guard
+
+// KDE.cpp:40-66: Intialize / SetThresholds once; framesToLearn is re-read every frame (and update_model is live)
+void kde_keep_frozen(bgs_params& p, const bgs_params& old) {
+  p.kde_sequence_length = old.kde_sequence_length, p.kde_time_window = old.kde_time_window, p.kde_sd_estimation = old.kde_sd_estimation;
+  p.kde_color_ratios = old.kde_color_ratios, p.kde_threshold = old.kde_threshold, p.kde_alpha = old.kde_alpha;
+}
+
+constexpr Family kKde = [] {
+  Family f{};
+  f.check = kde_check, f.allocate = kde_allocate, f.release = kde_free, f.key = kde_key, f.run = kde_run, f.get_state = kde_get_state;
+  f.reset_stream = kde_reset_stream, f.keep_frozen = kde_keep_frozen;
+  return f;
+}();

@@ -7,7 +7,6 @@
 // The SOMs' training counter m_K is the model object's own state (restarted by Init, advanced by Update while m_K <= m_TSteps, and
 // m_TSteps may change between frames), so it is kept per stream here and not derived from bgs_engine::seen.
 
-bool is_lb(bgs_algo a) { return a >= BGS_LB_SIMPLE_GAUSSIAN && a <= BGS_LB_FUZZY_ADAPTIVE_SOM; }
 bool is_lb_som(bgs_algo a) { return a == BGS_LB_ADAPTIVE_SOM || a == BGS_LB_FUZZY_ADAPTIVE_SOM; }
 
 const char* lb_name(bgs_algo a) {
@@ -83,7 +82,7 @@ int lb_allocate(bgs_engine* e) {
 }
 
 void lb_free(bgs_engine* e) {
-  if (e->lb_model) (void)hipFree(e->lb_model);  // free_all has already dropped a model built from chunks
+  if (e->lb_model) (void)hipFree(e->lb_model);
   if (e->lb_k) (void)hipFree(e->lb_k);
   if (e->lb_bg) (void)hipFree(e->lb_bg);
   e->lb_model = nullptr, e->lb_k = nullptr, e->lb_bg = nullptr;
@@ -226,3 +225,13 @@ int64_t lb_get_state(bgs_engine* e, int stream, const char* plane, void* dst, si
   }
   return fail(BGS_ERR_STATE, "unknown state plane '%s' for algorithm %d", plane, (int)e->algo);
 }
+
+void lb_reset_stream(bgs_engine* e, int stream) {
+  if (!e->lb_mk.empty()) e->lb_mk[stream] = 0;
+}
+
+constexpr Family kLb = [] {
+  Family f{};
+  f.check = lb_check, f.allocate = lb_allocate, f.release = lb_free, f.key = lb_key, f.run = lb_run, f.get_state = lb_get_state, f.reset_stream = lb_reset_stream;
+  return f;
+}();

@@ -1,0 +1,243 @@
+// engine_mog2.h — host side of MixtureOfGaussianV2BGS (BGS_MOG2; kernel_mog2.h: tiles of ranked weights + fixed-slot records +
+// rank->slot meta words): the automatic choice of how a launch loads the model, the per-frame and the clip launch, the state export.
+// Included by bgs_hip.hip inside its anonymous namespace, after engine_mog1.h (mog_lr_key, mog_clip_fusable).
+
+int mog2_check(bgs_algo, const bgs_params& p) {
+  if (p.mog2_nmixtures != bgs::kMog2K) return fail(BGS_ERR_UNSUPPORTED, "MOG2 kernel is built for K=%d mixtures, got %d", bgs::kMog2K, p.mog2_nmixtures);
+  return BGS_OK;
+}
+
+int mog2_check_geometry(bgs_algo, int, int, int ch) {
+  if (ch != 3) return fail(BGS_ERR_UNSUPPORTED, "MixtureOfGaussianV2BGS needs 3 channels: getBackgroundImage asserts nchannels == 3 (MixtureOfGaussianV2BGS.cpp:59)");
+  return BGS_OK;
+}
+
+// Automatic choice of how a per-frame launch loads a pixel's model (kernel_mog2.h; results are identical, only speed differs):
+//   1 eager   everything at once, no dependent loads: right when most pixels have most modes and need them;
+//   2 count   only the modes a pixel has (one dependent round): quiet scenes, one or two modes per pixel;
+//   4 filter  summaries first, then only the records they cannot rule out (one dependent round, +4 B per mode for the
+//             summaries): pays when at least half of a pixel's records are ruled out (modes far apart).
+// About 256 sampled workgroups of every filter-kernel launch count, per pixel, the modes it has and the records that kernel loads
+// or would load (when another kernel is current, every 16th launch - every 4th of a stream's first 64 - is a filter launch for
+// that purpose).  The host never blocks: the counters come back through a pinned buffer and an event that is queried before
+// every launch; it switches at once on clear evidence, else when two samples in a row ask for the same other mode.
+void mog2_stat_read(bgs_engine* e) {
+  // the newest post whose copy has completed; everything older is dropped with it
+  int slot = -1;
+  for (unsigned back = 1; back <= (unsigned)bgs_engine::kStatSlots && back <= e->stat_seq; ++back) {
+    const int i = (int)((e->stat_seq - back) % bgs_engine::kStatSlots);
+    if (!e->stat_posted[i]) break;  // already consumed (and so is everything older)
+    if (slot < 0 && hipEventQuery(e->stat_ev[i]) == hipSuccess) slot = i;
+    if (slot >= 0) e->stat_posted[i] = false;
+  }
+  if (slot < 0) return;
+  const unsigned* hs = e->h_stat + 3 * slot;
+  const unsigned total = hs[0], live = hs[1], need = hs[2];
+  if (total < 64 * 5) return;
+  const float lf = (float)live / (float)total, nf = (float)need / (float)total;
+  const int want = (nf < 0.5f * lf && lf - nf > 0.1f) ? 4 : lf < 0.7f ? 2 : 1;
+  const bool clear = (want == 4 && nf < 0.35f * lf) || (want != 4 && e->mog2_sparse_now == 4 && nf > 0.8f * lf);
+  static const bool debug = getenv("BGS_DEBUG_STAT") != nullptr;
+  if (debug)
+    fprintf(stderr, "[bgs] mog2 auto: %u record slots sampled, %.3f live, %.3f needed after the summaries -> mode %d (now %d)\n", total, lf, nf, want, e->mog2_sparse_now);
+  if (want != e->mog2_sparse_now && (clear || want == e->mog2_sparse_want)) e->mog2_sparse_now = want;
+  e->mog2_sparse_want = want;
+}
+void mog2_stat_post(bgs_engine* e, hipStream_t s) {
+  const int i = (int)(e->stat_seq % bgs_engine::kStatSlots);  // the oldest slot is reused (its event re-recorded) if nobody read it
+  (void)hipMemcpyAsync(e->h_stat + 3 * i, e->d_stat, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, s);
+  (void)hipMemsetAsync(e->d_stat, 0, 3 * sizeof(unsigned), s);
+  (void)hipEventRecord(e->stat_ev[i], s);
+  e->stat_posted[i] = true;
+  e->stat_seq++;
+}
+
+int launch_mog2(bgs_engine* e, bgs::Mog2Args& a, hipStream_t s, bool timed = true) {
+  const bgs_params& p = e->p;
+  // shadow test only when it can change the delivered mask: not thresholded, or the threshold separates shadow from foreground
+  a.shadow = p.mog2_detect_shadows && (!p.enable_threshold || ((p.mog2_shadow_value > p.threshold) != (255 > p.threshold)));
+  a.want_bg = a.bgimg != nullptr, a.packed = a.fg_bits != nullptr;
+  a.xcd_swizzle = e->xcd_swizzle, a.complete = e->mog2_complete;
+  const bool autom = timed && e->mog2_sparse == 3;
+  if (autom) mog2_stat_read(e);
+  int mode = e->mog2_sparse == 3 ? e->mog2_sparse_now : e->mog2_sparse;
+  if (mode >= 4 && (a.shadow || a.want_bg)) mode = 2;  // shadow test and background image read every mode's mean: nothing to rule out
+  // auto mode: the filter kernel's sampled workgroups count what each way of loading would read; when another kernel is current,
+  // every 16th launch (every 4th of the first 64) goes through the filter kernel anyway so that the choice keeps following the scene
+  if (autom && mode != 4) {
+    const unsigned n = e->mog2_launches++;
+    if ((n & (n < 64 ? 3u : 15u)) == 0) mode = 4;
+  }
+  a.sparse = mode;
+  a.stat = (autom && mode == 4) ? e->d_stat : nullptr;
+  if (a.packed && a.npix % 64) return fail(BGS_ERR_UNSUPPORTED, "packed mask needs pixels %% 64 == 0");
+  Timed t(e, s, "mog2_update_kernel", timed);
+  const dim3 grid(blocks_for(a.npix)), block(bgs::kBlock);  // one pixel per lane (round 2's 1 / 2 / 4 comparison: equal or better everywhere)
+  unsigned every = 1;  // sample about 256 workgroups per launch whatever the grid: enough to decide, few enough atomics not to show
+  while (grid.x / every > 256) every <<= 1;
+  a.stat_mask = every - 1;
+  // BGS_MOG2_LDS_PAD=bytes: unused dynamic LDS per workgroup - fewer workgroups fit a CU (160 KB): the occupancy study of DESIGN.md 6.1
+  // (round 4: 2 / 3 / 4 / 5 waves per SIMD 2.15 / 1.50 / 1.22 / 1.09 ms; a build of the filter kernel without the shadow and background
+  // code - 66 instead of 91 VGPRs, 7 waves - ran no faster than this one's 5: profiles/r04_mog2_occupancy_ab.txt)
+  static const unsigned lds_pad = getenv("BGS_MOG2_LDS_PAD") ? (unsigned)std::max(0, std::min(65536, atoi(getenv("BGS_MOG2_LDS_PAD")))) : 0u;
+  if (mode >= 4)
+    hipLaunchKernelGGL((bgs::mog2_update_kernel<bgs::kMog2Filter>), grid, block, lds_pad, s, a);
+  else if (mode >= 2)
+    hipLaunchKernelGGL((bgs::mog2_update_kernel<bgs::kMog2Count>), grid, block, lds_pad, s, a);
+  else
+    hipLaunchKernelGGL((bgs::mog2_update_kernel<bgs::kMog2Eager>), grid, block, lds_pad, s, a);
+  if (a.stat) mog2_stat_post(e, s);
+  return BGS_OK;
+}
+
+void mog2_fill_args(const bgs_engine* e, bgs::Mog2Args& m, double lr) {
+  const bgs_params& p = e->p;
+  m.state = e->mog2_state;
+  m.alphaT = (float)lr, m.alpha1 = 1.f - m.alphaT, m.prune = (float)(-lr * (double)p.mog2_ct);
+  m.Tb = p.mog2_var_threshold, m.TB = p.mog2_background_ratio, m.Tg = p.mog2_var_threshold_gen;
+  m.varInit = p.mog2_var_init, m.varMin = p.mog2_var_min, m.varMax = p.mog2_var_max, m.tau = p.mog2_tau;
+  m.thr = p.threshold, m.enable_thr = p.enable_threshold, m.shadow_val = p.mog2_shadow_value;
+}
+
+void mog2_clear(bgs_engine* e, const bgs::Mog2Args& m, hipStream_t s) {
+  hipLaunchKernelGGL(bgs::mog2_clear_kernel, dim3(blocks_for(m.npix)), dim3(bgs::kBlock), 0, s, m);
+}
+
+// One launch over `fuse` (2, 4 or 8) consecutive frames of streams whose model starts at c.m.state_off (kernel_mog2.h, clip launches)
+int launch_mog2_clip(bgs_engine* e, bgs::Mog2ClipArgs& c, int fuse, hipStream_t s) {
+  const bgs_params& p = e->p;
+  bgs::Mog2Args& a = c.m;
+  a.shadow = p.mog2_detect_shadows && (!p.enable_threshold || ((p.mog2_shadow_value > p.threshold) != (255 > p.threshold)));
+  a.want_bg = a.bgimg != nullptr, a.packed = a.fg_bits != nullptr;
+  a.xcd_swizzle = e->xcd_swizzle, a.complete = e->mog2_complete;
+  a.sparse = e->mog2_sparse == 0 ? 0 : 1;  // clip launches load every record at once (kernel_mog2.h)
+  a.stat = nullptr;
+  if (a.packed && a.npix % 64) return fail(BGS_ERR_UNSUPPORTED, "packed mask needs pixels %% 64 == 0");
+  Timed t(e, s, "mog2_clip_kernel");
+  const dim3 grid(blocks_for(a.npix)), block(bgs::kBlock);
+  unsigned every = 1;
+  while (grid.x / every > 256) every <<= 1;
+  a.stat_mask = every - 1;
+#define MOG2_CLIP_CASE(TV) \
+  if (fuse == TV) hipLaunchKernelGGL((bgs::mog2_clip_kernel<TV>), grid, block, 0, s, c);
+  MOG2_CLIP_CASE(2) MOG2_CLIP_CASE(4) MOG2_CLIP_CASE(8)
+#undef MOG2_CLIP_CASE
+  return BGS_OK;
+}
+
+size_t mog2_state_bytes(const bgs_engine* e) {
+  const size_t P = e->n * e->S;
+  return (P + bgs::kMog2Tile - 1) / bgs::kMog2Tile * bgs::kMog2TileBytes;
+}
+
+int mog2_allocate(bgs_engine* e) {
+  const size_t bytes = mog2_state_bytes(e);
+  HIP_TRY(hipMalloc((void**)&e->d_stat, 3 * sizeof(unsigned)));
+  HIP_TRY(hipMemsetAsync(e->d_stat, 0, 3 * sizeof(unsigned), e->stream));  // ordered: allocate() drains e->stream before it returns
+  HIP_TRY(hipHostMalloc((void**)&e->h_stat, 3 * bgs_engine::kStatSlots * sizeof(unsigned), hipHostMallocDefault));
+  for (int i = 0; i < bgs_engine::kStatSlots; ++i) HIP_TRY(hipEventCreateWithFlags(&e->stat_ev[i], hipEventDisableTiming));
+  return model_allocate(e, (void**)&e->mog2_state, bytes);
+}
+
+void mog2_release(bgs_engine* e) {
+  dfree(e->mog2_state), dfree(e->d_stat);
+  if (e->h_stat) (void)hipHostFree(e->h_stat), e->h_stat = nullptr;
+  for (int i = 0; i < bgs_engine::kStatSlots; ++i) {
+    if (e->stat_ev[i]) (void)hipEventDestroy(e->stat_ev[i]), e->stat_ev[i] = nullptr;
+    e->stat_posted[i] = false;
+  }
+}
+
+uint64_t mog2_key(const bgs_engine* e, int i) { return mog_lr_key(e, i, e->p.mog2_history, 2); }
+
+int mog2_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
+  const bgs_params& p = e->p;
+  double lr = p.alpha;
+  int64_t nframes = e->seen[first];
+  bgs::Mog2Args m{};
+  m.state_off = e->n * first, m.npix = e->n * count;
+  mog2_fill_args(e, m, 0.0);
+  if (nframes == 0 || lr >= 1) {  // needToInitialize: bgmodel = zeros, modesUsed = 0
+    mog2_clear(e, m, s);
+    nframes = 0;
+  }
+  ++nframes;
+  const int64_t n2 = 2 * nframes;
+  lr = (lr >= 0 && nframes > 1) ? lr : 1. / (double)std::min<int64_t>(n2, p.mog2_history);
+  mog2_fill_args(e, m, lr);
+  m.frame = d_frames, m.fg = d_fg, m.bgimg = d_bg, m.fg_bits = d_bits;
+  int rc = launch_mog2(e, m, s);
+  if (rc) return rc;
+  if (nframes == 1)  // re-initialisation restarts the count (the streams of a run may otherwise have different ages: launch_key)
+    for (int i = first; i < first + count; ++i) e->seen[i] = 0;
+  *flags = BGS_FG_VALID | BGS_BG_VALID;
+  return BGS_OK;
+}
+
+int mog2_clip_fused(bgs_engine* e, int first, int count, int fuse, size_t slab, const uint8_t* fr, uint8_t* fg, uint8_t* bg, uint64_t* bits, hipStream_t s, uint32_t* flags) {
+  const bgs_params& p = e->p;
+  const int64_t seen = e->seen[first];
+  bgs::Mog2ClipArgs c{};
+  c.m.state_off = e->n * first, c.m.npix = e->n * count;
+  mog2_fill_args(e, c.m, 0.0);
+  if (seen == 0) mog2_clear(e, c.m, s);  // needToInitialize on a stream's first frame
+  for (int j = 0; j < fuse; ++j) {       // the learning rate of each frame, as the single-frame path computes it
+    const int64_t nf = seen + j + 1;
+    const double lr = (p.alpha >= 0 && nf > 1) ? p.alpha : 1. / (double)std::min<int64_t>(2 * nf, p.mog2_history);
+    c.alphaT[j] = (float)lr, c.alpha1[j] = 1.f - c.alphaT[j], c.prune[j] = (float)(-lr * (double)p.mog2_ct);
+  }
+  c.m.frame = fr, c.m.fg = fg, c.m.bgimg = bg, c.m.fg_bits = bits;
+  c.frame_stride = slab * 3, c.fg_stride = slab, c.bg_stride = slab * 3, c.bits_stride = slab / 64;
+  *flags = BGS_FG_VALID | BGS_BG_VALID;
+  return launch_mog2_clip(e, c, fuse, s);
+}
+
+// canonical export: "w" [K][n], "var" [K][n], "mu" [K][3][n] floats, "nmodes" [n] bytes — whatever the device layout
+int64_t mog2_get_state(bgs_engine* e, int stream, const char* plane, void* dst, size_t cap) {
+  const size_t n = e->n, off = n * stream;
+  int p0 = -1, np = 0;
+  if (!strcmp(plane, "w")) p0 = 0, np = 5;
+  if (!strcmp(plane, "var")) p0 = 5, np = 5;
+  if (!strcmp(plane, "mu")) p0 = 10, np = 15;
+  if (!strcmp(plane, "summary")) p0 = 100, np = 5;  // uint32 [K][n] by rank: the 16-bit word q0 | q1 << 5 | q2 << 10 | class << 15 (kernel_mog2.h; for the invariant test)
+  const bool nm = !strcmp(plane, "nmodes") || !strcmp(plane, "summary_valid");  // bytes [n]; summary_valid: bit 15 of the meta word
+  const bool want_valid = !strcmp(plane, "summary_valid");
+  if (p0 < 0 && !nm) return unknown_plane(e, plane);
+  // device layout (kernel_mog2.h): weights by rank, {var, mean} records in fixed slots, meta = rank -> slot.  Exported in the
+  // reference's array order (rank); entries past a pixel's mode count are zero, as in the reference's zero-initialised bgmodel.
+  const size_t need = nm ? n : (size_t)np * n * 4;
+  if (cap < need) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
+  const size_t T = bgs::kMog2Tile, TB = bgs::kMog2TileBytes;
+  const size_t t0 = off / T, t1 = (off + n + T - 1) / T;
+  std::vector<uint8_t> tiles((t1 - t0) * TB);
+  if (d2h_staged(tiles.data(), e->mog2_state + t0 * TB, tiles.size()) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
+  for (size_t i = 0; i < n; ++i) {
+    const size_t sp = off + i, in = sp % T;
+    const uint8_t* tb = tiles.data() + (sp / T - t0) * TB;
+    const float* w = reinterpret_cast<const float*>(tb) + in;
+    const float* rec = reinterpret_cast<const float*>(tb + bgs::kMog2RecOff) + in * 4;
+    const uint16_t* sum = reinterpret_cast<const uint16_t*>(tb + bgs::kMog2SumOff) + in;
+    const unsigned meta = reinterpret_cast<const uint16_t*>(tb + bgs::kMog2MetaOff)[in];
+    if (nm) {
+      ((uint8_t*)dst)[i] = want_valid ? (uint8_t)((meta >> 15) & 1u) : (uint8_t)bgs::mog2_meta_count(meta);
+      continue;
+    }
+    for (int r = 0; r < bgs::kMog2K; ++r) {
+      const unsigned f = (meta >> (3 * r)) & 7u;
+      const float* rc = f ? rec + (size_t)(f - 1) * T * 4 : nullptr;
+      if (p0 == 100) ((uint32_t*)dst)[(size_t)r * n + i] = f ? sum[(size_t)(f - 1) * T] : 0u;
+      if (p0 == 0) ((float*)dst)[(size_t)r * n + i] = f ? w[(size_t)r * T] : 0.f;
+      if (p0 == 5) ((float*)dst)[(size_t)r * n + i] = f ? rc[0] : 0.f;
+      if (p0 == 10)
+        for (int c = 0; c < 3; ++c) ((float*)dst)[((size_t)r * 3 + c) * n + i] = f ? rc[1 + c] : 0.f;
+    }
+  }
+  return (int64_t)need;
+}
+
+constexpr Family kMog2 = [] {
+  Family f{};
+  f.check = mog2_check, f.check_geometry = mog2_check_geometry, f.allocate = mog2_allocate, f.release = mog2_release, f.key = mog2_key, f.run = mog2_run;
+  f.get_state = mog2_get_state, f.clip_fused = mog2_clip_fused, f.clip_fusable = mog_clip_fusable;
+  return f;
+}();

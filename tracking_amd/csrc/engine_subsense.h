@@ -460,8 +460,9 @@ int ss_process_range(bgs_engine* e, int first, int count, const uint8_t* d_frame
 // 2 parts 3.01 ms young / 2.24 aged, 4 parts 3.99 / 2.30 against 2.82 / 1.60-1.67 as one launch (profiles/r04_subsense_token_parts.txt;
 // same reasons as the token's).  Same kernels on the same per-stream state: results do not depend on the cut (tests: 1, 2, 4 parts in
 // child processes).
-int ss_process(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, hipStream_t s, int64_t t) {
+int ss_process(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, hipStream_t s) {
   SsDevice* d = e->ss;
+  const int64_t t = e->seen[first];
   static const int parts_env = getenv("BGS_SS_PARTS") ? std::max(1, std::min((int)SsDevice::kParts, atoi(getenv("BGS_SS_PARTS")))) : bgs::kSsParts;
   static const bool overlap = !(getenv("BGS_SS_OVERLAP") && atoi(getenv("BGS_SS_OVERLAP")) == 0);
   const size_t N = e->n, C = (size_t)e->ch;
@@ -606,8 +607,9 @@ void lob_fill_args(const bgs_engine* e, bgs::SsArgs& a, int first, unsigned fram
   a.refill = refill;
 }
 
-int lob_process(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, hipStream_t s, int64_t t) {
+int lob_process(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, hipStream_t s) {
   SsDevice* d = e->ss;
+  const int64_t t = e->seen[first];
   const size_t N = e->n, off = N * first, npix = N * count, nS = (size_t)e->p.subsense_n_samples, C = (size_t)e->ch;
   const dim3 block(bgs::kBlock);
   if (t == 0) {  // LOBSTER.cpp:27-34: construct + initialize on the first frame, then fall through to operator()
@@ -682,3 +684,42 @@ void ss_free(bgs_engine* e) {
     e->ss = nullptr;
   }
 }
+
+// SuBSENSE / LOBSTER: the frame index itself goes into the kernels (counter-based random draws); + which half of the ping-pong maps is current
+uint64_t ss_key(const bgs_engine* e, int i) { return (uint64_t)e->seen[i] | (uint64_t)(e->ss->pp[i] & 1) << 62; }
+
+// the mask is also model state (m_oLastFGMask): the packed mask is made from there
+int ss_finish(bgs_engine* e, int first, int count, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
+  const size_t npix = e->n * count, off = e->n * first;
+  if (d_bits) hipLaunchKernelGGL(bgs::mask_pack_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, (const uint8_t*)(e->ss->u8[SS_LASTFG] + off), d_bits, npix);
+  *flags = BGS_FG_VALID | BGS_BG_VALID;
+  return BGS_OK;
+}
+int ss_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
+  int rc = ss_process(e, first, count, d_frames, d_fg, d_bg, s);
+  return rc ? rc : ss_finish(e, first, count, d_bits, s, flags);
+}
+int lob_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
+  int rc = lob_process(e, first, count, d_frames, d_fg, d_bg, s);
+  return rc ? rc : ss_finish(e, first, count, d_bits, s, flags);
+}
+
+// handed to the model object once, when it is built on the first frame (SuBSENSE.cpp:27-36, LOBSTER.cpp:27-34)
+void ss_keep_frozen(bgs_params& p, const bgs_params& old) {
+  p.lbsp_rel_threshold = old.lbsp_rel_threshold, p.lbsp_threshold_offset = old.lbsp_threshold_offset;
+  p.subsense_min_color_dist_threshold = old.subsense_min_color_dist_threshold, p.subsense_n_samples = old.subsense_n_samples;
+  p.subsense_n_required = old.subsense_n_required, p.subsense_samples_for_moving_avgs = old.subsense_samples_for_moving_avgs;
+  p.subsense_desc_dist_threshold_offset = old.subsense_desc_dist_threshold_offset;
+}
+
+constexpr Family kSubsense = [] {
+  Family f{};
+  f.allocate = ss_allocate, f.release = ss_free, f.key = ss_key, f.run = ss_run, f.get_state = ss_get_state, f.keep_frozen = ss_keep_frozen;
+  return f;
+}();
+
+constexpr Family kLobster = [] {
+  Family f = kSubsense;
+  f.allocate = lob_allocate, f.run = lob_run;
+  return f;
+}();

@@ -26,8 +26,12 @@ int vu_mode(const bgs_engine* e) { return vu_model_params(e->p).bin_count > bgs:
 
 uint64_t vu_key(const bgs_engine*, int) { return 0; }  // first frames and the quiet phase go into the launch as per-stream bits
 
+int vu_check_geometry(bgs_algo, int, int, int ch) {
+  if (ch != 3) return fail(BGS_ERR_UNSUPPORTED, "VuMeter reads 3-channel frames only (cvCvtColor(frame, gray, CV_RGB2GRAY) asserts, VuMeter.cpp:49)");
+  return BGS_OK;
+}
+
 int vu_allocate(bgs_engine* e) {
-  if (e->ch != 3) return fail(BGS_ERR_UNSUPPORTED, "VuMeter reads 3-channel frames only (cvCvtColor(frame, gray, CV_RGB2GRAY) asserts, VuMeter.cpp:49)");
   const size_t n = e->n, S = (size_t)e->S;
   if (n * S >= (size_t)1 << 31) return fail(BGS_ERR_INVALID, "VuMeter: streams x pixels must stay below 2^31");
   const VuModelParams mp = vu_model_params(e->p);
@@ -43,7 +47,7 @@ int vu_allocate(bgs_engine* e) {
 }
 
 void vu_free(bgs_engine* e) {
-  if (e->vu_hist) (void)hipFree(e->vu_hist);  // free_all has already dropped a model built from chunks
+  if (e->vu_hist) (void)hipFree(e->vu_hist);
   void* dev[] = {e->vu_bg, e->vu_raw, e->vu_tmp, e->vu_live};
   for (void* d : dev)
     if (d) (void)hipFree(d);
@@ -135,3 +139,20 @@ int64_t vu_get_state(bgs_engine* e, int stream, const char* plane, void* dst, si
   }
   return fail(BGS_ERR_STATE, "unknown state plane '%s' for algorithm %d", plane, (int)e->algo);
 }
+
+void vu_reset_stream(bgs_engine* e, int stream) {
+  if (!e->vu_count.empty()) e->vu_count[stream] = 0;
+}
+
+// VuMeter.cpp:42-47: SetAlpha / SetBinSize / SetThreshold on the first frame only; enableFilter is live
+void vu_keep_frozen(bgs_params& p, const bgs_params& old) { p.vu_bin_size = old.vu_bin_size, p.vu_alpha = old.vu_alpha, p.vu_threshold = old.vu_threshold; }
+
+// the filtered mask is finished by erode + median: its packed form is made from the byte mask
+bool vu_needs_byte_mask(const bgs_engine* e) { return e->p.vu_enable_filter != 0; }
+
+constexpr Family kVuMeter = [] {
+  Family f{};
+  f.check_geometry = vu_check_geometry, f.allocate = vu_allocate, f.release = vu_free, f.key = vu_key, f.run = vu_run, f.get_state = vu_get_state;
+  f.reset_stream = vu_reset_stream, f.keep_frozen = vu_keep_frozen, f.needs_byte_mask = vu_needs_byte_mask, f.bg_channels = 1;
+  return f;
+}();
