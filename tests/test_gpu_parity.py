@@ -425,11 +425,10 @@ def test_subsense_flood_fill_finish_kernel_path(golden_frames, tmp_path):
 
 
 def test_round2_forms_of_the_round3_kernels_still_match(golden_frames):
-    """Round 3 replaced several kernels and kept the earlier forms behind knobs that are read once per process (A/B builds, and the
-    fallbacks for geometries the new forms do not take): SuBSENSE with the self updates in phase B, the tile flood fill and the
-    LDS-count median; AdaptiveSelectiveBackgroundLearning through the LDS-tile kernel; LOBSTER's phase A with one pixel per lane in lock
-    step (round 4 feeds the lanes from a queue).  One child process with all of them set:
-    same masks, backgrounds and models as the oracle."""
+    """Round 3 replaced several kernels; two of the earlier forms are still the fallbacks for geometries the new forms do not take and
+    can be forced by knobs that are read once per process: SuBSENSE's flood fill with a wave per 64x64 tile (BGS_SS_FLOOD_TILES=1, the
+    path of images taller than 4 096 rows) and AdaptiveSelectiveBackgroundLearning through the LDS-tile kernel (BGS_ASBL_TABLE=0).  One
+    child process with both set (LOBSTER runs along with no knob of its own left): same masks, backgrounds and models as the oracle."""
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
@@ -447,19 +446,18 @@ def test_round2_forms_of_the_round3_kernels_still_match(golden_frames):
             "eng, orc, _ = run_pair(capi.LOBSTER, g)\n"
             "check_lobster_state(eng, orc, 240, 320)\n"
             "print('round-2 forms OK')\n") % (os.path.dirname(here), here, os.path.join(here, "golden", "frames_96x80.npz"))
-    env = dict(os.environ, BGS_SS_SELF_IN_A="0", BGS_SS_FLOOD_TILES="1", BGS_SS_MEDIAN_BITS="0", BGS_ASBL_TABLE="0", BGS_LOB_QUEUE="0")
+    env = dict(os.environ, BGS_SS_FLOOD_TILES="1", BGS_ASBL_TABLE="0")
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "round-2 forms OK" in r.stdout, r.stdout + r.stderr
 
 
-@pytest.mark.parametrize("knob", ["BGS_SS_FEEDBACK_SPLIT=1", "BGS_SS_QUEUE=1", "BGS_SS_IPASS_MIN=1 BGS_SS_FLOOD_WG1024=1 BGS_SS_B_LATE=1", "BGS_SS_IPASS_MIN=48 BGS_SS_REFILL=4"])
+@pytest.mark.parametrize("knob", ["BGS_SS_IPASS_MIN=1", "BGS_SS_IPASS_MIN=48 BGS_SS_REFILL=4"])
 def test_subsense_round4_forms_behind_knobs_match_the_oracle(knob):
-    """Round 4 built the two restructurings of phase A the verdict asked for - the rules behind the loop as a kernel of their own
-    (BGS_SS_FEEDBACK_SPLIT=1) and the inter-LBSP tests worked off a per-wave list by whichever lane is free (BGS_SS_QUEUE=1) - measured
-    both slower than the form that runs by default and kept them as A/B knobs.  Also behind knobs: the inter-LBSP passes
-    taken at once (BGS_SS_IPASS_MIN=1, round 3's form; the default puts off a pass that fewer than 16 lanes would join) or put off
-    until 48 lanes join, the flood strips in 1024-lane workgroups, phase B started behind the flood fill.  Knobs are read once per process: one
-    child process each, same masks, backgrounds and whole model as the oracle incl. a scene cut (model reset) and a large frame."""
+    """The tuning knobs of phase A's stage 2 that are left (the restructurings round 4 measured and lost are gone): the
+    inter-LBSP passes taken at once (BGS_SS_IPASS_MIN=1, round 3's form; the default puts off a pass that fewer than 16 lanes would
+    join) or put off until 48 lanes join, with the lanes refilled from the queue as soon as four are idle (BGS_SS_REFILL=4).  Knobs are
+    read once per process: one child process each, same masks, backgrounds and whole model as the oracle incl. a scene cut (model
+    reset) and a large frame."""
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
@@ -481,16 +479,11 @@ def test_subsense_round4_forms_behind_knobs_match_the_oracle(knob):
     assert r.returncode == 0 and "knob form OK" in r.stdout, r.stdout + r.stderr
 
 
-@pytest.mark.parametrize("knob", ["BGS_SS_PARTS=4 BGS_SS_PART_MIN_PIXELS=1", "BGS_SS_PARTS=2 BGS_SS_PART_MIN_PIXELS=1 GPU_MAX_HW_QUEUES=8", "BGS_SS_PARTS=1 BGS_SS_PART_MIN_PIXELS=1",
-                                  "BGS_SS_A_TOKEN=1 BGS_SS_PART_MIN_PIXELS=1"])
-def test_subsense_batch_in_parts_and_ranges_on_their_own_streams_match_the_oracle(knob):
-    """Round 4, engine_subsense.h: callers may drive stream ranges on HIP streams of their own (every call has its own pair of events on
-    the side stream); behind knobs - measured, no gain, off by default - a large batch is cut into parts on HIP streams of the engine
-    (BGS_SS_PARTS) and the phase A launches of all calls take turns (the "phase A token", BGS_SS_A_TOKEN=1) so that one part's phase B
-    and post-processing run beside another part's phase A.  Five cameras with different scenes (one with a scene cut: refreshModel(0.1)),
-    (a) as one batch call cut into 4 / 2 / 1 parts (5 streams: uneven parts), (b) as the ranges [0, 2) and [2, 5) on two HIP streams -
-    every mask, background and whole model equals its own oracle's.  The size threshold is lowered so that 240 x 320 frames take the paths
-    1080p batches take; knobs are read once per process: child processes."""
+def test_subsense_one_batch_and_ranges_on_their_own_streams_match_the_oracle():
+    """engine_subsense.h: callers may drive stream ranges on HIP streams of their own (every call has its own pair of events on the side
+    stream).  Five cameras with different scenes (one with a scene cut: refreshModel(0.1)), (a) as one batch call, (b) as the ranges
+    [0, 2) and [2, 5) on two HIP streams - every mask, background and whole model equals its own oracle's.  In a child process, with no
+    knob set."""
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
@@ -521,7 +514,7 @@ def test_subsense_batch_in_parts_and_ranges_on_their_own_streams_match_the_oracl
             "    for s in range(S): check_subsense_state(eng, orcs[s], H, W, stream=s)\n"
             "    eng.close()\n"
             "print('parts and ranges OK')\n") % (os.path.dirname(here), here)
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **dict(kv.split("=") for kv in knob.split())), capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "parts and ranges OK" in r.stdout, r.stdout + r.stderr
 
 
@@ -544,7 +537,7 @@ def test_subsense_large_frame_5x5_spread():
 
 
 def test_subsense_modulo_by_multiplication_is_exact(golden_frames):
-    """ss_feedback_kernel takes its five run-time `x % d` (which sample, which neighbour: BackgroundSubtractorSuBSENSE.cpp:508-551) as
+    """Stage 3 of ss_phase_a_kernel takes its five run-time `x % d` (which sample, which neighbour: BackgroundSubtractorSuBSENSE.cpp:508-551) as
     x - (mulhi(x, m[d]) >> (ceil(log2 d) - 1)) d with m from a 576-entry table (Granlund & Montgomery 1994, N = 31).  The table the
     DEVICE holds, against integer division: every d in 2..575, x over the edges of [0, 2^31) and 20 000 random draws each."""
     eng = Engine(capi.SUBSENSE)

@@ -39,28 +39,21 @@ struct SsDevice {
   uint8_t* u8[SS_NU8] = {nullptr};
   float *dsLT = nullptr, *dsST = nullptr;
   bgs::SsScalars* sc = nullptr;
-  bgs::SsScalars* scSnap = nullptr;  // the scalars as phase A found them (ss_feedback_kernel runs beside the frame-level block that rewrites sc)
-  uint32_t* ho = nullptr;            // [S][N][2] phase A -> ss_feedback_kernel hand-over (kernel_subsense.h)
   void* lastRec = nullptr;           // [S][N] 16-byte records: the full refresh's packed view of last colour / flag / descriptors (BGR)
   uint32_t* magic = nullptr;         // ss_mod's multipliers
   int* flood_flags = nullptr;  // [S][kSsFloodFlags], see ss_flood_kernel
   hipStream_t side = nullptr;  // phase B runs here, beside the post-processing chain (both only need phase A)
-  // One {evA, evB} pair per call in flight (a ring: calls for disjoint stream ranges may be in flight on several HIP streams), and the
-  // "phase A token": evTok[k] is recorded behind a call's phase A, and the next call's phase A - whatever HIP stream it is on - waits
-  // for it (ss_process).  part[]: the engine's own streams for the parts of one large batch (ss_process).
-  static constexpr int kRing = 8, kParts = 4;
-  hipEvent_t evA[kRing] = {nullptr}, evB[kRing] = {nullptr}, evTok[kRing] = {nullptr};
-  int ring = 0, tok = -1;        // next pair to use; the token of the last call (-1: none yet)
-  hipStream_t tokStream = nullptr;
-  hipStream_t part[kParts] = {nullptr};  // part 0 runs on the caller's stream
-  hipEvent_t evFork = nullptr, evPart[kParts] = {nullptr};
+  // One {evA, evB} pair per call in flight (a ring: calls for disjoint stream ranges may be in flight on several HIP streams)
+  static constexpr int kRing = 8;
+  hipEvent_t evA[kRing] = {nullptr}, evB[kRing] = {nullptr};
+  int ring = 0;  // next pair to use
   uint64_t *mbits = nullptr, *rbits = nullptr;  // flood fill: bit-packed mask / reached set, [S][rows][W64]
   uint64_t* bitws = nullptr;                     // SS_NBITS more bit planes of the same shape: the post-processing chain's intermediates
   std::vector<uint8_t> pp;   // per stream: which copy of Dlast / RawST is current
   int use3x3 = 1, lrScaling = 0, medK = 9;
   float capLo0 = 4.f, capHi0 = 512.f;
   void release() {
-    void* p[] = {samples, lut, lastColor, curColor, lastDesc, curDesc, req, dsLT, dsST, sc, scSnap, ho, lastRec, magic, flood_flags, mbits, rbits, bitws};
+    void* p[] = {samples, lut, lastColor, curColor, lastDesc, curDesc, req, dsLT, dsST, sc, lastRec, magic, flood_flags, mbits, rbits, bitws};
     for (void* q : p)
       if (q) (void)hipFree(q);
     for (auto& q : f32)
@@ -68,16 +61,11 @@ struct SsDevice {
     for (auto& q : u8)
       if (q) (void)hipFree(q), q = nullptr;
     if (side) (void)hipStreamSynchronize(side), (void)hipStreamDestroy(side), side = nullptr;
-    for (auto& q : part)
-      if (q) (void)hipStreamSynchronize(q), (void)hipStreamDestroy(q), q = nullptr;
     for (int i = 0; i < kRing; ++i)
-      for (hipEvent_t* q : {&evA[i], &evB[i], &evTok[i]})
+      for (hipEvent_t* q : {&evA[i], &evB[i]})
         if (*q) (void)hipEventDestroy(*q), *q = nullptr;
-    for (auto& q : evPart)
-      if (q) (void)hipEventDestroy(q), q = nullptr;
-    if (evFork) (void)hipEventDestroy(evFork), evFork = nullptr;
-    ring = 0, tok = -1, tokStream = nullptr;
-    samples = nullptr, lut = lastColor = curColor = nullptr, lastDesc = req = curDesc = nullptr, dsLT = dsST = nullptr, sc = nullptr, scSnap = nullptr, ho = nullptr, lastRec = nullptr, magic = nullptr, flood_flags = nullptr, mbits = rbits = nullptr, bitws = nullptr;
+    ring = 0;
+    samples = nullptr, lut = lastColor = curColor = nullptr, lastDesc = req = curDesc = nullptr, dsLT = dsST = nullptr, sc = nullptr, lastRec = nullptr, magic = nullptr, flood_flags = nullptr, mbits = rbits = nullptr, bitws = nullptr;
   }
 };
 
@@ -95,7 +83,7 @@ int ss_allocate(bgs_engine* e) {
     d->use3x3 = !(total > qvga * 2);
     int k = (int)std::floor((float)total / qvga + 0.5f) + 9;
     k = std::min(k, 14);
-    d->medK = (k % 2) ? k : k - 1;
+    d->medK = (k % 2) ? k : k - 1;  // k is 10..14 here: medK is 9, 11 or 13 (9 below QVGA); ss_process's bit-sliced median takes 3..13
     d->capLo0 = 2.f, d->capHi0 = 256.f;
   }
   const size_t N = e->n, P = N * e->S, nS = (size_t)p.subsense_n_samples, C = (size_t)e->ch;
@@ -107,8 +95,6 @@ int ss_allocate(bgs_engine* e) {
   DMALLOC(d->req, P * 2 * 2);
   DMALLOC(d->lut, (size_t)e->S * 256);
   DMALLOC(d->sc, (size_t)e->S * sizeof(bgs::SsScalars));
-  DMALLOC(d->scSnap, (size_t)e->S * sizeof(bgs::SsScalars));
-  DMALLOC(d->ho, P * 2 * sizeof(uint32_t));
   if (C == 3) DMALLOC(d->lastRec, P * 16);
   {
     uint32_t m[bgs::kSsMagicN];
@@ -135,7 +121,7 @@ void ss_fill_args(const bgs_engine* e, bgs::SsArgs& a, int first, int cur_pp, un
   const SsDevice* d = e->ss;
   const bgs_params& p = e->p;
   a.samples = d->samples, a.nSpad = d->nSpad, a.pixelMajor = d->pixelMajor, a.lastColor = d->lastColor, a.lastDesc = d->lastDesc, a.req = d->req, a.lut = d->lut, a.sc = d->sc;
-  a.scSnap = d->scSnap, a.ho = d->ho, a.magic = d->magic, a.lastRec = (uint4*)d->lastRec;
+  a.magic = d->magic, a.lastRec = (uint4*)d->lastRec;
   a.R = d->f32[SS_R], a.V = d->f32[SS_V], a.T = d->f32[SS_T];
   a.DlastOld = d->f32[cur_pp ? SS_DLAST1 : SS_DLAST0], a.DlastNew = d->f32[cur_pp ? SS_DLAST0 : SS_DLAST1];
   a.RawSTOld = d->f32[cur_pp ? SS_RAWST1 : SS_RAWST0], a.RawSTNew = d->f32[cur_pp ? SS_RAWST0 : SS_RAWST1];
@@ -146,11 +132,10 @@ void ss_fill_args(const bgs_engine* e, bgs::SsArgs& a, int first, int cur_pp, un
   a.rows = e->rows, a.cols = e->cols, a.nS = p.subsense_n_samples, a.nReq = p.subsense_n_required, a.nMinColor = p.subsense_min_color_dist_threshold;
   a.nDescOff = p.subsense_desc_dist_threshold_offset, a.nMov = p.subsense_samples_for_moving_avgs, a.lbspOff = p.lbsp_threshold_offset;
   a.use3x3 = d->use3x3, a.lrScaling = d->lrScaling, a.medK = d->medK, a.relT = p.lbsp_rel_threshold;
-  static const bool self_in_a = !(getenv("BGS_SS_SELF_IN_A") && atoi(getenv("BGS_SS_SELF_IN_A")) == 0);
-  a.selfInA = (e->algo == BGS_SUBSENSE && self_in_a) ? 1 : 0;  // (LOBSTER's phase A leaves every write to phase B)
+  a.selfInA = e->algo == BGS_SUBSENSE ? 1 : 0;  // (LOBSTER's phase A leaves every write to phase B)
   static const int refill = getenv("BGS_SS_REFILL") ? std::max(1, std::min(64, atoi(getenv("BGS_SS_REFILL")))) : bgs::kSsRefill;  // tuning knob
   a.refill = refill;
-  static const int ipass_min = getenv("BGS_SS_IPASS_MIN") ? std::max(1, std::min(64, atoi(getenv("BGS_SS_IPASS_MIN")))) : bgs::kSsIpassMin;  // 1 = the round-3 form
+  static const int ipass_min = getenv("BGS_SS_IPASS_MIN") ? std::max(1, std::min(64, atoi(getenv("BGS_SS_IPASS_MIN")))) : bgs::kSsIpassMin;  // tuning knob; 1 = every I pass at once
   a.ipassMin = ipass_min;
   a.frameIndex = frameIndex, a.first = first;
   const int64_t fi = frameIndex ? frameIndex : 1;
@@ -178,8 +163,7 @@ void ss_initial_lut(const bgs_params& p, int channels, uint8_t lut[256]) {
 // a wave per 64x64 tile otherwise (BGS_SS_FLOOD_TILES=1 forces the latter: A/B and test knob).
 void ss_launch_flood(dim3 tile_grid, int count, int tilesY, hipStream_t s, const uint64_t* mbits, uint64_t* rbits, int rows, int W64, int* fl, int k) {
   static const bool tiles_only = getenv("BGS_SS_FLOOD_TILES") && atoi(getenv("BGS_SS_FLOOD_TILES")) == 1;
-  static const bool wide_groups = getenv("BGS_SS_FLOOD_WG1024") && atoi(getenv("BGS_SS_FLOOD_WG1024")) == 1;  // A/B and test knob: round 3's 1024-lane workgroups for every height
-  if (tilesY <= bgs::kSsFloodNWSmall * bgs::kSsFloodKTSmall && !tiles_only && !wide_groups)
+  if (tilesY <= bgs::kSsFloodNWSmall * bgs::kSsFloodKTSmall && !tiles_only)
     hipLaunchKernelGGL((bgs::ss_flood_strip_kernel<bgs::kSsFloodNWSmall, bgs::kSsFloodKTSmall>), dim3(W64, count), dim3(bgs::kSsFloodNWSmall * 64), 0, s, mbits, rbits, rows, W64, fl, k);
   else if (tilesY <= 16 * bgs::kSsFloodKT && !tiles_only)
     hipLaunchKernelGGL((bgs::ss_flood_strip_kernel<16, bgs::kSsFloodKT>), dim3(W64, count), dim3(1024), 0, s, mbits, rbits, rows, W64, fl, k);
@@ -258,21 +242,19 @@ int ss_side_stream(SsDevice* d) {
   for (int i = 0; i < SsDevice::kRing; ++i) {
     HIP_TRY(hipEventCreateWithFlags(&d->evA[i], hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&d->evB[i], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&d->evTok[i], hipEventDisableTiming));
   }
   return BGS_OK;
 }
 
-// the smallest launch of phase A that takes part in the token / is a part of its own: 2^20 pixels (4 096 workgroups; BGS_SS_PART_MIN_PIXELS:
-// the tests set 1 so that small frames take the same paths)
-size_t ss_part_min_pixels() {
-  static const size_t v = getenv("BGS_SS_PART_MIN_PIXELS") ? (size_t)std::max(1ll, atoll(getenv("BGS_SS_PART_MIN_PIXELS"))) : (size_t)1 << 20;
-  return v;
-}
-
-// streams [first, first + count) on HIP stream s; ss_process (below) decides how a batch is cut into such calls
-int ss_process_range(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, hipStream_t s, int64_t t) {
+// One batch = SuBSENSEBGS::process for streams [first, first + count) on HIP stream s: phase A; phase B on the side stream, beside
+// blink + the post-processing chain (both only need phase A); the caller's stream waits for phase B; refresh; background.
+// What else was tried around this sequence and lost - the per-pixel rules as a kernel of their own in front of phase B, a per-wave
+// candidate list in phase A, phase A of successive calls taking turns through a token, a batch cut into parts on streams of the engine,
+// phase B started behind the flood fill, 1024-lane flood strips for every height - DESIGN.md 7d, profiles/r04_subsense_token_parts.txt,
+// profiles/r04_subsense_step_timeline.txt, profiles/r04_subsense_phase_a_pmc.txt.
+int ss_process(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, hipStream_t s) {
   SsDevice* d = e->ss;
+  const int64_t t = e->seen[first];
   const size_t N = e->n, off = N * first, npix = N * count;
   // (frames need no particular alignment: the tile loaders read dwords relative to each image's own base, which is unaligned anyway for
   // every second stream of a batch whose rows*cols*channels is odd - global dword loads may be unaligned on this hardware)
@@ -286,66 +268,20 @@ int ss_process_range(bgs_engine* e, int first, int count, const uint8_t* d_frame
   bgs::SsArgs a{};
   ss_fill_args(e, a, first, cur, (unsigned)(t + 1));
   a.frame = d_frames, a.fg = d_fg, a.bgimg = d_bg;
+  const dim3 tilesA((e->cols + bgs::kSsTW - 1) / bgs::kSsTW, (e->rows + bgs::kSsATH - 1) / bgs::kSsATH, count);
   const dim3 tilesB((e->cols + bgs::kSsTW - 1) / bgs::kSsTW, (e->rows + bgs::kSsBTH - 1) / bgs::kSsBTH, count), block(bgs::kBlock);
-  // BGS_SS_FEEDBACK_SPLIT=1: the rules behind the loop as ss_feedback_kernel in front of phase B instead of stage 3 of phase A
-  // (identical results; measured slower, kernel_subsense.h - kept as an A/B knob)
-  static const bool split = getenv("BGS_SS_FEEDBACK_SPLIT") && atoi(getenv("BGS_SS_FEEDBACK_SPLIT")) == 1;
-  static const bool overlap = !(getenv("BGS_SS_OVERLAP") && atoi(getenv("BGS_SS_OVERLAP")) == 0);
-  if (overlap) {
-    const int rc = ss_side_stream(d);
-    if (rc != BGS_OK) return rc;
-  }
-  const int slot = d->ring;  // this call's {evA, evB, evTok}
+  const int rc = ss_side_stream(d);
+  if (rc != BGS_OK) return rc;
+  const int slot = d->ring;  // this call's {evA, evB}
   d->ring = (d->ring + 1) % SsDevice::kRing;
-  // The phase A token (round 4; OFF by default - measured, no gain).  Phase A is bound by vector issue, everything behind it (phase
-  // B's scattered writes, the post-processing chain's many small launches) by DRAM and by latency: a step is A followed by a tail that
-  // leaves the vector units idle.  When the cameras are driven as several stream ranges on HIP streams of their own
-  // (bgs_process_range_device), one range's tail can run beside another range's phase A - but left to themselves the ranges stay
-  // aligned (round 2).  With the token, large launches of phase A take turns: each waits for the phase A of the call
-  // before it, on whatever HIP stream that was, so that A0 A1 A0' A1' ... run back to back and every tail beside the other range's
-  // phase A.  Measured on 8 x 1080p, fresh-noise frames (profiles/r04_subsense_token_parts.txt): two ranges on two streams WITHOUT the
-  // token 2.56 ms young / 1.50-1.57 aged (one batch call: 2.82 / 1.60-1.67), with it 2.67 / 1.55-1.62; four ranges are slower either
-  // way (3.1-3.3 / 2.0-2.2).  Phase A beside another range's tail runs 25 % longer (1.2 -> 1.5 ms per 8 frames: it is not as purely
-  // issue-bound as its counters suggest), and a tail of ~25 launches does not shrink with its range.  BGS_SS_A_TOKEN=1: on (A/B knob).
-  static const bool token_on = (getenv("BGS_SS_A_TOKEN") && atoi(getenv("BGS_SS_A_TOKEN")) == 1) || (getenv("BGS_SS_PARTS") && atoi(getenv("BGS_SS_PARTS")) > 1);  // (the parts of a batch rely on it)
-  const bool token = token_on && overlap && npix >= ss_part_min_pixels();
-  if (token && d->tok >= 0 && d->tokStream != s) HIP_TRY(hipStreamWaitEvent(s, d->evTok[d->tok], 0));
   {
     Timed tm(e, s, "ss_phase_a_kernel");
-    // BGS_SS_QUEUE=1: BGR frames through the per-wave candidate list (kernel_subsense.h "rounds"; identical results; measured slower: the
-    // candidates a wave holds per trip are too few to fill its lanes) - A/B knob
-    static const bool queue = getenv("BGS_SS_QUEUE") && atoi(getenv("BGS_SS_QUEUE")) == 1;
-    const int ath = (e->ch == 3 && queue && !split) ? bgs::kSsQATH : bgs::kSsATH;
-    const dim3 tilesA((e->cols + bgs::kSsTW - 1) / bgs::kSsTW, (e->rows + ath - 1) / ath, count);
-    if (e->ch == 3) {
-      if (split) hipLaunchKernelGGL((bgs::ss_phase_a_kernel<3, true, false>), tilesA, block, 0, s, a);
-      else if (queue) hipLaunchKernelGGL((bgs::ss_phase_a_kernel<3, false, true>), tilesA, block, 0, s, a);
-      else hipLaunchKernelGGL((bgs::ss_phase_a_kernel<3, false, false>), tilesA, block, 0, s, a);
-    } else {
-      if (split) hipLaunchKernelGGL((bgs::ss_phase_a_kernel<1, true, false>), tilesA, block, 0, s, a);
-      else hipLaunchKernelGGL((bgs::ss_phase_a_kernel<1, false, false>), tilesA, block, 0, s, a);
-    }
-  }
-  if (token) {
-    HIP_TRY(hipEventRecord(d->evTok[slot], s));
-    d->tok = slot, d->tokStream = s;
+    SS_LAUNCH(ss_phase_a_kernel, tilesA, block, s, a);
   }
   // Phase B (the scattered sample writes) and the post-processing chain both depend on phase A only, and the next frame depends
   // on both: phase B goes to a side stream and rejoins at the end, so its memory-bound scatter overlaps the LDS-bound morphology.
-  // (One side stream for every call: phase B launches then run in the order of their calls, which is the order the token gives
-  // their phase A launches anyway.)
-  // Round 4: the per-pixel rules behind the loop (:498-576) are ss_feedback_kernel; it produces the update requests phase B applies, so
-  // it goes in front of phase B on the side stream - both beside the post-processing chain, which only needs phase A's `raw`.
-  const dim3 gridF((e->cols + bgs::kBlock - 1) / bgs::kBlock, e->rows, count);
-  // WHERE phase B starts.  The timeline of an 8 x 1080p step on the aged model (round 4, profiles/r04_subsense_step_timeline.txt):
-  // phase B alone 368 us, the chain alone 288 us, both together 600 - 640 us - hardly better than one after the other.  Beside phase
-  // B's ~8 M scattered 16-byte writes (DRAM row activations) every launch of the chain takes four to five times as long
-  // and phase B itself 10 - 20 % longer.  Tried: the lowest stream priority for the side stream (no change); 256-lane instead of
-  // 1024-lane workgroups for the flood strips (kept; 250 -> 224 us beside phase B, 43 us alone either way); and phase B started
-  // BEHIND the flood fill, so that the chain's latency-bound first half runs alone (BGS_SS_B_LATE=1): the second half (median, box
-  // filters, byte maps) then takes the slowdown instead - median 21 -> 170 - 250 us - and the step is the same or 2 % longer.  The
-  // two share DRAM, not compute; the default stays phase B right behind phase A.
-  static const bool b_early = !(getenv("BGS_SS_B_LATE") && atoi(getenv("BGS_SS_B_LATE")) == 1);
+  // (One side stream for every call: phase B launches then run in the order of their calls.)  The two share DRAM, not compute: together
+  // they take hardly less than one after the other (profiles/r04_subsense_step_timeline.txt).
   // Phase B beside the chain is held to 4 workgroups per CU by unused dynamic LDS (round 4).  Its workgroups (17 KB of LDS, 4 waves) fit
   // eight to a CU = every wave slot of the CU, and each lives long (scattered 16-byte writes): the chain's small launches on the
   // caller's stream then wait for wave slots - 50-130 us each instead of 5 (profiles/r04_subsense_step_timeline.txt) - and the chain
@@ -355,32 +291,16 @@ int ss_process_range(bgs_engine* e, int first, int count, const uint8_t* d_frame
   // the register allocation (__attribute__((amdgpu_waves_per_eu(1, 4))): the kernel descriptor then claims 97 VGPRs, no LDS taken) measured
   // 1-2 % slower than the pad, not faster.  BGS_SS_B_LDS_PAD=bytes
   static const unsigned b_lds_pad = getenv("BGS_SS_B_LDS_PAD") ? (unsigned)std::max(0, std::min(140000, atoi(getenv("BGS_SS_B_LDS_PAD")))) : bgs::kSsBLdsPad;
-  auto launch_b = [&]() -> int {
-    if (overlap) {
-      HIP_TRY(hipEventRecord(d->evA[slot], s));
-      HIP_TRY(hipStreamWaitEvent(d->side, d->evA[slot], 0));
-      if (split) SS_LAUNCH(ss_feedback_kernel, gridF, block, d->side, a);
-      SS_LAUNCH_LDS(ss_phase_b_kernel, tilesB, block, b_lds_pad, d->side, a);
-      HIP_TRY(hipEventRecord(d->evB[slot], d->side));
-    } else {
-      if (split) SS_LAUNCH(ss_feedback_kernel, gridF, block, s, a);
-      SS_LAUNCH(ss_phase_b_kernel, tilesB, block, s, a);
-    }
-    return BGS_OK;
-  };
-  if (b_early || !overlap) {
-    const int rc = launch_b();
-    if (rc != BGS_OK) return rc;
-  }
+  HIP_TRY(hipEventRecord(d->evA[slot], s));
+  HIP_TRY(hipStreamWaitEvent(d->side, d->evA[slot], 0));
+  SS_LAUNCH_LDS(ss_phase_b_kernel, tilesB, block, b_lds_pad, d->side, a);
+  HIP_TRY(hipEventRecord(d->evB[slot], d->side));
   // byte maps of this launch as vectors when the pixel count and the caller's buffers allow it (the engine's own planes are 256-byte aligned)
   const bool v16 = npix % 16 == 0 && (off % 16) == 0, v4 = npix % 4 == 0 && (off % 4) == 0 && e->cols % 4 == 0 && (!d_fg || aligned(d_fg, 4));
-  auto launch_blink = [&]() {  // :624-627; only reads phase A's `raw`
-    if (v16)
-      hipLaunchKernelGGL(bgs::ss_blink_kernel<16>, dim3(blocks_for(npix / 16)), block, 0, s, a, npix);
-    else
-      hipLaunchKernelGGL(bgs::ss_blink_kernel<1>, dim3(blocks_for(npix)), block, 0, s, a, npix);
-  };
-  if (b_early || !overlap) launch_blink();
+  if (v16)  // :624-627; only reads phase A's `raw`
+    hipLaunchKernelGGL(bgs::ss_blink_kernel<16>, dim3(blocks_for(npix / 16)), block, 0, s, a, npix);
+  else
+    hipLaunchKernelGGL(bgs::ss_blink_kernel<1>, dim3(blocks_for(npix)), block, 0, s, a, npix);
   uint8_t* raw = d->u8[SS_RAW] + off;
   uint8_t* lastFG = d->u8[SS_LASTFG] + off;
   // :628-636 on bit planes (kernel_subsense.h): a lane owns 64 pixels of a row
@@ -408,32 +328,19 @@ int ss_process_range(bgs_engine* e, int first, int count, const uint8_t* d_frame
   int* fl = d->flood_flags + (size_t)first * bgs::kSsFloodFlags;
   HIP_TRY(hipMemsetAsync(fl, 0, (size_t)count * bgs::kSsFloodFlags * sizeof(int), s));
   static const int batch = getenv("BGS_SS_FLOOD_BATCH") ? std::max(0, std::min(bgs::kSsFloodBatch, atoi(getenv("BGS_SS_FLOOD_BATCH")))) : bgs::kSsFloodBatch;  // test knob: 0/1 force the finish kernel to do the work
-  // (the finish kernel almost always returns at once; 256 lanes so that it does not wait for a quarter of a CU beside phase B - see ss_flood_strip_kernel)
-  static const bool wide_finish = getenv("BGS_SS_FLOOD_WG1024") && atoi(getenv("BGS_SS_FLOOD_WG1024")) == 1;
   for (int k = 0; k < batch; ++k) ss_launch_flood(fgrid, count, tilesY, s, mbits, rbits, e->rows, W64, fl, k);
-  hipLaunchKernelGGL(bgs::ss_flood_finish_kernel, dim3(count), dim3(wide_finish ? 1024 : 256), 0, s, (const uint64_t*)mbits, rbits, e->rows, W64, fl, batch);
-  if (!(b_early || !overlap)) {
-    const int rc = launch_b();
-    if (rc != BGS_OK) return rc;
-    launch_blink();
-  }
+  // (the finish kernel almost always returns at once; 256 lanes so that it does not wait for a quarter of a CU beside phase B - see ss_flood_strip_kernel)
+  hipLaunchKernelGGL(bgs::ss_flood_finish_kernel, dim3(count), dim3(256), 0, s, (const uint64_t*)mbits, rbits, e->rows, W64, fl, batch);
   // erode x3 :632 = one 7x7 box -> b_tmp;  :631-634 -> b_cur
   hipLaunchKernelGGL((bgs::ss_bits_box_kernel<0, 3>), wgrid, block, 0, s, (const uint64_t*)b_pre, b_tmp, e->rows, e->cols, W64, nwords);
   hipLaunchKernelGGL(bgs::ss_bits_combine_kernel, wgrid, block, 0, s, (const uint64_t*)b_raw, (const uint64_t*)b_pre, (const uint64_t*)rbits, (const uint64_t*)b_tmp, b_cur, e->cols, W64, nwords);
-  // medianBlur :635 of the binary mask -> the byte map phase A reads (lastFG) and its bit plane (b_fg): bit-sliced on the planes
-  // (round 3); BGS_SS_MEDIAN_BITS=0: round 2's counts in LDS (morph_box_kernel) + a pack launch
-  static const bool median_bits = !(getenv("BGS_SS_MEDIAN_BITS") && atoi(getenv("BGS_SS_MEDIAN_BITS")) == 0);
-  if (median_bits && d->medK >= 3 && d->medK <= 13) {
-    switch (d->medK / 2) {
+  // medianBlur :635 of the binary mask -> the byte map phase A reads (lastFG) and its bit plane (b_fg): bit-sliced on the planes.
+  // medK is 9, 11 or 13 (ss_allocate), inside the radii 1..6 the kernel is built for
+  switch (d->medK / 2) {
 #define SS_MEDIAN_CASE(RV) \
   case RV: hipLaunchKernelGGL((bgs::ss_bits_median_kernel<RV>), wgrid, block, 0, s, (const uint64_t*)b_cur, b_fg, lastFG, e->rows, e->cols, W64, nwords); break;
-      SS_MEDIAN_CASE(1) SS_MEDIAN_CASE(2) SS_MEDIAN_CASE(3) SS_MEDIAN_CASE(4) SS_MEDIAN_CASE(5) SS_MEDIAN_CASE(6)
+    SS_MEDIAN_CASE(1) SS_MEDIAN_CASE(2) SS_MEDIAN_CASE(3) SS_MEDIAN_CASE(4) SS_MEDIAN_CASE(5) SS_MEDIAN_CASE(6)
 #undef SS_MEDIAN_CASE
-    }
-  } else {
-    bgs::MorphArgs m{nullptr, lastFG, e->rows, e->cols, 3, d->medK, b_cur, W64};
-    bgs::morph_launch(m, count, s);
-    pack(lastFG, b_fg);
   }
   hipLaunchKernelGGL((bgs::ss_bits_box_kernel<1, 3>), wgrid, block, 0, s, (const uint64_t*)b_fg, b_dil, e->rows, e->cols, W64, nwords);  // dilate x3 :636
   if (v4)  // :637-642
@@ -445,47 +352,11 @@ int ss_process_range(bgs_engine* e, int first, int count, const uint8_t* d_frame
     SS_LAUNCH(ss_downsample_kernel, dim3(blocks_for(dsn), 1, count), block, s, a);
   }
   hipLaunchKernelGGL(bgs::ss_frame_level_kernel, dim3(count), dim3(256), 0, s, a);
-  if (overlap) HIP_TRY(hipStreamWaitEvent(s, d->evB[slot], 0));  // the refresh below and the next frame need phase B's writes
+  HIP_TRY(hipStreamWaitEvent(s, d->evB[slot], 0));  // the refresh below and the next frame need phase B's writes
   ss_launch_refresh(e, a, N, count, 1, s);  // refreshModel(0.1f) if asked (:680)
   if (d_bg) SS_LAUNCH(ss_background_kernel, dim3(blocks_for(N * e->ch), 1, count), block, s, a);
   HIP_TRY(hipGetLastError());
   for (int i = first; i < first + count; ++i) d->pp[i] = (uint8_t)(cur ^ 1);
-  return BGS_OK;
-}
-
-// One batch = SuBSENSEBGS::process for streams [first, first + count).  BGS_SS_PARTS=n (default 1: off - measured slower) cuts a large
-// batch into up to SsDevice::kParts parts, part 0 on the caller's stream, the others on streams of the engine, each an
-// ss_process_range call of its own with the phase A token, so that each part's tail (phase B, post-processing) runs beside the next
-// part's phase A and only the last part's tail is left standing alone; the caller's stream continues behind all of it.  8 x 1080p:
-// 2 parts 3.01 ms young / 2.24 aged, 4 parts 3.99 / 2.30 against 2.82 / 1.60-1.67 as one launch (profiles/r04_subsense_token_parts.txt;
-// same reasons as the token's).  Same kernels on the same per-stream state: results do not depend on the cut (tests: 1, 2, 4 parts in
-// child processes).
-int ss_process(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, hipStream_t s) {
-  SsDevice* d = e->ss;
-  const int64_t t = e->seen[first];
-  static const int parts_env = getenv("BGS_SS_PARTS") ? std::max(1, std::min((int)SsDevice::kParts, atoi(getenv("BGS_SS_PARTS")))) : bgs::kSsParts;
-  static const bool overlap = !(getenv("BGS_SS_OVERLAP") && atoi(getenv("BGS_SS_OVERLAP")) == 0);
-  const size_t N = e->n, C = (size_t)e->ch;
-  const int P = std::min<int>({parts_env, count, (int)std::min<size_t>(N * (size_t)count / ss_part_min_pixels(), (size_t)SsDevice::kParts)});  // a part is a launch that fills the device
-  if (t == 0 || !overlap || P < 2) return ss_process_range(e, first, count, d_frames, d_fg, d_bg, s, t);  // (the first frame's full refresh is one launch)
-  if (!d->evFork) {
-    HIP_TRY(hipEventCreateWithFlags(&d->evFork, hipEventDisableTiming));
-    for (int p = 1; p < SsDevice::kParts; ++p) {
-      HIP_TRY(hipStreamCreateWithFlags(&d->part[p], hipStreamNonBlocking));
-      HIP_TRY(hipEventCreateWithFlags(&d->evPart[p], hipEventDisableTiming));
-    }
-  }
-  HIP_TRY(hipEventRecord(d->evFork, s));  // the frames are ready, and every earlier call has been joined into s
-  for (int p = 0; p < P; ++p) {
-    const int f = first + (int)((int64_t)count * p / P), n = first + (int)((int64_t)count * (p + 1) / P) - f;
-    const size_t o = (size_t)(f - first) * N;
-    hipStream_t ps = p == 0 ? s : d->part[p];
-    if (p) HIP_TRY(hipStreamWaitEvent(ps, d->evFork, 0));
-    const int rc = ss_process_range(e, f, n, d_frames + o * C, d_fg ? d_fg + o : nullptr, d_bg ? d_bg + o * C : nullptr, ps, t);
-    if (rc != BGS_OK) return rc;
-    if (p) HIP_TRY(hipEventRecord(d->evPart[p], ps));
-  }
-  for (int p = 1; p < P; ++p) HIP_TRY(hipStreamWaitEvent(s, d->evPart[p], 0));
   return BGS_OK;
 }
 
@@ -643,18 +514,11 @@ int lob_process(bgs_engine* e, int first, int count, const uint8_t* d_frames, ui
   lob_fill_args(e, a, first, (unsigned)(t + 1));
   a.frame = d_frames, a.fg = d_fg, a.bgimg = d_bg;
   a.lastColor = d->curColor, a.lastDesc = d->curDesc;  // phase A writes / phase B reads what a requesting pixel copies into the model
-  const dim3 tiles((e->cols + bgs::kSsTW - 1) / bgs::kSsTW, (e->rows + bgs::kSsTH - 1) / bgs::kSsTH, count);
   const dim3 tilesB((e->cols + bgs::kSsTW - 1) / bgs::kSsTW, (e->rows + bgs::kSsBTH - 1) / bgs::kSsBTH, count);
   {
-    // round 4: lanes fed from a queue (kernel_subsense.h); BGS_LOB_QUEUE=0: one pixel per lane in lock step (rounds 1-3; A/B and test knob)
-    static const bool queue = !(getenv("BGS_LOB_QUEUE") && atoi(getenv("BGS_LOB_QUEUE")) == 0);
-    Timed tm(e, s, "lob_phase_a_kernel");
-    if (queue) {
-      const dim3 tilesQ((e->cols + bgs::kSsTW - 1) / bgs::kSsTW, (e->rows + bgs::kLobATH - 1) / bgs::kLobATH, count);
-      SS_LAUNCH(lob_phase_a_queue_kernel, tilesQ, block, s, a);
-    } else {
-      SS_LAUNCH(lob_phase_a_kernel, tiles, block, s, a);
-    }
+    Timed tm(e, s, "lob_phase_a_kernel");  // (the label tools key on; the kernel is the queue form, kernel_subsense.h)
+    const dim3 tilesQ((e->cols + bgs::kSsTW - 1) / bgs::kSsTW, (e->rows + bgs::kLobATH - 1) / bgs::kLobATH, count);
+    SS_LAUNCH(lob_phase_a_queue_kernel, tilesQ, block, s, a);
   }
   // (Phase B beside the median on the side stream, as in SuBSENSE's step, was tried at the end of round 4: LOBSTER's tail is only 0.15-0.2
   // ms and the two event hops cost more than the overlap gives - 8 x 1080p 2.39 against 2.34 ms on S_surv, 0.64 against 0.59 on smooth input.)
@@ -668,16 +532,6 @@ int lob_process(bgs_engine* e, int first, int count, const uint8_t* d_frames, ui
 }
 
 void ss_free(bgs_engine* e) {
-#ifdef BGS_SS_STATS
-  {
-    unsigned long long h[16] = {0};
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(bgs::g_ss_stats), sizeof h) == hipSuccess)
-      fprintf(stderr, "ss_stats trips %llu active_lanes %llu refills %llu | R narrow %llu lanes %llu wide %llu lanes %llu | passes %llu lanes %llu | put off %llu lanes %llu\n", h[0], h[1], h[2], h[3], h[4], h[5],
-              h[6], h[7], h[8], h[9], h[10]);
-    unsigned long long z[16] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(bgs::g_ss_stats), z, sizeof z);
-  }
-#endif
   if (e->ss) {
     e->ss->release();
     delete e->ss;

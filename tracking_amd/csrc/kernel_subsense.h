@@ -27,14 +27,17 @@
 // miss capacity as the limit, hence batches (2.40) -> rejection tests per batch, inter-LBSP per candidate pass (2.17) -> eight
 // samples per trip (1.99): VALU-bound.
 // Ten f32 maps [N] (+2 second copies), byte maps [N].  The current frame's 5x5 neighbourhood is staged through LDS once per
-// workgroup (phase A: 64x32 pixel tile + halo 2, with an LDS work queue over its pixels; phase B: 64x16 targets; LOBSTER's phase A: 64x4).
-//   lob_phase_a_kernel   LOBSTER's operator()                     BackgroundSubtractorLOBSTER.cpp:172-284 (shares phase B, refresh, background)
+// workgroup (phase A: 64x32 pixel tile + halo 2, with an LDS work queue over its pixels; phase B: 64x16 targets; LOBSTER's phase A: 64x16,
+// same queue).
+//   lob_phase_a_queue_kernel   LOBSTER's operator()               BackgroundSubtractorLOBSTER.cpp:172-284 (shares phase B, refresh, background)
+// Forms that were measured and lost (the rules behind the loop as a kernel of their own, a per-wave candidate list in phase A, LOBSTER with
+// one pixel per lane) are gone from the code; what they measured is in DESIGN.md 7d and under profiles/.
 #pragma once
 #include "bgs_device.h"
 
 namespace bgs {
 
-constexpr int kSsTW = 64, kSsTH = 4;  // one lane per pixel
+constexpr int kSsTW = 64;  // tile width of every tiled kernel here: one wave per tile row
 
 // per-stream scalars that the frame-level block updates ON THE DEVICE
 struct SsScalars {
@@ -62,10 +65,8 @@ struct SsArgs {
   float relT, fLT, fST;
   unsigned frameIndex;
   int first;             // first stream of this launch (blockIdx.z is relative to it)
-  int selfInA;           // 1: a pixel's SELF update is stored before phase B (SuBSENSE: by ss_feedback_kernel; round 3: by phase A itself); phase B then only applies the diffusion
+  int selfInA;           // 1: a pixel's SELF update is stored by phase A itself (SuBSENSE), phase B then only applies the diffusion; 0: phase B applies both (LOBSTER)
   uint4* lastRec;        // [S][N] scratch of the full refresh (BGR): a pixel's last colour, foreground flag and descriptors as ONE 16-byte record
-  uint32_t* ho;          // [S][N][2] hand-over from phase A to ss_feedback_kernel (round 4), see there
-  SsScalars* scSnap;     // [S] the per-stream scalars as they stood when phase A ran (the frame-level block rewrites `sc` beside ss_feedback_kernel)
   const uint32_t* magic; // [1024] multipliers of ss_mod
 };
 
@@ -180,24 +181,11 @@ __device__ __forceinline__ size_t ss_rec(const SsArgs& a, int stream, size_t N, 
 // The result of a pixel does not depend on when or where it is processed: every model read is of start-of-frame state.
 constexpr int kSsATH = 32, kSsAPix = kSsTW * kSsATH, kSsRefill = 16, kSsIpassMin = 16;
 constexpr unsigned kSsBLdsPad = 22000;  // unused dynamic LDS of phase B beside the chain: 4 instead of 8 of its workgroups per CU (engine_subsense.h; BGS_SS_B_LDS_PAD)
-constexpr int kSsParts = 1;  // parts a large batch is cut into (engine_subsense.h: ss_process); BGS_SS_PARTS
 constexpr uint32_t kSsNotInterior = 0xffffffffu;
 
-
-// SPLIT: the per-pixel rules behind the loop (:498-576) run in ss_feedback_kernel instead of stage 3 (see there for what was measured)
-// QUEUE (BGR only): the inter-LBSP tests of a wave go through a per-wave work list in LDS and are computed by WHOEVER is free, 64 at a
-// time (stage 2, "rounds"); the tile is 64 x 16 then (kSsQATH) so that the extra LDS still allows four workgroups per CU.
-constexpr int kSsQATH = 16, kSsQList = 256;
-#ifdef BGS_SS_STATS  // experiment builds only (tools/r04_ss_stats.sh): what the waves of stage 2 did, summed over the process
-__device__ unsigned long long g_ss_stats[16];
-#define SS_STAT(i, v) (st[i] += (unsigned)(v))
-#else
-#define SS_STAT(i, v) ((void)0)
-#endif
-template <int C, bool SPLIT, bool QUEUE>
+template <int C>
 __global__ __launch_bounds__(kBlock) void ss_phase_a_kernel(const SsArgs a) {
-  static_assert(!QUEUE || C == 3, "the candidate queue is built for BGR records");
-  constexpr int ATH = QUEUE ? kSsQATH : kSsATH, APIX = kSsTW * ATH;
+  constexpr int ATH = kSsATH, APIX = kSsAPix;
   constexpr int HW = kSsTW + 4, HH = ATH + 4;
   constexpr int ROWB = (HW * C + 3 + 3) / 4 * 4;
   constexpr uint32_t maxColor = 255 * C, maxDesc = 16 * C;  // s_nColorMaxDataRange_*, s_nDescMaxDataRange_*
@@ -208,14 +196,6 @@ __global__ __launch_bounds__(kBlock) void ss_phase_a_kernel(const SsArgs a) {
   // good | minDesc << 8 | minSum << 16 (3-dword stride: conflict-free for consecutive pixels)
   __shared__ uint32_t ctx[APIX][3];
   __shared__ unsigned nz_block, qhead;
-  // QUEUE: what a worker lane needs of the lane that owns a candidate - its pixel's 48 LBSP neighbours as bytes (12 dwords: channel c
-  // in words 4c .. 4c+3, neighbour k in byte k), its current colour, where its held samples start and whether they are the pixel-major
-  // part - plus, per wave, the work list (lane << 3 | sample) and, per lane, the eight 16-bit results
-  __shared__ uint32_t nbs[QUEUE ? kBlock : 1][12];
-  __shared__ uint32_t hcur[QUEUE ? kBlock : 1], hrec[QUEUE ? kBlock : 1];
-  __shared__ uint16_t hq[QUEUE ? kBlock : 2];
-  __shared__ uint16_t qlist[QUEUE ? (kBlock / kWave) * kSsQList : 2];
-  __shared__ __attribute__((aligned(16))) uint16_t qres[QUEUE ? kBlock * 8 : 8];
   const int stream = a.first + blockIdx.z;
   const size_t N = (size_t)a.rows * a.cols, sN = (size_t)stream * N;
   const uint8_t* img = a.frame + (size_t)blockIdx.z * N * C;
@@ -249,124 +229,42 @@ __global__ __launch_bounds__(kBlock) void ss_phase_a_kernel(const SsArgs a) {
     }
   };
   auto interior_of = [&](int x, int y) { return x >= 2 && x < a.cols - 2 && y >= 2 && y < a.rows - 2; };  // LBSP::validateROI; border pixels are never touched
-
-  __shared__ uint32_t magic[SPLIT ? 1 : kSsMagicN];  // ss_mod's multipliers (stage 3)
-  if constexpr (!SPLIT) {
-    for (int k = threadIdx.x; k < kSsMagicN; k += kBlock) magic[k] = a.magic[k];
-  }
+  __shared__ uint32_t magic[kSsMagicN];  // ss_mod's multipliers (stage 3)
+  for (int k = threadIdx.x; k < kSsMagicN; k += kBlock) magic[k] = a.magic[k];
   unsigned nzcount = 0;
-  if constexpr (SPLIT) {
-    // ---- stage 1: thresholds and intra descriptors; and everything of :498-582 that needs the frame or the pixel's last colour /
-    // descriptor - the distance to the last frame (:498), the new instability flag (:467), the non-zero-descriptor count (:577-578), the
-    // last colour / descriptor themselves (:579-582) - so that the rest of the per-pixel rules can run in a kernel of its own
-    // (ss_feedback_kernel) that needs neither the LDS tile nor this kernel's registers.  Pixels go through in half-batches: the loads of
-    // four pixels are issued before the first of them is worked on.
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) a.scSnap[stream] = a.sc[stream];
-    {
-      constexpr int HB = PPL / 2;
-  #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        float Rs[HB], rawLT[HB], rawST[HB], finLT[HB], finST[HB];
-        uint32_t us[HB], lfg[HB], blk[HB], lcw[HB];
-        uint2 ldw[HB];
-  #pragma unroll
-        for (int r = 0; r < HB; ++r) {  // all loads first
-          const int q = (h * HB + r) * kBlock + threadIdx.x, x = x0 + (q % kSsTW), y = y0 + (q / kSsTW);
-          const bool in = interior_of(x, y);
-          const size_t i = in ? sN + (size_t)y * a.cols + x : sN;
-          Rs[r] = a.R[i], us[r] = a.unstable[i];
-          rawLT[r] = a.RawLT[i], rawST[r] = a.RawSTOld[i], finLT[r] = a.FinLT[i], finST[r] = a.FinST[i], lfg[r] = a.lastFG[i], blk[r] = a.blinks[i];
-          if constexpr (C == 3) {  // 3 bytes / 3 words with one 4- / 8-byte load (both arrays are padded by 8 bytes)
-            lcw[r] = *reinterpret_cast<const uint32_t*>(a.lastColor + i * 3);
-            ldw[r] = *reinterpret_cast<const uint2*>(a.lastDesc + i * 3);
-          } else {
-            lcw[r] = a.lastColor[i], ldw[r] = make_uint2(a.lastDesc[i], 0u);
-          }
-        }
-  #pragma unroll
-        for (int r = 0; r < HB; ++r) {
-          const int q = (h * HB + r) * kBlock + threadIdx.x, lx = q % kSsTW, ly = q / kSsTW;
-          if (!interior_of(x0 + lx, y0 + ly)) {
-            ctx[q][2] = kSsNotInterior;
-            continue;
-          }
-          const float Rv = Rs[r];
-          const int unst_old = (int)us[r];
-          const int stabOff = a.nMinColor / 5;
-          const uint32_t colorThr = (uint32_t)((Rv * (float)a.nMinColor) - (float)((!unst_old) * stabOff)) / (C == 1 ? 2 : 1);                  // :459 / :328 (trailing /2)
-          const uint32_t descThr = (1u << ((uint32_t)floorf(Rv + 0.5f))) + (uint32_t)a.nDescOff + (uint32_t)(unst_old * a.nDescOff);        // :460
-          int cur[C];
-          uint32_t nb[C][8];
-          gather(ly, lx, cur, nb);
-          unsigned intra[3] = {0, 0, 0};
-  #pragma unroll
-          for (int c = 0; c < C; ++c) intra[c] = ss_lbsp(nb[c], cur[c], lut[cur[c]]);  // :465-466 / :331
-          // the thresholds are only ever compared with distances <= 765: clamping them to 16 bits changes no comparison
-          ctx[q][0] = intra[0] | (intra[1] << 16);
-          ctx[q][1] = intra[2] | (min(colorThr, 0xffffu) << 16);
-          ctx[q][2] = min(descThr, 0xffffu);
-          {
-            const size_t i = sN + (size_t)(y0 + ly) * a.cols + (x0 + lx);
-            uint32_t l1 = 0, hd = 0;  // :498
-            if constexpr (C == 3) {
-              const uint32_t cw = (uint32_t)cur[0] | ((uint32_t)cur[1] << 8) | ((uint32_t)cur[2] << 16);
-              l1 = __builtin_amdgcn_sad_u8(cw, lcw[r] & 0xffffffu, 0u);
-              hd = (uint32_t)__popc((ldw[r].x ^ (intra[0] | (intra[1] << 16)))) + (uint32_t)__popc((ldw[r].y ^ intra[2]) & 0xffffu);
-            } else {
-              l1 = (uint32_t)abs((int)lcw[r] - cur[0]);
-              hd = (uint32_t)__popc((ldw[r].x ^ intra[0]) & 0xffffu);
-            }
-            const uint32_t unst = (Rv > 3.0f || (rawLT[r] - finLT[r]) > 0.1f || (rawST[r] - finST[r]) > 0.1f) ? 1u : 0u;  // :467
-            a.unstable[i] = (uint8_t)unst;
-            a.ho[i * 2 + 1] = l1 | (hd << 10) | (unst << 16) | ((uint32_t)(lfg[r] != 0) << 17) | ((uint32_t)(blk[r] != 0) << 18);
-            if constexpr (C == 3)
-              nzcount += (__popc(intra[0]) + __popc(intra[1]) + __popc(intra[2])) >= 4;  // :577-578
-            else
-              nzcount += __popc(intra[0]) >= 2;  // :430-431
-  #pragma unroll
-            for (int c = 0; c < C; ++c) {  // :579-582
-              a.lastDesc[i * C + c] = (uint16_t)intra[c];
-              a.lastColor[i * C + c] = (uint8_t)cur[c];
-            }
-          }
-        }
-      }
+  // ---- stage 1: thresholds and intra descriptors
+  {
+    float Rs[PPL];
+    int us[PPL];
+#pragma unroll
+    for (int r = 0; r < PPL; ++r) {  // all loads first
+      const int q = r * kBlock + threadIdx.x, x = x0 + (q % kSsTW), y = y0 + (q / kSsTW);
+      const bool in = interior_of(x, y);
+      const size_t i = sN + (size_t)y * a.cols + x;
+      Rs[r] = in ? a.R[i] : 1.0f, us[r] = in ? a.unstable[i] : 0;
     }
-  } else {
-    // ---- stage 1: thresholds and intra descriptors
-    {
-      float Rs[PPL];
-      int us[PPL];
-  #pragma unroll
-      for (int r = 0; r < PPL; ++r) {  // all loads first
-        const int q = r * kBlock + threadIdx.x, x = x0 + (q % kSsTW), y = y0 + (q / kSsTW);
-        const bool in = interior_of(x, y);
-        const size_t i = sN + (size_t)y * a.cols + x;
-        Rs[r] = in ? a.R[i] : 1.0f, us[r] = in ? a.unstable[i] : 0;
+#pragma unroll
+    for (int r = 0; r < PPL; ++r) {
+      const int q = r * kBlock + threadIdx.x, lx = q % kSsTW, ly = q / kSsTW;
+      if (!interior_of(x0 + lx, y0 + ly)) {
+        ctx[q][2] = kSsNotInterior;
+        continue;
       }
-  #pragma unroll
-      for (int r = 0; r < PPL; ++r) {
-        const int q = r * kBlock + threadIdx.x, lx = q % kSsTW, ly = q / kSsTW;
-        if (!interior_of(x0 + lx, y0 + ly)) {
-          ctx[q][2] = kSsNotInterior;
-          continue;
-        }
-        const float Rv = Rs[r];
-        const int unst_old = us[r];
-        const int stabOff = a.nMinColor / 5;
-        const uint32_t colorThr = (uint32_t)((Rv * (float)a.nMinColor) - (float)((!unst_old) * stabOff)) / (C == 1 ? 2 : 1);                  // :459 / :328 (trailing /2)
-        const uint32_t descThr = (1u << ((uint32_t)floorf(Rv + 0.5f))) + (uint32_t)a.nDescOff + (uint32_t)(unst_old * a.nDescOff);        // :460
-        int cur[C];
-        uint32_t nb[C][8];
-        gather(ly, lx, cur, nb);
-        unsigned intra[3] = {0, 0, 0};
-  #pragma unroll
-        for (int c = 0; c < C; ++c) intra[c] = ss_lbsp(nb[c], cur[c], lut[cur[c]]);  // :465-466 / :331
-        // the thresholds are only ever compared with distances <= 765: clamping them to 16 bits changes no comparison
-        ctx[q][0] = intra[0] | (intra[1] << 16);
-        ctx[q][1] = intra[2] | (min(colorThr, 0xffffu) << 16);
-        ctx[q][2] = min(descThr, 0xffffu);
-      }
+      const float Rv = Rs[r];
+      const int unst_old = us[r];
+      const int stabOff = a.nMinColor / 5;
+      const uint32_t colorThr = (uint32_t)((Rv * (float)a.nMinColor) - (float)((!unst_old) * stabOff)) / (C == 1 ? 2 : 1);                  // :459 / :328 (trailing /2)
+      const uint32_t descThr = (1u << ((uint32_t)floorf(Rv + 0.5f))) + (uint32_t)a.nDescOff + (uint32_t)(unst_old * a.nDescOff);        // :460
+      int cur[C];
+      uint32_t nb[C][8];
+      gather(ly, lx, cur, nb);
+      unsigned intra[3] = {0, 0, 0};
+#pragma unroll
+      for (int c = 0; c < C; ++c) intra[c] = ss_lbsp(nb[c], cur[c], lut[cur[c]]);  // :465-466 / :331
+      // the thresholds are only ever compared with distances <= 765: clamping them to 16 bits changes no comparison
+      ctx[q][0] = intra[0] | (intra[1] << 16);
+      ctx[q][1] = intra[2] | (min(colorThr, 0xffffu) << 16);
+      ctx[q][2] = min(descThr, 0xffffu);
     }
   }
   __syncthreads();
@@ -398,16 +296,11 @@ __global__ __launch_bounds__(kBlock) void ss_phase_a_kernel(const SsArgs a) {
     for (int j = 0; j < B; ++j) bt[j] = SsSample<C>{}, nbt[j] = SsSample<C>{};
 #pragma unroll
     for (int c = 0; c < C; ++c) cur[c] = 0, intra[c] = 0, curm[c] = 0;
-#ifdef BGS_SS_STATS
-    unsigned st[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
     for (;;) {
       const unsigned long long idle = __ballot(!active);
       const int nidle = __popcll(idle);
       if (qempty && nidle == kWave) break;
-      SS_STAT(0, 1), SS_STAT(1, kWave - nidle);  // trips, active lanes
       if (!qempty && nidle >= a.refill) {  // wave-uniform
-        SS_STAT(2, 1);
         const int leader = __ffsll((long long)idle) - 1;
         unsigned base = 0;
         if (lane == leader) base = atomicAdd(&qhead, (unsigned)nidle);
@@ -426,20 +319,6 @@ __global__ __launch_bounds__(kBlock) void ss_phase_a_kernel(const SsArgs a) {
             gather(ly, lx, cur, nb);
 #pragma unroll
             for (int c = 0; c < C; ++c) curm[c] = (uint32_t)cur[c] << (8 * c);
-            if constexpr (QUEUE) {  // the neighbours as bytes for whoever computes this pixel's inter-LBSP tests
-#pragma unroll
-              for (int c = 0; c < 3; ++c) {
-                uint32_t w[4];
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {  // words 0, 1: neighbours 0-3, 4-7 (the high halves of nb[4i .. 4i+3]); words 2, 3: neighbours 8-15 (the low halves)
-                  const uint32_t h01 = __builtin_amdgcn_perm(nb[c][4 * i + 1], nb[c][4 * i], 0x0c0c0602u), h23 = __builtin_amdgcn_perm(nb[c][4 * i + 3], nb[c][4 * i + 2], 0x0c0c0602u);
-                  const uint32_t l01 = __builtin_amdgcn_perm(nb[c][4 * i + 1], nb[c][4 * i], 0x0c0c0400u), l23 = __builtin_amdgcn_perm(nb[c][4 * i + 3], nb[c][4 * i + 2], 0x0c0c0400u);
-                  w[i] = h01 | (h23 << 16), w[2 + i] = l01 | (l23 << 16);
-                }
-                *reinterpret_cast<uint4*>(&nbs[threadIdx.x][4 * c]) = make_uint4(w[0], w[1], w[2], w[3]);
-              }
-              hcur[threadIdx.x] = curm[0] | curm[1] | curm[2];
-            }
             const size_t p = (size_t)(y0 + ly) * a.cols + (x0 + lx);
             rec = ss_rec(a, stream, N, p, 0), rnext = ss_rec(a, stream, N, p, B);
 #pragma unroll
@@ -456,11 +335,6 @@ __global__ __launch_bounds__(kBlock) void ss_phase_a_kernel(const SsArgs a) {
       // behind the nReq-th match have no side effects, and min() does not care about order.
       // (round 4) A lane whose candidates were left over by the I passes below keeps its batch and its candidate bits (`fresh` false):
       // it neither loads nor re-tests anything until a pass has taken them.
-      {
-        const unsigned long long fm = __ballot(active && fresh), wm = __ballot(active && fresh && idx > 0);
-        SS_STAT(3, fm != 0), SS_STAT(4, __popcll(fm)), SS_STAT(5, wm != 0), SS_STAT(6, __popcll(wm));
-        (void)fm, (void)wm;
-      }
       if (active && fresh) {  // :469-497 (BGR) / :334-357 (gray); an active lane always has good < nReq and idx < nS here
         wide = idx > 0;
         auto reject_bits = [&](const SsSample<C>(&bb)[B], int first) -> uint32_t {
@@ -499,179 +373,73 @@ __global__ __launch_bounds__(kBlock) void ss_phase_a_kernel(const SsArgs a) {
         }
         fresh = false;
       }
-      if constexpr (QUEUE) {
-        // ROUNDS (round 4, BGS_SS_QUEUE=1; NOT the default: measured slower).  One candidate per lane and pass leaves the wave at
-        // ~25 % lane use on a young model (profiles/r04_subsense_phase_a_pmc.txt: 2.65 M passes of ~230 vector instructions per
-        // 8 x 1080p launch for 43 M candidates, half of the kernel's vector instructions).  Here every lane that has candidates puts some
-        // on its wave's list and ALL 64 lanes work the list off, 64 entries at a time, each lane computing whichever candidate falls to
-        // it from what its owner left in LDS (neighbours, colour, thresholds) and the sample re-read from memory (a cache hit: the
-        // owner's load).  A pixel past its first batch enqueues up to four candidates at once - speculation: a candidate behind the
-        // nReq-th match is computed in vain, but such pixels rarely match at all - a pixel on its first batch only as many as it still
-        // needs (at most two).  Results come back as 16 bits per candidate; the owner applies them in sample order and stops at its
-        // nReq-th match, exactly the reference's early exit.  Same integers as the direct form below (parity-tested).
-        // What the counters said: the vector instruction count did not move (1 184 M -> 1 181 M per launch) and 3.9 M list passes ran
-        // where 2.65 M direct ones had - a wave holds only ~20 candidates per trip (a third of its lanes are between pixels or have
-        // none), so a list pass is still two thirds empty and pays ~60 instructions of LDS traffic on top; LDS bank conflicts x 5.
-        // Young 8 x 1080p phase A 2.04 -> 2.42 ms, aged 1.06 -> 1.49 ms.  Filling the lanes needs candidates from SEVERAL trips of a
-        // lane in flight at once, i.e. speculating across sample batches - not built.
-        const int wbase = (int)(threadIdx.x & ~(kWave - 1));
-        uint16_t* wl = qlist + (threadIdx.x / kWave) * kSsQList;
-        const size_t recBase = (size_t)stream * N * (size_t)a.nSpad;
-        const unsigned long long lt = (1ull << lane) - 1ull;
-        if (active) hrec[threadIdx.x] = (uint32_t)(rec - recBase), hq[threadIdx.x] = (uint16_t)((unsigned)q | (wide ? 0x8000u : 0u));
-        for (;;) {
-          const bool want = active && cand != 0 && good < a.nReq;
-          if (!__any(want)) break;
-          uint32_t enq = 0;
-          if (want) {
-            const int quota = wide ? 4 : min(a.nReq - good, 2);
-            uint32_t x = cand;
+      // I passes: one candidate per lane and pass.  (Round 4 tried to fill the idle lanes of a sparse pass by splitting each candidate
+      // over three lanes, one channel each, the helpers reading the owner's neighbours from the frame tile: parity-green, but a
+      // sub-pass of 21 candidates cost ~150 vector + 25 LDS instructions against ~230 for a whole pass, and 40 % of the passes hold 22-42
+      // candidates, i.e. need two: -4 % vector instructions, +90 M bank-conflict cycles, no time gained - profiles/r04_subsense_phase_a_pmc.txt.)
+      for (;;) {
+        const bool go = active && cand != 0 && good < a.nReq;
+        const unsigned long long gm = __ballot(go);
+        if (!gm) break;
+        // DENSE PASSES (round 4): a pass costs the same ~230 vector instructions for one candidate as for 64, and once the lanes
+        // with two or three candidates in their batch are the only ones left it ran at a few lanes.  So a pass that fewer than
+        // ipassMin lanes would join is put off while some other active lane has something else to do (its next batch, or finishing
+        // and handing its lane to a new pixel): the waiting lanes keep batch and candidate bits and join the passes of the next trip.
+        // Every trip still makes progress - either a pass runs, or a lane without candidates moves on - and each pixel still sees
+        // its samples in order up to its nReq-th match: the same integers for any ipassMin (1 = every pass at once, the round-3 form).
+        // Not once the tile's queue is empty: no new pixel can join then, a trip is a memory round trip, and waiting only strings
+        // more of them together (measured: the aged model, whose pixels mostly take one trip, lost 13 % without this condition).
+        if (!qempty && __popcll(gm) < a.ipassMin && __any(active && !go)) break;
+        SsSample<C> smp = bt[0];
+        if (go) {
+          const int j = __ffs((int)cand) - 1;
+          cand &= cand - 1;
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-              if (k < quota && x) enq |= x & (0u - x), x &= x - 1u;
-            cand &= ~enq;
-          }
-          unsigned n_list = 0;  // wave-uniform: at most 4 x 64 = kSsQList entries
+          for (int jj = 1; jj < B; ++jj)
+            if (j == jj) smp = bt[jj];
 #pragma unroll
-          for (int b = 0; b < 2 * B; ++b) {
-            const bool has = (enq >> b) & 1u;
-            const unsigned long long mb = __ballot(has);
-            if (has) wl[n_list + (unsigned)__popcll(mb & lt)] = (uint16_t)((lane << 3) | b);
-            n_list += (unsigned)__popcll(mb);
-          }
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-          for (unsigned base = 0; base < n_list; base += kWave) {
-            const bool valid = base + (unsigned)lane < n_list;
-            const unsigned ent = valid ? (unsigned)wl[base + lane] : ((unsigned)lane << 3);
-            const int ot = wbase + (int)(ent >> 3), j = (int)(ent & 7u);
-            const unsigned oqw = hq[ot];
-            const int oq = (int)(oqw & 0x7fffu);
-            const size_t srec = recBase + hrec[ot] + ((oqw >> 15) ? (size_t)j : (size_t)j * N);
-            const SsSample<3> sv = SsSample<3>::load(a.samples, valid ? srec : recBase);  // (unconditional, see the prefetch note: a valid address either way)
-            const uint32_t c0w = ctx[oq][0], c1w = ctx[oq][1], oDescThr = ctx[oq][2], oColorThr = c1w >> 16;
-            const uint32_t curw = hcur[ot];
-            const uint32_t totColorThr = oColorThr * 3, totDescThr = oDescThr * 3, scColorThr = totColorThr / 2;
+          for (int jj = 0; jj < B; ++jj)
+            if (j == B + jj) smp = nbt[jj];
+        }
+        bool matched = false;
+        uint32_t mDesc = 0, mSum = 0;
+        if (go) {
+          if constexpr (C == 1) {
+            const int bcc = smp.color(0);
+            const unsigned bdc = smp.desc(0);
+            const uint32_t cd = (uint32_t)abs(cur[0] - bcc);
+            const uint32_t intraD = (uint32_t)__popc(intra[0] ^ bdc);
+            const unsigned inter = ss_lbsp(nb[0], bcc, lut[bcc]);
+            const uint32_t dd = (intraD + (uint32_t)__popc(inter ^ bdc)) / 2;
+            if (dd <= descThr) {
+              uint32_t sd = (dd / 4) * (255 / 16) + cd;
+              sd = sd < 255 ? sd : 255;
+              if (sd <= colorThr) matched = true, mDesc = dd, mSum = sd;
+            }
+          } else {
+            const uint32_t totColorThr = colorThr * 3, totDescThr = descThr * 3, scColorThr = totColorThr / 2;
             uint32_t totDesc = 0, totSum = 0;
             bool ok = true;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-              const uint4 w = *reinterpret_cast<const uint4*>(&nbs[ot][4 * c]);
-              uint32_t nbf[8];
-#pragma unroll
-              for (int k = 0; k < 4; ++k) {
-                nbf[k] = __builtin_amdgcn_perm(w.x, w.z, 0x0c000c00u | ((uint32_t)(4 + k) << 16) | (uint32_t)k);
-                nbf[4 + k] = __builtin_amdgcn_perm(w.y, w.w, 0x0c000c00u | ((uint32_t)(4 + k) << 16) | (uint32_t)k);
-              }
-              const int cc = (int)((curw >> (8 * c)) & 0xffu), bcc = sv.color(c);
-              const uint32_t ic = c == 0 ? (c0w & 0xffffu) : c == 1 ? (c0w >> 16) : (c1w & 0xffffu);
-              const uint32_t cd = (uint32_t)abs(cc - bcc);
-              const uint32_t intraD = (uint32_t)__popc(ic ^ sv.desc(c));
-              const unsigned inter = ss_lbsp(nbf, bcc, lut[bcc]);
-              const uint32_t interD = (uint32_t)__popc(inter ^ sv.desc(c));
+              const int bcc = smp.color(c);
+              const uint32_t cd = (uint32_t)abs(cur[c] - bcc);
+              const uint32_t intraD = (uint32_t)__popc(intra[c] ^ smp.desc(c));
+              const unsigned inter = ss_lbsp(nb[c], bcc, lut[bcc]);
+              const uint32_t interD = (uint32_t)__popc(inter ^ smp.desc(c));
               const uint32_t dd = (intraD + interD) / 2;
               uint32_t sd = (dd / 2) * (255 / 16) + cd;
               sd = sd < 255 ? sd : 255;
               ok = ok && sd <= scColorThr;
               totDesc += dd, totSum += sd;
             }
-            const bool m = ok && !(totDesc > totDescThr || totSum > totColorThr);
-            if (valid) qres[ot * 8 + j] = (uint16_t)(m ? (totDesc | (totSum << 6)) : 0xffffu);
+            if (ok && !(totDesc > totDescThr || totSum > totColorThr)) matched = true, mDesc = totDesc, mSum = totSum;
           }
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-          if (enq) {
-            const uint4 rr = *reinterpret_cast<const uint4*>(&qres[threadIdx.x * 8]);
-            const uint32_t rw[4] = {rr.x, rr.y, rr.z, rr.w};
-#pragma unroll
-            for (int b = 0; b < 2 * B; ++b) {
-              const uint32_t r = (rw[b >> 1] >> (16 * (b & 1))) & 0xffffu;
-              if (((enq >> b) & 1u) && good < a.nReq && r != 0xffffu) {
-                const uint32_t mDesc = r & 0x3fu, mSum = r >> 6;
-                minDesc = minDesc > mDesc ? mDesc : minDesc;
-                minSum = minSum > mSum ? mSum : minSum;
-                good++;
-              }
-            }
-          }
-          __builtin_amdgcn_wave_barrier();  // (the next round rewrites the list and the results)
         }
-      }
-      // I passes: one candidate per lane and pass.  (Round 4 tried to fill the idle lanes of a sparse pass by splitting each candidate
-      // over three lanes, one channel each, the helpers reading the owner's neighbours from the frame tile: parity-green, but a
-      // sub-pass of 21 candidates cost ~150 vector + 25 LDS instructions against ~230 for a whole pass, and 40 % of the passes hold 22-42
-      // candidates, i.e. need two: -4 % vector instructions, +90 M bank-conflict cycles, no time gained - profiles/r04_subsense_phase_a_pmc.txt.)
-      if constexpr (!QUEUE) {
-        for (;;) {
-          const bool go = active && cand != 0 && good < a.nReq;
-          const unsigned long long gm = __ballot(go);
-          if (!gm) break;
-          // DENSE PASSES (round 4): a pass costs the same ~230 vector instructions for one candidate as for 64, and once the lanes
-          // with two or three candidates in their batch are the only ones left it ran at a few lanes.  So a pass that fewer than
-          // ipassMin lanes would join is put off while some other active lane has something else to do (its next batch, or finishing
-          // and handing its lane to a new pixel): the waiting lanes keep batch and candidate bits and join the passes of the next trip.
-          // Every trip still makes progress - either a pass runs, or a lane without candidates moves on - and each pixel still sees
-          // its samples in order up to its nReq-th match: the same integers for any ipassMin (1 = every pass at once, the round-3 form).
-          // Not once the tile's queue is empty: no new pixel can join then, a trip is a memory round trip, and waiting only strings
-          // more of them together (measured: the aged model, whose pixels mostly take one trip, lost 13 % without this condition).
-          if (!qempty && __popcll(gm) < a.ipassMin && __any(active && !go)) {
-            SS_STAT(9, 1), SS_STAT(10, __popcll(gm));
-            break;
-          }
-          SS_STAT(7, 1), SS_STAT(8, __popcll(gm));
-          SsSample<C> smp = bt[0];
-          if (go) {
-            const int j = __ffs((int)cand) - 1;
-            cand &= cand - 1;
-  #pragma unroll
-            for (int jj = 1; jj < B; ++jj)
-              if (j == jj) smp = bt[jj];
-  #pragma unroll
-            for (int jj = 0; jj < B; ++jj)
-              if (j == B + jj) smp = nbt[jj];
-          }
-          bool matched = false;
-          uint32_t mDesc = 0, mSum = 0;
-          if (go) {
-            if constexpr (C == 1) {
-              const int bcc = smp.color(0);
-              const unsigned bdc = smp.desc(0);
-              const uint32_t cd = (uint32_t)abs(cur[0] - bcc);
-              const uint32_t intraD = (uint32_t)__popc(intra[0] ^ bdc);
-              const unsigned inter = ss_lbsp(nb[0], bcc, lut[bcc]);
-              const uint32_t dd = (intraD + (uint32_t)__popc(inter ^ bdc)) / 2;
-              if (dd <= descThr) {
-                uint32_t sd = (dd / 4) * (255 / 16) + cd;
-                sd = sd < 255 ? sd : 255;
-                if (sd <= colorThr) matched = true, mDesc = dd, mSum = sd;
-              }
-            } else {
-              const uint32_t totColorThr = colorThr * 3, totDescThr = descThr * 3, scColorThr = totColorThr / 2;
-              uint32_t totDesc = 0, totSum = 0;
-              bool ok = true;
-  #pragma unroll
-              for (int c = 0; c < 3; ++c) {
-                const int bcc = smp.color(c);
-                const uint32_t cd = (uint32_t)abs(cur[c] - bcc);
-                const uint32_t intraD = (uint32_t)__popc(intra[c] ^ smp.desc(c));
-                const unsigned inter = ss_lbsp(nb[c], bcc, lut[bcc]);
-                const uint32_t interD = (uint32_t)__popc(inter ^ smp.desc(c));
-                const uint32_t dd = (intraD + interD) / 2;
-                uint32_t sd = (dd / 2) * (255 / 16) + cd;
-                sd = sd < 255 ? sd : 255;
-                ok = ok && sd <= scColorThr;
-                totDesc += dd, totSum += sd;
-              }
-              if (ok && !(totDesc > totDescThr || totSum > totColorThr)) matched = true, mDesc = totDesc, mSum = totSum;
-            }
-          }
-          if (go && matched) {
-            minDesc = minDesc > mDesc ? mDesc : minDesc;
-            minSum = minSum > mSum ? mSum : minSum;
-            good++;
-          }
+        if (go && matched) {
+          minDesc = minDesc > mDesc ? mDesc : minDesc;
+          minSum = minSum > mSum ? mSum : minSum;
+          good++;
         }
       }
       if (active && !(cand != 0 && good < a.nReq)) {  // (a lane with candidates left waits for the next trip's passes)
@@ -687,161 +455,140 @@ __global__ __launch_bounds__(kBlock) void ss_phase_a_kernel(const SsArgs a) {
         }
       }
     }
-#ifdef BGS_SS_STATS
-    if (lane == 0)
-      for (int i = 0; i < 12; ++i) atomicAdd(&g_ss_stats[i], (unsigned long long)st[i]);
-#endif
   }
   __syncthreads();
 
-  if constexpr (SPLIT) {
-    // ---- stage 3: the outcome of the loop goes to memory: the raw segmentation (the post-processing chain starts from it) and the
-    // hand-over word of ss_feedback_kernel, which applies :498-576 beside that chain
-  #pragma unroll
-    for (int r = 0; r < PPL; ++r) {
-      const int qq = r * kBlock + threadIdx.x, lx = qq % kSsTW, ly = qq / kSsTW;
-      const int x = x0 + lx, y = y0 + ly;
-      if (x < a.cols && y < a.rows) {
-        const size_t i = sN + (size_t)y * a.cols + x;
-        const uint32_t res = ctx[qq][2];
-        const bool in = interior_of(x, y);
-        a.raw[i] = (in && (int)(res & 0xffu) < a.nReq) ? 255 : 0;
-        if (in) a.ho[i * 2] = res;
+  // ---- stage 3: everything after the loop, :498-582
+  const SsScalars sc = a.sc[stream];
+  auto at = [&](int ry, int rx, int c) -> int {
+    const uint8_t* rowp = reinterpret_cast<const uint8_t*>(tile[ry]);
+    const int shift = (int)(((long)(y0 + ry - 2) * a.cols * C + rb) & 3L);
+    return rowp[shift + rx * C + c];
+  };
+#pragma unroll 2
+  for (int r = 0; r < PPL; ++r) {
+    const int qq = r * kBlock + threadIdx.x, lx = qq % kSsTW, ly = qq / kSsTW;
+    const int x = x0 + lx, y = y0 + ly;
+    if (interior_of(x, y)) {
+      const size_t p = (size_t)y * a.cols + x, i = sN + p;
+      const uint32_t fr = a.frameIndex, pi = (uint32_t)p;
+      float Rv = a.R[i], Vv = a.V[i], Tv = a.T[i];
+      const float rawLT_old = a.RawLT[i], rawST_old = a.RawSTOld[i], finLT = a.FinLT[i], finST = a.FinST[i];
+      const float dlast_old = a.DlastOld[i], dminLT_old = a.DminLT[i], dminST_old = a.DminST[i];
+      const int lastfg = a.lastFG[i], blink = a.blinks[i];
+      int lastc[C], cur[C];
+      unsigned lastd[C], intra[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) lastc[c] = a.lastColor[i * C + c], lastd[c] = a.lastDesc[i * C + c], cur[c] = at(ly + 2, lx + 2, c);
+      const int unst = (Rv > 3.0f || (rawLT_old - finLT) > 0.1f || (rawST_old - finST) > 0.1f) ? 1 : 0;  // :467
+      // the random neighbour of the background branch (:526-551) depends only on `unst`
+      const bool use3 = a.use3x3 && !unst;
+      int xn, yn;
+      {
+        const uint32_t r4 = ss_rand(fr, pi, 4);
+        if (use3) {
+          const int rr = (int)(r4 % 8u);
+          xn = x + kSsN3[rr][0], yn = y + kSsN3[rr][1];
+        } else {
+          const int rr = (int)(r4 % 24u);
+          xn = x + kSsN5[rr][0], yn = y + kSsN5[rr][1];
+        }
+        xn = min(max(xn, 2), a.cols - 3), yn = min(max(yn, 2), a.rows - 3);
       }
-    }
-  } else {
-    // ---- stage 3: everything after the loop, :498-582
-    const SsScalars sc = a.sc[stream];
-    auto at = [&](int ry, int rx, int c) -> int {
-      const uint8_t* rowp = reinterpret_cast<const uint8_t*>(tile[ry]);
-      const int shift = (int)(((long)(y0 + ry - 2) * a.cols * C + rb) & 3L);
-      return rowp[shift + rx * C + c];
-    };
-  #pragma unroll 2
-    for (int r = 0; r < PPL; ++r) {
-      const int qq = r * kBlock + threadIdx.x, lx = qq % kSsTW, ly = qq / kSsTW;
-      const int x = x0 + lx, y = y0 + ly;
-      if (interior_of(x, y)) {
-        const size_t p = (size_t)y * a.cols + x, i = sN + p;
-        const uint32_t fr = a.frameIndex, pi = (uint32_t)p;
-        float Rv = a.R[i], Vv = a.V[i], Tv = a.T[i];
-        const float rawLT_old = a.RawLT[i], rawST_old = a.RawSTOld[i], finLT = a.FinLT[i], finST = a.FinST[i];
-        const float dlast_old = a.DlastOld[i], dminLT_old = a.DminLT[i], dminST_old = a.DminST[i];
-        const int lastfg = a.lastFG[i], blink = a.blinks[i];
-        int lastc[C], cur[C];
-        unsigned lastd[C], intra[C];
-  #pragma unroll
-        for (int c = 0; c < C; ++c) lastc[c] = a.lastColor[i * C + c], lastd[c] = a.lastDesc[i * C + c], cur[c] = at(ly + 2, lx + 2, c);
-        const int unst = (Rv > 3.0f || (rawLT_old - finLT) > 0.1f || (rawST_old - finST) > 0.1f) ? 1 : 0;  // :467
-        // the random neighbour of the background branch (:526-551) depends only on `unst`
-        const bool use3 = a.use3x3 && !unst;
-        int xn, yn;
-        {
-          const uint32_t r4 = ss_rand(fr, pi, 4);
-          if (use3) {
-            const int rr = (int)(r4 % 8u);
-            xn = x + kSsN3[rr][0], yn = y + kSsN3[rr][1];
-          } else {
-            const int rr = (int)(r4 % 24u);
-            xn = x + kSsN5[rr][0], yn = y + kSsN5[rr][1];
-          }
-          xn = min(max(xn, 2), a.cols - 3), yn = min(max(yn, 2), a.rows - 3);
-        }
-        const size_t j = sN + (size_t)yn * a.cols + xn;
-        const float nbrLast = a.DlastOld[j], nbrRaw = a.RawSTOld[j];  // previous frame's copy (contract)
-        const uint32_t c0 = ctx[qq][0], c1 = ctx[qq][1], res = ctx[qq][2];
-        intra[0] = c0 & 0xffffu;
-        if constexpr (C == 3) intra[1] = c0 >> 16, intra[2] = c1 & 0xffffu;
-        const int good = (int)(res & 0xffu);
-        const uint32_t minDesc = (res >> 8) & 0xffu, minSum = res >> 16;
-        uint32_t l1 = 0, hd = 0;
-  #pragma unroll
-        for (int c = 0; c < C; ++c) {
-          l1 += (uint32_t)abs(lastc[c] - cur[c]);
-          hd += (uint32_t)__popc((lastd[c] ^ intra[c]) & 0xffffu);
-        }
-        const float fLT = a.fLT, fST = a.fST;
-        const float normLast = ((float)l1 / maxColor + (float)hd / maxDesc) / 2;  // :498
-        a.DlastNew[i] = dlast_old * (1.0f - fST) + normLast * fST;
-        a.unstable[i] = (uint8_t)unst;
-        float dminLT = dminLT_old, dminST = dminST_old, rawLT = rawLT_old, rawST = rawST_old;
-        bool isfg;
-        uint16_t reqSelf = 0, reqNbr = 0;
-        if (good < a.nReq) {  // foreground :500-515
-          float nm = ((float)minSum / maxColor + (float)minDesc / maxDesc) / 2 + (float)(a.nReq - good) / a.nReq;
-          nm = nm > 1.0f ? 1.0f : nm;
-          dminLT = dminLT * (1.0f - fLT) + nm * fLT;
-          dminST = dminST * (1.0f - fST) + nm * fST;
-          rawLT = rawLT * (1.0f - fLT) + fLT;
-          rawST = rawST * (1.0f - fST) + fST;
-          isfg = true;
-          if (sc.cooldown && (ss_rand(fr, pi, 0) % 2u) == 0) reqSelf = ss_req(ss_mod(ss_rand(fr, pi, 1), (uint32_t)a.nS, magic), 12);
-        } else {  // background :516-552
-          const float nm = ((float)minSum / maxColor + (float)minDesc / maxDesc) / 2;
-          dminLT = dminLT * (1.0f - fLT) + nm * fLT;
-          dminST = dminST * (1.0f - fST) + nm * fST;
-          rawLT = rawLT * (1.0f - fLT);
-          rawST = rawST * (1.0f - fST);
-          isfg = false;
-          const uint32_t lr = (uint32_t)ceilf(Tv);  // (the reference computes these in size_t; every value fits 31 bits)
-          if (ss_mod(ss_rand(fr, pi, 2), lr, magic) == 0) reqSelf = ss_req(ss_mod(ss_rand(fr, pi, 3), (uint32_t)a.nS, magic), 12);
-          const uint32_t nrand = ss_rand(fr, pi, 5);
-          if (ss_mod(nrand, use3 ? lr : (lr / 2 + 1), magic) == 0 || (nbrRaw > 0.995f && nbrLast < 0.010f && ss_mod(nrand, (uint32_t)sc.capLo, magic) == 0))
-            reqNbr = ss_req(ss_mod(ss_rand(fr, pi, 6), (uint32_t)a.nS, magic), (yn - y + 2) * 5 + (xn - x + 2));
-        }
-        a.DminLT[i] = dminLT, a.DminST[i] = dminST, a.RawLT[i] = rawLT, a.RawSTNew[i] = rawST;
-        a.raw[i] = isfg ? 255 : 0;
-        a.req[i * 2] = reqSelf, a.req[i * 2 + 1] = reqNbr;
-        // Round 3: the self update is stored HERE.  No other pixel reads this pixel's samples in phase A (every pixel tests its own
-        // model only, and this lane is done with it), so the write cannot be seen early; a diffusion request of another source for
-        // the same slot is ordered against it in phase B exactly as before (the request stays in a.req: an earlier source's loses
-        // there, a later source's is applied after this launch and wins).  It takes half of the scattered 16-byte writes out of
-        // phase B, whose only limit they are, into a kernel that is bound by vector issue.
-        if (a.selfInA && reqSelf) {
-          unsigned dsc[C];
-  #pragma unroll
-          for (int c = 0; c < C; ++c) dsc[c] = intra[c];
-          SsSample<C>::make(cur, dsc).store(a.samples, ss_rec(a, stream, N, p, (int)ss_req_slot(reqSelf)));
-        }
-        // feedback :553-576
-        const float dmin_min = dminLT < dminST ? dminLT : dminST, dmin_max = dminLT > dminST ? dminLT : dminST;
-        if (lastfg || (dmin_min < 0.1f && isfg)) {
-          if (Tv < sc.capHi) Tv += div_rn(0.5f, dmin_max * Vv);
-        } else if (Tv > sc.capLo)
-          Tv -= div_rn(0.25f * Vv, dmin_max);
-        if (Tv < sc.capLo)
-          Tv = sc.capLo;
-        else if (Tv > sc.capHi)
-          Tv = sc.capHi;
-        if (dmin_max > 0.1f && blink)
-          Vv += 1.0f;
-        else if (Vv > 0.1f) {
-          Vv -= lastfg ? 0.1f / 4 : unst ? 0.1f / 2 : 0.1f;
-          if (Vv < 0.1f) Vv = 0.1f;
-        }
-        const float pw = 1.0f + dmin_min * 2;
-        if ((double)Rv < __dmul_rn((double)pw, (double)pw))  // std::pow(float, int) is a double in C++11; the square is exact
-          Rv += 0.01f * (Vv - 0.1f);
-        else {
-          Rv -= div_rn(0.01f, Vv);
-          if (Rv < 1.0f) Rv = 1.0f;
-        }
-        a.R[i] = Rv, a.V[i] = Vv, a.T[i] = Tv;
-        if constexpr (C == 3)
-          nzcount += (__popc(intra[0]) + __popc(intra[1]) + __popc(intra[2])) >= 4;  // :577-578
-        else
-          nzcount += __popc(intra[0]) >= 2;  // :430-431
-  #pragma unroll
-        for (int c = 0; c < C; ++c) {  // :579-582
-          a.lastDesc[i * C + c] = (uint16_t)intra[c];
-          a.lastColor[i * C + c] = (uint8_t)cur[c];
-        }
-      } else if (x < a.cols && y < a.rows) {
-        const size_t i = sN + (size_t)y * a.cols + x;
-        a.raw[i] = 0;
-        a.req[i * 2] = 0, a.req[i * 2 + 1] = 0;
-        a.DlastNew[i] = a.DlastOld[i], a.RawSTNew[i] = a.RawSTOld[i];
+      const size_t j = sN + (size_t)yn * a.cols + xn;
+      const float nbrLast = a.DlastOld[j], nbrRaw = a.RawSTOld[j];  // previous frame's copy (contract)
+      const uint32_t c0 = ctx[qq][0], c1 = ctx[qq][1], res = ctx[qq][2];
+      intra[0] = c0 & 0xffffu;
+      if constexpr (C == 3) intra[1] = c0 >> 16, intra[2] = c1 & 0xffffu;
+      const int good = (int)(res & 0xffu);
+      const uint32_t minDesc = (res >> 8) & 0xffu, minSum = res >> 16;
+      uint32_t l1 = 0, hd = 0;
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        l1 += (uint32_t)abs(lastc[c] - cur[c]);
+        hd += (uint32_t)__popc((lastd[c] ^ intra[c]) & 0xffffu);
       }
+      const float fLT = a.fLT, fST = a.fST;
+      const float normLast = ((float)l1 / maxColor + (float)hd / maxDesc) / 2;  // :498
+      a.DlastNew[i] = dlast_old * (1.0f - fST) + normLast * fST;
+      a.unstable[i] = (uint8_t)unst;
+      float dminLT = dminLT_old, dminST = dminST_old, rawLT = rawLT_old, rawST = rawST_old;
+      bool isfg;
+      uint16_t reqSelf = 0, reqNbr = 0;
+      if (good < a.nReq) {  // foreground :500-515
+        float nm = ((float)minSum / maxColor + (float)minDesc / maxDesc) / 2 + (float)(a.nReq - good) / a.nReq;
+        nm = nm > 1.0f ? 1.0f : nm;
+        dminLT = dminLT * (1.0f - fLT) + nm * fLT;
+        dminST = dminST * (1.0f - fST) + nm * fST;
+        rawLT = rawLT * (1.0f - fLT) + fLT;
+        rawST = rawST * (1.0f - fST) + fST;
+        isfg = true;
+        if (sc.cooldown && (ss_rand(fr, pi, 0) % 2u) == 0) reqSelf = ss_req(ss_mod(ss_rand(fr, pi, 1), (uint32_t)a.nS, magic), 12);
+      } else {  // background :516-552
+        const float nm = ((float)minSum / maxColor + (float)minDesc / maxDesc) / 2;
+        dminLT = dminLT * (1.0f - fLT) + nm * fLT;
+        dminST = dminST * (1.0f - fST) + nm * fST;
+        rawLT = rawLT * (1.0f - fLT);
+        rawST = rawST * (1.0f - fST);
+        isfg = false;
+        const uint32_t lr = (uint32_t)ceilf(Tv);  // (the reference computes these in size_t; every value fits 31 bits)
+        if (ss_mod(ss_rand(fr, pi, 2), lr, magic) == 0) reqSelf = ss_req(ss_mod(ss_rand(fr, pi, 3), (uint32_t)a.nS, magic), 12);
+        const uint32_t nrand = ss_rand(fr, pi, 5);
+        if (ss_mod(nrand, use3 ? lr : (lr / 2 + 1), magic) == 0 || (nbrRaw > 0.995f && nbrLast < 0.010f && ss_mod(nrand, (uint32_t)sc.capLo, magic) == 0))
+          reqNbr = ss_req(ss_mod(ss_rand(fr, pi, 6), (uint32_t)a.nS, magic), (yn - y + 2) * 5 + (xn - x + 2));
+      }
+      a.DminLT[i] = dminLT, a.DminST[i] = dminST, a.RawLT[i] = rawLT, a.RawSTNew[i] = rawST;
+      a.raw[i] = isfg ? 255 : 0;
+      a.req[i * 2] = reqSelf, a.req[i * 2 + 1] = reqNbr;
+      // Round 3: the self update is stored HERE.  No other pixel reads this pixel's samples in phase A (every pixel tests its own
+      // model only, and this lane is done with it), so the write cannot be seen early; a diffusion request of another source for
+      // the same slot is ordered against it in phase B exactly as before (the request stays in a.req: an earlier source's loses
+      // there, a later source's is applied after this launch and wins).  It takes half of the scattered 16-byte writes out of
+      // phase B, whose only limit they are, into a kernel that is bound by vector issue.
+      if (a.selfInA && reqSelf) {
+        unsigned dsc[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) dsc[c] = intra[c];
+        SsSample<C>::make(cur, dsc).store(a.samples, ss_rec(a, stream, N, p, (int)ss_req_slot(reqSelf)));
+      }
+      // feedback :553-576
+      const float dmin_min = dminLT < dminST ? dminLT : dminST, dmin_max = dminLT > dminST ? dminLT : dminST;
+      if (lastfg || (dmin_min < 0.1f && isfg)) {
+        if (Tv < sc.capHi) Tv += div_rn(0.5f, dmin_max * Vv);
+      } else if (Tv > sc.capLo)
+        Tv -= div_rn(0.25f * Vv, dmin_max);
+      if (Tv < sc.capLo)
+        Tv = sc.capLo;
+      else if (Tv > sc.capHi)
+        Tv = sc.capHi;
+      if (dmin_max > 0.1f && blink)
+        Vv += 1.0f;
+      else if (Vv > 0.1f) {
+        Vv -= lastfg ? 0.1f / 4 : unst ? 0.1f / 2 : 0.1f;
+        if (Vv < 0.1f) Vv = 0.1f;
+      }
+      const float pw = 1.0f + dmin_min * 2;
+      if ((double)Rv < __dmul_rn((double)pw, (double)pw))  // std::pow(float, int) is a double in C++11; the square is exact
+        Rv += 0.01f * (Vv - 0.1f);
+      else {
+        Rv -= div_rn(0.01f, Vv);
+        if (Rv < 1.0f) Rv = 1.0f;
+      }
+      a.R[i] = Rv, a.V[i] = Vv, a.T[i] = Tv;
+      if constexpr (C == 3)
+        nzcount += (__popc(intra[0]) + __popc(intra[1]) + __popc(intra[2])) >= 4;  // :577-578
+      else
+        nzcount += __popc(intra[0]) >= 2;  // :430-431
+#pragma unroll
+      for (int c = 0; c < C; ++c) {  // :579-582
+        a.lastDesc[i * C + c] = (uint16_t)intra[c];
+        a.lastColor[i * C + c] = (uint8_t)cur[c];
+      }
+    } else if (x < a.cols && y < a.rows) {
+      const size_t i = sN + (size_t)y * a.cols + x;
+      a.raw[i] = 0;
+      a.req[i * 2] = 0, a.req[i * 2 + 1] = 0;
+      a.DlastNew[i] = a.DlastOld[i], a.RawSTNew[i] = a.RawSTOld[i];
     }
   }
 #pragma unroll
@@ -851,264 +598,20 @@ __global__ __launch_bounds__(kBlock) void ss_phase_a_kernel(const SsArgs a) {
   if (threadIdx.x == 0 && nz_block) atomicAdd(&a.sc[stream].nzCount, nz_block);
 }
 
-// ----------------------------------------------------------------------------------------------- feedback (:498-576), round 4
-// Everything BackgroundSubtractorSuBSENSE::operator() does to a pixel after its sample-consensus loop that is not the frame itself:
-// rolling means of the distances and of the raw segmentation (:498-522), the update decisions (:508-551: which of its own samples, which
-// neighbour's), the T / v / R feedback (:553-576).  Rounds 1-3 ran it as stage 3 of phase A, where it was a third of a kernel that is
-// bound by vector issue (~700 of ~2 200 lane-instructions per quiet pixel: seven counter hashes, five run-time `%`, up to eight
-// correctly rounded divisions).  Nothing in it needs the frame tile or phase A's registers, so it is a pointwise kernel of its own now,
-// launched on the side stream in front of phase B - beside the post-processing chain, which only needs `raw`.  What phase A hands over
-// is 8 bytes per pixel (`ho`):
-//   word 0  good | minDesc << 8 | minSum << 16         the outcome of the loop (:469-497)
-//   word 1  l1 | hd << 10 | unstable << 16 | lastFG != 0 << 17 | blink != 0 << 18
-//           l1 / hd: L1 colour distance and Hamming descriptor distance to the pixel's last frame (:498); the three flags are this
-//           frame's inputs of the rules, captured before the chain rewrites the maps they come from (m_oLastFGMask, m_oBlinksFrame;
-//           `unstable` needs the final-segmentation means that ss_finish_kernel updates)
-// and the per-stream scalars as they stood at the start of the frame (scSnap: the frame-level block rewrites `sc` beside this kernel).
-// The statements, their order and every operand are those of stage 3 before: same floats, same draws.  x % d with d in 1..1023 is exact
-// through ss_mod.  grid: (ceil(cols / 256), rows, streams).
-template <int C>
-__global__ __launch_bounds__(kBlock) void ss_feedback_kernel(const SsArgs a) {
-  constexpr uint32_t maxColor = 255 * C, maxDesc = 16 * C;
-  __shared__ uint32_t magic[kSsMagicN];
-  for (int k = threadIdx.x; k < kSsMagicN; k += kBlock) magic[k] = a.magic[k];
-  __syncthreads();
-  const int stream = a.first + blockIdx.z;
-  const size_t N = (size_t)a.rows * a.cols, sN = (size_t)stream * N;
-  const int x = blockIdx.x * kBlock + threadIdx.x, y = blockIdx.y;
-  if (x >= a.cols) return;
-  const size_t p = (size_t)y * a.cols + x, i = sN + p;
-  if (!(x >= 2 && x < a.cols - 2 && y >= 2 && y < a.rows - 2)) {  // LBSP::validateROI: border pixels are never touched
-    a.req[i * 2] = 0, a.req[i * 2 + 1] = 0;
-    a.DlastNew[i] = a.DlastOld[i], a.RawSTNew[i] = a.RawSTOld[i];
-    return;
-  }
-  const SsScalars sc = a.scSnap[stream];
-  const uint32_t fr = a.frameIndex, pi = (uint32_t)p;
-  const uint2 hw = *reinterpret_cast<const uint2*>(a.ho + i * 2);
-  float Rv = a.R[i], Vv = a.V[i], Tv = a.T[i];
-  const float rawLT_old = a.RawLT[i], rawST_old = a.RawSTOld[i];
-  const float dlast_old = a.DlastOld[i], dminLT_old = a.DminLT[i], dminST_old = a.DminST[i];
-  const int good = (int)(hw.x & 0xffu);
-  const uint32_t minDesc = (hw.x >> 8) & 0xffu, minSum = hw.x >> 16;
-  const uint32_t l1 = hw.y & 0x3ffu, hd = (hw.y >> 10) & 0x3fu;
-  const int unst = (int)((hw.y >> 16) & 1u), lastfg = (int)((hw.y >> 17) & 1u), blink = (int)((hw.y >> 18) & 1u);
-  // the random neighbour of the background branch (:526-551) depends only on `unst`
-  const bool use3 = a.use3x3 && !unst;
-  int xn, yn;
-  {
-    const uint32_t r4 = ss_rand(fr, pi, 4);
-    if (use3) {
-      const int rr = (int)(r4 % 8u);
-      xn = x + kSsN3[rr][0], yn = y + kSsN3[rr][1];
-    } else {
-      const int rr = (int)(r4 % 24u);
-      xn = x + kSsN5[rr][0], yn = y + kSsN5[rr][1];
-    }
-    xn = min(max(xn, 2), a.cols - 3), yn = min(max(yn, 2), a.rows - 3);
-  }
-  const size_t j = sN + (size_t)yn * a.cols + xn;
-  const float nbrLast = a.DlastOld[j], nbrRaw = a.RawSTOld[j];  // previous frame's copy (contract)
-  const float fLT = a.fLT, fST = a.fST;
-  const float normLast = ((float)l1 / maxColor + (float)hd / maxDesc) / 2;  // :498
-  a.DlastNew[i] = dlast_old * (1.0f - fST) + normLast * fST;
-  float dminLT = dminLT_old, dminST = dminST_old, rawLT = rawLT_old, rawST = rawST_old;
-  bool isfg;
-  uint16_t reqSelf = 0, reqNbr = 0;
-  if (good < a.nReq) {  // foreground :500-515
-    float nm = ((float)minSum / maxColor + (float)minDesc / maxDesc) / 2 + (float)(a.nReq - good) / a.nReq;
-    nm = nm > 1.0f ? 1.0f : nm;
-    dminLT = dminLT * (1.0f - fLT) + nm * fLT;
-    dminST = dminST * (1.0f - fST) + nm * fST;
-    rawLT = rawLT * (1.0f - fLT) + fLT;
-    rawST = rawST * (1.0f - fST) + fST;
-    isfg = true;
-    if (sc.cooldown && (ss_rand(fr, pi, 0) % 2u) == 0) reqSelf = ss_req(ss_mod(ss_rand(fr, pi, 1), (uint32_t)a.nS, magic), 12);
-  } else {  // background :516-552
-    const float nm = ((float)minSum / maxColor + (float)minDesc / maxDesc) / 2;
-    dminLT = dminLT * (1.0f - fLT) + nm * fLT;
-    dminST = dminST * (1.0f - fST) + nm * fST;
-    rawLT = rawLT * (1.0f - fLT);
-    rawST = rawST * (1.0f - fST);
-    isfg = false;
-    const uint32_t lr = (uint32_t)ceilf(Tv);  // (the reference computes these in size_t; every value fits 31 bits)
-    if (ss_mod(ss_rand(fr, pi, 2), lr, magic) == 0) reqSelf = ss_req(ss_mod(ss_rand(fr, pi, 3), (uint32_t)a.nS, magic), 12);
-    const uint32_t nrand = ss_rand(fr, pi, 5);
-    if (ss_mod(nrand, use3 ? lr : (lr / 2 + 1), magic) == 0 || (nbrRaw > 0.995f && nbrLast < 0.010f && ss_mod(nrand, (uint32_t)sc.capLo, magic) == 0))
-      reqNbr = ss_req(ss_mod(ss_rand(fr, pi, 6), (uint32_t)a.nS, magic), (yn - y + 2) * 5 + (xn - x + 2));
-  }
-  a.DminLT[i] = dminLT, a.DminST[i] = dminST, a.RawLT[i] = rawLT, a.RawSTNew[i] = rawST;
-  *reinterpret_cast<uint32_t*>(a.req + i * 2) = (uint32_t)reqSelf | ((uint32_t)reqNbr << 16);
-  // The SELF update is stored here (round 3: by phase A).  Nobody reads a pixel's samples between its consensus loop and phase B, so
-  // the write cannot be seen early; a diffusion request of another source for the same slot is ordered against it in phase B exactly
-  // as before (the request stays in a.req: an earlier source's loses there, a later source's is applied by phase B, after this
-  // launch, and wins).  It keeps half of the scattered 16-byte writes out of phase B, whose only limit they are.
-  if (a.selfInA && reqSelf) {
-    int cur[C];
-    unsigned dsc[C];
-    if constexpr (C == 3) {  // what phase A left as the pixel's last colour / descriptor IS this frame's
-      const uint32_t cw = *reinterpret_cast<const uint32_t*>(a.lastColor + i * 3);
-      const uint2 dw = *reinterpret_cast<const uint2*>(a.lastDesc + i * 3);
-      cur[0] = (int)(cw & 0xffu), cur[1] = (int)((cw >> 8) & 0xffu), cur[2] = (int)((cw >> 16) & 0xffu);
-      dsc[0] = dw.x & 0xffffu, dsc[1] = dw.x >> 16, dsc[2] = dw.y & 0xffffu;
-    } else {
-      cur[0] = a.lastColor[i], dsc[0] = a.lastDesc[i];
-    }
-    SsSample<C>::make(cur, dsc).store(a.samples, ss_rec(a, stream, N, p, (int)ss_req_slot(reqSelf)));
-  }
-  // feedback :553-576
-  const float dmin_min = dminLT < dminST ? dminLT : dminST, dmin_max = dminLT > dminST ? dminLT : dminST;
-  if (lastfg || (dmin_min < 0.1f && isfg)) {
-    if (Tv < sc.capHi) Tv += div_rn(0.5f, dmin_max * Vv);
-  } else if (Tv > sc.capLo)
-    Tv -= div_rn(0.25f * Vv, dmin_max);
-  if (Tv < sc.capLo)
-    Tv = sc.capLo;
-  else if (Tv > sc.capHi)
-    Tv = sc.capHi;
-  if (dmin_max > 0.1f && blink)
-    Vv += 1.0f;
-  else if (Vv > 0.1f) {
-    Vv -= lastfg ? 0.1f / 4 : unst ? 0.1f / 2 : 0.1f;
-    if (Vv < 0.1f) Vv = 0.1f;
-  }
-  const float pw = 1.0f + dmin_min * 2;
-  if ((double)Rv < __dmul_rn((double)pw, (double)pw))  // std::pow(float, int) is a double in C++11; the square is exact
-    Rv += 0.01f * (Vv - 0.1f);
-  else {
-    Rv -= div_rn(0.01f, Vv);
-    if (Rv < 1.0f) Rv = 1.0f;
-  }
-  a.R[i] = Rv, a.V[i] = Vv, a.T[i] = Tv;
-}
-
 // ----------------------------------------------------------------------------------------------- LOBSTER, phase A
 // BackgroundSubtractorLOBSTER::operator() (package_bgs/pl/BackgroundSubtractorLOBSTER.cpp:172-284): the sample-consensus
 // test of SuBSENSE with fixed thresholds and no feedback maps; update requests go through the same phase B.
 // a.nMinColor = nColorDistThreshold, a.nDescOff = nDescDistThreshold; a.lastColor / a.lastDesc point at SCRATCH planes here
 // (what a requesting pixel will write: its current colour and intra descriptor) - LOBSTER's own last-frame images are
 // only read by refreshModel.  Learning rate = BGSLOBSTER_DEFAULT_LEARNING_RATE (LOBSTER.cpp:36 passes none).
-template <int C>
-__global__ __launch_bounds__(kBlock) void lob_phase_a_kernel(const SsArgs a) {
-  constexpr int HW = kSsTW + 4, HH = kSsTH + 4;
-  constexpr int ROWB = (HW * C + 3 + 3) / 4 * 4;
-  constexpr uint32_t kLearningRate = 16;
-  __shared__ uint32_t tile[HH][ROWB / 4];
-  __shared__ uint8_t lut[256];
-  const int stream = a.first + blockIdx.z;
-  const size_t N = (size_t)a.rows * a.cols, sN = (size_t)stream * N;
-  const uint8_t* img = a.frame + (size_t)blockIdx.z * N * C;
-  const int x0 = blockIdx.x * kSsTW, y0 = blockIdx.y * kSsTH;
-  const long imgsz = (long)N * C, rb = (long)(x0 - 2) * C;
-  for (int i = threadIdx.x; i < HH * (ROWB / 4); i += kBlock) {
-    const int ry = i / (ROWB / 4), rd = i - ry * (ROWB / 4);
-    const int y = min(max(y0 + ry - 2, 0), a.rows - 1);
-    const long off = (((long)y * a.cols * C + rb) & ~3L) + 4L * rd;
-    uint32_t v = 0;
-    if (off >= 0 && off + 4 <= imgsz)
-      v = *reinterpret_cast<const uint32_t*>(img + off);
-    else if (off < imgsz && off + 4 > 0)
-      for (int b = 0; b < 4; ++b)
-        if (off + b >= 0 && off + b < imgsz) v |= (uint32_t)img[off + b] << (8 * b);
-    tile[ry][rd] = v;
-  }
-  lut[threadIdx.x] = a.lut[(size_t)stream * 256 + threadIdx.x];
-  __syncthreads();
-  const int lx = threadIdx.x % kSsTW, ly = threadIdx.x / kSsTW;
-  const int x = x0 + lx, y = y0 + ly;
-  if (x >= a.cols || y >= a.rows) return;
-  const size_t p = (size_t)y * a.cols + x, i = sN + p;
-  if (!(x >= 2 && x < a.cols - 2 && y >= 2 && y < a.rows - 2)) {  // outside LBSP::validateROI: never foreground, never updated
-    a.raw[i] = 0;
-    a.req[i * 2] = 0, a.req[i * 2 + 1] = 0;
-    return;
-  }
-  int cur[C];
-  uint32_t nb[C][8];
-  {
-    LbspWin<C> win;
-    win.load(&tile[0][0], ROWB / 4, ly, lx, (int)(((long)(y0 - 2) * a.cols * C + rb) & 3L), (a.cols * C) & 3);
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      cur[c] = win.centre(c);
-      win.pack(c, nb[c]);
-    }
-  }
-  const uint32_t colorThr = (uint32_t)a.nMinColor, descThr = (uint32_t)a.nDescOff;
-  const uint32_t descThr3 = descThr * 3, colorThr3 = colorThr * 3, scDesc = descThr3 / 2, scColor = colorThr3 / 2;  // :225-228
-  size_t rec = ss_rec(a, stream, N, p, 0);
-  const size_t rstep = a.pixelMajor ? 1 : N;
-  int good = 0, idx = 0;
-  int bc[C];
-  unsigned bd[C];
-  SsSample<C> smp = SsSample<C>::load(a.samples, rec), nsmp = smp;
-  while (good < a.nReq && idx < a.nS) {  // :192-205 (gray) / :241-258 (BGR); sample idx+1 is in flight while idx is tested (the loop is latency-bound)
-    rec += (idx + 1 < a.nS) ? rstep : 0;  // unconditional, see phase A: the loaded registers must BE nsmp for the load to stay in flight
-    nsmp = SsSample<C>::load(a.samples, rec);
-#pragma unroll
-    for (int c = 0; c < C; ++c) bc[c] = smp.color(c), bd[c] = smp.desc(c);
-    if constexpr (C == 1) {
-      const int bcc = bc[0];
-      const uint32_t cd = (uint32_t)abs(cur[0] - bcc);
-      if (cd <= colorThr / 2) {
-        const unsigned inter = ss_lbsp(nb[0], bcc, lut[bcc]);
-        if ((uint32_t)__popc(inter ^ bd[0]) <= descThr) good++;
-      }
-    } else {
-      uint32_t totC = 0, totD = 0;
-      bool ok = true;
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        if (ok) {
-          const int bcc = bc[c];
-          const uint32_t cd = (uint32_t)abs(cur[c] - bcc);
-          if (cd > scColor) {
-            ok = false;
-          } else {
-            const unsigned inter = ss_lbsp(nb[c], bcc, lut[bcc]);
-            const uint32_t dd = (uint32_t)__popc(inter ^ bd[c]);
-            if (dd > scDesc)
-              ok = false;
-            else
-              totC += cd, totD += dd;
-          }
-        }
-      if (ok && totD <= descThr3 && totC <= colorThr3) good++;
-    }
-    idx++;
-    ss_wait_here(nsmp);
-    smp = nsmp;
-  }
-  uint16_t reqSelf = 0, reqNbr = 0;
-  if (good >= a.nReq) {
-    const uint32_t fr = a.frameIndex, pi = (uint32_t)p;
-    if ((ss_rand(fr, pi, 0) % kLearningRate) == 0) reqSelf = ss_req(ss_rand(fr, pi, 1) % (uint32_t)a.nS, 12);  // :209-214 / :262-269
-    if ((ss_rand(fr, pi, 2) % kLearningRate) == 0) {                                                             // :215-222 / :270-279
-      const int r = (int)(ss_rand(fr, pi, 3) % 8u);
-      const int xn = min(max(x + kSsN3[r][0], 2), a.cols - 3), yn = min(max(y + kSsN3[r][1], 2), a.rows - 3);
-      reqNbr = ss_req(ss_rand(fr, pi, 4) % (uint32_t)a.nS, (yn - y + 2) * 5 + (xn - x + 2));
-    }
-    if (reqSelf | reqNbr) {
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        a.lastColor[i * C + c] = (uint8_t)cur[c];
-        a.lastDesc[i * C + c] = (uint16_t)ss_lbsp(nb[c], cur[c], lut[cur[c]]);
-      }
-    }
-  }
-  a.raw[i] = good < a.nReq ? 255 : 0;  // :207 / :260
-  a.req[i * 2] = reqSelf, a.req[i * 2 + 1] = reqNbr;
-}
-
-// Round 4: LOBSTER's phase A with the LANES FED FROM A QUEUE (the form SuBSENSE's phase A took in round 2).  lob_phase_a_kernel above
-// gives every lane one pixel and walks the samples in lock step: a wave runs as many trips as its slowest pixel needs, and on a scene
-// with a few percent of foreground nearly every wave holds a pixel that matches nothing and walks all 35 samples (8 x 1080p, S_surv:
-// 2.36 - 2.53 ms although the average pixel tests six).  Here a workgroup owns a 64 x 16 tile (four pixels per lane), a lane that has
+// The LANES ARE FED FROM A QUEUE (the form SuBSENSE's phase A took in round 2).  Rounds 1-3 gave every lane one pixel and walked the
+// samples in lock step: a wave ran as many trips as its slowest pixel needed, and on a scene with a few percent of foreground nearly
+// every wave holds a pixel that matches nothing and walks all 35 samples (8 x 1080p, S_surv: 2.36 - 2.53 ms although the average pixel
+// tests six; DESIGN.md 7d, profiles/r04_lobster_queue.txt).  Here a workgroup owns a 64 x 16 tile (four pixels per lane), a lane that has
 // finished its pixel takes the next one from the tile's queue, and a trip tests one sample per active lane: the cheap part (colour
 // distances, exact: a sample matches only if EVERY test of :192-205 / :241-258 passes, so their order is free) for everybody, the
 // inter-LBSP part only when some lane's sample got that far.  What a pixel leaves behind is its match count in LDS; the update
 // requests and the colour / descriptor a requesting pixel hands to phase B are made afterwards, densely, for the whole tile.
-// Same results as lob_phase_a_kernel (BGS_LOB_QUEUE=0), whole-model parity tests.
 constexpr int kLobATH = 16;
 template <int C>
 __global__ __launch_bounds__(kBlock) void lob_phase_a_queue_kernel(const SsArgs a) {
@@ -1810,7 +1313,7 @@ __global__ __launch_bounds__(kBlock) void ss_flood_kernel(const uint64_t* mbits,
 // 8 x 1080p find wave slots beside phase B (which runs on its own stream at the same time) more easily than 1024-lane ones - the
 // first strip launch 224 instead of 250 us there, 43 us alone either way; what slows it beside phase B is its rounds of memory
 // round trips queueing behind phase B's scattered writes (engine_subsense.h).  <16, 4>: images up to 4096 rows (taller ones take
-// ss_flood_kernel); BGS_SS_FLOOD_WG1024=1 forces it for every height (tests).
+// ss_flood_kernel).
 constexpr int kSsFloodKT = 4, kSsFloodKTSmall = 5, kSsFloodNWSmall = 4;
 template <int NW, int KT>
 __global__ __launch_bounds__(NW * 64) void ss_flood_strip_kernel(const uint64_t* mbits, uint64_t* rbits, int rows, int W64, int* flags, int k) {
