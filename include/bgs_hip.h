@@ -176,7 +176,10 @@ typedef struct bgs_params {
 
   /* package_bgs/dp/ wrappers (DP*BGS.cpp:19 constructors): threshold = LowThreshold (HighThreshold = 2x, the mask that is
    * returned), alpha, gaussians = MaxModes (1..8).  learningFrames of WrenGA / Mean / AdaptiveMedian = learning_frames above
-   * (default 30 for those three; it has no effect because the wrappers clear the update mask every frame). */
+   * (default 30 for those three; it has no effect because the wrappers clear the update mask every frame).
+   * DPMeanBGS and DPAdaptiveMedianBGS hold `int threshold` and their params classes narrow it: dp_threshold stands for that int,
+   * (int)dp_threshold; Mean wraps it into an unsigned int (a negative one: no foreground), AdaptiveMedian into an unsigned char,
+   * twice (130 -> high threshold 4; 256 = 0).  NaN or a value outside int's range: BGS_ERR_UNSUPPORTED from bgs_create. */
   float dp_threshold;   /* Zivkovic 25, Grimson 9, WrenGA 12.25, Mean 2700, AdaptiveMedian 40 */
   float dp_alpha;       /* Zivkovic 0.001, Grimson 0.01, WrenGA 0.005, Mean 1e-6 */
   int32_t dp_gaussians; /* 3 */

@@ -1,8 +1,9 @@
 /* dp_oracle.c - TEST INFRASTRUCTURE ONLY (the checker the HIP kernels are compared with; never linked into the product).
  *
  * CPU restatement of the in-tree `package_bgs/dp/` background models, statement by statement from the
- * reference's own sources (they are self-contained float/byte arithmetic; they cannot be compiled here only because
- * dp/Image.h includes <opencv2/opencv.hpp>, which is absent - so this is a restatement from source, not from recall):
+ * reference's own sources (self-contained float/byte arithmetic).  The restatement is PINNED: the reference's own model files,
+ * compiled unmodified behind a stand-in <opencv2/opencv.hpp> (oracle/ref_stub, oracle/ref_dp_cli.cpp), produced
+ * tests/golden/dp_ref_*.npz, which tests/test_dp_cpu.py compares with this file bit for bit (masks and every model plane):
  *
  *   BGS_DP_ZIVKOVIC_AGMM   DPZivkovicAGMMBGS::process  dp/DPZivkovicAGMMBGS.cpp:29-80  over ZivkovicAGMM::SubtractPixel  dp/ZivkovicAGMM.cpp:103-364
  *   BGS_DP_GRIMSON_GMM     DPGrimsonGMMBGS::process    dp/DPGrimsonGMMBGS.cpp:29-82    over GrimsonGMM::SubtractPixel    dp/GrimsonGMM.cpp:119-295
@@ -16,6 +17,15 @@
  * HIGH-threshold mask (high = 2 * low, "used by post-processing"), img_bgmodel is never written.
  * Pixels are the frame's bytes in memory order (pixel(0) is the first byte, i.e. B of a BGR frame; the sources call it R).
  * Arithmetic is float where the source's is float and double where it is double (gcc x86-64: no x87, no FMA contraction).
+ *
+ * Thresholds are held in the types of the reference's params classes, through which the wrappers pass them:
+ *   Zivkovic / Grimson / Wren  float& LowThreshold(), HighThreshold()   low = (float)threshold, high = 2 * low in float
+ *   Mean                       unsigned int& (MeanBGS.h:50-60)          the wrapper's `int threshold` wraps modulo 2^32, high = 2u * low
+ *                              wraps again; SubtractPixel compares `float dist > unsigned`, i.e. with (float)high
+ *   AdaptiveMedian             unsigned char& (AdaptiveMedianBGS.h:50-58)  low = the int's low byte, high = the low byte of 2 * low
+ *                              (threshold 130 -> low 130, high 4); the comparison is between ints
+ * bgs_params carries dp_threshold as a float: for the two integer classes it stands for the wrapper's int, (int)dp_threshold;
+ * NaN and values outside int's range are refused.
  */
 #include "dp_oracle.h"
 
@@ -30,7 +40,8 @@ struct dp_state {
   bgs_algo algo;
   int rows, cols, K;
   size_t n;
-  float low, high, alpha;
+  float low, high, alpha; /* low / high: the three float classes */
+  unsigned ulow, uhigh;   /* Mean (unsigned int) and AdaptiveMedian (unsigned char) */
   int learning_frames, sampling_rate;
   float* modes;    /* Zivkovic: [n][K][5] = sigma, muR, muG, muB, weight (struct GMM, ZivkovicAGMM.h:96-103)
                       Grimson:  [n][K][6] = variance, muR, muG, muB, weight, significants (GrimsonGMM.h) */
@@ -52,6 +63,17 @@ int dp_create(bgs_algo algo, const bgs_params* p, const uint8_t* img, int rows, 
   s->algo = algo, s->rows = rows, s->cols = cols, s->n = (size_t)rows * cols;
   s->low = p->dp_threshold;  /* params.LowThreshold() = threshold */
   s->high = 2 * s->low;      /* params.HighThreshold() = 2*params.LowThreshold() */
+  if (algo == BGS_DP_MEAN || algo == BGS_DP_ADAPTIVE_MEDIAN) {
+    if (!(p->dp_threshold >= -2147483648.0f && p->dp_threshold < 2147483648.0f)) return dp_destroy(s), BGS_ERR_UNSUPPORTED; /* no int holds it */
+    const int threshold = (int)p->dp_threshold; /* the wrapper's `int threshold` */
+    if (algo == BGS_DP_MEAN) {
+      s->ulow = (unsigned)threshold; /* unsigned int& LowThreshold() */
+      s->uhigh = 2u * s->ulow;
+    } else {
+      s->ulow = (unsigned char)threshold; /* unsigned char& LowThreshold() */
+      s->uhigh = (unsigned char)(2 * s->ulow);
+    }
+  }
   s->alpha = p->dp_alpha;
   s->K = p->dp_gaussians;
   s->learning_frames = p->learning_frames, s->sampling_rate = p->dp_sampling_rate;
@@ -185,7 +207,16 @@ static uint8_t zivkovic_pixel(const dp_state* s, float* g, const uint8_t* pixel,
 
 /* GrimsonGMM::SubtractPixel, dp/GrimsonGMM.cpp:119-295.  qsort(compareGMM) orders by `significants`, largest first;
  * glibc's qsort is a merge sort for arrays this small, i.e. stable: restated as a stable insertion sort.
- * sqrt(float) resolves to the float overload (the file is C++ and <cmath> is in scope through OpenCV's headers). */
+ * sqrt(float) resolves to the float overload (the file is C++; libstdc++'s <math.h> declares the <cmath> overloads globally).
+ * Both are properties of the build environment, not of the source: the fixture build (tests/golden/make_dp_ref.py) records the
+ * overload it got and holds cases with equal keys (`ties`, `modes_ties`), DESIGN.md section 4. */
+static unsigned long long grimson_ties; /* sorts that met two modes with equal keys: what a test needs to know it exercised them */
+unsigned long long dp_grimson_sort_ties(int reset) {
+  const unsigned long long v = grimson_ties;
+  if (reset) grimson_ties = 0;
+  return v;
+}
+
 static void grimson_sort(float* g, int numModes) {
   enum { SIG = 5, F = 6 };
   for (int i = 1; i < numModes; ++i) {
@@ -196,6 +227,7 @@ static void grimson_sort(float* g, int numModes) {
       memcpy(g + (j + 1) * F, g + j * F, sizeof(t));
       j--;
     }
+    if (j >= 0 && g[j * F + SIG] == t[SIG]) grimson_ties++; /* equal keys: kept in their order, as a stable sort does */
     memcpy(g + (j + 1) * F, t, sizeof(t));
   }
 }
@@ -320,17 +352,18 @@ int dp_process(dp_state* s, const uint8_t* img, int64_t frame_num, uint8_t* fg) 
         const uint8_t* px = img + i * 3;
         float dist = 0; /* SubtractPixel, MeanBGS.cpp:77-98 */
         for (int ch = 0; ch < 3; ++ch) dist += (px[ch] - mean[ch]) * (px[ch] - mean[ch]);
-        fg[i] = dist > s->high ? DP_FOREGROUND : DP_BACKGROUND;
+        fg[i] = dist > (float)s->uhigh ? DP_FOREGROUND : DP_BACKGROUND;
         for (int ch = 0; ch < 3; ++ch) mean[ch] = s->alpha * mean[ch] + (1.0f - s->alpha) * px[ch]; /* Update :52-75 */
       }
       break;
     case BGS_DP_ADAPTIVE_MEDIAN: {
       const int update = (frame_num % s->sampling_rate) == 1; /* AdaptiveMedianBGS.cpp:60 */
+      const int high = (int)s->uhigh;
       for (size_t i = 0; i < n; ++i) {
         uint8_t* med = s->median + i * 3;
         const uint8_t* px = img + i * 3;
         int diffR = abs(px[0] - med[0]), diffG = abs(px[1] - med[1]), diffB = abs(px[2] - med[2]); /* :92-108 */
-        fg[i] = (diffR <= s->high && diffG <= s->high && diffB <= s->high) ? DP_BACKGROUND : DP_FOREGROUND;
+        fg[i] = (diffR <= high && diffG <= high && diffB <= high) ? DP_BACKGROUND : DP_FOREGROUND;
         if (update)
           for (int ch = 0; ch < 3; ++ch) {
             if (px[ch] > med[ch])

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.environ.get("BGS_ORACLE_LIB") or os.path.join(_HERE, "libbgs_oracle.so")  # BGS_ORACLE_LIB: e.g. an ASan/UBSan build (tools/sanitize_cpu.sh)
 _REF_LBSP = os.path.join(_HERE, "_ref", "libref_lbsp.so")
 _REF_SDLAMA = os.path.join(_HERE, "_ref", "ref_sdlama_cli")
+_REF_DP = os.path.join(_HERE, "_ref", "ref_dp_cli")
 
 _P = C.c_void_p
 _lib = None
@@ -37,6 +38,8 @@ def lib():
         l.orc_get_state.restype = C.c_int64
         l.orc_destroy.argtypes = [_P]
         l.orc_destroy.restype = None
+        l.dp_grimson_sort_ties.argtypes = [C.c_int]
+        l.dp_grimson_sort_ties.restype = C.c_ulonglong
         l.orc_bgr2gray.argtypes = [_P, C.c_size_t, _P, C.c_size_t, C.c_int, C.c_int]
         l.orc_bgr2gray.restype = None
         l.orc_lbsp_lut.argtypes = [C.c_float, C.c_int, C.c_int, _P]
@@ -133,6 +136,11 @@ class Oracle:
         n = lib().orc_get_state(self._h, plane.encode(), _ptr(out), out.nbytes)
         assert n == out.nbytes, (plane, n, out.nbytes)
         return out
+
+
+def dp_grimson_sort_ties(reset=True):
+    """Sorts of the DPGrimsonGMM restatement that met two modes with equal keys since the last reset (dp_oracle.c)."""
+    return int(lib().dp_grimson_sort_ties(int(reset)))
 
 
 def bgr2gray(img):
@@ -241,6 +249,49 @@ def ref_sigmadelta_clip(frames, amp=1, vmin=15, vmax=255):
         frames.tofile(fin)
         subprocess.run([_REF_SDLAMA, fin, str(rows), str(cols), str(n), str(amp), str(vmin), str(vmax), fout], check=True)
         return np.fromfile(fout, np.uint8).reshape(n - 1, rows, cols)
+
+
+def ref_dp_available():
+    return os.path.exists(_REF_DP)
+
+
+DP_REF_FIELDS = {"ziv": 5, "grim": 6}  # floats per mode, in the order of the source's struct
+
+
+def ref_dp_clip(cls, frames, planes=False, poison=None, exe=None, **params):
+    """High-threshold masks of every frame from the REFERENCE'S OWN package_bgs/dp model (compiled as is into oracle/_ref/ref_dp_cli
+    behind oracle/ref_stub) driven in the DP*BGS wrappers' order.  cls: ziv, grim, wren, mean, median; params: threshold, alpha,
+    gaussians, rate, learn (the wrapper's names, oracle/ref_dp_cli.cpp).  planes=True also returns the model after the last frame
+    in the layout of bgs_get_state: modes [K*F][n] / nmodes [n], gauss [4][n], mean [3][n], median [n][3].  poison: the byte every
+    image buffer of the reference holds before it is written (a fresh process per call, so two values expose uninitialised reads)."""
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    T, H, W = frames.shape[:3]
+    assert frames.shape == (T, H, W, 3)
+    n = H * W
+    args = [exe or _REF_DP, cls, str(T), str(H), str(W)] + ["%s=%s" % (k, repr(v)) for k, v in sorted(params.items())] + ["planes=%d" % bool(planes)]
+    env = dict(os.environ)
+    if poison is not None:
+        env["REF_STUB_POISON"] = str(int(poison))
+    out = subprocess.run(args, input=frames.tobytes(), stdout=subprocess.PIPE, env=env, check=True).stdout
+    masks = np.frombuffer(out, np.uint8, T * n).reshape(T, H, W).copy()
+    if not planes:
+        assert len(out) == T * n
+        return masks
+    tail = np.frombuffer(out, np.uint8, offset=T * n)
+    if cls in DP_REF_FIELDS:
+        P = int(params.get("gaussians", 3)) * DP_REF_FIELDS[cls]
+        assert tail.size == n * P * 4 + n
+        model = {"modes": np.ascontiguousarray(tail[:n * P * 4].view(np.float32).reshape(n, P).T), "nmodes": tail[n * P * 4:].copy()}
+    elif cls == "wren":
+        assert tail.size == n * 24
+        model = {"gauss": np.ascontiguousarray(tail.view(np.float32).reshape(n, 6)[:, :4].T)}  # var[1..2] are never read after InitModel
+    elif cls == "mean":
+        assert tail.size == n * 12
+        model = {"mean": np.ascontiguousarray(tail.view(np.float32).reshape(n, 3).T)}
+    else:
+        assert tail.size == n * 3
+        model = {"median": tail.reshape(n, 3).copy()}
+    return masks, model
 
 
 # ---- N3 frame preparation (ingest_oracle.c) ----

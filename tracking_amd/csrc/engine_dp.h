@@ -27,7 +27,26 @@ int dp_check(bgs_algo algo, const bgs_params& p) {
   if ((algo == BGS_DP_ZIVKOVIC_AGMM || algo == BGS_DP_GRIMSON_GMM) && (p.dp_gaussians < 1 || p.dp_gaussians > 5))
     return fail(BGS_ERR_UNSUPPORTED, "dp GMM kernels are built for 1..5 gaussians, got %d", p.dp_gaussians);
   if (algo == BGS_DP_ADAPTIVE_MEDIAN && p.dp_sampling_rate == 0) return fail(BGS_ERR_UNSUPPORTED, "AdaptiveMedian samplingRate 0 (frame_num %% 0)");
+  // DPMeanBGS / DPAdaptiveMedianBGS hold `int threshold`: dp_threshold stands for that int (dp_thresholds below)
+  if ((algo == BGS_DP_MEAN || algo == BGS_DP_ADAPTIVE_MEDIAN) && !(p.dp_threshold >= -2147483648.0f && p.dp_threshold < 2147483648.0f))
+    return fail(BGS_ERR_UNSUPPORTED, "%s threshold is an int in the reference, got %g", algo == BGS_DP_MEAN ? "DPMeanBGS" : "DPAdaptiveMedianBGS", (double)p.dp_threshold);
   return BGS_OK;
+}
+
+// LowThreshold / HighThreshold in the types of the reference's params classes, through which the wrappers pass `threshold`
+// (high = 2 * low in that type).  Zivkovic / Grimson / Wren: float.  Mean: unsigned int (MeanBGS.h:50-60) - a negative int wraps,
+// and `dist > high` converts high to float.  AdaptiveMedian: unsigned char (AdaptiveMedianBGS.h:50-58) - the int is cut to a byte
+// and 2 * low to a byte again (130 -> high 4).  Both integer results are exact as floats where the kernels compare them.
+void dp_thresholds(bgs_algo algo, float threshold, float* low, float* high) {
+  if (algo == BGS_DP_MEAN) {
+    const unsigned lo = (unsigned)(int)threshold, hi = 2u * lo;
+    *low = (float)lo, *high = (float)hi;
+  } else if (algo == BGS_DP_ADAPTIVE_MEDIAN) {
+    const unsigned char lo = (unsigned char)(int)threshold, hi = (unsigned char)(2 * lo);
+    *low = lo, *high = hi;
+  } else {
+    *low = threshold, *high = 2 * threshold;
+  }
 }
 
 bool dp_is_gmm(const bgs_engine* e) { return e->algo == BGS_DP_ZIVKOVIC_AGMM || e->algo == BGS_DP_GRIMSON_GMM; }
@@ -67,7 +86,8 @@ int dp_process(bgs_engine* e, int first, int count, int frames, size_t slab, con
   a.frames = frames, a.frame_stride = slab * 3, a.fg_stride = slab, a.bits_stride = slab / 64;
   a.frame = d_frames, a.state = e->dp_state, a.bstate = e->bgstate, a.fg = d_fg, a.fg_bits = d_bits;
   a.n = e->n, a.npix = e->n * count, a.first = first;
-  a.low = p.dp_threshold, a.high = 2 * a.low, a.alpha = p.dp_alpha;  // HighThreshold = 2*LowThreshold, e.g. DPZivkovicAGMMBGS.cpp:58
+  dp_thresholds(e->algo, p.dp_threshold, &a.low, &a.high);  // HighThreshold = 2*LowThreshold, e.g. DPZivkovicAGMMBGS.cpp:58
+  a.alpha = p.dp_alpha;
   a.update = 0, a.xcd_swizzle = e->xcd_swizzle;
   const unsigned blocks = blocks_for(a.npix);
   if (t == 0 && (e->algo == BGS_DP_ZIVKOVIC_AGMM || e->algo == BGS_DP_GRIMSON_GMM))  // InitModel: all modes and counts 0
