@@ -297,3 +297,86 @@ def test_packed_only_call_equals_byte_mask_call_for_every_algorithm(algo):
                 eng.get_state("no_such_plane", (1,), np.uint8, stream=0)
             assert ei.value.code == capi.ERR_STATE and "unknown state plane" in str(ei.value)
             eng.close()
+
+
+@pytest.mark.parametrize("algo", KNOWN_IDS)
+def test_every_family_returns_its_memory(algo):
+    """Create / set_geometry / one frame on the device path / destroy, for every class: after two warm-up cycles (runtime pools, code
+    objects, streams) N more cycles leave the device's free memory where it was, within the 12 MiB of the chunked-model test above.
+    8 streams of 540x960: the smallest model (ASBL's two gray planes) is 8 MB per engine, FrameDifference's ring 25 MB, the LB, KDE
+    and SuBSENSE models hundreds of MB and more.  N is three cycles, or as many as it takes for N x (what set_geometry took from the
+    device in the second warm-up cycle) to reach four times the slack: a family whose state is not given back shows, and so does any
+    one buffer of it that N engines make larger than the slack (a small buffer beside a large model can still hide).  Id 10
+    (BGS_LBSP_DESC) is no engine class: its geometry is refused and there is nothing to give back."""
+    torch = _torch()
+    S, H, W, slack = 8, 540, 960, 12 << 20
+    if algo == capi.LBSP_DESC:
+        with Engine(algo, n_streams=S) as eng, pytest.raises(capi.BgsError) as ei:
+            eng.set_geometry(H, W, 3)
+        assert ei.value.code == capi.ERR_UNSUPPORTED
+        return
+    frames = torch.from_numpy(np.stack([synth.random_frames(1, H, W, 3, seed=900 + s)[0] for s in range(S)])).cuda()  # [S][H][W][3]
+    fg = torch.empty((S, H, W), dtype=torch.uint8, device="cuda")
+
+    def cycle():
+        eng = Engine(algo, n_streams=S)
+        torch.cuda.synchronize()
+        before = torch.cuda.mem_get_info()[0]
+        eng.set_geometry(H, W, 3)
+        took = before - torch.cuda.mem_get_info()[0]
+        eng.process_batch_device(frames, fg, None, None)
+        torch.cuda.synchronize()
+        eng.close()
+        return took
+
+    cycle()
+    took = cycle()
+    assert took >= 7 << 20, (algo, took)  # every class keeps at least two bytes per pixel
+    N = max(3, -(-4 * slack // took))
+    assert N <= 8 and N * took >= 4 * slack, (algo, N, took)
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for _ in range(N):
+        cycle()
+    torch.cuda.synchronize()
+    free1 = torch.cuda.mem_get_info()[0]
+    print("algo %d: %.1f MB per engine, %d cycles, %d bytes missing" % (algo, took / 1e6, N, free0 - free1))
+    assert free0 - free1 < slack, "algorithm %d: device memory not returned: %d bytes missing after %d engines of %d bytes" % (algo, free0 - free1, N, took)
+
+
+REFUSED_GRAY = [capi.LB_SIMPLE_GAUSSIAN, capi.LB_FUZZY_GAUSSIAN, capi.LB_MOG, capi.LB_ADAPTIVE_SOM, capi.LB_FUZZY_ADAPTIVE_SOM, capi.VUMETER, capi.KDE]
+
+
+@pytest.mark.parametrize("algo", REFUSED_GRAY)
+def test_refused_geometry_leaves_a_usable_engine(algo):
+    """The classes that refuse 1-channel frames when the geometry is set (the five lb/ models and KDE with colour ratios on - its
+    default - at the head of their allocate, VuMeter in its geometry check): set_geometry(32, 64, 1) returns BGS_ERR_UNSUPPORTED and
+    leaves an engine without a model (no frames seen, bgs_get_state says so); set_geometry(32, 64, 3) then succeeds, and three frames
+    give the flags, masks and backgrounds of an engine that was never refused, byte for byte.  KDE learns from one frame here so that
+    frames 2 and 3 have a mask."""
+    _torch()
+    H, W = 32, 64
+    params = capi.default_params(algo)
+    if algo == capi.KDE:
+        assert params.kde_color_ratios == 1
+        params.kde_frames_to_learn = 1
+    with Engine(algo, params=params) as eng, Engine(algo, params=params) as fresh:
+        with pytest.raises(capi.BgsError) as ei:
+            eng.set_geometry(H, W, 1)
+        assert ei.value.code == capi.ERR_UNSUPPORTED and "3-channel" in str(ei.value), str(ei.value)
+        assert eng.frames_seen(0) == 0
+        with pytest.raises(capi.BgsError) as ei:
+            eng.get_state("count", (1,), np.int64)
+        assert ei.value.code == capi.ERR_STATE and "no model yet" in str(ei.value)
+        eng.set_geometry(H, W, 3)
+        fresh.set_geometry(H, W, 3)
+        compared = 0
+        for t, frame in enumerate(synth.random_frames(3, H, W, 3, seed=930)):
+            (fg, bg), (rfg, rbg) = eng.process(frame), fresh.process(frame)
+            assert eng.stream_flags(0) == fresh.stream_flags(0), (algo, t)
+            for got, want, what in ((fg, rfg, "mask"), (bg, rbg, "background")):
+                assert (got is None) == (want is None), (algo, t, what)
+                if got is not None:
+                    assert np.array_equal(got, want), (algo, t, what)
+                    compared += 1
+        assert fg is not None and compared >= 2, (algo, "nothing was compared")

@@ -6,10 +6,11 @@
 // device entry points take HBM pointers and launch over streams x pixels.  There is no CPU fallback: if HIP
 // is unavailable every compute entry point fails with BGS_ERR_HIP.
 //
-// This file holds what every class shares: the engine's members, allocation helpers, the split of a call into runs of streams
-// (launch_key), the packed-mask plumbing, clip calls, the host path and the C entry points.  What a class does - checks, model
-// allocation, the launch key, one frame, a fused clip, the state export - lives in its engine_*.h and is reached only through
-// that file's `Family` of entry points, looked up once per engine by family_of() below.
+// This file holds what every class shares: the engine's generic members, allocation helpers (DevPtr, DMALLOC, model_allocate), the
+// split of a call into runs of streams (launch_key), the packed-mask plumbing, clip calls, the host path and the C entry points.
+// What a class is and does lives in its engine_*.h: its state struct (a FamilyState: device buffers, tables, per-stream counters;
+// the engine holds it as `model`) and its checks, model allocation, launch key, one frame, fused clip and state export, reached
+// only through that file's `Family` of entry points, looked up once per engine by family_of() below.
 #include "../../include/bgs_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -94,8 +96,13 @@ inline unsigned blocks_for(size_t groups) { return (unsigned)((groups + bgs::kBl
 }  // namespace
 
 namespace {
-struct SsDevice;  // engine_subsense.h
-struct Family;    // below
+struct Family;  // below
+
+// The model of one engine, as its family defines it in its engine_*.h: device buffers (DevPtr members, freed by the destructor), host
+// tables and whatever the reference's model object counts per stream.  Made by Family::allocate, destroyed by free_all.
+struct FamilyState {
+  virtual ~FamilyState() = default;
+};
 }
 
 // One virtual address range backed by separately created physical chunks (hipMemAddressReserve + hipMemCreate x n + hipMemMap): how
@@ -103,15 +110,26 @@ struct Family;    // below
 struct VmmRange {
   std::vector<hipMemGenericAllocationHandle_t> handles;
   void* base = nullptr;
-  void** owner = nullptr;  // the engine member model_allocate filled with `base` (free_all nulls it: the range is not hipFree's to release)
+  void** owner = nullptr;  // the raw pointer inside the DevPtr that model_allocate filled with `base` (free_all nulls it: the range is not hipFree's to release)
   size_t bytes = 0, chunk = 0, mapped = 0;  // mapped: chunks actually mapped (a failure half-way leaves fewer than handles)
 };
 
+// What is here is what the generic code below uses itself.  A family's model - buffers, tables, per-stream counters - is the state
+// struct of its engine_*.h behind `model`; what stays is
+//  - geometry, the per-stream bookkeeping every family shares (seen, rpos, last_flags), staging, lanes, pins, timing, ingest, cc scratch, vmm;
+//  - the frame history ring: process_clip_run, bgs_process and bgs_submit read and write it themselves, so it is a service of the
+//    generic code that the history classes use, not their private state;
+//  - `counter`: the families that have a learning phase counted in frames share it with that one meaning, and bgs_reset_stream clears it;
+//  - p and fz: both may be set before the geometry is known, i.e. before there is a state;
+//  - the knobs, which bgs_create (environment) and bgs_set_option set before allocation.
 struct bgs_engine {
   bgs_algo algo;
   const Family* fam = nullptr;  // the class's entry points (family_of)
+  std::unique_ptr<FamilyState> model;  // the class's state (null until the geometry is set, and for the frame history classes)
   bgs_params p;
+  bgs_fuzzy_params fz{};  // bgs_set_fuzzy_params
   int device = 0;
+  int n_cu = 256;  // compute units of `device` (allocate): the persistent kernels size their grids by it
   int S = 1;
   int rows = 0, cols = 0, ch = 0;
   size_t n = 0;  // pixels per stream; 0 until the geometry is known
@@ -125,81 +143,22 @@ struct bgs_engine {
   bool borrow = false;               // device path: history = the caller's previous d_frames, no copies
   bool borrow_in_clip = false;       // set by process_clip: frames of the clip serve as history, for the range of that call
   const uint8_t* borrowed[2] = {nullptr, nullptr};
-  // byte state (SFD background, ABL/ASBL background): [S][n*state_ch]
-  uint8_t* bgstate = nullptr;
-  int state_ch = 0;
-  uint8_t* abl_lut = nullptr;   // ABL: 256 x 256 table of background bytes for the current alpha (kernel_pointwise.h)
-  double abl_lut_alpha = 0;     // the alpha it was built for (ASBL: two tables of 257 rows, learning then detection phase)
-  double asbl_lut_alpha[2] = {0, 0};
-  bool abl_lut_valid = false;
-  int n_cu = 256;
-  uint8_t* bgstate2 = nullptr;  // ASBL: second buffer of the ping-pong pair (the 3x3 median reads neighbours' OLD background)
-  std::vector<uint8_t> flip;    // ASBL: which buffer holds the current background, per stream
-  float* mog1_state = nullptr;  // MOG1 model (kernel_mog1.h, tiled)
-  float* dp_state = nullptr;    // package_bgs/dp models (kernel_dp.h): [S][planes][n]
-  SsDevice* ss = nullptr;       // SuBSENSE model (engine_subsense.h)
-  int2* gmg_rec = nullptr;        // GMG histograms (kernel_gmg.h): {colour, weight} records [F][P]
-  uint8_t* gmg_nfeat = nullptr;
-  // KDE model (kernel_kde.h / engine_kde.h): stream-major planes of 4-byte records, the kernel table and the colour-ratio gate
-  uint32_t *kde_samples = nullptr, *kde_tb = nullptr, *kde_meta = nullptr, *kde_acc = nullptr;
-  double* kde_lut = nullptr;
-  int2* kde_gate = nullptr;
-  unsigned long long* kde_trips = nullptr;  // diagnostics: density-loop trips (BGS_KDE_TRIPS=1)
-  uint64_t kde_lanes = 0;                   // lanes the counted launches covered
-  bool kde_count_trips = false;
-  struct KdeStream {                        // the reference object's counters, one set per stream (engine_kde.h)
-    int64_t fn = 0, top = 0, tidx = 0, tbc = 0, tbtop = 0;
-  };
-  std::vector<KdeStream> kde;
-  // DPPratiMediodBGS / DPTextureBGS models (kernel_dp2.h / engine_dp2.h): stream-major planes
-  uint32_t *pm_samples = nullptr, *pm_med = nullptr;  // samples [S][H][n], medoid ping-pong [2][S][n]
-  uint16_t* pm_dist = nullptr;                        // [S][H][n]
-  uint32_t *tex_r = nullptr, *tex_gb = nullptr;       // histogram planes [S][16][n], [S][32][n]
-  uint8_t* tex_mask = nullptr;                        // the last frame's mask [S][n] (the transposed update gate)
-  // package_bgs/lb/ models (kernel_lb.h / engine_lb.h): planar doubles [S][P][n], MoG mode counts, the SOMs' background bytes
-  double* lb_model = nullptr;
-  int32_t* lb_k = nullptr;
-  uint8_t* lb_bg = nullptr;
-  std::vector<int> lb_mk;          // the SOMs' training counter m_K, one per stream
-  // VuMeter (kernel_vumeter.h / engine_vumeter.h): histogram planes [bin][S][n], background bytes and live-bin bitmaps [S][n], the
-  // unfiltered and the eroded mask [S][n]
-  float* vu_hist = nullptr;
-  uint8_t *vu_bg = nullptr, *vu_raw = nullptr, *vu_tmp = nullptr;
-  uint32_t* vu_live = nullptr;
-  std::vector<int> vu_count;       // m_nCount of each stream's model object
-  int vu_sparse = 1;               // BGS_VU_SPARSE: 0 dense, 1 live-bin with whole-line stores, 2 live-bin with masked stores (identical results)
-  // Fuzzy integrals (kernel_fuzzy.h / engine_fuzzy.h): the float BGR background [S][n][3]; per-frame scratch: seven float planes
-  // [S][n] (gray of input and background, hs[3], integral column-major, blurred integral row-major), pi codes, scan block products,
-  // per-stream min / max keys; the LBP table
-  bgs_fuzzy_params fz;
-  float *fz_bg = nullptr, *fz_f = nullptr, *fz_tab = nullptr;
-  uint8_t *fz_code = nullptr, *fz_bprod = nullptr;
-  uint32_t* fz_minmax = nullptr;
-  std::vector<int64_t> fz_fn;        // frameNumber of each stream's object
-  std::vector<uint8_t> fz_detected;  // the stream has an integral image
-  int lb_px = 1;                   // pixels per lane of the two Gaussian kernels (BGS_LB_PX=2: the double2 form, A/B; identical results)
-  // MOG2 model (kernel_mog2.h: tiles of ranked weights + fixed-slot records + rank->slot meta words)
-  uint8_t* mog2_state = nullptr;
-  int xcd_swizzle = 1;             // XCD-aware block order (kernel_mog2.h): 0 off, 1 model kernels (MOG2, MOG1, dp), 2 also the byte-stream kernels
-  int mog2_sparse = 3;             // data-dependent traffic (kernel_mog2.h): 0 dense (everything loaded and written), 1 only what changed is written, 2 / 4 a lane also loads only the modes its pixel has, 3 = choose 1 or 4 from the scene
-  int mog2_complete = 1;           // sector-complete stores (kernel_mog2.h); BGS_MOG2_COMPLETE=0 for A/B runs
-  bool clip_fuse = true;           // MOG2 clip calls keep the model in registers across frames (option 7; results identical either way)
-  int mog2_sparse_now = 2;         // what auto mode currently runs
-  int mog2_sparse_want = 2;        // what the last poll asked for (a switch needs two polls in a row)
-  unsigned mog2_launches = 0;      // auto mode: per-frame launches so far (every 16th one samples)
-  unsigned* d_stat = nullptr;      // device: {record slots sampled, modes live, records needed after the summaries}
-  // pinned copies of the counters, a ring of kStatSlots posts (one per sampling launch, each with its event): a host that runs far
-  // ahead of the device still finds the most recent sample that has COMPLETED when it looks
-  static constexpr int kStatSlots = 8;
-  unsigned* h_stat = nullptr;      // [kStatSlots][3]
-  hipEvent_t stat_ev[kStatSlots] = {nullptr};
-  bool stat_posted[kStatSlots] = {false};
-  unsigned stat_seq = 0;           // posts so far
-  int model_chunk_mb = 256;        // big models are built from physical chunks of this size (model_allocate); 0: one plain hipMalloc
-  bool poison = false;             // BGS_DEBUG_POISON: every fresh device buffer is filled with 0xA5 (see dmalloc)
+
+  struct Knobs {
+    int xcd_swizzle = 1;             // XCD-aware block order (kernel_mog2.h): 0 off, 1 model kernels (MOG2, MOG1, dp), 2 also the byte-stream kernels
+    int mog2_sparse = 3;             // data-dependent traffic (kernel_mog2.h): 0 dense (everything loaded and written), 1 only what changed is written, 2 / 4 a lane also loads only the modes its pixel has, 3 = choose 1 or 4 from the scene
+    int mog2_complete = 1;           // sector-complete stores (kernel_mog2.h); BGS_MOG2_COMPLETE=0 for A/B runs
+    bool clip_fuse = true;           // MOG2 clip calls keep the model in registers across frames (option 7; results identical either way)
+    int lb_px = 1;                   // pixels per lane of the two Gaussian kernels (BGS_LB_PX=2: the double2 form, A/B; identical results)
+    int vu_sparse = 1;               // BGS_VU_SPARSE: 0 dense, 1 live-bin with whole-line stores, 2 live-bin with masked stores (identical results)
+    bool kde_count_trips = false;    // diagnostics: count density-loop trips (BGS_KDE_TRIPS=1)
+    int model_chunk_mb = 256;        // big models are built from physical chunks of this size (model_allocate); 0: one plain hipMalloc
+    size_t model_chunk_min_bytes = (size_t)768 << 20;  // models below this take one plain hipMalloc (BGS_MODEL_CHUNK_MIN_MB: test knob)
+    bool poison = false;             // BGS_DEBUG_POISON: every fresh device buffer is filled with 0xA5 (see dmalloc)
+    int host_register = 0;           // BGS_OPT_HOST_REGISTER: roles that may be page-locked in place (bit 0 input, 1 mask, 2 background); 0 = always stage
+  } knob;
   // a model built from fixed-size physical chunks with the virtual memory API (model_allocate)
   VmmRange vmm;
-  size_t model_chunk_min_bytes = (size_t)768 << 20;     // models below this take one plain hipMalloc (BGS_MODEL_CHUNK_MIN_MB: test knob)
 
   // host staging (bgs_process)
   uint8_t *h_in = nullptr, *h_fg = nullptr, *h_bg = nullptr;
@@ -230,7 +189,6 @@ struct bgs_engine {
   // CPU spent copying images into / out of pinned staging, bytes that crossed the bus each way
   double diag_reg_ms = 0, diag_stage_in_ms = 0, diag_stage_out_ms = 0;
   int64_t diag_reg_calls = 0, diag_unreg_calls = 0, diag_h2d_bytes = 0, diag_d2h_bytes = 0, diag_frames = 0;
-  int host_register = 0;          // BGS_OPT_HOST_REGISTER: roles that may be page-locked in place (bit 0 input, 1 mask, 2 background); 0 = always stage
   bool ingest_on = false;             // bgs_set_ingest: bgs_process takes raw frames
   bgs_ingest ingest{};
   int raw_rows = 0, raw_cols = 0;     // geometry of the raw frames (fixed by the first one)
@@ -255,13 +213,12 @@ namespace {
 struct Family {
   int (*check)(bgs_algo, const bgs_params&);                      // nullable; needs no device (bgs_create, bgs_set_params)
   int (*check_geometry)(bgs_algo, int rows, int cols, int ch);    // nullable; refusals made before the device is opened
-  int (*allocate)(bgs_engine*);                                   // rows / cols / ch / n are set, e->stream exists; a failure is followed by release
-  void (*release)(bgs_engine*);                                   // frees whatever allocate made (possibly part of it) and nulls the pointers
+  int (*allocate)(bgs_engine*);                                   // rows / cols / ch / n are set, e->stream exists; makes e->model (make_state) and fills it; after a failure free_all destroys what there is of it
   uint64_t (*key)(const bgs_engine*, int stream);                 // streams whose next frame has the same key share a launch
   // one frame: launches on s, advances the family's own per-stream counters, *flags = BGS_FG_VALID / BGS_BG_VALID of the run
   int (*run)(bgs_engine*, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s, uint32_t* flags);
   int64_t (*get_state)(bgs_engine*, int stream, const char* plane, void* dst, size_t cap);
-  void (*reset_stream)(bgs_engine*, int stream);                  // nullable; per-stream counters beyond seen / counter / last_flags
+  void (*reset_stream)(bgs_engine*, int stream);                  // nullable; per-stream counters of the state beyond seen / counter / last_flags (called only when there is a state)
   void (*keep_frozen)(bgs_params& p, const bgs_params& old);      // nullable; what bgs_set_params restores once the geometry is set
   int (*apply_params)(bgs_engine*);                               // nullable; device tables that follow live parameters (bgs_set_params)
   bool (*needs_byte_mask)(const bgs_engine*);                     // nullable (no); the packed mask is made from the finished byte mask
@@ -291,10 +248,47 @@ void dfree(T*& p) {
   if (p) (void)hipFree(p), p = nullptr;
 }
 
-// bgs_get_state: `nb` device bytes at src are plane `plane`
-int64_t copy_plane(const char* plane, void* dst, size_t cap, const uint8_t* src, size_t nb) {
-  if (cap < nb) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
-  if (d2h_staged(dst, src, nb) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
+// A device buffer owned by a family's state struct: freed with the struct.  A chunked model (model_allocate) is not hipFree's to
+// release: free_all nulls `p` through VmmRange::owner and releases the range BEFORE the state is destroyed.
+template <class T>
+struct DevPtr {
+  T* p = nullptr;
+  DevPtr() = default;
+  DevPtr(DevPtr&& o) noexcept : p(o.p) { o.p = nullptr; }
+  DevPtr& operator=(DevPtr&& o) noexcept {
+    std::swap(p, o.p);
+    return *this;
+  }
+  DevPtr(const DevPtr&) = delete;
+  DevPtr& operator=(const DevPtr&) = delete;
+  ~DevPtr() { reset(); }
+  void reset() { dfree(p); }
+  operator T*() const { return p; }
+};
+
+// the state of e's family: made by its allocate, typed again by the one-line accessor of its engine_*.h
+template <class St>
+St& make_state(bgs_engine* e) {
+  St* st = new St();
+  e->model.reset(st);
+  return *st;
+}
+template <class St>
+St& state_of(const bgs_engine* e) {
+  return static_cast<St&>(*e->model);
+}
+
+// bgs_get_state.  fetch: device memory into scratch of the library's own; too_small: the refusal of a caller's buffer, made before
+// anything is read back; copy_plane / copy_host: `nb` bytes of device memory / of a value the host already holds are plane `plane`
+int fetch(void* dst, const void* src, size_t nb) { return d2h_staged(dst, src, nb) == BGS_OK ? BGS_OK : fail(BGS_ERR_HIP, "hipMemcpy failed"); }
+int64_t too_small(const char* plane) { return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane); }
+int64_t copy_plane(const char* plane, void* dst, size_t cap, const void* src, size_t nb) {
+  if (cap < nb) return too_small(plane);
+  return fetch(dst, src, nb) ? BGS_ERR_HIP : (int64_t)nb;
+}
+int64_t copy_host(const char* plane, void* dst, size_t cap, const void* src, size_t nb) {
+  if (cap < nb) return too_small(plane);
+  std::memcpy(dst, src, nb);
   return (int64_t)nb;
 }
 int64_t unknown_plane(const bgs_engine* e, const char* plane) { return fail(BGS_ERR_STATE, "unknown state plane '%s' for algorithm %d", plane, (int)e->algo); }
@@ -318,12 +312,16 @@ void lane_release(bgs_engine::Lane& ln) {  // whatever of a lane came to be (bgs
 // allocator-dependent: the buffer is filled with 0xA5 (a NaN-free but wildly wrong float, a mode count of 165) before first use.
 int dmalloc(bgs_engine* e, void** p, size_t bytes) {
   HIP_TRY(hipMalloc(p, bytes));
-  if (e->poison) HIP_TRY(hipMemsetAsync(*p, 0xA5, bytes, e->stream));  // allocate() drains e->stream before it returns
+  if (e->knob.poison) HIP_TRY(hipMemsetAsync(*p, 0xA5, bytes, e->stream));  // allocate() drains e->stream before it returns
   return BGS_OK;
 }
+template <class T>
+void** raw_of(T*& p) { return (void**)&p; }
+template <class T>
+void** raw_of(DevPtr<T>& d) { return (void**)&d.p; }
 #define DMALLOC(ptr, bytes)                               \
   do {                                                    \
-    int rc__ = dmalloc(e, (void**)&(ptr), (bytes));       \
+    int rc__ = dmalloc(e, raw_of(ptr), (bytes));          \
     if (rc__) return rc__;                                \
   } while (0)
 
@@ -401,10 +399,10 @@ void vmm_free(VmmRange& v) {
 // A model of `bytes`: chunked (see above) from 768 MB up - smaller ones sit in the 256 MiB Infinity Cache for a good part and are
 // not HBM-bound - else, or when the virtual memory API refuses, one hipMalloc.  An engine has at most one such model.
 int model_allocate(bgs_engine* e, void** out, size_t bytes) {
-  if (e->model_chunk_mb > 0 && bytes >= e->model_chunk_min_bytes && !e->vmm.base) {
-    if (vmm_allocate(e->vmm, e->device, out, bytes, (size_t)e->model_chunk_mb << 20) == BGS_OK) {
+  if (e->knob.model_chunk_mb > 0 && bytes >= e->knob.model_chunk_min_bytes && !e->vmm.base) {
+    if (vmm_allocate(e->vmm, e->device, out, bytes, (size_t)e->knob.model_chunk_mb << 20) == BGS_OK) {
       e->vmm.owner = out;
-      if (e->poison) HIP_TRY(hipMemsetAsync(*out, 0xA5, e->vmm.bytes, e->stream));
+      if (e->knob.poison) HIP_TRY(hipMemsetAsync(*out, 0xA5, e->vmm.bytes, e->stream));
       return BGS_OK;
     }
     (void)hipGetLastError();
@@ -413,9 +411,11 @@ int model_allocate(bgs_engine* e, void** out, size_t bytes) {
   }
   return dmalloc(e, out, bytes);
 }
+template <class T>
+int model_allocate(bgs_engine* e, DevPtr<T>& out, size_t bytes) { return model_allocate(e, raw_of(out), bytes); }
 
-// The families.  Order matters where one borrows from another: engine_asbl.h and engine_gmg.h use engine_pointwise.h's launch macro
-// and "bg" export, engine_mog2.h uses engine_mog1.h's launch key.
+// The families.  Order matters where one borrows from another: engine_asbl.h uses engine_pointwise.h's launch macro, engine_mog2.h
+// uses engine_mog1.h's launch key.
 #include "engine_pointwise.h"
 #include "engine_asbl.h"
 #include "engine_gmg.h"
@@ -433,7 +433,6 @@ int model_allocate(bgs_engine* e, void** out, size_t bytes) {
 constexpr Family kUnbuilt = [] {
   Family f{};
   f.allocate = [](bgs_engine* e) -> int { return fail(BGS_ERR_UNSUPPORTED, "algorithm %d is not implemented in this build", (int)e->algo); };
-  f.release = [](bgs_engine*) {};
   return f;
 }();
 
@@ -477,11 +476,12 @@ const Family* family_of(bgs_algo algo) {
 }
 
 void free_all(bgs_engine* e) {
-  if (e->vmm.base) {  // a model built by model_allocate from physical chunks: not hipFree's to release
+  if (e->vmm.base) {  // a model built by model_allocate from physical chunks is not hipFree's to release: its DevPtr is emptied before the state goes
     if (e->vmm.owner) *e->vmm.owner = nullptr;
     vmm_free(e->vmm);
   }
-  e->fam->release(e);
+  e->model.reset();
+  for (auto& r : e->ring) dfree(r);
   dfree(e->cc_work), e->cc_cap = 0;
   dfree(e->pack_fg), e->pack_fg_bytes = 0;
   if (e->h_raw) (void)hipHostFree(e->h_raw), e->h_raw = nullptr;
@@ -520,6 +520,8 @@ int allocate(bgs_engine* e, int rows, int cols, int ch) {
   HIP_TRY(hipSetDevice(e->device));
   e->rows = rows, e->cols = cols, e->ch = ch, e->n = (size_t)rows * cols;
   if (!e->stream) HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, e->device) == hipSuccess && prop.multiProcessorCount > 0) e->n_cu = prop.multiProcessorCount;
   int rc = e->fam->allocate(e);
   if (rc) return rc;
   // Whatever allocation enqueued on e->stream (statistics counters, poison fills) is complete before the caller's first
@@ -540,7 +542,7 @@ bool host_pin(bgs_engine* e, int stream, int role, const void* ptr, size_t bytes
   if (!ptr || !bytes) return false;
   for (const auto& a : e->arenas)  // inside an arena the caller registered as a whole: nothing to do per image
     if ((const uint8_t*)ptr >= a.first && (const uint8_t*)ptr + bytes <= a.first + a.second) return true;
-  if (!((e->host_register >> role) & 1)) return false;
+  if (!((e->knob.host_register >> role) & 1)) return false;
   bgs_engine::HostPin& hp = e->pin[(size_t)stream * 3 + role];
   if (hp.ptr == ptr && hp.bytes == bytes) {
     if (hp.pinned) return true;
@@ -710,7 +712,7 @@ int process_clip_run(bgs_engine* e, int first, int count, int slab_count, int nf
   const size_t slab = e->n * slab_count;  // pixels from one frame of the clip to the next
   const size_t words = slab / 64;
   const Family& fam = *e->fam;
-  const bool fuse_ok = e->clip_fuse && fam.clip_fused && (!fam.clip_fusable || fam.clip_fusable(e));
+  const bool fuse_ok = e->knob.clip_fuse && fam.clip_fused && (!fam.clip_fusable || fam.clip_fusable(e));
   // FrameDifference / WeightedMoving*: frame t needs frames t-1 (t-2).  A per-frame call copies its frame into the engine's ring; inside
   // a clip the earlier frames of the clip ARE that history, so only the last one (two) are copied into the ring, once, at the end.
   const bool ring_clip = e->nring > 0 && !e->borrow && nframes >= 2;
@@ -938,20 +940,18 @@ int bgs_create(bgs_algo algo, const bgs_params* params, int hip_device, int n_st
   e->lanes.assign(n_streams, bgs_engine::Lane());
   e->last_flags.assign(n_streams, 0);
   e->counter.assign(n_streams, 0);
-  e->flip.assign(n_streams, 0);
-  e->kde.assign(n_streams, bgs_engine::KdeStream());
   fz_defaults(&e->fz);  // a fuzzy engine starts from the constructor's values whatever bgs_params it was handed (bgs_set_fuzzy_params)
-  if (const char* env = getenv("BGS_KDE_TRIPS")) e->kde_count_trips = atoi(env) != 0;
-  if (const char* env = getenv("BGS_MOG2_COMPLETE")) e->mog2_complete = atoi(env) != 0;
-  if (const char* env = getenv("BGS_LB_PX")) e->lb_px = atoi(env) == 2 ? 2 : 1;
-  if (const char* env = getenv("BGS_VU_SPARSE")) e->vu_sparse = std::min(std::max(atoi(env), 0), 2);
-  if (const char* env = getenv("BGS_XCD_SWIZZLE")) e->xcd_swizzle = atoi(env);
-  if (const char* env = getenv("BGS_MOG2_SPARSE")) e->mog2_sparse = atoi(env);
-  if (const char* env = getenv("BGS_MODEL_CHUNK_MB")) e->model_chunk_mb = atoi(env);
-  if (const char* env = getenv("BGS_MODEL_CHUNK_MIN_MB")) e->model_chunk_min_bytes = (size_t)std::max(atoi(env), 0) << 20;
-  if (const char* env = getenv("BGS_CLIP_FUSE")) e->clip_fuse = atoi(env) != 0;
-  if (const char* env = getenv("BGS_DEBUG_POISON")) e->poison = atoi(env) != 0;
-  if (const char* env = getenv("BGS_HOST_REGISTER")) e->host_register = atoi(env) & 7;
+  if (const char* env = getenv("BGS_KDE_TRIPS")) e->knob.kde_count_trips = atoi(env) != 0;
+  if (const char* env = getenv("BGS_MOG2_COMPLETE")) e->knob.mog2_complete = atoi(env) != 0;
+  if (const char* env = getenv("BGS_LB_PX")) e->knob.lb_px = atoi(env) == 2 ? 2 : 1;
+  if (const char* env = getenv("BGS_VU_SPARSE")) e->knob.vu_sparse = std::min(std::max(atoi(env), 0), 2);
+  if (const char* env = getenv("BGS_XCD_SWIZZLE")) e->knob.xcd_swizzle = atoi(env);
+  if (const char* env = getenv("BGS_MOG2_SPARSE")) e->knob.mog2_sparse = atoi(env);
+  if (const char* env = getenv("BGS_MODEL_CHUNK_MB")) e->knob.model_chunk_mb = atoi(env);
+  if (const char* env = getenv("BGS_MODEL_CHUNK_MIN_MB")) e->knob.model_chunk_min_bytes = (size_t)std::max(atoi(env), 0) << 20;
+  if (const char* env = getenv("BGS_CLIP_FUSE")) e->knob.clip_fuse = atoi(env) != 0;
+  if (const char* env = getenv("BGS_DEBUG_POISON")) e->knob.poison = atoi(env) != 0;
+  if (const char* env = getenv("BGS_HOST_REGISTER")) e->knob.host_register = atoi(env) & 7;
   *out = e;
   return BGS_OK;
 }
@@ -1028,24 +1028,24 @@ int bgs_set_option(bgs_engine* e, int option, int64_t value) {
     case 1: e->borrow = value != 0; return BGS_OK;
     case 2:  // round-2 A/B knobs (pixels per lane, planar layout): accepted and ignored since the slot layout of round 3
     case 3: return BGS_OK;
-    case 4: e->xcd_swizzle = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 2); return BGS_OK;
-    case 6: e->mog2_sparse = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 4); return BGS_OK;
-    case 7: e->clip_fuse = value != 0; return BGS_OK;
+    case 4: e->knob.xcd_swizzle = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 2); return BGS_OK;
+    case 6: e->knob.mog2_sparse = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 4); return BGS_OK;
+    case 7: e->knob.clip_fuse = value != 0; return BGS_OK;
     case 8:
       if (hipSetDevice(e->device) == hipSuccess && e->stream) (void)hipStreamSynchronize(e->stream);
       (void)hipDeviceSynchronize();
       for (size_t i = 0; i < e->pin.size(); ++i)
         if (!((value >> (i % 3)) & 1) && e->pin[i].pinned) (void)hipHostUnregister(const_cast<void*>(e->pin[i].ptr)), e->pin[i] = bgs_engine::HostPin();
-      e->host_register = (int)(value & 7);
+      e->knob.host_register = (int)(value & 7);
       return BGS_OK;
     case 5: return BGS_OK;  // BGS_OPT_PLACEMENT_PROBE of rounds 1-2: accepted and ignored (placement is deterministic since round 3: model_allocate)
     case 9:
       if (e->n) return fail(BGS_ERR_INVALID, "the model is allocated when the geometry is set");
-      e->model_chunk_mb = (int)std::max<int64_t>(value, 0);
+      e->knob.model_chunk_mb = (int)std::max<int64_t>(value, 0);
       return BGS_OK;
     case 10:
       if (e->n) return fail(BGS_ERR_INVALID, "the model is allocated when the geometry is set");
-      e->model_chunk_min_bytes = (size_t)std::max<int64_t>(value, 0) << 20;
+      e->knob.model_chunk_min_bytes = (size_t)std::max<int64_t>(value, 0) << 20;
       return BGS_OK;
     default: return fail(BGS_ERR_INVALID, "unknown option %d", option);
   }
@@ -1329,15 +1329,11 @@ int64_t bgs_get_state(bgs_engine* e, int stream, const char* plane, void* dst, s
     for (size_t i = 0; i < e->pin.size(); ++i) rec[i % 3] += e->pin[i].pinned, rec[3 + i % 3] += e->pin[i].refused;  // per role: input, mask, background
     rec[6] = (double)e->diag_reg_calls, rec[7] = e->diag_reg_ms, rec[8] = (double)e->diag_unreg_calls, rec[9] = (double)e->diag_frames;
     rec[10] = (double)e->diag_h2d_bytes, rec[11] = (double)e->diag_d2h_bytes, rec[12] = e->diag_stage_in_ms, rec[13] = e->diag_stage_out_ms, rec[14] = (double)e->arenas.size();
-    if (cap < sizeof(rec)) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
-    memcpy(dst, rec, sizeof(rec));
-    return (int64_t)sizeof(rec);
+    return copy_host(plane, dst, cap, rec, sizeof(rec));
   }
   if (!strcmp(plane, "placement")) {  // diagnostics: [0] chunk size in MiB of the chunked model (0: one plain allocation), [1] number of chunks
     float rec[2] = {e->vmm.base ? (float)(e->vmm.chunk >> 20) : 0.f, (float)e->vmm.handles.size()};
-    if (cap < sizeof(rec)) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
-    memcpy(dst, rec, sizeof(rec));
-    return (int64_t)sizeof(rec);
+    return copy_host(plane, dst, cap, rec, sizeof(rec));
   }
   return e->fam->get_state(e, stream, plane, dst, cap);
 }
@@ -1356,7 +1352,7 @@ int bgs_reset_stream(bgs_engine* e, int stream) {
   if (!e) return fail(BGS_ERR_INVALID, "engine is NULL");
   if (stream < 0 || stream >= e->S) return fail(BGS_ERR_INVALID, "stream %d outside 0..%d", stream, e->S - 1);
   e->seen[stream] = 0, e->counter[stream] = 0, e->last_flags[stream] = 0;
-  if (e->fam->reset_stream) e->fam->reset_stream(e, stream);
+  if (e->model && e->fam->reset_stream) e->fam->reset_stream(e, stream);
   if (e->last_fg_stream == stream) e->last_fg_stream = -1;
   return BGS_OK;
 }

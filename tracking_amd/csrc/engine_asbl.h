@@ -1,47 +1,52 @@
 // engine_asbl.h — host side of AdaptiveSelectiveBackgroundLearning (BGS_ASBL; kernels in kernel_stencil.h, the gray kernel and its
 // launch macro in kernel_pointwise.h / engine_pointwise.h).  Included by bgs_hip.hip inside its anonymous namespace.
-// State: a ping-pong pair of gray backgrounds (the 3x3 median reads neighbours' OLD background), e->flip says which one is current.
+
+// a ping-pong pair of gray backgrounds [S][n] (the 3x3 median reads neighbours' OLD background), which of them is current per stream,
+// and the two tables of kAsblLutRows rows (learning then detection phase) with the alphas they were built for
+struct AsblState : FamilyState {
+  DevPtr<uint8_t> bg[2], lut;
+  std::vector<uint8_t> flip;
+  double lut_alpha[2] = {0, 0};
+  bool lut_valid = false;
+};
+AsblState& asbl_of(const bgs_engine* e) { return state_of<AsblState>(e); }
 
 // ASBL's two tables (learning / detection phase), same rules as abl_build_lut
 int asbl_build_lut(bgs_engine* e) {
+  AsblState& st = asbl_of(e);
   const size_t one = (size_t)bgs::kAsblLutRows * 256;
-  if (!e->abl_lut) HIP_TRY(hipMalloc((void**)&e->abl_lut, 2 * one));
+  if (!st.lut) HIP_TRY(hipMalloc((void**)&st.lut.p, 2 * one));
   const bgs_params& p = e->p;
   for (int learn = 1; learn >= 0; --learn)
-    hipLaunchKernelGGL(bgs::asbl_lut_kernel, dim3(bgs::kAsblLutRows), dim3(bgs::kBlock), 0, e->stream, e->abl_lut + (learn ? 0 : one), learn, p.alpha_learn, 1 - p.alpha_learn,
+    hipLaunchKernelGGL(bgs::asbl_lut_kernel, dim3(bgs::kAsblLutRows), dim3(bgs::kBlock), 0, e->stream, st.lut + (learn ? 0 : one), learn, p.alpha_learn, 1 - p.alpha_learn,
                        p.alpha_detection, 1 - p.alpha_detection);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->stream));
-  e->asbl_lut_alpha[0] = p.alpha_learn, e->asbl_lut_alpha[1] = p.alpha_detection, e->abl_lut_valid = true;
+  st.lut_alpha[0] = p.alpha_learn, st.lut_alpha[1] = p.alpha_detection, st.lut_valid = true;
   return BGS_OK;
 }
 
 int asbl_allocate(bgs_engine* e) {
-  e->state_ch = 1;
-  DMALLOC(e->bgstate, e->n * e->S);
-  DMALLOC(e->bgstate2, e->n * e->S);
-  cu_count(e);
+  AsblState& st = make_state<AsblState>(e);
+  for (auto& b : st.bg) DMALLOC(b, e->n * e->S);
+  st.flip.assign(e->S, 0);
   return asbl_build_lut(e);
-}
-
-void asbl_release(bgs_engine* e) {
-  dfree(e->bgstate), dfree(e->bgstate2), dfree(e->abl_lut);
-  e->abl_lut_valid = false;
 }
 
 uint64_t asbl_key(const bgs_engine* e, int i) {
   const bgs_params& p = e->p;
-  return (uint64_t)(e->seen[i] == 0) | (uint64_t)e->flip[i] << 1 | (uint64_t)((p.learning_frames > 0 && e->counter[i] <= p.learning_frames) ? 4 : 0);
+  return (uint64_t)(e->seen[i] == 0) | (uint64_t)asbl_of(e).flip[i] << 1 | (uint64_t)((p.learning_frames > 0 && e->counter[i] <= p.learning_frames) ? 4 : 0);
 }
 
 int asbl_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
   const bgs_params& p = e->p;
   const int C = e->ch;
   const size_t npix = e->n * count, off = e->n * first;
-  const int cur = e->flip[first];
+  AsblState& st = asbl_of(e);
+  const int cur = st.flip[first];
   for (int i = first; i < first + count; ++i)
-    if (e->flip[i] != cur) return fail(BGS_ERR_INVALID, "streams %d and %d are not in lock-step", first, i);
-  uint8_t* bufs[2] = {e->bgstate, e->bgstate2};
+    if (st.flip[i] != cur) return fail(BGS_ERR_INVALID, "streams %d and %d are not in lock-step", first, i);
+  uint8_t* bufs[2] = {st.bg[0], st.bg[1]};
   if (e->seen[first] == 0) {  // img_input(gray).copyTo(img_background): a frame of threshold -1 ... simplest exact way is a tiny gray kernel
     bgs::FrameArgs a{};  // LAUNCH_FRAME_KERNEL reads `a`
     a.cur = d_frames, a.fg = bufs[cur] + off, a.npix = npix, a.enable_thr = 0;
@@ -68,7 +73,7 @@ int asbl_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8
       const size_t nstrips = (size_t)count * nsx * ((e->rows + R - 1) / R), per_wg = bgs::kAsbl2Block / bgs::kWave;
       if (nstrips >= (1u << 31)) return fail(BGS_ERR_UNSUPPORTED, "AdaptiveSelectiveBackgroundLearning: launch too large");
       const dim3 grid((unsigned)std::min<size_t>((nstrips + per_wg - 1) / per_wg, (size_t)2 * e->n_cu));
-      const uint8_t* lut = e->abl_lut + (q.learn ? 0 : (size_t)bgs::kAsblLutRows * 256);
+      const uint8_t* lut = st.lut + (q.learn ? 0 : (size_t)bgs::kAsblLutRows * 256);
       if (C == 3)
         hipLaunchKernelGGL((bgs::asbl_stream_kernel<3>), grid, dim3(bgs::kAsbl2Block), 0, s, q, lut, count, R);
       else
@@ -86,7 +91,7 @@ int asbl_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8
     hipLaunchKernelGGL(bgs::mask_pack_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, (const uint8_t*)d_fg, d_bits, npix);
   }
   for (int i = first; i < first + count; ++i) {
-    e->flip[i] = (uint8_t)(cur ^ 1);
+    st.flip[i] = (uint8_t)(cur ^ 1);
     if (q.learn) e->counter[i]++;
   }
   *flags = BGS_FG_VALID | BGS_BG_VALID;
@@ -94,19 +99,20 @@ int asbl_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8
 }
 
 int64_t asbl_get_state(bgs_engine* e, int stream, const char* plane, void* dst, size_t cap) {
-  if (!strcmp(plane, "bg")) return copy_plane(plane, dst, cap, (e->flip[stream] ? e->bgstate2 : e->bgstate) + e->n * stream, e->n);
+  if (!strcmp(plane, "bg")) return copy_plane(plane, dst, cap, asbl_of(e).bg[asbl_of(e).flip[stream]] + e->n * stream, e->n);
   return unknown_plane(e, plane);
 }
 
 int asbl_apply_params(bgs_engine* e) {
-  if (e->abl_lut_valid && e->p.alpha_learn == e->asbl_lut_alpha[0] && e->p.alpha_detection == e->asbl_lut_alpha[1]) return BGS_OK;
+  const AsblState& st = asbl_of(e);
+  if (st.lut_valid && e->p.alpha_learn == st.lut_alpha[0] && e->p.alpha_detection == st.lut_alpha[1]) return BGS_OK;
   if (hipSetDevice(e->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(BGS_ERR_HIP, "device sync failed");
   return asbl_build_lut(e);
 }
 
 constexpr Family kAsbl = [] {
   Family f{};
-  f.allocate = asbl_allocate, f.release = asbl_release, f.key = asbl_key, f.run = asbl_run, f.get_state = asbl_get_state;
+  f.allocate = asbl_allocate, f.key = asbl_key, f.run = asbl_run, f.get_state = asbl_get_state;
   f.apply_params = asbl_apply_params, f.needs_byte_mask = always, f.bg_channels = 1;
   return f;
 }();

@@ -1,6 +1,11 @@
 // engine_dp.h — host side of the package_bgs/dp/ models (kernel_dp.h); included inside bgs_hip.hip's anonymous namespace.
-// State: `dp_planes` float planes, tiled over the global pixel index (kernel_dp.h), plus e->bgstate (mode count per pixel,
-// or the AdaptiveMedian byte image).
+
+struct DpState : FamilyState {
+  DevPtr<float> planes;     // dp_planes_of() float planes, tiled over the global pixel index (kernel_dp.h); none for AdaptiveMedian
+  DevPtr<uint8_t> nmodes;   // the GMMs' mode count per pixel [S][n]
+  DevPtr<uint8_t> median;   // AdaptiveMedian's image [S][n*3]
+};
+DpState& dp_of(const bgs_engine* e) { return state_of<DpState>(e); }
 
 int dp_planes_of(const bgs_engine* e) {
   switch (e->algo) {
@@ -55,20 +60,18 @@ int dp_allocate(bgs_engine* e) {
   if (e->ch != 3) return fail(BGS_ERR_UNSUPPORTED, "the dp/ models read RgbImage pixels: 3-channel frames only (dp/Image.h:257-265)");
   const size_t P = e->n * e->S;
   const int planes = dp_planes_of(e);
-  e->state_ch = dp_is_gmm(e) ? 1 : e->algo == BGS_DP_ADAPTIVE_MEDIAN ? 3 : 0;  // bgstate = modes per pixel / the median image
-  if (e->state_ch) DMALLOC(e->bgstate, P * e->state_ch);
+  DpState& st = make_state<DpState>(e);
+  if (dp_is_gmm(e)) DMALLOC(st.nmodes, P);
+  if (e->algo == BGS_DP_ADAPTIVE_MEDIAN) DMALLOC(st.median, P * 3);
   if (planes) {
     const size_t tiles = (P + bgs::kDpTile - 1) / bgs::kDpTile, bytes = tiles * planes * bgs::kDpTile * sizeof(float);
-    if (!e->stream) HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    int rc = model_allocate(e, (void**)&e->dp_state, bytes);  // chunked placement for multi-GB models (bgs_hip.hip)
+    int rc = model_allocate(e, st.planes, bytes);  // chunked placement for multi-GB models (bgs_hip.hip)
     if (rc) return rc;
   }
   // Nothing is initialised here: InitModel runs in dp_process at a stream's first frame, on the launch stream (an
   // allocation-time memset on another stream is not ordered before a kernel on the caller's / a non-blocking stream).
   return BGS_OK;
 }
-
-void dp_release(bgs_engine* e) { dfree(e->dp_state), dfree(e->bgstate); }
 
 uint64_t dp_key(const bgs_engine* e, int i) {
   const int64_t t = e->seen[i];
@@ -81,21 +84,22 @@ uint64_t dp_key(const bgs_engine* e, int i) {
 // slab: pixels from one frame of a clip to the next (a single frame: the run is the whole slab)
 int dp_process(bgs_engine* e, int first, int count, int frames, size_t slab, const uint8_t* d_frames, uint8_t* d_fg, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
   const bgs_params& p = e->p;
+  const DpState& st = dp_of(e);
   const int64_t t = e->seen[first];
   bgs::DpArgs a{};
   a.frames = frames, a.frame_stride = slab * 3, a.fg_stride = slab, a.bits_stride = slab / 64;
-  a.frame = d_frames, a.state = e->dp_state, a.bstate = e->bgstate, a.fg = d_fg, a.fg_bits = d_bits;
+  a.frame = d_frames, a.state = st.planes, a.bstate = dp_is_gmm(e) ? st.nmodes : st.median, a.fg = d_fg, a.fg_bits = d_bits;
   a.n = e->n, a.npix = e->n * count, a.first = first;
   dp_thresholds(e->algo, p.dp_threshold, &a.low, &a.high);  // HighThreshold = 2*LowThreshold, e.g. DPZivkovicAGMMBGS.cpp:58
   a.alpha = p.dp_alpha;
-  a.update = 0, a.xcd_swizzle = e->xcd_swizzle;
+  a.update = 0, a.xcd_swizzle = e->knob.xcd_swizzle;
   const unsigned blocks = blocks_for(a.npix);
   if (t == 0 && (e->algo == BGS_DP_ZIVKOVIC_AGMM || e->algo == BGS_DP_GRIMSON_GMM))  // InitModel: all modes and counts 0
     hipLaunchKernelGGL(bgs::dp_gmm_clear_kernel, dim3(blocks), dim3(bgs::kBlock), 0, s, a, dp_planes_of(e));
   if (t == 0 && (e->algo == BGS_DP_WREN_GA || e->algo == BGS_DP_MEAN))  // InitModel from the first frame
     hipLaunchKernelGGL(bgs::dp_init_kernel, dim3(blocks), dim3(bgs::kBlock), 0, s, a, e->algo == BGS_DP_WREN_GA ? 4 : 3, 36.0f);
   if (t == 0 && e->algo == BGS_DP_ADAPTIVE_MEDIAN)
-    HIP_TRY(hipMemcpyAsync(e->bgstate + (size_t)first * e->n * 3, d_frames, a.npix * 3, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(st.median + (size_t)first * e->n * 3, d_frames, a.npix * 3, hipMemcpyDeviceToDevice, s));
   switch (e->algo) {
     case BGS_DP_ZIVKOVIC_AGMM: {
       Timed tm(e, s, "dp_gmm_kernel");
@@ -120,7 +124,7 @@ int dp_process(bgs_engine* e, int first, int count, int frames, size_t slab, con
     default: {
       a.update = (t % p.dp_sampling_rate) == 1;  // AdaptiveMedianBGS.cpp:60
       Timed tm(e, s, "dp_median_kernel");
-      const uint8_t* med0 = e->bgstate + (size_t)first * e->n * 3;
+      const uint8_t* med0 = st.median + (size_t)first * e->n * 3;
       if (a.npix % 4 == 0 && aligned(d_frames, 4) && aligned(med0, 4) && (!d_fg || aligned(d_fg, 4)))
         hipLaunchKernelGGL((bgs::dp_median_kernel<4>), dim3(blocks_for(a.npix / 4)), dim3(bgs::kBlock), 0, s, a);
       else
@@ -147,7 +151,7 @@ int64_t dp_export_planes(bgs_engine* e, int stream, int planes, void* dst, size_
   if (cap < (size_t)planes * n * 4) return fail(BGS_ERR_STATE, "buffer too small for %d planes", planes);
   const size_t t0 = g0 / T, t1 = (g0 + n - 1) / T + 1, TF = (size_t)planes * T;
   std::vector<float> tiles((t1 - t0) * TF);
-  if (d2h_staged(tiles.data(), e->dp_state + t0 * TF, tiles.size() * 4) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
+  if (fetch(tiles.data(), dp_of(e).planes + t0 * TF, tiles.size() * 4)) return BGS_ERR_HIP;
   for (int q = 0; q < planes; ++q)
     for (size_t i = 0; i < n; ++i) {
       const size_t g = g0 + i;
@@ -162,8 +166,8 @@ int64_t dp_get_state(bgs_engine* e, int stream, const char* plane, void* dst, si
   const int planes = dp_planes_of(e);
   const char* fname = (e->algo == BGS_DP_WREN_GA) ? "gauss" : (e->algo == BGS_DP_MEAN) ? "mean" : "modes";
   if (planes && !strcmp(plane, fname)) return dp_export_planes(e, stream, planes, dst, cap);
-  if (e->state_ch == 1 && !strcmp(plane, "nmodes")) return copy_plane(plane, dst, cap, e->bgstate + off, n);
-  if (e->state_ch == 3 && !strcmp(plane, "median")) return copy_plane(plane, dst, cap, e->bgstate + off * 3, n * 3);
+  if (dp_is_gmm(e) && !strcmp(plane, "nmodes")) return copy_plane(plane, dst, cap, dp_of(e).nmodes + off, n);
+  if (e->algo == BGS_DP_ADAPTIVE_MEDIAN && !strcmp(plane, "median")) return copy_plane(plane, dst, cap, dp_of(e).median + off * 3, n * 3);
   return unknown_plane(e, plane);
 }
 
@@ -175,7 +179,7 @@ void dp_keep_frozen(bgs_params& p, const bgs_params& old) {
 
 constexpr Family kDp = [] {
   Family f{};
-  f.check = dp_check, f.allocate = dp_allocate, f.release = dp_release, f.key = dp_key, f.run = dp_run, f.get_state = dp_get_state;
+  f.check = dp_check, f.allocate = dp_allocate, f.key = dp_key, f.run = dp_run, f.get_state = dp_get_state;
   f.keep_frozen = dp_keep_frozen, f.clip_fused = dp_clip_fused, f.clip_fusable = dp_is_gmm;
   return f;
 }();

@@ -15,6 +15,17 @@ int dp2_check(bgs_algo algo, const bgs_params& p) {
   return BGS_OK;
 }
 
+struct PratiState : FamilyState {
+  DevPtr<uint32_t> samples, med;  // samples [S][H][n], medoid ping-pong [2][S][n]
+  DevPtr<uint16_t> dist;          // [S][H][n]
+};
+struct TexState : FamilyState {
+  DevPtr<uint32_t> r, gb;  // histogram planes [S][16][n], [S][32][n]
+  DevPtr<uint8_t> mask;    // the last frame's mask [S][n] (the transposed update gate)
+};
+PratiState& prati_of(const bgs_engine* e) { return state_of<PratiState>(e); }
+TexState& tex_of(const bgs_engine* e) { return state_of<TexState>(e); }
+
 struct PratiSched {
   int cnt, pos, par;  // samples in the buffer, the slot a full buffer replaces, which median plane is current
   bool sample, masks;
@@ -41,23 +52,18 @@ int dp2_allocate(bgs_engine* e) {
   if (n * S >= (size_t)1 << 31) return fail(BGS_ERR_INVALID, "dp: streams x pixels must stay below 2^31");
   if (e->algo == BGS_DP_PRATI_MEDIOD) {
     const size_t H = (size_t)e->p.dp_history_size;
-    DMALLOC(e->pm_samples, S * H * n * 4);
-    DMALLOC(e->pm_dist, S * H * n * 2);
-    DMALLOC(e->pm_med, 2 * S * n * 4);
+    PratiState& st = make_state<PratiState>(e);
+    DMALLOC(st.samples, S * H * n * 4);
+    DMALLOC(st.dist, S * H * n * 2);
+    DMALLOC(st.med, 2 * S * n * 4);
   } else {
-    DMALLOC(e->tex_r, S * 16 * n * 4);
-    DMALLOC(e->tex_gb, S * 32 * n * 4);
-    DMALLOC(e->tex_mask, S * n);
+    TexState& st = make_state<TexState>(e);
+    DMALLOC(st.r, S * 16 * n * 4);
+    DMALLOC(st.gb, S * 32 * n * 4);
+    DMALLOC(st.mask, S * n);
   }
   // Nothing is initialised here: a stream's first frame clears its planes on the launch stream (dp2_run)
   return BGS_OK;
-}
-
-void dp2_free(bgs_engine* e) {
-  void* dev[] = {e->pm_samples, e->pm_dist, e->pm_med, e->tex_r, e->tex_gb, e->tex_mask};
-  for (void* d : dev)
-    if (d) (void)hipFree(d);
-  e->pm_samples = nullptr, e->pm_dist = nullptr, e->pm_med = nullptr, e->tex_r = nullptr, e->tex_gb = nullptr, e->tex_mask = nullptr;
 }
 
 // One frame of DPPratiMediodBGS::process / DPTextureBGS::process for streams [first, first+count), which share dp2_key.
@@ -66,17 +72,18 @@ int dp2_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_
   const bool fresh = e->seen[first] == 0;
   if (e->algo == BGS_DP_PRATI_MEDIOD) {
     const bgs_params& p = e->p;
+    const PratiState& st = prati_of(e);
     const size_t H = (size_t)p.dp_history_size;
     if (fresh) {  // new MEDIAN_BUFFERs: empty (the planes read as 0 until filled: bgs_get_state)
-      HIP_TRY(hipMemsetAsync(e->pm_samples + first * H * n, 0, npix * H * 4, s));
-      HIP_TRY(hipMemsetAsync(e->pm_dist + first * H * n, 0, npix * H * 2, s));
-      for (int k = 0; k < 2; ++k) HIP_TRY(hipMemsetAsync(e->pm_med + k * S * n + first * n, 0, npix * 4, s));
+      HIP_TRY(hipMemsetAsync(st.samples + first * H * n, 0, npix * H * 4, s));
+      HIP_TRY(hipMemsetAsync(st.dist + first * H * n, 0, npix * H * 2, s));
+      for (int k = 0; k < 2; ++k) HIP_TRY(hipMemsetAsync(st.med + k * S * n + first * n, 0, npix * 4, s));
     }
     const PratiSched q = prati_sched(e, first);
     bgs::PratiArgs a{};
     a.cur = d_frames, a.fg = d_fg, a.fg_bits = d_bits;
-    a.samples = e->pm_samples + first * H * n, a.dist = e->pm_dist + first * H * n;
-    a.med_in = e->pm_med + q.par * S * n + first * n, a.med_out = e->pm_med + (q.par ^ 1) * S * n + first * n;
+    a.samples = st.samples + first * H * n, a.dist = st.dist + first * H * n;
+    a.med_in = st.med + q.par * S * n + first * n, a.med_out = st.med + (q.par ^ 1) * S * n + first * n;
     a.npix = (uint32_t)npix, a.n = (uint32_t)n, a.rows = e->rows, a.cols = e->cols, a.H = (int)H;
     a.cnt = q.cnt, a.pos = q.pos, a.sample = q.sample, a.masks = q.masks;
     // dist (a byte) > LowThreshold as unsigned ints, HighThreshold = 2 * LowThreshold (DPPratiMediodBGS.cpp:57-58)
@@ -85,9 +92,10 @@ int dp2_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_
     Timed tm(e, s, "prati_kernel");
     hipLaunchKernelGGL(bgs::prati_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, a);
   } else {
-    uint32_t* hr = e->tex_r + first * 16 * n;
-    uint32_t* hgb = e->tex_gb + first * 32 * n;
-    uint8_t* mask = e->tex_mask + first * n;
+    const TexState& st = tex_of(e);
+    uint32_t* hr = st.r + first * 16 * n;
+    uint32_t* hgb = st.gb + first * 32 * n;
+    uint8_t* mask = st.mask + first * n;
     if (fresh) {  // pixels outside the interior keep 0 (the reference leaves them uninitialised and never reads them)
       HIP_TRY(hipMemsetAsync(hr, 0, npix * 16 * 4, s));
       HIP_TRY(hipMemsetAsync(hgb, 0, npix * 32 * 4, s));
@@ -116,35 +124,30 @@ int dp2_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_
 int64_t dp2_get_state(bgs_engine* e, int stream, const char* plane, void* dst, size_t cap) {
   const size_t n = e->n, S = (size_t)e->S;
   if (e->algo == BGS_DP_PRATI_MEDIOD) {
+    const PratiState& st = prati_of(e);
     const size_t H = (size_t)e->p.dp_history_size;
     const PratiSched q = prati_sched(e, stream);
     if (!strcmp(plane, "count")) {
-      if (cap < 16) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
       const int64_t v[2] = {q.cnt, q.pos};
-      memcpy(dst, v, 16);
-      return 16;
+      return copy_host(plane, dst, cap, v, 16);
     }
-    if (!strcmp(plane, "dist")) {
-      if (cap < H * n * 2) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
-      if (d2h_staged(dst, e->pm_dist + (size_t)stream * H * n, H * n * 2)) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-      return (int64_t)(H * n * 2);
-    }
+    if (!strcmp(plane, "dist")) return copy_plane(plane, dst, cap, st.dist + (size_t)stream * H * n, H * n * 2);
     const bool smp = !strcmp(plane, "samples"), med = !strcmp(plane, "median");
     if (smp || med) {
       const size_t words = smp ? H * n : n;
-      if (cap < words * 3) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
+      if (cap < words * 3) return too_small(plane);
       std::vector<uint32_t> v(words);
-      const uint32_t* src = smp ? e->pm_samples + (size_t)stream * H * n : e->pm_med + (size_t)q.par * S * n + (size_t)stream * n;
-      if (d2h_staged(v.data(), src, words * 4)) return fail(BGS_ERR_HIP, "hipMemcpy failed");
+      const uint32_t* src = smp ? st.samples + (size_t)stream * H * n : st.med + (size_t)q.par * S * n + (size_t)stream * n;
+      if (fetch(v.data(), src, words * 4)) return BGS_ERR_HIP;
       for (size_t r = 0; r < words; ++r)
         for (int c = 0; c < 3; ++c) ((uint8_t*)dst)[r * 3 + c] = (uint8_t)(v[r] >> (8 * c));
       return (int64_t)(words * 3);
     }
   } else if (!strcmp(plane, "hist")) {
-    if (cap < n * 192) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
+    const TexState& st = tex_of(e);
+    if (cap < n * 192) return too_small(plane);
     std::vector<uint32_t> r(16 * n), gb(32 * n);
-    if (d2h_staged(r.data(), e->tex_r + (size_t)stream * 16 * n, r.size() * 4) || d2h_staged(gb.data(), e->tex_gb + (size_t)stream * 32 * n, gb.size() * 4))
-      return fail(BGS_ERR_HIP, "hipMemcpy failed");
+    if (fetch(r.data(), st.r + (size_t)stream * 16 * n, r.size() * 4) || fetch(gb.data(), st.gb + (size_t)stream * 32 * n, gb.size() * 4)) return BGS_ERR_HIP;
     uint8_t* o = (uint8_t*)dst;
     for (size_t i = 0; i < n; ++i)
       for (int b = 0; b < 192; ++b) {
@@ -154,7 +157,7 @@ int64_t dp2_get_state(bgs_engine* e, int stream, const char* plane, void* dst, s
       }
     return (int64_t)(n * 192);
   }
-  return fail(BGS_ERR_STATE, "unknown state plane '%s' for algorithm %d", plane, (int)e->algo);
+  return unknown_plane(e, plane);
 }
 
 // PratiMediodBGS::Initalize copies m_params once (DPPratiMediodBGS.cpp:55-64)
@@ -165,7 +168,7 @@ void prati_keep_frozen(bgs_params& p, const bgs_params& old) {
 
 constexpr Family kDpTexture = [] {
   Family f{};
-  f.check = dp2_check, f.allocate = dp2_allocate, f.release = dp2_free, f.key = dp2_key, f.run = dp2_run, f.get_state = dp2_get_state;
+  f.check = dp2_check, f.allocate = dp2_allocate, f.key = dp2_key, f.run = dp2_run, f.get_state = dp2_get_state;
   return f;
 }();
 

@@ -7,6 +7,17 @@
 // `frameNumber <= framesToLearn` is evaluated per stream and per frame, so streams of different ages share every launch (per-stream
 // bits) and raising frames_to_learn mid-run sends a detecting stream back to learning, as it would the wrapper.
 
+struct FuzzyState : FamilyState {
+  DevPtr<float> bg;      // the float BGR background [S][n][3]
+  DevPtr<float> f;       // per-frame scratch: seven planes [S][n] (gray of input and background, hs[3], integral column-major, blurred integral row-major)
+  DevPtr<float> tab;     // the LBP table
+  DevPtr<uint8_t> code, bprod;       // pi codes, scan block products
+  DevPtr<uint32_t> minmax;           // per-stream min / max keys
+  std::vector<int64_t> fn;           // frameNumber of each stream's object
+  std::vector<uint8_t> detected;     // the stream has an integral image
+};
+FuzzyState& fz_of(const bgs_engine* e) { return state_of<FuzzyState>(e); }
+
 bool is_fuzzy(bgs_algo a) { return a == BGS_FUZZY_SUGENO || a == BGS_FUZZY_CHOQUET; }
 const char* fz_name(bgs_algo a) { return a == BGS_FUZZY_SUGENO ? "FuzzySugenoIntegral" : "FuzzyChoquetIntegral"; }
 
@@ -55,30 +66,25 @@ int fz_allocate(bgs_engine* e) {
   if (rc) return rc;
   const size_t n = e->n, S = (size_t)e->S, nb = (n + bgs::kFzScan - 1) / bgs::kFzScan;
   if (n * S * 3 >= (size_t)1 << 31) return fail(BGS_ERR_INVALID, "%s: streams x pixels x 3 must stay below 2^31", fz_name(e->algo));
-  DMALLOC(e->fz_bg, S * n * 3 * sizeof(float));
-  DMALLOC(e->fz_f, S * n * 7 * sizeof(float));  // gray_in, gray_bg, hs[3], iq, I
-  DMALLOC(e->fz_code, S * n);
-  DMALLOC(e->fz_bprod, S * nb);
-  DMALLOC(e->fz_minmax, S * 2 * sizeof(uint32_t));
-  DMALLOC(e->fz_tab, 264 * sizeof(float));
+  FuzzyState& st = make_state<FuzzyState>(e);
+  DMALLOC(st.bg, S * n * 3 * sizeof(float));
+  DMALLOC(st.f, S * n * 7 * sizeof(float));  // gray_in, gray_bg, hs[3], iq, I
+  DMALLOC(st.code, S * n);
+  DMALLOC(st.bprod, S * nb);
+  DMALLOC(st.minmax, S * 2 * sizeof(uint32_t));
+  DMALLOC(st.tab, 264 * sizeof(float));
   float tab[264];
   fz_table(tab);
-  HIP_TRY(hipMemcpyAsync(e->fz_tab, tab, sizeof(tab), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(st.tab, tab, sizeof(tab), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));  // `tab` leaves scope
-  e->fz_fn.assign(S, 0);
-  e->fz_detected.assign(S, 0);
+  st.fn.assign(S, 0);
+  st.detected.assign(S, 0);
   return BGS_OK;
-}
-
-void fz_free(bgs_engine* e) {
-  void* dev[] = {e->fz_bg, e->fz_f, e->fz_code, e->fz_bprod, e->fz_minmax, e->fz_tab};
-  for (void* d : dev)
-    if (d) (void)hipFree(d);
-  e->fz_bg = e->fz_f = e->fz_tab = nullptr, e->fz_code = e->fz_bprod = nullptr, e->fz_minmax = nullptr;
 }
 
 // One frame of Fuzzy*Integral::process for streams [first, first+count).
 int fz_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
+  FuzzyState& fs = fz_of(e);
   const size_t n = e->n, P = n * (size_t)e->S;
   const bgs_fuzzy_params& p = e->fz;
   const uint32_t nb = (uint32_t)((n + bgs::kFzScan - 1) / bgs::kFzScan);
@@ -89,10 +95,10 @@ int fz_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t
     const size_t o = (size_t)f * n, so = (size_t)(first + f) * n;
     bgs::FzArgs a{};
     a.cur = d_frames + o * 3, a.fg = d_fg ? d_fg + o : nullptr, a.bgout = d_bg ? d_bg + o * 3 : nullptr;
-    a.bg = e->fz_bg + so * 3;
-    a.gray_in = e->fz_f + so, a.gray_bg = e->fz_f + P + so, a.hs = e->fz_f + 2 * P + so, a.iq = e->fz_f + 5 * P + so, a.I = e->fz_f + 6 * P + so;
-    a.plane = P, a.code = e->fz_code + so, a.bprod = e->fz_bprod + (size_t)(first + f) * nb, a.minmax = e->fz_minmax + (size_t)(first + f) * 2;
-    a.tab = e->fz_tab, a.n = (uint32_t)n, a.nb = nb, a.W = e->cols, a.H = e->rows;
+    a.bg = fs.bg + so * 3;
+    a.gray_in = fs.f + so, a.gray_bg = fs.f + P + so, a.hs = fs.f + 2 * P + so, a.iq = fs.f + 5 * P + so, a.I = fs.f + 6 * P + so;
+    a.plane = P, a.code = fs.code + so, a.bprod = fs.bprod + (size_t)(first + f) * nb, a.minmax = fs.minmax + (size_t)(first + f) * 2;
+    a.tab = fs.tab, a.n = (uint32_t)n, a.nb = nb, a.W = e->cols, a.H = e->rows;
     a.a_learn = (float)p.alpha_learn, a.b_learn = (float)(1 - p.alpha_learn);
     a.a_update = (float)p.alpha_update, a.thr = (float)p.threshold;
     if (p.option == 1) a.G[0] = 0.4f, a.G[1] = 0.3f, a.G[2] = 0.3f;  // FuzzyMeasureG, Fuzzy*Integral.cpp:109 / :116
@@ -101,13 +107,13 @@ int fz_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t
     int detecting = 0;
     for (int i = 0; i < c; ++i) {
       const int st = first + f + i;
-      if (e->seen[st] == 0) e->fz_fn[st] = 0, e->fz_detected[st] = 0, a.init_mask |= (uint64_t)1 << i;  // a new object: img_background_f3 is empty
-      const bool learn = e->fz_fn[st] <= (int64_t)p.frames_to_learn;            // if(frameNumber <= framesToLearn)
+      if (e->seen[st] == 0) fs.fn[st] = 0, fs.detected[st] = 0, a.init_mask |= (uint64_t)1 << i;  // a new object: img_background_f3 is empty
+      const bool learn = fs.fn[st] <= (int64_t)p.frames_to_learn;            // if(frameNumber <= framesToLearn)
       if (learn) a.learn_mask |= (uint64_t)1 << i;
-      else ++detecting, e->fz_detected[st] = 1;
+      else ++detecting, fs.detected[st] = 1;
       e->last_flags[st] = learn ? 0u : (uint32_t)(BGS_FG_VALID | BGS_BG_VALID);  // per_stream_flags: learning and detecting streams share the run
       all &= e->last_flags[st];
-      e->fz_fn[st]++;
+      fs.fn[st]++;
     }
     const uint32_t npix = (uint32_t)(n * c);
     Timed tm(e, s, detecting ? "fuzzy_frame (prep, pixel, scan block / top / apply, median, update)" : "fuzzy_prep_kernel (learning)");
@@ -129,45 +135,30 @@ int fz_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t
 
 // bgs_get_state planes (include/bgs_hip.h)
 int64_t fz_get_state(bgs_engine* e, int stream, const char* plane, void* dst, size_t cap) {
+  const FuzzyState& st = fz_of(e);
   const size_t n = e->n, P = n * (size_t)e->S;
-  auto need = [&](size_t bytes) { return cap < bytes ? fail(BGS_ERR_STATE, "buffer too small for plane %s", plane) : 0; };
   if (!strcmp(plane, "count")) {
-    if (need(8)) return BGS_ERR_STATE;
-    const int64_t v = e->seen[stream] == 0 ? 0 : e->fz_fn[stream];
-    memcpy(dst, &v, 8);
-    return 8;
+    const int64_t v = e->seen[stream] == 0 ? 0 : st.fn[stream];
+    return copy_host(plane, dst, cap, &v, 8);
   }
   const bool bgp = !strcmp(plane, "background"), ip = !strcmp(plane, "integral"), mp = !strcmp(plane, "minmax");
-  if (!bgp && !ip && !mp) return fail(BGS_ERR_STATE, "unknown state plane '%s' for algorithm %d", plane, (int)e->algo);
+  if (!bgp && !ip && !mp) return unknown_plane(e, plane);
   if (e->seen[stream] == 0) return fail(BGS_ERR_STATE, "stream %d has no background yet", stream);
-  if ((ip || mp) && !e->fz_detected[stream]) return fail(BGS_ERR_STATE, "stream %d has not detected yet: no integral image", stream);
-  if (bgp) {
-    if (need(n * 12)) return BGS_ERR_STATE;
-    if (d2h_staged(dst, e->fz_bg + (size_t)stream * n * 3, n * 12)) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-    return (int64_t)(n * 12);
-  }
-  if (ip) {
-    if (need(n * 4)) return BGS_ERR_STATE;
-    if (d2h_staged(dst, e->fz_f + 6 * P + (size_t)stream * n, n * 4)) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-    return (int64_t)(n * 4);
-  }
-  if (need(8)) return BGS_ERR_STATE;
+  if ((ip || mp) && !st.detected[stream]) return fail(BGS_ERR_STATE, "stream %d has not detected yet: no integral image", stream);
+  if (bgp) return copy_plane(plane, dst, cap, st.bg + (size_t)stream * n * 3, n * 12);
+  if (ip) return copy_plane(plane, dst, cap, st.f + 6 * P + (size_t)stream * n, n * 4);
   uint32_t k[2];
-  if (d2h_staged(k, e->fz_minmax + (size_t)stream * 2, 8)) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-  for (int i = 0; i < 2; ++i) {
-    const uint32_t b = k[i] ^ ((k[i] >> 31) ? 0x80000000u : 0xffffffffu);
-    memcpy((char*)dst + 4 * i, &b, 4);
-  }
-  return 8;
+  if (cap < 8) return too_small(plane);
+  if (fetch(k, st.minmax + (size_t)stream * 2, 8)) return BGS_ERR_HIP;
+  for (uint32_t& b : k) b ^= (b >> 31) ? 0x80000000u : 0xffffffffu;
+  return copy_host(plane, dst, cap, k, 8);
 }
 
-void fz_reset_stream(bgs_engine* e, int stream) {
-  if (!e->fz_fn.empty()) e->fz_fn[stream] = 0, e->fz_detected[stream] = 0;
-}
+void fz_reset_stream(bgs_engine* e, int stream) { fz_of(e).fn[stream] = 0, fz_of(e).detected[stream] = 0; }
 
 constexpr Family kFuzzy = [] {
   Family f{};
-  f.check_geometry = fz_check_geometry, f.allocate = fz_allocate, f.release = fz_free, f.key = fz_key, f.run = fz_run, f.get_state = fz_get_state;
+  f.check_geometry = fz_check_geometry, f.allocate = fz_allocate, f.key = fz_key, f.run = fz_run, f.get_state = fz_get_state;
   f.reset_stream = fz_reset_stream, f.needs_byte_mask = always, f.per_stream_flags = true;
   return f;
 }();

@@ -10,6 +10,19 @@
 //         (DESIGN.md §5, quirk 2); here one per stream, restarted by bgs_reset_stream
 //   tbtop NPBGmodel::TemporalBufferTop
 
+struct KdeState : FamilyState {
+  DevPtr<uint32_t> samples, tb, meta, acc;  // stream-major planes of 4-byte records (kernel_kde.h)
+  DevPtr<double> lut;                       // the kernel table
+  DevPtr<int2> gate;                        // the colour-ratio gate
+  DevPtr<unsigned long long> trips;         // diagnostics: density-loop trips (BGS_KDE_TRIPS=1)
+  uint64_t lanes = 0;                       // lanes the counted launches covered
+  struct Stream {                           // the reference object's counters (above)
+    int64_t fn = 0, top = 0, tidx = 0, tbc = 0, tbtop = 0;
+  };
+  std::vector<Stream> of;                   // one set per stream
+};
+KdeState& kde_of(const bgs_engine* e) { return state_of<KdeState>(e); }
+
 int kde_tbl(const bgs_params& p) { return std::max(p.kde_time_window / p.kde_sequence_length, 2); }    // TemporalBufferLength
 int kde_rate(const bgs_params& p) { return std::max(p.kde_time_window / p.kde_sequence_length, 2); }   // sampling period (same expression)
 
@@ -68,41 +81,36 @@ int kde_allocate(bgs_engine* e) {
     return fail(BGS_ERR_UNSUPPORTED, "KDE colour ratios need 3-channel frames (BGR2SnGnRn reads 3 bytes per pixel of a gray frame: NPBGSubtractor.cpp:1141)");
   const size_t n = e->n, S = (size_t)e->S, SL = (size_t)p.kde_sequence_length, TBL = (size_t)kde_tbl(p);
   if (n * S >= (size_t)1 << 31) return fail(BGS_ERR_INVALID, "KDE: streams x pixels must stay below 2^31");
-  DMALLOC(e->kde_samples, S * SL * n * 4);
-  DMALLOC(e->kde_tb, S * TBL * n * 4);
-  DMALLOC(e->kde_meta, S * n * 4);
-  DMALLOC(e->kde_acc, S * n * 4);
-  DMALLOC(e->kde_lut, (size_t)bgs::kKdeBins * bgs::kKdeWidth * sizeof(double));
-  DMALLOC(e->kde_gate, 256 * sizeof(int2));
-  DMALLOC(e->kde_trips, sizeof(unsigned long long));
+  KdeState& st = make_state<KdeState>(e);
+  st.of.assign(S, KdeState::Stream());
+  DMALLOC(st.samples, S * SL * n * 4);
+  DMALLOC(st.tb, S * TBL * n * 4);
+  DMALLOC(st.meta, S * n * 4);
+  DMALLOC(st.acc, S * n * 4);
+  DMALLOC(st.lut, (size_t)bgs::kKdeBins * bgs::kKdeWidth * sizeof(double));
+  DMALLOC(st.gate, 256 * sizeof(int2));
+  DMALLOC(st.trips, sizeof(unsigned long long));
   std::vector<double> tab;
   kde_kernel_table(tab);
   int2 gate[256];
   kde_gate_table(p.kde_alpha, gate);
-  HIP_TRY(hipMemcpyAsync(e->kde_lut, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->kde_gate, gate, sizeof(gate), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemsetAsync(e->kde_trips, 0, sizeof(unsigned long long), e->stream));
+  HIP_TRY(hipMemcpyAsync(st.lut, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(st.gate, gate, sizeof(gate), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemsetAsync(st.trips, 0, sizeof(unsigned long long), e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));  // `tab` and `gate` leave scope
   return BGS_OK;
 }
 
-void kde_free(bgs_engine* e) {
-  void* dev[] = {e->kde_samples, e->kde_tb, e->kde_meta, e->kde_acc, e->kde_lut, e->kde_gate, e->kde_trips};
-  for (void* d : dev)
-    if (d) (void)hipFree(d);
-  e->kde_samples = e->kde_tb = e->kde_meta = e->kde_acc = nullptr, e->kde_lut = nullptr, e->kde_gate = nullptr, e->kde_trips = nullptr;
-}
-
 // What the next frame of stream i does: 0 learn, 1 Estimation + subtract, 2 subtract (KDE.cpp:74-88).
 int kde_phase(const bgs_engine* e, int i) {
-  const int64_t F = e->p.kde_frames_to_learn, fn = e->kde[i].fn;
+  const int64_t F = e->p.kde_frames_to_learn, fn = kde_of(e).of[i].fn;
   return fn < F ? 0 : fn == F ? 1 : 2;
 }
 
 // Everything the launch of stream i's next frame depends on (launch_key): first frame (model clear), phase, learning slot,
 // temporal-buffer top and whether this update is a sampling event.
 uint64_t kde_key(const bgs_engine* e, int i) {
-  const bgs_engine::KdeStream& k = e->kde[i];
+  const KdeState::Stream& k = kde_of(e).of[i];
   const int ph = kde_phase(e, i);
   const int64_t tidx = ph == 1 ? 0 : k.tidx;  // Estimation restarts TimeIndex
   const bool sample = ph > 0 && tidx % kde_rate(e->p) == 0 && k.tbc >= kde_tbl(e->p);
@@ -112,39 +120,40 @@ uint64_t kde_key(const bgs_engine* e, int i) {
 // One frame of KDE::process for streams [first, first+count), which share kde_key.
 int kde_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t*, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
   const bgs_params& p = e->p;
+  KdeState& st = kde_of(e);
   const size_t n = e->n, npix = n * count, SL = (size_t)p.kde_sequence_length, TBL = (size_t)kde_tbl(p);
   if (e->seen[first] == 0) {  // a new model (NPBGmodel's constructor: Sequence zero-filled); every plane cleared, run-contiguous
-    HIP_TRY(hipMemsetAsync(e->kde_samples + first * SL * n, 0, npix * SL * 4, s));
-    HIP_TRY(hipMemsetAsync(e->kde_tb + first * TBL * n, 0, npix * TBL * 4, s));
-    HIP_TRY(hipMemsetAsync(e->kde_meta + first * n, 0, npix * 4, s));
-    HIP_TRY(hipMemsetAsync(e->kde_acc + first * n, 0, npix * 4, s));
-    for (int i = first; i < first + count; ++i) e->kde[i] = bgs_engine::KdeStream();
+    HIP_TRY(hipMemsetAsync(st.samples + first * SL * n, 0, npix * SL * 4, s));
+    HIP_TRY(hipMemsetAsync(st.tb + first * TBL * n, 0, npix * TBL * 4, s));
+    HIP_TRY(hipMemsetAsync(st.meta + first * n, 0, npix * 4, s));
+    HIP_TRY(hipMemsetAsync(st.acc + first * n, 0, npix * 4, s));
+    for (int i = first; i < first + count; ++i) st.of[i] = KdeState::Stream();
   }
   bgs::KdeArgs a{};
   a.cur = d_frames, a.fg = d_fg, a.fg_bits = d_bits;
-  a.samples = e->kde_samples + first * SL * n, a.tb = e->kde_tb + first * TBL * n, a.meta = e->kde_meta + first * n, a.acc = e->kde_acc + first * n;
-  a.lut = e->kde_lut, a.gate = e->kde_gate, a.trips = e->kde_count_trips ? e->kde_trips : nullptr;
+  a.samples = st.samples + first * SL * n, a.tb = st.tb + first * TBL * n, a.meta = st.meta + first * n, a.acc = st.acc + first * n;
+  a.lut = st.lut, a.gate = st.gate, a.trips = e->knob.kde_count_trips ? st.trips.p : nullptr;
   a.npix = (uint32_t)npix, a.n = (uint32_t)n;
   a.th = p.kde_threshold, a.th_sum = p.kde_threshold * (double)SL;
   a.SL = (int)SL, a.TBL = (int)TBL, a.C = e->ch;
   a.mode = e->ch == 1 ? bgs::kKdeGray : p.kde_color_ratios ? bgs::kKdeRatios : bgs::kKdeRgb;
   a.sd_fixed = p.kde_sd_estimation ? -1 : (int)std::floor(((1.0 - 0.5) * bgs::kKdeBins) / (36.5 - 0.5));  // DEFAULTSEGMA's bin: 1
-  a.xcd_swizzle = e->xcd_swizzle >= 2;
-  const bgs_engine::KdeStream k0 = e->kde[first];
+  a.xcd_swizzle = e->knob.xcd_swizzle >= 2;
+  const KdeState::Stream k0 = st.of[first];
   const int ph = kde_phase(e, first);
   const dim3 grid(blocks_for(npix)), block(bgs::kBlock);
   *flags = 0;
   if (ph == 0) {  // AddFrame: no output (img_output untouched)
     a.top = (int)k0.top;
     hipLaunchKernelGGL(bgs::kde_learn_kernel, grid, block, 0, s, a);
-    for (int i = first; i < first + count; ++i) e->kde[i].fn++, e->kde[i].top = (e->kde[i].top + 1) % (int64_t)SL;
+    for (int i = first; i < first + count; ++i) st.of[i].fn++, st.of[i].top = (st.of[i].top + 1) % (int64_t)SL;
     return BGS_OK;
   }
   if (ph == 1) {  // Estimation
     hipLaunchKernelGGL(bgs::kde_estimate_kernel, grid, block, 0, s, a);
-    for (int i = first; i < first + count; ++i) e->kde[i].fn++, e->kde[i].tidx = 0;
+    for (int i = first; i < first + count; ++i) st.of[i].fn++, st.of[i].tidx = 0;
   }
-  const bgs_engine::KdeStream& k = e->kde[first];
+  const KdeState::Stream& k = st.of[first];
   a.update = p.kde_update_model != 0;
   a.sample = k.tidx % kde_rate(p) == 0 && k.tbc >= (int64_t)TBL;
   a.tb_top = (int)k.tbtop, a.tb_next = (int)((k.tbtop + 1) % (int64_t)TBL);
@@ -152,10 +161,10 @@ int kde_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_
     Timed tm(e, s, "kde_frame_kernel");
     hipLaunchKernelGGL(bgs::kde_frame_kernel, grid, block, 0, s, a);
   }
-  if (a.trips) e->kde_lanes += npix;
+  if (a.trips) st.lanes += npix;
   if (a.update)
     for (int i = first; i < first + count; ++i) {
-      bgs_engine::KdeStream& q = e->kde[i];
+      KdeState::Stream& q = st.of[i];
       q.tbtop = (q.tbtop + 1) % (int64_t)TBL, q.tbc++, q.tidx++;
     }
   *flags = BGS_FG_VALID;
@@ -165,44 +174,32 @@ int kde_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_
 // bgs_get_state planes: "samples" u8 [SL][n][C] in slot order, "sd_bins" u8 [n][C], "qtop" u8 [n], "acc" u32 [n];
 // diagnostics "trips": u64 {density-loop trips, lanes} summed over every frame launch since creation (BGS_KDE_TRIPS=1).
 int64_t kde_get_state(bgs_engine* e, int stream, const char* plane, void* dst, size_t cap) {
-  const bgs_params& p = e->p;
-  const size_t n = e->n, C = (size_t)e->ch, SL = (size_t)p.kde_sequence_length;
-  auto fetch = [&](const uint32_t* src, size_t words, std::vector<uint32_t>& v) -> int {
-    v.resize(words);
-    return d2h_staged(v.data(), src, words * 4);
-  };
-  std::vector<uint32_t> v;
-  if (!strcmp(plane, "samples")) {
-    if (cap < SL * n * C) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
-    if (fetch(e->kde_samples + (size_t)stream * SL * n, SL * n, v)) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-    for (size_t r = 0; r < SL * n; ++r)
-      for (size_t c = 0; c < C; ++c) ((uint8_t*)dst)[r * C + c] = (uint8_t)(v[r] >> (8 * c));
-    return (int64_t)(SL * n * C);
-  }
-  const bool sd = !strcmp(plane, "sd_bins"), qt = !strcmp(plane, "qtop"), acc = !strcmp(plane, "acc");
-  if (sd || qt || acc) {
-    const size_t need = sd ? n * C : qt ? n : n * 4;
-    if (cap < need) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
-    if (fetch((acc ? e->kde_acc : e->kde_meta) + (size_t)stream * n, n, v)) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-    for (size_t i = 0; i < n; ++i) {
-      if (acc) ((uint32_t*)dst)[i] = v[i];
-      if (qt) ((uint8_t*)dst)[i] = (uint8_t)(v[i] >> 24);
-      if (sd)
-        for (size_t c = 0; c < C; ++c) ((uint8_t*)dst)[i * C + c] = (uint8_t)(v[i] >> (8 * c));
+  const KdeState& st = kde_of(e);
+  const size_t n = e->n, C = (size_t)e->ch, SL = (size_t)e->p.kde_sequence_length;
+  const bool smp = !strcmp(plane, "samples"), sd = !strcmp(plane, "sd_bins"), qt = !strcmp(plane, "qtop");
+  if (!strcmp(plane, "acc")) return copy_plane(plane, dst, cap, st.acc + (size_t)stream * n, n * 4);
+  if (smp || sd || qt) {  // 4-byte records on the device, bytes for the caller
+    const size_t words = smp ? SL * n : n, need = qt ? n : words * C;
+    if (cap < need) return too_small(plane);
+    std::vector<uint32_t> v(words);
+    if (fetch(v.data(), (smp ? st.samples + (size_t)stream * SL * n : st.meta + (size_t)stream * n), words * 4)) return BGS_ERR_HIP;
+    for (size_t r = 0; r < words; ++r) {
+      if (qt) ((uint8_t*)dst)[r] = (uint8_t)(v[r] >> 24);
+      else
+        for (size_t c = 0; c < C; ++c) ((uint8_t*)dst)[r * C + c] = (uint8_t)(v[r] >> (8 * c));
     }
     return (int64_t)need;
   }
   if (!strcmp(plane, "trips")) {
-    uint64_t rec[2] = {0, e->kde_lanes};
-    if (cap < sizeof(rec)) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
-    if (d2h_staged(rec, e->kde_trips, 8)) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-    memcpy(dst, rec, sizeof(rec));
-    return (int64_t)sizeof(rec);
+    uint64_t rec[2] = {0, st.lanes};
+    if (cap < sizeof(rec)) return too_small(plane);
+    if (fetch(rec, st.trips, 8)) return BGS_ERR_HIP;
+    return copy_host(plane, dst, cap, rec, sizeof(rec));
   }
-  return fail(BGS_ERR_STATE, "unknown state plane '%s' for algorithm %d", plane, (int)e->algo);
+  return unknown_plane(e, plane);
 }
 
-void kde_reset_stream(bgs_engine* e, int stream) { e->kde[stream] = bgs_engine::KdeStream(); }  // sized by bgs_create, unlike lb_mk / vu_count / fz_fn (sized by allocate): no guard
+void kde_reset_stream(bgs_engine* e, int stream) { kde_of(e).of[stream] = KdeState::Stream(); }
 
 // KDE.cpp:40-66: Intialize / SetThresholds once; framesToLearn is re-read every frame (and update_model is live)
 void kde_keep_frozen(bgs_params& p, const bgs_params& old) {
@@ -212,7 +209,7 @@ void kde_keep_frozen(bgs_params& p, const bgs_params& old) {
 
 constexpr Family kKde = [] {
   Family f{};
-  f.check = kde_check, f.allocate = kde_allocate, f.release = kde_free, f.key = kde_key, f.run = kde_run, f.get_state = kde_get_state;
+  f.check = kde_check, f.allocate = kde_allocate, f.key = kde_key, f.run = kde_run, f.get_state = kde_get_state;
   f.reset_stream = kde_reset_stream, f.keep_frozen = kde_keep_frozen;
   return f;
 }();

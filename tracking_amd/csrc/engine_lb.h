@@ -7,6 +7,14 @@
 // The SOMs' training counter m_K is the model object's own state (restarted by Init, advanced by Update while m_K <= m_TSteps, and
 // m_TSteps may change between frames), so it is kept per stream here and not derived from bgs_engine::seen.
 
+struct LbState : FamilyState {
+  DevPtr<double> model;  // planar doubles [S][P][n]
+  DevPtr<int32_t> k;     // MoG: modes per pixel [S][n]
+  DevPtr<uint8_t> bg;    // the SOMs' background bytes [S][n*3]
+  std::vector<int> mk;   // the SOMs' training counter m_K, one per stream
+};
+LbState& lb_of(const bgs_engine* e) { return state_of<LbState>(e); }
+
 bool is_lb_som(bgs_algo a) { return a == BGS_LB_ADAPTIVE_SOM || a == BGS_LB_FUZZY_ADAPTIVE_SOM; }
 
 const char* lb_name(bgs_algo a) {
@@ -72,24 +80,19 @@ int lb_allocate(bgs_engine* e) {
   if (e->ch != 3) return fail(BGS_ERR_UNSUPPORTED, "%s reads 3-channel frames only (BGModel::InitModel copies into an 8UC3 image, lb/BGModel.cpp:72)", lb_name(e->algo));
   const size_t n = e->n, S = (size_t)e->S;
   if (n * S >= (size_t)1 << 31) return fail(BGS_ERR_INVALID, "lb: streams x pixels must stay below 2^31");
-  int rc = model_allocate(e, (void**)&e->lb_model, S * n * lb_planes_of(e->algo) * sizeof(double));
+  LbState& st = make_state<LbState>(e);
+  int rc = model_allocate(e, st.model, S * n * lb_planes_of(e->algo) * sizeof(double));
   if (rc) return rc;
-  if (e->algo == BGS_LB_MOG) DMALLOC(e->lb_k, S * n * sizeof(int32_t));
-  if (is_lb_som(e->algo)) DMALLOC(e->lb_bg, S * n * 3);
-  e->lb_mk.assign(S, 0);
+  if (e->algo == BGS_LB_MOG) DMALLOC(st.k, S * n * sizeof(int32_t));
+  if (is_lb_som(e->algo)) DMALLOC(st.bg, S * n * 3);
+  st.mk.assign(S, 0);
   // Nothing is initialised here: a stream's first frame builds its model inside the launch (LbArgs::init)
   return BGS_OK;
 }
 
-void lb_free(bgs_engine* e) {
-  if (e->lb_model) (void)hipFree(e->lb_model);
-  if (e->lb_k) (void)hipFree(e->lb_k);
-  if (e->lb_bg) (void)hipFree(e->lb_bg);
-  e->lb_model = nullptr, e->lb_k = nullptr, e->lb_bg = nullptr;
-}
-
 // One frame of LB*::process for streams [first, first+count), which share lb_key.
 int lb_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
+  LbState& st = lb_of(e);
   const size_t n = e->n;
   const int P = lb_planes_of(e->algo);
   const LbModelParams mp = lb_model_params(e->algo, e->p);
@@ -100,8 +103,8 @@ int lb_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t
     const size_t o = (size_t)(f - first) * n;
     a.cur = d_frames + o * 3, a.fg = d_fg ? d_fg + o : nullptr, a.bg = d_bg ? d_bg + o * 3 : nullptr;
     a.fg_bits = d_bits ? d_bits + o / 64 : nullptr;
-    a.model = e->lb_model + (size_t)f * P * n;
-    a.k = e->lb_k ? e->lb_k + (size_t)f * n : nullptr, a.bgplane = e->lb_bg ? e->lb_bg + (size_t)f * n * 3 : nullptr;
+    a.model = st.model + (size_t)f * P * n;
+    a.k = st.k ? st.k + (size_t)f * n : nullptr, a.bgplane = st.bg ? st.bg + (size_t)f * n * 3 : nullptr;
     a.npix = (uint32_t)(n * c);
   };
   if (!is_lb_som(e->algo)) {
@@ -112,7 +115,7 @@ int lb_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t
       hipLaunchKernelGGL(bgs::lb_mog_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, a);
     } else {
       const bool fuzzy = e->algo == BGS_LB_FUZZY_GAUSSIAN;
-      const bool two = e->lb_px == 2 && n % 2 == 0;  // pairs of pixels never straddle two streams then, and every double2 is aligned
+      const bool two = e->knob.lb_px == 2 && n % 2 == 0;  // pairs of pixels never straddle two streams then, and every double2 is aligned
       Timed tm(e, s, fuzzy ? "lb_fuzzy_gauss_kernel" : "lb_gauss_kernel");
       if (two) {
         if (fuzzy)
@@ -132,7 +135,7 @@ int lb_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t
     std::vector<double> al(count), ep(count);
     bool same = true;
     for (int i = 0; i < count; ++i) {
-      int& mk = e->lb_mk[first + i];
+      int& mk = st.mk[first + i];
       if (a.init) mk = 0;
       if (mk <= mp.tsteps) {
         ep[i] = mp.eps1, al[i] = mp.alpha1 - (double)mk * (mp.alpha1 - mp.alpha2) / (double)mp.tsteps;
@@ -162,76 +165,49 @@ int lb_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t
 
 // bgs_get_state planes (include/bgs_hip.h), in the reference's memory order.
 int64_t lb_get_state(bgs_engine* e, int stream, const char* plane, void* dst, size_t cap) {
+  const LbState& st = lb_of(e);
   const size_t n = e->n;
   const int P = lb_planes_of(e->algo);
-  auto need = [&](size_t bytes) { return cap < bytes ? fail(BGS_ERR_STATE, "buffer too small for plane %s", plane) : 0; };
-  if (is_lb_som(e->algo) && !strcmp(plane, "count")) {
-    if (need(8)) return BGS_ERR_STATE;
-    const int64_t v = e->lb_mk[stream];
-    memcpy(dst, &v, 8);
-    return 8;
+  const bool som = is_lb_som(e->algo), mog = e->algo == BGS_LB_MOG, gauss = !som && !mog;
+  if (som && !strcmp(plane, "count")) {
+    const int64_t v = st.mk[stream];
+    return copy_host(plane, dst, cap, &v, 8);
   }
-  if (is_lb_som(e->algo) && !strcmp(plane, "bg")) {
-    if (need(n * 3)) return BGS_ERR_STATE;
-    if (d2h_staged(dst, e->lb_bg + (size_t)stream * n * 3, n * 3)) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-    return (int64_t)(n * 3);
-  }
-  std::vector<int32_t> K;
-  if (e->algo == BGS_LB_MOG) {
-    K.resize(n);
-    if (d2h_staged(K.data(), e->lb_k + (size_t)stream * n, n * 4)) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-    if (!strcmp(plane, "k")) {
-      if (need(n * 4)) return BGS_ERR_STATE;
-      memcpy(dst, K.data(), n * 4);
-      return (int64_t)(n * 4);
-    }
-  }
+  if (som && !strcmp(plane, "bg")) return copy_plane(plane, dst, cap, st.bg + (size_t)stream * n * 3, n * 3);
+  if (mog && !strcmp(plane, "k")) return copy_plane(plane, dst, cap, st.k + (size_t)stream * n, n * 4);
+  // the planes made from the model: doubles per pixel of the export
+  const bool mu = !strcmp(plane, "mu"), var = !strcmp(plane, "var"), w = !strcmp(plane, "w"), key = !strcmp(plane, "sortkey");
+  const size_t per = som ? (!strcmp(plane, "som") ? 27 : 0) : (mu || var) ? (mog ? 9 : 3) : (mog && (w || key)) ? 3 : 0;
+  if (!per) return unknown_plane(e, plane);
+  if (cap < n * per * 8) return too_small(plane);
+  std::vector<int32_t> K(mog ? n : 0);
+  if (mog && fetch(K.data(), st.k + (size_t)stream * n, n * 4)) return BGS_ERR_HIP;
   std::vector<double> m((size_t)P * n);
-  if (d2h_staged(m.data(), e->lb_model + (size_t)stream * P * n, m.size() * 8)) return fail(BGS_ERR_HIP, "hipMemcpy failed");
+  if (fetch(m.data(), st.model + (size_t)stream * P * n, m.size() * 8)) return BGS_ERR_HIP;
   double* o = (double*)dst;
-  if (is_lb_som(e->algo) && !strcmp(plane, "som")) {
-    if (need(n * 27 * 8)) return BGS_ERR_STATE;
-    for (size_t i = 0; i < n; ++i)
+  auto at = [&](int k, int f, size_t i) { return k < K[i] ? m[(size_t)(7 * k + f) * n + i] : 0.0; };  // MoG slots >= K: the constructor's zeros
+  for (size_t i = 0; i < n; ++i) {
+    if (som)
       for (int j = 0; j < 27; ++j) o[i * 27 + j] = m[(size_t)j * n + i];
-    return (int64_t)(n * 27 * 8);
-  }
-  const bool mu = !strcmp(plane, "mu"), var = !strcmp(plane, "var");
-  if ((e->algo == BGS_LB_SIMPLE_GAUSSIAN || e->algo == BGS_LB_FUZZY_GAUSSIAN) && (mu || var)) {
-    if (need(n * 24)) return BGS_ERR_STATE;
-    for (size_t i = 0; i < n; ++i)
+    else if (gauss)
       for (int c = 0; c < 3; ++c) o[i * 3 + c] = m[(size_t)((mu ? 0 : 3) + c) * n + i];
-    return (int64_t)(n * 24);
+    else if (mu || var)
+      for (int k = 0; k < 3; ++k)
+        for (int c = 0; c < 3; ++c) o[(i * 3 + k) * 3 + c] = at(k, (mu ? 1 : 4) + c, i);
+    else
+      for (int k = 0; k < 3; ++k) {
+        double v = at(k, 0, i);
+        if (key && k < K[i]) v = v / std::sqrt(at(k, 6, i) + at(k, 5, i) + at(k, 4, i));  // Red + Green + Blue
+        o[i * 3 + k] = v;
+      }
   }
-  if (e->algo == BGS_LB_MOG) {
-    auto at = [&](int k, int f, size_t i) { return k < K[i] ? m[(size_t)(7 * k + f) * n + i] : 0.0; };  // slots >= K: the constructor's zeros
-    if (mu || var) {
-      if (need(n * 72)) return BGS_ERR_STATE;
-      for (size_t i = 0; i < n; ++i)
-        for (int k = 0; k < 3; ++k)
-          for (int c = 0; c < 3; ++c) o[(i * 3 + k) * 3 + c] = at(k, (mu ? 1 : 4) + c, i);
-      return (int64_t)(n * 72);
-    }
-    const bool w = !strcmp(plane, "w"), key = !strcmp(plane, "sortkey");
-    if (w || key) {
-      if (need(n * 24)) return BGS_ERR_STATE;
-      for (size_t i = 0; i < n; ++i)
-        for (int k = 0; k < 3; ++k) {
-          double v = at(k, 0, i);
-          if (key && k < K[i]) v = v / std::sqrt(at(k, 6, i) + at(k, 5, i) + at(k, 4, i));  // Red + Green + Blue
-          o[i * 3 + k] = v;
-        }
-      return (int64_t)(n * 24);
-    }
-  }
-  return fail(BGS_ERR_STATE, "unknown state plane '%s' for algorithm %d", plane, (int)e->algo);
+  return (int64_t)(n * per * 8);
 }
 
-void lb_reset_stream(bgs_engine* e, int stream) {
-  if (!e->lb_mk.empty()) e->lb_mk[stream] = 0;
-}
+void lb_reset_stream(bgs_engine* e, int stream) { lb_of(e).mk[stream] = 0; }
 
 constexpr Family kLb = [] {
   Family f{};
-  f.check = lb_check, f.allocate = lb_allocate, f.release = lb_free, f.key = lb_key, f.run = lb_run, f.get_state = lb_get_state, f.reset_stream = lb_reset_stream;
+  f.check = lb_check, f.allocate = lb_allocate, f.key = lb_key, f.run = lb_run, f.get_state = lb_get_state, f.reset_stream = lb_reset_stream;
   return f;
 }();

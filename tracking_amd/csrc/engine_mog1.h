@@ -6,13 +6,16 @@ int mog1_check(bgs_algo, const bgs_params& p) {
   return BGS_OK;
 }
 
+struct Mog1State : FamilyState {
+  DevPtr<float> model;  // tiles of kMog1Tile pixels (kernel_mog1.h)
+};
+Mog1State& mog1_of(const bgs_engine* e) { return state_of<Mog1State>(e); }
+
 int mog1_allocate(bgs_engine* e) {
   const size_t tile_floats = e->ch == 3 ? bgs::mog1_tile_floats<3>() : bgs::mog1_tile_floats<1>();
   const size_t tiles = (e->n * e->S + bgs::kMog1Tile - 1) / bgs::kMog1Tile;
-  return model_allocate(e, (void**)&e->mog1_state, tiles * tile_floats * sizeof(float));
+  return model_allocate(e, make_state<Mog1State>(e).model, tiles * tile_floats * sizeof(float));
 }
-
-void mog1_release(bgs_engine* e) { dfree(e->mog1_state); }
 
 // MOG1 / MOG2: needToInitialize + the learning rate of stream i's next frame
 uint64_t mog_lr_key(const bgs_engine* e, int i, int64_t cap, int64_t mult) {
@@ -35,7 +38,7 @@ void mog1_fill_args(const bgs_engine* e, bgs::Mog1Args& m, double lr) {
   m.sk0 = C == 3 ? (float)(m.w0 / (defaultNoiseSigma * 2 * std::sqrt(3.))) : (float)(m.w0 / (defaultNoiseSigma * 2));
   m.var0 = (float)(defaultNoiseSigma * defaultNoiseSigma * 4);
   m.minVar = (float)(p.mog1_noise_sigma * p.mog1_noise_sigma);
-  m.thr = p.threshold, m.enable_thr = p.enable_threshold, m.packed = m.fg_bits != nullptr, m.xcd_swizzle = e->xcd_swizzle;
+  m.thr = p.threshold, m.enable_thr = p.enable_threshold, m.packed = m.fg_bits != nullptr, m.xcd_swizzle = e->knob.xcd_swizzle;
 }
 
 void mog1_clear(bgs_engine* e, const bgs::Mog1Args& m, hipStream_t s) {  // needToInitialize: bgmodel = zeros
@@ -52,7 +55,7 @@ int mog1_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8
   double lr = p.alpha;
   int64_t nframes = e->seen[first];
   bgs::Mog1Args m{};
-  m.state = e->mog1_state, m.state_off = e->n * first, m.npix = npix;
+  m.state = mog1_of(e).model, m.state_off = e->n * first, m.npix = npix;
   if (nframes == 0 || lr >= 1) {
     mog1_clear(e, m, s);
     nframes = 0;
@@ -79,7 +82,7 @@ int mog1_clip_fused(bgs_engine* e, int first, int count, int fuse, size_t slab, 
   const size_t npix = e->n * count, C = (size_t)e->ch;
   const int64_t seen = e->seen[first];
   bgs::Mog1ClipArgs c{};
-  c.m.state = e->mog1_state, c.m.state_off = e->n * first, c.m.npix = npix;
+  c.m.state = mog1_of(e).model, c.m.state_off = e->n * first, c.m.npix = npix;
   if (seen == 0) mog1_clear(e, c.m, s);  // needToInitialize on a stream's first frame
   c.m.frame = fr, c.m.fg = fg, c.m.fg_bits = bits;
   mog1_fill_args(e, c.m, 0.0);
@@ -111,10 +114,10 @@ int64_t mog1_get_state(bgs_engine* e, int stream, const char* plane, void* dst, 
   if (!strcmp(plane, "var")) kind = 3, nf = C;
   if (kind < 0) return unknown_plane(e, plane);
   const size_t need = (size_t)K * nf * n * 4;
-  if (cap < need) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
+  if (cap < need) return too_small(plane);
   const size_t T = bgs::kMog1Tile, TF = C == 3 ? bgs::mog1_tile_floats<3>() : bgs::mog1_tile_floats<1>(), t0 = off / T, t1 = (off + n + T - 1) / T;
   std::vector<float> tiles((t1 - t0) * TF);
-  if (d2h_staged(tiles.data(), e->mog1_state + t0 * TF, tiles.size() * 4) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
+  if (fetch(tiles.data(), mog1_of(e).model + t0 * TF, tiles.size() * 4)) return BGS_ERR_HIP;
   for (size_t i = 0; i < n; ++i) {
     const size_t sp = off + i, l = sp % T;
     const float* tb = tiles.data() + (sp / T - t0) * TF;
@@ -136,7 +139,7 @@ int64_t mog1_get_state(bgs_engine* e, int stream, const char* plane, void* dst, 
 
 constexpr Family kMog1 = [] {
   Family f{};
-  f.check = mog1_check, f.allocate = mog1_allocate, f.release = mog1_release, f.key = mog1_key, f.run = mog1_run, f.get_state = mog1_get_state;
+  f.check = mog1_check, f.allocate = mog1_allocate, f.key = mog1_key, f.run = mog1_run, f.get_state = mog1_get_state;
   f.clip_fused = mog1_clip_fused, f.clip_fusable = mog_clip_fusable;
   return f;
 }();

@@ -21,35 +21,57 @@ int mog2_check_geometry(bgs_algo, int, int, int ch) {
 // or would load (when another kernel is current, every 16th launch - every 4th of a stream's first 64 - is a filter launch for
 // that purpose).  The host never blocks: the counters come back through a pinned buffer and an event that is queried before
 // every launch; it switches at once on clear evidence, else when two samples in a row ask for the same other mode.
-void mog2_stat_read(bgs_engine* e) {
+struct Mog2State : FamilyState {
+  DevPtr<uint8_t> model;     // tiles of ranked weights + fixed-slot records + rank->slot meta words (kernel_mog2.h)
+  int sparse_now = 2;        // what auto mode currently runs
+  int sparse_want = 2;       // what the last poll asked for (a switch needs two polls in a row)
+  unsigned launches = 0;     // auto mode: per-frame launches so far (every 16th one samples)
+  DevPtr<unsigned> d_stat;   // device: {record slots sampled, modes live, records needed after the summaries}
+  // pinned copies of the counters, a ring of kStatSlots posts (one per sampling launch, each with its event): a host that runs far
+  // ahead of the device still finds the most recent sample that has COMPLETED when it looks
+  static constexpr int kStatSlots = 8;
+  unsigned* h_stat = nullptr;  // [kStatSlots][3]
+  hipEvent_t stat_ev[kStatSlots] = {nullptr};
+  bool stat_posted[kStatSlots] = {false};
+  unsigned stat_seq = 0;  // posts so far
+  ~Mog2State() override {
+    model.reset(), d_stat.reset();
+    if (h_stat) (void)hipHostFree(h_stat);
+    for (hipEvent_t ev : stat_ev)
+      if (ev) (void)hipEventDestroy(ev);
+  }
+};
+Mog2State& mog2_of(const bgs_engine* e) { return state_of<Mog2State>(e); }
+
+void mog2_stat_read(Mog2State& st) {
   // the newest post whose copy has completed; everything older is dropped with it
   int slot = -1;
-  for (unsigned back = 1; back <= (unsigned)bgs_engine::kStatSlots && back <= e->stat_seq; ++back) {
-    const int i = (int)((e->stat_seq - back) % bgs_engine::kStatSlots);
-    if (!e->stat_posted[i]) break;  // already consumed (and so is everything older)
-    if (slot < 0 && hipEventQuery(e->stat_ev[i]) == hipSuccess) slot = i;
-    if (slot >= 0) e->stat_posted[i] = false;
+  for (unsigned back = 1; back <= (unsigned)Mog2State::kStatSlots && back <= st.stat_seq; ++back) {
+    const int i = (int)((st.stat_seq - back) % Mog2State::kStatSlots);
+    if (!st.stat_posted[i]) break;  // already consumed (and so is everything older)
+    if (slot < 0 && hipEventQuery(st.stat_ev[i]) == hipSuccess) slot = i;
+    if (slot >= 0) st.stat_posted[i] = false;
   }
   if (slot < 0) return;
-  const unsigned* hs = e->h_stat + 3 * slot;
+  const unsigned* hs = st.h_stat + 3 * slot;
   const unsigned total = hs[0], live = hs[1], need = hs[2];
   if (total < 64 * 5) return;
   const float lf = (float)live / (float)total, nf = (float)need / (float)total;
   const int want = (nf < 0.5f * lf && lf - nf > 0.1f) ? 4 : lf < 0.7f ? 2 : 1;
-  const bool clear = (want == 4 && nf < 0.35f * lf) || (want != 4 && e->mog2_sparse_now == 4 && nf > 0.8f * lf);
+  const bool clear = (want == 4 && nf < 0.35f * lf) || (want != 4 && st.sparse_now == 4 && nf > 0.8f * lf);
   static const bool debug = getenv("BGS_DEBUG_STAT") != nullptr;
   if (debug)
-    fprintf(stderr, "[bgs] mog2 auto: %u record slots sampled, %.3f live, %.3f needed after the summaries -> mode %d (now %d)\n", total, lf, nf, want, e->mog2_sparse_now);
-  if (want != e->mog2_sparse_now && (clear || want == e->mog2_sparse_want)) e->mog2_sparse_now = want;
-  e->mog2_sparse_want = want;
+    fprintf(stderr, "[bgs] mog2 auto: %u record slots sampled, %.3f live, %.3f needed after the summaries -> mode %d (now %d)\n", total, lf, nf, want, st.sparse_now);
+  if (want != st.sparse_now && (clear || want == st.sparse_want)) st.sparse_now = want;
+  st.sparse_want = want;
 }
-void mog2_stat_post(bgs_engine* e, hipStream_t s) {
-  const int i = (int)(e->stat_seq % bgs_engine::kStatSlots);  // the oldest slot is reused (its event re-recorded) if nobody read it
-  (void)hipMemcpyAsync(e->h_stat + 3 * i, e->d_stat, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, s);
-  (void)hipMemsetAsync(e->d_stat, 0, 3 * sizeof(unsigned), s);
-  (void)hipEventRecord(e->stat_ev[i], s);
-  e->stat_posted[i] = true;
-  e->stat_seq++;
+void mog2_stat_post(Mog2State& st, hipStream_t s) {
+  const int i = (int)(st.stat_seq % Mog2State::kStatSlots);  // the oldest slot is reused (its event re-recorded) if nobody read it
+  (void)hipMemcpyAsync(st.h_stat + 3 * i, st.d_stat, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, s);
+  (void)hipMemsetAsync(st.d_stat, 0, 3 * sizeof(unsigned), s);
+  (void)hipEventRecord(st.stat_ev[i], s);
+  st.stat_posted[i] = true;
+  st.stat_seq++;
 }
 
 int launch_mog2(bgs_engine* e, bgs::Mog2Args& a, hipStream_t s, bool timed = true) {
@@ -57,19 +79,20 @@ int launch_mog2(bgs_engine* e, bgs::Mog2Args& a, hipStream_t s, bool timed = tru
   // shadow test only when it can change the delivered mask: not thresholded, or the threshold separates shadow from foreground
   a.shadow = p.mog2_detect_shadows && (!p.enable_threshold || ((p.mog2_shadow_value > p.threshold) != (255 > p.threshold)));
   a.want_bg = a.bgimg != nullptr, a.packed = a.fg_bits != nullptr;
-  a.xcd_swizzle = e->xcd_swizzle, a.complete = e->mog2_complete;
-  const bool autom = timed && e->mog2_sparse == 3;
-  if (autom) mog2_stat_read(e);
-  int mode = e->mog2_sparse == 3 ? e->mog2_sparse_now : e->mog2_sparse;
+  a.xcd_swizzle = e->knob.xcd_swizzle, a.complete = e->knob.mog2_complete;
+  Mog2State& st = mog2_of(e);
+  const bool autom = timed && e->knob.mog2_sparse == 3;
+  if (autom) mog2_stat_read(st);
+  int mode = e->knob.mog2_sparse == 3 ? st.sparse_now : e->knob.mog2_sparse;
   if (mode >= 4 && (a.shadow || a.want_bg)) mode = 2;  // shadow test and background image read every mode's mean: nothing to rule out
   // auto mode: the filter kernel's sampled workgroups count what each way of loading would read; when another kernel is current,
   // every 16th launch (every 4th of the first 64) goes through the filter kernel anyway so that the choice keeps following the scene
   if (autom && mode != 4) {
-    const unsigned n = e->mog2_launches++;
+    const unsigned n = st.launches++;
     if ((n & (n < 64 ? 3u : 15u)) == 0) mode = 4;
   }
   a.sparse = mode;
-  a.stat = (autom && mode == 4) ? e->d_stat : nullptr;
+  a.stat = (autom && mode == 4) ? st.d_stat.p : nullptr;
   if (a.packed && a.npix % 64) return fail(BGS_ERR_UNSUPPORTED, "packed mask needs pixels %% 64 == 0");
   Timed t(e, s, "mog2_update_kernel", timed);
   const dim3 grid(blocks_for(a.npix)), block(bgs::kBlock);  // one pixel per lane (round 2's 1 / 2 / 4 comparison: equal or better everywhere)
@@ -83,13 +106,13 @@ int launch_mog2(bgs_engine* e, bgs::Mog2Args& a, hipStream_t s, bool timed = tru
     hipLaunchKernelGGL((bgs::mog2_update_kernel<bgs::kMog2Count>), grid, block, 0, s, a);
   else
     hipLaunchKernelGGL((bgs::mog2_update_kernel<bgs::kMog2Eager>), grid, block, 0, s, a);
-  if (a.stat) mog2_stat_post(e, s);
+  if (a.stat) mog2_stat_post(st, s);
   return BGS_OK;
 }
 
 void mog2_fill_args(const bgs_engine* e, bgs::Mog2Args& m, double lr) {
   const bgs_params& p = e->p;
-  m.state = e->mog2_state;
+  m.state = mog2_of(e).model;
   m.alphaT = (float)lr, m.alpha1 = 1.f - m.alphaT, m.prune = (float)(-lr * (double)p.mog2_ct);
   m.Tb = p.mog2_var_threshold, m.TB = p.mog2_background_ratio, m.Tg = p.mog2_var_threshold_gen;
   m.varInit = p.mog2_var_init, m.varMin = p.mog2_var_min, m.varMax = p.mog2_var_max, m.tau = p.mog2_tau;
@@ -106,8 +129,8 @@ int launch_mog2_clip(bgs_engine* e, bgs::Mog2ClipArgs& c, int fuse, hipStream_t 
   bgs::Mog2Args& a = c.m;
   a.shadow = p.mog2_detect_shadows && (!p.enable_threshold || ((p.mog2_shadow_value > p.threshold) != (255 > p.threshold)));
   a.want_bg = a.bgimg != nullptr, a.packed = a.fg_bits != nullptr;
-  a.xcd_swizzle = e->xcd_swizzle, a.complete = e->mog2_complete;
-  a.sparse = e->mog2_sparse == 0 ? 0 : 1;  // clip launches load every record at once (kernel_mog2.h)
+  a.xcd_swizzle = e->knob.xcd_swizzle, a.complete = e->knob.mog2_complete;
+  a.sparse = e->knob.mog2_sparse == 0 ? 0 : 1;  // clip launches load every record at once (kernel_mog2.h)
   a.stat = nullptr;
   if (a.packed && a.npix % 64) return fail(BGS_ERR_UNSUPPORTED, "packed mask needs pixels %% 64 == 0");
   Timed t(e, s, "mog2_clip_kernel");
@@ -128,21 +151,12 @@ size_t mog2_state_bytes(const bgs_engine* e) {
 }
 
 int mog2_allocate(bgs_engine* e) {
-  const size_t bytes = mog2_state_bytes(e);
-  HIP_TRY(hipMalloc((void**)&e->d_stat, 3 * sizeof(unsigned)));
-  HIP_TRY(hipMemsetAsync(e->d_stat, 0, 3 * sizeof(unsigned), e->stream));  // ordered: allocate() drains e->stream before it returns
-  HIP_TRY(hipHostMalloc((void**)&e->h_stat, 3 * bgs_engine::kStatSlots * sizeof(unsigned), hipHostMallocDefault));
-  for (int i = 0; i < bgs_engine::kStatSlots; ++i) HIP_TRY(hipEventCreateWithFlags(&e->stat_ev[i], hipEventDisableTiming));
-  return model_allocate(e, (void**)&e->mog2_state, bytes);
-}
-
-void mog2_release(bgs_engine* e) {
-  dfree(e->mog2_state), dfree(e->d_stat);
-  if (e->h_stat) (void)hipHostFree(e->h_stat), e->h_stat = nullptr;
-  for (int i = 0; i < bgs_engine::kStatSlots; ++i) {
-    if (e->stat_ev[i]) (void)hipEventDestroy(e->stat_ev[i]), e->stat_ev[i] = nullptr;
-    e->stat_posted[i] = false;
-  }
+  Mog2State& st = make_state<Mog2State>(e);
+  HIP_TRY(hipMalloc((void**)&st.d_stat.p, 3 * sizeof(unsigned)));
+  HIP_TRY(hipMemsetAsync(st.d_stat, 0, 3 * sizeof(unsigned), e->stream));  // ordered: allocate() drains e->stream before it returns
+  HIP_TRY(hipHostMalloc((void**)&st.h_stat, 3 * Mog2State::kStatSlots * sizeof(unsigned), hipHostMallocDefault));
+  for (hipEvent_t& ev : st.stat_ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  return model_allocate(e, st.model, mog2_state_bytes(e));
 }
 
 uint64_t mog2_key(const bgs_engine* e, int i) { return mog_lr_key(e, i, e->p.mog2_history, 2); }
@@ -203,11 +217,11 @@ int64_t mog2_get_state(bgs_engine* e, int stream, const char* plane, void* dst, 
   // device layout (kernel_mog2.h): weights by rank, {var, mean} records in fixed slots, meta = rank -> slot.  Exported in the
   // reference's array order (rank); entries past a pixel's mode count are zero, as in the reference's zero-initialised bgmodel.
   const size_t need = nm ? n : (size_t)np * n * 4;
-  if (cap < need) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
+  if (cap < need) return too_small(plane);
   const size_t T = bgs::kMog2Tile, TB = bgs::kMog2TileBytes;
   const size_t t0 = off / T, t1 = (off + n + T - 1) / T;
   std::vector<uint8_t> tiles((t1 - t0) * TB);
-  if (d2h_staged(tiles.data(), e->mog2_state + t0 * TB, tiles.size()) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
+  if (fetch(tiles.data(), mog2_of(e).model + t0 * TB, tiles.size())) return BGS_ERR_HIP;
   for (size_t i = 0; i < n; ++i) {
     const size_t sp = off + i, in = sp % T;
     const uint8_t* tb = tiles.data() + (sp / T - t0) * TB;
@@ -234,7 +248,7 @@ int64_t mog2_get_state(bgs_engine* e, int stream, const char* plane, void* dst, 
 
 constexpr Family kMog2 = [] {
   Family f{};
-  f.check = mog2_check, f.check_geometry = mog2_check_geometry, f.allocate = mog2_allocate, f.release = mog2_release, f.key = mog2_key, f.run = mog2_run;
+  f.check = mog2_check, f.check_geometry = mog2_check_geometry, f.allocate = mog2_allocate, f.key = mog2_key, f.run = mog2_run;
   f.get_state = mog2_get_state, f.clip_fused = mog2_clip_fused, f.clip_fusable = mog_clip_fusable;
   return f;
 }();

@@ -50,20 +50,17 @@ bgs::FrameArgs frame_args(const bgs_engine* e, int count, const uint8_t* d_frame
   a.thr = p.threshold, a.enable_thr = p.enable_threshold, a.enable_weight = p.enable_weight;
   // The XCD-aware block order pays where a workgroup's working set is a multi-plane tile (MOG2, MOG1, dp); the byte-stream
   // kernels run 2-5 % faster in plain block order (tools/ab_pointwise.py), so they only use it at level 2 (for A/B runs).
-  a.xcd_swizzle = e->xcd_swizzle >= 2;
+  a.xcd_swizzle = e->knob.xcd_swizzle >= 2;
   return a;
 }
 
 // ------------------------------------------------------------------------------ FrameDifference, WeightedMovingMean / Variance
-// frame history ring (FD: 2 slots, WMM/WMV: 3): frame t of stream s lives in ring[t % nring] + s*n*ch
+// frame history ring (FD: 2 slots, WMM/WMV: 3): frame t of stream s lives in ring[t % nring] + s*n*ch.  The ring is the engine's
+// (the generic clip and host paths use it, free_all frees it): these classes have no state of their own.
 int ring_allocate(bgs_engine* e) {
   e->nring = e->algo == BGS_FRAME_DIFF ? 2 : 3;
   for (int i = 0; i < e->nring; ++i) DMALLOC(e->ring[i], e->n * e->S * e->ch);
   return BGS_OK;
-}
-
-void ring_release(bgs_engine* e) {
-  for (auto& r : e->ring) dfree(r);
 }
 
 uint64_t ring_key(const bgs_engine* e, int i) {  // ring slot + warm-up level
@@ -114,38 +111,35 @@ int64_t ring_get_state(bgs_engine* e, int stream, const char* plane, void* dst, 
 
 constexpr Family kFrameHistory = [] {
   Family f{};
-  f.allocate = ring_allocate, f.release = ring_release, f.key = ring_key, f.run = ring_run, f.get_state = ring_get_state;
+  f.allocate = ring_allocate, f.key = ring_key, f.run = ring_run, f.get_state = ring_get_state;
   return f;
 }();
 
 // ------------------------------------------------------------------------ StaticFrameDifference, AdaptiveBackgroundLearning
+// State: the background image [S][n*ch]; ABL: the 256 x 256 table of background bytes for one alpha (kernel_pointwise.h)
+struct SbgState : FamilyState {
+  DevPtr<uint8_t> bg, lut;
+  double lut_alpha = 0;  // the alpha `lut` was built for
+  bool lut_valid = false;
+};
+SbgState& sbg_of(const bgs_engine* e) { return state_of<SbgState>(e); }
+
 // (Re)build ABL's lookup table for the current alpha on e->stream.  Called when the geometry is set and when bgs_set_params
 // changes alpha; both drain the device first / the stream after, so no launch on any stream sees a half-written table.
 int abl_build_lut(bgs_engine* e) {
-  if (!e->abl_lut) HIP_TRY(hipMalloc((void**)&e->abl_lut, 256 * 256));
-  hipLaunchKernelGGL(bgs::abl_lut_kernel, dim3(256), dim3(bgs::kBlock), 0, e->stream, e->abl_lut, e->p.alpha, 1 - e->p.alpha);
+  SbgState& st = sbg_of(e);
+  if (!st.lut) HIP_TRY(hipMalloc((void**)&st.lut.p, 256 * 256));
+  hipLaunchKernelGGL(bgs::abl_lut_kernel, dim3(256), dim3(bgs::kBlock), 0, e->stream, st.lut.p, e->p.alpha, 1 - e->p.alpha);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->stream));
-  e->abl_lut_alpha = e->p.alpha, e->abl_lut_valid = true;
+  st.lut_alpha = e->p.alpha, st.lut_valid = true;
   return BGS_OK;
 }
 
-void cu_count(bgs_engine* e) {  // the persistent kernels (abl, asbl) size their grids by it
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, e->device) == hipSuccess && prop.multiProcessorCount > 0) e->n_cu = prop.multiProcessorCount;
-}
-
 int sbg_allocate(bgs_engine* e) {
-  e->state_ch = e->ch;
-  DMALLOC(e->bgstate, e->n * e->S * e->state_ch);
-  if (e->algo != BGS_ABL) return BGS_OK;
-  cu_count(e);
-  return abl_build_lut(e);
-}
-
-void sbg_release(bgs_engine* e) {
-  dfree(e->bgstate), dfree(e->abl_lut);
-  e->abl_lut_valid = false;
+  SbgState& st = make_state<SbgState>(e);
+  DMALLOC(st.bg, e->n * e->S * e->ch);
+  return e->algo == BGS_ABL ? abl_build_lut(e) : BGS_OK;
 }
 
 uint64_t sfd_key(const bgs_engine* e, int i) { return e->seen[i] == 0; }
@@ -160,7 +154,7 @@ int sbg_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_
   const int C = e->ch;
   const size_t npix = e->n * count, off = e->n * first, fb = npix * C;
   bgs::FrameArgs a = frame_args(e, count, d_frames, d_fg, d_bg, d_bits);
-  uint8_t* st = e->bgstate + off * C;
+  uint8_t* st = sbg_of(e).bg + off * C;
   if (e->seen[first] == 0) HIP_TRY(hipMemcpyAsync(st, d_frames, fb, hipMemcpyDeviceToDevice, s));  // img_input.copyTo(img_background)
   a.p1 = st;
   if (e->algo == BGS_STATIC_FRAME_DIFF) {
@@ -190,7 +184,7 @@ int sbg_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_
       per_cu_cache.store(per_cu, std::memory_order_relaxed);                                                                               \
     }                                                                                                                                      \
     const dim3 grid((unsigned)std::min<size_t>(ntiles, (size_t)per_cu * e->n_cu));                                                        \
-    hipLaunchKernelGGL((bgs::abl_kernel<GV, CV, UV>), grid, block, 0, s, a, (const uint8_t*)e->abl_lut);                                   \
+    hipLaunchKernelGGL((bgs::abl_kernel<GV, CV, UV>), grid, block, 0, s, a, (const uint8_t*)sbg_of(e).lut.p);                                   \
   }
       ABL_CASE(16, 3, true) ABL_CASE(4, 3, true) ABL_CASE(1, 3, true) ABL_CASE(16, 1, true) ABL_CASE(4, 1, true) ABL_CASE(1, 1, true)
       ABL_CASE(16, 3, false) ABL_CASE(4, 3, false) ABL_CASE(1, 3, false) ABL_CASE(16, 1, false) ABL_CASE(4, 1, false) ABL_CASE(1, 1, false)
@@ -203,15 +197,14 @@ int sbg_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_
   return BGS_OK;
 }
 
-// "bg": the byte state of the classes that keep one (here and in engine_gmg.h)
-int64_t bgstate_get_state(bgs_engine* e, int stream, const char* plane, void* dst, size_t cap) {
-  const size_t nb = e->n * e->state_ch;
-  if (!strcmp(plane, "bg")) return copy_plane(plane, dst, cap, e->bgstate + nb * stream, nb);
+int64_t sbg_get_state(bgs_engine* e, int stream, const char* plane, void* dst, size_t cap) {
+  const size_t nb = e->n * e->ch;
+  if (!strcmp(plane, "bg")) return copy_plane(plane, dst, cap, sbg_of(e).bg + nb * stream, nb);
   return unknown_plane(e, plane);
 }
 
 int abl_apply_params(bgs_engine* e) {
-  if (e->abl_lut_valid && e->p.alpha == e->abl_lut_alpha) return BGS_OK;
+  if (sbg_of(e).lut_valid && e->p.alpha == sbg_of(e).lut_alpha) return BGS_OK;
   // a launch still in flight on some stream may be reading the table: let the device drain before it is rewritten
   if (hipSetDevice(e->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(BGS_ERR_HIP, "device sync failed");
   return abl_build_lut(e);
@@ -219,7 +212,7 @@ int abl_apply_params(bgs_engine* e) {
 
 constexpr Family kStaticFrameDiff = [] {
   Family f{};
-  f.allocate = sbg_allocate, f.release = sbg_release, f.key = sfd_key, f.run = sbg_run, f.get_state = bgstate_get_state;
+  f.allocate = sbg_allocate, f.key = sfd_key, f.run = sbg_run, f.get_state = sbg_get_state;
   return f;
 }();
 
@@ -235,19 +228,22 @@ int sd_check_geometry(bgs_algo, int, int, int ch) {
   return BGS_OK;
 }
 
+struct SdState : FamilyState {
+  DevPtr<uint8_t> mt, vt;  // sdLaMa091's Mt and Vt images [S][n*3]
+};
+SdState& sd_of(const bgs_engine* e) { return state_of<SdState>(e); }
+
 int sd_allocate(bgs_engine* e) {
-  e->state_ch = 3;
-  DMALLOC(e->bgstate, e->n * e->S * 3);
-  DMALLOC(e->bgstate2, e->n * e->S * 3);  // Vt
+  SdState& st = make_state<SdState>(e);
+  DMALLOC(st.mt, e->n * e->S * 3);
+  DMALLOC(st.vt, e->n * e->S * 3);
   return BGS_OK;
 }
-
-void sd_release(bgs_engine* e) { dfree(e->bgstate), dfree(e->bgstate2); }
 
 int sd_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t*, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
   const bgs_params& p = e->p;
   const size_t npix = e->n * count, off = e->n * first, fb = npix * 3;
-  uint8_t *mt = e->bgstate + off * 3, *vt = e->bgstate2 + off * 3;
+  uint8_t *mt = sd_of(e).mt + off * 3, *vt = sd_of(e).vt + off * 3;
   if (e->seen[first] == 0) {  // SigmaDeltaBGS.cpp:33-39: allocate + initialise, return without output
     HIP_TRY(hipMemcpyAsync(mt, d_frames, fb, hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(bgs::sigmadelta_init_vt_kernel, dim3(blocks_for(fb)), dim3(bgs::kBlock), 0, s, vt, fb, e->cols, (int)(uint8_t)p.sd_min_var);
@@ -255,7 +251,7 @@ int sd_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t
   }
   bgs::SigmaDeltaArgs q{};
   q.cur = d_frames, q.mt = mt, q.vt = vt, q.fg = d_fg, q.fg_bits = d_bits, q.npix = npix;
-  q.N = (uint32_t)p.sd_amp_factor, q.vmin = (uint8_t)p.sd_min_var, q.vmax = (uint8_t)p.sd_max_var, q.xcd_swizzle = e->xcd_swizzle >= 2;
+  q.N = (uint32_t)p.sd_amp_factor, q.vmin = (uint8_t)p.sd_min_var, q.vmax = (uint8_t)p.sd_max_var, q.xcd_swizzle = e->knob.xcd_swizzle >= 2;
   int G = 16;
   if (npix % 16 || !aligned(d_frames, 16) || !aligned(mt, 16) || !aligned(vt, 16) || (d_fg && !aligned(d_fg, 16))) G = (npix % 4 || !aligned(d_frames, 4) || !aligned(mt, 4) || (d_fg && !aligned(d_fg, 4))) ? 1 : 4;
   {
@@ -270,12 +266,14 @@ int sd_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t
 
 int64_t sd_get_state(bgs_engine* e, int stream, const char* plane, void* dst, size_t cap) {
   const size_t nb = e->n * 3;
-  if (e->seen[stream] >= 1 && (!strcmp(plane, "mt") || !strcmp(plane, "vt"))) return copy_plane(plane, dst, cap, (!strcmp(plane, "mt") ? e->bgstate : e->bgstate2) + nb * stream, nb);
-  return bgstate_get_state(e, stream, plane, dst, cap);
+  const SdState& st = sd_of(e);
+  if (e->seen[stream] >= 1 && !strcmp(plane, "vt")) return copy_plane(plane, dst, cap, st.vt + nb * stream, nb);
+  if ((e->seen[stream] >= 1 && !strcmp(plane, "mt")) || !strcmp(plane, "bg")) return copy_plane(plane, dst, cap, st.mt + nb * stream, nb);  // "bg": Mt under the name of the other byte classes
+  return unknown_plane(e, plane);
 }
 
 constexpr Family kSigmaDelta = [] {
   Family f{};
-  f.check_geometry = sd_check_geometry, f.allocate = sd_allocate, f.release = sd_release, f.key = sfd_key, f.run = sd_run, f.get_state = sd_get_state;
+  f.check_geometry = sd_check_geometry, f.allocate = sd_allocate, f.key = sfd_key, f.run = sd_run, f.get_state = sd_get_state;
   return f;
 }();

@@ -30,52 +30,43 @@ enum { SS_UNSTABLE, SS_BLINKS, SS_LASTFG, SS_LASTRAW, SS_LASTRAWBLINK, SS_LASTDI
   } while (0)
 
 constexpr int SS_NBITS = 6;  // raw, closed-tmp / eroded, pre (closed), combined, final mask, dilated
-struct SsDevice {
-  void* samples = nullptr;  // records of colour + descriptor (kernel_subsense.h: SsSample, ss_rec)
+struct SsDevice : FamilyState {
+  DevPtr<void> samples;  // records of colour + descriptor (kernel_subsense.h: SsSample, ss_rec)
   int nSpad = 0, pixelMajor = 0;
-  uint8_t *lut = nullptr, *lastColor = nullptr, *curColor = nullptr;  // cur*: LOBSTER scratch (kernel_subsense.h)
-  uint16_t *lastDesc = nullptr, *req = nullptr, *curDesc = nullptr;
-  float* f32[SS_NF32] = {nullptr};
-  uint8_t* u8[SS_NU8] = {nullptr};
-  float *dsLT = nullptr, *dsST = nullptr;
-  bgs::SsScalars* sc = nullptr;
-  void* lastRec = nullptr;           // [S][N] 16-byte records: the full refresh's packed view of last colour / flag / descriptors (BGR)
-  uint32_t* magic = nullptr;         // ss_mod's multipliers
-  int* flood_flags = nullptr;  // [S][kSsFloodFlags], see ss_flood_kernel
+  DevPtr<uint8_t> lut, lastColor, curColor;  // cur*: LOBSTER scratch (kernel_subsense.h)
+  DevPtr<uint16_t> lastDesc, req, curDesc;
+  DevPtr<float> f32[SS_NF32];
+  DevPtr<uint8_t> u8[SS_NU8];
+  DevPtr<float> dsLT, dsST;
+  DevPtr<bgs::SsScalars> sc;
+  DevPtr<void> lastRec;          // [S][N] 16-byte records: the full refresh's packed view of last colour / flag / descriptors (BGR)
+  DevPtr<uint32_t> magic;        // ss_mod's multipliers
+  DevPtr<int> flood_flags;       // [S][kSsFloodFlags], see ss_flood_kernel
   hipStream_t side = nullptr;  // phase B runs here, beside the post-processing chain (both only need phase A)
   // One {evA, evB} pair per call in flight (a ring: calls for disjoint stream ranges may be in flight on several HIP streams)
   static constexpr int kRing = 8;
   hipEvent_t evA[kRing] = {nullptr}, evB[kRing] = {nullptr};
   int ring = 0;  // next pair to use
-  uint64_t *mbits = nullptr, *rbits = nullptr;  // flood fill: bit-packed mask / reached set, [S][rows][W64]
-  uint64_t* bitws = nullptr;                     // SS_NBITS more bit planes of the same shape: the post-processing chain's intermediates
+  DevPtr<uint64_t> mbits, rbits;  // flood fill: bit-packed mask / reached set, [S][rows][W64]
+  DevPtr<uint64_t> bitws;         // SS_NBITS more bit planes of the same shape: the post-processing chain's intermediates
   std::vector<uint8_t> pp;   // per stream: which copy of Dlast / RawST is current
   int use3x3 = 1, lrScaling = 0, medK = 9;
   float capLo0 = 4.f, capHi0 = 512.f;
-  void release() {
-    void* p[] = {samples, lut, lastColor, curColor, lastDesc, curDesc, req, dsLT, dsST, sc, lastRec, magic, flood_flags, mbits, rbits, bitws};
-    for (void* q : p)
-      if (q) (void)hipFree(q);
-    for (auto& q : f32)
-      if (q) (void)hipFree(q), q = nullptr;
-    for (auto& q : u8)
-      if (q) (void)hipFree(q), q = nullptr;
-    if (side) (void)hipStreamSynchronize(side), (void)hipStreamDestroy(side), side = nullptr;
+  ~SsDevice() override {  // the side stream is drained before the buffers its launches use go (the members' destructors)
+    if (side) (void)hipStreamSynchronize(side), (void)hipStreamDestroy(side);
     for (int i = 0; i < kRing; ++i)
-      for (hipEvent_t* q : {&evA[i], &evB[i]})
-        if (*q) (void)hipEventDestroy(*q), *q = nullptr;
-    ring = 0;
-    samples = nullptr, lut = lastColor = curColor = nullptr, lastDesc = req = curDesc = nullptr, dsLT = dsST = nullptr, sc = nullptr, lastRec = nullptr, magic = nullptr, flood_flags = nullptr, mbits = rbits = nullptr, bitws = nullptr;
+      for (hipEvent_t q : {evA[i], evB[i]})
+        if (q) (void)hipEventDestroy(q);
   }
 };
+SsDevice& ss_of(const bgs_engine* e) { return state_of<SsDevice>(e); }
 
 int ss_allocate(bgs_engine* e) {
   if (e->rows < 5 || e->cols < 5) return fail(BGS_ERR_UNSUPPORTED, "SuBSENSE needs at least 5x5 pixels (LBSP::validateROI)");
   const bgs_params& p = e->p;
   if (p.subsense_n_samples < 1 || p.subsense_n_samples > bgs::kSsMaxSamples || p.subsense_n_required > p.subsense_n_samples)
     return fail(BGS_ERR_UNSUPPORTED, "SuBSENSE: nBGSamples must be 1..%d and nRequiredBGSamples <= nBGSamples", bgs::kSsMaxSamples);
-  SsDevice* d = new SsDevice();
-  e->ss = d;
+  SsDevice* d = &make_state<SsDevice>(e);
   // geometry-dependent switches of BackgroundSubtractorSuBSENSE::initialize (:121-140), ROI = whole frame (SuBSENSE.cpp:36)
   const int total = e->rows * e->cols, qvga = 320 * 240;
   if (total >= qvga) {
@@ -118,10 +109,10 @@ int ss_allocate(bgs_engine* e) {
 }
 
 void ss_fill_args(const bgs_engine* e, bgs::SsArgs& a, int first, int cur_pp, unsigned frameIndex) {
-  const SsDevice* d = e->ss;
+  const SsDevice* d = &ss_of(e);
   const bgs_params& p = e->p;
   a.samples = d->samples, a.nSpad = d->nSpad, a.pixelMajor = d->pixelMajor, a.lastColor = d->lastColor, a.lastDesc = d->lastDesc, a.req = d->req, a.lut = d->lut, a.sc = d->sc;
-  a.magic = d->magic, a.lastRec = (uint4*)d->lastRec;
+  a.magic = d->magic, a.lastRec = (uint4*)d->lastRec.p;
   a.R = d->f32[SS_R], a.V = d->f32[SS_V], a.T = d->f32[SS_T];
   a.DlastOld = d->f32[cur_pp ? SS_DLAST1 : SS_DLAST0], a.DlastNew = d->f32[cur_pp ? SS_DLAST0 : SS_DLAST1];
   a.RawSTOld = d->f32[cur_pp ? SS_RAWST1 : SS_RAWST0], a.RawSTNew = d->f32[cur_pp ? SS_RAWST0 : SS_RAWST1];
@@ -186,7 +177,7 @@ int ss_launch_refresh(bgs_engine* e, const bgs::SsArgs& a, size_t N, int count, 
 }
 
 int ss_init_streams(bgs_engine* e, int first, int count, const uint8_t* d_frames, hipStream_t s) {
-  SsDevice* d = e->ss;
+  SsDevice* d = &ss_of(e);
   const size_t N = e->n, off = N * first, npix = N * count, C = (size_t)e->ch;
   uint8_t lut[256];
   ss_initial_lut(e->p, e->ch, lut);
@@ -214,7 +205,7 @@ int ss_init_streams(bgs_engine* e, int first, int count, const uint8_t* d_frames
   // BGR: the full refresh below writes every record of these streams, zeros included (kernel_subsense.h: ss_refresh_kernel, mode 0) -
   // clearing the 13 GB of an 8 x 1080p model first took 3 ms beside the refresh's 5
   const bool refresh_fills = C == 3 && d->pixelMajor && e->p.subsense_n_samples > bgs::kSsBatch;
-  if (!refresh_fills) HIP_TRY(hipMemsetAsync((uint8_t*)d->samples + off * (size_t)d->nSpad * (C == 3 ? 16 : 4), 0, npix * (size_t)d->nSpad * (C == 3 ? 16 : 4), s));
+  if (!refresh_fills) HIP_TRY(hipMemsetAsync((uint8_t*)d->samples.p + off * (size_t)d->nSpad * (C == 3 ? 16 : 4), 0, npix * (size_t)d->nSpad * (C == 3 ? 16 : 4), s));
   // first-frame descriptors (:229-243) with the initial LUT, border = 0; LastColor interior = frame
   bgs::LbspArgs la{};
   la.img = d_frames, la.desc = d->lastDesc + off * C, la.rows = e->rows, la.cols = e->cols;
@@ -253,7 +244,7 @@ int ss_side_stream(SsDevice* d) {
 // phase B started behind the flood fill, 1024-lane flood strips for every height - DESIGN.md 7d, profiles/r04_subsense_token_parts.txt,
 // profiles/r04_subsense_step_timeline.txt, profiles/r04_subsense_phase_a_pmc.txt.
 int ss_process(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, hipStream_t s) {
-  SsDevice* d = e->ss;
+  SsDevice* d = &ss_of(e);
   const int64_t t = e->seen[first];
   const size_t N = e->n, off = N * first, npix = N * count;
   // (frames need no particular alignment: the tile loaders read dwords relative to each image's own base, which is unaligned anyway for
@@ -361,7 +352,7 @@ int ss_process(bgs_engine* e, int first, int count, const uint8_t* d_frames, uin
 }
 
 int64_t ss_get_state(bgs_engine* e, int stream, const char* plane, void* dst, size_t cap) {
-  SsDevice* d = e->ss;
+  SsDevice* d = &ss_of(e);
   if (e->algo == BGS_LOBSTER) {  // the LOBSTER model has no feedback maps
     bool ok = false;
     for (const char* nm : {"lastfg", "lastcolor", "lastdesc", "color", "desc", "lut"}) ok = ok || !strcmp(plane, nm);
@@ -392,18 +383,14 @@ int64_t ss_get_state(bgs_engine* e, int stream, const char* plane, void* dst, si
                      {"lastdesc", d->lastDesc + off * C, N * 2 * C},
                      {"lut", d->lut + (size_t)stream * 256, 256}};
   for (const Ent& t : tab)
-    if (!strcmp(plane, t.name)) {
-      if (cap < t.bytes) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
-      if (d2h_staged(dst, t.p, t.bytes) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-      return (int64_t)t.bytes;
-    }
+    if (!strcmp(plane, t.name)) return copy_plane(plane, dst, cap, t.p, t.bytes);
   if (!strcmp(plane, "color") || !strcmp(plane, "desc")) {  // canonical export: color u8 [nS][N][C], desc u16 [nS][N][C], whatever the record layout
     const bool wantColor = !strcmp(plane, "color");
     const size_t need = N * nS * C * (wantColor ? 1 : 2), recB = C == 3 ? 16 : 4;
-    if (cap < need) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
+    if (cap < need) return too_small(plane);
     const size_t per = d->pixelMajor ? (size_t)d->nSpad : nS;  // records per pixel held on the device
     std::vector<uint8_t> recs(N * per * recB);
-    if (d2h_staged(recs.data(), (const uint8_t*)d->samples + off * per * recB, recs.size()) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
+    if (fetch(recs.data(), (const uint8_t*)d->samples.p + off * per * recB, recs.size())) return BGS_ERR_HIP;
     for (size_t k = 0; k < nS; ++k)
       for (size_t px = 0; px < N; ++px) {  // export: [nS][N][C], whatever the device order
         const size_t B = bgs::kSsBatch;  // same mapping as ss_rec (kernel_subsense.h)
@@ -420,23 +407,16 @@ int64_t ss_get_state(bgs_engine* e, int stream, const char* plane, void* dst, si
   }
   if (!strcmp(plane, "floodflags")) {  // diagnostics: which launches of the last flood fill still changed something, [kSsFloodFlags] int32; the last one = the finish kernel had to work
     if (e->algo != BGS_SUBSENSE) return fail(BGS_ERR_STATE, "floodflags: SuBSENSE only");
-    const size_t nb = (size_t)bgs::kSsFloodFlags * sizeof(int);
-    if (cap < nb) return fail(BGS_ERR_STATE, "buffer too small for plane floodflags");
-    if (d2h_staged(dst, d->flood_flags + (size_t)stream * bgs::kSsFloodFlags, nb) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-    return (int64_t)nb;
+    return copy_plane(plane, dst, cap, d->flood_flags + (size_t)stream * bgs::kSsFloodFlags, (size_t)bgs::kSsFloodFlags * sizeof(int));
   }
-  if (!strcmp(plane, "magic") && d->magic) {  // ss_mod's table (kernel_subsense.h), for the test that checks it against plain integer division
-    if (cap < bgs::kSsMagicN * 4) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
-    if (d2h_staged(dst, d->magic, bgs::kSsMagicN * 4) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-    return bgs::kSsMagicN * 4;
-  }
+  // ss_mod's table (kernel_subsense.h), for the test that checks it against plain integer division
+  if (!strcmp(plane, "magic") && d->magic) return copy_plane(plane, dst, cap, d->magic, bgs::kSsMagicN * 4);
   if (!strcmp(plane, "scalars")) {
-    if (cap < 7 * sizeof(double)) return fail(BGS_ERR_STATE, "buffer too small for plane scalars");
+    if (cap < 7 * sizeof(double)) return too_small(plane);
     bgs::SsScalars sc;
-    if (d2h_staged(&sc, d->sc + stream, sizeof(sc)) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-    double* o = (double*)dst;
-    o[0] = (double)e->seen[stream], o[1] = sc.framesSinceReset, o[2] = sc.cooldown, o[3] = sc.capLo, o[4] = sc.capHi, o[5] = sc.autoReset, o[6] = sc.lastNZ;
-    return 7 * sizeof(double);
+    if (fetch(&sc, d->sc + stream, sizeof(sc))) return BGS_ERR_HIP;
+    const double o[7] = {(double)e->seen[stream], (double)sc.framesSinceReset, (double)sc.cooldown, (double)sc.capLo, (double)sc.capHi, (double)sc.autoReset, (double)sc.lastNZ};
+    return copy_host(plane, dst, cap, o, sizeof(o));
   }
   return fail(BGS_ERR_STATE, "unknown state plane '%s' for SuBSENSE", plane);
 }
@@ -448,8 +428,7 @@ int lob_allocate(bgs_engine* e) {
   const bgs_params& p = e->p;
   if (p.subsense_n_samples < 1 || p.subsense_n_samples > bgs::kSsMaxSamples || p.subsense_n_required > p.subsense_n_samples)
     return fail(BGS_ERR_UNSUPPORTED, "LOBSTER: nBGSamples must be 1..%d and nRequiredBGSamples <= nBGSamples", bgs::kSsMaxSamples);
-  SsDevice* d = new SsDevice();
-  e->ss = d;
+  SsDevice* d = &make_state<SsDevice>(e);
   const size_t N = e->n, P = N * e->S, nS = (size_t)p.subsense_n_samples, C = (size_t)e->ch;
   d->pixelMajor = 0, d->nSpad = (int)nS;  // LOBSTER: sample-major (kernel_subsense.h)
   DMALLOC(d->samples, P * nS * (C == 3 ? 16 : 4));
@@ -467,7 +446,7 @@ int lob_allocate(bgs_engine* e) {
 }
 
 void lob_fill_args(const bgs_engine* e, bgs::SsArgs& a, int first, unsigned frameIndex) {
-  const SsDevice* d = e->ss;
+  const SsDevice* d = &ss_of(e);
   const bgs_params& p = e->p;
   a.samples = d->samples, a.nSpad = d->nSpad, a.pixelMajor = d->pixelMajor, a.lastColor = d->lastColor, a.lastDesc = d->lastDesc, a.req = d->req, a.lut = d->lut;
   a.lastFG = d->u8[SS_LASTFG], a.raw = d->u8[SS_RAW];
@@ -479,7 +458,7 @@ void lob_fill_args(const bgs_engine* e, bgs::SsArgs& a, int first, unsigned fram
 }
 
 int lob_process(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, hipStream_t s) {
-  SsDevice* d = e->ss;
+  SsDevice* d = &ss_of(e);
   const int64_t t = e->seen[first];
   const size_t N = e->n, off = N * first, npix = N * count, nS = (size_t)e->p.subsense_n_samples, C = (size_t)e->ch;
   const dim3 block(bgs::kBlock);
@@ -495,7 +474,7 @@ int lob_process(bgs_engine* e, int first, int count, const uint8_t* d_frames, ui
     std::memcpy(lutv.v, lut, 256);
     hipLaunchKernelGGL(bgs::ss_init_consts_kernel, dim3(count), block, 0, s, d->lut, (bgs::SsScalars*)nullptr, lutv, bgs::SsScalars{}, first);
     HIP_TRY(hipMemsetAsync(d->u8[SS_LASTFG] + off, 0, npix, s));
-    HIP_TRY(hipMemsetAsync((uint8_t*)d->samples + off * nS * (C == 3 ? 16 : 4), 0, npix * nS * (C == 3 ? 16 : 4), s));
+    HIP_TRY(hipMemsetAsync((uint8_t*)d->samples.p + off * nS * (C == 3 ? 16 : 4), 0, npix * nS * (C == 3 ? 16 : 4), s));
     bgs::LbspArgs la{};
     la.img = d_frames, la.desc = d->lastDesc + off * C, la.rows = e->rows, la.cols = e->cols;
     std::memcpy(la.lut, lut, 256);
@@ -531,21 +510,13 @@ int lob_process(bgs_engine* e, int first, int count, const uint8_t* d_frames, ui
   return BGS_OK;
 }
 
-void ss_free(bgs_engine* e) {
-  if (e->ss) {
-    e->ss->release();
-    delete e->ss;
-    e->ss = nullptr;
-  }
-}
-
 // SuBSENSE / LOBSTER: the frame index itself goes into the kernels (counter-based random draws); + which half of the ping-pong maps is current
-uint64_t ss_key(const bgs_engine* e, int i) { return (uint64_t)e->seen[i] | (uint64_t)(e->ss->pp[i] & 1) << 62; }
+uint64_t ss_key(const bgs_engine* e, int i) { return (uint64_t)e->seen[i] | (uint64_t)(ss_of(e).pp[i] & 1) << 62; }
 
 // the mask is also model state (m_oLastFGMask): the packed mask is made from there
 int ss_finish(bgs_engine* e, int first, int count, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
   const size_t npix = e->n * count, off = e->n * first;
-  if (d_bits) hipLaunchKernelGGL(bgs::mask_pack_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, (const uint8_t*)(e->ss->u8[SS_LASTFG] + off), d_bits, npix);
+  if (d_bits) hipLaunchKernelGGL(bgs::mask_pack_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, (const uint8_t*)(ss_of(e).u8[SS_LASTFG] + off), d_bits, npix);
   *flags = BGS_FG_VALID | BGS_BG_VALID;
   return BGS_OK;
 }
@@ -568,7 +539,7 @@ void ss_keep_frozen(bgs_params& p, const bgs_params& old) {
 
 constexpr Family kSubsense = [] {
   Family f{};
-  f.allocate = ss_allocate, f.release = ss_free, f.key = ss_key, f.run = ss_run, f.get_state = ss_get_state, f.keep_frozen = ss_keep_frozen;
+  f.allocate = ss_allocate, f.key = ss_key, f.run = ss_run, f.get_state = ss_get_state, f.keep_frozen = ss_keep_frozen;
   return f;
 }();
 
