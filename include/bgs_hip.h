@@ -313,8 +313,9 @@ int bgs_fuzzy_check(bgs_algo algo, const bgs_fuzzy_params* p, int rows, int cols
                                    written back: A/B, placement probe); 1 eager (every record read, only what changed written); 2 count
                                    (only the modes a pixel has are read); 4 filter (4-byte summaries first, then only the records they
                                    cannot rule out); 3 (default) automatic, from what sampled workgroups count */
-#define BGS_OPT_CLIP_FUSE 7     /* 1 (default): bgs_process_clip_device runs 8 / 4 / 2 consecutive frames of a mixture model per launch with the
-                                   model held in registers; 0: one launch per frame.  Identical results, only speed differs. */
+#define BGS_OPT_CLIP_FUSE 7     /* 1 (default): bgs_process_clip_device runs 8 / 4 / 2 consecutive frames of a mixture model or of a
+                                   package_bgs/lb model per launch with the model held in registers; 0: one launch per frame.  Identical
+                                   results, only speed differs. */
 #define BGS_OPT_MODEL_CHUNK_MB 9
 #define BGS_OPT_MODEL_CHUNK_MIN_MB 10 /* models smaller than this many MiB take one plain allocation (default 768: below that a good part of the
                                    model sits in the 256 MiB Infinity Cache and placement does not matter); before the geometry is set.
@@ -377,7 +378,8 @@ int bgs_process_range_device(bgs_engine* e, int first, int count, const void* d_
  *   d_frames  [nframes][count][rows][cols][channels]   frame t of all streams, then frame t+1 ...
  *   d_fg      [nframes][count][rows][cols] or NULL;  d_bg [nframes][count][rows][cols][channels] or NULL
  *   d_fg_bits [nframes][count][ceil(rows*cols/64)] or NULL;  out_flags: nframes words or NULL
- * The mixture models (MixtureOfGaussianV2BGS, MixtureOfGaussianV1BGS, DPZivkovicAGMMBGS, DPGrimsonGMMBGS) take runs of 8 / 4 / 2
+ * The mixture models (MixtureOfGaussianV2BGS, MixtureOfGaussianV1BGS, DPZivkovicAGMMBGS, DPGrimsonGMMBGS) and the five
+ * package_bgs/lb classes (LBSimpleGaussian, LBFuzzyGaussian, LBMixtureOfGaussians, LBAdaptiveSOM, LBFuzzyAdaptiveSOM) take runs of 8 / 4 / 2
  * frames through ONE launch that loads each pixel's model once, applies the frames in order in registers and writes the model back
  * once (model traffic per frame / 8, / 4, / 2); FrameDifference / WeightedMovingMean / WeightedMovingVariance take their frame history
  * from the clip itself instead of copying every frame into the engine's ring; every other class runs the same launches as the

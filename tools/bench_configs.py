@@ -6,7 +6,8 @@ Not the driver's bench line (bench.py is); the numbers go to DESIGN.md §6.
   --only kde: KDE (package_bgs/ae) young / aged model, static and ~10 % foreground scenes, 8 x 1080p
   --only dp2: DPPratiMediodBGS (sampled / other frames) and DPTextureBGS, 8 x 1080p
   --only lb: the five package_bgs/lb models (double-precision planes), static and ~10 % foreground scenes, SOMs inside and past their
-             calibration phase, the Gaussian pair with one and two pixels per lane, 8 x 1080p  (lb_<class>: one class, short legs)
+             calibration phase, the Gaussian pair with one and two pixels per lane, 8 x 1080p  (lb_<class>: one class, short legs);
+             then clip calls of T = 4 and 8 frames, fused and frame by frame alternating  (lb_clip: these legs alone)
   --only vumeter: VuMeter (package_bgs/av), dense and live-bin kernels (BGS_VU_SPARSE 0 / 1 / 2), filter on and off, on S_surv and on
              fresh uniform noise (every bin live: the live-bin kernels' worst case), 8 x 1080p
   --only fuzzy: FuzzySugenoIntegral and FuzzyChoquetIntegral (package_bgs/tb), ms per learning step and per detecting step on S_surv,
@@ -707,6 +708,56 @@ def run_lb(S=8, rows=1080, cols=1920, steps=30, only=None, px_variants=(2, 1), c
         torch.cuda.empty_cache()
 
 
+def run_lb_clip(S=8, rows=1080, cols=1920, only=None, rounds=5, reps=3, scenes=(("static + noise", 0.0), ("~10 % foreground", 0.1))):
+    """Clip calls of the five package_bgs/lb classes at S x 1080p, byte mask + background image out, model aged 100 frames (the SOMs
+    online): T = 4 and T = 8 frames per call with BGS_OPT_CLIP_FUSE 1 (one lb_*_clip_kernel launch per call) and 0 (T launches of
+    the per-frame kernel: the frame-by-frame path) alternating on the same engine, `rounds` times `reps` calls each.  ms per
+    frame = kernel time (HIP events around every launch) over the frames; the median of the rounds, and the spread (min .. max) of
+    the unfused rounds, which is what a gain has to exceed.  B/pixel/frame: frame 3 + mask 1 + background 3 per frame, the model
+    read and written once per call (dense bound for MoG and the SOMs, SOMs + the 3 kept background bytes each way)."""
+    dev = torch.device("cuda", 0)
+    px = S * rows * cols
+    model = {"sg": 96, "fg": 96, "mog": 344, "som": 438, "fsom": 438}
+    for label, frac in scenes:
+        pool = kde_scene(12, S, rows, cols, frac, dev)
+        learn = kde_scene(11, S, rows, cols, 0.0, dev) if frac > 0 else pool
+        fg = torch.empty((8, S, rows, cols), dtype=torch.uint8, device=dev)
+        bg = torch.empty((8, S, rows, cols, 3), dtype=torch.uint8, device=dev)
+        for key, (name, algo) in LB_CLASSES.items():
+            if only and key != only:
+                continue
+            e = Engine(getattr(capi, algo), n_streams=S)
+            e.set_geometry(rows, cols, 3)
+            for t in range(100):
+                e.process_batch_device(learn[t] if t < 11 else pool[t % 12], None, None, None)
+            for T in (4, 8):
+                slab = pool[:T]
+                ms = {1: [], 0: []}
+                kn = {}
+                for _ in range(rounds):
+                    for fuse in (1, 0):
+                        e.set_option(capi.OPT_CLIP_FUSE, fuse)
+                        torch.cuda.synchronize()
+                        e.enable_kernel_timing(True)
+                        for _ in range(reps):
+                            e.process_clip_device(slab, T, fg, bg)
+                        torch.cuda.synchronize()
+                        avg, n, kn[fuse] = e.kernel_timing()
+                        e.enable_kernel_timing(False)
+                        assert n == reps * (1 if fuse else T) and ("clip" in kn[fuse]) == bool(fuse), (n, kn[fuse])
+                        ms[fuse].append(avg * n / (reps * T))
+                f, u = float(np.median(ms[1])), float(np.median(ms[0]))
+                spread = max(ms[0]) - min(ms[0])
+                bpf = model[key] / T + 7
+                print("%-20s %-17s clip T=%d %dx%d x%d streams: fused %s %.3f ms/frame (min %.3f max %.3f), unfused %s %.3f ms/frame (min %.3f max %.3f, spread %.3f); "
+                      "gain %.3f ms = x%.2f -> %s; fused %.1f B/px/frame -> %.0f GB/s"
+                      % (name, label, T, cols, rows, S, kn[1], f, min(ms[1]), max(ms[1]), kn[0], u, min(ms[0]), max(ms[0]), spread, u - f, u / f,
+                         "faster than the spread" if u - f > spread else "NOT faster than the spread", bpf, bpf * px / (f * 1e-3) / 1e9))
+            e.close()
+        del pool, learn, fg, bg
+        torch.cuda.empty_cache()
+
+
 def run_vumeter(S=8, rows=1080, cols=1920, steps=30, age=60):
     """VuMeter (reference defaults: 32 bins, alpha 0.995) at S x 1080p, byte mask + background image out, for the three kernel variants
     in one process on the same frames: the model kernel's ms per step (HIP events around the launch, mean of `steps`) and the wall ms
@@ -830,6 +881,10 @@ def main():
         return
     if args.only == "lb":
         run_lb(S)
+        run_lb_clip(S)
+        return
+    if args.only == "lb_clip":  # the clip legs alone
+        run_lb_clip(S)
         return
     if args.only == "vumeter":
         run_vumeter(S)

@@ -148,7 +148,7 @@ struct bgs_engine {
     int xcd_swizzle = 1;             // XCD-aware block order (kernel_mog2.h): 0 off, 1 model kernels (MOG2, MOG1, dp), 2 also the byte-stream kernels
     int mog2_sparse = 3;             // data-dependent traffic (kernel_mog2.h): 0 dense (everything loaded and written), 1 only what changed is written, 2 / 4 a lane also loads only the modes its pixel has, 3 = choose 1 or 4 from the scene
     int mog2_complete = 1;           // sector-complete stores (kernel_mog2.h); BGS_MOG2_COMPLETE=0 for A/B runs
-    bool clip_fuse = true;           // MOG2 clip calls keep the model in registers across frames (option 7; results identical either way)
+    bool clip_fuse = true;           // clip calls of the families with a clip_fused entry keep the model in registers across frames (option 7; results identical either way)
     int lb_px = 1;                   // pixels per lane of the two Gaussian kernels (BGS_LB_PX=2: the double2 form, A/B; identical results)
     int vu_sparse = 1;               // BGS_VU_SPARSE: 0 dense, 1 live-bin with whole-line stores, 2 live-bin with masked stores (identical results)
     bool kde_count_trips = false;    // diagnostics: count density-loop trips (BGS_KDE_TRIPS=1)
@@ -666,7 +666,7 @@ int process_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, ui
 
 
 // bgs_process_clip_device: `nframes` consecutive frames of streams [first, first+count).  Every algorithm: frame by frame
-// through process_range (the same launches as nframes range calls).  Families with a clip_fused entry (MOG2, MOG1, the dp GMMs): runs
+// through process_range (the same launches as nframes range calls).  Families with a clip_fused entry (MOG2, MOG1, the dp GMMs, the five lb/ classes): runs
 // of 8 / 4 / 2 frames go through ONE launch that keeps the model in registers; what is left over takes the single-frame kernel.
 int process_clip_run(bgs_engine* e, int first, int count, int slab_count, int nframes, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits,
                      hipStream_t s, uint32_t* out_flags);

@@ -90,34 +90,52 @@ int lb_allocate(bgs_engine* e) {
   return BGS_OK;
 }
 
-// One frame of LB*::process for streams [first, first+count), which share lb_key.
-int lb_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
-  LbState& st = lb_of(e);
-  const size_t n = e->n;
-  const int P = lb_planes_of(e->algo);
-  const LbModelParams mp = lb_model_params(e->algo, e->p);
+// Kernel arguments of streams [f, f + c) of a run that starts at stream `first`: the parameters of this call and the pointers of
+// one frame (d_* point at the run's first stream).  `init`: the frame is these streams' first one.
+bgs::LbArgs lb_args(const bgs_engine* e, const LbModelParams& mp, bool init, int first, int f, int c, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits) {
+  const LbState& st = lb_of(e);
+  const size_t n = e->n, o = (size_t)(f - first) * n;
   bgs::LbArgs a{};
-  a.n = (uint32_t)n, a.init = e->seen[first] == 0;
+  a.n = (uint32_t)n, a.init = init;
   a.threshold = mp.threshold, a.noise = mp.noise, a.noise0 = 50.0, a.alpha = mp.alpha, a.bg_threshold = mp.bg_threshold;
-  auto slab = [&](int f, int c) {  // arguments of streams [f, f + c)
-    const size_t o = (size_t)(f - first) * n;
-    a.cur = d_frames + o * 3, a.fg = d_fg ? d_fg + o : nullptr, a.bg = d_bg ? d_bg + o * 3 : nullptr;
-    a.fg_bits = d_bits ? d_bits + o / 64 : nullptr;
-    a.model = st.model + (size_t)f * P * n;
-    a.k = st.k ? st.k + (size_t)f * n : nullptr, a.bgplane = st.bg ? st.bg + (size_t)f * n * 3 : nullptr;
-    a.npix = (uint32_t)(n * c);
-  };
+  a.cur = d_frames + o * 3, a.fg = d_fg ? d_fg + o : nullptr, a.bg = d_bg ? d_bg + o * 3 : nullptr;
+  a.fg_bits = d_bits ? d_bits + o / 64 : nullptr;
+  a.model = st.model + (size_t)f * lb_planes_of(e->algo) * n;
+  a.k = st.k ? st.k + (size_t)f * n : nullptr, a.bgplane = st.bg ? st.bg + (size_t)f * n * 3 : nullptr;
+  a.npix = (uint32_t)(n * c);
+  a.bps = (uint32_t)blocks_for(n);
+  return a;
+}
+
+// BGModelSom::Update's phase test for one frame of one stream: calibration while m_K <= m_TSteps (frame 1 counts), alpha with the
+// integers promoted to double.  Advances the stream's counter.
+void lb_som_schedule(const LbModelParams& mp, int& mk, double* alpha, double* eps) {
+  if (mk <= mp.tsteps) {
+    *eps = mp.eps1, *alpha = mp.alpha1 - (double)mk * (mp.alpha1 - mp.alpha2) / (double)mp.tsteps;
+    ++mk;
+  } else {
+    *eps = mp.eps2, *alpha = mp.alpha2;
+  }
+}
+
+// the two Gaussian kernels take two pixels per lane when asked to and n is even: pairs of pixels never straddle two streams then,
+// and every double2 is aligned
+bool lb_two_px(const bgs_engine* e) { return e->knob.lb_px == 2 && e->n % 2 == 0; }
+
+// One frame for streams [first, first+count), `init`: their first one.
+int lb_frame(bgs_engine* e, bool init, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s) {
+  LbState& st = lb_of(e);
+  const LbModelParams mp = lb_model_params(e->algo, e->p);
   if (!is_lb_som(e->algo)) {
-    slab(first, count);
+    const bgs::LbArgs a = lb_args(e, mp, init, first, first, count, d_frames, d_fg, d_bg, d_bits);
     const size_t npix = a.npix;
     if (e->algo == BGS_LB_MOG) {
       Timed tm(e, s, "lb_mog_kernel");
       hipLaunchKernelGGL(bgs::lb_mog_kernel, dim3(blocks_for(npix)), dim3(bgs::kBlock), 0, s, a);
     } else {
       const bool fuzzy = e->algo == BGS_LB_FUZZY_GAUSSIAN;
-      const bool two = e->knob.lb_px == 2 && n % 2 == 0;  // pairs of pixels never straddle two streams then, and every double2 is aligned
       Timed tm(e, s, fuzzy ? "lb_fuzzy_gauss_kernel" : "lb_gauss_kernel");
-      if (two) {
+      if (lb_two_px(e)) {
         if (fuzzy)
           hipLaunchKernelGGL((bgs::lb_gauss_kernel<true, 2>), dim3(blocks_for(npix / 2)), dim3(bgs::kBlock), 0, s, a);
         else
@@ -130,26 +148,20 @@ int lb_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t
       }
     }
   } else {
-    // BGModelSom::Update's phase test, per stream: calibration while m_K <= m_TSteps (frame 1 counts), alpha with the integers
-    // promoted to double.  Streams whose counters differ get their own table entry in the same launch.
+    // Streams whose counters differ get their own table entry in the same launch.
     std::vector<double> al(count), ep(count);
     bool same = true;
     for (int i = 0; i < count; ++i) {
       int& mk = st.mk[first + i];
-      if (a.init) mk = 0;
-      if (mk <= mp.tsteps) {
-        ep[i] = mp.eps1, al[i] = mp.alpha1 - (double)mk * (mp.alpha1 - mp.alpha2) / (double)mp.tsteps;
-        ++mk;
-      } else {
-        ep[i] = mp.eps2, al[i] = mp.alpha2;
-      }
+      if (init) mk = 0;
+      lb_som_schedule(mp, mk, &al[i], &ep[i]);
       same = same && al[i] == al[0] && ep[i] == ep[0];
     }
     const bool fuzzy = e->algo == BGS_LB_FUZZY_ADAPTIVE_SOM;
     for (int f = 0; f < count; f += same ? count : bgs::kLbTable) {
       const int c = same ? count : std::min(bgs::kLbTable, count - f);
-      slab(first + f, c);
-      a.uniform = same, a.bps = (uint32_t)blocks_for(n);
+      bgs::LbArgs a = lb_args(e, mp, init, first, first + f, c, d_frames, d_fg, d_bg, d_bits);
+      a.uniform = same;
       const dim3 grid(a.bps * (unsigned)c);
       for (int i = 0; i < (same ? 1 : c); ++i) a.alpha_s[i] = al[f + i], a.eps_s[i] = ep[f + i];
       Timed tm(e, s, fuzzy ? "lb_fuzzy_som_kernel" : "lb_som_kernel");
@@ -159,7 +171,88 @@ int lb_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t
         hipLaunchKernelGGL(bgs::lb_som_kernel<false>, grid, dim3(bgs::kBlock), 0, s, a);
     }
   }
+  return BGS_OK;
+}
+
+// One frame of LB*::process for streams [first, first+count), which share lb_key.
+int lb_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s, uint32_t* flags) {
   *flags = BGS_FG_VALID | BGS_BG_VALID;
+  return lb_frame(e, e->seen[first] == 0, first, count, d_frames, d_fg, d_bg, d_bits, s);
+}
+
+template <int T>
+void lb_launch_clip(const bgs_engine* e, hipStream_t s, const bgs::LbClipArgs& c) {
+  const dim3 block(bgs::kBlock);
+  const size_t npix = c.a.npix;
+  switch (e->algo) {
+    case BGS_LB_MOG: hipLaunchKernelGGL((bgs::lb_mog_clip_kernel<T>), dim3(blocks_for(npix)), block, 0, s, c); break;
+    case BGS_LB_ADAPTIVE_SOM: hipLaunchKernelGGL((bgs::lb_som_clip_kernel<false, T>), dim3(c.a.bps * (unsigned)(npix / c.a.n)), block, 0, s, c); break;
+    case BGS_LB_FUZZY_ADAPTIVE_SOM: hipLaunchKernelGGL((bgs::lb_som_clip_kernel<true, T>), dim3(c.a.bps * (unsigned)(npix / c.a.n)), block, 0, s, c); break;
+    case BGS_LB_FUZZY_GAUSSIAN:
+      if (lb_two_px(e))
+        hipLaunchKernelGGL((bgs::lb_gauss_clip_kernel<true, 2, T>), dim3(blocks_for(npix / 2)), block, 0, s, c);
+      else
+        hipLaunchKernelGGL((bgs::lb_gauss_clip_kernel<true, 1, T>), dim3(blocks_for(npix)), block, 0, s, c);
+      break;
+    default:
+      if (lb_two_px(e))
+        hipLaunchKernelGGL((bgs::lb_gauss_clip_kernel<false, 2, T>), dim3(blocks_for(npix / 2)), block, 0, s, c);
+      else
+        hipLaunchKernelGGL((bgs::lb_gauss_clip_kernel<false, 1, T>), dim3(blocks_for(npix)), block, 0, s, c);
+  }
+}
+
+const char* lb_clip_kernel_name(bgs_algo a) {
+  switch (a) {
+    case BGS_LB_SIMPLE_GAUSSIAN: return "lb_gauss_clip_kernel";
+    case BGS_LB_FUZZY_GAUSSIAN: return "lb_fuzzy_gauss_clip_kernel";
+    case BGS_LB_MOG: return "lb_mog_clip_kernel";
+    case BGS_LB_ADAPTIVE_SOM: return "lb_som_clip_kernel";
+    default: return "lb_fuzzy_som_clip_kernel";
+  }
+}
+
+// `fuse` = 8 / 4 / 2 consecutive frames of streams [first, first+count) in one launch (kernel_lb.h: lb_*_clip_kernel); the streams
+// have seen the same number of frames (process_clip_run).  slab: pixels from one frame of the clip to the next.
+int lb_clip_fused(bgs_engine* e, int first, int count, int fuse, size_t slab, const uint8_t* fr, uint8_t* fg, uint8_t* bg, uint64_t* bits, hipStream_t s, uint32_t* flags) {
+  LbState& st = lb_of(e);
+  const LbModelParams mp = lb_model_params(e->algo, e->p);
+  const bool init = e->seen[first] == 0;
+  *flags = BGS_FG_VALID | BGS_BG_VALID;
+  bgs::LbClipArgs c{};
+  c.a = lb_args(e, mp, init, first, first, count, fr, fg, bg, bits);
+  c.frame_stride = slab * 3, c.fg_stride = slab, c.bits_stride = slab / 64;
+  if (is_lb_som(e->algo)) {
+    // The training schedule of the run's frames, counter advanced per frame as lb_frame does.  Streams of one age share m_K unless
+    // trainingSteps changed between calls that fed them separately: such a run takes the per-frame launches and their table.
+    std::vector<int> mk(count);
+    bool same = true;
+    for (int i = 0; i < count; ++i) {
+      mk[i] = init ? 0 : st.mk[first + i];
+      for (int t = 0; t < fuse; ++t) {
+        double al, ep;
+        lb_som_schedule(mp, mk[i], &al, &ep);
+        if (i == 0) c.alpha_t[t] = al, c.eps_t[t] = ep;
+        same = same && al == c.alpha_t[t] && ep == c.eps_t[t];
+      }
+    }
+    if (!same) {
+      for (int t = 0; t < fuse; ++t) {
+        int rc = lb_frame(e, init && t == 0, first, count, fr + (size_t)t * c.frame_stride, fg ? fg + (size_t)t * c.fg_stride : nullptr,
+                          bg ? bg + (size_t)t * c.frame_stride : nullptr, bits ? bits + (size_t)t * c.bits_stride : nullptr, s);
+        if (rc) return rc;
+      }
+      return BGS_OK;
+    }
+    for (int i = 0; i < count; ++i) st.mk[first + i] = mk[i];
+  }
+  Timed tm(e, s, lb_clip_kernel_name(e->algo));
+  switch (fuse) {
+    case 8: lb_launch_clip<8>(e, s, c); break;
+    case 4: lb_launch_clip<4>(e, s, c); break;
+    case 2: lb_launch_clip<2>(e, s, c); break;
+    default: return fail(BGS_ERR_INVALID, "internal: lb clip run of %d frames", fuse);
+  }
   return BGS_OK;
 }
 
@@ -209,5 +302,6 @@ void lb_reset_stream(bgs_engine* e, int stream) { lb_of(e).mk[stream] = 0; }
 constexpr Family kLb = [] {
   Family f{};
   f.check = lb_check, f.allocate = lb_allocate, f.key = lb_key, f.run = lb_run, f.get_state = lb_get_state, f.reset_stream = lb_reset_stream;
+  f.clip_fused = lb_clip_fused;
   return f;
 }();
