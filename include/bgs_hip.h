@@ -58,7 +58,8 @@ typedef enum bgs_algo {
    * move again: BGS_ALGO_COUNT == 21 (the CPU restatement bounds its defaults table with it), BGS_ALGO_END == 26 (the end marker of
    * the lb/ round), BGS_ALGO_LIMIT == 28 (the end marker of the VuMeter round) and "ids 26 and 28 are not algorithms".  So none of
    * the three counts the classes, ids 26 and 28 are permanent holes, and the end marker every range check uses is BGS_ALGO_LAST,
-   * through BGS_ALGO_KNOWN() below.
+   * through BGS_ALGO_KNOWN() below.  Id 31 is the third hole: the tests of the fuzzy-integral round pinned "id 31 is unknown" by
+   * number, so the T2FGMM pair took 32 and 33.
    * TO ADD A CLASS: declare it after the last one with an explicit value (the old BGS_ALGO_LAST), raise BGS_ALGO_LAST by one, and
    * touch nothing else here - not BGS_ALGO_COUNT, not BGS_ALGO_END, not BGS_ALGO_LIMIT, not the holes.  The tests of the round that
    * adds the class must pin "id BGS_ALGO_LAST is unknown" through BGS_ALGO_KNOWN() and bgs_create ONLY, never the marker's value: a
@@ -78,11 +79,16 @@ typedef enum bgs_algo {
    * Their parameters are bgs_fuzzy_params, not bgs_params. */
   BGS_FUZZY_SUGENO = 29,          /* FuzzySugenoIntegral::process (USTC_BGS type 21)  package_bgs/tb/FuzzySugenoIntegral.cpp:31-173 */
   BGS_FUZZY_CHOQUET = 30,         /* FuzzyChoquetIntegral::process (USTC_BGS type 22) package_bgs/tb/FuzzyChoquetIntegral.cpp:31-173 */
-  BGS_ALGO_LAST = 31              /* one past the last id; moves with every class added */
+  /* id 31 is a hole (see above) */
+  /* package_bgs/tb type-2 fuzzy GMMs (3-channel frames; output = the high-threshold mask, no background image).  Their parameters
+   * are bgs_t2f_params, not bgs_params. */
+  BGS_T2FGMM_UM = 32,             /* T2FGMM_UM::process (USTC_BGS type 17)            package_bgs/tb/T2FGMM_UM.cpp:29-83 */
+  BGS_T2FGMM_UV = 33,             /* T2FGMM_UV::process (USTC_BGS type 18)            package_bgs/tb/T2FGMM_UV.cpp:29-83 */
+  BGS_ALGO_LAST = 34              /* one past the last id; moves with every class added */
 } bgs_algo;
 
 /* "id is an algorithm": the one range check (bgs_default_params, bgs_create, bgs_node_create) */
-#define BGS_ALGO_KNOWN(id) (((int)(id) >= 0 && (int)(id) < 26) || (int)(id) == 27 || ((int)(id) >= 29 && (int)(id) < (int)BGS_ALGO_LAST))
+#define BGS_ALGO_KNOWN(id) (((int)(id) >= 0 && (int)(id) < 26) || (int)(id) == 27 || ((int)(id) >= 29 && (int)(id) < 31) || ((int)(id) >= 32 && (int)(id) < (int)BGS_ALGO_LAST))
 
 typedef enum bgs_status {
   BGS_OK = 0,
@@ -262,6 +268,23 @@ typedef struct bgs_fuzzy_params {
   double threshold;         /* 0.67 threshold */
 } bgs_fuzzy_params;
 
+/* T2FGMM_UM / T2FGMM_UV (package_bgs/tb/T2FGMM_UM.cpp:19, :99-111), in the wrapper's member types.  A struct of its own, as
+ * bgs_fuzzy_params.  bgs_create gives a T2FGMM engine these defaults whatever bgs_params it was handed.  The wrapper hands the values
+ * to its model object once, on the first frame: they are taken when the geometry is set, and a bgs_set_t2f_params after that
+ * succeeds and leaves the values in force unchanged (bgs_get_t2f_params returns what is in force).  threshold and alpha are narrowed
+ * to float on the way, as T2FGMMParams' accessors do; the high threshold is 2 * (float)threshold.
+ * Refused with BGS_ERR_UNSUPPORTED, the class named: gaussians outside 1..5, a parameter that is not finite as a float, alpha
+ * outside [0, 1) as a float (the reference's sort keys become NaN there and its mode order is qsort's accident), kv == 0 for
+ * T2FGMM_UV, 1-channel frames. */
+typedef struct bgs_t2f_params {
+  uint32_t struct_size;  /* sizeof(bgs_t2f_params) = 40 */
+  double threshold;      /* 9.0  threshold */
+  double alpha;          /* 0.01 alpha */
+  float km;              /* 1.5  km: T2FGMM_UM's factor */
+  float kv;              /* 0.6  kv: T2FGMM_UV's factor */
+  int32_t gaussians;     /* 3    gaussians: modes per pixel, 1..5 */
+} bgs_t2f_params;
+
 /* Largest dp_history_size the PratiMediod kernel is built for (every dist entry then fits in 16 bits: 64 x 255 < 65536). */
 #define BGS_PRATI_MAX_HISTORY 64
 
@@ -288,6 +311,14 @@ int bgs_get_fuzzy_params(const bgs_engine* e, bgs_fuzzy_params* p);
 /* Every refusal of the two classes without an engine and without a device: parameters (p == NULL: the defaults) and, where rows > 0,
  * the frame geometry.  bgs_set_fuzzy_params and bgs_set_geometry run the same checks.  The message names the class. */
 int bgs_fuzzy_check(bgs_algo algo, const bgs_fuzzy_params* p, int rows, int cols, int channels);
+
+/* The T2FGMM classes' own parameters (bgs_t2f_params above); BGS_ERR_INVALID for an engine of any other class. */
+int bgs_t2f_default_params(bgs_t2f_params* p);
+int bgs_set_t2f_params(bgs_engine* e, const bgs_t2f_params* p);
+int bgs_get_t2f_params(const bgs_engine* e, bgs_t2f_params* p);
+/* Every refusal of the two classes without an engine and without a device: parameters (p == NULL: the defaults) and, where rows > 0,
+ * the frame geometry.  The message names the class. */
+int bgs_t2f_check(bgs_algo algo, const bgs_t2f_params* p, int rows, int cols, int channels);
 
 /* Engine options.
  *   BGS_OPT_BORROW_FRAMES  device path of the history-keeping classes (FrameDifference, WeightedMovingMean/Variance):
@@ -510,7 +541,10 @@ const char* bgs_last_error(void);
  * VuMeter: "hist" f32 [binCount][n], the reference's dense histogram planes (whatever the engine keeps internally), "background"
  * u8 [n], "count" int64 [1] = the stream's m_nCount.
  * Fuzzy integrals: "background" f32 [n][3] (BGR), "integral" f32 [n] = the (blurred) integral image of the stream's last detecting
- * frame, "minmax" f32 [2] of that image, "count" int64 [1] = the stream's frameNumber. */
+ * frame, "minmax" f32 [2] of that image, "count" int64 [1] = the stream's frameNumber.
+ * T2FGMM_UM / T2FGMM_UV: "modes" f32 [gaussians*6][n] in the reference's struct order {variance, muR, muG, muB, weight,
+ * significants} (the sixth is recomputed from the stored five for the modes below the pixel's count and reads 0 above it),
+ * "nmodes" u8 [n]. */
 
 /* LBSP 16-bit double-cross descriptors of a whole 8UC3 / 8UC1 image (LBSP.h:50-95,
  * LBSP_16bits_dbcross_{3ch3t,1ch}.i).  d_desc: [rows][cols][channels] uint16; the

@@ -12,6 +12,8 @@ Not the driver's bench line (bench.py is); the numbers go to DESIGN.md §6.
              fresh uniform noise (every bin live: the live-bin kernels' worst case), 8 x 1080p
   --only fuzzy: FuzzySugenoIntegral and FuzzyChoquetIntegral (package_bgs/tb), ms per learning step and per detecting step on S_surv,
              8 x 1080p  (fuzzy_choquet / fuzzy_sugeno: one class, short legs, no calibration: for kernel-trace passes)
+  --only t2f: T2FGMM_UM and T2FGMM_UV (package_bgs/tb) beside DPGrimsonGMM timed in the same process, reference defaults (K = 3), on
+             S_surv, 8 x 1080p: ms per step and ms per frame at clip T = 8
 usage: bench_configs.py [--streams S] [--swizzle 0|1]"""
 import argparse
 import os
@@ -867,6 +869,49 @@ def run_fuzzy(S=8, rows=1080, cols=1920, steps=20, only=None, calibrate=True):
         e.close()
 
 
+def run_t2f(S=8, rows=1080, cols=1920, steps=30, clips=10, age=40):
+    """T2FGMM_UM / T2FGMM_UV beside DPGrimsonGMM (the yardstick: the same control flow with one plane per mode more) in one process,
+    reference defaults (K = 3), on S_surv, byte mask out: kernel ms per single-frame step (mean of `steps`) and per frame of a
+    T = 8 clip launch (mean of `clips` launches / 8).  `dense` is what a step requests when every mode is live and every field
+    changes: K * F * 4 bytes of model in and out, the count byte, 3 of frame, 1 of mask; the kernels store only fields whose bits
+    changed, so the real traffic is below it.  copy_frac is that figure's rate over this process's float4 copy rate."""
+    dev = torch.device("cuda", 0)
+    px = S * rows * cols
+    T = 8
+    copy = capi.calibrate_copy(0, 2 << 30, 0)
+    pool = synth.SurvStreams(S, rows, cols, seed0=4321, device=dev).pool(2 * T)
+    fg = torch.empty((S, rows, cols), dtype=torch.uint8, device=dev)
+    cfg = torch.empty((T, S, rows, cols), dtype=torch.uint8, device=dev)
+    # two rounds over the three classes, a fresh engine each time: the second round shows the spread inside one process
+    for algo, name, F in ((capi.DP_GRIMSON_GMM, "DPGrimsonGMMBGS", 6), (capi.T2FGMM_UM, "T2FGMM_UM", 5), (capi.T2FGMM_UV, "T2FGMM_UV", 5)) * 2:
+        e = Engine(algo, n_streams=S)
+        e.set_geometry(rows, cols, 3)
+        K = e.params.dp_gaussians if algo == capi.DP_GRIMSON_GMM else e.get_t2f_params().gaussians  # the classes' own defaults: the comparison is at equal K or says so
+        dense = 2 * K * F * 4 + 1 + 3 + 1
+        t = 0
+        for _ in range(age):
+            e.process_batch_device(pool[t % (2 * T)], fg, None, None)
+            t += 1
+        torch.cuda.synchronize()
+        e.enable_kernel_timing(True)
+        for _ in range(steps):
+            e.process_batch_device(pool[t % (2 * T)], fg, None, None)
+            t += 1
+        torch.cuda.synchronize()
+        ms, n, kname = e.kernel_timing()
+        ratio = float((fg != 0).float().mean())
+        e.enable_kernel_timing(False)
+        e.enable_kernel_timing(True)
+        for i in range(clips):
+            e.process_clip_device(pool[(i % 2) * T:(i % 2) * T + T], T, cfg, None, None)
+        torch.cuda.synchronize()
+        cms, cn, cname = e.kernel_timing()
+        gbps = dense * px / (ms * 1e-3) / 1e9
+        print("%-16s K=%d %dx%d x%d streams: %.3f ms/step (%s; mean of %d) -> %7.1f Mpix/s; dense %d B/px -> %.0f GB/s = %.2f of copy %.0f GB/s; clip T=8: %.3f ms/launch = %.3f ms/frame (%s; mean of %d); fg ratio %.3f"
+              % (name, K, cols, rows, S, ms, kname, n, px / ms / 1e3, dense, gbps, gbps / copy, copy, cms, cms / T, cname, cn, ratio))
+        e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=8)
@@ -891,6 +936,9 @@ def main():
         return
     if args.only == "fuzzy":
         run_fuzzy(S)
+        return
+    if args.only == "t2f":
+        run_t2f(S)
         return
     if args.only in ("fuzzy_choquet", "fuzzy_sugeno"):
         run_fuzzy(S, steps=5, only="FuzzyChoquetIntegral" if args.only == "fuzzy_choquet" else "FuzzySugenoIntegral", calibrate=False)

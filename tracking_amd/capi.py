@@ -19,10 +19,12 @@ DP_PRATI_MEDIOD, DP_TEXTURE = 19, 20
 LB_SIMPLE_GAUSSIAN, LB_FUZZY_GAUSSIAN, LB_MOG, LB_ADAPTIVE_SOM, LB_FUZZY_ADAPTIVE_SOM = range(21, 26)
 VUMETER = 27  # id 26 is a permanent hole (BGS_ALGO_END is frozen there); BGS_ALGO_LIMIT = 28  # frozen, and id 28 is the second permanent hole
 FUZZY_SUGENO, FUZZY_CHOQUET = 29, 30  # package_bgs/tb fuzzy integrals; their parameters are BgsFuzzyParams, not BgsParams
-ALGO_LAST = 31  # one past the last id
+T2FGMM_UM, T2FGMM_UV = 32, 33  # package_bgs/tb type-2 fuzzy GMMs (id 31 is the third hole); their parameters are BgsT2fParams
+ALGO_LAST = 34  # one past the last id
 ALGO_LIMIT = 28  # frozen, and id 28 is the second permanent hole
 FUZZY_SUGENO, FUZZY_CHOQUET = 29, 30  # package_bgs/tb fuzzy integrals; their parameters are BgsFuzzyParams, not BgsParams
-ALGO_LAST = 31  # one past the last id
+T2FGMM_UM, T2FGMM_UV = 32, 33  # package_bgs/tb type-2 fuzzy GMMs (id 31 is the third hole); their parameters are BgsT2fParams
+ALGO_LAST = 34  # one past the last id
 PRATI_MAX_HISTORY = 64  # BGS_PRATI_MAX_HISTORY
 FG_VALID, BG_VALID = 1, 2
 OPT_BORROW_FRAMES, OPT_MOG2_PIXELS_PER_LANE, OPT_MOG2_TILED, OPT_XCD_SWIZZLE, OPT_PLACEMENT_PROBE, OPT_MOG2_SPARSE, OPT_CLIP_FUSE, OPT_HOST_REGISTER, OPT_MODEL_CHUNK_MB, OPT_MODEL_CHUNK_MIN_MB = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
@@ -111,6 +113,11 @@ class BgsFuzzyParams(C.Structure):
                 ("color_space", C.c_int32), ("option", C.c_int32), ("smooth", C.c_int32), ("reserved_", C.c_int32), ("threshold", C.c_double)]
 
 
+class BgsT2fParams(C.Structure):
+    """struct bgs_t2f_params, field for field (T2FGMM_UM / T2FGMM_UV)."""
+    _fields_ = [("struct_size", C.c_uint32), ("threshold", C.c_double), ("alpha", C.c_double), ("km", C.c_float), ("kv", C.c_float), ("gaussians", C.c_int32)]
+
+
 class BgsError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("libbgs_hip error %d: %s" % (code, text))
@@ -128,6 +135,10 @@ SYMBOLS = [
     ("bgs_set_fuzzy_params", C.c_int, [_P, C.POINTER(BgsFuzzyParams)]),
     ("bgs_get_fuzzy_params", C.c_int, [_P, C.POINTER(BgsFuzzyParams)]),
     ("bgs_fuzzy_check", C.c_int, [C.c_int, C.POINTER(BgsFuzzyParams), C.c_int, C.c_int, C.c_int]),
+    ("bgs_t2f_default_params", C.c_int, [C.POINTER(BgsT2fParams)]),
+    ("bgs_set_t2f_params", C.c_int, [_P, C.POINTER(BgsT2fParams)]),
+    ("bgs_get_t2f_params", C.c_int, [_P, C.POINTER(BgsT2fParams)]),
+    ("bgs_t2f_check", C.c_int, [C.c_int, C.POINTER(BgsT2fParams), C.c_int, C.c_int, C.c_int]),
     ("bgs_set_option", C.c_int, [_P, C.c_int, C.c_int64]),
     ("bgs_set_geometry", C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     ("bgs_process", C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_uint32)]),
@@ -240,6 +251,14 @@ def default_params(algo):
 def fuzzy_default_params(**kw):
     p = BgsFuzzyParams()
     check(lib().bgs_fuzzy_default_params(C.byref(p)))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def t2f_default_params(**kw):
+    p = BgsT2fParams()
+    check(lib().bgs_t2f_default_params(C.byref(p)))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

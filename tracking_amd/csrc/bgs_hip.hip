@@ -36,6 +36,7 @@
 #include "kernel_lb.h"
 #include "kernel_vumeter.h"
 #include "kernel_fuzzy.h"
+#include "kernel_t2f.h"
 #include "kernel_cc.h"
 #include "kernel_dp.h"
 #include "kernel_mog1.h"
@@ -120,7 +121,7 @@ struct VmmRange {
 //  - the frame history ring: process_clip_run, bgs_process and bgs_submit read and write it themselves, so it is a service of the
 //    generic code that the history classes use, not their private state;
 //  - `counter`: the families that have a learning phase counted in frames share it with that one meaning, and bgs_reset_stream clears it;
-//  - p and fz: both may be set before the geometry is known, i.e. before there is a state;
+//  - p, fz and t2f: all may be set before the geometry is known, i.e. before there is a state;
 //  - the knobs, which bgs_create (environment) and bgs_set_option set before allocation.
 struct bgs_engine {
   bgs_algo algo;
@@ -128,6 +129,7 @@ struct bgs_engine {
   std::unique_ptr<FamilyState> model;  // the class's state (null until the geometry is set, and for the frame history classes)
   bgs_params p;
   bgs_fuzzy_params fz{};  // bgs_set_fuzzy_params
+  bgs_t2f_params t2f{};   // bgs_set_t2f_params; frozen once the geometry is set
   int device = 0;
   int n_cu = 256;  // compute units of `device` (allocate): the persistent kernels size their grids by it
   int S = 1;
@@ -428,6 +430,7 @@ int model_allocate(bgs_engine* e, DevPtr<T>& out, size_t bytes) { return model_a
 #include "engine_lb.h"
 #include "engine_vumeter.h"
 #include "engine_fuzzy.h"
+#include "engine_t2f.h"
 
 // an id that BGS_ALGO_KNOWN accepts but no engine class stands behind (BGS_LBSP_DESC is a stand-alone entry point): refused when the geometry is set
 constexpr Family kUnbuilt = [] {
@@ -467,6 +470,8 @@ const Family* family_of(bgs_algo algo) {
     case BGS_VUMETER: return &kVuMeter;
     case BGS_FUZZY_SUGENO:
     case BGS_FUZZY_CHOQUET: return &kFuzzy;
+    case BGS_T2FGMM_UM:
+    case BGS_T2FGMM_UV: return &kT2f;
     case BGS_LBSP_DESC:
     case BGS_ALGO_END:
     case BGS_ALGO_LIMIT:
@@ -940,6 +945,7 @@ int bgs_create(bgs_algo algo, const bgs_params* params, int hip_device, int n_st
   e->lanes.assign(n_streams, bgs_engine::Lane());
   e->last_flags.assign(n_streams, 0);
   e->counter.assign(n_streams, 0);
+  t2f_defaults(&e->t2f);
   fz_defaults(&e->fz);  // a fuzzy engine starts from the constructor's values whatever bgs_params it was handed (bgs_set_fuzzy_params)
   if (const char* env = getenv("BGS_KDE_TRIPS")) e->knob.kde_count_trips = atoi(env) != 0;
   if (const char* env = getenv("BGS_MOG2_COMPLETE")) e->knob.mog2_complete = atoi(env) != 0;
@@ -1003,6 +1009,39 @@ int bgs_get_fuzzy_params(const bgs_engine* e, bgs_fuzzy_params* p) {
   if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
   if (!is_fuzzy(e->algo)) return fail(BGS_ERR_INVALID, "bgs_get_fuzzy_params: algorithm %d is not a fuzzy integral", (int)e->algo);
   *p = e->fz;
+  return BGS_OK;
+}
+
+int bgs_t2f_default_params(bgs_t2f_params* p) {
+  if (!p) return fail(BGS_ERR_INVALID, "params is NULL");
+  t2f_defaults(p);
+  return BGS_OK;
+}
+
+int bgs_set_t2f_params(bgs_engine* e, const bgs_t2f_params* p) {
+  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
+  if (!is_t2f(e->algo)) return fail(BGS_ERR_INVALID, "bgs_set_t2f_params: algorithm %d is not T2FGMM_UM / T2FGMM_UV", (int)e->algo);
+  if (p->struct_size != sizeof(bgs_t2f_params)) return fail(BGS_ERR_INVALID, "bgs_t2f_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_t2f_params));
+  int rc = t2f_check(e->algo, *p);
+  if (rc) return rc;
+  if (!e->n) e->t2f = *p;  // the model object exists once the geometry is set: it keeps what it was built with (T2FGMM_UM.cpp `if(firstTime)`)
+  return BGS_OK;
+}
+
+int bgs_t2f_check(bgs_algo algo, const bgs_t2f_params* p, int rows, int cols, int channels) {
+  if (!is_t2f(algo)) return fail(BGS_ERR_INVALID, "bgs_t2f_check: algorithm %d is not T2FGMM_UM / T2FGMM_UV", (int)algo);
+  bgs_t2f_params d;
+  t2f_defaults(&d);
+  if (p && p->struct_size != sizeof(bgs_t2f_params)) return fail(BGS_ERR_INVALID, "bgs_t2f_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_t2f_params));
+  int rc = t2f_check(algo, p ? *p : d);
+  if (rc || rows <= 0) return rc;
+  return t2f_check_geometry(algo, rows, cols, channels);
+}
+
+int bgs_get_t2f_params(const bgs_engine* e, bgs_t2f_params* p) {
+  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
+  if (!is_t2f(e->algo)) return fail(BGS_ERR_INVALID, "bgs_get_t2f_params: algorithm %d is not T2FGMM_UM / T2FGMM_UV", (int)e->algo);
+  *p = e->t2f;
   return BGS_OK;
 }
 

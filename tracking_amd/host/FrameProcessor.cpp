@@ -20,6 +20,8 @@ FrameProcessor::FrameProcessor()
   wrenGA = nullptr, enableDPWrenGABGS = false;
   pratiMediod = nullptr, enableDPPratiMediodBGS = false;
   textureBGS = nullptr, enableDPTextureBGS = false;
+  type2FuzzyGMM_UM = nullptr, enableT2FGMM_UM = false;
+  type2FuzzyGMM_UV = nullptr, enableT2FGMM_UV = false;
   fuzzySugenoIntegral = nullptr, enableFuzzySugenoIntegral = false;
   fuzzyChoquetIntegral = nullptr, enableFuzzyChoquetIntegral = false;
   lbSimpleGaussian = nullptr, enableLBSimpleGaussian = false;
@@ -57,6 +59,8 @@ void FrameProcessor::init() {  // FrameProcessor.cpp:35-155
   if (enableDPWrenGABGS) wrenGA = new DPWrenGABGS;
   if (enableDPPratiMediodBGS) pratiMediod = new DPPratiMediodBGS;  // :81-88 (DPEigenbackgroundBGS between them is not built)
   if (enableDPTextureBGS) textureBGS = new DPTextureBGS;
+  if (enableT2FGMM_UM) type2FuzzyGMM_UM = new T2FGMM_UM;  // :90-94
+  if (enableT2FGMM_UV) type2FuzzyGMM_UV = new T2FGMM_UV;
   if (enableFuzzySugenoIntegral) fuzzySugenoIntegral = new FuzzySugenoIntegral;  // :102-106
   if (enableFuzzyChoquetIntegral) fuzzyChoquetIntegral = new FuzzyChoquetIntegral;
   if (enableLBSimpleGaussian) lbSimpleGaussian = new LBSimpleGaussian;  // :108-122
@@ -133,6 +137,8 @@ void FrameProcessor::process(const Image& img_input) {  // :169-340
   if (enableDPWrenGABGS) process("DPWrenGABGS", wrenGA, img_prep, img_wrenga);
   if (enableDPPratiMediodBGS) process("DPPratiMediodBGS", pratiMediod, img_prep, img_pramed);  // :217-224
   if (enableDPTextureBGS) process("DPTextureBGS", textureBGS, img_prep, img_texbgs);
+  if (enableT2FGMM_UM) process("T2FGMM_UM", type2FuzzyGMM_UM, img_prep, img_t2fgmm_um);  // :226-230
+  if (enableT2FGMM_UV) process("T2FGMM_UV", type2FuzzyGMM_UV, img_prep, img_t2fgmm_uv);
   if (enableFuzzySugenoIntegral) process("FuzzySugenoIntegral", fuzzySugenoIntegral, img_prep, img_fsi);  // :238-242
   if (enableFuzzyChoquetIntegral) process("FuzzyChoquetIntegral", fuzzyChoquetIntegral, img_prep, img_fci);
   if (enableLBSimpleGaussian) process("LBSimpleGaussian", lbSimpleGaussian, img_prep, img_lb_sg);  // :244-257
@@ -164,6 +170,8 @@ void FrameProcessor::finish() {  // :342-482 (reverse order of init)
   delete lbSimpleGaussian, lbSimpleGaussian = nullptr;
   delete fuzzyChoquetIntegral, fuzzyChoquetIntegral = nullptr;  // :412-416
   delete fuzzySugenoIntegral, fuzzySugenoIntegral = nullptr;
+  delete type2FuzzyGMM_UV, type2FuzzyGMM_UV = nullptr;  // :424-428
+  delete type2FuzzyGMM_UM, type2FuzzyGMM_UM = nullptr;
   delete textureBGS, textureBGS = nullptr;
   delete pratiMediod, pratiMediod = nullptr;
   delete wrenGA, wrenGA = nullptr;
@@ -214,6 +222,8 @@ void FrameProcessor::saveConfig() {  // :496-552 (keys of the classes this build
   fs.writeInt("enableDPWrenGABGS", enableDPWrenGABGS);
   fs.writeInt("enableDPPratiMediodBGS", enableDPPratiMediodBGS);  // :522-524
   fs.writeInt("enableDPTextureBGS", enableDPTextureBGS);
+  fs.writeInt("enableT2FGMM_UM", enableT2FGMM_UM);  // :526-527
+  fs.writeInt("enableT2FGMM_UV", enableT2FGMM_UV);
   fs.writeInt("enableFuzzySugenoIntegral", enableFuzzySugenoIntegral);  // :530-531
   fs.writeInt("enableFuzzyChoquetIntegral", enableFuzzyChoquetIntegral);
   fs.writeInt("enableLBSimpleGaussian", enableLBSimpleGaussian);  // :533-537
@@ -250,6 +260,8 @@ void FrameProcessor::loadConfig() {  // :554-610 (defaults: PreProcessor and Fra
   enableDPWrenGABGS = fs.readInt("enableDPWrenGABGS", false);
   enableDPPratiMediodBGS = fs.readInt("enableDPPratiMediodBGS", false);  // :580-582
   enableDPTextureBGS = fs.readInt("enableDPTextureBGS", false);
+  enableT2FGMM_UM = fs.readInt("enableT2FGMM_UM", false);  // :584-585
+  enableT2FGMM_UV = fs.readInt("enableT2FGMM_UV", false);
   enableFuzzySugenoIntegral = fs.readInt("enableFuzzySugenoIntegral", false);  // :588-589
   enableFuzzyChoquetIntegral = fs.readInt("enableFuzzyChoquetIntegral", false);
   enableLBSimpleGaussian = fs.readInt("enableLBSimpleGaussian", false);  // :591-595

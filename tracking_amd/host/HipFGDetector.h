@@ -64,6 +64,11 @@ class HipFGDetector : public CvFGDetector {
     if (i == 35) bgs = new hipbgs::SigmaDeltaBGS;
     if (i == 36) bgs = new hipbgs::SuBSENSEBGS();
     if (i == 37) bgs = new hipbgs::LOBSTERBGS();
+    switch (i) {  // tb/'s type-2 fuzzy GMMs
+      case 17: bgs = new hipbgs::T2FGMM_UM; break;
+      case 18: bgs = new hipbgs::T2FGMM_UV; break;
+      default: break;
+    }
     if (!bgs) CV_Error(CV_StsBadArg, "HipFGDetector: this type is outside the package_bgs hot path libbgs_hip covers");
   }
   ~HipFGDetector() {}

@@ -2,9 +2,12 @@
 // cvCreateBlobTrackerAuto1 (ustc_src/trackingMain.cpp:33-35, :613-618; the shipped build uses type 36 = SuBSENSE).
 // Same type table, same Process / GetMask / Release protocol; OpenCV-legacy's CvFGDetector base and IplImage are not in this
 // image, so the mask is handed out as a bgs_hip::Image (INTEGRATION.md shows the IplImage-returning version for the reference).
-// Types whose class is outside the hot path (ustc_bgs.cpp:23-58: dp Eigenbackground, tb/'s T2FGMM and T2FMRF pairs, jmo/, LbpMrf,
-// ck/, db/, sjn/; of ae/ only KDE, type 32, of lb/ the five per-pixel models, types 25-29, av/'s VuMeter, type 31, and of tb/ the two
-// fuzzy integrals, types 21 and 22, are built) throw instead of silently running something else.
+// Types whose class is outside the hot path (ustc_bgs.cpp:23-58: dp Eigenbackground, tb/'s T2FMRF pair, jmo/, LbpMrf, ck/, db/,
+// sjn/; of ae/ only KDE, type 32, of lb/ the five per-pixel models, types 25-29, av/'s VuMeter, type 31, and of tb/ the two fuzzy
+// integrals, types 21 and 22, and the two type-2 fuzzy GMMs, types 17 and 18, are built) throw instead of silently running something
+// else.  T2FMRF_UM / T2FMRF_UV (19, 20) stay refused on purpose: T2FMRF.cpp:331 reads the weights of ANOTHER pixel's modes, so the
+// result depends on pixel order, and the MRF result goes into the low-threshold mask, which the wrapper clears before it returns
+// the high-threshold one.
 #pragma once
 #include "bgs_host.h"
 #include "blob.h"
@@ -48,6 +51,11 @@ class USTC_BGS {
     if (i == 35) bgs = new SigmaDeltaBGS;
     if (i == 36) bgs = new SuBSENSEBGS();
     if (i == 37) bgs = new LOBSTERBGS();
+    switch (i) {  // tb/'s type-2 fuzzy GMMs
+      case 17: bgs = new T2FGMM_UM; break;
+      case 18: bgs = new T2FGMM_UV; break;
+      default: break;
+    }
     if (!bgs) throw Exception(BGS_ERR_UNSUPPORTED, "USTC_BGS: type " + std::to_string(i) + " is outside the package_bgs hot path built here");
   }
   ~USTC_BGS() {}
