@@ -108,6 +108,69 @@ def test_fused_clip_path_matches_reference_fixture(cls, case):
     eng.close()
 
 
+@pytest.mark.parametrize("cls", ["ziv", "grim"])
+def test_write_back_gives_the_same_bytes_frame_by_frame_fused_and_unfused(cls):
+    """alpha06_k4 (40 frames of 8 x 14, K = 4, alpha 0.6) three ways: one process_batch_device call per frame, process_clip_device in
+    calls of 8 frames (one launch each, the model in registers), and the same calls with BGS_OPT_CLIP_FUSE 0.  Every mask and the
+    model equal the fixture's, and the raw bytes of `modes` and `nmodes` are the same in all three, slots above the count included:
+    the write-back rule (a field is stored if its bits changed, or if its slot was not loaded and was in use after ANY frame of the
+    launch).  ziv: the counts read after every frame must show, in every run of 8, a pixel whose count peaks above both its value at
+    the run's start and at its end - a slot that comes into use and is pruned again inside one launch, which only that rule writes.
+    grim never shrinks a count at an alpha in [0, 1): there the K = 4 sort and the stale `significants` above the count are pinned."""
+    torch = _torch()
+    r = dp_ref.load(cls)["alpha06_k4"]
+    p = r["params"]
+    T, H, W = r["masks"].shape
+    n, NC = H * W, 8
+    assert (T, H, W, p["gaussians"]) == (40, 8, 14, 4)
+    shape, _ = dp_ref.plane_shape(cls, "modes", p, n)
+    d_all = torch.from_numpy(np.array(r["frames"][:, None])).cuda()  # [T][1][H][W][3]
+
+    def engine():
+        eng = Engine(dp_ref.CLASSES[cls][1], params=dp_ref.engine_params(cls, p))
+        eng.set_geometry(H, W, 3)
+        eng.enable_kernel_timing(True)
+        return eng
+
+    def finish(eng, launches, where):
+        _, nl, name = eng.kernel_timing()
+        assert (nl, name) == (launches, "dp_gmm_kernel"), (where, nl, name)
+        check_planes(cls, eng, r["planes"], p, n, where="alpha06_k4 " + where)
+        model = eng.get_state("modes", shape, np.float32).tobytes(), eng.get_state("nmodes", (n,), np.uint8).tobytes()
+        eng.close()
+        return model
+
+    eng = engine()
+    counts = np.zeros((T + 1, n), np.int64)  # counts[t + 1]: after frame t
+    for t in range(T):
+        d_fg = torch.full((1, H, W), 9, dtype=torch.uint8, device="cuda")
+        assert eng.process_batch_device(d_all[t], d_fg, None, None) == capi.FG_VALID
+        torch.cuda.synchronize()
+        assert np.array_equal(d_fg.cpu().numpy()[0], r["masks"][t]), (t, "frame by frame")
+        counts[t + 1] = eng.get_state("nmodes", (n,), np.uint8)
+    models = {"frame by frame": finish(eng, T, "frame by frame")}
+    if cls == "ziv":
+        for t0 in range(0, T, NC):
+            peak = counts[t0 + 1:t0 + NC + 1].max(axis=0)
+            came_and_went = int(((peak > counts[t0]) & (peak > counts[t0 + NC])).sum())
+            print("ziv frames %d-%d: %d of %d pixels bring a slot into use and lose it again" % (t0, t0 + NC - 1, came_and_went, n))
+            assert came_and_went >= 1, t0
+    for fuse, launches in ((1, T // NC), (0, T)):
+        eng = engine()
+        eng.set_option(capi.OPT_CLIP_FUSE, fuse)
+        for t0 in range(0, T, NC):
+            d_fg = torch.full((NC, 1, H, W), 9, dtype=torch.uint8, device="cuda")
+            flags = eng.process_clip_device(d_all[t0:t0 + NC], NC, d_fg, None, None)
+            torch.cuda.synchronize()
+            assert flags == [capi.FG_VALID] * NC
+            fg = d_fg.cpu().numpy()[:, 0]
+            assert np.array_equal(fg, r["masks"][t0:t0 + NC]), (fuse, t0, int((fg != r["masks"][t0:t0 + NC]).sum()))
+        assert eng.frames_seen(0) == T
+        models["fuse %d" % fuse] = finish(eng, launches, "fuse %d" % fuse)
+    for where, model in models.items():
+        assert model == models["frame by frame"], "%s: modes / nmodes bytes differ from the frame-by-frame run" % where
+
+
 @pytest.mark.parametrize("case,form", [("tile", 4), ("tile_t130", 4), ("tile_t300", 4), ("ragged", 1), ("ragged_t130", 1), ("ragged_t300", 1)])
 def test_both_median_kernel_forms_on_device_buffers(case, form):
     """dp_median_kernel<4> (pixel count a multiple of 4, torch's aligned buffers) and dp_median_kernel<1> through the device path,

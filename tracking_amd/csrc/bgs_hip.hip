@@ -671,8 +671,9 @@ int process_run(bgs_engine* e, int first, int count, const uint8_t* d_frames, ui
 
 
 // bgs_process_clip_device: `nframes` consecutive frames of streams [first, first+count).  Every algorithm: frame by frame
-// through process_range (the same launches as nframes range calls).  Families with a clip_fused entry (MOG2, MOG1, the dp GMMs, the five lb/ classes): runs
-// of 8 / 4 / 2 frames go through ONE launch that keeps the model in registers; what is left over takes the single-frame kernel.
+// through process_range (the same launches as nframes range calls).  Families with a clip_fused entry (MOG2, MOG1, the dp GMMs,
+// T2FGMM_UM / T2FGMM_UV, the five lb/ classes): runs of 8 / 4 / 2 frames go through ONE launch that keeps the model in registers;
+// what is left over takes the single-frame kernel.
 int process_clip_run(bgs_engine* e, int first, int count, int slab_count, int nframes, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits,
                      hipStream_t s, uint32_t* out_flags);
 

@@ -17,15 +17,36 @@ int dp_planes_of(const bgs_engine* e) {
   }
 }
 
-template <bool GRIMSON>
-void dp_launch_gmm(int K, unsigned blocks, hipStream_t s, const bgs::DpArgs& a) {
+// calls fn(std::integral_constant<int, K>) for the 1..5 gaussians the tiled GMM kernels are built for (dp_check, t2f_check)
+template <class Fn>
+void dp_for_gaussians(int K, Fn fn) {
   switch (K) {
-    case 1: hipLaunchKernelGGL((bgs::dp_gmm_kernel<1, GRIMSON>), dim3(blocks), dim3(bgs::kBlock), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((bgs::dp_gmm_kernel<2, GRIMSON>), dim3(blocks), dim3(bgs::kBlock), 0, s, a); break;
-    case 3: hipLaunchKernelGGL((bgs::dp_gmm_kernel<3, GRIMSON>), dim3(blocks), dim3(bgs::kBlock), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((bgs::dp_gmm_kernel<4, GRIMSON>), dim3(blocks), dim3(bgs::kBlock), 0, s, a); break;
-    default: hipLaunchKernelGGL((bgs::dp_gmm_kernel<5, GRIMSON>), dim3(blocks), dim3(bgs::kBlock), 0, s, a); break;
+    case 1: fn(std::integral_constant<int, 1>()); break;
+    case 2: fn(std::integral_constant<int, 2>()); break;
+    case 3: fn(std::integral_constant<int, 3>()); break;
+    case 4: fn(std::integral_constant<int, 4>()); break;
+    default: fn(std::integral_constant<int, 5>()); break;
   }
+}
+
+// dp_gmm_kernel<K, Model<second>>: Model = bgs::DpGmmModel (Zivkovic / Grimson) or bgs::T2fModel (UM / UV)
+template <template <bool> class Model, class Args>
+void dp_launch_gmm(int K, bool second, unsigned blocks, hipStream_t s, const Args& args) {
+  dp_for_gaussians(K, [&](auto k) {
+    auto kernel = second ? bgs::dp_gmm_kernel<decltype(k)::value, Model<true>> : bgs::dp_gmm_kernel<decltype(k)::value, Model<false>>;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(bgs::kBlock), 0, s, args);
+  });
+}
+
+// what every launch on the tiled state is told: `frames` frames for streams [first, first+count), slab = pixels from one frame of a
+// clip to the next; the thresholds, alpha and update are the caller's
+bgs::DpArgs dp_args(const bgs_engine* e, int first, int count, int frames, size_t slab, const uint8_t* d_frames, float* planes, uint8_t* bstate, uint8_t* d_fg, uint64_t* d_bits) {
+  bgs::DpArgs a{};
+  a.frames = frames, a.frame_stride = slab * 3, a.fg_stride = slab, a.bits_stride = slab / 64;
+  a.frame = d_frames, a.state = planes, a.bstate = bstate, a.fg = d_fg, a.fg_bits = d_bits;
+  a.n = e->n, a.npix = e->n * count, a.first = first;
+  a.xcd_swizzle = e->knob.xcd_swizzle;
+  return a;
 }
 
 int dp_check(bgs_algo algo, const bgs_params& p) {
@@ -86,13 +107,9 @@ int dp_process(bgs_engine* e, int first, int count, int frames, size_t slab, con
   const bgs_params& p = e->p;
   const DpState& st = dp_of(e);
   const int64_t t = e->seen[first];
-  bgs::DpArgs a{};
-  a.frames = frames, a.frame_stride = slab * 3, a.fg_stride = slab, a.bits_stride = slab / 64;
-  a.frame = d_frames, a.state = st.planes, a.bstate = dp_is_gmm(e) ? st.nmodes : st.median, a.fg = d_fg, a.fg_bits = d_bits;
-  a.n = e->n, a.npix = e->n * count, a.first = first;
+  bgs::DpArgs a = dp_args(e, first, count, frames, slab, d_frames, st.planes, dp_is_gmm(e) ? st.nmodes : st.median, d_fg, d_bits);
   dp_thresholds(e->algo, p.dp_threshold, &a.low, &a.high);  // HighThreshold = 2*LowThreshold, e.g. DPZivkovicAGMMBGS.cpp:58
   a.alpha = p.dp_alpha;
-  a.update = 0, a.xcd_swizzle = e->knob.xcd_swizzle;
   const unsigned blocks = blocks_for(a.npix);
   if (t == 0 && (e->algo == BGS_DP_ZIVKOVIC_AGMM || e->algo == BGS_DP_GRIMSON_GMM))  // InitModel: all modes and counts 0
     hipLaunchKernelGGL(bgs::dp_gmm_clear_kernel, dim3(blocks), dim3(bgs::kBlock), 0, s, a, dp_planes_of(e));
@@ -101,14 +118,10 @@ int dp_process(bgs_engine* e, int first, int count, int frames, size_t slab, con
   if (t == 0 && e->algo == BGS_DP_ADAPTIVE_MEDIAN)
     HIP_TRY(hipMemcpyAsync(st.median + (size_t)first * e->n * 3, d_frames, a.npix * 3, hipMemcpyDeviceToDevice, s));
   switch (e->algo) {
-    case BGS_DP_ZIVKOVIC_AGMM: {
-      Timed tm(e, s, "dp_gmm_kernel");
-      dp_launch_gmm<false>(p.dp_gaussians, blocks, s, a);
-      break;
-    }
+    case BGS_DP_ZIVKOVIC_AGMM:
     case BGS_DP_GRIMSON_GMM: {
       Timed tm(e, s, "dp_gmm_kernel");
-      dp_launch_gmm<true>(p.dp_gaussians, blocks, s, a);
+      dp_launch_gmm<bgs::DpGmmModel>(p.dp_gaussians, e->algo == BGS_DP_GRIMSON_GMM, blocks, s, a);
       break;
     }
     case BGS_DP_WREN_GA: {
@@ -145,18 +158,30 @@ int dp_clip_fused(bgs_engine* e, int first, int count, int fuse, size_t slab, co
   return dp_process(e, first, count, fuse, slab, fr, fg, bits, s, flags);
 }
 
+// the tiles of a tiled state of `planes` planes (kernel_dp.h) that hold one stream, fetched to the host
+struct DpTiles {
+  std::vector<float> tiles;
+  size_t g0, t0, TF;
+  float at(int plane, size_t i) const {
+    const size_t g = g0 + i, T = bgs::kDpTile;
+    return tiles[(g / T - t0) * TF + (size_t)plane * T + g % T];
+  }
+};
+int dp_fetch_tiles(const bgs_engine* e, int stream, int planes, const float* d_planes, DpTiles* out) {
+  const size_t n = e->n, T = bgs::kDpTile;
+  out->g0 = (size_t)stream * n, out->t0 = out->g0 / T, out->TF = (size_t)planes * T;
+  out->tiles.resize(((out->g0 + n - 1) / T + 1 - out->t0) * out->TF);
+  return fetch(out->tiles.data(), d_planes + out->t0 * out->TF, out->tiles.size() * 4);
+}
+
 // canonical export [plane][n] of one stream from the tiled device layout
 int64_t dp_export_planes(bgs_engine* e, int stream, int planes, void* dst, size_t cap) {
-  const size_t n = e->n, g0 = (size_t)stream * n, T = bgs::kDpTile;
+  const size_t n = e->n;
   if (cap < (size_t)planes * n * 4) return fail(BGS_ERR_STATE, "buffer too small for %d planes", planes);
-  const size_t t0 = g0 / T, t1 = (g0 + n - 1) / T + 1, TF = (size_t)planes * T;
-  std::vector<float> tiles((t1 - t0) * TF);
-  if (fetch(tiles.data(), dp_of(e).planes + t0 * TF, tiles.size() * 4)) return BGS_ERR_HIP;
+  DpTiles tiles;
+  if (dp_fetch_tiles(e, stream, planes, dp_of(e).planes, &tiles)) return BGS_ERR_HIP;
   for (int q = 0; q < planes; ++q)
-    for (size_t i = 0; i < n; ++i) {
-      const size_t g = g0 + i;
-      ((float*)dst)[(size_t)q * n + i] = tiles[(g / T - t0) * TF + (size_t)q * T + g % T];
-    }
+    for (size_t i = 0; i < n; ++i) ((float*)dst)[(size_t)q * n + i] = tiles.at(q, i);
   return (int64_t)planes * n * 4;
 }
 

@@ -40,17 +40,6 @@ int t2f_check_geometry(bgs_algo algo, int, int, int ch) {
   return BGS_OK;
 }
 
-template <bool UV>
-void t2f_launch(int K, unsigned blocks, hipStream_t s, const bgs::T2fArgs& a) {
-  switch (K) {
-    case 1: hipLaunchKernelGGL((bgs::t2f_gmm_kernel<1, UV>), dim3(blocks), dim3(bgs::kBlock), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((bgs::t2f_gmm_kernel<2, UV>), dim3(blocks), dim3(bgs::kBlock), 0, s, a); break;
-    case 3: hipLaunchKernelGGL((bgs::t2f_gmm_kernel<3, UV>), dim3(blocks), dim3(bgs::kBlock), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((bgs::t2f_gmm_kernel<4, UV>), dim3(blocks), dim3(bgs::kBlock), 0, s, a); break;
-    default: hipLaunchKernelGGL((bgs::t2f_gmm_kernel<5, UV>), dim3(blocks), dim3(bgs::kBlock), 0, s, a); break;
-  }
-}
-
 int t2f_allocate(bgs_engine* e) {
   const bgs_t2f_params& p = e->t2f;  // the defaults or what passed t2f_check in bgs_set_t2f_params: nothing to refuse here
   const size_t P = e->n * e->S;
@@ -71,20 +60,14 @@ int t2f_process(bgs_engine* e, int first, int count, int frames, size_t slab, co
   const T2fState& st = t2f_of(e);
   bgs::T2fArgs ta{};
   bgs::DpArgs& a = ta.d;
-  a.frames = frames, a.frame_stride = slab * 3, a.fg_stride = slab, a.bits_stride = slab / 64;
-  a.frame = d_frames, a.state = st.planes, a.bstate = st.nmodes, a.fg = d_fg, a.fg_bits = d_bits;
-  a.n = e->n, a.npix = e->n * count, a.first = first;
+  a = dp_args(e, first, count, frames, slab, d_frames, st.planes, st.nmodes, d_fg, d_bits);
   a.low = st.low, a.high = st.high, a.alpha = st.alpha;
-  a.xcd_swizzle = e->knob.xcd_swizzle;
   ta.km = st.km, ta.kv = st.kv;
   const unsigned blocks = blocks_for(a.npix);
   if (e->seen[first] == 0)  // InitModel: every mode field and every count 0 (T2FGMM.cpp:86-99)
     hipLaunchKernelGGL(bgs::dp_gmm_clear_kernel, dim3(blocks), dim3(bgs::kBlock), 0, s, a, st.K * 5);
   Timed tm(e, s, frames > 1 ? "t2f_gmm_kernel (clip: the model stays in registers)" : "t2f_gmm_kernel");
-  if (e->algo == BGS_T2FGMM_UV)
-    t2f_launch<true>(st.K, blocks, s, ta);
-  else
-    t2f_launch<false>(st.K, blocks, s, ta);
+  dp_launch_gmm<bgs::T2fModel>(st.K, e->algo == BGS_T2FGMM_UV, blocks, s, ta);
   *flags = BGS_FG_VALID;  // img_bgmodel is never written by the wrappers
   return BGS_OK;
 }
@@ -101,25 +84,21 @@ int t2f_clip_fused(bgs_engine* e, int first, int count, int fuse, size_t slab, c
 // (kernel_t2f.h) and is recomputed here for the modes below the pixel's count, 0 above it.  "nmodes": [n] bytes.
 int64_t t2f_get_state(bgs_engine* e, int stream, const char* plane, void* dst, size_t cap) {
   const T2fState& st = t2f_of(e);
-  const size_t n = e->n, T = bgs::kDpTile;
+  const size_t n = e->n;
   if (!strcmp(plane, "nmodes")) return copy_plane(plane, dst, cap, st.nmodes + n * stream, n);
   if (strcmp(plane, "modes")) return unknown_plane(e, plane);
-  const int K = st.K, planes = K * 5;
+  const int K = st.K;
   if (cap < (size_t)K * 6 * n * 4) return too_small(plane);
-  const size_t g0 = (size_t)stream * n, t0 = g0 / T, t1 = (g0 + n - 1) / T + 1, TF = (size_t)planes * T;
-  std::vector<float> tiles((t1 - t0) * TF);
+  DpTiles tiles;
   std::vector<uint8_t> cnt(n);
-  if (fetch(tiles.data(), st.planes + t0 * TF, tiles.size() * 4) || fetch(cnt.data(), st.nmodes + g0, n)) return BGS_ERR_HIP;
+  if (dp_fetch_tiles(e, stream, K * 5, st.planes, &tiles) || fetch(cnt.data(), st.nmodes + n * stream, n)) return BGS_ERR_HIP;
   float* out = (float*)dst;
-  for (size_t i = 0; i < n; ++i) {
-    const size_t g = g0 + i;
-    const float* px = &tiles[(g / T - t0) * TF + g % T];
+  for (size_t i = 0; i < n; ++i)
     for (int k = 0; k < K; ++k) {
-      for (int f = 0; f < 5; ++f) out[(size_t)(k * 6 + f) * n + i] = px[(size_t)(k * 5 + f) * T];
-      const float var = px[(size_t)(k * 5) * T], w = px[(size_t)(k * 5 + 4) * T];
+      for (int f = 0; f < 5; ++f) out[(size_t)(k * 6 + f) * n + i] = tiles.at(k * 5 + f, i);
+      const float var = tiles.at(k * 5, i), w = tiles.at(k * 5 + 4, i);
       out[(size_t)(k * 6 + 5) * n + i] = k < cnt[i] ? w / std::sqrt(var) : 0.0f;  // float sqrt and divide, as the source's
     }
-  }
   return (int64_t)K * 6 * n * 4;
 }
 

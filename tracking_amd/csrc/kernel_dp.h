@@ -1,7 +1,7 @@
 // kernel_dp.h — SURVEY.md N4: the in-tree package_bgs/dp/ background models, one fused kernel each.
 //
-//   dp_gmm_kernel<K, false>  ZivkovicAGMM::SubtractPixel  package_bgs/dp/ZivkovicAGMM.cpp:103-364  (DPZivkovicAGMMBGS.cpp:29-80)
-//   dp_gmm_kernel<K, true>   GrimsonGMM::SubtractPixel    package_bgs/dp/GrimsonGMM.cpp:119-295    (DPGrimsonGMMBGS.cpp:29-82)
+//   dp_gmm_kernel<K, DpGmmModel<false>>  ZivkovicAGMM::SubtractPixel  package_bgs/dp/ZivkovicAGMM.cpp:103-364  (DPZivkovicAGMMBGS.cpp:29-80)
+//   dp_gmm_kernel<K, DpGmmModel<true>>   GrimsonGMM::SubtractPixel    package_bgs/dp/GrimsonGMM.cpp:119-295    (DPGrimsonGMMBGS.cpp:29-82)
 //   dp_wren_kernel           WrenGA::SubtractPixel + Update  package_bgs/dp/WrenGA.cpp:79-134       (DPWrenGABGS.cpp:29-81)
 //   dp_mean_kernel           MeanBGS::SubtractPixel + Update package_bgs/dp/MeanBGS.cpp:52-98       (DPMeanBGS.cpp:29-82)
 //   dp_median_kernel         AdaptiveMedianBGS::SubtractPixel + Update  dp/AdaptiveMedianBGS.cpp:58-108 (DPAdaptiveMedianBGS.cpp:29-81)
@@ -52,219 +52,266 @@ __device__ __forceinline__ void dp_store_mask(const DpArgs& a, size_t gp, bool a
   }
 }
 
-template <int K, bool GRIMSON>
-__global__ __launch_bounds__(kBlock) void dp_gmm_kernel(const DpArgs a) {
-  constexpr int F = GRIMSON ? 6 : 5;
-  // field order inside a mode = the source's struct: Zivkovic {sigma, muR, muG, muB, weight}, Grimson {variance, muR, muG, muB, weight, significants}
+// ---- the tiled GMMs: Zivkovic, Grimson and kernel_t2f.h's T2FGMM, one register-resident scaffold for the three ----
+// T2FGMM::SubtractPixel (tb/T2FGMM.cpp) is GrimsonGMM::SubtractPixel around another match distance, with a mean update that subtracts
+// k * |d| and a sort key that never needs storing (kernel_t2f.h): it has Grimson's six fields per mode, five of them planes.
+enum DpGmm { kDpZivkovic, kDpGrimson, kDpT2f };
+
+// What a model brings to dp_gmm_kernel: its kernel argument type (with the DpArgs inside it), which of the three sources it follows,
+// and the source's match distance of one mode, which also leaves in d what the mean update multiplies by k.
+template <bool GRIMSON>
+struct DpGmmModel {  // ZivkovicAGMM / GrimsonGMM: the squared distance, d = mean - pixel
+  using Args = DpArgs;
+  static constexpr DpGmm kSource = GRIMSON ? kDpGrimson : kDpZivkovic;
+  __device__ __forceinline__ explicit DpGmmModel(const Args&) {}
+  __device__ __forceinline__ static const DpArgs& dp(const Args& args) { return args; }
+  __device__ __forceinline__ float distance(const float (&mu)[3], float, const float (&px)[3], float (&d)[3]) const {
+    d[0] = mu[0] - px[0], d[1] = mu[1] - px[1], d[2] = mu[2] - px[2];
+    return (d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+  }
+};
+
+// One lane = one pixel of the launch, `a.frames` frames of it (clip launches: the model stays in registers in between).
+// The whole scaffold is the body of the kernel itself, the shared steps lambdas over its local arrays: moved into a function of its
+// own - even an inlined one - the same statements cost up to six VGPRs and an occupancy step (T2FGMM_UV at K = 3 and 5).
+template <int K, class Model>
+__global__ __launch_bounds__(kBlock) void dp_gmm_kernel(const typename Model::Args args) {
+  const DpArgs& a = Model::dp(args);
+  const Model model(args);
+  constexpr DpGmm MODEL = Model::kSource;
+  constexpr bool ZIVKOVIC = MODEL == kDpZivkovic, GRIMSON = MODEL == kDpGrimson, T2F = MODEL == kDpT2f;
+  constexpr int F = GRIMSON ? 6 : 5;  // planes per mode
+  // field order inside a mode = the source's struct: Zivkovic {sigma, muR, muG, muB, weight}, Grimson / T2FGMM {variance, muR, muG, muB, weight, significants}
   constexpr int VAR = 0, MU = 1, WEIGHT = 4, SIG = 5;
   const size_t gp = xcd_block(a.xcd_swizzle) * kBlock + threadIdx.x;
   const bool active = gp < a.npix;
-  const int T = a.frames > 0 ? a.frames : 1;  // frames of this launch (clip launches: the model stays in registers in between)
+  const int T = a.frames > 0 ? a.frames : 1;
   float* st = nullptr;
   uint8_t* pn = nullptr;
   int nModes = 0, nLoaded = 0, nUsed = 0;
-  float g[K][F];
+  float g[K][F], sig[K];  // sig: T2FGMM's sort key (unused by the other two)
   uint32_t g0[K][F];
+  // three packed bytes of the pixel in frame t of the launch
+  auto fetch_pixel = [&](int t) {
+    const uint8_t* p = a.frame + (size_t)t * a.frame_stride + gp * 3;
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+  };
   uint32_t pw = 0;
   if (active) {
     st = dp_plane0(a, gp, K * F);
     pn = a.bstate + (size_t)a.first * a.n + gp;
-    pw = (uint32_t)a.frame[gp * 3] | ((uint32_t)a.frame[gp * 3 + 1] << 8) | ((uint32_t)a.frame[gp * 3 + 2] << 16);
-    // Data-dependent traffic (exact): the sources never read a mode at an index >= the pixel's count (they only create one
-    // there, writing every field), so only the used modes are loaded; at the end a field is stored if its bits changed, or
-    // unconditionally when the slot was not loaded and is now in use.  One lane = one pixel: no neighbour shares the slot.
+    pw = fetch_pixel(0);
+    // Data-dependent traffic (exact): the sources never read a mode at an index >= the pixel's count (they only create one there,
+    // writing every field), so only the used modes are loaded, and g0 keeps their bits.  One lane = one pixel: no neighbour shares the slot.
     nModes = *pn;
     nLoaded = nModes;
 #pragma unroll
-    for (int k = 0; k < K; ++k)
+    for (int k = 0; k < K; ++k) {
+      if constexpr (T2F) sig[k] = 0.f;
 #pragma unroll
       for (int f = 0; f < F; ++f) {
         g[k][f] = k < nLoaded ? st[(k * F + f) * kDpTile] : 0.f;
         g0[k][f] = __float_as_uint(g[k][f]);
       }
+    }
   }
+  // the sort key: Grimson keeps `significants` in its sixth plane, T2FGMM in registers
+  auto key = [&](int k) -> float& {
+    if constexpr (T2F)
+      return sig[k];
+    else
+      return g[k][F - 1];
+  };
+  auto swap = [&](int x, int y) {
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+      const float tmp = g[x][f];
+      g[x][f] = g[y][f], g[y][f] = tmp;
+    }
+    if constexpr (T2F) {
+      const float ts = sig[x];
+      sig[x] = sig[y], sig[y] = ts;
+    }
+  };
   for (int t = 0; t < T; ++t) {
-  int mask = 0;
-  if (active) {
-    const float px[3] = {(float)(pw & 0xffu), (float)((pw >> 8) & 0xffu), (float)(pw >> 16)};
-    if (t + 1 < T) {  // the next frame's pixel, requested before this frame's arithmetic
-      const uint8_t* nf = a.frame + (size_t)(t + 1) * a.frame_stride + gp * 3;
-      pw = (uint32_t)nf[0] | ((uint32_t)nf[1] << 8) | ((uint32_t)nf[2] << 16);
-    }
-    const float m_bg_threshold = 0.75f, m_variance = 36.0f, m_complexity_prior = 0.05f;
-    const float Alpha = a.alpha;
-    bool bFitsPDF = false, bBackgroundHigh = false;
-    const float fOneMinAlpha = 1 - Alpha;
-    const float prune = -Alpha * m_complexity_prior;  // Zivkovic only
-    float totalWeight = 0.0f;
-    int backgroundGaussians = 0;
-    {
-      double sum = 0.0;
-      bool stop = false;
-#pragma unroll
-      for (int k = 0; k < K; ++k)
-        if (k < nModes && !stop) {
-          if (sum < (double)m_bg_threshold) {
-            backgroundGaussians++;
-            sum = __dadd_rn(sum, (double)g[k][WEIGHT]);
-          } else
-            stop = true;
-        }
-    }
-    auto swap_modes = [&](float(&x)[F], float(&y)[F]) {
-#pragma unroll
-      for (int f = 0; f < F; ++f) {
-        const float t = x[f];
-        x[f] = y[f], y[f] = t;
-      }
-    };
-#pragma unroll
-    for (int im = 0; im < K; ++im) {
-      if (im < nModes) {  // nModes shrinks inside the loop, as in the source
-        float weight = g[im][WEIGHT];
-        if (!bFitsPDF) {
-          const float var = g[im][VAR], muR = g[im][MU], muG = g[im][MU + 1], muB = g[im][MU + 2];
-          const float dR = muR - px[0], dG = muG - px[1], dB = muB - px[2];
-          const float dist = (dR * dR + dG * dG + dB * dB);
-          if (dist < a.high * var && im < backgroundGaussians) bBackgroundHigh = true;
-          if (dist < a.low * var) {
-            bFitsPDF = true;
-            const float k = div_rn(Alpha, weight);
-            if constexpr (GRIMSON) {
-              weight = fOneMinAlpha * weight + Alpha;
-            } else {
-              weight = fOneMinAlpha * weight + prune;
-              weight += Alpha;
-            }
-            g[im][WEIGHT] = weight;
-            g[im][MU] = muR - k * (dR);
-            g[im][MU + 1] = muG - k * (dG);
-            g[im][MU + 2] = muB - k * (dB);
-            const float sigmanew = var + k * (dist - var);
-            g[im][VAR] = sigmanew < 4 ? 4 : sigmanew > 5 * m_variance ? 5 * m_variance : sigmanew;
-            if constexpr (GRIMSON) {
-              g[im][SIG] = div_rn(g[im][WEIGHT], sqrt_rn(g[im][VAR]));
-            } else {
-              bool stop = false;  // ZivkovicAGMM.cpp:219-234: move the grown mode up while it outweighs its predecessor
-#pragma unroll
-              for (int il = im; il > 0; --il)
-                if (!stop) {
-                  if (g[il][WEIGHT] > g[il - 1][WEIGHT])
-                    swap_modes(g[il], g[il - 1]);
-                  else
-                    stop = true;
-                }
-            }
-          } else {
-            if constexpr (GRIMSON) {
-              weight = fOneMinAlpha * weight;
-              if (weight < 0.0f) weight = 0.0f, nModes--;
-              g[im][WEIGHT] = weight;
-              g[im][SIG] = div_rn(weight, sqrt_rn(g[im][VAR]));
-            } else {
-              weight = fOneMinAlpha * weight + prune;
-              if (weight < -prune) weight = 0.0f, nModes--;
-              g[im][WEIGHT] = weight;
-            }
-          }
-        } else {
-          if constexpr (GRIMSON) {
-            weight = fOneMinAlpha * weight;
-            if (weight < 0.0f) weight = 0.0f, nModes--;
-            g[im][WEIGHT] = weight;
-            g[im][SIG] = div_rn(weight, sqrt_rn(g[im][VAR]));
-          } else {
-            weight = fOneMinAlpha * weight + prune;
-            if (weight < -prune) weight = 0.0f, nModes--;
-            g[im][WEIGHT] = weight;
-          }
-        }
-        totalWeight += weight;
-      }
-    }
-    // stable insertion by adjacent swaps, largest `significants` first (qsort + compareGMM, GrimsonGMM.cpp:45-56)
-    auto grimson_sort = [&](int count) {
-#pragma unroll
-      for (int i2 = 1; i2 < K; ++i2)
-        if (i2 < count) {
-          bool stop = false;
-#pragma unroll
-          for (int j = i2; j > 0; --j)
-            if (!stop) {
-              if (g[j - 1][F - 1] < g[j][F - 1])
-                swap_modes(g[j - 1], g[j]);
-              else
-                stop = true;
-            }
-        }
-    };
-    if constexpr (GRIMSON) {
-      const double invTotalWeight = 1.0 / (double)totalWeight;
-#pragma unroll
-      for (int k = 0; k < K; ++k)
-        if (k < nModes) {
-          g[k][WEIGHT] *= (float)invTotalWeight;
-          g[k][SIG] = div_rn(g[k][WEIGHT], sqrt_rn(g[k][VAR]));
-        }
-      grimson_sort(nModes);
-    } else {
-#pragma unroll
-      for (int k = 0; k < K; ++k)
-        if (k < nModes) g[k][WEIGHT] = div_rn(g[k][WEIGHT], totalWeight);
-    }
-    if (!bFitsPDF) {
-      if (nModes < K) nModes++;  // else: replace the weakest (the last one)
-      const int last = nModes - 1;
-#pragma unroll
-      for (int k = 0; k < K; ++k)
-        if (k == last) {
-          if constexpr (GRIMSON) {
-            g[k][MU] = px[0], g[k][MU + 1] = px[1], g[k][MU + 2] = px[2];
-            g[k][VAR] = m_variance;
-            g[k][SIG] = 0;
-          }
-          g[k][WEIGHT] = nModes == 1 ? 1.0f : Alpha;
-        }
-      float sum = 0.0f;
-#pragma unroll
-      for (int k = 0; k < K; ++k)
-        if (k < nModes) sum += g[k][WEIGHT];
-      if constexpr (GRIMSON) {
-        const double invSum = 1.0 / (double)sum;
+    int mask = 0;
+    if (active) {
+      const float px[3] = {(float)(pw & 0xffu), (float)((pw >> 8) & 0xffu), (float)(pw >> 16)};
+      if (t + 1 < T) pw = fetch_pixel(t + 1);  // the next frame's pixel, requested before this frame's arithmetic
+      const float m_bg_threshold = 0.75f, m_variance = 36.0f, m_complexity_prior = 0.05f;
+      const float Alpha = a.alpha;
+      bool bFitsPDF = false, bBackgroundHigh = false;
+      const float fOneMinAlpha = 1 - Alpha;
+      const float prune = -Alpha * m_complexity_prior;  // Zivkovic only
+      float totalWeight = 0.0f;
+      int backgroundGaussians = 0;
+      {  // how many leading modes make up the background: their weights, summed in double, up to m_bg_threshold
+        double sum = 0.0;
+        bool stop = false;
 #pragma unroll
         for (int k = 0; k < K; ++k)
-          if (k < nModes) {
-            g[k][WEIGHT] *= (float)invSum;
-            g[k][SIG] = div_rn(g[k][WEIGHT], sqrt_rn(g[k][VAR]));
-          }
-      } else {
-        const float invSum = div_rn(1.0f, sum);
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-          if (k < nModes) g[k][WEIGHT] *= invSum;
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-          if (k == last) g[k][MU] = px[0], g[k][MU + 1] = px[1], g[k][MU + 2] = px[2], g[k][VAR] = m_variance;
-        bool stop = false;  // ZivkovicAGMM.cpp:331-345
-#pragma unroll
-        for (int il = K - 1; il > 0; --il)
-          if (il <= last && !stop) {
-            if (g[il][WEIGHT] > g[il - 1][WEIGHT])
-              swap_modes(g[il], g[il - 1]);
-            else
+          if (k < nModes && !stop) {
+            if (sum < (double)m_bg_threshold) {
+              backgroundGaussians++;
+              sum = __dadd_rn(sum, (double)g[k][WEIGHT]);
+            } else
               stop = true;
           }
       }
+      // stable insertion by adjacent swaps, largest `significants` first (qsort + compareGMM, GrimsonGMM.cpp:45-56; compareT2FGMM
+      // is the same; glibc's qsort keeps equal keys in order)
+      auto sort_by_key = [&]() {
+#pragma unroll
+        for (int i2 = 1; i2 < K; ++i2)
+          if (i2 < nModes) {
+            bool stop = false;
+#pragma unroll
+            for (int j = i2; j > 0; --j)
+              if (!stop) {
+                if (key(j - 1) < key(j))
+                  swap(j - 1, j);
+                else
+                  stop = true;
+              }
+          }
+      };
+      // weight *= (float)inv; significants = weight / sqrt(variance), for every mode below the count
+      auto renormalise = [&](double inv) {
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+          if (k < nModes) {
+            g[k][WEIGHT] *= (float)inv;
+            key(k) = div_rn(g[k][WEIGHT], sqrt_rn(g[k][VAR]));
+          }
+      };
+#pragma unroll
+      for (int im = 0; im < K; ++im) {
+        if (im < nModes) {  // nModes shrinks inside the loop, as in the source
+          float weight = g[im][WEIGHT];
+          if constexpr (ZIVKOVIC) {
+            // Zivkovic keeps the source's own branch structure (the decay after a failed match and after an earlier fit are two
+            // branches, the bubble starts at im): folded into Grimson's shape below, clip launches on S_sat were 2 % slower
+            auto decay = [&]() {
+              weight = fOneMinAlpha * weight + prune;
+              if (weight < -prune) weight = 0.0f, nModes--;
+              g[im][WEIGHT] = weight;
+            };
+            if (!bFitsPDF) {
+              const float var = g[im][VAR], muR = g[im][MU], muG = g[im][MU + 1], muB = g[im][MU + 2];
+              const float dR = muR - px[0], dG = muG - px[1], dB = muB - px[2];
+              const float dist = (dR * dR + dG * dG + dB * dB);
+              if (dist < a.high * var && im < backgroundGaussians) bBackgroundHigh = true;
+              if (dist < a.low * var) {
+                bFitsPDF = true;
+                const float k = div_rn(Alpha, weight);
+                weight = fOneMinAlpha * weight + prune;
+                weight += Alpha;
+                g[im][WEIGHT] = weight;
+                g[im][MU] = muR - k * (dR);
+                g[im][MU + 1] = muG - k * (dG);
+                g[im][MU + 2] = muB - k * (dB);
+                const float sigmanew = var + k * (dist - var);
+                g[im][VAR] = sigmanew < 4 ? 4 : sigmanew > 5 * m_variance ? 5 * m_variance : sigmanew;
+                bool stop = false;  // ZivkovicAGMM.cpp:219-234: move the grown mode up while it outweighs its predecessor
+#pragma unroll
+                for (int il = im; il > 0; --il)
+                  if (!stop) {
+                    if (g[il][WEIGHT] > g[il - 1][WEIGHT])
+                      swap(il, il - 1);
+                    else
+                      stop = true;
+                  }
+              } else
+                decay();
+            } else
+              decay();
+          } else {
+            bool matched = false;
+            if (!bFitsPDF) {
+              const float var = g[im][VAR];
+              const float mu[3] = {g[im][MU], g[im][MU + 1], g[im][MU + 2]};
+              float d[3];  // what the mean update multiplies by k: Grimson mu - pixel, T2FGMM |mu - pixel|
+              const float dist = model.distance(mu, var, px, d);
+              if (dist < a.high * var && im < backgroundGaussians) bBackgroundHigh = true;
+              if (dist < a.low * var) {
+                bFitsPDF = true, matched = true;
+                const float k = div_rn(Alpha, weight);
+                weight = fOneMinAlpha * weight + Alpha;
+                g[im][MU] = mu[0] - k * (d[0]);
+                g[im][MU + 1] = mu[1] - k * (d[1]);
+                g[im][MU + 2] = mu[2] - k * (d[2]);
+                const float sigmanew = var + k * (dist - var);
+                g[im][VAR] = sigmanew < 4 ? 4 : sigmanew > 5 * m_variance ? 5 * m_variance : sigmanew;
+              }
+            }
+            if (!matched) {  // both of the source's decay branches: the fit was found earlier, or this mode does not fit
+              weight = fOneMinAlpha * weight;
+              if (weight < 0.0f) weight = 0.0f, nModes--;
+            }
+            g[im][WEIGHT] = weight;
+            // Grimson's in-loop `significants` stay: a mode left above the count keeps this value in its plane.  T2FGMM's are not
+            // made (kernel_t2f.h): the key is in registers, and the first renormalisation overwrites every one before anything reads it.
+            if constexpr (GRIMSON) g[im][SIG] = div_rn(weight, sqrt_rn(g[im][VAR]));
+          }
+          totalWeight += weight;
+        }
+      }
+      if constexpr (ZIVKOVIC) {
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+          if (k < nModes) g[k][WEIGHT] = div_rn(g[k][WEIGHT], totalWeight);
+      } else {
+        renormalise(1.0 / (double)totalWeight);
+        sort_by_key();
+      }
+      if (!bFitsPDF) {
+        if (nModes < K) nModes++;  // else: replace the weakest (the last one)
+        // the order follows each source: Grimson / T2FGMM fill the new mode before the renormalisation, Zivkovic its mean and variance after
+        const int last = nModes - 1;
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+          if (k == last) {
+            if constexpr (!ZIVKOVIC) {
+              g[k][MU] = px[0], g[k][MU + 1] = px[1], g[k][MU + 2] = px[2];
+              g[k][VAR] = m_variance;
+              key(k) = 0;
+            }
+            g[k][WEIGHT] = nModes == 1 ? 1.0f : Alpha;
+          }
+        float sum = 0.0f;
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+          if (k < nModes) sum += g[k][WEIGHT];
+        if constexpr (ZIVKOVIC) {
+          const float invSum = div_rn(1.0f, sum);
+#pragma unroll
+          for (int k = 0; k < K; ++k)
+            if (k < nModes) g[k][WEIGHT] *= invSum;
+#pragma unroll
+          for (int k = 0; k < K; ++k)
+            if (k == last) g[k][MU] = px[0], g[k][MU + 1] = px[1], g[k][MU + 2] = px[2], g[k][VAR] = m_variance;
+          bool stop = false;  // ZivkovicAGMM.cpp:331-345
+#pragma unroll
+          for (int il = K - 1; il > 0; --il)
+            if (il <= last && !stop) {
+              if (g[il][WEIGHT] > g[il - 1][WEIGHT])
+                swap(il, il - 1);
+              else
+                stop = true;
+            }
+        } else {
+          renormalise(1.0 / (double)sum);
+        }
+      }
+      if constexpr (!ZIVKOVIC) sort_by_key();  // the second qsort runs whether or not a mode was added (GrimsonGMM.cpp:281, T2FGMM.cpp:292)
+      mask = bBackgroundHigh ? 0 : 255;
+      nUsed = max(nUsed, nModes);
     }
-    if constexpr (GRIMSON) grimson_sort(nModes);  // the second qsort runs whether or not a mode was added (:281)
-    mask = bBackgroundHigh ? 0 : 255;
-    nUsed = max(nUsed, nModes);
-  }
-  dp_store_mask(a, gp, active, mask, t);
+    dp_store_mask(a, gp, active, mask, t);
   }
   if (active) {
-    // a slot that was not loaded is written if it was in use at the end of ANY frame of the launch: the source wrote it then, and a
-    // later frame that prunes the mode again leaves those values behind the count
+    // A field is stored if its bits changed.  A slot that was not loaded is written if it was in use at the end of ANY frame of the
+    // launch: the source wrote it then, and a later frame that prunes the mode again leaves those values behind the count.
     if (nModes != nLoaded) *pn = (uint8_t)nModes;
 #pragma unroll
     for (int k = 0; k < K; ++k)
