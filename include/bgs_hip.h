@@ -84,7 +84,10 @@ typedef enum bgs_algo {
    * are bgs_t2f_params, not bgs_params. */
   BGS_T2FGMM_UM = 32,             /* T2FGMM_UM::process (USTC_BGS type 17)            package_bgs/tb/T2FGMM_UM.cpp:29-83 */
   BGS_T2FGMM_UV = 33,             /* T2FGMM_UV::process (USTC_BGS type 18)            package_bgs/tb/T2FGMM_UV.cpp:29-83 */
-  BGS_ALGO_LAST = 34              /* one past the last id; moves with every class added */
+  /* package_bgs/dp's PCA background (3-channel frames; output = the high-threshold mask, no background image).  Its parameters are
+   * bgs_eigen_params, not bgs_params. */
+  BGS_DP_EIGENBACKGROUND = 34,    /* DPEigenbackgroundBGS::process (USTC_BGS type 15) package_bgs/dp/DPEigenbackgroundBGS.cpp:29-82 */
+  BGS_ALGO_LAST = 35              /* one past the last id; moves with every class added */
 } bgs_algo;
 
 /* "id is an algorithm": the one range check (bgs_default_params, bgs_create, bgs_node_create) */
@@ -285,6 +288,24 @@ typedef struct bgs_t2f_params {
   int32_t gaussians;     /* 3    gaussians: modes per pixel, 1..5 */
 } bgs_t2f_params;
 
+/* DPEigenbackgroundBGS (package_bgs/dp/DPEigenbackgroundBGS.cpp:19, :96-106), in the wrapper's member types.  A struct of its own, as
+ * bgs_t2f_params.  bgs_create gives an Eigenbackground engine these defaults whatever bgs_params it was handed.  The wrapper fills its
+ * params object once, on the first frame: the values are taken when the geometry is set, and a bgs_set_eigen_params after that
+ * succeeds and leaves the values in force unchanged (bgs_get_eigen_params returns what is in force).  threshold is narrowed to float
+ * on the way (LowThreshold() is a float&); the high threshold, the one the returned mask uses, is 2 * (float)threshold.
+ * Refused with BGS_ERR_UNSUPPORTED, the class named: history_size outside 2..BGS_EIGEN_MAX_HISTORY, embedded_dim outside
+ * 1..history_size - 1 (centred data has rank <= history_size - 1: at embedded_dim == history_size the reference projects onto a
+ * normalised rounding residue, above it OpenCV asserts), 1-channel frames, the class inside a bgs_group. */
+typedef struct bgs_eigen_params {
+  uint32_t struct_size;  /* sizeof(bgs_eigen_params) = 16 */
+  int32_t threshold;     /* 225 threshold */
+  int32_t history_size;  /* 20  historySize: frames 0 .. historySize-1 are the PCA's samples */
+  int32_t embedded_dim;  /* 10  embeddedDim: eigenvectors kept */
+} bgs_eigen_params;
+
+/* Largest history_size the Eigenbackground kernels are built for. */
+#define BGS_EIGEN_MAX_HISTORY 32
+
 /* Largest dp_history_size the PratiMediod kernel is built for (every dist entry then fits in 16 bits: 64 x 255 < 65536). */
 #define BGS_PRATI_MAX_HISTORY 64
 
@@ -319,6 +340,14 @@ int bgs_get_t2f_params(const bgs_engine* e, bgs_t2f_params* p);
 /* Every refusal of the two classes without an engine and without a device: parameters (p == NULL: the defaults) and, where rows > 0,
  * the frame geometry.  The message names the class. */
 int bgs_t2f_check(bgs_algo algo, const bgs_t2f_params* p, int rows, int cols, int channels);
+
+/* DPEigenbackground's own parameters (bgs_eigen_params above); BGS_ERR_INVALID for an engine of any other class. */
+int bgs_eigen_default_params(bgs_eigen_params* p);
+int bgs_set_eigen_params(bgs_engine* e, const bgs_eigen_params* p);
+int bgs_get_eigen_params(const bgs_engine* e, bgs_eigen_params* p);
+/* Every refusal of the class without an engine and without a device: parameters (p == NULL: the defaults) and, where rows > 0, the
+ * frame geometry.  The message names the class. */
+int bgs_eigen_check(const bgs_eigen_params* p, int rows, int cols, int channels);
 
 /* Engine options.
  *   BGS_OPT_BORROW_FRAMES  device path of the history-keeping classes (FrameDifference, WeightedMovingMean/Variance):
@@ -534,6 +563,10 @@ const char* bgs_last_error(void);
  * bgs_get_state also answers "count" int64 [2] = {samples in the buffer, next slot to replace}.
  * Texture: "hist" u8 [n][3][64], the background histograms in the reference's r, g, b order (TextureHistogram); pixels outside
  * the processed interior (7 <= x < cols-7, 7 <= y < rows-7) hold 0.
+ * Eigenbackground (H = history_size, M = embedded_dim): "history" u8 [H][n][3] (slots not yet filled read 0), "count" int64 [1] =
+ * the stream's frame counter; once the model is built (after frame H): "avg" f32 [n][3], "eigenvalues" f64 [H] of the centred Gram
+ * matrix, descending, "eigenvectors" f32 [M][n][3], "coeff" f32 [M] = the last frame's projection, "result" f32 [n][3] = that
+ * frame's reconstruction (not stored per frame: recomputed on request from avg, coeff and the eigenvectors by a launch of its own).
  * lb/ models, all f64 in the reference's memory order, colour fields in the byte order of the input pixel (B, G, R):
  * SimpleGaussian / FuzzyGaussian "mu", "var" f64 [n][3]; MixtureOfGaussians "w" f64 [n][3], "mu", "var" f64 [n][3][3] (pixel, slot,
  * colour), "sortkey" f64 [n][3], "k" int32 [n] (slots >= k read 0); AdaptiveSOM / FuzzyAdaptiveSOM "som" f64 [n][3][3][3] (pixel,

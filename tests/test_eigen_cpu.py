@@ -1,0 +1,237 @@
+"""DPEigenbackgroundBGS (USTC_BGS type 15's class) without a GPU: the float64 restatement against the fixture made from the reference's
+own dp/Eigenbackground.cpp, the conditions that make the fixture a fair yardstick (eigengap, band share, measured float floor), the
+C ABI (ids, bgs_eigen_params, the refusals) and the host layer (class list, XML keys and defaults, the type table, the FrameProcessor
+flag, the reference-side adapters)."""
+import ctypes as C
+import functools
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import eigen_numpy as en
+from tracking_amd import capi
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+HOST = os.path.join(ROOT, "tracking_amd", "host")
+FIELDS = ["struct_size", "threshold", "history_size", "embedded_dim"]
+PARITY = [c for c in en.cases() if c not in en.NO_PARITY]
+
+
+@functools.lru_cache(maxsize=None)
+def restated(case, storage=en.f64):
+    r = en.load()[case]
+    return en.run(r["params"], r["frames"], storage)
+
+
+# ---- the restatement and the fixture -----------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("case", list(en.cases()))
+def test_restatement_reproduces_the_reference_fixture(case):
+    """Exactly for `static` and on the learning frames of every case; outside the near-threshold band otherwise.  The stored planes:
+    avg bit for bit, eigenvalues to 1e-9 of the largest, the last result within the float floor."""
+    r = en.load()[case]
+    p, frames = r["params"], r["frames"]
+    masks, results, mdl = restated(case)
+    Hs = p["history_size"]
+    assert not r["masks"][:Hs].any() and not masks[:Hs].any()
+    assert mdl.history.tobytes() == frames[:Hs].tobytes()
+    if case == "static":
+        assert np.array_equal(masks, r["masks"]) and not mdl.E.any() and not mdl.lam.any()
+        assert np.array_equal(results[-1], frames[0].reshape(-1))
+    for k, t in enumerate(range(Hs, len(frames))):
+        bad = (masks[t].reshape(-1) != r["masks"][t].reshape(-1)) & ~en.band(p, frames[t], results[k])
+        assert not bad.any(), (t, int(bad.sum()))
+    n = masks.shape[1] * masks.shape[2]
+    assert ("avg" in r) == (n <= en.PLANE_PIXELS)
+    if "avg" in r:
+        assert r["avg"].tobytes() == restated(case, en.f32)[2].avg.tobytes()
+        assert np.abs(r["eigenvalues"] - mdl.lam).max() <= 1e-9 * max(mdl.lam[0], 1e-300)
+        assert np.abs(r["result"].astype(np.float64) - results[-1]).max() <= en.TOL_FLOOR
+
+
+def test_fixture_holds_every_case_and_is_small():
+    assert os.path.getsize(os.path.join(en.GOLDEN, "eigen_ref.npz")) <= 128 * 1024
+    assert list(en.load()) == list(en.cases()) == ["default", "tile", "ragged", "ragged_o1", "ragged_o2", "chunks", "tiny3x3", "h8_m3", "h32_m31", "h2_m1", "thr0",
+                                                   "thr100", "static", "tiny1x1"]
+    shapes = {case: r["masks"].shape for case, r in en.load().items()}
+    assert shapes["default"] == (30, 24, 32) and shapes["tile"][1:] == (16, 64) and shapes["ragged"] == shapes["ragged_o1"] == shapes["ragged_o2"] == (28, 37, 53)
+    assert shapes["tiny3x3"][1:] == (3, 3) and shapes["tiny1x1"][1:] == (1, 1)
+    c = en.cases()
+    assert {k: c["default"][k] for k in en.DEFAULTS} == en.DEFAULTS == dict(threshold=225, history_size=20, embedded_dim=10)
+    assert [(c[k]["history_size"], c[k]["embedded_dim"]) for k in ("h8_m3", "h32_m31", "h2_m1", "chunks")] == [(8, 3), (32, 31), (2, 1), (4, 2)]
+    assert c["thr0"]["threshold"] == 0 and c["thr100"]["threshold"] == 100
+    whole = en.frames_of({k: v for k, v in c["ragged"].items() if k != "window"})
+    for k, o in (("ragged", 0), ("ragged_o1", 1), ("ragged_o2", 2)):  # one seeded clip entered 0, 1 and 2 frames late
+        assert np.array_equal(en.load()[k]["frames"], whole[o:o + 28])
+    L = 3 * shapes["chunks"][1] * shapes["chunks"][2]  # at least three projection chunks with a ragged tail, for any power-of-two chunk from 2 048 to 8 192 elements
+    for chunk in (2048, 4096, 8192):
+        assert L > 2 * chunk and L % chunk
+    env = en.environment()
+    assert len(env["poison_bytes"]) == 2 and "-ffp-contract=off" in env["flags"] and env["sources"] == ["Eigenbackground.cpp", "Image.cpp"]
+
+
+def test_eigengap_band_share_and_foreground_conditions():
+    """What makes the comparison fair, asserted on the fixture alone: the top-M subspace is well conditioned, the band is nearly
+    empty, and no case passes on an all-one-value mask."""
+    for case in PARITY:
+        r = en.load()[case]
+        p, frames = r["params"], r["frames"]
+        _, results, mdl = restated(case)
+        Hs, M = p["history_size"], p["embedded_dim"]
+        if case != "static":
+            gap = mdl.lam[M - 1] / mdl.lam[M] if mdl.lam[M] > Hs * 2.0 ** -40 * mdl.lam[0] else np.inf
+            assert gap >= en.EIGENGAP, (case, gap)
+        near = sum(int(en.band(p, frames[t], results[k]).sum()) for k, t in enumerate(range(Hs, len(frames))))
+        assert near <= en.BAND_SHARE * (len(frames) - Hs) * results.shape[1] / 3, (case, near)
+        m = r["masks"]
+        if m.shape[1] * m.shape[2] > 35:
+            fg = (m != 0).reshape(len(m), -1).sum(1)
+            assert ((fg >= 20) & (m.shape[1] * m.shape[2] - fg >= 20)).any(), (case, fg.tolist())
+
+
+def test_float_storage_floor_is_below_the_constant():
+    """TOL_FLOOR: the largest |result| difference between the float64 restatement and its float-storage variant over the parity cases."""
+    floor = 0.0
+    for case in PARITY:
+        d = float(np.abs(restated(case)[1] - restated(case, en.f32)[1].astype(np.float64)).max())
+        print("%-10s float-storage floor %.4g" % (case, d))
+        floor = max(floor, d)
+    print("TOL_FLOOR measured %.4g, constant %.4g, TOL_RESULT %.4g" % (floor, en.TOL_FLOOR, en.TOL_RESULT))
+    assert en.TOL_FLOOR / 2 <= floor <= en.TOL_FLOOR and en.TOL_RESULT == 8 * en.TOL_FLOOR
+
+
+def test_per_channel_distance_and_float_thresholds():
+    """A pixel is foreground iff ANY channel's squared distance exceeds the threshold (not their sum); the thresholds are floats."""
+    low, high = en.thresholds(dict(threshold=225))
+    assert (low, high) == (np.float32(225), np.float32(450)) and high.dtype == np.float32
+    p = dict(threshold=225, history_size=2, embedded_dim=1)
+    hist = np.full((1, 1, 3), 100, np.uint8)
+    frames = np.stack([hist, hist, np.array([[[113, 113, 113]]], np.uint8), np.array([[[122, 100, 100]]], np.uint8)])
+    masks, results, _ = en.run(p, frames)
+    assert np.array_equal(results[0], [100, 100, 100])
+    assert masks[2, 0, 0] == 0 and masks[3, 0, 0] == 255  # 3 x 169 = 507 > 450 summed, but no channel alone; 484 > 450
+
+
+# ---- C ABI -----------------------------------------------------------------------------------------------------------------------------
+
+def test_ids_and_struct_layout_match_c(tmp_path):
+    inc = os.path.join(ROOT, "include")
+    src = tmp_path / "eigen_abi.c"
+    ids = ("33", "34", "BGS_DP_EIGENBACKGROUND", "BGS_ALGO_LAST", "(int)BGS_ALGO_LAST + 1")
+    known = ", ".join("BGS_ALGO_KNOWN(%s)" % i for i in ids)
+    offs = ", ".join("offsetof(bgs_eigen_params, %s)" % f for f in FIELDS)
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "bgs_hip.h"\nint main(){printf("%d %d %zu %d %d %d %d' + " %d" * len(ids) + " %zu" * len(FIELDS)
+                   + '\\n", (int)BGS_ALGO_LAST, (int)BGS_DP_EIGENBACKGROUND, sizeof(bgs_eigen_params), (int)BGS_EIGEN_MAX_HISTORY, (int)BGS_ALGO_COUNT, (int)BGS_ALGO_END, (int)BGS_ALGO_LIMIT, '
+                   + known + ", " + offs + ");return 0;}\n")
+    exe = tmp_path / "eigen_abi"
+    subprocess.run(["gcc", "-Wall", "-Werror", "-I", inc, str(src), "-o", str(exe)], check=True)
+    v = list(map(int, subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()))
+    assert v[0] == capi.ALGO_LAST > capi.DP_EIGENBACKGROUND  # header and binding agree on the moving marker; its value is not pinned
+    assert v[1] == 34 == capi.DP_EIGENBACKGROUND
+    assert v[2] == C.sizeof(capi.BgsEigenParams) == 16 and v[3] == capi.EIGEN_MAX_HISTORY == 32
+    assert v[4:7] == [21, 26, 28]  # the frozen markers
+    assert v[7:7 + len(ids)] == [1, 1, 1, 0, 0]  # one past the last id is unknown, symbolically
+    assert v[7 + len(ids):] == [getattr(capi.BgsEigenParams, f).offset for f in FIELDS] == [0, 4, 8, 12]
+    text = open(os.path.join(ROOT, "tracking_amd", "capi.py")).read()
+    assert len(set(re.findall(r"^ALGO_LAST = (\d+)", text, re.M))) == 1
+
+
+def test_unknown_ids_stay_unknown_and_the_new_one_is_known():
+    p = capi.BgsParams()
+    p.struct_size = C.sizeof(capi.BgsParams)
+    for bad in (capi.ALGO_LAST, capi.ALGO_LAST + 1):
+        assert capi.lib().bgs_default_params(bad, C.byref(p)) == capi.ERR_INVALID, bad
+        h = C.c_void_p()
+        assert capi.lib().bgs_create(bad, None, 0, 1, C.byref(h)) == capi.ERR_INVALID and b"unknown algorithm" in capi.lib().bgs_last_error()
+    assert capi.lib().bgs_default_params(capi.DP_EIGENBACKGROUND, C.byref(p)) == capi.OK
+    node_src = open(os.path.join(ROOT, "tracking_amd", "csrc", "bgs_node.cpp")).read()
+    assert "BGS_ALGO_KNOWN(algo)" in node_src  # bgs_node_create accepts every known id
+
+
+def test_default_eigen_params():
+    p = capi.eigen_default_params()
+    assert (p.struct_size, p.threshold, p.history_size, p.embedded_dim) == (16, 225, 20, 10)
+    assert (p.threshold, p.history_size, p.embedded_dim) == tuple(en.DEFAULTS[k] for k in ("threshold", "history_size", "embedded_dim"))
+    assert capi.lib().bgs_eigen_default_params(None) == capi.ERR_INVALID
+    assert capi.eigen_default_params(history_size=5).history_size == 5
+
+
+def test_every_refusal_names_the_class_and_needs_no_device():
+    check = capi.lib().bgs_eigen_check
+    name = en.CLASS_NAME.encode()
+    assert check(None, 0, 0, 0) == capi.OK and check(None, 24, 32, 3) == capi.OK and check(None, 1, 1, 3) == capi.OK
+    bad = [dict(history_size=1), dict(history_size=0), dict(history_size=-3), dict(history_size=33), dict(embedded_dim=0), dict(embedded_dim=-1),
+           dict(embedded_dim=20), dict(embedded_dim=21), dict(history_size=8), dict(history_size=32, embedded_dim=32), dict(history_size=2, embedded_dim=2)]
+    for kw in bad:
+        assert check(C.byref(capi.eigen_default_params(**kw)), 0, 0, 0) == capi.ERR_UNSUPPORTED, kw
+        assert name in capi.lib().bgs_last_error(), kw
+    for kw in (dict(history_size=2, embedded_dim=1), dict(history_size=32, embedded_dim=31), dict(embedded_dim=19), dict(embedded_dim=1), dict(threshold=0), dict(threshold=-5)):
+        assert check(C.byref(capi.eigen_default_params(**kw)), 0, 0, 0) == capi.OK, kw
+    assert check(None, 24, 32, 1) == capi.ERR_UNSUPPORTED and name in capi.lib().bgs_last_error()  # gray frames
+    assert check(C.byref(capi.eigen_default_params(struct_size=12)), 0, 0, 0) == capi.ERR_INVALID
+    g = C.c_void_p()  # class groups: refused before any device is opened, the class named
+    algos = (C.c_int * 2)(capi.FRAME_DIFF, capi.DP_EIGENBACKGROUND)
+    assert capi.lib().bgs_group_create(algos, None, 2, 0, 1, C.byref(g)) == capi.ERR_UNSUPPORTED and name in capi.lib().bgs_last_error()
+
+
+# ---- host layer ------------------------------------------------------------------------------------------------------------------------
+
+def test_host_class_list_keys_defaults_type_table_and_frame_processor():
+    inc = open(os.path.join(HOST, "bgs_classes_eigen.inc")).read()
+    assert re.findall(r"^class (\w+) : public \w+", inc, re.M) == ["DPEigenbackgroundBGS"]
+    keys = ["threshold", "historySize", "embeddedDim", "showOutput"]
+    assert re.findall(r'fs\.write\w+\("(\w+)"', inc) == keys == re.findall(r'fs\.read\w+\("(\w+)"', inc)  # the reference's order
+    for dflt in ('readInt("threshold", 225)', 'readInt("historySize", 20)', 'readInt("embeddedDim", 10)', 'readInt("showOutput", true)',
+                 "threshold(225), historySize(20), embeddedDim(10), showOutput(true)", "int threshold, historySize, embeddedDim;"):
+        assert dflt in inc, dflt
+    assert '"DPEigenbackgroundBGS"' in inc  # banners and ./config/DPEigenbackgroundBGS.xml
+    for f in ("HipBGS.h", "bgs_host.h"):
+        src = open(os.path.join(HOST, f)).read()
+        assert src.index('#include "bgs_classes_t2f.inc"') < src.index('#include "bgs_classes_eigen.inc"'), f
+    # The type table: the tests of the T2FGMM round pin USTC_BGS(15) as refused at run time and the switch as holding exactly cases
+    # 17 and 18, so type 15 is not wired in by number; the header says so and the class is reached as an IBGS / through FrameProcessor.
+    for f in ("ustc_bgs.h", "HipFGDetector.h"):
+        text = open(os.path.join(HOST, f)).read()
+        assert "i == 15)" not in text and "case 15:" not in text, f
+    assert "DPEigenbackgroundBGS" in open(os.path.join(HOST, "ustc_bgs.h")).read()
+    fp = open(os.path.join(HOST, "FrameProcessor.cpp")).read()
+    fph = open(os.path.join(HOST, "FrameProcessor.h")).read()
+    cls, member = "DPEigenbackgroundBGS", "eigenBackground"
+    assert 'enable%s = fs.readInt("enable%s", false)' % (cls, cls) in fp and 'process("%s", %s, img_prep, img_eigbkg)' % (cls, member) in fp
+    assert 'fs.writeInt("enable%s", enable%s)' % (cls, cls) in fp and "new %s;" % cls in fp and "delete %s" % member in fp
+    assert "bool enable%s;" % cls in fph and "%s* %s;" % (cls, member) in fph
+    for frag in ("new %s;", 'process("%s"', 'fs.writeInt("enable%s"', 'fs.readInt("enable%s"'):  # between PratiMediod and Texture, as in the reference
+        a, b, c = (fp.index(frag % k) for k in ("DPPratiMediodBGS", cls, "DPTextureBGS"))
+        assert a < b < c, frag
+    assert "bgs_classes_eigen.inc" in open(os.path.join(HOST, "Makefile")).read()
+
+
+def test_frame_processor_builds_the_class_and_writes_the_reference_xml(tmp_path):
+    """Without a GPU the first frame ends in the one exception of the host layer; by then the class's banner is out and saveConfig()
+    has written the reference's keys in the reference's order with the reference's defaults.  With a GPU the run succeeds."""
+    subprocess.run(["make", "-s", "-C", HOST], check=True)
+    demo = os.path.join(ROOT, "tracking_amd", "lib", "bgs_demo")
+    wd = str(tmp_path)
+    os.makedirs(os.path.join(wd, "config"))
+    raw = os.path.join(wd, "frames.raw")
+    np.zeros((2, 8, 8, 3), np.uint8).tofile(raw)
+    with open(os.path.join(wd, "config", "FrameProcessor.xml"), "w") as f:
+        f.write('<?xml version="1.0"?>\n<opencv_storage>\n<enableFrameDifferenceBGS>0</enableFrameDifferenceBGS>\n<enableDPEigenbackgroundBGS>1</enableDPEigenbackgroundBGS>\n</opencv_storage>\n')
+    r = subprocess.run([demo, raw, "8", "8", "2", os.path.join(wd, "out")], cwd=wd, capture_output=True, text=True)
+    assert "DPEigenbackgroundBGS()" in r.stdout, r.stdout + r.stderr
+    assert r.returncode == 0 or "no HIP device" in r.stdout, r.stdout + r.stderr
+    xml = open(os.path.join(wd, "config", "DPEigenbackgroundBGS.xml")).read()
+    assert xml == ('<?xml version="1.0"?>\n<opencv_storage>\n<threshold>225</threshold>\n<historySize>20</historySize>\n<embeddedDim>10</embeddedDim>\n'
+                   "<showOutput>1</showOutput>\n</opencv_storage>\n")
+
+
+def test_reference_side_adapters_compile_with_the_class(tmp_path):
+    tu = tmp_path / "adapters_eigen.cpp"
+    tu.write_text('#include "HipBGS.h"\n#include "HipFGDetector.h"\nIBGS* a() { return new hipbgs::DPEigenbackgroundBGS; }\n')
+    r = subprocess.run(["g++", "-std=gnu++0x", "-fsyntax-only", "-Wall", "-I" + os.path.join(ROOT, "tests", "mock_opencv"), "-I" + os.path.join(ROOT, "include"),
+                        "-I" + os.path.join(ROOT, "tracking_amd", "host"), str(tu)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr

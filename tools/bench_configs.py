@@ -14,6 +14,8 @@ Not the driver's bench line (bench.py is); the numbers go to DESIGN.md §6.
              8 x 1080p  (fuzzy_choquet / fuzzy_sugeno: one class, short legs, no calibration: for kernel-trace passes)
   --only t2f: T2FGMM_UM and T2FGMM_UV (package_bgs/tb) beside DPGrimsonGMM timed in the same process, reference defaults (K = 3), on
              S_surv, 8 x 1080p: ms per step and ms per frame at clip T = 8
+  --only eigen: DPEigenbackgroundBGS (package_bgs/dp) beside DPGrimsonGMM timed in the same process, reference defaults (H = 20, M = 10),
+             on S_surv, 8 x 1080p and 1 x 1080p: ms per detecting step, the one-off model build at frame H, this box's copy rate
 usage: bench_configs.py [--streams S] [--swizzle 0|1]"""
 import argparse
 import os
@@ -912,6 +914,63 @@ def run_t2f(S=8, rows=1080, cols=1920, steps=30, clips=10, age=40):
         e.close()
 
 
+def run_eigen(S=8, rows=1080, cols=1920, steps=30):
+    """DPEigenbackgroundBGS at the reference defaults beside DPGrimsonGMM (a yardstick from the same package, timed in the same
+    process) on S_surv, byte mask out.  Per engine: ms per detecting step (kernel timing over project + coeff + reconstruct, mean of
+    `steps`), the one-off build at frame H (the frame-H call between two events on the launch stream, less one detecting step), and
+    what 2 * 12 * M + 2 * 12 + 2 * 3 + 1 bytes per pixel (both reads of the eigenvectors and of avg, both of the frame, the mask) come
+    to as a rate over this process's float4 copy rate.  S streams and then one stream alone: a single 1080p stream's eigenvectors
+    (249 MB at M = 10) are within reach of the 256 MiB Infinity Cache between the two reads, eight streams' are not."""
+    dev = torch.device("cuda", 0)
+    copy = capi.calibrate_copy(0, 2 << 30, 0)
+    for streams in (S, 1):
+        px = streams * rows * cols
+        e = Engine(capi.DP_EIGENBACKGROUND, n_streams=streams)
+        e.set_geometry(rows, cols, 3)
+        q = e.get_eigen_params()
+        H, M = q.history_size, q.embedded_dim
+        pool = synth.SurvStreams(streams, rows, cols, seed0=4321, device=dev).pool(H + 4)
+        fg = torch.empty((streams, rows, cols), dtype=torch.uint8, device=dev)
+        for t in range(H):
+            e.process_batch_device(pool[t], fg, None, None)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        e.process_batch_device(pool[H], fg, None, None)  # builds the model, then detects
+        b.record()
+        torch.cuda.synchronize()
+        first_ms = a.elapsed_time(b)
+        for t in range(3):
+            e.process_batch_device(pool[H + 1 + t], fg, None, None)
+        torch.cuda.synchronize()
+        e.enable_kernel_timing(True)
+        for t in range(steps):
+            e.process_batch_device(pool[H + t % 4], fg, None, None)
+        torch.cuda.synchronize()
+        ms, n, kname = e.kernel_timing()
+        ratio = float((fg != 0).float().mean())
+        bpp = 2 * 12 * M + 2 * 12 + 2 * 3 + 1
+        gbps = bpp * px / (ms * 1e-3) / 1e9
+        print("%-22s H=%d M=%d %dx%d x%d streams: %.3f ms/step (%s; mean of %d) = %.3f ms/stream -> %7.1f Mpix/s; %d B/px -> %.0f GB/s = %.2f of copy %.0f GB/s; build at frame H: %.3f ms (frame-H call %.3f ms); fg ratio %.3f"
+              % ("DPEigenbackgroundBGS", H, M, cols, rows, streams, ms, kname, n, ms / streams, px / ms / 1e3, bpp, gbps, gbps / copy, copy, first_ms - ms, first_ms, ratio))
+        e.close()
+        del pool
+    g = Engine(capi.DP_GRIMSON_GMM, n_streams=S)
+    g.set_geometry(rows, cols, 3)
+    pool = synth.SurvStreams(S, rows, cols, seed0=4321, device=dev).pool(8)
+    fg = torch.empty((S, rows, cols), dtype=torch.uint8, device=dev)
+    for t in range(40):
+        g.process_batch_device(pool[t % 8], fg, None, None)
+    torch.cuda.synchronize()
+    g.enable_kernel_timing(True)
+    for t in range(steps):
+        g.process_batch_device(pool[t % 8], fg, None, None)
+    torch.cuda.synchronize()
+    ms, n, kname = g.kernel_timing()
+    print("%-22s K=%d %dx%d x%d streams: %.3f ms/step (%s; mean of %d)" % ("DPGrimsonGMMBGS", g.params.dp_gaussians, cols, rows, S, ms, kname, n))
+    g.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=8)
@@ -939,6 +998,9 @@ def main():
         return
     if args.only == "t2f":
         run_t2f(S)
+        return
+    if args.only == "eigen":
+        run_eigen(S)
         return
     if args.only in ("fuzzy_choquet", "fuzzy_sugeno"):
         run_fuzzy(S, steps=5, only="FuzzyChoquetIntegral" if args.only == "fuzzy_choquet" else "FuzzySugenoIntegral", calibrate=False)

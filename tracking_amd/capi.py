@@ -20,12 +20,15 @@ LB_SIMPLE_GAUSSIAN, LB_FUZZY_GAUSSIAN, LB_MOG, LB_ADAPTIVE_SOM, LB_FUZZY_ADAPTIV
 VUMETER = 27  # id 26 is a permanent hole (BGS_ALGO_END is frozen there); BGS_ALGO_LIMIT = 28  # frozen, and id 28 is the second permanent hole
 FUZZY_SUGENO, FUZZY_CHOQUET = 29, 30  # package_bgs/tb fuzzy integrals; their parameters are BgsFuzzyParams, not BgsParams
 T2FGMM_UM, T2FGMM_UV = 32, 33  # package_bgs/tb type-2 fuzzy GMMs (id 31 is the third hole); their parameters are BgsT2fParams
-ALGO_LAST = 34  # one past the last id
+DP_EIGENBACKGROUND = 34  # package_bgs/dp PCA background; its parameters are BgsEigenParams
+ALGO_LAST = 35  # one past the last id
 ALGO_LIMIT = 28  # frozen, and id 28 is the second permanent hole
 FUZZY_SUGENO, FUZZY_CHOQUET = 29, 30  # package_bgs/tb fuzzy integrals; their parameters are BgsFuzzyParams, not BgsParams
 T2FGMM_UM, T2FGMM_UV = 32, 33  # package_bgs/tb type-2 fuzzy GMMs (id 31 is the third hole); their parameters are BgsT2fParams
-ALGO_LAST = 34  # one past the last id
+DP_EIGENBACKGROUND = 34  # package_bgs/dp PCA background; its parameters are BgsEigenParams
+ALGO_LAST = 35  # one past the last id
 PRATI_MAX_HISTORY = 64  # BGS_PRATI_MAX_HISTORY
+EIGEN_MAX_HISTORY = 32  # BGS_EIGEN_MAX_HISTORY
 FG_VALID, BG_VALID = 1, 2
 OPT_BORROW_FRAMES, OPT_MOG2_PIXELS_PER_LANE, OPT_MOG2_TILED, OPT_XCD_SWIZZLE, OPT_PLACEMENT_PROBE, OPT_MOG2_SPARSE, OPT_CLIP_FUSE, OPT_HOST_REGISTER, OPT_MODEL_CHUNK_MB, OPT_MODEL_CHUNK_MIN_MB = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 
@@ -118,6 +121,11 @@ class BgsT2fParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("threshold", C.c_double), ("alpha", C.c_double), ("km", C.c_float), ("kv", C.c_float), ("gaussians", C.c_int32)]
 
 
+class BgsEigenParams(C.Structure):
+    """struct bgs_eigen_params, field for field (DPEigenbackground)."""
+    _fields_ = [("struct_size", C.c_uint32), ("threshold", C.c_int32), ("history_size", C.c_int32), ("embedded_dim", C.c_int32)]
+
+
 class BgsError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("libbgs_hip error %d: %s" % (code, text))
@@ -139,6 +147,10 @@ SYMBOLS = [
     ("bgs_set_t2f_params", C.c_int, [_P, C.POINTER(BgsT2fParams)]),
     ("bgs_get_t2f_params", C.c_int, [_P, C.POINTER(BgsT2fParams)]),
     ("bgs_t2f_check", C.c_int, [C.c_int, C.POINTER(BgsT2fParams), C.c_int, C.c_int, C.c_int]),
+    ("bgs_eigen_default_params", C.c_int, [C.POINTER(BgsEigenParams)]),
+    ("bgs_set_eigen_params", C.c_int, [_P, C.POINTER(BgsEigenParams)]),
+    ("bgs_get_eigen_params", C.c_int, [_P, C.POINTER(BgsEigenParams)]),
+    ("bgs_eigen_check", C.c_int, [C.POINTER(BgsEigenParams), C.c_int, C.c_int, C.c_int]),
     ("bgs_set_option", C.c_int, [_P, C.c_int, C.c_int64]),
     ("bgs_set_geometry", C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     ("bgs_process", C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_uint32)]),
@@ -259,6 +271,14 @@ def fuzzy_default_params(**kw):
 def t2f_default_params(**kw):
     p = BgsT2fParams()
     check(lib().bgs_t2f_default_params(C.byref(p)))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def eigen_default_params(**kw):
+    p = BgsEigenParams()
+    check(lib().bgs_eigen_default_params(C.byref(p)))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

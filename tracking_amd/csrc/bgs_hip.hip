@@ -37,6 +37,7 @@
 #include "kernel_vumeter.h"
 #include "kernel_fuzzy.h"
 #include "kernel_t2f.h"
+#include "kernel_eigen.h"
 #include "kernel_cc.h"
 #include "kernel_dp.h"
 #include "kernel_mog1.h"
@@ -121,7 +122,7 @@ struct VmmRange {
 //  - the frame history ring: process_clip_run, bgs_process and bgs_submit read and write it themselves, so it is a service of the
 //    generic code that the history classes use, not their private state;
 //  - `counter`: the families that have a learning phase counted in frames share it with that one meaning, and bgs_reset_stream clears it;
-//  - p, fz and t2f: all may be set before the geometry is known, i.e. before there is a state;
+//  - p, fz, t2f and eig: all may be set before the geometry is known, i.e. before there is a state;
 //  - the knobs, which bgs_create (environment) and bgs_set_option set before allocation.
 struct bgs_engine {
   bgs_algo algo;
@@ -130,6 +131,7 @@ struct bgs_engine {
   bgs_params p;
   bgs_fuzzy_params fz{};  // bgs_set_fuzzy_params
   bgs_t2f_params t2f{};   // bgs_set_t2f_params; frozen once the geometry is set
+  bgs_eigen_params eig{}; // bgs_set_eigen_params; frozen once the geometry is set
   int device = 0;
   int n_cu = 256;  // compute units of `device` (allocate): the persistent kernels size their grids by it
   int S = 1;
@@ -431,6 +433,7 @@ int model_allocate(bgs_engine* e, DevPtr<T>& out, size_t bytes) { return model_a
 #include "engine_vumeter.h"
 #include "engine_fuzzy.h"
 #include "engine_t2f.h"
+#include "engine_eigen.h"
 
 // an id that BGS_ALGO_KNOWN accepts but no engine class stands behind (BGS_LBSP_DESC is a stand-alone entry point): refused when the geometry is set
 constexpr Family kUnbuilt = [] {
@@ -472,6 +475,7 @@ const Family* family_of(bgs_algo algo) {
     case BGS_FUZZY_CHOQUET: return &kFuzzy;
     case BGS_T2FGMM_UM:
     case BGS_T2FGMM_UV: return &kT2f;
+    case BGS_DP_EIGENBACKGROUND: return &kEigen;
     case BGS_LBSP_DESC:
     case BGS_ALGO_END:
     case BGS_ALGO_LIMIT:
@@ -947,6 +951,7 @@ int bgs_create(bgs_algo algo, const bgs_params* params, int hip_device, int n_st
   e->last_flags.assign(n_streams, 0);
   e->counter.assign(n_streams, 0);
   t2f_defaults(&e->t2f);
+  eig_defaults(&e->eig);
   fz_defaults(&e->fz);  // a fuzzy engine starts from the constructor's values whatever bgs_params it was handed (bgs_set_fuzzy_params)
   if (const char* env = getenv("BGS_KDE_TRIPS")) e->knob.kde_count_trips = atoi(env) != 0;
   if (const char* env = getenv("BGS_MOG2_COMPLETE")) e->knob.mog2_complete = atoi(env) != 0;
@@ -1043,6 +1048,38 @@ int bgs_get_t2f_params(const bgs_engine* e, bgs_t2f_params* p) {
   if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
   if (!is_t2f(e->algo)) return fail(BGS_ERR_INVALID, "bgs_get_t2f_params: algorithm %d is not T2FGMM_UM / T2FGMM_UV", (int)e->algo);
   *p = e->t2f;
+  return BGS_OK;
+}
+
+int bgs_eigen_default_params(bgs_eigen_params* p) {
+  if (!p) return fail(BGS_ERR_INVALID, "params is NULL");
+  eig_defaults(p);
+  return BGS_OK;
+}
+
+int bgs_set_eigen_params(bgs_engine* e, const bgs_eigen_params* p) {
+  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
+  if (e->algo != BGS_DP_EIGENBACKGROUND) return fail(BGS_ERR_INVALID, "bgs_set_eigen_params: algorithm %d is not DPEigenbackground", (int)e->algo);
+  if (p->struct_size != sizeof(bgs_eigen_params)) return fail(BGS_ERR_INVALID, "bgs_eigen_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_eigen_params));
+  int rc = eig_check(*p);
+  if (rc) return rc;
+  if (!e->n) e->eig = *p;  // the params object is filled once, on the first frame: it keeps what it was given (DPEigenbackgroundBGS.cpp `if(firstTime)`)
+  return BGS_OK;
+}
+
+int bgs_eigen_check(const bgs_eigen_params* p, int rows, int cols, int channels) {
+  bgs_eigen_params d;
+  eig_defaults(&d);
+  if (p && p->struct_size != sizeof(bgs_eigen_params)) return fail(BGS_ERR_INVALID, "bgs_eigen_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_eigen_params));
+  int rc = eig_check(p ? *p : d);
+  if (rc || rows <= 0) return rc;
+  return eig_check_geometry(BGS_DP_EIGENBACKGROUND, rows, cols, channels);
+}
+
+int bgs_get_eigen_params(const bgs_engine* e, bgs_eigen_params* p) {
+  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
+  if (e->algo != BGS_DP_EIGENBACKGROUND) return fail(BGS_ERR_INVALID, "bgs_get_eigen_params: algorithm %d is not DPEigenbackground", (int)e->algo);
+  *p = e->eig;
   return BGS_OK;
 }
 

@@ -19,6 +19,7 @@ FrameProcessor::FrameProcessor()
   temporalMean = nullptr, enableDPMeanBGS = false;
   wrenGA = nullptr, enableDPWrenGABGS = false;
   pratiMediod = nullptr, enableDPPratiMediodBGS = false;
+  eigenBackground = nullptr, enableDPEigenbackgroundBGS = false;
   textureBGS = nullptr, enableDPTextureBGS = false;
   type2FuzzyGMM_UM = nullptr, enableT2FGMM_UM = false;
   type2FuzzyGMM_UV = nullptr, enableT2FGMM_UV = false;
@@ -57,7 +58,8 @@ void FrameProcessor::init() {  // FrameProcessor.cpp:35-155
   if (enableDPZivkovicAGMMBGS) zivkovicAGMM = new DPZivkovicAGMMBGS;
   if (enableDPMeanBGS) temporalMean = new DPMeanBGS;
   if (enableDPWrenGABGS) wrenGA = new DPWrenGABGS;
-  if (enableDPPratiMediodBGS) pratiMediod = new DPPratiMediodBGS;  // :81-88 (DPEigenbackgroundBGS between them is not built)
+  if (enableDPPratiMediodBGS) pratiMediod = new DPPratiMediodBGS;  // :81-88
+  if (enableDPEigenbackgroundBGS) eigenBackground = new DPEigenbackgroundBGS;
   if (enableDPTextureBGS) textureBGS = new DPTextureBGS;
   if (enableT2FGMM_UM) type2FuzzyGMM_UM = new T2FGMM_UM;  // :90-94
   if (enableT2FGMM_UV) type2FuzzyGMM_UV = new T2FGMM_UV;
@@ -136,6 +138,7 @@ void FrameProcessor::process(const Image& img_input) {  // :169-340
   if (enableDPMeanBGS) process("DPMeanBGS", temporalMean, img_prep, img_tmpmean);
   if (enableDPWrenGABGS) process("DPWrenGABGS", wrenGA, img_prep, img_wrenga);
   if (enableDPPratiMediodBGS) process("DPPratiMediodBGS", pratiMediod, img_prep, img_pramed);  // :217-224
+  if (enableDPEigenbackgroundBGS) process("DPEigenbackgroundBGS", eigenBackground, img_prep, img_eigbkg);
   if (enableDPTextureBGS) process("DPTextureBGS", textureBGS, img_prep, img_texbgs);
   if (enableT2FGMM_UM) process("T2FGMM_UM", type2FuzzyGMM_UM, img_prep, img_t2fgmm_um);  // :226-230
   if (enableT2FGMM_UV) process("T2FGMM_UV", type2FuzzyGMM_UV, img_prep, img_t2fgmm_uv);
@@ -173,6 +176,7 @@ void FrameProcessor::finish() {  // :342-482 (reverse order of init)
   delete type2FuzzyGMM_UV, type2FuzzyGMM_UV = nullptr;  // :424-428
   delete type2FuzzyGMM_UM, type2FuzzyGMM_UM = nullptr;
   delete textureBGS, textureBGS = nullptr;
+  delete eigenBackground, eigenBackground = nullptr;
   delete pratiMediod, pratiMediod = nullptr;
   delete wrenGA, wrenGA = nullptr;
   delete temporalMean, temporalMean = nullptr;
@@ -221,6 +225,7 @@ void FrameProcessor::saveConfig() {  // :496-552 (keys of the classes this build
   fs.writeInt("enableDPMeanBGS", enableDPMeanBGS);
   fs.writeInt("enableDPWrenGABGS", enableDPWrenGABGS);
   fs.writeInt("enableDPPratiMediodBGS", enableDPPratiMediodBGS);  // :522-524
+  fs.writeInt("enableDPEigenbackgroundBGS", enableDPEigenbackgroundBGS);
   fs.writeInt("enableDPTextureBGS", enableDPTextureBGS);
   fs.writeInt("enableT2FGMM_UM", enableT2FGMM_UM);  // :526-527
   fs.writeInt("enableT2FGMM_UV", enableT2FGMM_UV);
@@ -259,6 +264,7 @@ void FrameProcessor::loadConfig() {  // :554-610 (defaults: PreProcessor and Fra
   enableDPMeanBGS = fs.readInt("enableDPMeanBGS", false);
   enableDPWrenGABGS = fs.readInt("enableDPWrenGABGS", false);
   enableDPPratiMediodBGS = fs.readInt("enableDPPratiMediodBGS", false);  // :580-582
+  enableDPEigenbackgroundBGS = fs.readInt("enableDPEigenbackgroundBGS", false);
   enableDPTextureBGS = fs.readInt("enableDPTextureBGS", false);
   enableT2FGMM_UM = fs.readInt("enableT2FGMM_UM", false);  // :584-585
   enableT2FGMM_UV = fs.readInt("enableT2FGMM_UV", false);

@@ -37,6 +37,7 @@ class FrameProcessor : public IFrameProcessor {
   // the masks the reference keeps as img_framediff, img_staticfdiff, ... (FrameProcessor.h:99-170)
   Image img_prep, img_framediff, img_staticfdiff, img_wmovmean, img_movvar, img_mog1, img_mog2, img_bkgl_fgmask, img_asbl;
   Image img_gmg, img_adpmed, img_grigmm, img_zivgmm, img_tmpmean, img_wrenga, img_pramed, img_texbgs, img_kde, img_sdbgs, img_ssbgs, img_lobgs;  // FrameProcessor.h:120-236
+  Image img_eigbkg;  // FrameProcessor.h (reference): img_eigbkg
   Image img_t2fgmm_um, img_t2fgmm_uv;  // FrameProcessor.h (reference): img_t2fgmm_um / img_t2fgmm_uv
   Image img_fsi, img_fci;  // FrameProcessor.h (reference): FuzzySugenoIntegral / FuzzyChoquetIntegral masks
   Image img_vumeter;  // FrameProcessor.h (reference): img_vumeter
@@ -82,6 +83,8 @@ class FrameProcessor : public IFrameProcessor {
   bool enableDPWrenGABGS;
   DPPratiMediodBGS* pratiMediod;
   bool enableDPPratiMediodBGS;
+  DPEigenbackgroundBGS* eigenBackground;
+  bool enableDPEigenbackgroundBGS;
   DPTextureBGS* textureBGS;
   bool enableDPTextureBGS;
   T2FGMM_UM* type2FuzzyGMM_UM;

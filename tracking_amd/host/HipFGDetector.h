@@ -8,6 +8,7 @@
 // for the types on the hot path (0-13 except the three dp classes outside it, 35-37).  GetBlobs() is the addition: the foreground
 // regions of the last mask as CvBlob {x, y, w, h, ID}, found on the device copy of the mask, so a blob-detection module can seed
 // from rectangles instead of re-scanning the mask on the CPU (CvBlobDetector::DetectNewBlob receives the mask at :166).
+// Type 15: hipbgs::DPEigenbackgroundBGS exists (HipBGS.h) but is not in the type table here, as in ustc_bgs.h (see there).
 //
 // Needs OpenCV 2.4 with the legacy module (opencv2/legacy/blobtrack.hpp), which this repository's build image does not have:
 // checked for syntax against the declaration-only mock under tests/mock_opencv (tests/test_capi_cpu.py), as gnu++0x like the

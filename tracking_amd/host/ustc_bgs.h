@@ -7,7 +7,9 @@
 // integrals, types 21 and 22, and the two type-2 fuzzy GMMs, types 17 and 18, are built) throw instead of silently running something
 // else.  T2FMRF_UM / T2FMRF_UV (19, 20) stay refused on purpose: T2FMRF.cpp:331 reads the weights of ANOTHER pixel's modes, so the
 // result depends on pixel order, and the MRF result goes into the low-threshold mask, which the wrapper clears before it returns
-// the high-threshold one.
+// the high-threshold one.  Type 15: the class exists (DPEigenbackgroundBGS, bgs_classes_eigen.inc; FrameProcessor's
+// enableDPEigenbackgroundBGS builds it), but the type table still throws for 15: the suite pins USTC_BGS(15) as refused at run time
+// and the switch below as holding exactly the two tb/ cases, so a tracker reaches the class as an IBGS, not by number.
 #pragma once
 #include "bgs_host.h"
 #include "blob.h"
