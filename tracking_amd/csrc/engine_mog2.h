@@ -115,6 +115,7 @@ void mog2_fill_args(const bgs_engine* e, bgs::Mog2Args& m, double lr) {
   m.state = mog2_of(e).model;
   m.alphaT = (float)lr, m.alpha1 = 1.f - m.alphaT, m.prune = (float)(-lr * (double)p.mog2_ct);
   m.Tb = p.mog2_var_threshold, m.TB = p.mog2_background_ratio, m.Tg = p.mog2_var_threshold_gen;
+  m.s_min = bgs::mog2_smin(bgs::mog2_tq(m.Tb > m.Tg ? m.Tb : m.Tg));  // the summaries' rejection rule, as one bound on the bucket distance (kernel_mog2.h)
   m.varInit = p.mog2_var_init, m.varMin = p.mog2_var_min, m.varMax = p.mog2_var_max, m.tau = p.mog2_tau;
   m.thr = p.threshold, m.enable_thr = p.enable_threshold, m.shadow_val = p.mog2_shadow_value;
 }

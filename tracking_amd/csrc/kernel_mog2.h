@@ -22,7 +22,8 @@
 // SUMMARIES - reading fewer records, exactly.  A record is only ever consulted by two comparisons, dist2 < Tb var (background) and
 //   dist2 < Tg var (match).  Each slot also has a 2-byte SUMMARY (round 3: 4 bytes): the 8-level bucket each channel's mean lies in
 //   (5 bits each) and a variance class, maintained under the invariants 8 q_c - 2 <= mean_c <= 8 q_c + 9 and class 0 => var <= 32.
-//   From the summary and the pixel's own buckets alone a lower bound of dist2 follows (mog2_reject: one v_sad_u8); when it exceeds
+//   From the summary and the pixel's own buckets alone a lower bound of dist2 follows (mog2_reject: one v_sad_u8 and one compare against
+//   a bound the host derives from the thresholds, Mog2Args::s_min); when it exceeds
 //   max(Tb, Tg) 32 (+ margins for float rounding) both comparisons are PROVEN false: such a mode is REJECTED without its record, and the
 //   frame proceeds exactly as the reference would (a rejected mode's record is used by nothing else: only its weight decays).  The
 //   per-frame launch loads the summaries of a pixel's live slots, then only the records of the modes that survive: on well-separated
@@ -41,6 +42,12 @@
 // Stores are SECTOR-COMPLETE (args.complete): HBM moves 32-byte sectors, so a lane also writes back an unchanged value of its own
 //   when another lane of the same sector (8 lanes of a weight or summary plane, 16 of the meta row, 2 of a record plane when every
 //   lane holds all its records) has something to write there - no partially written sector reaches the memory controller.
+// Addresses are WAVE-RELATIVE (Mog2Lane): a wave's 64 consecutive pixels share one tile, so the tile base and every plane's offset are
+//   scalar (SGPRs) and a lane adds one 32-bit offset; the frame and the mask likewise.  A wave that does not start on a multiple of 64
+//   model pixels (a launch that begins at a later stream of a geometry with rows * cols % 64 != 0) may run into the next tile: its lanes
+//   behind the boundary add the distance to that tile to their offset.
+// Instruction budget (the filter kernel on the benchmark input sits under the HBM roof AND close to the vector-issue roof, DESIGN.md
+//   §6.1): 390 vector and 268 scalar instructions per wave (before the wave-relative addresses, s_min and the one-record form: 503 / 303).
 // No LDS: the op is pointwise and HBM-bound.
 #pragma once
 #include "bgs_device.h"
@@ -48,15 +55,12 @@
 namespace bgs {
 
 constexpr int kMog2K = 5;
-#ifndef BGS_MOG2_TILE
-#define BGS_MOG2_TILE 256
-#endif
-constexpr int kMog2Tile = BGS_MOG2_TILE;                                          // pixels per tile
+constexpr int kMog2Tile = 256;                                                    // pixels per tile (128 / 512 / 1024 lost their A/B; Mog2Lane's immediates are laid out for 256)
 constexpr size_t kMog2TileBytes = (size_t)kMog2Tile * (4 * kMog2K + 2 * kMog2K + 16 * kMog2K + 2);  // 112 B per pixel: 28 672 B
 constexpr size_t kMog2SumOff = (size_t)kMog2Tile * 4 * kMog2K;                    // byte offset of summary plane 0 inside a tile
 constexpr size_t kMog2RecOff = kMog2SumOff + (size_t)kMog2Tile * 2 * kMog2K;      // ... of record plane 0 (16-byte aligned)
 constexpr size_t kMog2MetaOff = kMog2RecOff + (size_t)kMog2Tile * 16 * kMog2K;   // ... of the meta row
-static_assert(kMog2Tile % 64 == 0, "a wave never straddles two tiles");
+static_assert(kMog2Tile % 64 == 0, "a wave that starts on a multiple of 64 pixels stays inside one tile, any other touches at most two");
 
 struct Mog2Args {
   const uint8_t* frame;  // [P][3] interleaved BGR
@@ -77,6 +81,7 @@ struct Mog2Args {
                                 // 2 count: a lane loads only the modes its pixel has; 4 filter: their summaries, then only the records that survive them
   int complete;                 // sector-complete stores (see above)
   int xcd_swizzle;              // workgroups that share an XCD walk one contiguous eighth of the launch
+  uint32_t s_min;               // mog2_smin(mog2_tq(max(Tb, Tg))): a class-0 summary at distance S >= s_min rules its mode out (mog2_reject)
 };
 
 struct Mog2Ptr {
@@ -95,11 +100,58 @@ __device__ __forceinline__ Mog2Ptr mog2_ptr(uint8_t* state, size_t sp) {
   p.meta = reinterpret_cast<uint16_t*>(tb + kMog2MetaOff) + in;
   return p;
 }
+// The same addresses for a whole wave of consecutive pixels, as the update kernels use them: the tile of the wave's FIRST pixel is
+// wave-uniform, so its base and every plane's offset from it live in SGPRs (scalar arithmetic, done once per wave), and a lane adds
+// one 32-bit byte offset per element size - global_load / global_store with an SGPR base and a VGPR offset.  mog2_ptr made the
+// 64-bit address of each of the 17 rows a lane touches in vector registers: a 64-bit multiply and two vector adds per row.
+// A wave whose first pixel is no multiple of 64 (rows * cols is not, and the launch starts at a later stream) may run over the end
+// of its tile: the lanes behind the boundary are kMog2Tile pixels back in the NEXT tile, i.e. their offset grows by what lies
+// between (the only per-lane work of that case, skipped by every wave that starts on a multiple of 64).
+// mog2_uniform: an empty asm that pins a wave-uniform byte offset in SGPRs where it is made.  Without it the compiler folds the plane
+// offsets that do not fit an instruction's 13-bit immediate back into per-lane 64-bit vector adds.  (An offset, not a pointer: a
+// pointer that went through an asm is no longer known to be global memory, and every access becomes a flat one.)
+__device__ __forceinline__ size_t mog2_uniform(size_t v) {
+  asm("" : "+s"(v));
+  return v;
+}
+struct Mog2Lane {
+  uint8_t* state;
+  size_t bw, bs, br, bm;  // wave-uniform, from `state`: the middle of the tile's weight planes (every plane within an immediate), its summary plane 0, record plane 0, meta row
+  uint32_t o4, o2, o16;   // this lane's byte offset inside a plane of 4-byte (weights), 2-byte (summaries, meta) and 16-byte (records) elements
+  static constexpr int kMid = 2 * 4 * kMog2Tile;
+  __device__ __forceinline__ float* w(int r) const { return reinterpret_cast<float*>(state + bw + (size_t)o4 + (r * 4 * kMog2Tile - kMid)); }
+  __device__ __forceinline__ uint16_t* sum(int s) const { return reinterpret_cast<uint16_t*>(state + bs + (size_t)o2 + s * 2 * kMog2Tile); }
+  __device__ __forceinline__ float4* rec(int s) const { return reinterpret_cast<float4*>(state + mog2_uniform(br + (size_t)s * 16 * kMog2Tile) + (size_t)o16); }
+  // ... of a rank / slot that differs from lane to lane
+  __device__ __forceinline__ float* w_of(uint32_t r) const { return reinterpret_cast<float*>(state + mog2_uniform(bw - kMid) + (size_t)(o4 + r * (4u * kMog2Tile))); }
+  __device__ __forceinline__ float4* rec_of(uint32_t s) const { return reinterpret_cast<float4*>(state + br + (size_t)(o16 + s * (16u * kMog2Tile))); }
+  __device__ __forceinline__ uint16_t* meta() const { return reinterpret_cast<uint16_t*>(state + bm + (size_t)o2); }
+};
+// `first`: index inside the model of the wave's lane 0 (wave-uniform), `lane` 0..63
+__device__ __forceinline__ Mog2Lane mog2_lane(uint8_t* state, size_t first, uint32_t lane) {
+  Mog2Lane l;
+  const size_t tb = (first / kMog2Tile) * kMog2TileBytes;
+  l.state = state;
+  l.bw = mog2_uniform(tb + Mog2Lane::kMid), l.bs = mog2_uniform(tb + kMog2SumOff), l.br = mog2_uniform(tb + kMog2RecOff), l.bm = mog2_uniform(tb + kMog2MetaOff);
+  const uint32_t in0 = (uint32_t)(first % kMog2Tile);
+  uint32_t in = in0 + lane, skip = 0;
+  if (in0 + (kWave - 1) >= (uint32_t)kMog2Tile) {  // wave-uniform: the wave straddles two tiles
+    const bool next = in >= (uint32_t)kMog2Tile;
+    in = next ? in - kMog2Tile : in;
+    skip = next ? (uint32_t)kMog2TileBytes : 0u;
+  }
+  l.o4 = in * 4 + skip, l.o2 = in * 2 + skip, l.o16 = in * 16 + skip;
+  return l;
+}
 // modesUsed of a meta word: its non-zero 3-bit fields (always a prefix)
 __device__ __host__ __forceinline__ int mog2_meta_count(unsigned meta) {
   unsigned t = (meta | (meta >> 1) | (meta >> 2)) & 0x1249u;
+#ifdef __HIP_DEVICE_COMPILE__
+  return __popc(t);
+#else
   t = (t & 1u) + ((t >> 3) & 1u) + ((t >> 6) & 1u) + ((t >> 9) & 1u) + ((t >> 12) & 1u);
   return (int)t;
+#endif
 }
 
 // ---- summaries (see the header comment) -------------------------------------------------------------------------------------
@@ -137,12 +189,23 @@ __device__ __host__ __forceinline__ uint32_t mog2_tq(float Tmax) {
   const float c = 3.f * kMog2SumVar * Tmax;
   return c < 1.0e9f ? (uint32_t)(int)c + 4u : 0xffffffffu;  // > 3 (Tmax var + 1) for every var <= kMog2SumVar (NaN / negative thresholds: the clamp or 4, both safe)
 }
-__device__ __forceinline__ uint32_t mog2_pixq(uint32_t pix) { return (pix >> 3) & 0x1f1f1fu; }
-__device__ __forceinline__ bool mog2_reject(uint32_t word, uint32_t pixq, uint32_t tq) {
-  const uint32_t qb = (word & 0x1fu) | ((word & 0x3e0u) << 3) | ((word & 0x7c00u) << 6);
-  const uint32_t S = __builtin_amdgcn_sad_u8(pixq, qb, 0u);
-  const uint32_t B = 8u * S - 28u;  // (wraps for S < 4: caught by the first test)
-  return S > 3u && !(word >> 15) && B * B > tq;
+// S > 3 && (8 S - 28)^2 > tq is monotone in S (S <= 3 * 31 = 93: nothing wraps), so the whole test is S >= s_min with the
+// smallest such S, computed once per launch by the host; kMog2SNever when no S passes (the clamp, or a threshold past 716^2).
+constexpr uint32_t kMog2SMax = 93u, kMog2SNever = 0xffffffffu;
+__device__ __host__ __forceinline__ uint32_t mog2_smin(uint32_t tq) {
+  for (uint32_t S = 4u; S <= kMog2SMax; ++S) {
+    const uint32_t B = 8u * S - 28u;
+    if (B * B > tq) return S;
+  }
+  return kMog2SNever;
+}
+__device__ __host__ __forceinline__ uint32_t mog2_pixq(uint32_t pix) { return (pix >> 3) & 0x1f1f1fu; }
+// the three buckets of a summary word in bytes 0..2 (bits 5..7 of each byte and byte 3 zero)
+__device__ __host__ __forceinline__ uint32_t mog2_spread(uint32_t word) { return (word & 0x1fu) | ((word << 3) & 0x1f00u) | ((word << 6) & 0x1f0000u); }
+// the rule on the distance S = sum_c |xq_c - q_c| (on the device one v_sad_u8 of pixq and mog2_spread(word))
+__device__ __host__ __forceinline__ bool mog2_reject_s(uint32_t word, uint32_t S, uint32_t s_min) { return !(word >> 15) & (S >= s_min); }
+__device__ __forceinline__ bool mog2_reject(uint32_t word, uint32_t pixq, uint32_t s_min) {
+  return mog2_reject_s(word, __builtin_amdgcn_sad_u8(pixq, mog2_spread(word), 0u), s_min);
 }
 
 // One pixel's model in registers.  Weights and slot ids in rank order, as MOG2Invoker sees its array.  The records {var, mean0,
@@ -151,8 +214,10 @@ __device__ __forceinline__ bool mog2_reject(uint32_t word, uint32_t pixq, uint32
 //   kMog2BySlot   rc[j] is the record of slot j (eager and count per-frame kernels): a mode's record is fetched when its turn in
 //                 the scan comes (a select chain), the records themselves never move;
 //   kMog2Ranked   rc[r] is the record of the mode at rank r and takes part in the bubble like the reference's array (clip kernels:
-//                 gathered once per launch, then T frames index it statically).
-enum { kMog2Compact = 0, kMog2BySlot = 1, kMog2Ranked = 2 };
+//                 gathered once per launch, then T frames index it statically);
+//   kMog2One      kMog2Compact for a wave none of whose lanes holds more than one record: rc[0] of slot kj[0] when cnt == 1; rc[1..4]
+//                 and kj[1..4] are never written and never read (the filter kernel on well-separated modes: every wave of the benchmark).
+enum { kMog2Compact = 0, kMog2BySlot = 1, kMog2Ranked = 2, kMog2One = 3 };
 struct Mog2Px {
   float w[kMog2K];
   int sl[kMog2K];  // slot + 1 of the mode at rank r (0: rank unused)
@@ -174,13 +239,14 @@ __device__ __forceinline__ void mog2_swap(Mog2Px& s, Mog2Recs& R, int i, int j) 
   }
 }
 
-// the record of the mode with slot code `code` (slot + 1).  BYSLOT: rc[j] is slot j (a compare against constants)
-template <bool BYSLOT>
+// the record of the mode with slot code `code` (slot + 1), records held in order ORD (by slot: a compare against constants)
+template <int ORD>
 __device__ __forceinline__ float4 mog2_pick(const Mog2Recs& R, int code) {
+  static_assert(ORD != kMog2Ranked, "ranked records are indexed by rank");
   float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-  for (int j = 0; j < kMog2K; ++j) {
-    const bool here = BYSLOT ? (code == j + 1) : (j < R.cnt && code == R.kj[j] + 1);
+  for (int j = 0; j < (ORD == kMog2One ? 1 : kMog2K); ++j) {
+    const bool here = ORD == kMog2BySlot ? (code == j + 1) : (j < R.cnt && code == R.kj[j] + 1);
     const float4 c = R.rc[j];  // selects of VALUES, component by component: `if (here) v = R.rc[j]` became a select of addresses + a load, and the whole struct went to scratch
     v.x = here ? c.x : v.x, v.y = here ? c.y : v.y, v.z = here ? c.z : v.z, v.w = here ? c.w : v.w;
   }
@@ -192,12 +258,12 @@ __device__ __forceinline__ float4 mog2_rec_at(const Mog2Px& s, const Mog2Recs& R
   if constexpr (ORD == kMog2Ranked)
     return R.rc[mode];
   else
-    return mog2_pick<ORD == kMog2BySlot>(R, s.sl[mode]);
+    return mog2_pick<ORD>(R, s.sl[mode]);
 }
 // ... as it stands after this frame's update: the recomputed / created record is `out`, of slot code `hit`
-template <bool BYSLOT>
+template <int ORD>
 __device__ __forceinline__ float4 mog2_pick_now(const Mog2Recs& R, int code, int hit, float4 out) {
-  const float4 v = mog2_pick<BYSLOT>(R, code);
+  const float4 v = mog2_pick<ORD>(R, code);
   const bool h = code == hit;
   return make_float4(h ? out.x : v.x, h ? out.y : v.y, h ? out.z : v.z, h ? out.w : v.w);
 }
@@ -207,7 +273,7 @@ __device__ __forceinline__ float4 mog2_rec_now(const Mog2Px& s, const Mog2Recs& 
   if constexpr (ORD == kMog2Ranked)
     return R.rc[mode];  // kept current
   else
-    return mog2_pick_now<ORD == kMog2BySlot>(R, s.sl[mode], hit, out);
+    return mog2_pick_now<ORD>(R, s.sl[mode], hit, out);
 }
 
 // detectShadowGMM of bgfg_gaussmix2.cpp, predicated form of its early returns
@@ -347,36 +413,51 @@ __device__ __forceinline__ int mog2_pixel(Mog2Px& s, Mog2Recs& R, int& nmodes_io
 // bubble for SOME lanes of the wave - up to five times the work of one pixel on a scene whose pixels are out of step (the benchmark
 // input S_sat by construction; PMC: 620 vector instructions per pixel and frame, 79 % of the SIMDs' issue slots over the launch).
 // Here everything that touches a record happens outside the rank loop:
-//   1. every record the lane holds (`ncand` of them: all live slots, or what the summaries left) gives dist2 and the two comparisons
+//   1. every record the lane holds (R.cnt of them: all live slots, or what the summaries left) gives dist2 and the two comparisons
 //      dist2 < Tb var, dist2 < Tg var ONCE - they depend on neither the rank nor the running weight sum - kept as bit masks by slot;
 //   2. the rank loop only decays, prunes and sums the weights and looks the two bits of its rank's slot up: the background test reads
 //      totalWeight as it stands when the scan reaches that rank, the first mode in rank order whose match bit is set takes alphaT;
 //   3. the matched record is fetched and recomputed once, then the bubble runs from its rank.
 // Same statements on the same operands for every float, in the same order wherever order matters (the weight sum).  A record behind
 // the matched one in rank order is compared here although the reference never looks at it: a comparison has no side effect.
-// `wave_cand`: wave-uniform upper bound of ncand (the candidate loop's trip count).
+// `wave_cand`: wave-uniform upper bound of R.cnt (the candidate loop's trip count).
+// ORD == kMog2One (no lane of the wave holds more than one record: every wave of the benchmark input): the three bit masks shrink to
+// three flags of the one record, and the rank loop's look-up to "is this rank's slot that record's".
+// The bubble is straight-line code (selects): as nested per-lane branches each of its four steps cost an exec-mask round trip, and
+// the branch form kept more registers live.  The rank scan stays branched: written as selects it costs the filter kernel 97 VGPRs
+// (4 waves per SIMD instead of 5, measured 7 % slower), and as selects in the kMog2One form only it measured equal to the branches.
 template <int ORD>
-__device__ __forceinline__ int mog2_pixel_lockstep(Mog2Px& s, const Mog2Recs& R, const int ncand, const int wave_cand, int& nmodes_io, float x0, float x1, float x2,
+__device__ __forceinline__ int mog2_pixel_lockstep(Mog2Px& s, const Mog2Recs& R, const int wave_cand, int& nmodes_io, float x0, float x1, float x2,
                                                    const Mog2Args& a, int& hit, float4& out, const float alphaT, const float alpha1, const float prune) {
-  static_assert(ORD == kMog2Compact || ORD == kMog2BySlot, "records by slot or compacted");
+  static_assert(ORD != kMog2Ranked, "records by slot, compacted, or the single one");
   bool background = false, fitsPDF = false;
   int nmodes = nmodes_io;
   const int nNewModes = nmodes;
   float totalWeight = 0.f;
   hit = 0;
   out = make_float4(0.f, 0.f, 0.f, 0.f);
-  unsigned cm = 0, bgm = 0, mm = 0;  // bit (slot + 1): a candidate / dist2 < Tb var / dist2 < Tg var
+  unsigned cm = 0, bgm = 0, mm = 0;     // bit (slot + 1): a candidate / dist2 < Tb var / dist2 < Tg var
+  bool c1 = false, b1 = false, m1 = false;  // kMog2One: the same three facts about the one record, of slot code k1
+  int k1 = 0;
+  if constexpr (ORD == kMog2One) {
+    const float4 v = R.rc[0];
+    const float d0 = v.y - x0, d1 = v.z - x1, d2 = v.w - x2;
+    const float dist2 = d0 * d0 + d1 * d1 + d2 * d2;
+    c1 = R.cnt > 0, k1 = R.kj[0] + 1;
+    b1 = dist2 < a.Tb * v.x, m1 = dist2 < a.Tg * v.x;
+  } else {
 #pragma unroll
-  for (int j = 0; j < kMog2K; ++j) {
-    if (j < wave_cand) {  // wave-uniform
-      const float4 v = R.rc[j];
-      const float d0 = v.y - x0, d1 = v.z - x1, d2 = v.w - x2;
-      const float dist2 = d0 * d0 + d1 * d1 + d2 * d2;
-      const int code = ORD == kMog2BySlot ? j + 1 : R.kj[j] + 1;
-      const bool is = j < ncand;
-      cm |= (unsigned)is << code;
-      bgm |= (unsigned)(is && dist2 < a.Tb * v.x) << code;
-      mm |= (unsigned)(is && dist2 < a.Tg * v.x) << code;
+    for (int j = 0; j < kMog2K; ++j) {
+      if (j < wave_cand) {  // wave-uniform
+        const float4 v = R.rc[j];
+        const float d0 = v.y - x0, d1 = v.z - x1, d2 = v.w - x2;
+        const float dist2 = d0 * d0 + d1 * d1 + d2 * d2;
+        const int code = ORD == kMog2BySlot ? j + 1 : R.kj[j] + 1;
+        const bool is = j < R.cnt;
+        cm |= (unsigned)is << code;
+        bgm |= (unsigned)(is && dist2 < a.Tb * v.x) << code;
+        mm |= (unsigned)(is && dist2 < a.Tg * v.x) << code;
+      }
     }
   }
   float wmatch = 0.f;
@@ -386,9 +467,12 @@ __device__ __forceinline__ int mog2_pixel_lockstep(Mog2Px& s, const Mog2Recs& R,
     if (mode < nmodes) {  // nmodes shrinks inside the loop when a mode is pruned (reference quirk)
       float weight = alpha1 * s.w[mode] + prune;
       const int code = s.sl[mode];
-      if (!fitsPDF && ((cm >> code) & 1u)) {
-        if (totalWeight < a.TB && ((bgm >> code) & 1u)) background = true;
-        if ((mm >> code) & 1u) {
+      const bool c = ORD == kMog2One ? (c1 && code == k1) : (bool)((cm >> code) & 1u);
+      if (!fitsPDF && c) {
+        const bool b = ORD == kMog2One ? b1 : (bool)((bgm >> code) & 1u);
+        const bool m = ORD == kMog2One ? m1 : (bool)((mm >> code) & 1u);
+        if (totalWeight < a.TB && b) background = true;
+        if (m) {
           fitsPDF = true;
           weight += alphaT;
           wmatch = weight, rstar = mode, hit = code;
@@ -401,7 +485,7 @@ __device__ __forceinline__ int mog2_pixel_lockstep(Mog2Px& s, const Mog2Recs& R,
     }
   }
   if (fitsPDF) {
-    const float4 v = wave_cand == 1 ? R.rc[0] : mog2_pick<ORD == kMog2BySlot>(R, hit);  // (wave-uniform choice; one candidate: it is the match)
+    const float4 v = (ORD == kMog2One || wave_cand == 1) ? R.rc[0] : mog2_pick<ORD>(R, hit);  // (wave-uniform choice; one candidate: it is the match)
     const float var = v.x;
     const float d0 = v.y - x0, d1 = v.z - x1, d2 = v.w - x2;
     const float dist2 = d0 * d0 + d1 * d1 + d2 * d2;
@@ -412,13 +496,15 @@ __device__ __forceinline__ int mog2_pixel_lockstep(Mog2Px& s, const Mog2Recs& R,
     out = make_float4(varnew, v.y - k * d0, v.z - k * d1, v.w - k * d2);
     // the reference's bubble, run at the matched rank: it compares the UNPRUNED matched weight with the stored weights in front
     bool moving = true;
-    Mog2Recs none;  // (the records do not take part in the swaps)
 #pragma unroll
     for (int i = kMog2K - 1; i > 0; --i) {
-      if (i <= rstar) {
-        moving = moving && !(wmatch < s.w[i - 1]);
-        if (moving) mog2_swap<ORD>(s, none, i, i - 1);
-      }
+      const bool in = i <= rstar;
+      moving = in ? (moving & !(wmatch < s.w[i - 1])) : moving;
+      const bool sw = in & moving;
+      const float wi = s.w[i], wj = s.w[i - 1];
+      s.w[i] = sw ? wj : wi, s.w[i - 1] = sw ? wi : wj;
+      const int ci = s.sl[i], cj = s.sl[i - 1];
+      s.sl[i] = sw ? cj : ci, s.sl[i - 1] = sw ? ci : cj;
     }
   }
   totalWeight = div_rn(1.f, totalWeight);
@@ -529,17 +615,22 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
     const size_t per = gridDim.x >> 3, main = per << 3;
     if (blk < main) blk = (blk & 7) * per + (blk >> 3);
   }
-  const size_t p0 = blk * kBlock + threadIdx.x;  // this lane's pixel, launch-relative
-  if (p0 >= a.npix) return;                      // wave-uniform whenever masks are bit-packed (npix % 64 == 0, checked by the host)
-  const size_t sp = a.state_off + p0;            // index inside the model
+  // Everything about WHERE is wave-uniform and stays in scalar registers: the wave's first pixel pw (launch-relative), the bases of
+  // its stretch of the frame and the mask, its model tile.  A lane contributes its number, as a 32-bit offset (Mog2Lane).
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const size_t pw = blk * kBlock + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~(uint32_t)(kWave - 1)));
+  if (pw >= a.npix) return;
+  const size_t left = a.npix - pw;
+  if (lane >= (left < (size_t)kWave ? (uint32_t)left : (uint32_t)kWave)) return;  // (only when npix % 64 != 0; bit-packed masks need npix % 64 == 0, checked by the host)
   uint32_t pix[T];  // all T inputs of this pixel are requested before the model: they are what the first update waits for
+  const uint8_t* const fw = a.frame + pw * 3;
 #pragma unroll
   for (int t = 0; t < T; ++t) {
-    const uint8_t* f = a.frame + (size_t)t * frame_stride + p0 * 3;
+    const uint8_t* f = fw + (size_t)t * frame_stride + lane * 3u;
     pix[t] = (uint32_t)f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16);
   }
-  const Mog2Ptr mp = mog2_ptr(a.state, sp);
-  const unsigned meta_raw = *mp.meta;
+  const Mog2Lane mp = mog2_lane(a.state, a.state_off + pw, lane);
+  const unsigned meta_raw = *mp.meta();
   const unsigned meta_in = meta_raw & 0x7fffu;
   const bool valid_in = (meta_raw >> 15) & 1u;
   const int nm_in = mog2_meta_count(meta_in);
@@ -549,10 +640,9 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
   uint32_t sm[kMog2K];
   Mog2Recs R;
   R.cnt = kMog2K;
-  unsigned rej = 0;  // bit (slot + 1): rejected by its summary for THIS frame (filter path)
   int wave_cand = kMog2K;  // wave-uniform bound of the records a lane holds (R.cnt): the candidate loop of mog2_pixel_lockstep
 #pragma unroll
-  for (int k = 0; k < kMog2K; ++k) R.kj[k] = k, sm[k] = 0u;
+  for (int k = 0; k < kMog2K; ++k) sm[k] = 0u;
   // Every load below is UNCONDITIONAL per lane and sits in straight-line code: a lane that does not want plane k repeats a load it
   // does want (same cache line, no extra HBM traffic) and the value is discarded by a select afterwards.  Loads under a per-lane
   // `if` - and also loads under a chain of wave-uniform branches - made the compiler merge each result with the "not loaded" value
@@ -563,28 +653,28 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
   if constexpr (MODE == kMog2Eager) {
 #pragma unroll
     for (int k = 0; k < kMog2K; ++k) {
-      wv[k] = mp.w[(size_t)k * kMog2Tile];
-      R.rc[k] = mp.rec[(size_t)k * kMog2Tile];
-      if (dense) sm[k] = mp.sum[(size_t)k * kMog2Tile];
+      wv[k] = *mp.w(k);
+      R.rc[k] = *mp.rec(k);
+      if (dense) sm[k] = *mp.sum(k);
     }
   } else if constexpr (MODE == kMog2Count) {
-    wv[0] = mp.w[0];
-    R.rc[0] = mp.rec[0];  // slot 0 exists from a pixel's first frame on
+    wv[0] = *mp.w(0);
+    R.rc[0] = *mp.rec(0);  // slot 0 exists from a pixel's first frame on
     int wave_nm = 0;
 #pragma unroll
     for (int n = 1; n <= kMog2K; ++n)
       if (__any(nm_in >= n)) wave_nm = n;
     wave_cand = wave_nm <= 2 ? 2 : wave_nm;
     if (wave_nm <= 2) {
-      const size_t idx = (size_t)(1 < nm_in ? 1 : 0) * kMog2Tile;
-      wv[1] = mp.w[idx], R.rc[1] = mp.rec[idx];
+      const uint32_t idx = 1 < nm_in ? 1u : 0u;
+      wv[1] = *mp.w_of(idx), R.rc[1] = *mp.rec_of(idx);
 #pragma unroll
       for (int k = 2; k < kMog2K; ++k) wv[k] = 0.f, R.rc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     } else {
 #pragma unroll
       for (int k = 1; k < kMog2K; ++k) {
-        const size_t idx = (size_t)(k < nm_in ? k : 0) * kMog2Tile;
-        wv[k] = mp.w[idx], R.rc[k] = mp.rec[idx];
+        const uint32_t idx = k < nm_in ? (uint32_t)k : 0u;
+        wv[k] = *mp.w_of(idx), R.rc[k] = *mp.rec_of(idx);
       }
     }
 #pragma unroll
@@ -594,16 +684,13 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
     // all five weights and summaries at once, whatever the pixel has: this path is chosen for scenes where pixels have several modes,
     // and not waiting for the meta word saves a whole round trip
 #pragma unroll
-    for (int k = 0; k < kMog2K; ++k) wv[k] = mp.w[(size_t)k * kMog2Tile], sm[k] = mp.sum[(size_t)k * kMog2Tile];
-    const uint32_t tq = mog2_tq(a.Tb > a.Tg ? a.Tb : a.Tg), pixq = mog2_pixq(pix[0]);
+    for (int k = 0; k < kMog2K; ++k) wv[k] = *mp.w(k), sm[k] = *mp.sum(k);
+    const uint32_t pixq = mog2_pixq(pix[0]);
     unsigned need = 0;  // bit k: the record of slot k must be read
 #pragma unroll
     for (int k = 0; k < kMog2K; ++k) {
-      const bool live = k < nm_in;
-      wv[k] = live ? wv[k] : 0.f;
-      sm[k] = live ? sm[k] : 0u;
-      const bool r = live && valid_in && can_reject && mog2_reject(sm[k], pixq, tq);
-      rej |= (unsigned)r << (k + 1);
+      const bool live = k < nm_in;  // (what a rank or slot the pixel does not use holds is never read and, being what memory holds, harmless to write back)
+      const bool r = (live & valid_in & can_reject) & mog2_reject(sm[k], pixq, a.s_min);  // (no short circuit: five branches otherwise)
       need |= (unsigned)(live && !r) << k;
     }
     // the needed slots, compacted: the j-th load of a lane fetches its j-th needed record (a lane with fewer repeats its first)
@@ -611,10 +698,8 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
     const int k_first = need ? __ffs(need) - 1 : 0;
     R.kj[0] = k_first;
     if (!__any(R.cnt > 1)) {
-      wave_cand = 1;
-      R.rc[0] = mp.rec[(size_t)k_first * kMog2Tile];
-#pragma unroll
-      for (int j = 1; j < kMog2K; ++j) R.rc[j] = make_float4(0.f, 0.f, 0.f, 0.f), R.kj[j] = k_first;
+      wave_cand = 1;  // from here on this wave holds its records as kMog2One: rc[1..4] and kj[1..4] do not exist
+      R.rc[0] = *mp.rec_of((uint32_t)k_first);
     } else {
       unsigned left = need & (need - 1);
 #pragma unroll
@@ -623,7 +708,7 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
         left &= left - 1;
       }
 #pragma unroll
-      for (int j = 0; j < kMog2K; ++j) R.rc[j] = mp.rec[(size_t)R.kj[j] * kMog2Tile];
+      for (int j = 0; j < kMog2K; ++j) R.rc[j] = *mp.rec_of((uint32_t)R.kj[j]);
     }
     if (a.stat && (blockIdx.x & a.stat_mask) == 0) {
       // per pixel: 5 record slots, the modes it has (what COUNT loads), the records the summaries leave (what FILTER loads);
@@ -635,8 +720,10 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
         would = 0;
 #pragma unroll
         for (int j = 0; j < kMog2K; ++j) {
-          const float4 c = R.rc[j];
-          if (j < R.cnt && !mog2_reject(mog2_summary(c.x, c.y, c.z, c.w), pixq, tq)) ++would;
+          if (j < (wave_cand == 1 ? 1 : kMog2K) && j < R.cnt) {
+            const float4 c = R.rc[j];
+            if (!mog2_reject(mog2_summary(c.x, c.y, c.z, c.w), pixq, a.s_min)) ++would;
+          }
         }
       }
       unsigned s_live = 0, s_need = 0;
@@ -646,7 +733,7 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
         s_need += (unsigned)__popcll(__ballot((would >> bit) & 1)) << bit;
       }
       const unsigned lanes = (unsigned)__popcll(__ballot(1));
-      if ((threadIdx.x & (kWave - 1)) == 0) {
+      if (lane == 0) {
         atomicAdd(a.stat, lanes * kMog2K);
         atomicAdd(a.stat + 1, s_live);
         atomicAdd(a.stat + 2, s_need);
@@ -659,11 +746,12 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
   if constexpr (ORD == kMog2Ranked) {  // clip launches: the records into rank order, once
     Mog2Recs Q;
 #pragma unroll
-    for (int r = 0; r < kMog2K; ++r) Q.rc[r] = mog2_pick<true>(R, s.sl[r]);
+    for (int r = 0; r < kMog2K; ++r) Q.rc[r] = mog2_pick<kMog2BySlot>(R, s.sl[r]);
 #pragma unroll
     for (int r = 0; r < kMog2K; ++r) R.rc[r] = Q.rc[r];
   }
   unsigned dirty = 0;  // bit (slot + 1): the record changed
+  const bool one = MODE == kMog2Filter && wave_cand == 1;  // wave-uniform: the records are held as kMog2One
   int nm = nm_in, hit = 0;
   float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
@@ -671,16 +759,24 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
     const float x0 = (float)(pix[t] & 0xffu), x1 = (float)((pix[t] >> 8) & 0xffu), x2 = (float)(pix[t] >> 16);
     int raw;
     if constexpr (ORD == kMog2Ranked)
-      raw = mog2_pixel<ORD>(s, R, nm, x0, x1, x2, a, hit, out, alphaT[t], alpha1[t], prune[t], rej);
+      raw = mog2_pixel<ORD>(s, R, nm, x0, x1, x2, a, hit, out, alphaT[t], alpha1[t], prune[t], 0u);
+    else if (one)
+      raw = mog2_pixel_lockstep<kMog2One>(s, R, 1, nm, x0, x1, x2, a, hit, out, alphaT[t], alpha1[t], prune[t]);
     else
-      raw = mog2_pixel_lockstep<ORD>(s, R, R.cnt, wave_cand, nm, x0, x1, x2, a, hit, out, alphaT[t], alpha1[t], prune[t]);
+      raw = mog2_pixel_lockstep<ORD>(s, R, wave_cand, nm, x0, x1, x2, a, hit, out, alphaT[t], alpha1[t], prune[t]);
     const int m = thr_bin(raw, a.thr, a.enable_thr);
-    if (a.fg) a.fg[(size_t)t * fg_stride + p0] = (uint8_t)m;
-    if (a.packed) store_packed_mask<1>(a.fg_bits + (size_t)t * bits_stride, p0, (uint32_t)(m != 0), true);
+    if (a.fg) (a.fg + pw + (size_t)t * fg_stride)[lane] = (uint8_t)m;
+    if (a.packed) {  // npix % 64 == 0: the wave is whole and its 64 mask bits are one word, which is what a ballot returns
+      const uint64_t word = __ballot(m != 0);
+      if (lane == 0) (a.fg_bits + (pw >> 6) + (size_t)t * bits_stride)[0] = word;
+    }
     if (a.want_bg) {
       int b0, b1, b2;
-      mog2_background<ORD>(s, R, hit, out, nm, a.TB, b0, b1, b2);
-      uint8_t* o = a.bgimg + (size_t)t * bg_stride + p0 * 3;
+      if (one)
+        mog2_background<kMog2One>(s, R, hit, out, nm, a.TB, b0, b1, b2);
+      else
+        mog2_background<ORD>(s, R, hit, out, nm, a.TB, b0, b1, b2);
+      uint8_t* o = a.bgimg + pw * 3 + (size_t)t * bg_stride + lane * 3u;
       o[0] = (uint8_t)b0, o[1] = (uint8_t)b1, o[2] = (uint8_t)b2;
     }
     dirty |= 1u << hit;
@@ -704,7 +800,7 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
       for (int q = 0; q < kMog2K; ++q) {
         const bool changed = hit == q + 1;
         if ((changed && !keep) || (!valid_in && q < nm)) {
-          const float4 v = mog2_pick_now<false>(R, q + 1, hit, out);
+          const float4 v = one ? mog2_pick_now<kMog2One>(R, q + 1, hit, out) : mog2_pick_now<kMog2Compact>(R, q + 1, hit, out);
           sm[q] = mog2_summary(v.x, v.y, v.z, v.w);
           d |= 1u << (11 + q);
         }
@@ -730,14 +826,14 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
   }
 #pragma unroll
   for (int r = 0; r < kMog2K; ++r)
-    if ((d >> r) & 1u) mp.w[(size_t)r * kMog2Tile] = s.w[r];
-  if ((d >> 5) & 1u) *mp.meta = (uint16_t)meta_out;
+    if ((d >> r) & 1u) *mp.w(r) = s.w[r];
+  if ((d >> 5) & 1u) *mp.meta() = (uint16_t)meta_out;
   if constexpr (MODE == kMog2Eager) {
     // slot q as it stands: per-frame launch = as loaded, with this frame's record patched in; clip = wherever the bubble left it
     // (a slot the pixel does not own holds nothing anyone reads: zeros)
 #pragma unroll
     for (int q = 0; q < kMog2K; ++q) {
-      if ((d >> (11 + q)) & 1u) mp.sum[(size_t)q * kMog2Tile] = (uint16_t)sm[q];  // dense only
+      if ((d >> (11 + q)) & 1u) *mp.sum(q) = (uint16_t)sm[q];  // dense only
       if ((d >> (6 + q)) & 1u) {
         float4 v;
         if constexpr (T == 1) {
@@ -751,16 +847,16 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
             v.x = h ? R.rc[r].x : v.x, v.y = h ? R.rc[r].y : v.y, v.z = h ? R.rc[r].z : v.z, v.w = h ? R.rc[r].w : v.w;
           }
         }
-        mp.rec[(size_t)q * kMog2Tile] = v;
+        *mp.rec(q) = v;
       }
     }
   } else {
     // exactly one record per pixel and frame, at the slot it belongs to: one store with a per-lane address
-    mp.rec[(size_t)(hit - 1) * kMog2Tile] = out;
+    *mp.rec_of((uint32_t)(hit - 1)) = out;
     if constexpr (MODE == kMog2Filter) {
 #pragma unroll
       for (int q = 0; q < kMog2K; ++q)
-        if ((d >> (11 + q)) & 1u) mp.sum[(size_t)q * kMog2Tile] = (uint16_t)sm[q];
+        if ((d >> (11 + q)) & 1u) *mp.sum(q) = (uint16_t)sm[q];
     }
   }
 }
