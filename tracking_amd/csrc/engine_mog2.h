@@ -17,15 +17,23 @@ int mog2_check_geometry(bgs_algo, int, int, int ch) {
 //   2 count   only the modes a pixel has (one dependent round): quiet scenes, one or two modes per pixel;
 //   4 filter  summaries first, then only the records they cannot rule out (one dependent round, +4 B per mode for the
 //             summaries): pays when at least half of a pixel's records are ruled out (modes far apart).
-// About 256 sampled workgroups of every filter-kernel launch count, per pixel, the modes it has and the records that kernel loads
-// or would load (when another kernel is current, every 16th launch - every 4th of a stream's first 64 - is a filter launch for
-// that purpose).  The host never blocks: the counters come back through a pinned buffer and an event that is queried before
+// About 256 sampled workgroups of a sampling filter-kernel launch count, per pixel, the modes it has and the records that kernel loads
+// or would load.  When another kernel is current, every 16th launch - every 4th of a stream's first 64 - is a filter launch for
+// that purpose (a launch that delivers the shadow test or the background image samples in the count kernel instead).  While the
+// filter kernel is current every launch samples until two polls in a row have confirmed it, then every 8th: a sample costs a copy, a
+// memset and an event record on the launch stream between two update kernels.  The host never blocks: the counters come back through a pinned buffer and an event that is queried before
 // every launch; it switches at once on clear evidence, else when two samples in a row ask for the same other mode.
 struct Mog2State : FamilyState {
   DevPtr<uint8_t> model;     // tiles of ranked weights + fixed-slot records + rank->slot meta words (kernel_mog2.h)
   int sparse_now = 2;        // what auto mode currently runs
   int sparse_want = 2;       // what the last poll asked for (a switch needs two polls in a row)
   unsigned launches = 0;     // auto mode: per-frame launches so far (every 16th one samples)
+  // while the filter kernel is current: a sampling launch is followed by a copy, a memset and an event record on the launch stream.
+  // Once two polls in a row have confirmed mode 4 only every 8th filter launch samples; a poll that asks for another mode brings
+  // back a sample on each of the next 8 launches.
+  unsigned confirmed4 = 0;       // polls in a row that found mode 4 current and asked for it
+  unsigned every_left = 0;       // filter launches that still sample each time
+  unsigned filter_launches = 0;  // filter launches in the steady state (every 8th one samples)
   DevPtr<unsigned> d_stat;   // device: {record slots sampled, modes live, records needed after the summaries}
   // pinned copies of the counters, a ring of kStatSlots posts (one per sampling launch, each with its event): a host that runs far
   // ahead of the device still finds the most recent sample that has COMPLETED when it looks
@@ -62,8 +70,15 @@ void mog2_stat_read(Mog2State& st) {
   static const bool debug = getenv("BGS_DEBUG_STAT") != nullptr;
   if (debug)
     fprintf(stderr, "[bgs] mog2 auto: %u record slots sampled, %.3f live, %.3f needed after the summaries -> mode %d (now %d)\n", total, lf, nf, want, st.sparse_now);
+  const bool confirms = want == 4 && st.sparse_now == 4;  // (the poll that switches to mode 4 does not count)
   if (want != st.sparse_now && (clear || want == st.sparse_want)) st.sparse_now = want;
   st.sparse_want = want;
+  if (confirms) {
+    st.confirmed4++;
+  } else {
+    st.confirmed4 = 0;
+    st.every_left = 8;
+  }
 }
 void mog2_stat_post(Mog2State& st, hipStream_t s) {
   const int i = (int)(st.stat_seq % Mog2State::kStatSlots);  // the oldest slot is reused (its event re-recorded) if nobody read it
@@ -84,22 +99,36 @@ int launch_mog2(bgs_engine* e, bgs::Mog2Args& a, hipStream_t s, bool timed = tru
   const bool autom = timed && e->knob.mog2_sparse == 3;
   if (autom) mog2_stat_read(st);
   int mode = e->knob.mog2_sparse == 3 ? st.sparse_now : e->knob.mog2_sparse;
-  if (mode >= 4 && (a.shadow || a.want_bg)) mode = 2;  // shadow test and background image read every mode's mean: nothing to rule out
+  const bool every_mean = a.shadow || a.want_bg;  // shadow test and background image read every mode's mean: nothing to rule out,
+  if (mode >= 4 && every_mean) mode = 2;          // and the filter kernel is built without them (kernel_mog2.h, FEAT)
   // auto mode: the filter kernel's sampled workgroups count what each way of loading would read; when another kernel is current,
-  // every 16th launch (every 4th of the first 64) goes through the filter kernel anyway so that the choice keeps following the scene
+  // every 16th launch (every 4th of the first 64) goes through the filter kernel anyway so that the choice keeps following the scene.
+  // A launch that reads every mean samples in the count kernel instead, which posts the same three numbers the filter kernel would
+  // with nothing ruled out.
+  bool sample = false;
   if (autom && mode != 4) {
     const unsigned n = st.launches++;
-    if ((n & (n < 64 ? 3u : 15u)) == 0) mode = 4;
+    if ((n & (n < 64 ? 3u : 15u)) == 0) sample = true, mode = every_mean ? 2 : 4;
+  } else if (autom) {
+    // the filter kernel is current: every launch samples until two polls in a row have confirmed it, then every 8th
+    if (st.every_left > 0 || st.confirmed4 < 2) {
+      sample = true;
+      if (st.every_left > 0) st.every_left--;
+    } else {
+      sample = (st.filter_launches++ & 7u) == 0;
+    }
   }
+  if (mode >= 4 && every_mean) return fail(BGS_ERR_INVALID, "MOG2: the filter kernel cannot deliver the shadow test or the background image");
   a.sparse = mode;
-  a.stat = (autom && mode == 4) ? st.d_stat.p : nullptr;
+  a.stat = sample ? st.d_stat.p : nullptr;
   if (a.packed && a.npix % 64) return fail(BGS_ERR_UNSUPPORTED, "packed mask needs pixels %% 64 == 0");
   Timed t(e, s, "mog2_update_kernel", timed);
   const dim3 grid(blocks_for(a.npix)), block(bgs::kBlock);  // one pixel per lane (round 2's 1 / 2 / 4 comparison: equal or better everywhere)
   unsigned every = 1;  // sample about 256 workgroups per launch whatever the grid: enough to decide, few enough atomics not to show
   while (grid.x / every > 256) every <<= 1;
   a.stat_mask = every - 1;
-  // (occupancy study, DESIGN.md 6.1: 2 / 3 / 4 / 5 waves per SIMD 2.15 / 1.50 / 1.22 / 1.09 ms - profiles/r04_mog2_occupancy_ab.txt)
+  // (occupancy, DESIGN.md 6.1: 2 / 3 / 4 / 5 waves per SIMD 2.15 / 1.50 / 1.22 / 1.09 ms - profiles/r04_mog2_occupancy_ab.txt; the
+  // 60-VGPR filter kernel at 5 / 6 / 7 / 8 waves: 6 is fastest by about 1 %, which is what it is held to - profiles/mog2_stream_ab.txt)
   if (mode >= 4)
     hipLaunchKernelGGL((bgs::mog2_update_kernel<bgs::kMog2Filter>), grid, block, 0, s, a);
   else if (mode >= 2)

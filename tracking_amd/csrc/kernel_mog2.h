@@ -47,7 +47,11 @@
 //   model pixels (a launch that begins at a later stream of a geometry with rows * cols % 64 != 0) may run into the next tile: its lanes
 //   behind the boundary add the distance to that tile to their offset.
 // Instruction budget (the filter kernel on the benchmark input sits under the HBM roof AND close to the vector-issue roof, DESIGN.md
-//   §6.1): 390 vector and 268 scalar instructions per wave (before the wave-relative addresses, s_min and the one-record form: 503 / 303).
+//   §6.1): 391 vector and 246 scalar instructions per wave (before the wave-relative addresses, s_min and the one-record form: 503 / 303).
+// Register budget of the filter kernel: 60 VGPRs, no scratch (it was 89: five waves per SIMD).  Its instantiation is built without the
+//   shadow test and the background image (launches that deliver them go to the count kernel, launch_mog2), and a wave in which some
+//   lane needs several records streams them instead of holding five float4 per lane (mog2_stream).  It would fit 8 waves per SIMD and
+//   is held to 6, which measured fastest (mog2_update_kernel<kMog2Filter> below; the gain over 5 waves is about 1 %).
 // No LDS: the op is pointwise and HBM-bound.
 #pragma once
 #include "bgs_device.h"
@@ -210,21 +214,24 @@ __device__ __forceinline__ bool mog2_reject(uint32_t word, uint32_t pixq, uint32
 
 // One pixel's model in registers.  Weights and slot ids in rank order, as MOG2Invoker sees its array.  The records {var, mean0,
 // mean1, mean2} in one of three orders (template parameter ORD of what follows):
-//   kMog2Compact  rc[j] is the record of slot kj[j] for j < cnt, wherever the loads put it (filter kernel);
+//   kMog2Stream   NO record is held (filter kernel, a wave in which some lane needs more than one): the records went through two
+//                 registers' worth of float4 as they landed and left the three bit masks cm / bgm / mm behind (mog2_stream); the
+//                 matched record is read again from its slot, a line the wave has just loaded;
 //   kMog2BySlot   rc[j] is the record of slot j (eager and count per-frame kernels): a mode's record is fetched when its turn in
 //                 the scan comes (a select chain), the records themselves never move;
 //   kMog2Ranked   rc[r] is the record of the mode at rank r and takes part in the bubble like the reference's array (clip kernels:
 //                 gathered once per launch, then T frames index it statically);
-//   kMog2One      kMog2Compact for a wave none of whose lanes holds more than one record: rc[0] of slot kj[0] when cnt == 1; rc[1..4]
-//                 and kj[1..4] are never written and never read (the filter kernel on well-separated modes: every wave of the benchmark).
-enum { kMog2Compact = 0, kMog2BySlot = 1, kMog2Ranked = 2, kMog2One = 3 };
+//   kMog2One      a wave none of whose lanes needs more than one record: rc[0] of slot k0 when cnt == 1; rc[1..4] are never
+//                 written and never read (the filter kernel on well-separated modes: every wave of the benchmark).
+enum { kMog2Stream = 0, kMog2BySlot = 1, kMog2Ranked = 2, kMog2One = 3 };
 struct Mog2Px {
   float w[kMog2K];
   int sl[kMog2K];  // slot + 1 of the mode at rank r (0: rank unused)
 };
 struct Mog2Recs {
   float4 rc[kMog2K];
-  int kj[kMog2K], cnt;
+  int k0, cnt;           // filter kernel: the first needed slot, the number of needed records
+  unsigned cm, bgm, mm;  // kMog2Stream: bit (slot + 1) = the record was needed / dist2 < Tb var / dist2 < Tg var
 };
 
 template <int ORD>
@@ -239,14 +246,14 @@ __device__ __forceinline__ void mog2_swap(Mog2Px& s, Mog2Recs& R, int i, int j) 
   }
 }
 
-// the record of the mode with slot code `code` (slot + 1), records held in order ORD (by slot: a compare against constants)
+// the record of the mode with slot code `code` (slot + 1), records held by slot: a compare against constants
 template <int ORD>
 __device__ __forceinline__ float4 mog2_pick(const Mog2Recs& R, int code) {
-  static_assert(ORD != kMog2Ranked, "ranked records are indexed by rank");
+  static_assert(ORD == kMog2BySlot, "ranked records are indexed by rank; the filter kernel holds one record or none");
   float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-  for (int j = 0; j < (ORD == kMog2One ? 1 : kMog2K); ++j) {
-    const bool here = ORD == kMog2BySlot ? (code == j + 1) : (j < R.cnt && code == R.kj[j] + 1);
+  for (int j = 0; j < kMog2K; ++j) {
+    const bool here = code == j + 1;
     const float4 c = R.rc[j];  // selects of VALUES, component by component: `if (here) v = R.rc[j]` became a select of addresses + a load, and the whole struct went to scratch
     v.x = here ? c.x : v.x, v.y = here ? c.y : v.y, v.z = here ? c.z : v.z, v.w = here ? c.w : v.w;
   }
@@ -421,15 +428,19 @@ __device__ __forceinline__ int mog2_pixel(Mog2Px& s, Mog2Recs& R, int& nmodes_io
 // Same statements on the same operands for every float, in the same order wherever order matters (the weight sum).  A record behind
 // the matched one in rank order is compared here although the reference never looks at it: a comparison has no side effect.
 // `wave_cand`: wave-uniform upper bound of R.cnt (the candidate loop's trip count).
+// ORD == kMog2Stream (filter kernel, several records): step 1 has happened while the records landed (mog2_stream: R.cm / R.bgm / R.mm),
+// and step 3 reads the matched record again from its slot `mp.rec_of(hit - 1)`.
+// FEAT: the shadow test is compiled in (it reads every mode's mean: the filter kernel, which never runs it, is built without).
 // ORD == kMog2One (no lane of the wave holds more than one record: every wave of the benchmark input): the three bit masks shrink to
 // three flags of the one record, and the rank loop's look-up to "is this rank's slot that record's".
 // The bubble is straight-line code (selects): as nested per-lane branches each of its four steps cost an exec-mask round trip, and
 // the branch form kept more registers live.  The rank scan stays branched: written as selects it costs the filter kernel 97 VGPRs
 // (4 waves per SIMD instead of 5, measured 7 % slower), and as selects in the kMog2One form only it measured equal to the branches.
-template <int ORD>
-__device__ __forceinline__ int mog2_pixel_lockstep(Mog2Px& s, const Mog2Recs& R, const int wave_cand, int& nmodes_io, float x0, float x1, float x2,
-                                                   const Mog2Args& a, int& hit, float4& out, const float alphaT, const float alpha1, const float prune) {
-  static_assert(ORD != kMog2Ranked, "records by slot, compacted, or the single one");
+template <int ORD, bool FEAT>
+__device__ __forceinline__ int mog2_pixel_lockstep(Mog2Px& s, const Mog2Recs& R, const Mog2Lane& mp, const int wave_cand, int& nmodes_io, float x0, float x1,
+                                                   float x2, const Mog2Args& a, int& hit, float4& out, const float alphaT, const float alpha1, const float prune) {
+  static_assert(ORD != kMog2Ranked, "records by slot, streamed, or the single one");
+  static_assert(!FEAT || ORD == kMog2BySlot, "the shadow test needs every record in registers");
   bool background = false, fitsPDF = false;
   int nmodes = nmodes_io;
   const int nNewModes = nmodes;
@@ -443,8 +454,10 @@ __device__ __forceinline__ int mog2_pixel_lockstep(Mog2Px& s, const Mog2Recs& R,
     const float4 v = R.rc[0];
     const float d0 = v.y - x0, d1 = v.z - x1, d2 = v.w - x2;
     const float dist2 = d0 * d0 + d1 * d1 + d2 * d2;
-    c1 = R.cnt > 0, k1 = R.kj[0] + 1;
+    c1 = R.cnt > 0, k1 = R.k0 + 1;
     b1 = dist2 < a.Tb * v.x, m1 = dist2 < a.Tg * v.x;
+  } else if constexpr (ORD == kMog2Stream) {
+    cm = R.cm, bgm = R.bgm, mm = R.mm;
   } else {
 #pragma unroll
     for (int j = 0; j < kMog2K; ++j) {
@@ -452,7 +465,7 @@ __device__ __forceinline__ int mog2_pixel_lockstep(Mog2Px& s, const Mog2Recs& R,
         const float4 v = R.rc[j];
         const float d0 = v.y - x0, d1 = v.z - x1, d2 = v.w - x2;
         const float dist2 = d0 * d0 + d1 * d1 + d2 * d2;
-        const int code = ORD == kMog2BySlot ? j + 1 : R.kj[j] + 1;
+        const int code = j + 1;
         const bool is = j < R.cnt;
         cm |= (unsigned)is << code;
         bgm |= (unsigned)(is && dist2 < a.Tb * v.x) << code;
@@ -485,7 +498,13 @@ __device__ __forceinline__ int mog2_pixel_lockstep(Mog2Px& s, const Mog2Recs& R,
     }
   }
   if (fitsPDF) {
-    const float4 v = (ORD == kMog2One || wave_cand == 1) ? R.rc[0] : mog2_pick<ORD>(R, hit);  // (wave-uniform choice; one candidate: it is the match)
+    float4 v;
+    if constexpr (ORD == kMog2Stream)
+      v = *mp.rec_of((uint32_t)(hit - 1));  // hit is 1 .. 5 here: a slot of this pixel, inside its tile
+    else if constexpr (ORD == kMog2One)
+      v = R.rc[0];  // one candidate: it is the match
+    else
+      v = wave_cand == 1 ? R.rc[0] : mog2_pick<ORD>(R, hit);  // (wave-uniform choice)
     const float var = v.x;
     const float d0 = v.y - x0, d1 = v.z - x1, d2 = v.w - x2;
     const float dist2 = d0 * d0 + d1 * d1 + d2 * d2;
@@ -540,8 +559,10 @@ __device__ __forceinline__ int mog2_pixel_lockstep(Mog2Px& s, const Mog2Recs& R,
   }
   nmodes_io = nmodes;
   if (background) return 0;
-  if (a.shadow) {
-    if (mog2_shadow<ORD>(s, R, hit, out, nmodes, x0, x1, x2, a)) return a.shadow_val;
+  if constexpr (FEAT) {
+    if (a.shadow) {
+      if (mog2_shadow<ORD>(s, R, hit, out, nmodes, x0, x1, x2, a)) return a.shadow_val;
+    }
   }
   return 255;
 }
@@ -580,6 +601,64 @@ __device__ __forceinline__ void mog2_group_or(unsigned v, unsigned& or2, unsigne
   or16 = v;
 }
 
+// The filter kernel's multi-record path: a wave in which some lane needs more than one record.  The records are STREAMED, not held:
+// a wave-uniform loop over the slots 0 .. 4, in which a lane that needs slot k loads it and any other repeats the load of its first
+// needed slot (the same line, no HBM traffic; unconditional loads in straight-line code, see mog2_body).  The load of slot k + 1 is
+// issued before slot k is consumed, so two records (8 VGPRs) are in flight and five records cost about three round trips.  A landed
+// record gives what mog2_pixel_lockstep's candidate loop computes - dist2 and the two comparisons, as bits (slot + 1) of R.cm /
+// R.bgm / R.mm - and is dropped.  Holding five float4 per lane instead (the compacted form this replaces) cost the whole kernel
+// 26 VGPRs, i.e. 5 waves per SIMD where it now runs 8, although no wave of the benchmark input ever takes this path.
+// While a record is there it also serves its two other readers, both only for a pixel whose summaries were not valid on entry
+// (every live record of such a pixel is needed): sm[k] takes the record's summary (the rebuild at the end of mog2_body then only
+// patches the slot this frame changes), and a sampled workgroup counts in `would` the records that fresh summaries would have left.
+__device__ __forceinline__ void mog2_stream(const Mog2Lane& mp, Mog2Recs& R, const unsigned need, const bool valid_in, const bool sampled, const uint32_t pix,
+                                            const Mog2Args& a, uint32_t (&sm)[kMog2K], int& would) {
+  const float x0 = (float)(pix & 0xffu), x1 = (float)((pix >> 8) & 0xffu), x2 = (float)(pix >> 16);
+  const uint32_t pixq = mog2_pixq(pix), k_first = (uint32_t)R.k0;
+  const bool rebuild = __any(!valid_in);  // wave-uniform: nobody pays for mog2_summary in a wave of valid pixels
+  unsigned cm = 0, bgm = 0, mm = 0;
+  int fresh = 0;
+  float4 cur = *mp.rec_of((need & 1u) ? 0u : k_first);
+#pragma unroll
+  for (int k = 0; k < kMog2K; ++k) {
+    float4 nxt = cur;
+    if (k + 1 < kMog2K) nxt = *mp.rec_of(((need >> (k + 1)) & 1u) ? (uint32_t)(k + 1) : k_first);
+    const bool is = (need >> k) & 1u;
+    const float d0 = cur.y - x0, d1 = cur.z - x1, d2 = cur.w - x2;
+    const float dist2 = d0 * d0 + d1 * d1 + d2 * d2;
+    cm |= (unsigned)is << (k + 1);
+    bgm |= (unsigned)(is && dist2 < a.Tb * cur.x) << (k + 1);
+    mm |= (unsigned)(is && dist2 < a.Tg * cur.x) << (k + 1);
+    if (rebuild) {
+      const uint32_t word = mog2_summary(cur.x, cur.y, cur.z, cur.w);
+      const bool mine = is && !valid_in;
+      sm[k] = mine ? word : sm[k];
+      if (sampled) fresh += (int)(mine && !mog2_reject(word, pixq, a.s_min));
+    }
+    cur = nxt;
+  }
+  R.cm = cm, R.bgm = bgm, R.mm = mm;
+  would = valid_in ? would : fresh;  // (read by sampled workgroups only)
+}
+
+// What a sampled workgroup adds to the three counters of the engine's automatic choice (engine_mog2.h): per pixel 5 record slots, the
+// modes it has (what COUNT loads), the records the summaries leave (`would`: what FILTER loads).  Sums over the wave from the ballots of
+// the three bits of each count.
+__device__ __forceinline__ void mog2_stat_add(const Mog2Args& a, const uint32_t lane, const int nm_in, const int would) {
+  unsigned s_live = 0, s_need = 0;
+#pragma unroll
+  for (int bit = 0; bit < 3; ++bit) {
+    s_live += (unsigned)__popcll(__ballot((nm_in >> bit) & 1)) << bit;
+    s_need += (unsigned)__popcll(__ballot((would >> bit) & 1)) << bit;
+  }
+  const unsigned lanes = (unsigned)__popcll(__ballot(1));
+  if (lane == 0) {
+    atomicAdd(a.stat, lanes * kMog2K);
+    atomicAdd(a.stat + 1, s_live);
+    atomicAdd(a.stat + 2, s_need);
+  }
+}
+
 // T consecutive frames of one pixel per lane (T = 1: the per-frame launch; 2 / 4 / 8: clip launches, bgs_process_clip_device).
 // The model of a pixel is loaded once, updated T times in registers in frame order with exactly the statements of the reference,
 // and what changed is written back once: results are those of T successive single-frame launches, bit for bit, because a pixel's
@@ -606,7 +685,10 @@ template <int MODE, int T>
 __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_stride, const size_t fg_stride, const size_t bg_stride, const size_t bits_stride,
                                           const float* alphaT, const float* alpha1, const float* prune) {
   static_assert(T == 1 || MODE == kMog2Eager, "clip launches load eagerly");
-  constexpr int ORD = MODE == kMog2Filter ? kMog2Compact : T > 1 ? kMog2Ranked : kMog2BySlot;
+  constexpr int ORD = MODE == kMog2Filter ? kMog2Stream : T > 1 ? kMog2Ranked : kMog2BySlot;
+  // The shadow test and the background image read every mode's mean: there is nothing to rule out, and launches that deliver them never
+  // reach the filter kernel (launch_mog2).  Its instantiation is built without them - they kept every record live to the kernel's end.
+  constexpr bool FEAT = MODE != kMog2Filter;
   size_t blk = blockIdx.x;
   if (a.xcd_swizzle) {
     // Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 says which blocks share an XCD and its L2).  Give
@@ -635,7 +717,7 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
   const bool valid_in = (meta_raw >> 15) & 1u;
   const int nm_in = mog2_meta_count(meta_in);
   const bool dense = MODE == kMog2Eager && a.sparse == 0;
-  const bool can_reject = !a.shadow && !a.want_bg;  // the shadow test and the background image read every mode's mean
+  const bool sampled = MODE != kMog2Eager && a.stat && (blockIdx.x & a.stat_mask) == 0;  // wave-uniform: this workgroup counts for the automatic choice
   float wv[kMog2K];
   uint32_t sm[kMog2K];
   Mog2Recs R;
@@ -690,55 +772,32 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
 #pragma unroll
     for (int k = 0; k < kMog2K; ++k) {
       const bool live = k < nm_in;  // (what a rank or slot the pixel does not use holds is never read and, being what memory holds, harmless to write back)
-      const bool r = (live & valid_in & can_reject) & mog2_reject(sm[k], pixq, a.s_min);  // (no short circuit: five branches otherwise)
+      const bool r = (live & valid_in) & mog2_reject(sm[k], pixq, a.s_min);  // (no short circuit: five branches otherwise)
       need |= (unsigned)(live && !r) << k;
     }
-    // the needed slots, compacted: the j-th load of a lane fetches its j-th needed record (a lane with fewer repeats its first)
     R.cnt = __popc(need);
-    const int k_first = need ? __ffs(need) - 1 : 0;
-    R.kj[0] = k_first;
+    // the first needed slot; a lane that needs none loads slot 4 and discards it (any slot of its own tile will do)
+    R.k0 = (int)min((unsigned)__builtin_ctzg(need, 32), (unsigned)(kMog2K - 1));
+    // what a sampled workgroup counts as "records the filter path loads": a pixel whose summaries were not valid has all its records
+    // loaded, and what fresh summaries would have left is counted instead, so that a single filter launch in the middle of another
+    // kernel's run can tell whether filtering would pay
+    int would = R.cnt;
     if (!__any(R.cnt > 1)) {
-      wave_cand = 1;  // from here on this wave holds its records as kMog2One: rc[1..4] and kj[1..4] do not exist
-      R.rc[0] = *mp.rec_of((uint32_t)k_first);
+      wave_cand = 1;  // from here on this wave holds its records as kMog2One: rc[1..4] do not exist
+      R.rc[0] = *mp.rec_of((uint32_t)R.k0);
+      if (sampled && !valid_in) {
+        const float4 c = R.rc[0];
+        would = (int)(R.cnt > 0 && !mog2_reject(mog2_summary(c.x, c.y, c.z, c.w), pixq, a.s_min));
+      }
     } else {
-      unsigned left = need & (need - 1);
-#pragma unroll
-      for (int j = 1; j < kMog2K; ++j) {
-        R.kj[j] = left ? __ffs(left) - 1 : k_first;
-        left &= left - 1;
-      }
-#pragma unroll
-      for (int j = 0; j < kMog2K; ++j) R.rc[j] = *mp.rec_of((uint32_t)R.kj[j]);
+      mog2_stream(mp, R, need, valid_in, sampled, pix[0], a, sm, would);
     }
-    if (a.stat && (blockIdx.x & a.stat_mask) == 0) {
-      // per pixel: 5 record slots, the modes it has (what COUNT loads), the records the summaries leave (what FILTER loads);
-      // sums over the wave from the ballots of the three bits of each count
-      // (a pixel whose summaries were not valid had all its records loaded: what fresh summaries would have left is counted instead,
-      // so that a single filter launch in the middle of another kernel's run can tell whether filtering would pay)
-      int would = R.cnt;
-      if (!valid_in && can_reject) {
-        would = 0;
-#pragma unroll
-        for (int j = 0; j < kMog2K; ++j) {
-          if (j < (wave_cand == 1 ? 1 : kMog2K) && j < R.cnt) {
-            const float4 c = R.rc[j];
-            if (!mog2_reject(mog2_summary(c.x, c.y, c.z, c.w), pixq, a.s_min)) ++would;
-          }
-        }
-      }
-      unsigned s_live = 0, s_need = 0;
-#pragma unroll
-      for (int bit = 0; bit < 3; ++bit) {
-        s_live += (unsigned)__popcll(__ballot((nm_in >> bit) & 1)) << bit;
-        s_need += (unsigned)__popcll(__ballot((would >> bit) & 1)) << bit;
-      }
-      const unsigned lanes = (unsigned)__popcll(__ballot(1));
-      if (lane == 0) {
-        atomicAdd(a.stat, lanes * kMog2K);
-        atomicAdd(a.stat + 1, s_live);
-        atomicAdd(a.stat + 2, s_need);
-      }
-    }
+    if (sampled) mog2_stat_add(a, lane, nm_in, would);
+  }
+  if constexpr (MODE == kMog2Count) {
+    // a launch that delivers the shadow test or the background image cannot go through the filter kernel; when it is its turn to sample
+    // for the automatic choice, the count kernel posts what the filter kernel would have: with nothing ruled out, need = live
+    if (sampled) mog2_stat_add(a, lane, nm_in, nm_in);
   }
   Mog2Px s;
 #pragma unroll
@@ -761,23 +820,22 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
     if constexpr (ORD == kMog2Ranked)
       raw = mog2_pixel<ORD>(s, R, nm, x0, x1, x2, a, hit, out, alphaT[t], alpha1[t], prune[t], 0u);
     else if (one)
-      raw = mog2_pixel_lockstep<kMog2One>(s, R, 1, nm, x0, x1, x2, a, hit, out, alphaT[t], alpha1[t], prune[t]);
+      raw = mog2_pixel_lockstep<kMog2One, false>(s, R, mp, 1, nm, x0, x1, x2, a, hit, out, alphaT[t], alpha1[t], prune[t]);
     else
-      raw = mog2_pixel_lockstep<ORD>(s, R, wave_cand, nm, x0, x1, x2, a, hit, out, alphaT[t], alpha1[t], prune[t]);
+      raw = mog2_pixel_lockstep<ORD, FEAT>(s, R, mp, wave_cand, nm, x0, x1, x2, a, hit, out, alphaT[t], alpha1[t], prune[t]);
     const int m = thr_bin(raw, a.thr, a.enable_thr);
     if (a.fg) (a.fg + pw + (size_t)t * fg_stride)[lane] = (uint8_t)m;
     if (a.packed) {  // npix % 64 == 0: the wave is whole and its 64 mask bits are one word, which is what a ballot returns
       const uint64_t word = __ballot(m != 0);
       if (lane == 0) (a.fg_bits + (pw >> 6) + (size_t)t * bits_stride)[0] = word;
     }
-    if (a.want_bg) {
-      int b0, b1, b2;
-      if (one)
-        mog2_background<kMog2One>(s, R, hit, out, nm, a.TB, b0, b1, b2);
-      else
+    if constexpr (FEAT) {
+      if (a.want_bg) {
+        int b0, b1, b2;
         mog2_background<ORD>(s, R, hit, out, nm, a.TB, b0, b1, b2);
-      uint8_t* o = a.bgimg + pw * 3 + (size_t)t * bg_stride + lane * 3u;
-      o[0] = (uint8_t)b0, o[1] = (uint8_t)b1, o[2] = (uint8_t)b2;
+        uint8_t* o = a.bgimg + pw * 3 + (size_t)t * bg_stride + lane * 3u;
+        o[0] = (uint8_t)b0, o[1] = (uint8_t)b1, o[2] = (uint8_t)b2;
+      }
     }
     dirty |= 1u << hit;
   }
@@ -791,6 +849,8 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
     // Summaries.  The common case costs a select and a few compares: the one record that changed is `out`; its stored summary is
     // kept while it still covers the record (hysteresis: quiet pixels rewrite theirs rarely).  Rewrites and rebuilds (a pixel whose
     // summaries were not valid on entry had all its records loaded for this) take the slot loop - skipped by the whole wave otherwise.
+    // A streamed wave took the summaries of such a pixel's records as they landed (mog2_stream): sm[q] already is what is wanted,
+    // except for the slot this frame changed or created.
     uint32_t old = 0;
 #pragma unroll
     for (int q = 0; q < kMog2K; ++q) old = hit == q + 1 ? sm[q] : old;
@@ -800,8 +860,14 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
       for (int q = 0; q < kMog2K; ++q) {
         const bool changed = hit == q + 1;
         if ((changed && !keep) || (!valid_in && q < nm)) {
-          const float4 v = one ? mog2_pick_now<kMog2One>(R, q + 1, hit, out) : mog2_pick_now<kMog2Compact>(R, q + 1, hit, out);
-          sm[q] = mog2_summary(v.x, v.y, v.z, v.w);
+          if (one) {
+            // an unchanged slot gets here only with summaries that were not valid: every live record was needed then, and in this
+            // form that is at most one - slot 0, in rc[0] (the pixel had one mode and this frame created the second)
+            const float4 c = R.rc[0];
+            sm[q] = mog2_summary(changed ? out.x : c.x, changed ? out.y : c.y, changed ? out.z : c.z, changed ? out.w : c.w);
+          } else {
+            sm[q] = changed ? mog2_summary(out.x, out.y, out.z, out.w) : sm[q];
+          }
           d |= 1u << (11 + q);
         }
       }
@@ -865,6 +931,16 @@ __device__ __forceinline__ void mog2_body(const Mog2Args& a, const size_t frame_
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void mog2_update_kernel(const Mog2Args a) {
   mog2_body<MODE, 1>(a, 0, 0, 0, 0, &a.alphaT, &a.alpha1, &a.prune);
+}
+// The filter kernel fits 8 waves per SIMD (60 VGPRs) and is held to 6: measured against 5, 7 and 8 and against the 89-VGPR kernel it
+// replaces, 6 was the fastest or equal to the fastest in every job, 7 and 8 up to 1 % slower than 6 (profiles/mog2_stream_ab.txt,
+// DESIGN.md §6.1).  A/B builds: make EXTRA=-DBGS_MOG2_FILTER_WAVES=8.
+#ifndef BGS_MOG2_FILTER_WAVES
+#define BGS_MOG2_FILTER_WAVES 6
+#endif
+template <>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, BGS_MOG2_FILTER_WAVES))) void mog2_update_kernel<kMog2Filter>(const Mog2Args a) {
+  mog2_body<kMog2Filter, 1>(a, 0, 0, 0, 0, &a.alphaT, &a.alpha1, &a.prune);
 }
 
 template <int T>
