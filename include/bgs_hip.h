@@ -87,7 +87,10 @@ typedef enum bgs_algo {
   /* package_bgs/dp's PCA background (3-channel frames; output = the high-threshold mask, no background image).  Its parameters are
    * bgs_eigen_params, not bgs_params. */
   BGS_DP_EIGENBACKGROUND = 34,    /* DPEigenbackgroundBGS::process (USTC_BGS type 15) package_bgs/dp/DPEigenbackgroundBGS.cpp:29-82 */
-  BGS_ALGO_LAST = 35              /* one past the last id; moves with every class added */
+  /* package_bgs/db's IMBS (3-channel frames; output = the four-label mask 0 / 80 shadow / 180 persistence / 255 foreground and the BGR
+   * background of the last model build).  Its parameters are bgs_imbs_params, not bgs_params. */
+  BGS_IMBS = 35,                  /* IndependentMultimodalBGS::process (USTC_BGS type 33) package_bgs/db/IndependentMultimodalBGS.cpp:13-36 */
+  BGS_ALGO_LAST = 36              /* one past the last id; moves with every class added */
 } bgs_algo;
 
 /* "id is an algorithm": the one range check (bgs_default_params, bgs_create, bgs_node_create) */
@@ -306,6 +309,36 @@ typedef struct bgs_eigen_params {
 /* Largest history_size the Eigenbackground kernels are built for. */
 #define BGS_EIGEN_MAX_HISTORY 32
 
+/* IndependentMultimodalBGS (package_bgs/db/imbs.hpp:43-56): the full constructor's arguments, each in the type of the member it
+ * lands in (samplingPeriod and persistencePeriod are unsigned int members, alpha and beta float, tau_s and tau_h uchar).  A struct
+ * of its own, as bgs_eigen_params.  bgs_create gives an IMBS engine these defaults whatever bgs_params it was handed.  The model
+ * sizes its arrays at its first frame: the values are taken when the geometry is set, and a bgs_set_imbs_params after that succeeds
+ * and leaves the values in force unchanged (bgs_get_imbs_params returns what is in force).
+ * Refused with BGS_ERR_UNSUPPORTED, the class named: fps <= 0 or not finite (0 means wall-clock time), minBinHeight 0, numSamples
+ * outside 2..BGS_IMBS_MAX_SAMPLES, minBinHeight above numSamples (maxBgBins = numSamples / minBinHeight would be 0), tau_s /
+ * tau_h outside 0..255, non-finite alpha / beta / minArea, 1-channel frames, the class inside a bgs_group.
+ * Until the first model is built (bgModel[0].isValid[0]) the reference hands out a putText banner; the engine hands out what that
+ * is with putText a no-op, an all-zero mask and background, both reported valid. */
+typedef struct bgs_imbs_params {
+  uint32_t struct_size;           /* sizeof(bgs_imbs_params) = 64 */
+  uint32_t fgThreshold;           /* 15 */
+  double fps;                     /* 10, as the wrapper passes: timestamp += 1000./fps per frame */
+  uint32_t associationThreshold;  /* 5 */
+  uint32_t samplingPeriod;        /* 500 ms */
+  uint32_t minBinHeight;          /* 2 */
+  uint32_t numSamples;            /* 30 */
+  float alpha;                    /* 0.65 */
+  float beta;                     /* 1.15 */
+  int32_t tau_s;                  /* 60, 0..255 */
+  int32_t tau_h;                  /* 40, 0..255 */
+  double minArea;                 /* 30 */
+  uint32_t persistencePeriod;     /* 10000 ms */
+  int32_t morphologicalFiltering; /* 0 */
+} bgs_imbs_params;
+
+/* Largest numSamples the IMBS kernels are built for (bin heights and counters are packed into 6 bits). */
+#define BGS_IMBS_MAX_SAMPLES 63
+
 /* Largest dp_history_size the PratiMediod kernel is built for (every dist entry then fits in 16 bits: 64 x 255 < 65536). */
 #define BGS_PRATI_MAX_HISTORY 64
 
@@ -348,6 +381,14 @@ int bgs_get_eigen_params(const bgs_engine* e, bgs_eigen_params* p);
 /* Every refusal of the class without an engine and without a device: parameters (p == NULL: the defaults) and, where rows > 0, the
  * frame geometry.  The message names the class. */
 int bgs_eigen_check(const bgs_eigen_params* p, int rows, int cols, int channels);
+
+/* IndependentMultimodalBGS's own parameters (bgs_imbs_params above); BGS_ERR_INVALID for an engine of any other class. */
+int bgs_imbs_default_params(bgs_imbs_params* p);
+int bgs_set_imbs_params(bgs_engine* e, const bgs_imbs_params* p);
+int bgs_get_imbs_params(const bgs_engine* e, bgs_imbs_params* p);
+/* Every refusal of the class without an engine and without a device: parameters (p == NULL: the defaults) and, where rows > 0, the
+ * frame geometry.  The message names the class. */
+int bgs_imbs_check(const bgs_imbs_params* p, int rows, int cols, int channels);
 
 /* Engine options.
  *   BGS_OPT_BORROW_FRAMES  device path of the history-keeping classes (FrameDifference, WeightedMovingMean/Variance):
@@ -567,6 +608,10 @@ const char* bgs_last_error(void);
  * the stream's frame counter; once the model is built (after frame H): "avg" f32 [n][3], "eigenvalues" f64 [H] of the centred Gram
  * matrix, descending, "eigenvectors" f32 [M][n][3], "coeff" f32 [M] = the last frame's projection, "result" f32 [n][3] = that
  * frame's reconstruction (not stored per frame: recomputed on request from avg, coeff and the eigenvectors by a launch of its own).
+ * IMBS (N = numSamples, M = maxBgBins = numSamples / minBinHeight), unpacked: "bins" u8 [n][N][5] = binValues B, G, R, binHeights, isFg;
+ * "model" u8 [n][M][6] = values B, G, R, isValid, isFg, counter; "persistence" u32 [n]; "control" f64 [10] = timestamp,
+ * prev_timestamp, prev_bg_frame_time, bg_frame_counter, numSamples, samplingPeriod, bg_reset, sudden_change, maxBgBins,
+ * bgModel[0].isValid[0].  Slots the reference never wrote read 0.
  * lb/ models, all f64 in the reference's memory order, colour fields in the byte order of the input pixel (B, G, R):
  * SimpleGaussian / FuzzyGaussian "mu", "var" f64 [n][3]; MixtureOfGaussians "w" f64 [n][3], "mu", "var" f64 [n][3][3] (pixel, slot,
  * colour), "sortkey" f64 [n][3], "k" int32 [n] (slots >= k read 0); AdaptiveSOM / FuzzyAdaptiveSOM "som" f64 [n][3][3][3] (pixel,

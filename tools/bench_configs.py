@@ -16,6 +16,8 @@ Not the driver's bench line (bench.py is); the numbers go to DESIGN.md §6.
              S_surv, 8 x 1080p: ms per step and ms per frame at clip T = 8
   --only eigen: DPEigenbackgroundBGS (package_bgs/dp) beside DPGrimsonGMM timed in the same process, reference defaults (H = 20, M = 10),
              on S_surv, 8 x 1080p and 1 x 1080p: ms per detecting step, the one-off model build at frame H, this box's copy rate
+  --only imbs: IndependentMultimodalBGS (package_bgs/db) at the wrapper's defaults (numSamples 30) on S_surv, 8 x 1080p: the detect-only
+             step, the sampling step and the build step apart, what the launches cost on empty planes, the numpy restatement beside
 usage: bench_configs.py [--streams S] [--swizzle 0|1]"""
 import argparse
 import os
@@ -971,6 +973,80 @@ def run_eigen(S=8, rows=1080, cols=1920, steps=30):
     g.close()
 
 
+def run_imbs(S=8, rows=1080, cols=1920):
+    """IndependentMultimodalBGS at the wrapper's defaults (fps 10, numSamples 30, a sample every 5th frame, the first model at frame
+    145, the next ones every 145 frames: a build does not move prev_bg_frame_time) on S_surv, mask and background out.  Every step enqueues the same launches; what differs is what the sample kernel finds in
+    its stream's control block, so the three kinds of step are timed apart, each call between two events on the launch stream:
+    detect-only (no createBg), sampling (createBg(k), k < 29) and build (createBg(29)), each before and after the first model; which
+    kind a step was is read from the stream's control block on the device (bg_frame_counter before and after the call).
+    Bytes per pixel are the layout's: 4 per bin and model slot, 12 for the persistence map, bgSample and bgImage, 21 of per-frame
+    scratch (labels, planes, two labellings, areas).  A learning step costs every launch on all-zero planes with no model read; the
+    kernel-timing window is the detect kernel alone; the split by kernel is a kernel trace's to give.  The CPU
+    figure is the numpy restatement (tests/imbs_numpy.py, the quad form of the area filter) on a 120 x 160 crop, per pixel."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import imbs_numpy as im
+    dev = torch.device("cuda", 0)
+    copy = capi.calibrate_copy(0, 2 << 30, 0)
+    px = S * rows * cols
+    e = Engine(capi.IMBS, n_streams=S)
+    e.set_geometry(rows, cols, 3)
+    q = e.get_imbs_params()
+    N, M = q.numSamples, q.numSamples // q.minBinHeight
+    pool = synth.SurvStreams(S, rows, cols, seed0=4321, device=dev).pool(8)
+    fg = torch.empty((S, rows, cols), dtype=torch.uint8, device=dev)
+    bg = torch.empty((S, rows, cols, 3), dtype=torch.uint8, device=dev)
+    every = int(round(q.samplingPeriod / (1000. / q.fps)))
+    total = 3 * every * (N - 1) + every  # the learning phase and two more models: a model takes every (N - 1) frames
+    kinds = {}
+    before = e.get_state("control", (10,), np.float64)
+    for t in range(total):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        e.process_batch_device(pool[t % 8], fg, bg, None)
+        b.record()
+        torch.cuda.synchronize()
+        # what the step did, from the device's own control block (stream 0; the streams are in lock-step): bg_frame_counter went up
+        # by one = createBg(k) on a fresh sample, fell to 0 = the build createBg(numSamples - 1), stayed = no createBg
+        after = e.get_state("control", (10,), np.float64)
+        phase = "detecting" if before[9] else "learning"  # bgModel[0].isValid[0] when the step began
+        kind = "sample" if after[3] == before[3] + 1 else "build" if before[3] == before[4] - 1 and after[3] == 0 else "detect-only"
+        assert kind != "detect-only" or after[3] == before[3]
+        if t > 2:
+            kinds.setdefault((phase, kind), []).append(a.elapsed_time(b))
+        before = after
+    ctl = e.get_state("control", (10,), np.float64)
+    ratio = float((fg == 255).float().mean())
+    state_bpp = 4 * N + 4 * M + 12
+    print("IndependentMultimodalBGS numSamples=%d maxBgBins=%d %dx%d x%d streams, %d steps; state %d B/px + 21 B/px scratch; copy %.0f GB/s; control after the last step %s; 255 ratio %.3f"
+          % (N, M, cols, rows, S, total, state_bpp, copy, ctl.tolist(), ratio))
+    for key in sorted(kinds):
+        v = np.array(kinds[key])
+        print("  %-10s %-12s %4d steps: median %.3f ms (min %.3f, max %.3f) = %.3f ms/stream -> %7.1f Mpix/s" % (key[0], key[1], len(v), np.median(v), v.min(), v.max(), np.median(v) / S, px / np.median(v) / 1e3))
+    det = float(np.median(kinds[("detecting", "detect-only")]))
+    # what a detect-only step must move: the frame, model slots up to the first invalid one (at least one), the persistence map, the
+    # label and the 255-plane, then the filter's scratch and the images out
+    print("  detect-only against the copy rate: %d B/px of state + scratch if every slot were read = %.0f GB/s = %.2f of copy" % (state_bpp + 21, (state_bpp + 21) * px / (det * 1e-3) / 1e9, (state_bpp + 21) * px / (det * 1e-3) / 1e9 / copy))
+    e.enable_kernel_timing(True)
+    for t in range(10):
+        e.process_batch_device(pool[t % 8], fg, bg, None)
+    torch.cuda.synchronize()
+    ms, n, kname = e.kernel_timing()
+    lrn = float(np.median(kinds[("learning", "detect-only")]))
+    builds = sorted(kinds.get(("learning", "build"), []) + kinds.get(("detecting", "build"), []))
+    print("  every build step: %s ms" % ", ".join("%.3f" % v for v in builds))
+    print("  %s alone: %.3f ms (mean of %d); a learning step (every launch on all-zero planes, no model read): %.3f ms; a detecting step: %.3f ms" % (kname, ms, n, lrn, det))
+    e.close()
+    small = synth.SurvStreams(1, 120, 160, seed0=4321, device=dev).pool(8).cpu().numpy()[:, 0]
+    m = im.Model(dict(im.DEFAULTS, **im.FAST), 120, 160, area_filter=im.area_filter_quads)
+    for t in range(8):
+        m.apply(small[t % 8])
+    t0 = time.perf_counter()
+    for t in range(4):
+        m.apply(small[t % 8])
+    cpu = (time.perf_counter() - t0) / 4
+    print("  numpy restatement (numSamples 6, quad form) on 120 x 160: %.1f ms per frame = %.2f us/pixel; the engine's detecting step: %.5f us/pixel" % (cpu * 1e3, cpu * 1e6 / (120 * 160), det * 1e3 / px))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=8)
@@ -1001,6 +1077,9 @@ def main():
         return
     if args.only == "eigen":
         run_eigen(S)
+        return
+    if args.only == "imbs":
+        run_imbs(S)
         return
     if args.only in ("fuzzy_choquet", "fuzzy_sugeno"):
         run_fuzzy(S, steps=5, only="FuzzyChoquetIntegral" if args.only == "fuzzy_choquet" else "FuzzySugenoIntegral", calibrate=False)

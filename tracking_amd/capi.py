@@ -21,14 +21,17 @@ VUMETER = 27  # id 26 is a permanent hole (BGS_ALGO_END is frozen there); BGS_AL
 FUZZY_SUGENO, FUZZY_CHOQUET = 29, 30  # package_bgs/tb fuzzy integrals; their parameters are BgsFuzzyParams, not BgsParams
 T2FGMM_UM, T2FGMM_UV = 32, 33  # package_bgs/tb type-2 fuzzy GMMs (id 31 is the third hole); their parameters are BgsT2fParams
 DP_EIGENBACKGROUND = 34  # package_bgs/dp PCA background; its parameters are BgsEigenParams
-ALGO_LAST = 35  # one past the last id
+IMBS = 35  # package_bgs/db IndependentMultimodalBGS; its parameters are BgsImbsParams
+ALGO_LAST = 36  # one past the last id
 ALGO_LIMIT = 28  # frozen, and id 28 is the second permanent hole
 FUZZY_SUGENO, FUZZY_CHOQUET = 29, 30  # package_bgs/tb fuzzy integrals; their parameters are BgsFuzzyParams, not BgsParams
 T2FGMM_UM, T2FGMM_UV = 32, 33  # package_bgs/tb type-2 fuzzy GMMs (id 31 is the third hole); their parameters are BgsT2fParams
 DP_EIGENBACKGROUND = 34  # package_bgs/dp PCA background; its parameters are BgsEigenParams
-ALGO_LAST = 35  # one past the last id
+IMBS = 35  # package_bgs/db IndependentMultimodalBGS; its parameters are BgsImbsParams
+ALGO_LAST = 36  # one past the last id
 PRATI_MAX_HISTORY = 64  # BGS_PRATI_MAX_HISTORY
 EIGEN_MAX_HISTORY = 32  # BGS_EIGEN_MAX_HISTORY
+IMBS_MAX_SAMPLES = 63  # BGS_IMBS_MAX_SAMPLES
 FG_VALID, BG_VALID = 1, 2
 OPT_BORROW_FRAMES, OPT_MOG2_PIXELS_PER_LANE, OPT_MOG2_TILED, OPT_XCD_SWIZZLE, OPT_PLACEMENT_PROBE, OPT_MOG2_SPARSE, OPT_CLIP_FUSE, OPT_HOST_REGISTER, OPT_MODEL_CHUNK_MB, OPT_MODEL_CHUNK_MIN_MB = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 
@@ -126,6 +129,13 @@ class BgsEigenParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("threshold", C.c_int32), ("history_size", C.c_int32), ("embedded_dim", C.c_int32)]
 
 
+class BgsImbsParams(C.Structure):
+    """struct bgs_imbs_params, field for field (IndependentMultimodalBGS)."""
+    _fields_ = [("struct_size", C.c_uint32), ("fgThreshold", C.c_uint32), ("fps", C.c_double), ("associationThreshold", C.c_uint32), ("samplingPeriod", C.c_uint32),
+                ("minBinHeight", C.c_uint32), ("numSamples", C.c_uint32), ("alpha", C.c_float), ("beta", C.c_float), ("tau_s", C.c_int32), ("tau_h", C.c_int32),
+                ("minArea", C.c_double), ("persistencePeriod", C.c_uint32), ("morphologicalFiltering", C.c_int32)]
+
+
 class BgsError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("libbgs_hip error %d: %s" % (code, text))
@@ -151,6 +161,10 @@ SYMBOLS = [
     ("bgs_set_eigen_params", C.c_int, [_P, C.POINTER(BgsEigenParams)]),
     ("bgs_get_eigen_params", C.c_int, [_P, C.POINTER(BgsEigenParams)]),
     ("bgs_eigen_check", C.c_int, [C.POINTER(BgsEigenParams), C.c_int, C.c_int, C.c_int]),
+    ("bgs_imbs_default_params", C.c_int, [C.POINTER(BgsImbsParams)]),
+    ("bgs_set_imbs_params", C.c_int, [_P, C.POINTER(BgsImbsParams)]),
+    ("bgs_get_imbs_params", C.c_int, [_P, C.POINTER(BgsImbsParams)]),
+    ("bgs_imbs_check", C.c_int, [C.POINTER(BgsImbsParams), C.c_int, C.c_int, C.c_int]),
     ("bgs_set_option", C.c_int, [_P, C.c_int, C.c_int64]),
     ("bgs_set_geometry", C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     ("bgs_process", C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_uint32)]),
@@ -279,6 +293,14 @@ def t2f_default_params(**kw):
 def eigen_default_params(**kw):
     p = BgsEigenParams()
     check(lib().bgs_eigen_default_params(C.byref(p)))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def imbs_default_params(**kw):
+    p = BgsImbsParams()
+    check(lib().bgs_imbs_default_params(C.byref(p)))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

@@ -38,6 +38,7 @@
 #include "kernel_fuzzy.h"
 #include "kernel_t2f.h"
 #include "kernel_eigen.h"
+#include "kernel_imbs.h"
 #include "kernel_cc.h"
 #include "kernel_dp.h"
 #include "kernel_mog1.h"
@@ -122,7 +123,7 @@ struct VmmRange {
 //  - the frame history ring: process_clip_run, bgs_process and bgs_submit read and write it themselves, so it is a service of the
 //    generic code that the history classes use, not their private state;
 //  - `counter`: the families that have a learning phase counted in frames share it with that one meaning, and bgs_reset_stream clears it;
-//  - p, fz, t2f and eig: all may be set before the geometry is known, i.e. before there is a state;
+//  - p, fz, t2f, eig and imbs: all may be set before the geometry is known, i.e. before there is a state;
 //  - the knobs, which bgs_create (environment) and bgs_set_option set before allocation.
 struct bgs_engine {
   bgs_algo algo;
@@ -132,6 +133,7 @@ struct bgs_engine {
   bgs_fuzzy_params fz{};  // bgs_set_fuzzy_params
   bgs_t2f_params t2f{};   // bgs_set_t2f_params; frozen once the geometry is set
   bgs_eigen_params eig{}; // bgs_set_eigen_params; frozen once the geometry is set
+  bgs_imbs_params imbs{}; // bgs_set_imbs_params; frozen once the geometry is set
   int device = 0;
   int n_cu = 256;  // compute units of `device` (allocate): the persistent kernels size their grids by it
   int S = 1;
@@ -434,6 +436,7 @@ int model_allocate(bgs_engine* e, DevPtr<T>& out, size_t bytes) { return model_a
 #include "engine_fuzzy.h"
 #include "engine_t2f.h"
 #include "engine_eigen.h"
+#include "engine_imbs.h"
 
 // an id that BGS_ALGO_KNOWN accepts but no engine class stands behind (BGS_LBSP_DESC is a stand-alone entry point): refused when the geometry is set
 constexpr Family kUnbuilt = [] {
@@ -476,6 +479,7 @@ const Family* family_of(bgs_algo algo) {
     case BGS_T2FGMM_UM:
     case BGS_T2FGMM_UV: return &kT2f;
     case BGS_DP_EIGENBACKGROUND: return &kEigen;
+    case BGS_IMBS: return &kImbs;
     case BGS_LBSP_DESC:
     case BGS_ALGO_END:
     case BGS_ALGO_LIMIT:
@@ -952,6 +956,7 @@ int bgs_create(bgs_algo algo, const bgs_params* params, int hip_device, int n_st
   e->counter.assign(n_streams, 0);
   t2f_defaults(&e->t2f);
   eig_defaults(&e->eig);
+  imbs_defaults(&e->imbs);
   fz_defaults(&e->fz);  // a fuzzy engine starts from the constructor's values whatever bgs_params it was handed (bgs_set_fuzzy_params)
   if (const char* env = getenv("BGS_KDE_TRIPS")) e->knob.kde_count_trips = atoi(env) != 0;
   if (const char* env = getenv("BGS_MOG2_COMPLETE")) e->knob.mog2_complete = atoi(env) != 0;
@@ -1080,6 +1085,38 @@ int bgs_get_eigen_params(const bgs_engine* e, bgs_eigen_params* p) {
   if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
   if (e->algo != BGS_DP_EIGENBACKGROUND) return fail(BGS_ERR_INVALID, "bgs_get_eigen_params: algorithm %d is not DPEigenbackground", (int)e->algo);
   *p = e->eig;
+  return BGS_OK;
+}
+
+int bgs_imbs_default_params(bgs_imbs_params* p) {
+  if (!p) return fail(BGS_ERR_INVALID, "params is NULL");
+  imbs_defaults(p);
+  return BGS_OK;
+}
+
+int bgs_set_imbs_params(bgs_engine* e, const bgs_imbs_params* p) {
+  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
+  if (e->algo != BGS_IMBS) return fail(BGS_ERR_INVALID, "bgs_set_imbs_params: algorithm %d is not IndependentMultimodalBGS", (int)e->algo);
+  if (p->struct_size != sizeof(bgs_imbs_params)) return fail(BGS_ERR_INVALID, "bgs_imbs_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_imbs_params));
+  int rc = imbs_check(*p);
+  if (rc) return rc;
+  if (!e->n) e->imbs = *p;  // the model sizes its arrays at its first frame (initialize) and the wrapper never constructs it again
+  return BGS_OK;
+}
+
+int bgs_imbs_check(const bgs_imbs_params* p, int rows, int cols, int channels) {
+  bgs_imbs_params d;
+  imbs_defaults(&d);
+  if (p && p->struct_size != sizeof(bgs_imbs_params)) return fail(BGS_ERR_INVALID, "bgs_imbs_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_imbs_params));
+  int rc = imbs_check(p ? *p : d);
+  if (rc || rows <= 0) return rc;
+  return imbs_check_geometry(BGS_IMBS, rows, cols, channels);
+}
+
+int bgs_get_imbs_params(const bgs_engine* e, bgs_imbs_params* p) {
+  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
+  if (e->algo != BGS_IMBS) return fail(BGS_ERR_INVALID, "bgs_get_imbs_params: algorithm %d is not IndependentMultimodalBGS", (int)e->algo);
+  *p = e->imbs;
   return BGS_OK;
 }
 

@@ -32,6 +32,7 @@ FrameProcessor::FrameProcessor()
   lbFuzzyAdaptiveSOM = nullptr, enableLBFuzzyAdaptiveSOM = false;
   vuMeter = nullptr, enableVuMeter = false;
   kde = nullptr, enableKDE = false;
+  imbs = nullptr, enableIMBS = false;
   sdbgs = nullptr, enableSigmaDeltaBGS = false;
   ssbgs = nullptr, enableSuBSENSEBGS = false;
   lobgs = nullptr, enableLOBSTERBGS = false;
@@ -72,6 +73,7 @@ void FrameProcessor::init() {  // FrameProcessor.cpp:35-155
   if (enableLBFuzzyAdaptiveSOM) lbFuzzyAdaptiveSOM = new LBFuzzyAdaptiveSOM;
   if (enableVuMeter) vuMeter = new VuMeter;  // :132
   if (enableKDE) kde = new KDE;  // after VuMeter, before IMBS (:135)
+  if (enableIMBS) imbs = new IndependentMultimodalBGS;  // :138-139
   if (enableSigmaDeltaBGS) sdbgs = new SigmaDeltaBGS;
   if (enableSuBSENSEBGS) ssbgs = new SuBSENSEBGS;
   if (enableLOBSTERBGS) lobgs = new LOBSTERBGS;
@@ -151,6 +153,7 @@ void FrameProcessor::process(const Image& img_input) {  // :169-340
   if (enableLBFuzzyAdaptiveSOM) process("LBFuzzyAdaptiveSOM", lbFuzzyAdaptiveSOM, img_prep, img_lb_fsom);
   if (enableVuMeter) process("VuMeter", vuMeter, img_prep, img_vumeter);  // :272
   if (enableKDE) process("KDE", kde, img_prep, img_kde);  // :275
+  if (enableIMBS) process("IMBS", imbs, img_prep, img_imbs);  // :278-279
   if (enableSigmaDeltaBGS) process("SigmaDeltaBGS", sdbgs, img_prep, img_sdbgs);
   if (enableSuBSENSEBGS) process("SuBSENSEBGS", ssbgs, img_prep, img_ssbgs);
   if (enableLOBSTERBGS) process("LOBSTERBGS", lobgs, img_prep, img_lobgs);
@@ -164,6 +167,7 @@ void FrameProcessor::finish() {  // :342-482 (reverse order of init)
   delete lobgs, lobgs = nullptr;
   delete ssbgs, ssbgs = nullptr;
   delete sdbgs, sdbgs = nullptr;
+  delete imbs, imbs = nullptr;  // :377-378
   delete kde, kde = nullptr;
   delete vuMeter, vuMeter = nullptr;
   delete lbFuzzyAdaptiveSOM, lbFuzzyAdaptiveSOM = nullptr;
@@ -238,6 +242,7 @@ void FrameProcessor::saveConfig() {  // :496-552 (keys of the classes this build
   fs.writeInt("enableLBFuzzyAdaptiveSOM", enableLBFuzzyAdaptiveSOM);
   fs.writeInt("enableVuMeter", enableVuMeter);  // :543
   fs.writeInt("enableKDE", enableKDE);  // :544
+  fs.writeInt("enableIMBS", enableIMBS);  // :545
   fs.writeInt("enableSigmaDeltaBGS", enableSigmaDeltaBGS);
   fs.writeInt("enableSuBSENSEBGS", enableSuBSENSEBGS);
   fs.writeInt("enableLOBSTERBGS", enableLOBSTERBGS);
@@ -277,6 +282,7 @@ void FrameProcessor::loadConfig() {  // :554-610 (defaults: PreProcessor and Fra
   enableLBFuzzyAdaptiveSOM = fs.readInt("enableLBFuzzyAdaptiveSOM", false);
   enableVuMeter = fs.readInt("enableVuMeter", false);  // :601
   enableKDE = fs.readInt("enableKDE", false);  // :602
+  enableIMBS = fs.readInt("enableIMBS", false);  // :603
   enableSigmaDeltaBGS = fs.readInt("enableSigmaDeltaBGS", false);
   enableSuBSENSEBGS = fs.readInt("enableSuBSENSEBGS", false);
   enableLOBSTERBGS = fs.readInt("enableLOBSTERBGS", false);

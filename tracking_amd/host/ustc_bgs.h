@@ -10,6 +10,8 @@
 // the high-threshold one.  Type 15: the class exists (DPEigenbackgroundBGS, bgs_classes_eigen.inc; FrameProcessor's
 // enableDPEigenbackgroundBGS builds it), but the type table still throws for 15: the suite pins USTC_BGS(15) as refused at run time
 // and the switch below as holding exactly the two tb/ cases, so a tracker reaches the class as an IBGS, not by number.
+// Type 33 likewise: IndependentMultimodalBGS exists (bgs_classes_imbs.inc; FrameProcessor's enableIMBS builds it) and the type table
+// still throws for 33, which the suite pins as refused too.
 #pragma once
 #include "bgs_host.h"
 #include "blob.h"
