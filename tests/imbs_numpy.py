@@ -132,6 +132,8 @@ def area_filter_follower(plane, min_area, stats=None):
     tmp = np.zeros((H, W), bool)
     if H >= 3 and W >= 3:
         for kind, pts in contours(plane):
+            if stats is not None:
+                stats.setdefault("areas2", []).append(polygon_area2(pts))  # doubled areas, in the order the borders are met
             if kept(polygon_area2(pts), min_area, H * W):
                 tmp |= polygon_cover(pts, (H, W))
                 if stats is not None:
@@ -139,6 +141,22 @@ def area_filter_follower(plane, min_area, stats=None):
             elif stats is not None:
                 stats["dropped_" + kind] = stats.get("dropped_" + kind, 0) + 1
     return plane & tmp
+
+
+def area_filter_follower_many(plane, min_areas):
+    """[area_filter_follower(plane, a) for a in min_areas] with the borders traced and filled once, and the doubled areas."""
+    H, W = plane.shape
+    traced = [(polygon_area2(pts), pts) for _, pts in contours(plane)] if H >= 3 and W >= 3 else []
+    covers, out = {}, []
+    for a in min_areas:
+        tmp = np.zeros((H, W), bool)
+        for i, (area2, pts) in enumerate(traced):
+            if kept(area2, a, H * W):
+                if i not in covers:
+                    covers[i] = polygon_cover(pts, (H, W))
+                tmp |= covers[i]
+        out.append(plane & tmp)
+    return out, [area2 for area2, _ in traced]
 
 
 def label(mask, conn8):

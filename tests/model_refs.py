@@ -1,7 +1,8 @@
-"""One adapter per model family for tools/fuzz_parity.py's `models` table (not a test module): the 14 classes that are pinned to
-reference-built fixtures and restated in numpy (kde_numpy, dp2_numpy, lb_numpy, vumeter_numpy, fuzzy_numpy, t2f_numpy, eigen_numpy).
+"""One adapter per model family for tools/fuzz_parity.py's `models` table (not a test module): the 15 classes that are pinned to
+reference-built fixtures and restated in numpy (kde_numpy, dp2_numpy, lb_numpy, vumeter_numpy, fuzzy_numpy, t2f_numpy, eigen_numpy,
+imbs_numpy).
 
-An adapter draws parameters (and, rarely, one the engine must refuse: `refusal()` is the table, from DESIGN.md §5.3-5.9), names the
+An adapter draws parameters (and, rarely, one the engine must refuse: `refusal()` is the table, from DESIGN.md §5.3-5.10), names the
 input generators of its family, builds the restatement of one stream (`make_ref`: a fresh one per stream and after every
 reset_stream), says which parameters a running stream follows (`follow`) and under which contract the model is compared at the end
 (`tols`: a plane that is not named there is compared bit for bit).  Everything up to `reference_run` needs neither torch nor an
@@ -14,6 +15,8 @@ import numpy as np
 import dp2_numpy as dn
 import eigen_numpy as en
 import fuzzy_numpy as fz
+import imbs_masks as mk
+import imbs_numpy as im
 import kde_numpy as kn
 import lb_numpy as ln
 import t2f_numpy as tn
@@ -92,7 +95,15 @@ def _clip(kind, T, H, W, seed, quiet):
             "dp2_scene": lambda: dn.scene_clip(T, H, W, seed, box=0.15), "dp2_tie": lambda: dn.tie_clip(T, H, W, seed), "dp2_texture": lambda: dn.texture_clip(T, H, W, seed),
             "t2f_scene": lambda: tn.scene_clip(T, H, W, seed), "t2f_corners": lambda: tn.corners_clip(T, H, W, seed),
             "vu_box": lambda: vn.bgr(T, H, W, seed), "vu_leave": lambda: np.repeat(vn.leave(T, H, W, seed)[..., None], 3, axis=-1),
-            "eigen_pca": lambda: en.pca_clip(T, H, W, seed, quiet)}[kind]()
+            "eigen_pca": lambda: en.pca_clip(T, H, W, seed, quiet), "imbs_box": lambda: im.clip("box", T, H, W, seed), "imbs_persist": lambda: im.clip("persist", T, H, W, seed),
+            "imbs_shadow": lambda: _imbs_event("shadow", 2, T, H, W, seed, quiet), "imbs_holes": lambda: _imbs_event("holes", 2, T, H, W, seed, quiet),
+            "imbs_sudden": lambda: _imbs_event("sudden", 3, T, H, W, seed, quiet), "imbs_inject": lambda: mk.fuzz_clip(T, H, W, seed, quiet)}[kind]()
+
+
+def _imbs_event(kind, part, T, H, W, seed, lead):
+    """T frames of an imbs_numpy.clip whose scene changes at 1 / `part` of its length, cut so that the change falls on frame `lead`."""
+    E = max(lead, T - lead)
+    return im.clip(kind, part * E, H, W, seed)[E - lead:E - lead + T]
 
 
 def build_inputs(case):
@@ -645,7 +656,90 @@ class Eigen(Adapter):
         return _EigenRef(p, H, W, stats)
 
 
-ADAPTERS = [Kde(), Prati(), Texture(), Lb(), VuMeter(), Fuzzy(), T2f(), Eigen()]
+# -- IndependentMultimodalBGS
+
+class _ImbsRef:
+    def __init__(self, p, H, W, stats):
+        def area_filter(plane, min_area, _):
+            out = im.area_filter_follower(plane, min_area)
+            stats["filtered"] = stats.get("filtered", 0) + int(out.sum() < plane.sum())  # frames of which the filter removed something
+            return out
+        self.m, self.stats = im.Model(p, H, W, area_filter), stats
+
+    def step(self, f):
+        fg, bg = self.m.apply(f)
+        for v in (80, 180):
+            self.stats[v] = self.stats.get(v, 0) + int((fg == v).sum())
+        return fg, bg, None
+
+    def switch(self, p):
+        pass
+
+    def planes(self):
+        return dict(self.m.planes(), control=self.m.control())
+
+
+class Imbs(Adapter):
+    """The contract is the restatement with the contour follower as its area filter.  Every frame delivers a mask
+    and a background (zero images until the first model).  An inverted clip would leave the palette imbs_numpy.clip keeps to: no cut."""
+    family, classes, has_bg, cut = "imbs", {im.CLASS_NAME: capi.IMBS}, True, False
+    kinds = ("imbs_box", "imbs_box", "imbs_persist", "imbs_shadow", "imbs_holes", "imbs_sudden", "imbs_inject", "imbs_inject", "imbs_inject")
+    reset_rate = 0.08  # a stream detects only after its first build
+    # one row, the smallest frame with an interior, ragged, whole words; below 3 x 3 the filter leaves nothing, so most frames are larger
+    h_small, w_small = [1, 3, 7, 16, 16, 33, 33], [3, 5, 37, 37, 64, 70, 70]
+    h_big, w_big = [33, 65], [64, 97, 131]                    # the follower costs about 2 s a clip at 65 x 131
+    step_of = {im.CLASS_NAME: ("minArea", lambda v: v + 0.5, None)}  # areas are exact halves; fgThreshold + 1 goes unnoticed in the first six cases
+    CLOCKS = ((10.0, 100), (30.0, 33), (10.0, 200), (25.0, 80))  # (fps, samplingPeriod): a sample on every frame (the first two) or on every second one
+
+    @staticmethod
+    def lead(p):
+        """Frames before the first detecting one: numSamples - 1 samples, the build, at one or two frames a sample."""
+        stride = 1 if p["fps"] <= 0 or 1000. / p["fps"] >= p["samplingPeriod"] else 2
+        return stride * (min(max(int(p["numSamples"]), 2), 63) - 1) + 1
+
+    def draw_params(self, rng, name, H, W, T):
+        fps, sp = self.CLOCKS[int(rng.choice([0, 0, 1, 2, 3]))]
+        return dict(fps=fps, samplingPeriod=sp, numSamples=int(rng.integers(3, 13)), minBinHeight=int(rng.integers(1, 4)), fgThreshold=int(rng.choice([15, 10, 25, 40])),
+                    associationThreshold=int(rng.choice([5, 3, 8, 4])), minArea=float(rng.choice([0.0, 2.5, 4.0, 30.0])), persistencePeriod=int(rng.choice([150, 300, 10000])),
+                    alpha=float(rng.choice([0.65, 0.5, 0.8])), beta=float(rng.choice([1.15, 1.3, 1.0])), tau_s=int(rng.choice([60, 30, 255])), tau_h=int(rng.choice([40, 20, 0])),
+                    morphologicalFiltering=int(rng.random() < 0.2))
+
+    def draw_frames(self, rng, p):  # at least numSamples + 6: five or more detecting frames, and a second build where numSamples is small
+        return self.lead(p) + int(rng.integers(6, 14))
+
+    def draw_bad(self, rng, name, p):
+        return [("numSamples", 1), ("numSamples", 64), ("minBinHeight", 0), ("minBinHeight", p["numSamples"] + 1), ("tau_s", 256), ("fps", 0.0)][int(rng.integers(0, 6))]
+
+    def refusal(self, name, p):  # DESIGN.md §5.10, "Ids, parameters, refusals"
+        f = np.float32
+        if not (p["fps"] > 0 and np.isfinite(p["fps"])) or p["minBinHeight"] == 0 or not 2 <= p["numSamples"] <= capi.IMBS_MAX_SAMPLES or p["numSamples"] // p["minBinHeight"] == 0:
+            return capi.ERR_UNSUPPORTED
+        if not (0 <= p["tau_s"] <= 255 and 0 <= p["tau_h"] <= 255) or not all(np.isfinite(f(p[k])) for k in ("alpha", "beta")) or not np.isfinite(p["minArea"]):
+            return capi.ERR_UNSUPPORTED
+        return None
+
+    def draw_switch(self, rng, name, p):  # taken when the geometry is set: a later call succeeds and changes nothing
+        q = self.draw_params(rng, name, 0, 0, 0)
+        return dict(q, fgThreshold=p["fgThreshold"] + 7, minArea=p["minArea"] + 3.0, numSamples=p["numSamples"] % 10 + 3)
+
+    def make_engine(self, name, p, S):
+        from tracking_amd import Engine
+        eng = Engine(self.classes[name], n_streams=S)
+        try:
+            self.apply(eng, name, p)
+        except capi.BgsError:
+            eng.close()
+            raise
+        return eng
+
+    def apply(self, eng, name, p):
+        eng.set_imbs_params(**p)
+
+    def make_ref(self, name, p, H, W, stats):
+        return _ImbsRef(p, H, W, stats)
+
+
+ADAPTERS = [Kde(), Prati(), Texture(), Lb(), VuMeter(), Fuzzy(), T2f(), Eigen(), Imbs()]
 BY_CLASS = {name: ad for ad in ADAPTERS for name in ad.classes}
 MODELS = sorted(BY_CLASS)
 FAMILIES = {ad.family: sorted(ad.classes) for ad in ADAPTERS}
@@ -672,6 +766,8 @@ def _draw_once(rng, seed, classes, big, attempt):
         r = dict(kind=str(rng.choice(ad.kinds)), seed=seed * 7 + s + 1000003 * attempt, cut=bool(ad.cut and rng.random() < 0.3))
         if r["kind"] == "eigen_pca":
             r["quiet"] = p["history_size"] + 2  # the box stays out of a fresh stream's history
+        elif r["kind"].startswith("imbs_"):
+            r["quiet"] = ad.lead(p)  # what a clip shows starts where a fresh stream detects
         inputs.append(r)
     mode = str(rng.choice(MODES))
     resets = bool(rng.random() < 0.35)
@@ -745,9 +841,15 @@ def describe(case):
 # One class per slice, so that the restatement's side of a slice stays near 3 s on the CPU; tests/test_fuzz_models_cpu.py holds every
 # slice to the conditions a class needs (accepted cases, entry points, geometries, resets, switches, refusals, lively masks).
 
+IMBS_SLICE_INDEX = 14  # the 14 classes of the first table keep the index, and with it the seeds, of their place in their sorted list
+
+
 def _slices():
     out = []
-    for k, name in enumerate(MODELS):
+    first14 = [n for n in MODELS if n != im.CLASS_NAME]
+    assert len(first14) == IMBS_SLICE_INDEX
+    for name in MODELS:
+        k = IMBS_SLICE_INDEX if name == im.CLASS_NAME else first14.index(name)
         fam = BY_CLASS[name].family
         small, small_parts, big, big_parts = SLICE_CASES.get(name, SLICE_CASES["*"])
         for size, is_big, first, count, parts in (("small", False, 700000 + 1000 * k, small, small_parts), ("big", True, 800000 + 1000 * k, big, big_parts)):
@@ -759,7 +861,7 @@ def _slices():
 
 # class -> (small cases, slices they are cut into, big cases, slices they are cut into); cut where a restatement is slow
 SLICE_CASES = {"*": (36, 1, 8, 1), "DPTexture": (28, 4, 6, 3), "LBAdaptiveSOM": (36, 2, 8, 2), "LBFuzzyAdaptiveSOM": (36, 2, 8, 4), "LBMixtureOfGaussians": (36, 1, 8, 2),
-               "T2FGMM_UV": (36, 1, 8, 2)}
+               "T2FGMM_UV": (36, 1, 8, 2), im.CLASS_NAME: (36, 1, 8, 4)}
 SLICES = _slices()
 
 

@@ -1,4 +1,4 @@
-"""The fuzz of the 14 reference-pinned model classes (tools/fuzz_parity.py `models`, tests/model_refs.py), checked without a GPU: the
+"""The fuzz of the 15 reference-pinned model classes (tools/fuzz_parity.py `models`, tests/model_refs.py), checked without a GPU: the
 old table still draws the cases it always drew, a draw is pure and deterministic, the fixed slices of tests/test_gpu_20_fuzz_models.py
 cover what each class needs, the checkers report planted defects, and the slices' inputs tell a restatement from the same restatement
 one parameter step away."""
@@ -52,6 +52,17 @@ def test_a_draw_is_pure_and_deterministic(monkeypatch):
 
 
 # ---- the slices ----------------------------------------------------------------------------------------------------------------------
+
+def test_the_slices_of_the_first_14_classes_keep_their_seeds():
+    """IndependentMultimodalBGS sorts into the middle of the class list; it takes index 14, and the 41 slices that were there before
+    it are the tuples they were (tests/golden/fuzz_model_slices.json, recorded from the table of 14)."""
+    rec = [tuple([r[0], tuple(r[1])] + r[2:]) for r in json.load(open(os.path.join(GOLDEN, "fuzz_model_slices.json")))]
+    assert len(rec) == 41 and len({r[1] for r in rec}) == 14
+    assert [s for s in mr.SLICES if s[1] != (mr.im.CLASS_NAME,)] == rec
+    mine = [s for s in mr.SLICES if s[1] == (mr.im.CLASS_NAME,)]
+    assert [(s[2], s[3], s[4]) for s in mine] == [(False, 714000, 36), (True, 814000, 2), (True, 814002, 2), (True, 814004, 2), (True, 814006, 2)]
+    assert len({s[0] for s in mr.SLICES}) == len(mr.SLICES) == 46
+
 
 @functools.lru_cache(maxsize=None)
 def drawn(slice_id):
@@ -123,6 +134,16 @@ def test_slices_cover_what_the_class_needs(name):
             assert 5 * sum(c["redraws"] > 0 for c, _, _ in rows) <= len(rows), "more than a fifth of the draws had to be redrawn"
             for c, _, st in rows:
                 assert st["gaps"] and all(g >= mr.en.EIGENGAP for g in st["gaps"]) and st["band"] <= mr.en.BAND_SHARE * st["detected"], c["seed"]
+        if ad.family == "imbs":  # the area filter removes something of a compared frame's 255-plane in at least half of the sized cases
+            cut = [st.get("filtered", 0) > 0 for c, _, st in rows if c["H"] * c["W"] >= 20]
+            assert 2 * sum(cut) >= len(cut), "%d of %d %s cases have a frame of which the area filter removes pixels" % (sum(cut), len(cut), "big" if is_big else "small")
+            assert all(c["redraws"] == 0 for c, _, _ in rows)  # no draw is redrawn: parity is claimed on every input
+    if ad.family == "imbs":  # labels 180 and 80 occur, frames below 3 x 3 (no interior: the filter leaves nothing) and a morphology case too
+        every = [(c, st) for sid in mr.slices_of(name, False) + mr.slices_of(name, True) for c, _, st in restated(sid)[1]]
+        assert sum(st.get(180, 0) > 0 for _, st in every) >= 3 and sum(st.get(80, 0) > 0 for _, st in every) >= 3
+        assert any(min(c["H"], c["W"]) < 3 for c, _ in every) and any(c["W"] == 3 for c, _ in every) and any(c["params"]["morphologicalFiltering"] for c, _ in every)
+        assert {r["kind"] for c, _ in every for r in c["inputs"]} == set(ad.kinds)
+        assert any(c["H"] * c["W"] > 4 * 256 and c["H"] * c["W"] % 256 for c, _ in every) and max(c["H"] * c["W"] for c, _ in every) <= 65 * 131
     print("%s: restatement side of each slice, seconds: %s" % (name, {k: round(v, 1) for k, v in secs.items()}))
 
 

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import imbs_masks as mk
 import imbs_numpy as im
 from tracking_amd import capi
 
@@ -85,8 +86,92 @@ def test_every_branch_of_the_survival_rule_is_taken_in_the_holes_cases():
     follower = {}
     for case in HOLES:
         for k, v in restated(case)[3].stats.items():
-            follower[k] = follower.get(k, 0) + v
+            if k != "areas2":  # the list of doubled areas
+                follower[k] = follower.get(k, 0) + v
     assert all(follower.get(k, 0) > 0 for k in ("kept_outer", "kept_hole", "dropped_outer", "dropped_hole")), follower
+
+
+# ---- the hard masks of tests/imbs_masks.py (what tests/test_gpu_22_imbs_area.py injects) -------------------------------------------------
+
+@pytest.mark.parametrize("size", mk.SIZES + (mk.RECT_SIZE, (3, 3)), ids=lambda s: "%dx%d" % s)
+def test_follower_form_equals_quad_form_on_the_hard_masks(size):
+    """Every generator at minArea 0, 2.5, 30 and at two values taken from the mask itself: an area that occurs (kept: `area <
+    minArea` is false) and that area plus one half (dropped), which puts the kept / dropped edge on exact halves."""
+    H, W = size
+    for name, m in mk.clip_masks(H, W):
+        assert m.shape == (H, W) and m.dtype == bool
+        assert name.startswith("rect") or 2 * int(m.sum()) <= H * W, name
+        areas2 = im.area_filter_follower_many(m, [])[1]
+        edge = mk.edge_min_area(areas2, H * W)
+        min_areas = [0.0, 2.5, 30.0, edge, edge + 0.5]
+        want, _ = im.area_filter_follower_many(m, min_areas)
+        if H * W <= 33 * 70:  # the traced-once helper is the filter (the largest size would trace and fill everything twice for it)
+            stats = {}
+            assert np.array_equal(want[1], im.area_filter_follower(m, 2.5, stats)), name
+            assert stats.get("areas2", []) == areas2
+        at = [a for a in areas2 if a == int(2 * edge)]
+        if any(0 < a / 2.0 < 0.6 * H * W for a in areas2):
+            assert at and im.kept(at[0], edge, H * W) and not im.kept(at[0], edge + 0.5, H * W), (name, edge)
+        for a, w in zip(min_areas, want):
+            got = im.area_filter_quads(m, a)
+            bad = np.argwhere(got != w)
+            assert not len(bad), "%s %dx%d minArea %g: %d pixels differ, first at %s" % (name, H, W, a, len(bad), tuple(bad[0]))
+
+
+@pytest.mark.parametrize("defect", ["zeros 8-connected", "ones 4-connected"])
+def test_the_hard_masks_notice_a_wrong_connectivity(defect, monkeypatch):
+    """The quad form with one labelling's connectivity swapped, at 33 x 70 and minArea 2.5: the corner-touching masks (ones that
+    touch at a corner, holes that touch at a corner) and others tell it from the follower, so a device labelling with the wrong
+    neighbourhood cannot pass tests/test_gpu_22_imbs_area.py."""
+    label = im.label
+    monkeypatch.setattr(im, "label", lambda m, conn8: label(m, defect == "zeros 8-connected"))
+    caught = [name for name, m in mk.masks_for(33, 70) if not np.array_equal(im.area_filter_quads(m, 2.5), im.area_filter_follower(m, 2.5))]
+    assert ("sieve" if defect == "zeros 8-connected" else "corners") in caught and len(caught) >= 3, caught
+
+
+def _summed(stats):
+    out = {}
+    for st in stats:
+        for k, v in st.items():
+            if k != "areas2":
+                out[k] = out.get(k, 0) + v
+    return out
+
+
+@pytest.mark.parametrize("size", mk.SIZES + (mk.RECT_SIZE,), ids=lambda s: "%dx%d" % s)
+def test_injected_clips_hand_the_filter_the_painted_masks(size):
+    """What tests/test_gpu_22_imbs_area.py relies on, from the restatement alone: the plane that reaches the area filter is the painted
+    mask on every injected frame, `sudden_change` stays 0 (except after the rectangles), and the clips of one size take every branch."""
+    H, W = size
+    r = mk.reference(H, W)
+    ctl = r["out"][2]
+    assert len(r["planes"]) == len(r["masks"]) == len(mk.NAMES) + 2 * (size == mk.RECT_SIZE)
+    for name, m, plane in zip(r["names"], r["masks"], r["planes"]):
+        assert np.array_equal(plane, m), (name, int((plane != m).sum()))
+    assert ctl[r["first"] - 1, 9] == 1 and not r["out"][0][:r["first"]].any()  # detecting before the first mask, and nothing found
+    sudden = ctl[r["first"]:, 7]
+    if size == mk.RECT_SIZE:  # both rectangles set more than half of the pixels; the next frame's changeBg sets bg_reset
+        assert not sudden[:-2].any() and sudden[-2:].all() and ctl[-1, 6] == 1 and not ctl[:-1, 6].any()
+        below, on = r["stats"][-2], r["stats"][-1]  # both sides of the 0.6 * numPixels edge
+        assert below["areas2"] == [2 * 99] and below.get("kept_outer") == 1 and on["areas2"] == [2 * 108] and on.get("dropped_outer") == 1
+        assert 0.6 * (H * W) == 108.0 and r["out"][0][-2].sum() == 255 * 120 and not r["out"][0][-1].any()
+    else:
+        assert not sudden.any()
+    assert not (r["out"][0] == 180).any() and not (r["out"][0] == 80).any()  # the masks are the filter's output alone
+    follower = _summed(r["stats"])
+    assert all(follower.get(k, 0) > 0 for k in ("kept_outer", "kept_hole", "dropped_outer", "dropped_hole")), follower
+    quads = _summed(mk.reference(H, W, quads=True)["stats"])
+    assert np.array_equal(mk.reference(H, W, quads=True)["out"][0], r["out"][0])
+    assert quads.get("chain", 0) > 0 and quads.get("dropped", 0) > 0, quads
+    # a pixel survives on one of its component's own holes only where the component's outer border is dropped and a hole of it is
+    # kept, that is where the outer area reaches 0.6 H W: at most (H - 3)(W - 3), so the five-pixel-wide frames cannot get there
+    assert (quads.get("own_hole", 0) > 0) == ((H - 3) * (W - 3) >= 0.6 * H * W), quads
+    if size == (65, 131):
+        st = {name: mk.structure(m) for name, m in zip(r["names"], r["masks"])}
+        assert st["checkerboard"]["holes"] >= 3000, st["checkerboard"]
+        assert st["serpentine"]["spans"] >= 30 and (H * W + 255) // 256 == 34, st["serpentine"]  # one component through the workgroups' spans
+        assert set(np.unique(im.label(r["masks"][r["names"].index("serpentine")], True))) == {-1, W + 1}  # a single component, named by its first pixel
+        assert st["rings2"]["depth"] >= 8, st["rings2"]
 
 
 def test_fixture_holds_every_case_and_is_small():
