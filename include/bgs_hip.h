@@ -90,7 +90,10 @@ typedef enum bgs_algo {
   /* package_bgs/db's IMBS (3-channel frames; output = the four-label mask 0 / 80 shadow / 180 persistence / 255 foreground and the BGR
    * background of the last model build).  Its parameters are bgs_imbs_params, not bgs_params. */
   BGS_IMBS = 35,                  /* IndependentMultimodalBGS::process (USTC_BGS type 33) package_bgs/db/IndependentMultimodalBGS.cpp:13-36 */
-  BGS_ALGO_LAST = 36              /* one past the last id; moves with every class added */
+  /* package_bgs/jmo's multi-layer LBP + colour model (3-channel frames; output = the thresholded, smoothed distance map and the BGR
+   * background of the first-ranked mode).  Its parameters are bgs_multilayer_params, not bgs_params. */
+  BGS_MULTILAYER = 36,            /* MultiLayerBGS::process (USTC_BGS type 23) package_bgs/jmo/MultiLayerBGS.cpp:60-249 */
+  BGS_ALGO_LAST = 37              /* one past the last id; moves with every class added */
 } bgs_algo;
 
 /* "id is an algorithm": the one range check (bgs_default_params, bgs_create, bgs_node_create) */
@@ -336,6 +339,47 @@ typedef struct bgs_imbs_params {
   int32_t morphologicalFiltering; /* 0 */
 } bgs_imbs_params;
 
+/* MultiLayerBGS (package_bgs/jmo/MultiLayerBGS.cpp:110-186, :292-331): the wrapper's parameters, each in the type of the member it
+ * lands in.  A struct of its own, as bgs_imbs_params.  bgs_create gives a MultiLayerBGS engine the wrapper's loadDefaultParams
+ * values whatever bgs_params it was handed.  The wrapper hands its values to the model at its first frame only: they are taken when
+ * the geometry is set, and a bgs_set_multilayer_params after that succeeds and leaves the values in force unchanged.
+ * status 0 = MLBGS_LEARN, 1 = MLBGS_DETECT; disable_detect_mode forces LEARN; at frame detect_after (> 0) the hard-coded DETECT values
+ * 0.01 / 0.01 / 0.001 are installed, not the detect_* ones, and disable_learning applies.  The bilateral sigmas
+ * of the reference's XML are no fields: LINUX_BILATERAL_FILTER is compiled out.  A model preload is not offered.
+ * Refused with BGS_ERR_UNSUPPORTED, the class named: max_mode_num outside 1..5, pattern_neig_half_size above
+ * BGS_MULTILAYER_MAX_HALF_SIZE, pattern_neig_gaus_sigma <= 0 while the half size is >= 0 (a negative half size means no
+ * smoothing), non-finite values, frames that are not 3-channel, the class inside a bgs_group.  texture_weight <= 0 is accepted: LBP is
+ * skipped and the patterns read as zero. */
+typedef struct bgs_multilayer_params {
+  uint32_t struct_size;                       /* sizeof(bgs_multilayer_params) = 96 */
+  int32_t max_mode_num;                       /* 5 */
+  float weight_updating_constant;             /* 5.0 */
+  float texture_weight;                       /* 0.5 */
+  float bg_mode_percent;                      /* 0.6 */
+  int32_t pattern_neig_half_size;             /* 4 */
+  float pattern_neig_gaus_sigma;              /* 3.0 */
+  float bg_prob_threshold;                    /* 0.2 */
+  float bg_prob_updating_threshold;           /* 0.2 */
+  int32_t robust_LBP_constant;                /* 3 */
+  float min_noised_angle;                     /* (float)(10.0 / 180.0 * PI), PI the float macro */
+  float shadow_rate;                          /* 0.6 */
+  float highlight_rate;                       /* 1.2 */
+  float frame_duration;                       /* 0.1 */
+  float learn_mode_learn_rate_per_second;     /* 0.5 */
+  float learn_weight_learn_rate_per_second;   /* 0.5 */
+  float learn_init_mode_weight;               /* 0.05 */
+  float detect_mode_learn_rate_per_second;    /* 0.01 */
+  float detect_weight_learn_rate_per_second;  /* 0.01 */
+  float detect_init_mode_weight;              /* 0.001 */
+  int32_t status;                             /* 0 */
+  int32_t disable_detect_mode;                /* 1 */
+  int32_t disable_learning;                   /* 0 */
+  int32_t detect_after;                       /* 0 */
+} bgs_multilayer_params;
+
+/* Largest pattern_neig_half_size the MultiLayerBGS smoothing kernel is built for (a 17 x 17 Gaussian). */
+#define BGS_MULTILAYER_MAX_HALF_SIZE 8
+
 /* Largest numSamples the IMBS kernels are built for (bin heights and counters are packed into 6 bits). */
 #define BGS_IMBS_MAX_SAMPLES 63
 
@@ -389,6 +433,17 @@ int bgs_get_imbs_params(const bgs_engine* e, bgs_imbs_params* p);
 /* Every refusal of the class without an engine and without a device: parameters (p == NULL: the defaults) and, where rows > 0, the
  * frame geometry.  The message names the class. */
 int bgs_imbs_check(const bgs_imbs_params* p, int rows, int cols, int channels);
+
+/* MultiLayerBGS's own parameters (bgs_multilayer_params above); BGS_ERR_INVALID for an engine of any other class. */
+int bgs_multilayer_default_params(bgs_multilayer_params* p);
+int bgs_set_multilayer_params(bgs_engine* e, const bgs_multilayer_params* p);
+int bgs_get_multilayer_params(const bgs_engine* e, bgs_multilayer_params* p);
+/* Every refusal of the class without an engine and without a device: parameters (p == NULL: the defaults) and, where rows > 0, the
+ * frame geometry.  The message names the class. */
+int bgs_multilayer_check(const bgs_multilayer_params* p, int rows, int cols, int channels);
+/* The two constants the host computes for the kernels, as float bits, without a device: bits[0] = the constructor's sinf(3 degrees)
+ * (m_fMinNoisedAngleSine, never recomputed), bits[1] = min_noised_angle of p (NULL: the defaults). */
+int bgs_multilayer_constants(const bgs_multilayer_params* p, uint32_t bits[2]);
 
 /* Engine options.
  *   BGS_OPT_BORROW_FRAMES  device path of the history-keeping classes (FrameDifference, WeightedMovingMean/Variance):
@@ -612,6 +667,9 @@ const char* bgs_last_error(void);
  * "model" u8 [n][M][6] = values B, G, R, isValid, isFg, counter; "persistence" u32 [n]; "control" f64 [10] = timestamp,
  * prev_timestamp, prev_bg_frame_time, bg_frame_counter, numSamples, samplingPeriod, bg_reset, sudden_change, maxBgBins,
  * bgModel[0].isValid[0].  Slots the reference never wrote read 0.
+ * MultiLayerBGS, unpacked in the reference's field order: "order" u8 [n][7] = num, bg_num, lbp_idxes[0..5) (entries at and past num read
+ * 0); "modes" f32 [n][5][18] = bg_pattern[6], bg_intensity[3], max_intensity[3], min_intensity[3], weight, max_weight, bg_layer_num per
+ * physical slot (slots that lbp_idxes[0..num) does not name read 0); "dist" f32 [n] = the last frame's smoothed distance map.
  * lb/ models, all f64 in the reference's memory order, colour fields in the byte order of the input pixel (B, G, R):
  * SimpleGaussian / FuzzyGaussian "mu", "var" f64 [n][3]; MixtureOfGaussians "w" f64 [n][3], "mu", "var" f64 [n][3][3] (pixel, slot,
  * colour), "sortkey" f64 [n][3], "k" int32 [n] (slots >= k read 0); AdaptiveSOM / FuzzyAdaptiveSOM "som" f64 [n][3][3][3] (pixel,

@@ -18,6 +18,8 @@ Not the driver's bench line (bench.py is); the numbers go to DESIGN.md §6.
              on S_surv, 8 x 1080p and 1 x 1080p: ms per detecting step, the one-off model build at frame H, this box's copy rate
   --only imbs: IndependentMultimodalBGS (package_bgs/db) at the wrapper's defaults (numSamples 30) on S_surv, 8 x 1080p: the detect-only
              step, the sampling step and the build step apart, what the launches cost on empty planes, the numpy restatement beside
+  --only multilayer: MultiLayerBGS (package_bgs/jmo) at the wrapper's defaults on S_surv, 8 x 1080p: ms per step, the model kernel and
+             the smoothing kernel apart, bytes per pixel of state, this box's copy rate
 usage: bench_configs.py [--streams S] [--swizzle 0|1]"""
 import argparse
 import os
@@ -1047,6 +1049,48 @@ def run_imbs(S=8, rows=1080, cols=1920):
     print("  numpy restatement (numSamples 6, quad form) on 120 x 160: %.1f ms per frame = %.2f us/pixel; the engine's detecting step: %.5f us/pixel" % (cpu * 1e3, cpu * 1e6 / (120 * 160), det * 1e3 / px))
 
 
+def run_multilayer(S=8, rows=1080, cols=1920, steps=30):
+    """MultiLayerBGS at the wrapper's defaults (five modes, a 9 x 9 Gaussian) on S_surv, mask and background out.  Every step is two
+    launches: ml_model_kernel (kernel timing: events around that launch alone) and ml_smooth_kernel (what is left of the step, which is
+    timed between two events on the launch stream with the host far ahead).  The model is aged 40 frames first, past the frame at which
+    a matched mode gets its layer (14).  Bytes per pixel are the layout's: 67 dword planes of model, the raw and the smoothed distance
+    map; what a step moves depends on how many modes a pixel lists (13 planes read per listed mode, 2 + 2 per listed mode + 11 written),
+    so the rate against this process's own copy rate is given for the mean number of listed modes read back from the state."""
+    dev = torch.device("cuda", 0)
+    copy = capi.calibrate_copy(0, 2 << 30, 0)
+    px = S * rows * cols
+    e = Engine(capi.MULTILAYER, n_streams=S)
+    e.set_geometry(rows, cols, 3)
+    pool = synth.SurvStreams(S, rows, cols, seed0=4321, device=dev).pool(8)
+    fg = torch.empty((S, rows, cols), dtype=torch.uint8, device=dev)
+    bg = torch.empty((S, rows, cols, 3), dtype=torch.uint8, device=dev)
+    for t in range(40):
+        e.process_batch_device(pool[t % 8], fg, bg, None)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for t in range(steps):
+        e.process_batch_device(pool[t % 8], fg, bg, None)
+    b.record()
+    torch.cuda.synchronize()
+    step = a.elapsed_time(b) / steps
+    e.enable_kernel_timing(True)
+    for t in range(steps):
+        e.process_batch_device(pool[t % 8], fg, bg, None)
+    torch.cuda.synchronize()
+    ms, n, kname = e.kernel_timing()
+    order = e.get_state("order", (rows * cols, 7), np.uint8)
+    listed = float(order[:, 0].mean())
+    ratio = float((fg != 0).float().mean())
+    state_bpp = 4 * 67 + 8
+    moved = 3 * 7 + 8 + 13 * 4 * listed + (2 + 2 * listed + 11) * 4 + 4 + 3 + 4 * 2 + 4 + 1  # frame and six neighbours, header, modes, write-back, raw, background, the blur
+    print("MultiLayerBGS defaults %dx%d x%d streams, %d steps after 40: %.3f ms/step = %.3f ms/stream -> %7.1f Mpix/s; %s %.3f ms (mean of %d), the rest of the step (ml_smooth_kernel) %.3f ms"
+          % (cols, rows, S, steps, step, step / S, px / step / 1e3, kname, ms, n, step - ms))
+    print("  state %d B/px (67 dword planes + raw + smoothed distance); %.2f modes listed per pixel (stream 0) -> about %.0f B/px moved per step = %.0f GB/s = %.2f of this process's copy rate %.0f GB/s; fg ratio %.3f"
+          % (state_bpp, listed, moved, moved * px / (step * 1e-3) / 1e9, moved * px / (step * 1e-3) / 1e9 / copy, copy, ratio))
+    e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=8)
@@ -1080,6 +1124,9 @@ def main():
         return
     if args.only == "imbs":
         run_imbs(S)
+        return
+    if args.only == "multilayer":
+        run_multilayer(S)
         return
     if args.only in ("fuzzy_choquet", "fuzzy_sugeno"):
         run_fuzzy(S, steps=5, only="FuzzyChoquetIntegral" if args.only == "fuzzy_choquet" else "FuzzySugenoIntegral", calibrate=False)

@@ -22,16 +22,19 @@ FUZZY_SUGENO, FUZZY_CHOQUET = 29, 30  # package_bgs/tb fuzzy integrals; their pa
 T2FGMM_UM, T2FGMM_UV = 32, 33  # package_bgs/tb type-2 fuzzy GMMs (id 31 is the third hole); their parameters are BgsT2fParams
 DP_EIGENBACKGROUND = 34  # package_bgs/dp PCA background; its parameters are BgsEigenParams
 IMBS = 35  # package_bgs/db IndependentMultimodalBGS; its parameters are BgsImbsParams
-ALGO_LAST = 36  # one past the last id
+MULTILAYER = 36  # package_bgs/jmo MultiLayerBGS; its parameters are BgsMultilayerParams
+ALGO_LAST = 37  # one past the last id
 ALGO_LIMIT = 28  # frozen, and id 28 is the second permanent hole
 FUZZY_SUGENO, FUZZY_CHOQUET = 29, 30  # package_bgs/tb fuzzy integrals; their parameters are BgsFuzzyParams, not BgsParams
 T2FGMM_UM, T2FGMM_UV = 32, 33  # package_bgs/tb type-2 fuzzy GMMs (id 31 is the third hole); their parameters are BgsT2fParams
 DP_EIGENBACKGROUND = 34  # package_bgs/dp PCA background; its parameters are BgsEigenParams
 IMBS = 35  # package_bgs/db IndependentMultimodalBGS; its parameters are BgsImbsParams
-ALGO_LAST = 36  # one past the last id
+MULTILAYER = 36  # package_bgs/jmo MultiLayerBGS; its parameters are BgsMultilayerParams
+ALGO_LAST = 37  # one past the last id
 PRATI_MAX_HISTORY = 64  # BGS_PRATI_MAX_HISTORY
 EIGEN_MAX_HISTORY = 32  # BGS_EIGEN_MAX_HISTORY
 IMBS_MAX_SAMPLES = 63  # BGS_IMBS_MAX_SAMPLES
+MULTILAYER_MAX_HALF_SIZE = 8  # BGS_MULTILAYER_MAX_HALF_SIZE
 FG_VALID, BG_VALID = 1, 2
 OPT_BORROW_FRAMES, OPT_MOG2_PIXELS_PER_LANE, OPT_MOG2_TILED, OPT_XCD_SWIZZLE, OPT_PLACEMENT_PROBE, OPT_MOG2_SPARSE, OPT_CLIP_FUSE, OPT_HOST_REGISTER, OPT_MODEL_CHUNK_MB, OPT_MODEL_CHUNK_MIN_MB = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 
@@ -136,6 +139,16 @@ class BgsImbsParams(C.Structure):
                 ("minArea", C.c_double), ("persistencePeriod", C.c_uint32), ("morphologicalFiltering", C.c_int32)]
 
 
+class BgsMultilayerParams(C.Structure):
+    """struct bgs_multilayer_params, field for field (MultiLayerBGS)."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_mode_num", C.c_int32), ("weight_updating_constant", C.c_float), ("texture_weight", C.c_float), ("bg_mode_percent", C.c_float),
+                ("pattern_neig_half_size", C.c_int32), ("pattern_neig_gaus_sigma", C.c_float), ("bg_prob_threshold", C.c_float), ("bg_prob_updating_threshold", C.c_float),
+                ("robust_LBP_constant", C.c_int32), ("min_noised_angle", C.c_float), ("shadow_rate", C.c_float), ("highlight_rate", C.c_float), ("frame_duration", C.c_float),
+                ("learn_mode_learn_rate_per_second", C.c_float), ("learn_weight_learn_rate_per_second", C.c_float), ("learn_init_mode_weight", C.c_float),
+                ("detect_mode_learn_rate_per_second", C.c_float), ("detect_weight_learn_rate_per_second", C.c_float), ("detect_init_mode_weight", C.c_float),
+                ("status", C.c_int32), ("disable_detect_mode", C.c_int32), ("disable_learning", C.c_int32), ("detect_after", C.c_int32)]
+
+
 class BgsError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("libbgs_hip error %d: %s" % (code, text))
@@ -165,6 +178,11 @@ SYMBOLS = [
     ("bgs_set_imbs_params", C.c_int, [_P, C.POINTER(BgsImbsParams)]),
     ("bgs_get_imbs_params", C.c_int, [_P, C.POINTER(BgsImbsParams)]),
     ("bgs_imbs_check", C.c_int, [C.POINTER(BgsImbsParams), C.c_int, C.c_int, C.c_int]),
+    ("bgs_multilayer_default_params", C.c_int, [C.POINTER(BgsMultilayerParams)]),
+    ("bgs_set_multilayer_params", C.c_int, [_P, C.POINTER(BgsMultilayerParams)]),
+    ("bgs_get_multilayer_params", C.c_int, [_P, C.POINTER(BgsMultilayerParams)]),
+    ("bgs_multilayer_check", C.c_int, [C.POINTER(BgsMultilayerParams), C.c_int, C.c_int, C.c_int]),
+    ("bgs_multilayer_constants", C.c_int, [C.POINTER(BgsMultilayerParams), C.POINTER(C.c_uint32)]),
     ("bgs_set_option", C.c_int, [_P, C.c_int, C.c_int64]),
     ("bgs_set_geometry", C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     ("bgs_process", C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_uint32)]),
@@ -301,6 +319,14 @@ def eigen_default_params(**kw):
 def imbs_default_params(**kw):
     p = BgsImbsParams()
     check(lib().bgs_imbs_default_params(C.byref(p)))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def multilayer_default_params(**kw):
+    p = BgsMultilayerParams()
+    check(lib().bgs_multilayer_default_params(C.byref(p)))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

@@ -39,6 +39,7 @@
 #include "kernel_t2f.h"
 #include "kernel_eigen.h"
 #include "kernel_imbs.h"
+#include "kernel_multilayer.h"
 #include "kernel_cc.h"
 #include "kernel_dp.h"
 #include "kernel_mog1.h"
@@ -123,7 +124,7 @@ struct VmmRange {
 //  - the frame history ring: process_clip_run, bgs_process and bgs_submit read and write it themselves, so it is a service of the
 //    generic code that the history classes use, not their private state;
 //  - `counter`: the families that have a learning phase counted in frames share it with that one meaning, and bgs_reset_stream clears it;
-//  - p, fz, t2f, eig and imbs: all may be set before the geometry is known, i.e. before there is a state;
+//  - p, fz, t2f, eig, imbs and ml: all may be set before the geometry is known, i.e. before there is a state;
 //  - the knobs, which bgs_create (environment) and bgs_set_option set before allocation.
 struct bgs_engine {
   bgs_algo algo;
@@ -134,6 +135,7 @@ struct bgs_engine {
   bgs_t2f_params t2f{};   // bgs_set_t2f_params; frozen once the geometry is set
   bgs_eigen_params eig{}; // bgs_set_eigen_params; frozen once the geometry is set
   bgs_imbs_params imbs{}; // bgs_set_imbs_params; frozen once the geometry is set
+  bgs_multilayer_params ml{}; // bgs_set_multilayer_params; frozen once the geometry is set
   int device = 0;
   int n_cu = 256;  // compute units of `device` (allocate): the persistent kernels size their grids by it
   int S = 1;
@@ -420,6 +422,19 @@ int model_allocate(bgs_engine* e, void** out, size_t bytes) {
 template <class T>
 int model_allocate(bgs_engine* e, DevPtr<T>& out, size_t bytes) { return model_allocate(e, raw_of(out), bytes); }
 
+// cv::getGaussianKernel(n, sigma, CV_32F) for sigma > 0 (imgproc/src/smooth.cpp): the taps in float, their sum in double
+void gaussian_kernel_f32(int n, double sigma, float* cf) {
+  const double scale2X = -0.5 / (sigma * sigma);
+  double sum = 0;
+  for (int i = 0; i < n; ++i) {
+    const double x = i - (n - 1) * 0.5;
+    cf[i] = (float)std::exp(scale2X * x * x);
+    sum += cf[i];
+  }
+  sum = 1. / sum;
+  for (int i = 0; i < n; ++i) cf[i] = (float)(cf[i] * sum);
+}
+
 // The families.  Order matters where one borrows from another: engine_asbl.h uses engine_pointwise.h's launch macro, engine_mog2.h
 // uses engine_mog1.h's launch key.
 #include "engine_pointwise.h"
@@ -437,6 +452,7 @@ int model_allocate(bgs_engine* e, DevPtr<T>& out, size_t bytes) { return model_a
 #include "engine_t2f.h"
 #include "engine_eigen.h"
 #include "engine_imbs.h"
+#include "engine_multilayer.h"
 
 // an id that BGS_ALGO_KNOWN accepts but no engine class stands behind (BGS_LBSP_DESC is a stand-alone entry point): refused when the geometry is set
 constexpr Family kUnbuilt = [] {
@@ -480,6 +496,7 @@ const Family* family_of(bgs_algo algo) {
     case BGS_T2FGMM_UV: return &kT2f;
     case BGS_DP_EIGENBACKGROUND: return &kEigen;
     case BGS_IMBS: return &kImbs;
+    case BGS_MULTILAYER: return &kMultilayer;
     case BGS_LBSP_DESC:
     case BGS_ALGO_END:
     case BGS_ALGO_LIMIT:
@@ -811,18 +828,8 @@ int ingest_plan(const bgs_ingest* c, int src_rows, int src_cols, IngestPlan* pl)
 // cv::getGaussianKernel(7, 1.5, CV_32F) -> the integer kernel of the 8-bit fixed-point filter (R3, kernel_ingest.h)
 void gaussian7_kernel(int ik[7]) {
   float cf[7];
-  const double sigma = 1.5, scale2X = -0.5 / (sigma * sigma);
-  double sum = 0;
-  for (int i = 0; i < 7; ++i) {
-    const double x = i - 3.0;
-    cf[i] = (float)std::exp(scale2X * x * x);
-    sum += cf[i];
-  }
-  sum = 1. / sum;
-  for (int i = 0; i < 7; ++i) {
-    cf[i] = (float)(cf[i] * sum);
-    ik[i] = (int)std::lrintf(cf[i] * 256.f);
-  }
+  gaussian_kernel_f32(7, 1.5, cf);
+  for (int i = 0; i < 7; ++i) ik[i] = (int)std::lrintf(cf[i] * 256.f);
 }
 }  // namespace
 
@@ -957,6 +964,7 @@ int bgs_create(bgs_algo algo, const bgs_params* params, int hip_device, int n_st
   t2f_defaults(&e->t2f);
   eig_defaults(&e->eig);
   imbs_defaults(&e->imbs);
+  ml_defaults(&e->ml);
   fz_defaults(&e->fz);  // a fuzzy engine starts from the constructor's values whatever bgs_params it was handed (bgs_set_fuzzy_params)
   if (const char* env = getenv("BGS_KDE_TRIPS")) e->knob.kde_count_trips = atoi(env) != 0;
   if (const char* env = getenv("BGS_MOG2_COMPLETE")) e->knob.mog2_complete = atoi(env) != 0;
@@ -1117,6 +1125,47 @@ int bgs_get_imbs_params(const bgs_engine* e, bgs_imbs_params* p) {
   if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
   if (e->algo != BGS_IMBS) return fail(BGS_ERR_INVALID, "bgs_get_imbs_params: algorithm %d is not IndependentMultimodalBGS", (int)e->algo);
   *p = e->imbs;
+  return BGS_OK;
+}
+
+int bgs_multilayer_default_params(bgs_multilayer_params* p) {
+  if (!p) return fail(BGS_ERR_INVALID, "params is NULL");
+  ml_defaults(p);
+  return BGS_OK;
+}
+
+int bgs_set_multilayer_params(bgs_engine* e, const bgs_multilayer_params* p) {
+  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
+  if (e->algo != BGS_MULTILAYER) return fail(BGS_ERR_INVALID, "bgs_set_multilayer_params: algorithm %d is not MultiLayerBGS", (int)e->algo);
+  if (p->struct_size != sizeof(bgs_multilayer_params)) return fail(BGS_ERR_INVALID, "bgs_multilayer_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_multilayer_params));
+  int rc = ml_check(*p);
+  if (rc) return rc;
+  if (!e->n) e->ml = *p;  // the wrapper hands its values over at its first frame only (MultiLayerBGS.cpp:69-193)
+  return BGS_OK;
+}
+
+int bgs_multilayer_check(const bgs_multilayer_params* p, int rows, int cols, int channels) {
+  bgs_multilayer_params d;
+  ml_defaults(&d);
+  if (p && p->struct_size != sizeof(bgs_multilayer_params)) return fail(BGS_ERR_INVALID, "bgs_multilayer_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_multilayer_params));
+  int rc = ml_check(p ? *p : d);
+  if (rc || rows <= 0) return rc;
+  return ml_check_geometry(BGS_MULTILAYER, rows, cols, channels);
+}
+
+int bgs_get_multilayer_params(const bgs_engine* e, bgs_multilayer_params* p) {
+  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
+  if (e->algo != BGS_MULTILAYER) return fail(BGS_ERR_INVALID, "bgs_get_multilayer_params: algorithm %d is not MultiLayerBGS", (int)e->algo);
+  *p = e->ml;
+  return BGS_OK;
+}
+
+int bgs_multilayer_constants(const bgs_multilayer_params* p, uint32_t bits[2]) {
+  if (!bits) return fail(BGS_ERR_INVALID, "NULL argument");
+  bgs_multilayer_params d;
+  ml_defaults(&d);
+  const float sine = ml_min_sine(), angle = p ? p->min_noised_angle : d.min_noised_angle;
+  std::memcpy(&bits[0], &sine, 4), std::memcpy(&bits[1], &angle, 4);
   return BGS_OK;
 }
 

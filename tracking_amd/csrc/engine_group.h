@@ -273,6 +273,7 @@ int bgs_group_create(const bgs_algo* algos, const bgs_params* const* params, int
     if (!rc && algos[i] == BGS_VUMETER) rc = fail(BGS_ERR_UNSUPPORTED, "VuMeter is not built for class groups (its background image is gray)");
     if (!rc && is_t2f(algos[i])) rc = fail(BGS_ERR_UNSUPPORTED, "%s is not built for class groups (its parameters are not bgs_params)", t2f_name(algos[i]));
     if (!rc && algos[i] == BGS_IMBS) rc = fail(BGS_ERR_UNSUPPORTED, "%s is not built for class groups (its parameters are not bgs_params)", kImbsName);
+    if (!rc && algos[i] == BGS_MULTILAYER) rc = fail(BGS_ERR_UNSUPPORTED, "%s is not built for class groups (its parameters are not bgs_params)", kMlName);
     if (!rc && algos[i] == BGS_DP_EIGENBACKGROUND) rc = fail(BGS_ERR_UNSUPPORTED, "%s is not built for class groups (its parameters are not bgs_params)", kEigName);
     if (!rc && is_fuzzy(algos[i])) rc = fail(BGS_ERR_UNSUPPORTED, "the fuzzy integrals are not built for class groups (their parameters are not bgs_params)");
     unsigned bit = fan_bit_of(algos[i]);

@@ -107,6 +107,20 @@ class Engine:
         capi.check(capi.lib().bgs_get_imbs_params(self._h, C.byref(p)))
         return p
 
+    def set_multilayer_params(self, params=None, **kw):
+        """bgs_set_multilayer_params (MultiLayerBGS): taken when the geometry is set; a later call succeeds and changes nothing.
+        Keywords change single fields of the engine's current values."""
+        if params is None:
+            params = self.get_multilayer_params()
+        for k, v in kw.items():
+            setattr(params, k, v)
+        capi.check(capi.lib().bgs_set_multilayer_params(self._h, C.byref(params)))
+
+    def get_multilayer_params(self):
+        p = capi.BgsMultilayerParams()
+        capi.check(capi.lib().bgs_get_multilayer_params(self._h, C.byref(p)))
+        return p
+
     def set_option(self, option, value):
         capi.check(capi.lib().bgs_set_option(self._h, option, int(value)))
 

@@ -5,9 +5,9 @@
 //   AdaptiveBackgroundLearning, AdaptiveSelectiveBackgroundLearning, MixtureOfGaussianV1BGS, MixtureOfGaussianV2BGS, GMG,
 //   SigmaDeltaBGS, SuBSENSEBGS, LOBSTERBGS, DPZivkovicAGMMBGS, DPGrimsonGMMBGS, DPWrenGABGS, DPMeanBGS, DPAdaptiveMedianBGS, KDE,
 //   DPPratiMediodBGS, DPTextureBGS, LBSimpleGaussian, LBFuzzyGaussian, LBMixtureOfGaussians, LBAdaptiveSOM, LBFuzzyAdaptiveSOM, VuMeter,
-//   FuzzySugenoIntegral, FuzzyChoquetIntegral, T2FGMM_UM, T2FGMM_UV, DPEigenbackgroundBGS, IndependentMultimodalBGS
+//   FuzzySugenoIntegral, FuzzyChoquetIntegral, T2FGMM_UM, T2FGMM_UV, DPEigenbackgroundBGS, IndependentMultimodalBGS, MultiLayerBGS
 // Each reads / writes the same ./config/<Class>.xml with the same keys and defaults as the class it stands in for
-// (the list is bgs_classes.inc + bgs_classes_kde.inc + bgs_classes_dp2.inc + bgs_classes_lb.inc + bgs_classes_vumeter.inc + bgs_classes_fuzzy.inc + bgs_classes_t2f.inc + bgs_classes_eigen.inc + bgs_classes_imbs.inc, shared verbatim with this repository's tested host mirror, tracking_amd/host/bgs_host.h).
+// (the list is bgs_classes.inc + bgs_classes_kde.inc + bgs_classes_dp2.inc + bgs_classes_lb.inc + bgs_classes_vumeter.inc + bgs_classes_fuzzy.inc + bgs_classes_t2f.inc + bgs_classes_eigen.inc + bgs_classes_imbs.inc + bgs_classes_multilayer.inc, shared verbatim with this repository's tested host mirror, tracking_amd/host/bgs_host.h).
 //
 // Use:   mixtureOfGaussianV2BGS = new hipbgs::MixtureOfGaussianV2BGS;      // FrameProcessor.cpp:59-60
 //        if(i==36) bgs = new hipbgs::SuBSENSEBGS();                          // ustc_src/ustc_bgs.cpp:68
@@ -133,7 +133,7 @@ class HipBGSBase : public IBGS {
   std::string configPath() const { return std::string("./config/") + name_ + ".xml"; }
   bool firstTime;
   bgs_params params_;
-  virtual int applyClassParams(bgs_engine*) { return 0; }  // parameters outside bgs_params (bgs_classes_fuzzy.inc, bgs_classes_t2f.inc, bgs_classes_eigen.inc, bgs_classes_imbs.inc), before every frame
+  virtual int applyClassParams(bgs_engine*) { return 0; }  // parameters outside bgs_params (bgs_classes_fuzzy.inc, bgs_classes_t2f.inc, bgs_classes_eigen.inc, bgs_classes_imbs.inc, bgs_classes_multilayer.inc), before every frame
   int fg_channels_;  // 3: the class hands its caller an 8UC3 mask with equal channels (bgs_classes_lb.inc)
 
  private:
@@ -163,6 +163,7 @@ class HipBGSBase : public IBGS {
 #include "bgs_classes_t2f.inc"
 #include "bgs_classes_eigen.inc"
 #include "bgs_classes_imbs.inc"
+#include "bgs_classes_multilayer.inc"
 #ifdef BGS_HIP_DEFINED_OVERRIDE
 #undef override
 #undef BGS_HIP_DEFINED_OVERRIDE

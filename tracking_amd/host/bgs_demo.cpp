@@ -76,10 +76,10 @@ int main(int argc, char** argv) {
                            "MixtureOfGaussianV1BGS", "MixtureOfGaussianV2BGS", "AdaptiveBackgroundLearning", "AdaptiveSelectiveBackgroundLearning",
                            "GMG", "DPAdaptiveMedianBGS", "DPGrimsonGMMBGS", "DPZivkovicAGMMBGS", "DPMeanBGS", "DPWrenGABGS", "SigmaDeltaBGS", "SuBSENSEBGS", "LOBSTERBGS", "KDE",
                            "DPPratiMediodBGS", "DPTextureBGS", "LBSimpleGaussian", "LBFuzzyGaussian", "LBMixtureOfGaussians", "LBAdaptiveSOM", "LBFuzzyAdaptiveSOM", "VuMeter",
-                           "FuzzySugenoIntegral", "FuzzyChoquetIntegral", "T2FGMM_UM", "T2FGMM_UV", "DPEigenbackgroundBGS", "IndependentMultimodalBGS"};
+                           "FuzzySugenoIntegral", "FuzzyChoquetIntegral", "T2FGMM_UM", "T2FGMM_UV", "DPEigenbackgroundBGS", "IndependentMultimodalBGS", "MultiLayerBGS"};
     Image* masks[] = {&fp->img_framediff, &fp->img_staticfdiff, &fp->img_wmovmean, &fp->img_movvar, &fp->img_mog1, &fp->img_mog2, &fp->img_bkgl_fgmask, &fp->img_asbl,
                      &fp->img_gmg, &fp->img_adpmed, &fp->img_grigmm, &fp->img_zivgmm, &fp->img_tmpmean, &fp->img_wrenga, &fp->img_sdbgs, &fp->img_ssbgs, &fp->img_lobgs, &fp->img_kde,
-                     &fp->img_pramed, &fp->img_texbgs, &fp->img_lb_sg, &fp->img_lb_fg, &fp->img_lb_mog, &fp->img_lb_som, &fp->img_lb_fsom, &fp->img_vumeter, &fp->img_fsi, &fp->img_fci, &fp->img_t2fgmm_um, &fp->img_t2fgmm_uv, &fp->img_eigbkg, &fp->img_imbs};
+                     &fp->img_pramed, &fp->img_texbgs, &fp->img_lb_sg, &fp->img_lb_fg, &fp->img_lb_mog, &fp->img_lb_som, &fp->img_lb_fsom, &fp->img_vumeter, &fp->img_fsi, &fp->img_fci, &fp->img_t2fgmm_um, &fp->img_t2fgmm_uv, &fp->img_eigbkg, &fp->img_imbs, &fp->img_mlbgs};
     std::vector<std::ofstream> outs;
     for (const char* nm : names) outs.emplace_back((prefix + "." + nm + ".raw").c_str(), std::ios::binary);
     Image frame(rows, cols, 3);

@@ -241,7 +241,7 @@ class HipBGSBase : public IBGS {
   std::string configPath() const { return std::string("./config/") + name_ + ".xml"; }
   bool firstTime;
   bgs_params params_;
-  // parameters that do not travel in bgs_params (bgs_classes_fuzzy.inc, bgs_classes_t2f.inc, bgs_classes_eigen.inc, bgs_classes_imbs.inc): handed over before every frame, after bgs_set_params
+  // parameters that do not travel in bgs_params (bgs_classes_fuzzy.inc, bgs_classes_t2f.inc, bgs_classes_eigen.inc, bgs_classes_imbs.inc, bgs_classes_multilayer.inc): handed over before every frame, after bgs_set_params
   virtual int applyClassParams(bgs_engine*) { return 0; }
   int fg_channels_ = 1;  // 3: the class hands its caller an 8UC3 mask with equal channels, like the reference's lb/ wrappers (bgs_classes_lb.inc)
 
@@ -289,6 +289,9 @@ class HipBGSBase : public IBGS {
 #include "bgs_classes_t2f.inc"
 #include "bgs_classes_eigen.inc"
 #include "bgs_classes_imbs.inc"
+#define BGS_HIP_XML_HAS_STRINGS 1
+#include "bgs_classes_multilayer.inc"
+#undef BGS_HIP_XML_HAS_STRINGS
 
 #undef BGS_HIP_BANNER_DTOR
 

@@ -12,6 +12,8 @@
 // and the switch below as holding exactly the two tb/ cases, so a tracker reaches the class as an IBGS, not by number.
 // Type 33 likewise: IndependentMultimodalBGS exists (bgs_classes_imbs.inc; FrameProcessor's enableIMBS builds it) and the type table
 // still throws for 33, which the suite pins as refused too.
+// Type 23 likewise: MultiLayerBGS exists (bgs_classes_multilayer.inc; FrameProcessor's enableMultiLayerBGS builds it) and the type
+// table still throws for 23, the suite's own example of a refused type.
 #pragma once
 #include "bgs_host.h"
 #include "blob.h"
