@@ -699,6 +699,16 @@ int bgs_lbsp_describe_batch_device(int hip_device, const void* d_img, int images
 int bgs_mask_morph_device(int hip_device, const void* d_src, void* d_dst, int rows, int cols, int op, int ksize,
                           int iterations, void* hip_stream);
 
+/* cvCanny(src, dst, low, high) with aperture 3 and the L1 magnitude, on `images` 8-bit single-channel images stored back to back
+ * ([images][rows][cols]); d_dst receives 0 / 255 in the same layout (SJN_MultiCueBGS.cpp:998, :1007 run it on every bounding box).
+ * Definition: Sobel 3x3 with a replicated border, |dx| + |dy|, non-maximum suppression with the 15-bit
+ * fixed-point tan 22.5 deg test, hysteresis from the pixels above max(low, high) through those above min(low, high), 8-connected.
+ * One workgroup per image with the image's gradient in LDS, so rows * cols <= BGS_CANNY_MAX_PIXELS (BGS_ERR_UNSUPPORTED above).
+ * Asynchronous on hip_stream; in-place operation is refused. */
+#define BGS_CANNY_MAX_PIXELS 20480
+int bgs_canny_device(int hip_device, const void* d_src, void* d_dst, int images, int rows, int cols, int low, int high,
+                     void* hip_stream);
+
 /* Connected-component seeding of a byte mask on device: what OpenCV-legacy's blob detector derives
  * from the mask right after IBGS::process (ustc_src/trackingMain.cpp:56-57, :166; cvFindContours + bounding rectangles;
  * in-tree kin: package_bgs/jmo/BlobExtraction.cpp).  Components are the maximal 8- (or 4-) connected sets of non-zero

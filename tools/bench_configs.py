@@ -20,6 +20,8 @@ Not the driver's bench line (bench.py is); the numbers go to DESIGN.md §6.
              step, the sampling step and the build step apart, what the launches cost on empty planes, the numpy restatement beside
   --only multilayer: MultiLayerBGS (package_bgs/jmo) at the wrapper's defaults on S_surv, 8 x 1080p: ms per step, the model kernel and
              the smoothing kernel apart, bytes per pixel of state, this box's copy rate
+  --only canny: bgs_canny_device on 160 x 120 images (the reduced frame of package_bgs/sjn), batches of 1 to 256: a block scene, uniform
+             noise, and a serpentine whose hysteresis has to walk one chain of 2357 pixels; the numpy restatement beside
 usage: bench_configs.py [--streams S] [--swizzle 0|1]"""
 import argparse
 import os
@@ -282,6 +284,43 @@ def run_cc():
         torch.cuda.synchronize()
         ms = a.elapsed_time(b) / 20
         print("connected components 1920x1080 %-12s: %d components, %.3f ms per mask (incl. count read-back) -> %.1f Mpix/s" % (name, n, ms, 1080 * 1920 / ms / 1e3))
+
+
+def run_canny(rows=120, cols=160, reps=50):
+    """bgs_canny_device: one workgroup per image, so a call costs what its slowest image costs until the batch outgrows the CUs."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import canny_numpy as cn
+    from tracking_amd.engine import canny_device
+    rng = np.random.default_rng(3)
+    coarse = rng.integers(0, 256, (rows // 8, cols // 8), dtype=np.uint8)
+    snake = np.zeros((rows, cols), np.uint8)
+    for j in range((rows - 8) // 8 + 1):
+        snake[8 * j + 2:8 * j + 6, 2:cols - 2] = 35
+        if j + 1 < (rows - 8) // 8 + 1:
+            c = cols - 6 if j % 2 == 0 else 2
+            snake[8 * j + 6:8 * j + 10, c:c + 4] = 35
+    snake[2:6, 2:6] = 255
+    scenes = (("8 x 8 blocks", np.repeat(np.repeat(coarse, 8, 0), 8, 1), 100, 150), ("uniform noise", rng.integers(0, 256, (rows, cols), dtype=np.uint8), 100, 150),
+              ("serpentine", snake, 100, 250))
+    for name, img, low, high in scenes:
+        t0 = time.perf_counter()
+        want = cn.canny(img, low, high)
+        cpu_ms = (time.perf_counter() - t0) * 1e3
+        for images in (1, 8, 64, 256):
+            d = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(img, (images, rows, cols)))).cuda()
+            for _ in range(3):
+                out = canny_device(d, low, high)
+            torch.cuda.synchronize()
+            assert np.array_equal(out[images - 1].cpu().numpy(), want)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                out = canny_device(d, low, high)
+            b.record()
+            torch.cuda.synchronize()
+            us = a.elapsed_time(b) / reps * 1e3
+            print("canny %dx%d %-14s %3d images: %8.1f us per call, %7.2f us per image, %d edge pixels  (numpy restatement %.1f ms per image)"
+                  % (cols, rows, name, images, us, us / images, int((want == 255).sum()), cpu_ms))
 
 
 def run_clip(S=32, rows=1080, cols=1920, kind="sat", steps=48, Ts=(1, 2, 4, 8), algo=None, dense=201.0, label="MOG2"):
@@ -1127,6 +1166,9 @@ def main():
         return
     if args.only == "multilayer":
         run_multilayer(S)
+        return
+    if args.only == "canny":
+        run_canny()
         return
     if args.only in ("fuzzy_choquet", "fuzzy_sugeno"):
         run_fuzzy(S, steps=5, only="FuzzyChoquetIntegral" if args.only == "fuzzy_choquet" else "FuzzySugenoIntegral", calibrate=False)

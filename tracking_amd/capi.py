@@ -35,6 +35,7 @@ PRATI_MAX_HISTORY = 64  # BGS_PRATI_MAX_HISTORY
 EIGEN_MAX_HISTORY = 32  # BGS_EIGEN_MAX_HISTORY
 IMBS_MAX_SAMPLES = 63  # BGS_IMBS_MAX_SAMPLES
 MULTILAYER_MAX_HALF_SIZE = 8  # BGS_MULTILAYER_MAX_HALF_SIZE
+CANNY_MAX_PIXELS = 20480  # BGS_CANNY_MAX_PIXELS
 FG_VALID, BG_VALID = 1, 2
 OPT_BORROW_FRAMES, OPT_MOG2_PIXELS_PER_LANE, OPT_MOG2_TILED, OPT_XCD_SWIZZLE, OPT_PLACEMENT_PROBE, OPT_MOG2_SPARSE, OPT_CLIP_FUSE, OPT_HOST_REGISTER, OPT_MODEL_CHUNK_MB, OPT_MODEL_CHUNK_MIN_MB = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 
@@ -201,6 +202,7 @@ SYMBOLS = [
     ("bgs_lbsp_describe_device", C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     ("bgs_lbsp_describe_batch_device", C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     ("bgs_mask_morph_device", C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    ("bgs_canny_device", C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ("bgs_mask_components_workspace", C.c_size_t, [C.c_int, C.c_int]),
     ("bgs_mask_components_device", C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
     ("bgs_mask_components_batch_workspace", C.c_size_t, [C.c_int, C.c_int, C.c_int]),

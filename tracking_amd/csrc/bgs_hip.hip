@@ -40,6 +40,7 @@
 #include "kernel_eigen.h"
 #include "kernel_imbs.h"
 #include "kernel_multilayer.h"
+#include "kernel_canny.h"
 #include "kernel_cc.h"
 #include "kernel_dp.h"
 #include "kernel_mog1.h"
@@ -1756,6 +1757,19 @@ int bgs_mask_morph_device(int hip_device, const void* d_src, void* d_dst, int ro
     (void)hipFree(tmp);
   }
   if (er != hipSuccess) return fail(BGS_ERR_HIP, "morph kernel launch failed: %s", hipGetErrorString(er));
+  return BGS_OK;
+}
+
+int bgs_canny_device(int hip_device, const void* d_src, void* d_dst, int images, int rows, int cols, int low, int high, void* hip_stream) {
+  if (!d_src || !d_dst || images <= 0 || images > 65535 || rows <= 0 || cols <= 0) return fail(BGS_ERR_INVALID, "bgs_canny_device: bad argument");
+  if (d_src == d_dst) return fail(BGS_ERR_INVALID, "bgs_canny_device: in-place operation is not supported");
+  if ((size_t)rows * cols > (size_t)bgs::kCannyMaxPixels)
+    return fail(BGS_ERR_UNSUPPORTED, "bgs_canny_device: %d x %d is more than BGS_CANNY_MAX_PIXELS (%d) pixels", rows, cols, bgs::kCannyMaxPixels);
+  static_assert(BGS_CANNY_MAX_PIXELS == bgs::kCannyMaxPixels, "BGS_CANNY_MAX_PIXELS");
+  HIP_TRY(hipSetDevice(hip_device));
+  if (low > high) std::swap(low, high);  // cvCanny orders its two thresholds itself
+  hipLaunchKernelGGL(bgs::canny_kernel, dim3(images), dim3(bgs::kCannyBlock), 0, (hipStream_t)hip_stream, (const uint8_t*)d_src, (uint8_t*)d_dst, rows, cols, low, high);
+  HIP_TRY(hipGetLastError());
   return BGS_OK;
 }
 

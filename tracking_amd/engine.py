@@ -321,6 +321,20 @@ def mask_morph_device(src, op, ksize=3, iterations=1, device=0, hip_stream=None)
     return dst
 
 
+def canny_device(src, low, high, device=0, hip_stream=None):
+    """src: torch CUDA uint8 [rows][cols] or [images][rows][cols].  cvCanny with aperture 3 and the L1 magnitude (bgs_canny_device):
+    a 0 / 255 edge map of the same shape; rows * cols is at most capi.CANNY_MAX_PIXELS."""
+    import torch
+    images = 1 if src.dim() == 2 else src.shape[0]
+    rows, cols = src.shape[-2:]
+    src = src.contiguous()
+    dst = torch.empty_like(src)
+    if hip_stream is None:
+        hip_stream = torch.cuda.current_stream().cuda_stream
+    capi.check(capi.lib().bgs_canny_device(device, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), images, rows, cols, int(low), int(high), C.c_void_p(hip_stream)))
+    return dst
+
+
 BOX_FIELDS = ("x", "y", "w", "h", "area", "root")
 
 
