@@ -195,6 +195,9 @@ def test_refusals_on_the_engine_and_groups():
                 eng.set_fuzzy_params(**kw)
             assert ei.value.code == capi.ERR_UNSUPPORTED and name in str(ei.value)
         assert eng.process(np.zeros((2, 2, 3), np.uint8)) == (None, None)  # still usable, with the values it had
+        with pytest.raises(capi.BgsError) as ei:  # the geometry is set now: a refusal stays a refusal and leaves the values alone
+            eng.set_fuzzy_params(option=3)
+        assert ei.value.code == capi.ERR_UNSUPPORTED and name in str(ei.value) and eng.get_fuzzy_params().option == 2
         eng.close()
     with pytest.raises(capi.BgsError):
         Engine(capi.VUMETER).set_fuzzy_params(option=1)

@@ -4,6 +4,7 @@ This module never computes anything itself and has no CPU path: if the HIP libra
 missing it raises at import of the symbols, and every call into a box without a GPU
 fails with BgsError(BGS_ERR_HIP).
 """
+import collections
 import ctypes as C
 import os
 
@@ -17,13 +18,7 @@ LOBSTER = 17
 KDE = 18
 DP_PRATI_MEDIOD, DP_TEXTURE = 19, 20
 LB_SIMPLE_GAUSSIAN, LB_FUZZY_GAUSSIAN, LB_MOG, LB_ADAPTIVE_SOM, LB_FUZZY_ADAPTIVE_SOM = range(21, 26)
-VUMETER = 27  # id 26 is a permanent hole (BGS_ALGO_END is frozen there); BGS_ALGO_LIMIT = 28  # frozen, and id 28 is the second permanent hole
-FUZZY_SUGENO, FUZZY_CHOQUET = 29, 30  # package_bgs/tb fuzzy integrals; their parameters are BgsFuzzyParams, not BgsParams
-T2FGMM_UM, T2FGMM_UV = 32, 33  # package_bgs/tb type-2 fuzzy GMMs (id 31 is the third hole); their parameters are BgsT2fParams
-DP_EIGENBACKGROUND = 34  # package_bgs/dp PCA background; its parameters are BgsEigenParams
-IMBS = 35  # package_bgs/db IndependentMultimodalBGS; its parameters are BgsImbsParams
-MULTILAYER = 36  # package_bgs/jmo MultiLayerBGS; its parameters are BgsMultilayerParams
-ALGO_LAST = 37  # one past the last id
+VUMETER = 27  # id 26 is a permanent hole (BGS_ALGO_END is frozen there)
 ALGO_LIMIT = 28  # frozen, and id 28 is the second permanent hole
 FUZZY_SUGENO, FUZZY_CHOQUET = 29, 30  # package_bgs/tb fuzzy integrals; their parameters are BgsFuzzyParams, not BgsParams
 T2FGMM_UM, T2FGMM_UV = 32, 33  # package_bgs/tb type-2 fuzzy GMMs (id 31 is the third hole); their parameters are BgsT2fParams
@@ -150,6 +145,23 @@ class BgsMultilayerParams(C.Structure):
                 ("status", C.c_int32), ("disable_detect_mode", C.c_int32), ("disable_learning", C.c_int32), ("detect_after", C.c_int32)]
 
 
+class ParamBlock(collections.namedtuple("ParamBlock", "name struct classes check_takes_algo live")):
+    """A class parameter block of the C ABI: struct bgs_<name>_params with bgs_<name>_default_params, bgs_set_<name>_params,
+    bgs_get_<name>_params and bgs_<name>_check.  check_takes_algo: bgs_<name>_check's first argument is the algorithm (blocks that
+    several classes share).  live: a set after the geometry acts from the next frame on; otherwise it is vetted and changes nothing."""
+
+
+# One row per block.  From it come the blocks' entries of SYMBOLS, <name>_default_params(**kw) below and
+# Engine.set_<name>_params / Engine.get_<name>_params (engine.py).
+PARAM_BLOCKS = [
+    ParamBlock("fuzzy", BgsFuzzyParams, "FUZZY_SUGENO / FUZZY_CHOQUET", True, True),
+    ParamBlock("t2f", BgsT2fParams, "T2FGMM_UM / T2FGMM_UV", True, False),
+    ParamBlock("eigen", BgsEigenParams, "DPEigenbackground", False, False),
+    ParamBlock("imbs", BgsImbsParams, "IndependentMultimodalBGS", False, False),
+    ParamBlock("multilayer", BgsMultilayerParams, "MultiLayerBGS", False, False),
+]
+
+
 class BgsError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("libbgs_hip error %d: %s" % (code, text))
@@ -163,26 +175,6 @@ SYMBOLS = [
     ("bgs_default_params", C.c_int, [C.c_int, C.POINTER(BgsParams)]),
     ("bgs_create", C.c_int, [C.c_int, C.POINTER(BgsParams), C.c_int, C.c_int, C.POINTER(_P)]),
     ("bgs_set_params", C.c_int, [_P, C.POINTER(BgsParams)]),
-    ("bgs_fuzzy_default_params", C.c_int, [C.POINTER(BgsFuzzyParams)]),
-    ("bgs_set_fuzzy_params", C.c_int, [_P, C.POINTER(BgsFuzzyParams)]),
-    ("bgs_get_fuzzy_params", C.c_int, [_P, C.POINTER(BgsFuzzyParams)]),
-    ("bgs_fuzzy_check", C.c_int, [C.c_int, C.POINTER(BgsFuzzyParams), C.c_int, C.c_int, C.c_int]),
-    ("bgs_t2f_default_params", C.c_int, [C.POINTER(BgsT2fParams)]),
-    ("bgs_set_t2f_params", C.c_int, [_P, C.POINTER(BgsT2fParams)]),
-    ("bgs_get_t2f_params", C.c_int, [_P, C.POINTER(BgsT2fParams)]),
-    ("bgs_t2f_check", C.c_int, [C.c_int, C.POINTER(BgsT2fParams), C.c_int, C.c_int, C.c_int]),
-    ("bgs_eigen_default_params", C.c_int, [C.POINTER(BgsEigenParams)]),
-    ("bgs_set_eigen_params", C.c_int, [_P, C.POINTER(BgsEigenParams)]),
-    ("bgs_get_eigen_params", C.c_int, [_P, C.POINTER(BgsEigenParams)]),
-    ("bgs_eigen_check", C.c_int, [C.POINTER(BgsEigenParams), C.c_int, C.c_int, C.c_int]),
-    ("bgs_imbs_default_params", C.c_int, [C.POINTER(BgsImbsParams)]),
-    ("bgs_set_imbs_params", C.c_int, [_P, C.POINTER(BgsImbsParams)]),
-    ("bgs_get_imbs_params", C.c_int, [_P, C.POINTER(BgsImbsParams)]),
-    ("bgs_imbs_check", C.c_int, [C.POINTER(BgsImbsParams), C.c_int, C.c_int, C.c_int]),
-    ("bgs_multilayer_default_params", C.c_int, [C.POINTER(BgsMultilayerParams)]),
-    ("bgs_set_multilayer_params", C.c_int, [_P, C.POINTER(BgsMultilayerParams)]),
-    ("bgs_get_multilayer_params", C.c_int, [_P, C.POINTER(BgsMultilayerParams)]),
-    ("bgs_multilayer_check", C.c_int, [C.POINTER(BgsMultilayerParams), C.c_int, C.c_int, C.c_int]),
     ("bgs_multilayer_constants", C.c_int, [C.POINTER(BgsMultilayerParams), C.POINTER(C.c_uint32)]),
     ("bgs_set_option", C.c_int, [_P, C.c_int, C.c_int64]),
     ("bgs_set_geometry", C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
@@ -234,6 +226,13 @@ SYMBOLS = [
     ("bgs_stream_flags", C.c_int, [_P, C.c_int, C.POINTER(C.c_uint32)]),
     ("bgs_last_mask_blobs", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_int32)]),
 ]
+for _b in PARAM_BLOCKS:
+    SYMBOLS += [
+        ("bgs_%s_default_params" % _b.name, C.c_int, [C.POINTER(_b.struct)]),
+        ("bgs_set_%s_params" % _b.name, C.c_int, [_P, C.POINTER(_b.struct)]),
+        ("bgs_get_%s_params" % _b.name, C.c_int, [_P, C.POINTER(_b.struct)]),
+        ("bgs_%s_check" % _b.name, C.c_int, ([C.c_int] if _b.check_takes_algo else []) + [C.POINTER(_b.struct), C.c_int, C.c_int, C.c_int]),
+    ]
 
 _lib = None
 
@@ -294,44 +293,21 @@ def default_params(algo):
     return p
 
 
-def fuzzy_default_params(**kw):
-    p = BgsFuzzyParams()
-    check(lib().bgs_fuzzy_default_params(C.byref(p)))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+def _block_default_params(b):
+    def default_params(**kw):
+        p = b.struct()
+        check(getattr(lib(), "bgs_%s_default_params" % b.name)(C.byref(p)))
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+    default_params.__name__ = default_params.__qualname__ = "%s_default_params" % b.name
+    default_params.__doc__ = "bgs_%s_default_params (%s); keywords change single fields of the defaults." % (b.name, b.classes)
+    return default_params
 
 
-def t2f_default_params(**kw):
-    p = BgsT2fParams()
-    check(lib().bgs_t2f_default_params(C.byref(p)))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def eigen_default_params(**kw):
-    p = BgsEigenParams()
-    check(lib().bgs_eigen_default_params(C.byref(p)))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def imbs_default_params(**kw):
-    p = BgsImbsParams()
-    check(lib().bgs_imbs_default_params(C.byref(p)))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def multilayer_default_params(**kw):
-    p = BgsMultilayerParams()
-    check(lib().bgs_multilayer_default_params(C.byref(p)))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+# fuzzy_default_params, t2f_default_params, eigen_default_params, imbs_default_params, multilayer_default_params
+for _b in PARAM_BLOCKS:
+    globals()["%s_default_params" % _b.name] = _block_default_params(_b)
 
 
 def calibrate_copy(device, nbytes, chunk_mb, iters=5):

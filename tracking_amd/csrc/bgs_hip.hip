@@ -125,18 +125,19 @@ struct VmmRange {
 //  - the frame history ring: process_clip_run, bgs_process and bgs_submit read and write it themselves, so it is a service of the
 //    generic code that the history classes use, not their private state;
 //  - `counter`: the families that have a learning phase counted in frames share it with that one meaning, and bgs_reset_stream clears it;
-//  - p, fz, t2f, eig, imbs and ml: all may be set before the geometry is known, i.e. before there is a state;
+//  - p and the class parameter blocks (one member per ParamBlock constant of an engine_*.h, which says who owns it and whether it
+//    is live or frozen once the geometry is set): all may be set before the geometry is known, i.e. before there is a state;
 //  - the knobs, which bgs_create (environment) and bgs_set_option set before allocation.
 struct bgs_engine {
   bgs_algo algo;
   const Family* fam = nullptr;  // the class's entry points (family_of)
   std::unique_ptr<FamilyState> model;  // the class's state (null until the geometry is set, and for the frame history classes)
   bgs_params p;
-  bgs_fuzzy_params fz{};  // bgs_set_fuzzy_params
-  bgs_t2f_params t2f{};   // bgs_set_t2f_params; frozen once the geometry is set
-  bgs_eigen_params eig{}; // bgs_set_eigen_params; frozen once the geometry is set
-  bgs_imbs_params imbs{}; // bgs_set_imbs_params; frozen once the geometry is set
-  bgs_multilayer_params ml{}; // bgs_set_multilayer_params; frozen once the geometry is set
+  bgs_fuzzy_params fz{};       // kFuzzyBlock
+  bgs_t2f_params t2f{};        // kT2fBlock
+  bgs_eigen_params eig{};      // kEigenBlock
+  bgs_imbs_params imbs{};      // kImbsBlock
+  bgs_multilayer_params ml{};  // kMultilayerBlock
   int device = 0;
   int n_cu = 256;  // compute units of `device` (allocate): the persistent kernels size their grids by it
   int S = 1;
@@ -218,7 +219,8 @@ namespace {
 
 // What a class of background model plugs into the engine: one constant of this per family at the end of its engine_*.h, found by
 // family_of().  `first`, `count`: a run of streams that share every kernel argument (launch_key); d_* point at the run's first
-// stream.  Entries marked nullable may stay null.
+// stream.  Entries marked nullable may stay null.  A family whose parameters are not bgs_params puts a ParamBlock constant (below)
+// beside it.
 struct Family {
   int (*check)(bgs_algo, const bgs_params&);                      // nullable; needs no device (bgs_create, bgs_set_params)
   int (*check_geometry)(bgs_algo, int rows, int cols, int ch);    // nullable; refusals made before the device is opened
@@ -238,6 +240,72 @@ struct Family {
   int bg_channels;        // channels of the background image the class hands out: 0 = as the frames, 1 = gray
   bool per_stream_flags;  // run writes e->last_flags[first..first+count) itself and returns their AND (streams of one launch differ)
 };
+
+const Family* family_of(bgs_algo algo);  // below
+
+// The parameters of a class that do not fit in bgs_params are a block of its own: an ABI struct P that begins with struct_size, held
+// by the engine as `member`.  Its family describes it once, in one constant of this next to its Family; the four entry points of the
+// block (bgs_<x>_default_params, bgs_set_<x>_params, bgs_get_<x>_params, bgs_<x>_check) are block_default / block_set / block_get /
+// block_check on that constant, and for_each_block lists it for bgs_create and bgs_group_create.
+template <class P>
+struct ParamBlock {
+  P bgs_engine::*member;
+  const Family* fam;        // the block belongs to the classes of this family
+  const char* struct_name;  // of P, for the struct_size refusal
+  const char* class_name;   // of the owning classes, for the wrong-class refusal
+  void (*defaults)(P*);
+  int (*check)(bgs_algo, const P&);  // needs no device; the geometry refusals are fam->check_geometry
+  bool live;  // a set after the geometry: true = acts from the next frame on, false = vetted, then ignored (the model keeps what it was built with)
+};
+
+// what the caller handed in, or the block's defaults (kept in d) for NULL; null after refusing a struct of another size
+template <class P>
+const P* block_arg(const ParamBlock<P>& b, const P* p, P& d) {
+  if (!p) return b.defaults(&d), &d;
+  if (p->struct_size != sizeof(P)) return fail(BGS_ERR_INVALID, "%s.struct_size %u != %zu (ABI mismatch)", b.struct_name, p->struct_size, sizeof(P)), nullptr;
+  return p;
+}
+
+// the refusals that need no engine, in the order the ABI promises: wrong class, struct_size, the family's check
+template <class P>
+int block_vet(const ParamBlock<P>& b, const char* fn, bgs_algo algo, const P* p) {
+  if (family_of(algo) != b.fam) return fail(BGS_ERR_INVALID, "%s: algorithm %d is not %s", fn, (int)algo, b.class_name);
+  P d;
+  p = block_arg(b, p, d);
+  return p ? b.check(algo, *p) : BGS_ERR_INVALID;
+}
+
+template <class P>
+int block_default(const ParamBlock<P>& b, P* p) {
+  if (!p) return fail(BGS_ERR_INVALID, "params is NULL");
+  b.defaults(p);
+  return BGS_OK;
+}
+
+template <class P>
+int block_set(const ParamBlock<P>& b, const char* fn, bgs_engine* e, const P* p) {
+  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
+  int rc = block_vet(b, fn, e->algo, p);
+  if (rc) return rc;
+  if (b.live || !e->n) e->*b.member = *p;
+  return BGS_OK;
+}
+
+template <class P>
+int block_get(const ParamBlock<P>& b, const char* fn, const bgs_engine* e, P* p) {
+  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
+  if (e->fam != b.fam) return fail(BGS_ERR_INVALID, "%s: algorithm %d is not %s", fn, (int)e->algo, b.class_name);
+  *p = e->*b.member;
+  return BGS_OK;
+}
+
+// p NULL: the defaults; rows <= 0: the parameters alone
+template <class P>
+int block_check(const ParamBlock<P>& b, const char* fn, bgs_algo algo, const P* p, int rows, int cols, int ch) {
+  int rc = block_vet(b, fn, algo, p);
+  if (rc || rows <= 0 || !b.fam->check_geometry) return rc;
+  return b.fam->check_geometry(algo, rows, cols, ch);
+}
 
 void vmm_free(VmmRange& v);  // below
 
@@ -504,6 +572,12 @@ const Family* family_of(bgs_algo algo) {
     case BGS_ALGO_LAST: break;
   }
   return &kUnbuilt;
+}
+
+// Every class parameter block: bgs_create sets each to its defaults, bgs_group_create refuses the classes that own one.
+template <class F>
+void for_each_block(F f) {
+  f(kFuzzyBlock), f(kT2fBlock), f(kEigenBlock), f(kImbsBlock), f(kMultilayerBlock);
 }
 
 void free_all(bgs_engine* e) {
@@ -962,11 +1036,7 @@ int bgs_create(bgs_algo algo, const bgs_params* params, int hip_device, int n_st
   e->lanes.assign(n_streams, bgs_engine::Lane());
   e->last_flags.assign(n_streams, 0);
   e->counter.assign(n_streams, 0);
-  t2f_defaults(&e->t2f);
-  eig_defaults(&e->eig);
-  imbs_defaults(&e->imbs);
-  ml_defaults(&e->ml);
-  fz_defaults(&e->fz);  // a fuzzy engine starts from the constructor's values whatever bgs_params it was handed (bgs_set_fuzzy_params)
+  for_each_block([e](const auto& b) { b.defaults(&(e->*b.member)); });  // a class with a block of its own starts from the constructor's values whatever bgs_params it was handed
   if (const char* env = getenv("BGS_KDE_TRIPS")) e->knob.kde_count_trips = atoi(env) != 0;
   if (const char* env = getenv("BGS_MOG2_COMPLETE")) e->knob.mog2_complete = atoi(env) != 0;
   if (const char* env = getenv("BGS_LB_PX")) e->knob.lb_px = atoi(env) == 2 ? 2 : 1;
@@ -999,173 +1069,38 @@ int bgs_set_params(bgs_engine* e, const bgs_params* params) {
   return BGS_OK;
 }
 
-int bgs_fuzzy_default_params(bgs_fuzzy_params* p) {
-  if (!p) return fail(BGS_ERR_INVALID, "params is NULL");
-  fz_defaults(p);
-  return BGS_OK;
-}
+// The class parameter blocks: each entry point names its block (ParamBlock, block_*).
+int bgs_fuzzy_default_params(bgs_fuzzy_params* p) { return block_default(kFuzzyBlock, p); }
+int bgs_set_fuzzy_params(bgs_engine* e, const bgs_fuzzy_params* p) { return block_set(kFuzzyBlock, __func__, e, p); }
+int bgs_get_fuzzy_params(const bgs_engine* e, bgs_fuzzy_params* p) { return block_get(kFuzzyBlock, __func__, e, p); }
+int bgs_fuzzy_check(bgs_algo algo, const bgs_fuzzy_params* p, int rows, int cols, int channels) { return block_check(kFuzzyBlock, __func__, algo, p, rows, cols, channels); }
 
-int bgs_set_fuzzy_params(bgs_engine* e, const bgs_fuzzy_params* p) {
-  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
-  if (!is_fuzzy(e->algo)) return fail(BGS_ERR_INVALID, "bgs_set_fuzzy_params: algorithm %d is not a fuzzy integral", (int)e->algo);
-  if (p->struct_size != sizeof(bgs_fuzzy_params)) return fail(BGS_ERR_INVALID, "bgs_fuzzy_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_fuzzy_params));
-  int rc = fz_check(e->algo, *p);
-  if (rc) return rc;
-  e->fz = *p;  // all seven are live: the host fills the launch arguments of the next frame from them
-  return BGS_OK;
-}
+int bgs_t2f_default_params(bgs_t2f_params* p) { return block_default(kT2fBlock, p); }
+int bgs_set_t2f_params(bgs_engine* e, const bgs_t2f_params* p) { return block_set(kT2fBlock, __func__, e, p); }
+int bgs_get_t2f_params(const bgs_engine* e, bgs_t2f_params* p) { return block_get(kT2fBlock, __func__, e, p); }
+int bgs_t2f_check(bgs_algo algo, const bgs_t2f_params* p, int rows, int cols, int channels) { return block_check(kT2fBlock, __func__, algo, p, rows, cols, channels); }
 
-int bgs_fuzzy_check(bgs_algo algo, const bgs_fuzzy_params* p, int rows, int cols, int channels) {
-  if (!is_fuzzy(algo)) return fail(BGS_ERR_INVALID, "bgs_fuzzy_check: algorithm %d is not a fuzzy integral", (int)algo);
-  bgs_fuzzy_params d;
-  fz_defaults(&d);
-  if (p && p->struct_size != sizeof(bgs_fuzzy_params)) return fail(BGS_ERR_INVALID, "bgs_fuzzy_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_fuzzy_params));
-  int rc = fz_check(algo, p ? *p : d);
-  if (rc || rows <= 0) return rc;
-  return fz_check_geometry(algo, rows, cols, channels);
-}
+int bgs_eigen_default_params(bgs_eigen_params* p) { return block_default(kEigenBlock, p); }
+int bgs_set_eigen_params(bgs_engine* e, const bgs_eigen_params* p) { return block_set(kEigenBlock, __func__, e, p); }
+int bgs_get_eigen_params(const bgs_engine* e, bgs_eigen_params* p) { return block_get(kEigenBlock, __func__, e, p); }
+int bgs_eigen_check(const bgs_eigen_params* p, int rows, int cols, int channels) { return block_check(kEigenBlock, __func__, BGS_DP_EIGENBACKGROUND, p, rows, cols, channels); }
 
-int bgs_get_fuzzy_params(const bgs_engine* e, bgs_fuzzy_params* p) {
-  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
-  if (!is_fuzzy(e->algo)) return fail(BGS_ERR_INVALID, "bgs_get_fuzzy_params: algorithm %d is not a fuzzy integral", (int)e->algo);
-  *p = e->fz;
-  return BGS_OK;
-}
+int bgs_imbs_default_params(bgs_imbs_params* p) { return block_default(kImbsBlock, p); }
+int bgs_set_imbs_params(bgs_engine* e, const bgs_imbs_params* p) { return block_set(kImbsBlock, __func__, e, p); }
+int bgs_get_imbs_params(const bgs_engine* e, bgs_imbs_params* p) { return block_get(kImbsBlock, __func__, e, p); }
+int bgs_imbs_check(const bgs_imbs_params* p, int rows, int cols, int channels) { return block_check(kImbsBlock, __func__, BGS_IMBS, p, rows, cols, channels); }
 
-int bgs_t2f_default_params(bgs_t2f_params* p) {
-  if (!p) return fail(BGS_ERR_INVALID, "params is NULL");
-  t2f_defaults(p);
-  return BGS_OK;
-}
-
-int bgs_set_t2f_params(bgs_engine* e, const bgs_t2f_params* p) {
-  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
-  if (!is_t2f(e->algo)) return fail(BGS_ERR_INVALID, "bgs_set_t2f_params: algorithm %d is not T2FGMM_UM / T2FGMM_UV", (int)e->algo);
-  if (p->struct_size != sizeof(bgs_t2f_params)) return fail(BGS_ERR_INVALID, "bgs_t2f_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_t2f_params));
-  int rc = t2f_check(e->algo, *p);
-  if (rc) return rc;
-  if (!e->n) e->t2f = *p;  // the model object exists once the geometry is set: it keeps what it was built with (T2FGMM_UM.cpp `if(firstTime)`)
-  return BGS_OK;
-}
-
-int bgs_t2f_check(bgs_algo algo, const bgs_t2f_params* p, int rows, int cols, int channels) {
-  if (!is_t2f(algo)) return fail(BGS_ERR_INVALID, "bgs_t2f_check: algorithm %d is not T2FGMM_UM / T2FGMM_UV", (int)algo);
-  bgs_t2f_params d;
-  t2f_defaults(&d);
-  if (p && p->struct_size != sizeof(bgs_t2f_params)) return fail(BGS_ERR_INVALID, "bgs_t2f_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_t2f_params));
-  int rc = t2f_check(algo, p ? *p : d);
-  if (rc || rows <= 0) return rc;
-  return t2f_check_geometry(algo, rows, cols, channels);
-}
-
-int bgs_get_t2f_params(const bgs_engine* e, bgs_t2f_params* p) {
-  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
-  if (!is_t2f(e->algo)) return fail(BGS_ERR_INVALID, "bgs_get_t2f_params: algorithm %d is not T2FGMM_UM / T2FGMM_UV", (int)e->algo);
-  *p = e->t2f;
-  return BGS_OK;
-}
-
-int bgs_eigen_default_params(bgs_eigen_params* p) {
-  if (!p) return fail(BGS_ERR_INVALID, "params is NULL");
-  eig_defaults(p);
-  return BGS_OK;
-}
-
-int bgs_set_eigen_params(bgs_engine* e, const bgs_eigen_params* p) {
-  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
-  if (e->algo != BGS_DP_EIGENBACKGROUND) return fail(BGS_ERR_INVALID, "bgs_set_eigen_params: algorithm %d is not DPEigenbackground", (int)e->algo);
-  if (p->struct_size != sizeof(bgs_eigen_params)) return fail(BGS_ERR_INVALID, "bgs_eigen_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_eigen_params));
-  int rc = eig_check(*p);
-  if (rc) return rc;
-  if (!e->n) e->eig = *p;  // the params object is filled once, on the first frame: it keeps what it was given (DPEigenbackgroundBGS.cpp `if(firstTime)`)
-  return BGS_OK;
-}
-
-int bgs_eigen_check(const bgs_eigen_params* p, int rows, int cols, int channels) {
-  bgs_eigen_params d;
-  eig_defaults(&d);
-  if (p && p->struct_size != sizeof(bgs_eigen_params)) return fail(BGS_ERR_INVALID, "bgs_eigen_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_eigen_params));
-  int rc = eig_check(p ? *p : d);
-  if (rc || rows <= 0) return rc;
-  return eig_check_geometry(BGS_DP_EIGENBACKGROUND, rows, cols, channels);
-}
-
-int bgs_get_eigen_params(const bgs_engine* e, bgs_eigen_params* p) {
-  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
-  if (e->algo != BGS_DP_EIGENBACKGROUND) return fail(BGS_ERR_INVALID, "bgs_get_eigen_params: algorithm %d is not DPEigenbackground", (int)e->algo);
-  *p = e->eig;
-  return BGS_OK;
-}
-
-int bgs_imbs_default_params(bgs_imbs_params* p) {
-  if (!p) return fail(BGS_ERR_INVALID, "params is NULL");
-  imbs_defaults(p);
-  return BGS_OK;
-}
-
-int bgs_set_imbs_params(bgs_engine* e, const bgs_imbs_params* p) {
-  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
-  if (e->algo != BGS_IMBS) return fail(BGS_ERR_INVALID, "bgs_set_imbs_params: algorithm %d is not IndependentMultimodalBGS", (int)e->algo);
-  if (p->struct_size != sizeof(bgs_imbs_params)) return fail(BGS_ERR_INVALID, "bgs_imbs_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_imbs_params));
-  int rc = imbs_check(*p);
-  if (rc) return rc;
-  if (!e->n) e->imbs = *p;  // the model sizes its arrays at its first frame (initialize) and the wrapper never constructs it again
-  return BGS_OK;
-}
-
-int bgs_imbs_check(const bgs_imbs_params* p, int rows, int cols, int channels) {
-  bgs_imbs_params d;
-  imbs_defaults(&d);
-  if (p && p->struct_size != sizeof(bgs_imbs_params)) return fail(BGS_ERR_INVALID, "bgs_imbs_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_imbs_params));
-  int rc = imbs_check(p ? *p : d);
-  if (rc || rows <= 0) return rc;
-  return imbs_check_geometry(BGS_IMBS, rows, cols, channels);
-}
-
-int bgs_get_imbs_params(const bgs_engine* e, bgs_imbs_params* p) {
-  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
-  if (e->algo != BGS_IMBS) return fail(BGS_ERR_INVALID, "bgs_get_imbs_params: algorithm %d is not IndependentMultimodalBGS", (int)e->algo);
-  *p = e->imbs;
-  return BGS_OK;
-}
-
-int bgs_multilayer_default_params(bgs_multilayer_params* p) {
-  if (!p) return fail(BGS_ERR_INVALID, "params is NULL");
-  ml_defaults(p);
-  return BGS_OK;
-}
-
-int bgs_set_multilayer_params(bgs_engine* e, const bgs_multilayer_params* p) {
-  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
-  if (e->algo != BGS_MULTILAYER) return fail(BGS_ERR_INVALID, "bgs_set_multilayer_params: algorithm %d is not MultiLayerBGS", (int)e->algo);
-  if (p->struct_size != sizeof(bgs_multilayer_params)) return fail(BGS_ERR_INVALID, "bgs_multilayer_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_multilayer_params));
-  int rc = ml_check(*p);
-  if (rc) return rc;
-  if (!e->n) e->ml = *p;  // the wrapper hands its values over at its first frame only (MultiLayerBGS.cpp:69-193)
-  return BGS_OK;
-}
-
-int bgs_multilayer_check(const bgs_multilayer_params* p, int rows, int cols, int channels) {
-  bgs_multilayer_params d;
-  ml_defaults(&d);
-  if (p && p->struct_size != sizeof(bgs_multilayer_params)) return fail(BGS_ERR_INVALID, "bgs_multilayer_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(bgs_multilayer_params));
-  int rc = ml_check(p ? *p : d);
-  if (rc || rows <= 0) return rc;
-  return ml_check_geometry(BGS_MULTILAYER, rows, cols, channels);
-}
-
-int bgs_get_multilayer_params(const bgs_engine* e, bgs_multilayer_params* p) {
-  if (!e || !p) return fail(BGS_ERR_INVALID, "NULL argument");
-  if (e->algo != BGS_MULTILAYER) return fail(BGS_ERR_INVALID, "bgs_get_multilayer_params: algorithm %d is not MultiLayerBGS", (int)e->algo);
-  *p = e->ml;
-  return BGS_OK;
-}
+int bgs_multilayer_default_params(bgs_multilayer_params* p) { return block_default(kMultilayerBlock, p); }
+int bgs_set_multilayer_params(bgs_engine* e, const bgs_multilayer_params* p) { return block_set(kMultilayerBlock, __func__, e, p); }
+int bgs_get_multilayer_params(const bgs_engine* e, bgs_multilayer_params* p) { return block_get(kMultilayerBlock, __func__, e, p); }
+int bgs_multilayer_check(const bgs_multilayer_params* p, int rows, int cols, int channels) { return block_check(kMultilayerBlock, __func__, BGS_MULTILAYER, p, rows, cols, channels); }
 
 int bgs_multilayer_constants(const bgs_multilayer_params* p, uint32_t bits[2]) {
   if (!bits) return fail(BGS_ERR_INVALID, "NULL argument");
   bgs_multilayer_params d;
-  ml_defaults(&d);
-  const float sine = ml_min_sine(), angle = p ? p->min_noised_angle : d.min_noised_angle;
+  p = block_arg(kMultilayerBlock, p, d);
+  if (!p) return BGS_ERR_INVALID;
+  const float sine = ml_min_sine(), angle = p->min_noised_angle;
   std::memcpy(&bits[0], &sine, 4), std::memcpy(&bits[1], &angle, 4);
   return BGS_OK;
 }

@@ -27,7 +27,7 @@ void eig_defaults(bgs_eigen_params* p) {  // DPEigenbackgroundBGS.cpp:19
 }
 
 // Needs no device: checked before the GPU is opened.
-int eig_check(const bgs_eigen_params& p) {
+int eig_check(bgs_algo, const bgs_eigen_params& p) {
   if (p.history_size < 2 || p.history_size > BGS_EIGEN_MAX_HISTORY)
     return fail(BGS_ERR_UNSUPPORTED, "%s: historySize %d is outside 2..%d", kEigName, p.history_size, BGS_EIGEN_MAX_HISTORY);
   // centred data has rank <= H - 1: at embeddedDim == historySize the reference projects onto a normalised rounding residue, above it OpenCV asserts
@@ -146,3 +146,5 @@ constexpr Family kEigen = [] {
   f.check_geometry = eig_check_geometry, f.allocate = eig_allocate, f.key = eig_key, f.run = eig_run, f.get_state = eig_get_state;
   return f;
 }();
+// frozen: the params object is filled once, on the first frame, and keeps what it was given (DPEigenbackgroundBGS.cpp `if(firstTime)`)
+constexpr ParamBlock<bgs_eigen_params> kEigenBlock{&bgs_engine::eig, &kEigen, "bgs_eigen_params", kEigName, eig_defaults, eig_check, false};

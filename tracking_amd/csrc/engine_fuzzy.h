@@ -18,7 +18,6 @@ struct FuzzyState : FamilyState {
 };
 FuzzyState& fz_of(const bgs_engine* e) { return state_of<FuzzyState>(e); }
 
-bool is_fuzzy(bgs_algo a) { return a == BGS_FUZZY_SUGENO || a == BGS_FUZZY_CHOQUET; }
 const char* fz_name(bgs_algo a) { return a == BGS_FUZZY_SUGENO ? "FuzzySugenoIntegral" : "FuzzyChoquetIntegral"; }
 
 void fz_defaults(bgs_fuzzy_params* p) {  // Fuzzy*Integral.cpp:20-21
@@ -162,3 +161,5 @@ constexpr Family kFuzzy = [] {
   f.reset_stream = fz_reset_stream, f.needs_byte_mask = always, f.per_stream_flags = true;
   return f;
 }();
+// live: all seven act on the next frame, the host fills its launch arguments from them
+constexpr ParamBlock<bgs_fuzzy_params> kFuzzyBlock{&bgs_engine::fz, &kFuzzy, "bgs_fuzzy_params", "FuzzySugenoIntegral / FuzzyChoquetIntegral", fz_defaults, fz_check, true};

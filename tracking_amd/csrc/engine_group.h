@@ -271,11 +271,10 @@ int bgs_group_create(const bgs_algo* algos, const bgs_params* const* params, int
       else p = *params[i];
     }
     if (!rc && algos[i] == BGS_VUMETER) rc = fail(BGS_ERR_UNSUPPORTED, "VuMeter is not built for class groups (its background image is gray)");
-    if (!rc && is_t2f(algos[i])) rc = fail(BGS_ERR_UNSUPPORTED, "%s is not built for class groups (its parameters are not bgs_params)", t2f_name(algos[i]));
-    if (!rc && algos[i] == BGS_IMBS) rc = fail(BGS_ERR_UNSUPPORTED, "%s is not built for class groups (its parameters are not bgs_params)", kImbsName);
-    if (!rc && algos[i] == BGS_MULTILAYER) rc = fail(BGS_ERR_UNSUPPORTED, "%s is not built for class groups (its parameters are not bgs_params)", kMlName);
-    if (!rc && algos[i] == BGS_DP_EIGENBACKGROUND) rc = fail(BGS_ERR_UNSUPPORTED, "%s is not built for class groups (its parameters are not bgs_params)", kEigName);
-    if (!rc && is_fuzzy(algos[i])) rc = fail(BGS_ERR_UNSUPPORTED, "the fuzzy integrals are not built for class groups (their parameters are not bgs_params)");
+    if (!rc)  // a class with a parameter block of its own: a group carries bgs_params only
+      for_each_block([&](const auto& b) {
+        if (family_of(algos[i]) == b.fam) rc = fail(BGS_ERR_UNSUPPORTED, "%s is not built for class groups (its parameters are %s, not bgs_params)", b.class_name, b.struct_name);
+      });
     unsigned bit = fan_bit_of(algos[i]);
     if (bit & g->fused) bit = 0;  // a second instance of a fused class runs as a member engine
     bgs_engine* m = nullptr;

@@ -25,7 +25,7 @@ void imbs_defaults(bgs_imbs_params* p) {  // imbs.hpp:43-56, fps as IndependentM
 }
 
 // Needs no device: checked before the GPU is opened.
-int imbs_check(const bgs_imbs_params& p) {
+int imbs_check(bgs_algo, const bgs_imbs_params& p) {
   if (!(p.fps > 0) || !std::isfinite(p.fps))
     return fail(BGS_ERR_UNSUPPORTED, "%s: fps %g must be finite and above 0 (fps 0 is wall-clock time in the reference, which cannot be reproduced)", kImbsName, p.fps);
   if (p.minBinHeight == 0) return fail(BGS_ERR_UNSUPPORTED, "%s: minBinHeight 0 (the reference divides by it in initialize before its own clamp)", kImbsName);
@@ -181,3 +181,5 @@ constexpr Family kImbs = [] {
   f.needs_byte_mask = always;
   return f;
 }();
+// frozen: the model sizes its arrays at its first frame (initialize) and the wrapper never constructs it again
+constexpr ParamBlock<bgs_imbs_params> kImbsBlock{&bgs_engine::imbs, &kImbs, "bgs_imbs_params", kImbsName, imbs_defaults, imbs_check, false};

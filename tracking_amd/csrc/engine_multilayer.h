@@ -38,7 +38,7 @@ float ml_min_sine() {
 }
 
 // Needs no device: checked before the GPU is opened.
-int ml_check(const bgs_multilayer_params& p) {
+int ml_check(bgs_algo, const bgs_multilayer_params& p) {
   const float fl[] = {p.weight_updating_constant, p.texture_weight, p.bg_mode_percent, p.pattern_neig_gaus_sigma, p.bg_prob_threshold, p.bg_prob_updating_threshold,
                       p.min_noised_angle, p.shadow_rate, p.highlight_rate, p.frame_duration, p.learn_mode_learn_rate_per_second, p.learn_weight_learn_rate_per_second,
                       p.learn_init_mode_weight, p.detect_mode_learn_rate_per_second, p.detect_weight_learn_rate_per_second, p.detect_init_mode_weight};
@@ -168,3 +168,5 @@ constexpr Family kMultilayer = [] {
   f.needs_byte_mask = always;
   return f;
 }();
+// frozen: the wrapper hands its values over at its first frame only (MultiLayerBGS.cpp:69-193)
+constexpr ParamBlock<bgs_multilayer_params> kMultilayerBlock{&bgs_engine::ml, &kMultilayer, "bgs_multilayer_params", kMlName, ml_defaults, ml_check, false};

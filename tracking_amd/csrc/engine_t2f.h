@@ -14,7 +14,6 @@ struct T2fState : FamilyState {
 };
 T2fState& t2f_of(const bgs_engine* e) { return state_of<T2fState>(e); }
 
-bool is_t2f(bgs_algo a) { return a == BGS_T2FGMM_UM || a == BGS_T2FGMM_UV; }
 const char* t2f_name(bgs_algo a) { return a == BGS_T2FGMM_UM ? "T2FGMM_UM" : "T2FGMM_UV"; }
 
 void t2f_defaults(bgs_t2f_params* p) {  // T2FGMM_UM.cpp:19, T2FGMM_UV.cpp:19
@@ -108,3 +107,5 @@ constexpr Family kT2f = [] {
   f.clip_fused = t2f_clip_fused;
   return f;
 }();
+// frozen: the model object exists once the geometry is set and keeps what it was built with (T2FGMM_UM.cpp `if(firstTime)`)
+constexpr ParamBlock<bgs_t2f_params> kT2fBlock{&bgs_engine::t2f, &kT2f, "bgs_t2f_params", "T2FGMM_UM / T2FGMM_UV", t2f_defaults, t2f_check, false};

@@ -51,74 +51,17 @@ class Engine:
         capi.check(capi.lib().bgs_set_params(self._h, C.byref(params)))
         self.params = params
 
-    def set_fuzzy_params(self, params=None, **kw):
-        """bgs_set_fuzzy_params (FUZZY_SUGENO / FUZZY_CHOQUET): acts from the next frame on.  Keywords change single fields of the
-        engine's current values."""
+    # set_<name>_params(params=None, **kw) / get_<name>_params() of every capi.PARAM_BLOCKS row are made from these two below the class
+    def _set_block_params(self, b, params, kw):
         if params is None:
-            params = self.get_fuzzy_params()
+            params = self._get_block_params(b)
         for k, v in kw.items():
             setattr(params, k, v)
-        capi.check(capi.lib().bgs_set_fuzzy_params(self._h, C.byref(params)))
+        capi.check(getattr(capi.lib(), "bgs_set_%s_params" % b.name)(self._h, C.byref(params)))
 
-    def get_fuzzy_params(self):
-        p = capi.BgsFuzzyParams()
-        capi.check(capi.lib().bgs_get_fuzzy_params(self._h, C.byref(p)))
-        return p
-
-    def set_t2f_params(self, params=None, **kw):
-        """bgs_set_t2f_params (T2FGMM_UM / T2FGMM_UV): taken when the geometry is set; a later call succeeds and changes nothing.
-        Keywords change single fields of the engine's current values."""
-        if params is None:
-            params = self.get_t2f_params()
-        for k, v in kw.items():
-            setattr(params, k, v)
-        capi.check(capi.lib().bgs_set_t2f_params(self._h, C.byref(params)))
-
-    def get_t2f_params(self):
-        p = capi.BgsT2fParams()
-        capi.check(capi.lib().bgs_get_t2f_params(self._h, C.byref(p)))
-        return p
-
-    def set_eigen_params(self, params=None, **kw):
-        """bgs_set_eigen_params (DPEigenbackground): taken when the geometry is set; a later call succeeds and changes nothing.
-        Keywords change single fields of the engine's current values."""
-        if params is None:
-            params = self.get_eigen_params()
-        for k, v in kw.items():
-            setattr(params, k, v)
-        capi.check(capi.lib().bgs_set_eigen_params(self._h, C.byref(params)))
-
-    def get_eigen_params(self):
-        p = capi.BgsEigenParams()
-        capi.check(capi.lib().bgs_get_eigen_params(self._h, C.byref(p)))
-        return p
-
-    def set_imbs_params(self, params=None, **kw):
-        """bgs_set_imbs_params (IndependentMultimodalBGS): taken when the geometry is set; a later call succeeds and changes nothing.
-        Keywords change single fields of the engine's current values."""
-        if params is None:
-            params = self.get_imbs_params()
-        for k, v in kw.items():
-            setattr(params, k, v)
-        capi.check(capi.lib().bgs_set_imbs_params(self._h, C.byref(params)))
-
-    def get_imbs_params(self):
-        p = capi.BgsImbsParams()
-        capi.check(capi.lib().bgs_get_imbs_params(self._h, C.byref(p)))
-        return p
-
-    def set_multilayer_params(self, params=None, **kw):
-        """bgs_set_multilayer_params (MultiLayerBGS): taken when the geometry is set; a later call succeeds and changes nothing.
-        Keywords change single fields of the engine's current values."""
-        if params is None:
-            params = self.get_multilayer_params()
-        for k, v in kw.items():
-            setattr(params, k, v)
-        capi.check(capi.lib().bgs_set_multilayer_params(self._h, C.byref(params)))
-
-    def get_multilayer_params(self):
-        p = capi.BgsMultilayerParams()
-        capi.check(capi.lib().bgs_get_multilayer_params(self._h, C.byref(p)))
+    def _get_block_params(self, b):
+        p = b.struct()
+        capi.check(getattr(capi.lib(), "bgs_get_%s_params" % b.name)(self._h, C.byref(p)))
         return p
 
     def set_option(self, option, value):
@@ -276,6 +219,26 @@ class Engine:
         if n < 0:
             capi.check(int(n))
         return np.frombuffer(buf, dtype=np.float32, count=int(n)).copy()
+
+
+def _block_methods(b):
+    def set_params(self, params=None, **kw):
+        self._set_block_params(b, params, kw)
+
+    def get_params(self):
+        return self._get_block_params(b)
+
+    late = "acts from the next frame on" if b.live else "taken when the geometry is set; a later call succeeds and changes nothing"
+    set_params.__doc__ = "bgs_set_%s_params (%s): %s.  Keywords change single fields of the engine's current values." % (b.name, b.classes, late)
+    get_params.__doc__ = "bgs_get_%s_params (%s): the engine's current values." % (b.name, b.classes)
+    for f, name in ((set_params, "set_%s_params" % b.name), (get_params, "get_%s_params" % b.name)):
+        f.__name__, f.__qualname__ = name, "Engine." + name
+        setattr(Engine, name, f)
+
+
+# Engine.set_fuzzy_params / get_fuzzy_params, and the same for t2f, eigen, imbs and multilayer
+for _b in capi.PARAM_BLOCKS:
+    _block_methods(_b)
 
 
 # -- stand-alone device primitives ---------------------------------------------------------------------------------
