@@ -709,6 +709,61 @@ int bgs_mask_morph_device(int hip_device, const void* d_src, void* d_dst, int ro
 int bgs_canny_device(int hip_device, const void* d_src, void* d_dst, int images, int rows, int cols, int low, int high,
                      void* hip_stream);
 
+/* ---- the model stage of SJN_MultiCueBGS (package_bgs/sjn): everything the class does per pixel -------------
+ * Frame reduction, the 7 x 7 blur, the HSV-cone conversion, the texture and colour codebooks with their cache-books, training,
+ * the confidence and landmark maps and the model update with absorption, as SJN_MultiCueBGS.cpp's own functions define them.
+ * The box stage between the landmark map and the update (morphology, labelling, bounding boxes, the Canny / Hausdorff ghost
+ * test) is not here: bgs_multicue_update_device takes the update maps that stage produces.  The books are fixed-capacity slot
+ * planes: an insert or an absorption into a full book is dropped and counted in the sticky "overflow" counter (the reference's
+ * arrays grow without bound; the capacities are at least twice the largest book it was measured to reach). */
+#define BGS_MULTICUE_TEXTURE_SLOTS 20
+#define BGS_MULTICUE_TEXTURE_CACHE_SLOTS 16
+#define BGS_MULTICUE_COLOR_SLOTS 32
+#define BGS_MULTICUE_COLOR_CACHE_SLOTS 16
+typedef struct bgs_multicue_params {
+  uint32_t struct_size;            /* sizeof(bgs_multicue_params) */
+  int32_t training_period;         /* g_iTrainingPeriod 20: frames 0 .. training_period train (training_period + 1 frames) */
+  int32_t t_model_threshold;       /* g_iT_ModelThreshold 1: the landmark is 255 where confidence > t_model_threshold / 6.0f */
+  int32_t c_model_threshold;       /* g_iC_ModelThreshold 10: read by nothing here; carried for the class */
+  float learning_rate;             /* g_fLearningRate 0.05f; training runs at learning_rate * 4 */
+  int32_t texture_train_vol_range; /* g_nTextureTrainVolRange 15 (a short in the reference) */
+  int32_t color_train_vol_range;   /* g_nColorTrainVolRange 20 (a short) */
+  int32_t absorption_enable;       /* g_bAbsorptionEnable 1: cache-books and absorption */
+  int32_t absorption_period;       /* g_iAbsortionPeriod 200 */
+  int32_t reduced_width;           /* g_iRWidth 160 */
+  int32_t reduced_height;          /* g_iRHeight 120 */
+  int32_t back_clear_period;       /* g_iBackClearPeriod 300 (handed over as a short) */
+  int32_t cache_clear_period;      /* g_iCacheClearPeriod 30: read by nothing (the cache-book clear uses the literal 10) */
+} bgs_multicue_params;
+typedef struct bgs_multicue bgs_multicue; /* n_streams models that move in lock step */
+int bgs_multicue_default_params(bgs_multicue_params* p);
+/* Every refusal, without a device (BGS_ERR_UNSUPPORTED, the class named): values that are not finite, periods and ranges
+ * outside 1..32767 (ranges may be 0), reduced sides below 5, reduced_width * reduced_height > BGS_CANNY_MAX_PIXELS (the class's
+ * per-box Canny runs on the reduced frame).  rows == 0 checks the parameters only; otherwise rows x cols is the frame. p NULL: the defaults. */
+int bgs_multicue_check(const bgs_multicue_params* p, int rows, int cols);
+int bgs_multicue_create(int hip_device, int n_streams, const bgs_multicue_params* p, bgs_multicue** m);
+void bgs_multicue_destroy(bgs_multicue* m);
+/* One BackgroundModeling_Par per stream on d_frames u8 [n_streams][rows][cols][3].  The first call fixes the geometry (another one
+ * later: BGS_ERR_GEOMETRY); a call after the (training_period + 1)-th: BGS_ERR_STATE. */
+int bgs_multicue_train_device(bgs_multicue* m, const void* d_frames, int rows, int cols, void* hip_stream);
+/* PreProcessing, T_GetConfidenceMap_Par and CreateLandmarkArray_Par.  d_landmark u8 [n_streams][rh][rw] (0 / 125 / 255), d_conf f32 of
+ * the same shape or NULL.  BGS_ERR_STATE before training is complete. */
+int bgs_multicue_landmark_device(bgs_multicue* m, const void* d_frames, int rows, int cols, void* d_landmark, void* d_conf, void* hip_stream);
+/* The model update on the XYZ frame and the landmark map of the last landmark call; d_update_map u8 [n_streams][rh][rw], its 2-pixel
+ * border ignored.  ghost == 1, step 2 of EvaluateGhostRegion: pixels whose map is non-zero get construction on the background books at
+ * learning_rate, then the clear with back_clear_period.  ghost == 0, step 2 of UpdateModel_Par with the map as g_aUpdateMap: non-zero
+ * takes the background path, zero the cache-book path with absorption (when enabled); the cache-book clear follows either way.
+ * BGS_ERR_STATE without a landmark call since the last ghost == 0 update. */
+int bgs_multicue_update_device(bgs_multicue* m, const void* d_update_map, int ghost, void* hip_stream);
+/* State of one stream, unpacked in the reference's field order (n = rh * rw; slots at and beyond m_iNumEntries read 0); returns the
+ * bytes written.  "gauss", "xyz" u8 [n][3]; "conf" f32 [n]; "landmark" u8 [n]; "tbook", "tcache" i32 [n][6][2] = m_iTotal,
+ * m_iNumEntries; "tmeans", "tcache_means" f32 [n][6][SLOTS]; "tmeta", "tcache_meta" i32 [n][6][SLOTS][3] = MNRL, first, last;
+ * "tref", "tcnt" i16 [n][6]; "cbook", "ccache" i32 [n][2]; "cmeans", "ccache_means" f64 [n][SLOTS][3]; "cmeta", "ccache_meta"
+ * i32 [n][SLOTS][3]; "cref", "ccnt" i16 [n]; "count" i64 [1] = g_iFrameCount; "overflow" i64 [1].  Waits for the device. */
+int64_t bgs_multicue_get_state(bgs_multicue* m, int stream, const char* plane, void* dst, size_t cap);
+/* BGR2HSVxyz_Par on a flat array of pixels: d_bgr, d_xyz u8 [pixels][3].  Asynchronous on hip_stream. */
+int bgs_multicue_xyz_device(int hip_device, const void* d_bgr, void* d_xyz, size_t pixels, void* hip_stream);
+
 /* Connected-component seeding of a byte mask on device: what OpenCV-legacy's blob detector derives
  * from the mask right after IBGS::process (ustc_src/trackingMain.cpp:56-57, :166; cvFindContours + bounding rectangles;
  * in-tree kin: package_bgs/jmo/BlobExtraction.cpp).  Components are the maximal 8- (or 4-) connected sets of non-zero

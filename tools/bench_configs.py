@@ -22,6 +22,9 @@ Not the driver's bench line (bench.py is); the numbers go to DESIGN.md §6.
              the smoothing kernel apart, bytes per pixel of state, this box's copy rate
   --only canny: bgs_canny_device on 160 x 120 images (the reduced frame of package_bgs/sjn), batches of 1 to 256: a block scene, uniform
              noise, and a serpentine whose hysteresis has to walk one chain of 2357 pixels; the numpy restatement beside
+  --only multicue: the model stage of SJN_MultiCueBGS (bgs_multicue) at the reference's defaults, 8 and 32 streams of 1080p frames reduced
+             to 160 x 120: us per train, landmark and update call, bytes of state per reduced pixel, the live bytes a call touches
+             over this box's copy rate
 usage: bench_configs.py [--streams S] [--swizzle 0|1]"""
 import argparse
 import os
@@ -321,6 +324,53 @@ def run_canny(rows=120, cols=160, reps=50):
             us = a.elapsed_time(b) / reps * 1e3
             print("canny %dx%d %-14s %3d images: %8.1f us per call, %7.2f us per image, %d edge pixels  (numpy restatement %.1f ms per image)"
                   % (cols, rows, name, images, us, us / images, int((want == 255).sum()), cpu_ms))
+
+
+def run_multicue(rows=1080, cols=1920, reps=30):
+    """bgs_multicue at the defaults (160 x 120 reduced pixels per stream whatever the frame size): a call is three preprocessing launches
+    and one model launch over S x 19 200 pixels, so it is bound by launches, not by bytes, until S is large."""
+    from tracking_amd.engine import MultiCueModel
+    copy = capi.calibrate_copy(0, 2 << 30, 0)
+    T, TC, CS, CC = capi.MULTICUE_TEXTURE_SLOTS, capi.MULTICUE_TEXTURE_CACHE_SLOTS, capi.MULTICUE_COLOR_SLOTS, capi.MULTICUE_COLOR_CACHE_SLOTS
+    state = 6 * (T + TC) * 16 + 6 * 2 * 8 + (CS + CC) * 36 + 2 * 8 + 7 * 4 + 9 + 4 + 1
+    print("multicue: %d bytes of state per reduced pixel (slots %d / %d / %d / %d); copy rate of this box %.0f GB/s" % (state, T, TC, CS, CC, copy))
+    for S in (8, 32):
+        g = torch.Generator(device="cuda").manual_seed(5)
+        coarse = torch.randint(0, 256, (S, rows // 8, cols // 8, 3), generator=g, device="cuda", dtype=torch.int16)
+        base = coarse.repeat_interleave(8, 1).repeat_interleave(8, 2)
+        pool = [(base + torch.randint(-2, 3, base.shape, generator=g, device="cuda", dtype=torch.int16)).clamp_(0, 255).to(torch.uint8) for _ in range(3)]
+        moved = [f.clone() for f in pool]
+        for f in moved:
+            f[:, rows // 4:rows // 2, cols // 4:cols // 2] = 200  # a block the model has not seen
+        p = capi.multicue_default_params()
+        um = torch.ones((S, p.reduced_height, p.reduced_width), dtype=torch.uint8, device="cuda")
+        um[:, p.reduced_height // 4:p.reduced_height // 2, p.reduced_width // 4:p.reduced_width // 2] = 0
+        times = {"train": [], "landmark": [], "update": []}
+
+        def timed(kind, call, *a, **kw):
+            a0, b0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a0.record()
+            out = call(*a, **kw)
+            b0.record()
+            times[kind].append((a0, b0))
+            return out
+
+        with MultiCueModel(p, n_streams=S) as m:
+            for t in range(p.training_period + 1):
+                timed("train", m.train, pool[t % 3])
+            for t in range(reps + 3):
+                timed("landmark", m.landmark, moved[t % 3])
+                timed("update", m.update, um)
+            torch.cuda.synchronize()
+            assert m.state("overflow")[0] == 0
+            live = sum(int(m.state(k)[..., 1].sum()) * b for k, b in (("tbook", 16), ("tcache", 16), ("cbook", 36), ("ccache", 36)))
+        n = p.reduced_height * p.reduced_width
+        for kind, ev in times.items():
+            us = np.array([a0.elapsed_time(b0) * 1e3 for a0, b0 in ev[3:]])
+            rw = {"train": 2, "landmark": 1, "update": 2}[kind]  # the live entries read (and written back) once
+            gbs = (S * live * rw + S * n * 16) / (np.median(us) * 1e-6) / 1e9
+            print("multicue %2d x %dx%d -> 160x120 %-8s: median %7.1f us per call (min %.1f, max %.1f, %d calls), %d launches; live state of stream 0 %d B/px -> at most about %.1f GB/s = %.3f of the copy rate (every live entry read and written once)%s"
+                  % (S, cols, rows, kind, np.median(us), us.min(), us.max(), len(us), 1 if kind == "update" else 4, live // n, gbs, gbs / copy, " (launch-bound)" if gbs / copy < 0.1 else ""))
 
 
 def run_clip(S=32, rows=1080, cols=1920, kind="sat", steps=48, Ts=(1, 2, 4, 8), algo=None, dense=201.0, label="MOG2"):
@@ -1169,6 +1219,9 @@ def main():
         return
     if args.only == "canny":
         run_canny()
+        return
+    if args.only == "multicue":
+        run_multicue()
         return
     if args.only in ("fuzzy_choquet", "fuzzy_sugeno"):
         run_fuzzy(S, steps=5, only="FuzzyChoquetIntegral" if args.only == "fuzzy_choquet" else "FuzzySugenoIntegral", calibrate=False)

@@ -31,6 +31,7 @@ EIGEN_MAX_HISTORY = 32  # BGS_EIGEN_MAX_HISTORY
 IMBS_MAX_SAMPLES = 63  # BGS_IMBS_MAX_SAMPLES
 MULTILAYER_MAX_HALF_SIZE = 8  # BGS_MULTILAYER_MAX_HALF_SIZE
 CANNY_MAX_PIXELS = 20480  # BGS_CANNY_MAX_PIXELS
+MULTICUE_TEXTURE_SLOTS, MULTICUE_TEXTURE_CACHE_SLOTS, MULTICUE_COLOR_SLOTS, MULTICUE_COLOR_CACHE_SLOTS = 20, 16, 32, 16  # BGS_MULTICUE_*_SLOTS
 FG_VALID, BG_VALID = 1, 2
 OPT_BORROW_FRAMES, OPT_MOG2_PIXELS_PER_LANE, OPT_MOG2_TILED, OPT_XCD_SWIZZLE, OPT_PLACEMENT_PROBE, OPT_MOG2_SPARSE, OPT_CLIP_FUSE, OPT_HOST_REGISTER, OPT_MODEL_CHUNK_MB, OPT_MODEL_CHUNK_MIN_MB = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 
@@ -145,6 +146,13 @@ class BgsMultilayerParams(C.Structure):
                 ("status", C.c_int32), ("disable_detect_mode", C.c_int32), ("disable_learning", C.c_int32), ("detect_after", C.c_int32)]
 
 
+class BgsMulticueParams(C.Structure):
+    """struct bgs_multicue_params, field for field (the model stage of SJN_MultiCueBGS; not yet a class parameter block)."""
+    _fields_ = [("struct_size", C.c_uint32), ("training_period", C.c_int32), ("t_model_threshold", C.c_int32), ("c_model_threshold", C.c_int32), ("learning_rate", C.c_float),
+                ("texture_train_vol_range", C.c_int32), ("color_train_vol_range", C.c_int32), ("absorption_enable", C.c_int32), ("absorption_period", C.c_int32),
+                ("reduced_width", C.c_int32), ("reduced_height", C.c_int32), ("back_clear_period", C.c_int32), ("cache_clear_period", C.c_int32)]
+
+
 class ParamBlock(collections.namedtuple("ParamBlock", "name struct classes check_takes_algo live")):
     """A class parameter block of the C ABI: struct bgs_<name>_params with bgs_<name>_default_params, bgs_set_<name>_params,
     bgs_get_<name>_params and bgs_<name>_check.  check_takes_algo: bgs_<name>_check's first argument is the algorithm (blocks that
@@ -195,6 +203,15 @@ SYMBOLS = [
     ("bgs_lbsp_describe_batch_device", C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     ("bgs_mask_morph_device", C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ("bgs_canny_device", C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    ("bgs_multicue_default_params", C.c_int, [C.POINTER(BgsMulticueParams)]),
+    ("bgs_multicue_check", C.c_int, [C.POINTER(BgsMulticueParams), C.c_int, C.c_int]),
+    ("bgs_multicue_create", C.c_int, [C.c_int, C.c_int, C.POINTER(BgsMulticueParams), C.POINTER(_P)]),
+    ("bgs_multicue_destroy", None, [_P]),
+    ("bgs_multicue_train_device", C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    ("bgs_multicue_landmark_device", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    ("bgs_multicue_update_device", C.c_int, [_P, _P, C.c_int, _P]),
+    ("bgs_multicue_get_state", C.c_int64, [_P, C.c_int, C.c_char_p, _P, C.c_size_t]),
+    ("bgs_multicue_xyz_device", C.c_int, [C.c_int, _P, _P, C.c_size_t, _P]),
     ("bgs_mask_components_workspace", C.c_size_t, [C.c_int, C.c_int]),
     ("bgs_mask_components_device", C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
     ("bgs_mask_components_batch_workspace", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
@@ -308,6 +325,15 @@ def _block_default_params(b):
 # fuzzy_default_params, t2f_default_params, eigen_default_params, imbs_default_params, multilayer_default_params
 for _b in PARAM_BLOCKS:
     globals()["%s_default_params" % _b.name] = _block_default_params(_b)
+
+
+def multicue_default_params(**kw):
+    """bgs_multicue_default_params (the model stage of SJN_MultiCueBGS); keywords change single fields of the defaults."""
+    p = BgsMulticueParams()
+    check(lib().bgs_multicue_default_params(C.byref(p)))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
 
 
 def calibrate_copy(device, nbytes, chunk_mb, iters=5):

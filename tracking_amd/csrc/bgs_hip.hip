@@ -41,6 +41,7 @@
 #include "kernel_imbs.h"
 #include "kernel_multilayer.h"
 #include "kernel_canny.h"
+#include "kernel_multicue.h"
 #include "kernel_cc.h"
 #include "kernel_dp.h"
 #include "kernel_mog1.h"
@@ -522,6 +523,7 @@ void gaussian_kernel_f32(int n, double sigma, float* cf) {
 #include "engine_eigen.h"
 #include "engine_imbs.h"
 #include "engine_multilayer.h"
+#include "engine_multicue.h"
 
 // an id that BGS_ALGO_KNOWN accepts but no engine class stands behind (BGS_LBSP_DESC is a stand-alone entry point): refused when the geometry is set
 constexpr Family kUnbuilt = [] {
@@ -907,6 +909,8 @@ void gaussian7_kernel(int ik[7]) {
   for (int i = 0; i < 7; ++i) ik[i] = (int)std::lrintf(cf[i] * 256.f);
 }
 }  // namespace
+
+struct bgs_multicue : McModel {};  // include/bgs_hip.h
 
 extern "C" {
 
@@ -1704,6 +1708,82 @@ int bgs_canny_device(int hip_device, const void* d_src, void* d_dst, int images,
   HIP_TRY(hipSetDevice(hip_device));
   if (low > high) std::swap(low, high);  // cvCanny orders its two thresholds itself
   hipLaunchKernelGGL(bgs::canny_kernel, dim3(images), dim3(bgs::kCannyBlock), 0, (hipStream_t)hip_stream, (const uint8_t*)d_src, (uint8_t*)d_dst, rows, cols, low, high);
+  HIP_TRY(hipGetLastError());
+  return BGS_OK;
+}
+
+// ---- the model stage of SJN_MultiCueBGS (engine_multicue.h)
+int bgs_multicue_default_params(bgs_multicue_params* p) {
+  if (!p) return fail(BGS_ERR_INVALID, "params is NULL");
+  mc_defaults(p);
+  return BGS_OK;
+}
+
+static const bgs_multicue_params* mc_arg(const bgs_multicue_params* p, bgs_multicue_params& d) {
+  if (!p) return mc_defaults(&d), &d;
+  if (p->struct_size != sizeof(*p)) return fail(BGS_ERR_INVALID, "bgs_multicue_params.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(*p)), nullptr;
+  return p;
+}
+
+int bgs_multicue_check(const bgs_multicue_params* p, int rows, int cols) {
+  bgs_multicue_params d;
+  if (!(p = mc_arg(p, d))) return BGS_ERR_INVALID;
+  int rc = mc_check((bgs_algo)0, *p);
+  if (rc || rows == 0) return rc;
+  if (rows < 0 || cols <= 0) return fail(BGS_ERR_INVALID, "bgs_multicue_check: bad geometry");
+  return mc_check_geometry((bgs_algo)0, rows, cols, 3);
+}
+
+int bgs_multicue_create(int hip_device, int n_streams, const bgs_multicue_params* p, bgs_multicue** m) {
+  if (!m) return fail(BGS_ERR_INVALID, "bgs_multicue_create: NULL argument");
+  *m = nullptr;
+  if (n_streams < 1 || n_streams > 65535) return fail(BGS_ERR_INVALID, "bgs_multicue_create: n_streams must be 1..65535");
+  bgs_multicue_params d;
+  if (!(p = mc_arg(p, d))) return BGS_ERR_INVALID;
+  int rc = mc_check((bgs_algo)0, *p);
+  if (rc) return rc;
+  bgs_multicue* o = new (std::nothrow) bgs_multicue();
+  if (!o) return fail(BGS_ERR_NOMEM, "out of memory");
+  rc = mc_create(hip_device, n_streams, p, o);
+  if (rc) {
+    delete o;
+    return rc;
+  }
+  *m = o;
+  return BGS_OK;
+}
+
+void bgs_multicue_destroy(bgs_multicue* m) {
+  if (!m) return;
+  (void)hipSetDevice(m->device);
+  (void)hipDeviceSynchronize();
+  delete m;
+}
+
+int bgs_multicue_train_device(bgs_multicue* m, const void* d_frames, int rows, int cols, void* hip_stream) {
+  if (!m) return fail(BGS_ERR_INVALID, "bgs_multicue_train_device: NULL argument");
+  return mc_train(*m, d_frames, rows, cols, (hipStream_t)hip_stream);
+}
+
+int bgs_multicue_landmark_device(bgs_multicue* m, const void* d_frames, int rows, int cols, void* d_landmark, void* d_conf, void* hip_stream) {
+  if (!m) return fail(BGS_ERR_INVALID, "bgs_multicue_landmark_device: NULL argument");
+  return mc_landmark(*m, d_frames, rows, cols, d_landmark, d_conf, (hipStream_t)hip_stream);
+}
+
+int bgs_multicue_update_device(bgs_multicue* m, const void* d_update_map, int ghost, void* hip_stream) {
+  if (!m) return fail(BGS_ERR_INVALID, "bgs_multicue_update_device: NULL argument");
+  return mc_update(*m, d_update_map, ghost, (hipStream_t)hip_stream);
+}
+
+int64_t bgs_multicue_get_state(bgs_multicue* m, int stream, const char* plane, void* dst, size_t cap) {
+  if (!m) return fail(BGS_ERR_INVALID, "bgs_multicue_get_state: NULL argument");
+  return mc_get_state(*m, stream, plane, dst, cap);
+}
+
+int bgs_multicue_xyz_device(int hip_device, const void* d_bgr, void* d_xyz, size_t pixels, void* hip_stream) {
+  if (!d_bgr || !d_xyz || !pixels || pixels > ((size_t)1 << 31)) return fail(BGS_ERR_INVALID, "bgs_multicue_xyz_device: bad argument");
+  HIP_TRY(hipSetDevice(hip_device));
+  hipLaunchKernelGGL(bgs::mc_xyz_kernel, dim3(blocks_for(pixels)), dim3(bgs::kBlock), 0, (hipStream_t)hip_stream, (const uint8_t*)d_bgr, (uint8_t*)d_xyz, pixels);
   HIP_TRY(hipGetLastError());
   return BGS_OK;
 }

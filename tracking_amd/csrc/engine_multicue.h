@@ -1,0 +1,245 @@
+// engine_multicue.h — host side of the model stage of package_bgs/sjn SJN_MultiCueBGS (kernel_multicue.h); included
+// inside bgs_hip.hip's anonymous namespace.
+//
+// The class itself (BGS_MULTICUE, its ParamBlock constant and Family) is not here yet: the box stage between the landmark map and the
+// update is missing.  What is here is the bgs_multicue object of include/bgs_hip.h, n_streams models that move in lock step, and
+// mc_defaults / mc_check / mc_check_geometry with the signatures a ParamBlock and a Family take.  Nothing here waits for the device
+// except bgs_multicue_get_state.
+
+constexpr const char* kMcName = "SJN_MultiCueBGS";
+
+void mc_defaults(bgs_multicue_params* p) {  // the constructor, SJN_MultiCueBGS.cpp:30-48
+  std::memset(p, 0, sizeof(*p));
+  p->struct_size = (uint32_t)sizeof(*p);
+  p->training_period = 20, p->t_model_threshold = 1, p->c_model_threshold = 10, p->learning_rate = 0.05f;
+  p->texture_train_vol_range = 15, p->color_train_vol_range = 20, p->absorption_enable = 1, p->absorption_period = 200;
+  p->reduced_width = 160, p->reduced_height = 120, p->back_clear_period = 300, p->cache_clear_period = 30;
+}
+
+// Needs no device.  nClearNum and the ranges are shorts in the reference, so the periods and ranges stop at 32767.
+int mc_check(bgs_algo, const bgs_multicue_params& p) {
+  if (!std::isfinite(p.learning_rate)) return fail(BGS_ERR_UNSUPPORTED, "%s: learning_rate must be finite", kMcName);
+  const struct { const char* name; int v, lo; } lim[] = {{"training_period", p.training_period, 1}, {"absorption_period", p.absorption_period, 1},
+      {"back_clear_period", p.back_clear_period, 1}, {"cache_clear_period", p.cache_clear_period, 1},
+      {"texture_train_vol_range", p.texture_train_vol_range, 0}, {"color_train_vol_range", p.color_train_vol_range, 0}};
+  for (const auto& l : lim)
+    if (l.v < l.lo || l.v > 32767) return fail(BGS_ERR_UNSUPPORTED, "%s: %s %d is outside %d..32767 (a short in the reference)", kMcName, l.name, l.v, l.lo);
+  if (p.reduced_width < 5 || p.reduced_height < 5)
+    return fail(BGS_ERR_UNSUPPORTED, "%s: the reduced frame %d x %d has a side below 5 (no pixel with all six neighbours)", kMcName, p.reduced_width, p.reduced_height);
+  if ((int64_t)p.reduced_width * p.reduced_height > BGS_CANNY_MAX_PIXELS)
+    return fail(BGS_ERR_UNSUPPORTED, "%s: the reduced frame %d x %d is more than BGS_CANNY_MAX_PIXELS (%d) pixels (the per-box Canny runs on it)", kMcName, p.reduced_width,
+                p.reduced_height, BGS_CANNY_MAX_PIXELS);
+  return BGS_OK;
+}
+int mc_check_geometry(bgs_algo, int rows, int cols, int ch) {
+  if (ch != 3) return fail(BGS_ERR_UNSUPPORTED, "%s: 3-channel frames only (ReduceImageSize, SJN_MultiCueBGS.cpp:547)", kMcName);
+  if ((int64_t)rows * cols >= ((int64_t)1 << 31) / 3) return fail(BGS_ERR_UNSUPPORTED, "%s: a frame must stay below 2^31 bytes", kMcName);
+  return BGS_OK;
+}
+
+struct McModel {
+  int device = 0, S = 1;
+  bgs_multicue_params p{};
+  int rows = 0, cols = 0;  // of the frames; fixed by the first training call
+  int rw = 0, rh = 0;
+  size_t n = 0;
+  int64_t count = 0;       // g_iFrameCount
+  bool have_landmark = false;
+  int taps[7] = {0};
+  uint8_t* arena = nullptr;  // one allocation; everything below points into it
+  uint8_t *red = nullptr, *gauss = nullptr, *xyz = nullptr, *landmark = nullptr;
+  float* conf = nullptr;
+  unsigned long long* overflow = nullptr;
+  bgs::McPlanes tb{}, tc{}, cb{}, cc{};
+  int16_t *tref = nullptr, *tcnt = nullptr, *cref = nullptr, *ccnt = nullptr;
+  ~McModel() {
+    if (arena) (void)hipFree(arena);
+  }
+};
+
+int mc_allocate(McModel& m) {
+  const size_t S = (size_t)m.S, n = m.n;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = off;
+    off += (bytes + 255) & ~(size_t)255;
+    return at;
+  };
+  struct Kind { bgs::McPlanes* pl; size_t K, NM, vsize; int cap; size_t head, mean, meta; };
+  Kind kinds[4] = {{&m.tb, 6, 1, 4, bgs::kMcTSlots}, {&m.tc, 6, 1, 4, bgs::kMcTCacheSlots}, {&m.cb, 1, 3, 8, bgs::kMcCSlots}, {&m.cc, 1, 3, 8, bgs::kMcCCacheSlots}};
+  // what has to start as 0 comes first (the heads: num = 0 makes every slot unread), then the referred indices (-1), then the rest
+  for (Kind& k : kinds) k.head = take(S * k.K * 2 * n * 4);
+  const size_t o_cnt = take(S * 7 * n * 2), o_over = take(8), o_conf = take(S * n * 4), o_lm = take(S * n), zero_end = off;
+  const size_t o_ref = take(S * 7 * n * 2), ref_end = off;
+  for (Kind& k : kinds) k.mean = take(S * k.K * k.cap * k.NM * n * k.vsize), k.meta = take(S * k.K * k.cap * 3 * n * 4);
+  const size_t o_red = take(S * n * 3), o_gauss = take(S * n * 3), o_xyz = take(S * n * 3);
+  HIP_TRY(hipMalloc((void**)&m.arena, off));
+  HIP_TRY(hipMemset(m.arena, 0, zero_end));
+  HIP_TRY(hipMemset(m.arena + o_ref, 0xff, ref_end - o_ref));  // int16 -1
+  HIP_TRY(hipMemset(m.arena + o_red, 0, off - o_red));
+  for (Kind& k : kinds) *k.pl = bgs::McPlanes{(int*)(m.arena + k.head), (void*)(m.arena + k.mean), (int*)(m.arena + k.meta), k.cap};
+  m.tcnt = (int16_t*)(m.arena + o_cnt), m.ccnt = m.tcnt + S * 6 * n;
+  m.tref = (int16_t*)(m.arena + o_ref), m.cref = m.tref + S * 6 * n;
+  m.overflow = (unsigned long long*)(m.arena + o_over), m.conf = (float*)(m.arena + o_conf), m.landmark = m.arena + o_lm;
+  m.red = m.arena + o_red, m.gauss = m.arena + o_gauss, m.xyz = m.arena + o_xyz;
+  return BGS_OK;
+}
+
+int mc_create(int device, int n_streams, const bgs_multicue_params* p, McModel* m) {
+  m->device = device, m->S = n_streams, m->p = *p;
+  m->rw = p->reduced_width, m->rh = p->reduced_height, m->n = (size_t)m->rw * m->rh;
+  float cf[7];
+  gaussian_kernel_f32(7, 0.7, cf);  // GaussianFiltering, :510-524
+  for (int i = 0; i < 7; ++i) m->taps[i] = (int)std::lrintf(cf[i] * 256.f);
+  HIP_TRY(hipSetDevice(device));
+  int rc = mc_allocate(*m);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());  // the fills are done before the caller's stream sees the model
+  return BGS_OK;
+}
+
+int mc_geometry(McModel& m, const char* fn, const void* d_frames, int rows, int cols, bool may_fix) {
+  if (!d_frames || rows <= 0 || cols <= 0) return fail(BGS_ERR_INVALID, "%s: bad argument", fn);
+  if (!m.rows && may_fix) {
+    int rc = mc_check_geometry((bgs_algo)0, rows, cols, 3);
+    if (rc) return rc;
+    m.rows = rows, m.cols = cols;
+  }
+  if (rows != m.rows || cols != m.cols) return fail(BGS_ERR_GEOMETRY, "%s: %d x %d frames after %d x %d", fn, rows, cols, m.rows, m.cols);
+  return BGS_OK;
+}
+
+// PreProcessing: reduce -> blur -> XYZ, three launches over all streams
+void mc_preprocess(McModel& m, const uint8_t* d_frames, hipStream_t s) {
+  const unsigned S = (unsigned)m.S;
+  hipLaunchKernelGGL(bgs::mc_reduce_kernel, dim3(blocks_for(m.n), S), dim3(bgs::kBlock), 0, s, d_frames, m.red, m.rows, m.cols, m.rh, m.rw, (double)m.rows / (double)m.rh,
+                     (double)m.cols / (double)m.rw);
+  bgs::BlurArgs b{};
+  b.src = m.red, b.dst = m.gauss, b.rows = m.rh, b.cols = m.rw;
+  for (int i = 0; i < 7; ++i) b.k[i] = m.taps[i];
+  const dim3 tiles((unsigned)((m.rw + bgs::kBlurTW - 1) / bgs::kBlurTW), (unsigned)((m.rh + bgs::kBlurTH - 1) / bgs::kBlurTH), S);
+  hipLaunchKernelGGL((bgs::ingest_blur7_kernel<3>), tiles, dim3(bgs::kBlock), 0, s, b);
+  hipLaunchKernelGGL(bgs::mc_xyz_kernel, dim3(blocks_for((size_t)m.S * m.n)), dim3(bgs::kBlock), 0, s, (const uint8_t*)m.gauss, m.xyz, (size_t)m.S * m.n);
+}
+
+bgs::McArgs mc_args(const McModel& m) {
+  bgs::McArgs a{};
+  a.xyz = m.xyz, a.landmark = m.landmark, a.tb = m.tb, a.tc = m.tc, a.cb = m.cb, a.cc = m.cc;
+  a.tref = m.tref, a.tcnt = m.tcnt, a.cref = m.cref, a.ccnt = m.ccnt, a.overflow = m.overflow;
+  a.landmark_out = m.landmark, a.conf_out = m.conf;
+  a.n = (uint32_t)m.n, a.rw = m.rw, a.rh = m.rh;
+  a.rate = m.p.learning_rate, a.conf_thr = (float)m.p.t_model_threshold / 6.f;  // g_fConfidenceThre, :54
+  a.trange = m.p.texture_train_vol_range, a.crange = m.p.color_train_vol_range;
+  a.absorb = m.p.absorption_enable != 0, a.absorb_period = m.p.absorption_period, a.clear_period = m.p.back_clear_period;
+  return a;
+}
+
+void mc_launch_update(const McModel& m, const bgs::McArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(bgs::mc_update_kernel, dim3(blocks_for(m.n), (unsigned)bgs::kMcBooks, (unsigned)m.S), dim3(bgs::kBlock), 0, s, a);
+}
+
+int mc_train(McModel& m, const void* d_frames, int rows, int cols, hipStream_t s) {
+  int rc = mc_geometry(m, "bgs_multicue_train_device", d_frames, rows, cols, true);
+  if (rc) return rc;
+  if (m.count > m.p.training_period) return fail(BGS_ERR_STATE, "bgs_multicue_train_device: training is complete after %d frames", m.p.training_period + 1);
+  HIP_TRY(hipSetDevice(m.device));
+  mc_preprocess(m, (const uint8_t*)d_frames, s);
+  bgs::McArgs a = mc_args(m);
+  const bool last = m.count == m.p.training_period;  // BackgroundModeling_Par's step 3, with nClearNum = training_period
+  a.mode = last ? 1 : 0, a.clear_period = m.p.training_period;
+  a.rate = m.p.learning_rate * 4;  // float
+  mc_launch_update(m, a, s);
+  HIP_TRY(hipGetLastError());
+  m.count += last ? 2 : 1;  // :308 and :87
+  return BGS_OK;
+}
+
+int mc_landmark(McModel& m, const void* d_frames, int rows, int cols, void* d_landmark, void* d_conf, hipStream_t s) {
+  if (!d_landmark) return fail(BGS_ERR_INVALID, "bgs_multicue_landmark_device: d_landmark is NULL");
+  if (m.count <= m.p.training_period) return fail(BGS_ERR_STATE, "bgs_multicue_landmark_device: training is not complete (%d frames)", m.p.training_period + 1);
+  int rc = mc_geometry(m, "bgs_multicue_landmark_device", d_frames, rows, cols, false);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(m.device));
+  mc_preprocess(m, (const uint8_t*)d_frames, s);
+  bgs::McArgs a = mc_args(m);
+  a.landmark_copy = (uint8_t*)d_landmark, a.conf_copy = (float*)d_conf;
+  hipLaunchKernelGGL(bgs::mc_landmark_kernel, dim3(blocks_for(m.n), (unsigned)m.S), dim3(bgs::kBlock), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  m.have_landmark = true;
+  return BGS_OK;
+}
+
+int mc_update(McModel& m, const void* d_map, int ghost, hipStream_t s) {
+  if (!d_map || (ghost != 0 && ghost != 1)) return fail(BGS_ERR_INVALID, "bgs_multicue_update_device: bad argument");
+  if (!m.have_landmark) return fail(BGS_ERR_STATE, "bgs_multicue_update_device: no bgs_multicue_landmark_device call since the last update");
+  HIP_TRY(hipSetDevice(m.device));
+  bgs::McArgs a = mc_args(m);
+  a.map = (const uint8_t*)d_map, a.mode = ghost ? 2 : 3;
+  mc_launch_update(m, a, s);
+  HIP_TRY(hipGetLastError());
+  if (!ghost) m.have_landmark = false;
+  return BGS_OK;
+}
+
+// one kind of book of one stream, transposed into the reference's order: book [nb][2], means [nb][cap][NM], meta [nb][cap][3]
+// with nb = n * K books in (pixel, k) order; slots at and beyond m_iNumEntries read 0
+template <class V>
+int64_t mc_get_book(const McModel& m, const bgs::McPlanes& pl, size_t K, size_t NM, int stream, int what, const char* plane, void* dst, size_t cap) {
+  const size_t n = m.n, C = (size_t)pl.cap, F = what == 0 ? 2 : what == 1 ? NM : 3;
+  const size_t per = what == 0 ? 2 : C * F, esize = what == 1 ? sizeof(V) : 4, nb = n * K * per * esize;
+  if (cap < nb) return too_small(plane);
+  std::vector<int32_t> head(K * 2 * n);
+  if (fetch(head.data(), pl.head + (size_t)stream * K * 2 * n, head.size() * 4)) return BGS_ERR_HIP;
+  if (what == 0) {
+    int32_t* o = (int32_t*)dst;
+    for (size_t i = 0; i < n; ++i)
+      for (size_t k = 0; k < K; ++k) o[(i * K + k) * 2] = head[(k * 2) * n + i], o[(i * K + k) * 2 + 1] = head[(k * 2 + 1) * n + i];
+    return (int64_t)nb;
+  }
+  std::memset(dst, 0, nb);
+  std::vector<uint8_t> raw(K * C * F * n * esize);
+  const uint8_t* src = what == 1 ? (const uint8_t*)pl.mean + (size_t)stream * raw.size() : (const uint8_t*)pl.meta + (size_t)stream * raw.size();
+  if (fetch(raw.data(), src, raw.size())) return BGS_ERR_HIP;
+  for (size_t i = 0; i < n; ++i)
+    for (size_t k = 0; k < K; ++k) {
+      const size_t num = (size_t)std::min<int64_t>(std::max<int64_t>(head[(k * 2 + 1) * n + i], 0), (int64_t)C);
+      for (size_t j = 0; j < num; ++j)
+        for (size_t f = 0; f < F; ++f)
+          std::memcpy((uint8_t*)dst + (((i * K + k) * C + j) * F + f) * esize, raw.data() + (((k * C + j) * F + f) * n + i) * esize, esize);
+    }
+  return (int64_t)nb;
+}
+
+int64_t mc_get_state(McModel& m, int stream, const char* plane, void* dst, size_t cap) {
+  if (!plane || !dst) return fail(BGS_ERR_INVALID, "bgs_multicue_get_state: NULL argument");
+  if (stream < 0 || stream >= m.S) return fail(BGS_ERR_INVALID, "stream %d outside 0..%d", stream, m.S - 1);
+  HIP_TRY(hipSetDevice(m.device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t n = m.n, k = (size_t)stream;
+  if (!strcmp(plane, "gauss")) return copy_plane(plane, dst, cap, m.gauss + k * n * 3, n * 3);
+  if (!strcmp(plane, "xyz")) return copy_plane(plane, dst, cap, m.xyz + k * n * 3, n * 3);
+  if (!strcmp(plane, "conf")) return copy_plane(plane, dst, cap, m.conf + k * n, n * 4);
+  if (!strcmp(plane, "landmark")) return copy_plane(plane, dst, cap, m.landmark + k * n, n);
+  if (!strcmp(plane, "count")) return copy_host(plane, dst, cap, &m.count, 8);
+  if (!strcmp(plane, "overflow")) return copy_plane(plane, dst, cap, m.overflow, 8);
+  if (!strcmp(plane, "cref")) return copy_plane(plane, dst, cap, m.cref + k * n, n * 2);
+  if (!strcmp(plane, "ccnt")) return copy_plane(plane, dst, cap, m.ccnt + k * n, n * 2);
+  if (!strcmp(plane, "tref") || !strcmp(plane, "tcnt")) {
+    if (cap < n * 12) return too_small(plane);
+    std::vector<int16_t> v(6 * n);
+    if (fetch(v.data(), (plane[1] == 'r' ? m.tref : m.tcnt) + k * 6 * n, v.size() * 2)) return BGS_ERR_HIP;
+    int16_t* o = (int16_t*)dst;
+    for (size_t i = 0; i < n; ++i)
+      for (size_t j = 0; j < 6; ++j) o[i * 6 + j] = v[j * n + i];
+    return (int64_t)(n * 12);
+  }
+  const struct { const char* book; const char* means; const char* meta; const bgs::McPlanes* pl; bool colour; } kinds[] = {
+      {"tbook", "tmeans", "tmeta", &m.tb, false}, {"tcache", "tcache_means", "tcache_meta", &m.tc, false},
+      {"cbook", "cmeans", "cmeta", &m.cb, true}, {"ccache", "ccache_means", "ccache_meta", &m.cc, true}};
+  for (const auto& kd : kinds) {
+    const int what = !strcmp(plane, kd.book) ? 0 : !strcmp(plane, kd.means) ? 1 : !strcmp(plane, kd.meta) ? 2 : -1;
+    if (what < 0) continue;
+    return kd.colour ? mc_get_book<double>(m, *kd.pl, 1, 3, stream, what, plane, dst, cap) : mc_get_book<float>(m, *kd.pl, 6, 1, stream, what, plane, dst, cap);
+  }
+  return fail(BGS_ERR_INVALID, "bgs_multicue_get_state: unknown plane %s", plane);
+}

@@ -298,6 +298,93 @@ def canny_device(src, low, high, device=0, hip_stream=None):
     return dst
 
 
+def multicue_xyz(bgr, device=0, hip_stream=None):
+    """bgr: torch CUDA uint8 [..., 3].  BGR2HSVxyz_Par of SJN_MultiCueBGS on every pixel (bgs_multicue_xyz_device): uint8 of the same shape."""
+    import torch
+    bgr = bgr.contiguous()
+    out = torch.empty_like(bgr)
+    if hip_stream is None:
+        hip_stream = torch.cuda.current_stream().cuda_stream
+    capi.check(capi.lib().bgs_multicue_xyz_device(device, C.c_void_p(bgr.data_ptr()), C.c_void_p(out.data_ptr()), bgr.numel() // 3, C.c_void_p(hip_stream)))
+    return out
+
+
+class MultiCueModel:
+    """The model stage of SJN_MultiCueBGS (bgs_multicue, include/bgs_hip.h): n_streams models that move in lock step.  Frames are torch
+    CUDA uint8 [n_streams][rows][cols][3] (or [rows][cols][3] for one stream); maps come back and go in as [n_streams][rh][rw]."""
+
+    def __init__(self, params=None, device=0, n_streams=1):
+        self._h = C.c_void_p()
+        self.params = params if params is not None else capi.multicue_default_params()
+        self.device, self.n_streams = device, n_streams
+        self.rh, self.rw = self.params.reduced_height, self.params.reduced_width
+        capi.check(capi.lib().bgs_multicue_create(device, n_streams, C.byref(self.params), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            capi.lib().bgs_multicue_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _frames(self, frames):
+        if frames.dim() == 3:
+            frames = frames[None]
+        assert frames.shape[0] == self.n_streams and frames.shape[3] == 3 and frames.dtype.itemsize == 1
+        return frames.contiguous()
+
+    @staticmethod
+    def _stream(hip_stream):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream().cuda_stream if hip_stream is None else hip_stream)
+
+    def train(self, frames, hip_stream=None):
+        f = self._frames(frames)
+        capi.check(capi.lib().bgs_multicue_train_device(self._h, C.c_void_p(f.data_ptr()), f.shape[1], f.shape[2], self._stream(hip_stream)))
+
+    def landmark(self, frames, want_conf=True, hip_stream=None):
+        """(landmark uint8 [n_streams][rh][rw] of 0 / 125 / 255, confidence float32 of the same shape or None)"""
+        import torch
+        f = self._frames(frames)
+        lm = torch.empty((self.n_streams, self.rh, self.rw), dtype=torch.uint8, device=f.device)
+        conf = torch.empty((self.n_streams, self.rh, self.rw), dtype=torch.float32, device=f.device) if want_conf else None
+        capi.check(capi.lib().bgs_multicue_landmark_device(self._h, C.c_void_p(f.data_ptr()), f.shape[1], f.shape[2], C.c_void_p(lm.data_ptr()),
+                                                           C.c_void_p(conf.data_ptr() if want_conf else None), self._stream(hip_stream)))
+        return lm, conf
+
+    def update(self, update_map, ghost=False, hip_stream=None):
+        m = update_map if update_map.dim() == 3 else update_map[None]
+        assert tuple(m.shape) == (self.n_streams, self.rh, self.rw) and m.dtype.itemsize == 1
+        m = m.contiguous()
+        capi.check(capi.lib().bgs_multicue_update_device(self._h, C.c_void_p(m.data_ptr()), 1 if ghost else 0, self._stream(hip_stream)))
+
+    def state(self, plane, stream=0):
+        """One plane of bgs_multicue_get_state as a numpy array in the reference's field order."""
+        n = self.rh * self.rw
+        T, TC, CS, CC = capi.MULTICUE_TEXTURE_SLOTS, capi.MULTICUE_TEXTURE_CACHE_SLOTS, capi.MULTICUE_COLOR_SLOTS, capi.MULTICUE_COLOR_CACHE_SLOTS
+        shapes = {"gauss": (np.uint8, (n, 3)), "xyz": (np.uint8, (n, 3)), "conf": (np.float32, (n,)), "landmark": (np.uint8, (n,)),
+                  "tbook": (np.int32, (n, 6, 2)), "tcache": (np.int32, (n, 6, 2)), "tmeans": (np.float32, (n, 6, T)), "tcache_means": (np.float32, (n, 6, TC)),
+                  "tmeta": (np.int32, (n, 6, T, 3)), "tcache_meta": (np.int32, (n, 6, TC, 3)), "tref": (np.int16, (n, 6)), "tcnt": (np.int16, (n, 6)),
+                  "cbook": (np.int32, (n, 2)), "ccache": (np.int32, (n, 2)), "cmeans": (np.float64, (n, CS, 3)), "ccache_means": (np.float64, (n, CC, 3)),
+                  "cmeta": (np.int32, (n, CS, 3)), "ccache_meta": (np.int32, (n, CC, 3)), "cref": (np.int16, (n,)), "ccnt": (np.int16, (n,)),
+                  "count": (np.int64, (1,)), "overflow": (np.int64, (1,))}
+        dt, shape = shapes[plane]
+        out = np.zeros(shape, dt)
+        got = capi.check(capi.lib().bgs_multicue_get_state(self._h, stream, plane.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes))
+        assert got == out.nbytes, (plane, got, out.nbytes)
+        return out
+
+
 BOX_FIELDS = ("x", "y", "w", "h", "area", "root")
 
 
