@@ -713,7 +713,8 @@ int bgs_canny_device(int hip_device, const void* d_src, void* d_dst, int images,
  * Frame reduction, the 7 x 7 blur, the HSV-cone conversion, the texture and colour codebooks with their cache-books, training,
  * the confidence and landmark maps and the model update with absorption, as SJN_MultiCueBGS.cpp's own functions define them.
  * The box stage between the landmark map and the update (morphology, labelling, bounding boxes, the Canny / Hausdorff ghost
- * test) is not here: bgs_multicue_update_device takes the update maps that stage produces.  The books are fixed-capacity slot
+ * test) is bgs_multicue_boxes_device below: bgs_multicue_update_device takes the update maps that stage produces, and
+ * bgs_multicue_process_device chains everything.  The books are fixed-capacity slot
  * planes: an insert or an absorption into a full book is dropped and counted in the sticky "overflow" counter (the reference's
  * arrays grow without bound; the capacities are at least twice the largest book it was measured to reach). */
 #define BGS_MULTICUE_TEXTURE_SLOTS 20
@@ -759,8 +760,33 @@ int bgs_multicue_update_device(bgs_multicue* m, const void* d_update_map, int gh
  * bytes written.  "gauss", "xyz" u8 [n][3]; "conf" f32 [n]; "landmark" u8 [n]; "tbook", "tcache" i32 [n][6][2] = m_iTotal,
  * m_iNumEntries; "tmeans", "tcache_means" f32 [n][6][SLOTS]; "tmeta", "tcache_meta" i32 [n][6][SLOTS][3] = MNRL, first, last;
  * "tref", "tcnt" i16 [n][6]; "cbook", "ccache" i32 [n][2]; "cmeans", "ccache_means" f64 [n][SLOTS][3]; "cmeta", "ccache_meta"
- * i32 [n][SLOTS][3]; "cref", "ccnt" i16 [n]; "count" i64 [1] = g_iFrameCount; "overflow" i64 [1].  Waits for the device. */
+ * i32 [n][SLOTS][3]; "cref", "ccnt" i16 [n]; "count" i64 [1] = g_iFrameCount; "overflow" i64 [1]; "box_overflow" i64 [1] (below).
+ * Waits for the device. */
 int64_t bgs_multicue_get_state(bgs_multicue* m, int stream, const char* plane, void* dst, size_t cap);
+/* The box stage: PostProcessing (SJN_MultiCueBGS.cpp:335) and step 1 of UpdateModel_Par (:367-382) as a pure function
+ * of (landmark map, frame), n_streams at once.  It reads the handle's parameters and geometry only (a first call fixes the geometry as
+ * a training call would; another one later: BGS_ERR_GEOMETRY) and touches neither the books nor the frame counter.
+ *   d_landmark u8 [n_streams][rh][rw]; d_frames u8 [n_streams][rows][cols][3]
+ *   d_fore u8 [n_streams][rh][rw]        g_aResizedForeMap after RemovingInvalidForeRegions (0 / 255)
+ *   d_ghost_map u8 [n_streams][rh][rw]   the aUpdateMap of EvaluateGhostRegion step 1: for bgs_multicue_update_device(..., ghost = 1)
+ *   d_update_map u8 [n_streams][rh][rw]  g_aUpdateMap: for the ghost = 0 call
+ *   d_count i32 [n_streams]              the label count of Labeling (it may exceed BGS_MULTICUE_MAX_BOXES)
+ *   d_boxes i32 [n_streams][BGS_MULTICUE_MAX_BOXES][BGS_MULTICUE_BOX_FIELDS]: m_aRLeft, m_aRRight, m_aRUpper, m_aRBottom, m_aLeft,
+ *     m_aRight, m_aUpper, m_aBottom, valid after EvaluateBoxSize, final m_ValidBox, frame-edge points, foreground-edge points,
+ *     foreground-edge points within squared distance 100 of a frame-edge point; rows at and beyond the count read 0.
+ * The reference has room for 300 boxes and writes past it; here the labels beyond BGS_MULTICUE_MAX_BOXES get no box, their pixels stay
+ * as they are, and the sticky "box_overflow" counter of bgs_multicue_get_state goes up by one per stream and call.
+ * Asynchronous on hip_stream; no allocation; the count never comes back to the host. */
+#define BGS_MULTICUE_MAX_BOXES 300
+#define BGS_MULTICUE_BOX_FIELDS 13
+int bgs_multicue_boxes_device(bgs_multicue* m, const void* d_landmark, const void* d_frames, int rows, int cols, void* d_fore, void* d_ghost_map,
+                              void* d_update_map, void* d_count, void* d_boxes, void* hip_stream);
+/* process() (SJN_MultiCueBGS.cpp:85-99) per stream in one asynchronous call.  While the frame counter is <= training_period: a training
+ * frame, and d_out is zeroed.  Afterwards the landmark call, the box stage, the ghost = 1 update with the ghost map, the ghost = 0
+ * update with the update map, and GetForegroundMap(result, NULL): the foreground map resized bilinearly to rows x cols (values between
+ * 0 and 255 are kept; the reference's three channels are equal).  d_out u8 [n_streams][rows][cols].  BGS_ERR_GEOMETRY for another
+ * frame size; BGS_ERR_STATE when a bgs_multicue_landmark_device call is still waiting for its updates. */
+int bgs_multicue_process_device(bgs_multicue* m, const void* d_frames, int rows, int cols, void* d_out, void* hip_stream);
 /* BGR2HSVxyz_Par on a flat array of pixels: d_bgr, d_xyz u8 [pixels][3].  Asynchronous on hip_stream. */
 int bgs_multicue_xyz_device(int hip_device, const void* d_bgr, void* d_xyz, size_t pixels, void* hip_stream);
 

@@ -22,7 +22,7 @@ Not the driver's bench line (bench.py is); the numbers go to DESIGN.md §6.
              the smoothing kernel apart, bytes per pixel of state, this box's copy rate
   --only canny: bgs_canny_device on 160 x 120 images (the reduced frame of package_bgs/sjn), batches of 1 to 256: a block scene, uniform
              noise, and a serpentine whose hysteresis has to walk one chain of 2357 pixels; the numpy restatement beside
-  --only multicue: the model stage of SJN_MultiCueBGS (bgs_multicue) at the reference's defaults, 8 and 32 streams of 1080p frames reduced
+  --only multicue: the model stage, the box stage and the whole step of SJN_MultiCueBGS (bgs_multicue) at the reference's defaults, 8 and 32 streams of 1080p frames reduced
              to 160 x 120: us per train, landmark and update call, bytes of state per reduced pixel, the live bytes a call touches
              over this box's copy rate
 usage: bench_configs.py [--streams S] [--swizzle 0|1]"""
@@ -371,6 +371,36 @@ def run_multicue(rows=1080, cols=1920, reps=30):
             gbs = (S * live * rw + S * n * 16) / (np.median(us) * 1e-6) / 1e9
             print("multicue %2d x %dx%d -> 160x120 %-8s: median %7.1f us per call (min %.1f, max %.1f, %d calls), %d launches; live state of stream 0 %d B/px -> at most about %.1f GB/s = %.3f of the copy rate (every live entry read and written once)%s"
                   % (S, cols, rows, kind, np.median(us), us.min(), us.max(), len(us), 1 if kind == "update" else 4, live // n, gbs, gbs / copy, " (launch-bound)" if gbs / copy < 0.1 else ""))
+
+        # the box stage (three launches: per-pixel preparation, one labelling workgroup per stream, one workgroup per (stream, box) slot) on
+        # the landmark map of the moved scene, on an empty map (the labelling chain alone: no box survives) and on a full one (one box with
+        # the largest window); then the whole step (ten launches)
+        def median_us(call, *a, n_calls=reps + 3):
+            ev = []
+            for _ in range(n_calls):
+                a0, b0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a0.record()
+                call(*a)
+                b0.record()
+                ev.append((a0, b0))
+            torch.cuda.synchronize()
+            us = np.array([a0.elapsed_time(b0) * 1e3 for a0, b0 in ev[3:]])
+            return np.median(us), us.min(), us.max(), len(us)
+
+        with MultiCueModel(p, n_streams=S) as m:
+            for t in range(p.training_period + 1):
+                m.process(pool[t % 3])
+            lm, _ = m.landmark(moved[0], want_conf=False)
+            m.update(um, ghost=True), m.update(um)
+            for name, lmap in (("scene", lm), ("empty", torch.zeros_like(lm)), ("full", torch.full_like(lm, 255))):
+                count = m.boxes(lmap, moved[0])[3]
+                med, lo, hi, k = median_us(m.boxes, lmap, moved[0])
+                print("multicue %2d x %dx%d -> 160x120 boxes/%-5s: median %7.1f us per call (min %.1f, max %.1f, %d calls), 3 launches; %d labels in stream 0"
+                      % (S, cols, rows, name, med, lo, hi, k, int(count[0])))
+            med, lo, hi, k = median_us(lambda: [m.process(moved[t % 3]) for t in range(3)], n_calls=reps // 3 + 3)
+            assert m.state("overflow")[0] == 0 and m.state("box_overflow")[0] == 0
+            print("multicue %2d x %dx%d -> 160x120 process     : median %7.1f us per call (min %.1f, max %.1f, %d triples of calls), 10 launches; %.2f us per stream"
+                  % (S, cols, rows, med / 3, lo / 3, hi / 3, k, med / 3 / S))
 
 
 def run_clip(S=32, rows=1080, cols=1920, kind="sat", steps=48, Ts=(1, 2, 4, 8), algo=None, dense=201.0, label="MOG2"):

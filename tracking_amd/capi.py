@@ -32,6 +32,7 @@ IMBS_MAX_SAMPLES = 63  # BGS_IMBS_MAX_SAMPLES
 MULTILAYER_MAX_HALF_SIZE = 8  # BGS_MULTILAYER_MAX_HALF_SIZE
 CANNY_MAX_PIXELS = 20480  # BGS_CANNY_MAX_PIXELS
 MULTICUE_TEXTURE_SLOTS, MULTICUE_TEXTURE_CACHE_SLOTS, MULTICUE_COLOR_SLOTS, MULTICUE_COLOR_CACHE_SLOTS = 20, 16, 32, 16  # BGS_MULTICUE_*_SLOTS
+MULTICUE_MAX_BOXES, MULTICUE_BOX_FIELDS = 300, 13  # BGS_MULTICUE_MAX_BOXES, BGS_MULTICUE_BOX_FIELDS
 FG_VALID, BG_VALID = 1, 2
 OPT_BORROW_FRAMES, OPT_MOG2_PIXELS_PER_LANE, OPT_MOG2_TILED, OPT_XCD_SWIZZLE, OPT_PLACEMENT_PROBE, OPT_MOG2_SPARSE, OPT_CLIP_FUSE, OPT_HOST_REGISTER, OPT_MODEL_CHUNK_MB, OPT_MODEL_CHUNK_MIN_MB = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 
@@ -211,6 +212,8 @@ SYMBOLS = [
     ("bgs_multicue_landmark_device", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     ("bgs_multicue_update_device", C.c_int, [_P, _P, C.c_int, _P]),
     ("bgs_multicue_get_state", C.c_int64, [_P, C.c_int, C.c_char_p, _P, C.c_size_t]),
+    ("bgs_multicue_boxes_device", C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    ("bgs_multicue_process_device", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     ("bgs_multicue_xyz_device", C.c_int, [C.c_int, _P, _P, C.c_size_t, _P]),
     ("bgs_mask_components_workspace", C.c_size_t, [C.c_int, C.c_int]),
     ("bgs_mask_components_device", C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),

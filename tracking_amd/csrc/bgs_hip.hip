@@ -42,6 +42,7 @@
 #include "kernel_multilayer.h"
 #include "kernel_canny.h"
 #include "kernel_multicue.h"
+#include "multicue_box.h"
 #include "kernel_cc.h"
 #include "kernel_dp.h"
 #include "kernel_mog1.h"
@@ -1775,6 +1776,17 @@ int bgs_multicue_update_device(bgs_multicue* m, const void* d_update_map, int gh
   return mc_update(*m, d_update_map, ghost, (hipStream_t)hip_stream);
 }
 
+int bgs_multicue_boxes_device(bgs_multicue* m, const void* d_landmark, const void* d_frames, int rows, int cols, void* d_fore, void* d_ghost_map, void* d_update_map,
+                              void* d_count, void* d_boxes, void* hip_stream) {
+  if (!m) return fail(BGS_ERR_INVALID, "bgs_multicue_boxes_device: NULL argument");
+  return mc_boxes(*m, d_landmark, d_frames, rows, cols, d_fore, d_ghost_map, d_update_map, d_count, d_boxes, (hipStream_t)hip_stream);
+}
+
+int bgs_multicue_process_device(bgs_multicue* m, const void* d_frames, int rows, int cols, void* d_out, void* hip_stream) {
+  if (!m) return fail(BGS_ERR_INVALID, "bgs_multicue_process_device: NULL argument");
+  return mc_process(*m, d_frames, rows, cols, d_out, (hipStream_t)hip_stream);
+}
+
 int64_t bgs_multicue_get_state(bgs_multicue* m, int stream, const char* plane, void* dst, size_t cap) {
   if (!m) return fail(BGS_ERR_INVALID, "bgs_multicue_get_state: NULL argument");
   return mc_get_state(*m, stream, plane, dst, cap);
@@ -2059,5 +2071,11 @@ int bgs_ingest_host(int hip_device, const bgs_ingest* c, const uint8_t* src, int
 
 
 }  // extern "C"
+
+namespace {
+void mc_launch_resize(const bgs::IngestArgs& g, unsigned streams, hipStream_t s) {  // engine_multicue.h
+  hipLaunchKernelGGL((bgs::ingest_geom_kernel<1>), dim3(blocks_for((size_t)g.rows * g.cols), 1, streams), dim3(bgs::kBlock), 0, s, g);
+}
+}  // namespace
 
 #include "engine_group.h"

@@ -1,10 +1,10 @@
-// engine_multicue.h — host side of the model stage of package_bgs/sjn SJN_MultiCueBGS (kernel_multicue.h); included
-// inside bgs_hip.hip's anonymous namespace.
+// engine_multicue.h — host side of package_bgs/sjn SJN_MultiCueBGS: the model stage (kernel_multicue.h), the box stage
+// (kernel_multicue_box.h, §5.14) and the whole-frame step that chains them as process() does; included inside bgs_hip.hip's anonymous
+// namespace.
 //
-// The class itself (BGS_MULTICUE, its ParamBlock constant and Family) is not here yet: the box stage between the landmark map and the
-// update is missing.  What is here is the bgs_multicue object of include/bgs_hip.h, n_streams models that move in lock step, and
-// mc_defaults / mc_check / mc_check_geometry with the signatures a ParamBlock and a Family take.  Nothing here waits for the device
-// except bgs_multicue_get_state.
+// The class itself (BGS_MULTICUE, its ParamBlock constant and Family) is not here yet.  What is here is the bgs_multicue object of
+// include/bgs_hip.h, n_streams models that move in lock step, and mc_defaults / mc_check / mc_check_geometry with the signatures a
+// ParamBlock and a Family take.  Nothing here waits for the device except bgs_multicue_get_state, and no call allocates.
 
 constexpr const char* kMcName = "SJN_MultiCueBGS";
 
@@ -49,7 +49,10 @@ struct McModel {
   uint8_t* arena = nullptr;  // one allocation; everything below points into it
   uint8_t *red = nullptr, *gauss = nullptr, *xyz = nullptr, *landmark = nullptr;
   float* conf = nullptr;
-  unsigned long long* overflow = nullptr;
+  unsigned long long *overflow = nullptr, *box_overflow = nullptr;
+  // the box stage's scratch (fore0, grey) and what the whole-frame step keeps between its launches
+  uint8_t *fore0 = nullptr, *grey = nullptr, *s_landmark = nullptr, *s_fore = nullptr, *s_ghost = nullptr, *s_update = nullptr;
+  int *s_count = nullptr, *s_boxes = nullptr;
   bgs::McPlanes tb{}, tc{}, cb{}, cc{};
   int16_t *tref = nullptr, *tcnt = nullptr, *cref = nullptr, *ccnt = nullptr;
   ~McModel() {
@@ -69,10 +72,11 @@ int mc_allocate(McModel& m) {
   Kind kinds[4] = {{&m.tb, 6, 1, 4, bgs::kMcTSlots}, {&m.tc, 6, 1, 4, bgs::kMcTCacheSlots}, {&m.cb, 1, 3, 8, bgs::kMcCSlots}, {&m.cc, 1, 3, 8, bgs::kMcCCacheSlots}};
   // what has to start as 0 comes first (the heads: num = 0 makes every slot unread), then the referred indices (-1), then the rest
   for (Kind& k : kinds) k.head = take(S * k.K * 2 * n * 4);
-  const size_t o_cnt = take(S * 7 * n * 2), o_over = take(8), o_conf = take(S * n * 4), o_lm = take(S * n), zero_end = off;
+  const size_t o_cnt = take(S * 7 * n * 2), o_over = take(8), o_bover = take(8), o_conf = take(S * n * 4), o_lm = take(S * n), zero_end = off;
   const size_t o_ref = take(S * 7 * n * 2), ref_end = off;
   for (Kind& k : kinds) k.mean = take(S * k.K * k.cap * k.NM * n * k.vsize), k.meta = take(S * k.K * k.cap * 3 * n * 4);
   const size_t o_red = take(S * n * 3), o_gauss = take(S * n * 3), o_xyz = take(S * n * 3);
+  const size_t o_box = take(S * n * 6), o_cb = take(S * sizeof(int) * (1 + (size_t)bgs::kMcMaxBoxes * bgs::kMcBoxFields));
   HIP_TRY(hipMalloc((void**)&m.arena, off));
   HIP_TRY(hipMemset(m.arena, 0, zero_end));
   HIP_TRY(hipMemset(m.arena + o_ref, 0xff, ref_end - o_ref));  // int16 -1
@@ -82,6 +86,10 @@ int mc_allocate(McModel& m) {
   m.tref = (int16_t*)(m.arena + o_ref), m.cref = m.tref + S * 6 * n;
   m.overflow = (unsigned long long*)(m.arena + o_over), m.conf = (float*)(m.arena + o_conf), m.landmark = m.arena + o_lm;
   m.red = m.arena + o_red, m.gauss = m.arena + o_gauss, m.xyz = m.arena + o_xyz;
+  m.box_overflow = (unsigned long long*)(m.arena + o_bover);
+  uint8_t* b = m.arena + o_box;
+  m.fore0 = b, m.grey = b + S * n, m.s_landmark = b + 2 * S * n, m.s_fore = b + 3 * S * n, m.s_ghost = b + 4 * S * n, m.s_update = b + 5 * S * n;
+  m.s_count = (int*)(m.arena + o_cb), m.s_boxes = m.s_count + S;
   return BGS_OK;
 }
 
@@ -181,6 +189,58 @@ int mc_update(McModel& m, const void* d_map, int ghost, hipStream_t s) {
   return BGS_OK;
 }
 
+// PostProcessing and step 1 of UpdateModel_Par: three launches over all streams (kernel_multicue_box.h, compiled in bgs_multicue_box.hip)
+void mc_launch_boxes(McModel& m, const uint8_t* d_landmark, const uint8_t* d_frames, uint8_t* d_fore, uint8_t* d_ghost, uint8_t* d_update, int* d_count, int* d_boxes,
+                     hipStream_t s) {
+  bgs::McBoxArgs a{};
+  a.landmark = d_landmark, a.frames = d_frames, a.fore0 = m.fore0, a.grey = m.grey, a.fore = d_fore, a.ghost = d_ghost, a.update = d_update;
+  a.count = d_count, a.boxes = d_boxes, a.box_overflow = m.box_overflow;
+  a.rows = m.rows, a.cols = m.cols, a.rw = m.rw, a.rh = m.rh;
+  a.inv_fy = 1.0 / ((double)m.rh / (double)m.rows), a.inv_fx = 1.0 / ((double)m.rw / (double)m.cols);
+  a.fh = (double)m.rows / (double)m.rh, a.fw = (double)m.cols / (double)m.rw;
+  bgs::mc_box_launch(a, (unsigned)m.S, s);
+}
+
+int mc_boxes(McModel& m, const void* d_landmark, const void* d_frames, int rows, int cols, void* d_fore, void* d_ghost, void* d_update, void* d_count, void* d_boxes,
+             hipStream_t s) {
+  if (!d_landmark || !d_fore || !d_ghost || !d_update || !d_count || !d_boxes) return fail(BGS_ERR_INVALID, "bgs_multicue_boxes_device: NULL argument");
+  int rc = mc_geometry(m, "bgs_multicue_boxes_device", d_frames, rows, cols, true);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(m.device));
+  mc_launch_boxes(m, (const uint8_t*)d_landmark, (const uint8_t*)d_frames, (uint8_t*)d_fore, (uint8_t*)d_ghost, (uint8_t*)d_update, (int*)d_count, (int*)d_boxes, s);
+  HIP_TRY(hipGetLastError());
+  return BGS_OK;
+}
+
+// ingest_geom_kernel<1> over g.rows x g.cols pixels of `streams` images.  Defined at the end of bgs_hip.hip, behind bgs_ingest_device, so that
+// the kernels of kernel_ingest.h are instantiated in the order they always were
+void mc_launch_resize(const bgs::IngestArgs& g, unsigned streams, hipStream_t s);
+
+// process(), SJN_MultiCueBGS.cpp:85-99: a training frame and zeros, or ForegroundExtraction, UpdateModel_Par and GetForegroundMap(result, NULL)
+int mc_process(McModel& m, const void* d_frames, int rows, int cols, void* d_out, hipStream_t s) {
+  if (!d_out) return fail(BGS_ERR_INVALID, "bgs_multicue_process_device: d_out is NULL");
+  if (m.have_landmark) return fail(BGS_ERR_STATE, "bgs_multicue_process_device: a bgs_multicue_landmark_device call is waiting for its updates");
+  if (m.count <= m.p.training_period) {
+    int rc = mc_train(m, d_frames, rows, cols, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(d_out, 0, (size_t)m.S * rows * cols, s));
+    return BGS_OK;
+  }
+  int rc = mc_landmark(m, d_frames, rows, cols, m.s_landmark, nullptr, s);
+  if (rc) return rc;
+  mc_launch_boxes(m, m.s_landmark, (const uint8_t*)d_frames, m.s_fore, m.s_ghost, m.s_update, m.s_count, m.s_boxes, s);
+  HIP_TRY(hipGetLastError());
+  if ((rc = mc_update(m, m.s_ghost, 1, s)) || (rc = mc_update(m, m.s_update, 0, s))) return rc;
+  // cvResize(temp_image, return_image): the foreground map, bilinear, to the frame's size (kernel_ingest.h; the three channels are equal)
+  bgs::IngestArgs g{};
+  g.src = m.s_fore, g.dst = (uint8_t*)d_out, g.src_rows = m.rh, g.src_cols = m.rw, g.rw = cols, g.rh = rows, g.rows = rows, g.cols = cols, g.src_step = (size_t)m.rw;
+  g.scale_x = 1. / ((double)cols / m.rw), g.scale_y = 1. / ((double)rows / m.rh);
+  g.mode = (m.rw == 2 * cols && m.rh == 2 * rows) ? 2 : 1;
+  mc_launch_resize(g, (unsigned)m.S, s);
+  HIP_TRY(hipGetLastError());
+  return BGS_OK;
+}
+
 // one kind of book of one stream, transposed into the reference's order: book [nb][2], means [nb][cap][NM], meta [nb][cap][3]
 // with nb = n * K books in (pixel, k) order; slots at and beyond m_iNumEntries read 0
 template <class V>
@@ -222,6 +282,7 @@ int64_t mc_get_state(McModel& m, int stream, const char* plane, void* dst, size_
   if (!strcmp(plane, "landmark")) return copy_plane(plane, dst, cap, m.landmark + k * n, n);
   if (!strcmp(plane, "count")) return copy_host(plane, dst, cap, &m.count, 8);
   if (!strcmp(plane, "overflow")) return copy_plane(plane, dst, cap, m.overflow, 8);
+  if (!strcmp(plane, "box_overflow")) return copy_plane(plane, dst, cap, m.box_overflow, 8);
   if (!strcmp(plane, "cref")) return copy_plane(plane, dst, cap, m.cref + k * n, n * 2);
   if (!strcmp(plane, "ccnt")) return copy_plane(plane, dst, cap, m.ccnt + k * n, n * 2);
   if (!strcmp(plane, "tref") || !strcmp(plane, "tcnt")) {

@@ -102,10 +102,12 @@ __device__ __forceinline__ void canny_image(const uint8_t* __restrict__ src, siz
   }
 }
 
+#ifndef BGS_CANNY_IMAGE_ONLY  // a translation unit that wants canny_image alone (bgs_multicue_box.hip) leaves the kernel to bgs_hip.hip
 __global__ __launch_bounds__(kCannyBlock) void canny_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int rows, int cols, int low, int high) {
   __shared__ CannyLds L;
   const size_t off = (size_t)blockIdx.x * rows * cols;
   canny_image(src + off, (size_t)cols, dst + off, (size_t)cols, rows, cols, low, high, L);
 }
+#endif
 
 }  // namespace bgs

@@ -310,8 +310,9 @@ def multicue_xyz(bgr, device=0, hip_stream=None):
 
 
 class MultiCueModel:
-    """The model stage of SJN_MultiCueBGS (bgs_multicue, include/bgs_hip.h): n_streams models that move in lock step.  Frames are torch
-    CUDA uint8 [n_streams][rows][cols][3] (or [rows][cols][3] for one stream); maps come back and go in as [n_streams][rh][rw]."""
+    """SJN_MultiCueBGS without its class plumbing (bgs_multicue, include/bgs_hip.h): n_streams models that move in lock step.  Frames are torch
+    CUDA uint8 [n_streams][rows][cols][3] (or [rows][cols][3] for one stream); maps come back and go in as [n_streams][rh][rw].
+    process(frames) is the reference's process(); train / landmark / boxes / update are its parts."""
 
     def __init__(self, params=None, device=0, n_streams=1):
         self._h = C.c_void_p()
@@ -368,6 +369,31 @@ class MultiCueModel:
         m = m.contiguous()
         capi.check(capi.lib().bgs_multicue_update_device(self._h, C.c_void_p(m.data_ptr()), 1 if ghost else 0, self._stream(hip_stream)))
 
+    def boxes(self, landmark, frames, hip_stream=None):
+        """The box stage (bgs_multicue_boxes_device) on landmark maps uint8 [n_streams][rh][rw] and frames.  Returns torch tensors
+        (fore, ghost_map, update_map uint8 [n_streams][rh][rw], count int32 [n_streams], boxes int32 [n_streams][300][13])."""
+        import torch
+        f = self._frames(frames)
+        lm = landmark if landmark.dim() == 3 else landmark[None]
+        assert tuple(lm.shape) == (self.n_streams, self.rh, self.rw) and lm.dtype.itemsize == 1
+        lm = lm.contiguous()
+        fore, ghost, upd = (torch.empty((self.n_streams, self.rh, self.rw), dtype=torch.uint8, device=f.device) for _ in range(3))
+        count = torch.empty(self.n_streams, dtype=torch.int32, device=f.device)
+        boxes = torch.empty((self.n_streams, capi.MULTICUE_MAX_BOXES, capi.MULTICUE_BOX_FIELDS), dtype=torch.int32, device=f.device)
+        capi.check(capi.lib().bgs_multicue_boxes_device(self._h, C.c_void_p(lm.data_ptr()), C.c_void_p(f.data_ptr()), f.shape[1], f.shape[2], C.c_void_p(fore.data_ptr()),
+                                                        C.c_void_p(ghost.data_ptr()), C.c_void_p(upd.data_ptr()), C.c_void_p(count.data_ptr()), C.c_void_p(boxes.data_ptr()),
+                                                        self._stream(hip_stream)))
+        return fore, ghost, upd, count, boxes
+
+    def process(self, frames, hip_stream=None):
+        """The reference's process() on one frame per stream (bgs_multicue_process_device): the foreground image, torch uint8
+        [n_streams][rows][cols]; zeros while the model trains."""
+        import torch
+        f = self._frames(frames)
+        out = torch.empty((self.n_streams, f.shape[1], f.shape[2]), dtype=torch.uint8, device=f.device)
+        capi.check(capi.lib().bgs_multicue_process_device(self._h, C.c_void_p(f.data_ptr()), f.shape[1], f.shape[2], C.c_void_p(out.data_ptr()), self._stream(hip_stream)))
+        return out
+
     def state(self, plane, stream=0):
         """One plane of bgs_multicue_get_state as a numpy array in the reference's field order."""
         n = self.rh * self.rw
@@ -377,7 +403,7 @@ class MultiCueModel:
                   "tmeta": (np.int32, (n, 6, T, 3)), "tcache_meta": (np.int32, (n, 6, TC, 3)), "tref": (np.int16, (n, 6)), "tcnt": (np.int16, (n, 6)),
                   "cbook": (np.int32, (n, 2)), "ccache": (np.int32, (n, 2)), "cmeans": (np.float64, (n, CS, 3)), "ccache_means": (np.float64, (n, CC, 3)),
                   "cmeta": (np.int32, (n, CS, 3)), "ccache_meta": (np.int32, (n, CC, 3)), "cref": (np.int16, (n,)), "ccnt": (np.int16, (n,)),
-                  "count": (np.int64, (1,)), "overflow": (np.int64, (1,))}
+                  "count": (np.int64, (1,)), "overflow": (np.int64, (1,)), "box_overflow": (np.int64, (1,))}
         dt, shape = shapes[plane]
         out = np.zeros(shape, dt)
         got = capi.check(capi.lib().bgs_multicue_get_state(self._h, stream, plane.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes))
