@@ -736,7 +736,7 @@ typedef struct bgs_multicue_params {
   int32_t back_clear_period;       /* g_iBackClearPeriod 300 (handed over as a short) */
   int32_t cache_clear_period;      /* g_iCacheClearPeriod 30: read by nothing (the cache-book clear uses the literal 10) */
 } bgs_multicue_params;
-typedef struct bgs_multicue bgs_multicue; /* n_streams models that move in lock step */
+typedef struct bgs_multicue bgs_multicue; /* n_streams models, each with its own frame counter (per-stream lifetime: below) */
 int bgs_multicue_default_params(bgs_multicue_params* p);
 /* Every refusal, without a device (BGS_ERR_UNSUPPORTED, the class named): values that are not finite, periods and ranges
  * outside 1..32767 (ranges may be 0), reduced sides below 5, reduced_width * reduced_height > BGS_CANNY_MAX_PIXELS (the class's
@@ -760,8 +760,8 @@ int bgs_multicue_update_device(bgs_multicue* m, const void* d_update_map, int gh
  * bytes written.  "gauss", "xyz" u8 [n][3]; "conf" f32 [n]; "landmark" u8 [n]; "tbook", "tcache" i32 [n][6][2] = m_iTotal,
  * m_iNumEntries; "tmeans", "tcache_means" f32 [n][6][SLOTS]; "tmeta", "tcache_meta" i32 [n][6][SLOTS][3] = MNRL, first, last;
  * "tref", "tcnt" i16 [n][6]; "cbook", "ccache" i32 [n][2]; "cmeans", "ccache_means" f64 [n][SLOTS][3]; "cmeta", "ccache_meta"
- * i32 [n][SLOTS][3]; "cref", "ccnt" i16 [n]; "count" i64 [1] = g_iFrameCount; "overflow" i64 [1]; "box_overflow" i64 [1] (below).
- * Waits for the device. */
+ * i32 [n][SLOTS][3]; "cref", "ccnt" i16 [n]; "count" i64 [1] = the stream's g_iFrameCount; "overflow" i64 [1]; "box_overflow" i64 [1]
+ * (below; both are the handle's, not the stream's).  Waits for the device. */
 int64_t bgs_multicue_get_state(bgs_multicue* m, int stream, const char* plane, void* dst, size_t cap);
 /* The box stage: PostProcessing (SJN_MultiCueBGS.cpp:335) and step 1 of UpdateModel_Par (:367-382) as a pure function
  * of (landmark map, frame), n_streams at once.  It reads the handle's parameters and geometry only (a first call fixes the geometry as
@@ -787,6 +787,27 @@ int bgs_multicue_boxes_device(bgs_multicue* m, const void* d_landmark, const voi
  * 0 and 255 are kept; the reference's three channels are equal).  d_out u8 [n_streams][rows][cols].  BGS_ERR_GEOMETRY for another
  * frame size; BGS_ERR_STATE when a bgs_multicue_landmark_device call is still waiting for its updates. */
 int bgs_multicue_process_device(bgs_multicue* m, const void* d_frames, int rows, int cols, void* d_out, void* hip_stream);
+/* ---- per-stream lifetime.  Every stream has a frame counter of its own ("count" of bgs_multicue_get_state); a handle's streams need not
+ * be the same age.  bgs_multicue_process_device is the range [0, n_streams) of the call below.  The piecewise calls (train / landmark /
+ * update / boxes) keep their meaning over all streams and return BGS_ERR_STATE, naming the range call, once the ages differ.
+ * Calls on one handle from several host threads are not supported: the counters are not locked. */
+/* process() for streams [first, first + count), which may be at different ages: d_frames u8 [count][rows][cols][3] and d_out u8
+ * [count][rows][cols] point at stream `first`.  Neighbouring streams in the same phase (training frame, last training frame, detecting)
+ * share one launch of each kernel.  A stream's frame 0, the first ever or the first after bgs_multicue_reset_stream, initialises that
+ * stream's model on hip_stream before it trains.  Disjoint ranges may be in flight on different HIP streams at the same time.
+ * BGS_ERR_INVALID for a range outside the handle, BGS_ERR_GEOMETRY for another frame size.  Asynchronous; no allocation. */
+int bgs_multicue_process_range_device(bgs_multicue* m, int first, int count, const void* d_frames, int rows, int cols, void* d_out, void* hip_stream);
+/* The stream's next frame is training frame 0.  Host-only: it neither touches nor waits for the device, and until that frame
+ * bgs_multicue_get_state returns for this stream what a newly created handle returns.  The caller orders that next frame behind whatever
+ * is still in flight for the stream on another HIP stream.  BGS_ERR_INVALID for a stream outside the handle. */
+int bgs_multicue_reset_stream(bgs_multicue* m, int stream);
+/* process() on one frame in host memory, for one stream, synchronous: `frame` is rows x cols x 3 bytes with a row pitch of `step` bytes,
+ * `out` receives rows x cols x out_channels bytes (out_channels 1 or 3; the reference's img_output is 8UC3 with equal channels, which the
+ * host writes: one channel crosses the bus) with a row pitch of out_step.  The call uses a HIP stream, page-locked staging and device buffers
+ * of the handle's own, made by the first such call: the only call of the object that allocates.  Pitches below the row size and streams
+ * outside the handle: BGS_ERR_INVALID; another frame size: BGS_ERR_GEOMETRY.  Ordering against device calls that step the same stream on
+ * other HIP streams is the caller's responsibility. */
+int bgs_multicue_process(bgs_multicue* m, int stream, const void* frame, int rows, int cols, size_t step, void* out, size_t out_step, int out_channels);
 /* BGR2HSVxyz_Par on a flat array of pixels: d_bgr, d_xyz u8 [pixels][3].  Asynchronous on hip_stream. */
 int bgs_multicue_xyz_device(int hip_device, const void* d_bgr, void* d_xyz, size_t pixels, void* hip_stream);
 

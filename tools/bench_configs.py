@@ -24,7 +24,8 @@ Not the driver's bench line (bench.py is); the numbers go to DESIGN.md §6.
              noise, and a serpentine whose hysteresis has to walk one chain of 2357 pixels; the numpy restatement beside
   --only multicue: the model stage, the box stage and the whole step of SJN_MultiCueBGS (bgs_multicue) at the reference's defaults, 8 and 32 streams of 1080p frames reduced
              to 160 x 120: us per train, landmark and update call, bytes of state per reduced pixel, the live bytes a call touches
-             over this box's copy rate
+             over this box's copy rate; the 32-stream step as two ranges on two HIP streams beside the one call; the host path of one
+             1080p camera (upload + step + download)
 usage: bench_configs.py [--streams S] [--swizzle 0|1]"""
 import argparse
 import os
@@ -401,6 +402,46 @@ def run_multicue(rows=1080, cols=1920, reps=30):
             assert m.state("overflow")[0] == 0 and m.state("box_overflow")[0] == 0
             print("multicue %2d x %dx%d -> 160x120 process     : median %7.1f us per call (min %.1f, max %.1f, %d triples of calls), 10 launches; %.2f us per stream"
                   % (S, cols, rows, med / 3, lo / 3, hi / 3, k, med / 3 / S))
+            if S == 32:  # the same detecting step as two ranges of 16 streams on two HIP streams (bgs_multicue_process_range_device), beside the one call above
+                side = [torch.cuda.Stream(), torch.cuda.Stream()]
+                cur = torch.cuda.current_stream()
+
+                def halves():
+                    for t in range(3):
+                        for h, s in enumerate(side):
+                            s.wait_stream(cur)  # the timing event before this call is on the current stream
+                            m.process(moved[t % 3][16 * h:16 * h + 16], first=16 * h, count=16, hip_stream=s.cuda_stream)
+                        for s in side:
+                            cur.wait_stream(s)
+
+                med2, lo2, hi2, k2 = median_us(halves, n_calls=reps // 3 + 3)
+                assert m.state("overflow")[0] == 0 and m.state("box_overflow")[0] == 0
+                print("multicue 32 x %dx%d -> 160x120 process as [0,16) + [16,32) on two HIP streams: median %7.1f us per step (min %.1f, max %.1f, %d triples of steps), 2 x 10 launches; the one call: %.1f us"
+                      % (cols, rows, med2 / 3, lo2 / 3, hi2 / 3, k2, med / 3))
+
+    # the host path of one camera (bgs_multicue_process): a 1080p frame from pageable memory into page-locked staging, upload, the detecting
+    # step of one stream, download of the one-channel image, the host's three equal channels; wall clock, the call is synchronous
+    p = capi.multicue_default_params()
+    rng = np.random.RandomState(5)
+    base = np.repeat(np.repeat(rng.randint(0, 256, (rows // 8, cols // 8, 3)), 8, 0), 8, 1)
+    host = [np.clip(base + rng.randint(-2, 3, base.shape), 0, 255).astype(np.uint8) for _ in range(3)]
+    for f in host[1:]:
+        f[rows // 4:rows // 2, cols // 4:cols // 2] = 200  # a block the model has not seen
+    with MultiCueModel(p, n_streams=1) as m:
+        for t in range(p.training_period + 1):
+            m.process_host(host[0], channels=3)
+        for channels in (1, 3):
+            ms = []
+            for t in range(reps + 3):
+                t0 = time.perf_counter()
+                m.process_host(host[1 + t % 2], channels=channels)
+                ms.append((time.perf_counter() - t0) * 1e3)
+            ms = np.array(ms[3:])
+            moved_bytes = rows * cols * 4
+            print("multicue  1 x %dx%d -> 160x120 host path, %d channel%s out: median %6.3f ms per frame (min %.3f, max %.3f, %d frames): upload %.1f MB + step + download %.1f MB -> %.1f GB/s over the bus"
+                  % (cols, rows, channels, "" if channels == 1 else "s", np.median(ms), ms.min(), ms.max(), len(ms), rows * cols * 3 / 1e6, rows * cols / 1e6,
+                     moved_bytes / (np.median(ms) * 1e-3) / 1e9))
+        assert m.state("overflow")[0] == 0 and m.state("box_overflow")[0] == 0
 
 
 def run_clip(S=32, rows=1080, cols=1920, kind="sat", steps=48, Ts=(1, 2, 4, 8), algo=None, dense=201.0, label="MOG2"):

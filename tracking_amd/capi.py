@@ -148,7 +148,7 @@ class BgsMultilayerParams(C.Structure):
 
 
 class BgsMulticueParams(C.Structure):
-    """struct bgs_multicue_params, field for field (the model stage of SJN_MultiCueBGS; not yet a class parameter block)."""
+    """struct bgs_multicue_params, field for field (SJN_MultiCueBGS; a bgs_multicue handle takes it at creation, no bgs_engine does)."""
     _fields_ = [("struct_size", C.c_uint32), ("training_period", C.c_int32), ("t_model_threshold", C.c_int32), ("c_model_threshold", C.c_int32), ("learning_rate", C.c_float),
                 ("texture_train_vol_range", C.c_int32), ("color_train_vol_range", C.c_int32), ("absorption_enable", C.c_int32), ("absorption_period", C.c_int32),
                 ("reduced_width", C.c_int32), ("reduced_height", C.c_int32), ("back_clear_period", C.c_int32), ("cache_clear_period", C.c_int32)]
@@ -214,6 +214,9 @@ SYMBOLS = [
     ("bgs_multicue_get_state", C.c_int64, [_P, C.c_int, C.c_char_p, _P, C.c_size_t]),
     ("bgs_multicue_boxes_device", C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("bgs_multicue_process_device", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
+    ("bgs_multicue_process_range_device", C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
+    ("bgs_multicue_reset_stream", C.c_int, [_P, C.c_int]),
+    ("bgs_multicue_process", C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_size_t, _P, C.c_size_t, C.c_int]),
     ("bgs_multicue_xyz_device", C.c_int, [C.c_int, _P, _P, C.c_size_t, _P]),
     ("bgs_mask_components_workspace", C.c_size_t, [C.c_int, C.c_int]),
     ("bgs_mask_components_device", C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),

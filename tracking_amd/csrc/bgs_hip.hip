@@ -1784,7 +1784,22 @@ int bgs_multicue_boxes_device(bgs_multicue* m, const void* d_landmark, const voi
 
 int bgs_multicue_process_device(bgs_multicue* m, const void* d_frames, int rows, int cols, void* d_out, void* hip_stream) {
   if (!m) return fail(BGS_ERR_INVALID, "bgs_multicue_process_device: NULL argument");
-  return mc_process(*m, d_frames, rows, cols, d_out, (hipStream_t)hip_stream);
+  return mc_process_range(*m, "bgs_multicue_process_device", 0, m->S, d_frames, rows, cols, d_out, (hipStream_t)hip_stream);
+}
+
+int bgs_multicue_process_range_device(bgs_multicue* m, int first, int count, const void* d_frames, int rows, int cols, void* d_out, void* hip_stream) {
+  if (!m) return fail(BGS_ERR_INVALID, "bgs_multicue_process_range_device: NULL argument");
+  return mc_process_range(*m, "bgs_multicue_process_range_device", first, count, d_frames, rows, cols, d_out, (hipStream_t)hip_stream);
+}
+
+int bgs_multicue_reset_stream(bgs_multicue* m, int stream) {
+  if (!m) return fail(BGS_ERR_INVALID, "bgs_multicue_reset_stream: NULL argument");
+  return mc_reset_stream(*m, stream);
+}
+
+int bgs_multicue_process(bgs_multicue* m, int stream, const void* frame, int rows, int cols, size_t step, void* out, size_t out_step, int out_channels) {
+  if (!m) return fail(BGS_ERR_INVALID, "bgs_multicue_process: NULL argument");
+  return mc_process_host(*m, stream, frame, rows, cols, step, out, out_step, out_channels);
 }
 
 int64_t bgs_multicue_get_state(bgs_multicue* m, int stream, const char* plane, void* dst, size_t cap) {

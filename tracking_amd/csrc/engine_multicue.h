@@ -2,9 +2,14 @@
 // (kernel_multicue_box.h, §5.14) and the whole-frame step that chains them as process() does; included inside bgs_hip.hip's anonymous
 // namespace.
 //
-// The class itself (BGS_MULTICUE, its ParamBlock constant and Family) is not here yet.  What is here is the bgs_multicue object of
-// include/bgs_hip.h, n_streams models that move in lock step, and mc_defaults / mc_check / mc_check_geometry with the signatures a
-// ParamBlock and a Family take.  Nothing here waits for the device except bgs_multicue_get_state, and no call allocates.
+// What is here is the bgs_multicue object of include/bgs_hip.h: n_streams models, each with a frame counter of its own.  A stream is
+// restarted alone (mc_reset_stream), any range of neighbouring streams is stepped in one call whatever their ages (mc_process_range), and
+// mc_process_host steps one stream on a frame in host memory.  The IBGS class SJN_MultiCueBGS (tracking_amd/host/bgs_classes_multicue.inc)
+// sits on a one-stream handle.  There is no bgs_algo for the class: BGS_ALGO_LAST, bgs_abi_version() and the type table stay as they are,
+// and the class is reached as an IBGS and through FrameProcessor.  mc_defaults / mc_check / mc_check_geometry have the
+// signatures a ParamBlock and a Family take.  Nothing here waits for the device except bgs_multicue_get_state and mc_process_host, and only
+// the first mc_process_host call allocates.  The host-side state is not locked: calls on one handle from several host threads are not
+// supported; disjoint ranges may be in flight on different HIP streams, since every plane and all scratch is indexed by stream.
 
 constexpr const char* kMcName = "SJN_MultiCueBGS";
 
@@ -43,8 +48,12 @@ struct McModel {
   int rows = 0, cols = 0;  // of the frames; fixed by the first training call
   int rw = 0, rh = 0;
   size_t n = 0;
-  int64_t count = 0;       // g_iFrameCount
-  bool have_landmark = false;
+  std::vector<int64_t> count;  // g_iFrameCount, one per stream; 0: the stream's next frame initialises its model (mc_reset_kernel)
+  bool have_landmark = false;  // of the piecewise calls, which need every stream at the same age: one flag serves them all
+  // bgs_multicue_process: a HIP stream, page-locked staging and device buffers for one frame and one image, made by its first call
+  hipStream_t h_stream = nullptr;
+  uint8_t *h_pin = nullptr, *h_dev = nullptr;
+  size_t h_frame = 0;          // bytes of a frame, rounded up to 256: where the image starts in both buffers
   int taps[7] = {0};
   uint8_t* arena = nullptr;  // one allocation; everything below points into it
   uint8_t *red = nullptr, *gauss = nullptr, *xyz = nullptr, *landmark = nullptr;
@@ -56,6 +65,9 @@ struct McModel {
   bgs::McPlanes tb{}, tc{}, cb{}, cc{};
   int16_t *tref = nullptr, *tcnt = nullptr, *cref = nullptr, *ccnt = nullptr;
   ~McModel() {
+    if (h_stream) (void)hipStreamSynchronize(h_stream), (void)hipStreamDestroy(h_stream);
+    if (h_pin) (void)hipHostFree(h_pin);
+    if (h_dev) (void)hipFree(h_dev);
     if (arena) (void)hipFree(arena);
   }
 };
@@ -99,6 +111,9 @@ int mc_create(int device, int n_streams, const bgs_multicue_params* p, McModel* 
   float cf[7];
   gaussian_kernel_f32(7, 0.7, cf);  // GaussianFiltering, :510-524
   for (int i = 0; i < 7; ++i) m->taps[i] = (int)std::lrintf(cf[i] * 256.f);
+  m->count.assign((size_t)n_streams, 0);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(BGS_ERR_HIP, "no HIP device visible: libbgs_hip has no CPU path");
   HIP_TRY(hipSetDevice(device));
   int rc = mc_allocate(*m);
   if (rc) return rc;
@@ -117,24 +132,35 @@ int mc_geometry(McModel& m, const char* fn, const void* d_frames, int rows, int 
   return BGS_OK;
 }
 
-// PreProcessing: reduce -> blur -> XYZ, three launches over all streams
-void mc_preprocess(McModel& m, const uint8_t* d_frames, hipStream_t s) {
-  const unsigned S = (unsigned)m.S;
-  hipLaunchKernelGGL(bgs::mc_reduce_kernel, dim3(blocks_for(m.n), S), dim3(bgs::kBlock), 0, s, d_frames, m.red, m.rows, m.cols, m.rh, m.rw, (double)m.rows / (double)m.rh,
-                     (double)m.cols / (double)m.rw);
+// Every launch below covers streams [k, k + c) of the handle: the kernels index their planes by the stream's place in the launch, so each
+// plane pointer is moved to stream k and d_frames, the maps and the outputs point at that stream's data.
+
+// PreProcessing: reduce -> blur -> XYZ, three launches.  It does not depend on a stream's age, so a range of mixed ages shares them.
+void mc_preprocess(McModel& m, int k, int c, const uint8_t* d_frames, hipStream_t s) {
+  const unsigned S = (unsigned)c;
+  const size_t at = (size_t)k * m.n * 3;
+  hipLaunchKernelGGL(bgs::mc_reduce_kernel, dim3(blocks_for(m.n), S), dim3(bgs::kBlock), 0, s, d_frames, m.red + at, m.rows, m.cols, m.rh, m.rw,
+                     (double)m.rows / (double)m.rh, (double)m.cols / (double)m.rw);
   bgs::BlurArgs b{};
-  b.src = m.red, b.dst = m.gauss, b.rows = m.rh, b.cols = m.rw;
+  b.src = m.red + at, b.dst = m.gauss + at, b.rows = m.rh, b.cols = m.rw;
   for (int i = 0; i < 7; ++i) b.k[i] = m.taps[i];
   const dim3 tiles((unsigned)((m.rw + bgs::kBlurTW - 1) / bgs::kBlurTW), (unsigned)((m.rh + bgs::kBlurTH - 1) / bgs::kBlurTH), S);
   hipLaunchKernelGGL((bgs::ingest_blur7_kernel<3>), tiles, dim3(bgs::kBlock), 0, s, b);
-  hipLaunchKernelGGL(bgs::mc_xyz_kernel, dim3(blocks_for((size_t)m.S * m.n)), dim3(bgs::kBlock), 0, s, (const uint8_t*)m.gauss, m.xyz, (size_t)m.S * m.n);
+  hipLaunchKernelGGL(bgs::mc_xyz_kernel, dim3(blocks_for((size_t)c * m.n)), dim3(bgs::kBlock), 0, s, (const uint8_t*)(m.gauss + at), m.xyz + at, (size_t)c * m.n);
 }
 
-bgs::McArgs mc_args(const McModel& m) {
+// one kind of book from stream k on: K books a stream, NM means of vsize bytes a slot
+bgs::McPlanes mc_planes_at(const bgs::McPlanes& pl, size_t K, size_t NM, size_t vsize, size_t k, size_t n) {
+  return bgs::McPlanes{pl.head + k * K * 2 * n, (uint8_t*)pl.mean + k * K * (size_t)pl.cap * NM * n * vsize, pl.meta + k * K * (size_t)pl.cap * 3 * n, pl.cap};
+}
+
+bgs::McArgs mc_args(const McModel& m, int first) {
   bgs::McArgs a{};
-  a.xyz = m.xyz, a.landmark = m.landmark, a.tb = m.tb, a.tc = m.tc, a.cb = m.cb, a.cc = m.cc;
-  a.tref = m.tref, a.tcnt = m.tcnt, a.cref = m.cref, a.ccnt = m.ccnt, a.overflow = m.overflow;
-  a.landmark_out = m.landmark, a.conf_out = m.conf;
+  const size_t k = (size_t)first, n = m.n;
+  a.xyz = m.xyz + k * n * 3, a.landmark = m.landmark + k * n;
+  a.tb = mc_planes_at(m.tb, 6, 1, 4, k, n), a.tc = mc_planes_at(m.tc, 6, 1, 4, k, n), a.cb = mc_planes_at(m.cb, 1, 3, 8, k, n), a.cc = mc_planes_at(m.cc, 1, 3, 8, k, n);
+  a.tref = m.tref + k * 6 * n, a.tcnt = m.tcnt + k * 6 * n, a.cref = m.cref + k * n, a.ccnt = m.ccnt + k * n, a.overflow = m.overflow;
+  a.landmark_out = m.landmark + k * n, a.conf_out = m.conf + k * n;
   a.n = (uint32_t)m.n, a.rw = m.rw, a.rh = m.rh;
   a.rate = m.p.learning_rate, a.conf_thr = (float)m.p.t_model_threshold / 6.f;  // g_fConfidenceThre, :54
   a.trange = m.p.texture_train_vol_range, a.crange = m.p.color_train_vol_range;
@@ -142,36 +168,85 @@ bgs::McArgs mc_args(const McModel& m) {
   return a;
 }
 
-void mc_launch_update(const McModel& m, const bgs::McArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(bgs::mc_update_kernel, dim3(blocks_for(m.n), (unsigned)bgs::kMcBooks, (unsigned)m.S), dim3(bgs::kBlock), 0, s, a);
+void mc_launch_update(const McModel& m, const bgs::McArgs& a, int c, hipStream_t s) {
+  hipLaunchKernelGGL(bgs::mc_update_kernel, dim3(blocks_for(m.n), (unsigned)bgs::kMcBooks, (unsigned)c), dim3(bgs::kBlock), 0, s, a);
+}
+
+// The phase of a stream's next frame, which is what neighbouring streams must share to go into one launch (what Family::key is for engines)
+enum McPhase { kMcTrain, kMcTrainLast, kMcDetect };
+McPhase mc_phase(const McModel& m, int k) {
+  const int64_t c = m.count[(size_t)k];
+  return c < m.p.training_period ? kMcTrain : c == m.p.training_period ? kMcTrainLast : kMcDetect;
+}
+// the end of the run of streams that starts at k and ends before `end`, all in k's phase
+int mc_run_end(const McModel& m, int k, int end) {
+  int e = k + 1;
+  while (e < end && mc_phase(m, e) == mc_phase(m, k)) ++e;
+  return e;
+}
+
+// The piecewise calls work on every stream at once and keep one protocol state for all of them
+int mc_lock_step(const McModel& m, const char* fn) {
+  for (int k = 1; k < m.S; ++k)
+    if (m.count[(size_t)k] != m.count[0])
+      return fail(BGS_ERR_STATE, "%s: the streams are not all the same age (stream 0 has seen %lld frames, stream %d %lld): use bgs_multicue_process_range_device", fn,
+                  (long long)m.count[0], k, (long long)m.count[(size_t)k]);
+  return BGS_OK;
+}
+
+// BackgroundModeling_Par on the preprocessed frames of a run of training streams [k, e) in one phase.  Streams at frame 0 get their model
+// initialised first, on the same HIP stream: one mc_reset_kernel launch per run of neighbours among them.
+void mc_train_run(McModel& m, int k, int e, hipStream_t s) {
+  for (int i = k; i < e;) {
+    if (m.count[(size_t)i] != 0) {
+      ++i;
+      continue;
+    }
+    int j = i + 1;
+    while (j < e && m.count[(size_t)j] == 0) ++j;
+    hipLaunchKernelGGL(bgs::mc_reset_kernel, dim3(blocks_for(m.n), (unsigned)(j - i)), dim3(bgs::kBlock), 0, s, mc_args(m, i));
+    i = j;
+  }
+  bgs::McArgs a = mc_args(m, k);
+  const bool last = mc_phase(m, k) == kMcTrainLast;  // BackgroundModeling_Par's step 3, with nClearNum = training_period
+  a.mode = last ? 1 : 0, a.clear_period = m.p.training_period;
+  a.rate = m.p.learning_rate * 4;  // float
+  mc_launch_update(m, a, e - k, s);
+  for (int i = k; i < e; ++i) m.count[(size_t)i] += last ? 2 : 1;  // :308 and :87
+}
+
+void mc_landmark_run(McModel& m, int k, int e, uint8_t* d_landmark, float* d_conf, hipStream_t s) {
+  bgs::McArgs a = mc_args(m, k);
+  a.landmark_copy = d_landmark, a.conf_copy = d_conf;
+  hipLaunchKernelGGL(bgs::mc_landmark_kernel, dim3(blocks_for(m.n), (unsigned)(e - k)), dim3(bgs::kBlock), 0, s, a);
+}
+
+void mc_update_run(McModel& m, int k, int e, const uint8_t* d_map, int ghost, hipStream_t s) {
+  bgs::McArgs a = mc_args(m, k);
+  a.map = d_map, a.mode = ghost ? 2 : 3;
+  mc_launch_update(m, a, e - k, s);
 }
 
 int mc_train(McModel& m, const void* d_frames, int rows, int cols, hipStream_t s) {
-  int rc = mc_geometry(m, "bgs_multicue_train_device", d_frames, rows, cols, true);
-  if (rc) return rc;
-  if (m.count > m.p.training_period) return fail(BGS_ERR_STATE, "bgs_multicue_train_device: training is complete after %d frames", m.p.training_period + 1);
+  int rc = mc_lock_step(m, "bgs_multicue_train_device");
+  if (rc || (rc = mc_geometry(m, "bgs_multicue_train_device", d_frames, rows, cols, true))) return rc;
+  if (m.count[0] > m.p.training_period) return fail(BGS_ERR_STATE, "bgs_multicue_train_device: training is complete after %d frames", m.p.training_period + 1);
   HIP_TRY(hipSetDevice(m.device));
-  mc_preprocess(m, (const uint8_t*)d_frames, s);
-  bgs::McArgs a = mc_args(m);
-  const bool last = m.count == m.p.training_period;  // BackgroundModeling_Par's step 3, with nClearNum = training_period
-  a.mode = last ? 1 : 0, a.clear_period = m.p.training_period;
-  a.rate = m.p.learning_rate * 4;  // float
-  mc_launch_update(m, a, s);
+  mc_preprocess(m, 0, m.S, (const uint8_t*)d_frames, s);
+  mc_train_run(m, 0, m.S, s);
   HIP_TRY(hipGetLastError());
-  m.count += last ? 2 : 1;  // :308 and :87
   return BGS_OK;
 }
 
 int mc_landmark(McModel& m, const void* d_frames, int rows, int cols, void* d_landmark, void* d_conf, hipStream_t s) {
   if (!d_landmark) return fail(BGS_ERR_INVALID, "bgs_multicue_landmark_device: d_landmark is NULL");
-  if (m.count <= m.p.training_period) return fail(BGS_ERR_STATE, "bgs_multicue_landmark_device: training is not complete (%d frames)", m.p.training_period + 1);
-  int rc = mc_geometry(m, "bgs_multicue_landmark_device", d_frames, rows, cols, false);
+  int rc = mc_lock_step(m, "bgs_multicue_landmark_device");
   if (rc) return rc;
+  if (m.count[0] <= m.p.training_period) return fail(BGS_ERR_STATE, "bgs_multicue_landmark_device: training is not complete (%d frames)", m.p.training_period + 1);
+  if ((rc = mc_geometry(m, "bgs_multicue_landmark_device", d_frames, rows, cols, false))) return rc;
   HIP_TRY(hipSetDevice(m.device));
-  mc_preprocess(m, (const uint8_t*)d_frames, s);
-  bgs::McArgs a = mc_args(m);
-  a.landmark_copy = (uint8_t*)d_landmark, a.conf_copy = (float*)d_conf;
-  hipLaunchKernelGGL(bgs::mc_landmark_kernel, dim3(blocks_for(m.n), (unsigned)m.S), dim3(bgs::kBlock), 0, s, a);
+  mc_preprocess(m, 0, m.S, (const uint8_t*)d_frames, s);
+  mc_landmark_run(m, 0, m.S, (uint8_t*)d_landmark, (float*)d_conf, s);
   HIP_TRY(hipGetLastError());
   m.have_landmark = true;
   return BGS_OK;
@@ -179,35 +254,36 @@ int mc_landmark(McModel& m, const void* d_frames, int rows, int cols, void* d_la
 
 int mc_update(McModel& m, const void* d_map, int ghost, hipStream_t s) {
   if (!d_map || (ghost != 0 && ghost != 1)) return fail(BGS_ERR_INVALID, "bgs_multicue_update_device: bad argument");
+  int rc = mc_lock_step(m, "bgs_multicue_update_device");
+  if (rc) return rc;
   if (!m.have_landmark) return fail(BGS_ERR_STATE, "bgs_multicue_update_device: no bgs_multicue_landmark_device call since the last update");
   HIP_TRY(hipSetDevice(m.device));
-  bgs::McArgs a = mc_args(m);
-  a.map = (const uint8_t*)d_map, a.mode = ghost ? 2 : 3;
-  mc_launch_update(m, a, s);
+  mc_update_run(m, 0, m.S, (const uint8_t*)d_map, ghost, s);
   HIP_TRY(hipGetLastError());
   if (!ghost) m.have_landmark = false;
   return BGS_OK;
 }
 
-// PostProcessing and step 1 of UpdateModel_Par: three launches over all streams (kernel_multicue_box.h, compiled in bgs_multicue_box.hip)
-void mc_launch_boxes(McModel& m, const uint8_t* d_landmark, const uint8_t* d_frames, uint8_t* d_fore, uint8_t* d_ghost, uint8_t* d_update, int* d_count, int* d_boxes,
-                     hipStream_t s) {
+// PostProcessing and step 1 of UpdateModel_Par: three launches over streams [k, k + c) (kernel_multicue_box.h, compiled in bgs_multicue_box.hip).
+// The caller's pointers are stream k's; the handle's own scratch is moved here.
+void mc_launch_boxes(McModel& m, int k, int c, const uint8_t* d_landmark, const uint8_t* d_frames, uint8_t* d_fore, uint8_t* d_ghost, uint8_t* d_update, int* d_count,
+                     int* d_boxes, hipStream_t s) {
   bgs::McBoxArgs a{};
-  a.landmark = d_landmark, a.frames = d_frames, a.fore0 = m.fore0, a.grey = m.grey, a.fore = d_fore, a.ghost = d_ghost, a.update = d_update;
+  a.landmark = d_landmark, a.frames = d_frames, a.fore0 = m.fore0 + (size_t)k * m.n, a.grey = m.grey + (size_t)k * m.n, a.fore = d_fore, a.ghost = d_ghost, a.update = d_update;
   a.count = d_count, a.boxes = d_boxes, a.box_overflow = m.box_overflow;
   a.rows = m.rows, a.cols = m.cols, a.rw = m.rw, a.rh = m.rh;
   a.inv_fy = 1.0 / ((double)m.rh / (double)m.rows), a.inv_fx = 1.0 / ((double)m.rw / (double)m.cols);
   a.fh = (double)m.rows / (double)m.rh, a.fw = (double)m.cols / (double)m.rw;
-  bgs::mc_box_launch(a, (unsigned)m.S, s);
+  bgs::mc_box_launch(a, (unsigned)c, s);
 }
 
 int mc_boxes(McModel& m, const void* d_landmark, const void* d_frames, int rows, int cols, void* d_fore, void* d_ghost, void* d_update, void* d_count, void* d_boxes,
              hipStream_t s) {
   if (!d_landmark || !d_fore || !d_ghost || !d_update || !d_count || !d_boxes) return fail(BGS_ERR_INVALID, "bgs_multicue_boxes_device: NULL argument");
-  int rc = mc_geometry(m, "bgs_multicue_boxes_device", d_frames, rows, cols, true);
-  if (rc) return rc;
+  int rc = mc_lock_step(m, "bgs_multicue_boxes_device");
+  if (rc || (rc = mc_geometry(m, "bgs_multicue_boxes_device", d_frames, rows, cols, true))) return rc;
   HIP_TRY(hipSetDevice(m.device));
-  mc_launch_boxes(m, (const uint8_t*)d_landmark, (const uint8_t*)d_frames, (uint8_t*)d_fore, (uint8_t*)d_ghost, (uint8_t*)d_update, (int*)d_count, (int*)d_boxes, s);
+  mc_launch_boxes(m, 0, m.S, (const uint8_t*)d_landmark, (const uint8_t*)d_frames, (uint8_t*)d_fore, (uint8_t*)d_ghost, (uint8_t*)d_update, (int*)d_count, (int*)d_boxes, s);
   HIP_TRY(hipGetLastError());
   return BGS_OK;
 }
@@ -217,27 +293,82 @@ int mc_boxes(McModel& m, const void* d_landmark, const void* d_frames, int rows,
 void mc_launch_resize(const bgs::IngestArgs& g, unsigned streams, hipStream_t s);
 
 // process(), SJN_MultiCueBGS.cpp:85-99: a training frame and zeros, or ForegroundExtraction, UpdateModel_Par and GetForegroundMap(result, NULL)
-int mc_process(McModel& m, const void* d_frames, int rows, int cols, void* d_out, hipStream_t s) {
-  if (!d_out) return fail(BGS_ERR_INVALID, "bgs_multicue_process_device: d_out is NULL");
-  if (m.have_landmark) return fail(BGS_ERR_STATE, "bgs_multicue_process_device: a bgs_multicue_landmark_device call is waiting for its updates");
-  if (m.count <= m.p.training_period) {
-    int rc = mc_train(m, d_frames, rows, cols, s);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(d_out, 0, (size_t)m.S * rows * cols, s));
-    return BGS_OK;
-  }
-  int rc = mc_landmark(m, d_frames, rows, cols, m.s_landmark, nullptr, s);
+// for streams [first, first + count), which may be at different ages: the three PreProcessing launches once for the whole range, then every
+// run of neighbours in one phase with one launch per kernel.  In lock step that is one run, and the launches are those of one stream.
+int mc_process_range(McModel& m, const char* fn, int first, int count, const void* d_frames, int rows, int cols, void* d_out, hipStream_t s) {
+  if (first < 0 || count < 1 || first > m.S - count) return fail(BGS_ERR_INVALID, "%s: streams %d..%d outside 0..%d", fn, first, first + count - 1, m.S - 1);
+  if (!d_out) return fail(BGS_ERR_INVALID, "%s: d_out is NULL", fn);
+  if (m.have_landmark) return fail(BGS_ERR_STATE, "%s: a bgs_multicue_landmark_device call is waiting for its updates", fn);
+  int rc = mc_geometry(m, fn, d_frames, rows, cols, true);
   if (rc) return rc;
-  mc_launch_boxes(m, m.s_landmark, (const uint8_t*)d_frames, m.s_fore, m.s_ghost, m.s_update, m.s_count, m.s_boxes, s);
+  HIP_TRY(hipSetDevice(m.device));
+  const size_t n = m.n, px = (size_t)rows * cols;
+  const int end = first + count;
+  mc_preprocess(m, first, count, (const uint8_t*)d_frames, s);
+  for (int k = first, e; k < end; k = e) {
+    e = mc_run_end(m, k, end);
+    const uint8_t* frames = (const uint8_t*)d_frames + (size_t)(k - first) * px * 3;
+    uint8_t* out = (uint8_t*)d_out + (size_t)(k - first) * px;
+    if (mc_phase(m, k) != kMcDetect) {
+      mc_train_run(m, k, e, s);
+      HIP_TRY(hipMemsetAsync(out, 0, (size_t)(e - k) * px, s));
+      continue;
+    }
+    uint8_t *lm = m.s_landmark + (size_t)k * n, *fore = m.s_fore + (size_t)k * n, *ghost = m.s_ghost + (size_t)k * n, *update = m.s_update + (size_t)k * n;
+    mc_landmark_run(m, k, e, lm, nullptr, s);
+    mc_launch_boxes(m, k, e - k, lm, frames, fore, ghost, update, m.s_count + k, m.s_boxes + (size_t)k * bgs::kMcMaxBoxes * bgs::kMcBoxFields, s);
+    mc_update_run(m, k, e, ghost, 1, s);
+    mc_update_run(m, k, e, update, 0, s);
+    // cvResize(temp_image, return_image): the foreground map, bilinear, to the frame's size (kernel_ingest.h; the three channels are equal)
+    bgs::IngestArgs g{};
+    g.src = fore, g.dst = out, g.src_rows = m.rh, g.src_cols = m.rw, g.rw = cols, g.rh = rows, g.rows = rows, g.cols = cols, g.src_step = (size_t)m.rw;
+    g.scale_x = 1. / ((double)cols / m.rw), g.scale_y = 1. / ((double)rows / m.rh);
+    g.mode = (m.rw == 2 * cols && m.rh == 2 * rows) ? 2 : 1;
+    mc_launch_resize(g, (unsigned)(e - k), s);
+  }
   HIP_TRY(hipGetLastError());
-  if ((rc = mc_update(m, m.s_ghost, 1, s)) || (rc = mc_update(m, m.s_update, 0, s))) return rc;
-  // cvResize(temp_image, return_image): the foreground map, bilinear, to the frame's size (kernel_ingest.h; the three channels are equal)
-  bgs::IngestArgs g{};
-  g.src = m.s_fore, g.dst = (uint8_t*)d_out, g.src_rows = m.rh, g.src_cols = m.rw, g.rw = cols, g.rh = rows, g.rows = rows, g.cols = cols, g.src_step = (size_t)m.rw;
-  g.scale_x = 1. / ((double)cols / m.rw), g.scale_y = 1. / ((double)rows / m.rh);
-  g.mode = (m.rw == 2 * cols && m.rh == 2 * rows) ? 2 : 1;
-  mc_launch_resize(g, (unsigned)m.S, s);
-  HIP_TRY(hipGetLastError());
+  return BGS_OK;
+}
+
+// host-only: the stream's next frame is training frame 0, and until then bgs_multicue_get_state shows what a new handle shows
+int mc_reset_stream(McModel& m, int stream) {
+  if (stream < 0 || stream >= m.S) return fail(BGS_ERR_INVALID, "bgs_multicue_reset_stream: stream %d outside 0..%d", stream, m.S - 1);
+  m.count[(size_t)stream] = 0;
+  m.have_landmark = false;  // a piecewise landmark call that waited for its updates is dropped: its streams are no longer the same age, or all start again
+  return BGS_OK;
+}
+
+// One stream, a frame in host memory, synchronous: upload, the range call for that stream, download of the one-channel image; the host
+// writes out_channels equal channels.  The HIP stream and the staging are made here, by the first call: the geometry is known then.
+int mc_process_host(McModel& m, int stream, const void* frame, int rows, int cols, size_t step, void* out, size_t out_step, int out_channels) {
+  const char* fn = "bgs_multicue_process";
+  if (!frame || !out || rows <= 0 || cols <= 0) return fail(BGS_ERR_INVALID, "%s: bad argument", fn);
+  if (stream < 0 || stream >= m.S) return fail(BGS_ERR_INVALID, "%s: stream %d outside 0..%d", fn, stream, m.S - 1);
+  if (out_channels != 1 && out_channels != 3) return fail(BGS_ERR_INVALID, "%s: out_channels must be 1 or 3", fn);
+  const size_t row = (size_t)cols * 3, px = (size_t)rows * cols;
+  if (step < row || out_step < (size_t)cols * out_channels)
+    return fail(BGS_ERR_INVALID, "%s: row pitches %zu and %zu are below the row sizes %zu and %zu", fn, step, out_step, row, (size_t)cols * out_channels);
+  int rc = mc_geometry(m, fn, frame, rows, cols, true);  // fixes the handle's geometry if nothing has yet: the staging below never changes size
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(m.device));
+  m.h_frame = (px * 3 + 255) & ~(size_t)255;
+  if (!m.h_pin) HIP_TRY(hipHostMalloc((void**)&m.h_pin, m.h_frame + px, hipHostMallocDefault));
+  if (!m.h_dev) HIP_TRY(hipMalloc((void**)&m.h_dev, m.h_frame + px));
+  if (!m.h_stream) HIP_TRY(hipStreamCreateWithFlags(&m.h_stream, hipStreamNonBlocking));
+  for (int y = 0; y < rows; ++y) std::memcpy(m.h_pin + (size_t)y * row, (const uint8_t*)frame + (size_t)y * step, row);
+  HIP_TRY(hipMemcpyAsync(m.h_dev, m.h_pin, px * 3, hipMemcpyHostToDevice, m.h_stream));
+  if ((rc = mc_process_range(m, fn, stream, 1, m.h_dev, rows, cols, m.h_dev + m.h_frame, m.h_stream))) return rc;
+  HIP_TRY(hipMemcpyAsync(m.h_pin + m.h_frame, m.h_dev + m.h_frame, px, hipMemcpyDeviceToHost, m.h_stream));
+  HIP_TRY(hipStreamSynchronize(m.h_stream));
+  const uint8_t* img = m.h_pin + m.h_frame;
+  for (int y = 0; y < rows; ++y) {
+    uint8_t* d = (uint8_t*)out + (size_t)y * out_step;
+    const uint8_t* q = img + (size_t)y * cols;
+    if (out_channels == 1)
+      std::memcpy(d, q, (size_t)cols);
+    else
+      for (int x = 0; x < cols; ++x) d[3 * x] = d[3 * x + 1] = d[3 * x + 2] = q[x];
+  }
   return BGS_OK;
 }
 
@@ -276,13 +407,30 @@ int64_t mc_get_state(McModel& m, int stream, const char* plane, void* dst, size_
   HIP_TRY(hipSetDevice(m.device));
   HIP_TRY(hipDeviceSynchronize());
   const size_t n = m.n, k = (size_t)stream;
+  if (!strcmp(plane, "count")) return copy_host(plane, dst, cap, &m.count[k], 8);
+  if (!strcmp(plane, "overflow")) return copy_plane(plane, dst, cap, m.overflow, 8);
+  if (!strcmp(plane, "box_overflow")) return copy_plane(plane, dst, cap, m.box_overflow, 8);
+  if (m.count[k] == 0) {
+    // before its frame 0 a stream shows a new handle's planes whatever the device still holds of an earlier life (mc_reset_stream does not
+    // touch the device): the referred indices -1, everything else 0
+    const struct { const char* name; size_t bytes; int fill; } fresh[] = {
+        {"gauss", n * 3, 0}, {"xyz", n * 3, 0}, {"conf", n * 4, 0}, {"landmark", n, 0}, {"tref", n * 12, 0xff}, {"tcnt", n * 12, 0}, {"cref", n * 2, 0xff}, {"ccnt", n * 2, 0},
+        {"tbook", n * 48, 0}, {"tcache", n * 48, 0}, {"cbook", n * 8, 0}, {"ccache", n * 8, 0},
+        {"tmeans", n * 6 * bgs::kMcTSlots * 4, 0}, {"tcache_means", n * 6 * bgs::kMcTCacheSlots * 4, 0}, {"tmeta", n * 6 * bgs::kMcTSlots * 12, 0},
+        {"tcache_meta", n * 6 * bgs::kMcTCacheSlots * 12, 0}, {"cmeans", n * bgs::kMcCSlots * 24, 0}, {"ccache_means", n * bgs::kMcCCacheSlots * 24, 0},
+        {"cmeta", n * bgs::kMcCSlots * 12, 0}, {"ccache_meta", n * bgs::kMcCCacheSlots * 12, 0}};
+    for (const auto& f : fresh) {
+      if (strcmp(plane, f.name)) continue;
+      if (cap < f.bytes) return too_small(plane);
+      std::memset(dst, f.fill, f.bytes);
+      return (int64_t)f.bytes;
+    }
+    return fail(BGS_ERR_INVALID, "bgs_multicue_get_state: unknown plane %s", plane);
+  }
   if (!strcmp(plane, "gauss")) return copy_plane(plane, dst, cap, m.gauss + k * n * 3, n * 3);
   if (!strcmp(plane, "xyz")) return copy_plane(plane, dst, cap, m.xyz + k * n * 3, n * 3);
   if (!strcmp(plane, "conf")) return copy_plane(plane, dst, cap, m.conf + k * n, n * 4);
   if (!strcmp(plane, "landmark")) return copy_plane(plane, dst, cap, m.landmark + k * n, n);
-  if (!strcmp(plane, "count")) return copy_host(plane, dst, cap, &m.count, 8);
-  if (!strcmp(plane, "overflow")) return copy_plane(plane, dst, cap, m.overflow, 8);
-  if (!strcmp(plane, "box_overflow")) return copy_plane(plane, dst, cap, m.box_overflow, 8);
   if (!strcmp(plane, "cref")) return copy_plane(plane, dst, cap, m.cref + k * n, n * 2);
   if (!strcmp(plane, "ccnt")) return copy_plane(plane, dst, cap, m.ccnt + k * n, n * 2);
   if (!strcmp(plane, "tref") || !strcmp(plane, "tcnt")) {

@@ -7,6 +7,7 @@
 //                       T_/C_ClearNonEssentialEntriesForCachebook :1494 / :1965, T_/C_Absorption :1612 / :2025, in the orders of
 //                       BackgroundModeling_Par :274, EvaluateGhostRegion :1029-1046 and UpdateModel_Par :384-427: ONE launch per call
 //   mc_landmark_kernel  T_GetConfidenceMap_Par :1567, CreateLandmarkArray_Par :434
+//   mc_reset_kernel     what Initialize :136 leaves of a model, for the streams whose next frame is frame 0, on the launch stream
 //
 // The books are fixed-capacity slot planes, [stream][book][slot][field][pixel]: every access of a wave is to consecutive pixels of one
 // plane.  A pixel has seven independent background books (six texture neighbours and the colour book) and as many cache-books, so the
@@ -256,6 +257,33 @@ __global__ __launch_bounds__(kBlock) void mc_update_kernel(const McArgs a) {
     McBook<double, 3> bg(a.cb, st, n, i), ca(a.cc, st, n, i);
     mc_book_step(a, bg, ca, s, a.crange, a.cref + st * n + i, a.ccnt + st * n + i, on, lm255);
   }
+}
+
+// grid (blocks of pixels, streams): what a stream's frame 0 must find, written on the stream that frame is launched on (a new handle
+// and a stream after bgs_multicue_reset_stream alike).  The planes a later kernel reads before it writes them:
+//   the four heads (m_iTotal, m_iNumEntries)  0: mc_construct reads both; with m_iNumEntries 0 no slot of mean / meta is read, and
+//                                             bgs_multicue_get_state shows slots at and beyond it as 0, so those planes stay as they are
+//   tref / cref -1, tcnt / ccnt 0             the cache-book path of mode 3 compares and counts them; training writes tref / cref only with
+//                                             absorption on, and never the counts
+//   conf / landmark 0                         read by no kernel before mc_landmark_kernel writes every pixel of them (the 2-pixel border
+//                                             included), but a training stream shows them through bgs_multicue_get_state
+// Everything else is written whole before it is read: red / gauss / xyz by the three PreProcessing launches of every frame, the scratch
+// maps, the counts and the boxes of the whole-frame step by mc_landmark_kernel, mc_box_prepare_kernel and mc_box_label_kernel.
+__global__ __launch_bounds__(kBlock) void mc_reset_kernel(const McArgs a) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= a.n) return;
+  const size_t n = a.n, st = blockIdx.y;
+#pragma unroll
+  for (size_t k = 0; k < 6; ++k) {
+    const size_t book = st * 6 + k;
+    a.tb.head[book * 2 * n + i] = 0, a.tb.head[(book * 2 + 1) * n + i] = 0;
+    a.tc.head[book * 2 * n + i] = 0, a.tc.head[(book * 2 + 1) * n + i] = 0;
+    a.tref[book * n + i] = -1, a.tcnt[book * n + i] = 0;
+  }
+  a.cb.head[st * 2 * n + i] = 0, a.cb.head[(st * 2 + 1) * n + i] = 0;
+  a.cc.head[st * 2 * n + i] = 0, a.cc.head[(st * 2 + 1) * n + i] = 0;
+  a.cref[st * n + i] = -1, a.ccnt[st * n + i] = 0;
+  a.conf_out[st * n + i] = 0.f, a.landmark_out[st * n + i] = 0;
 }
 
 // grid (blocks of pixels, streams): T_GetConfidenceMap_Par and CreateLandmarkArray_Par

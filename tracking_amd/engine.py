@@ -310,9 +310,11 @@ def multicue_xyz(bgr, device=0, hip_stream=None):
 
 
 class MultiCueModel:
-    """SJN_MultiCueBGS without its class plumbing (bgs_multicue, include/bgs_hip.h): n_streams models that move in lock step.  Frames are torch
+    """SJN_MultiCueBGS as a bgs_multicue handle (include/bgs_hip.h): n_streams models, each with a frame counter of its own.  Frames are torch
     CUDA uint8 [n_streams][rows][cols][3] (or [rows][cols][3] for one stream); maps come back and go in as [n_streams][rh][rw].
-    process(frames) is the reference's process(); train / landmark / boxes / update are its parts."""
+    process(frames) is the reference's process(), on all streams or on a range of them whatever their ages; reset_stream restarts one
+    camera; process_host takes a frame in host memory; train / landmark / boxes / update are process()'s parts and need every stream at the
+    same age."""
 
     def __init__(self, params=None, device=0, n_streams=1):
         self._h = C.c_void_p()
@@ -385,13 +387,40 @@ class MultiCueModel:
                                                         self._stream(hip_stream)))
         return fore, ghost, upd, count, boxes
 
-    def process(self, frames, hip_stream=None):
-        """The reference's process() on one frame per stream (bgs_multicue_process_device): the foreground image, torch uint8
-        [n_streams][rows][cols]; zeros while the model trains."""
+    def process(self, frames, first=0, count=None, hip_stream=None):
+        """The reference's process() on one frame per stream of [first, first + count) (bgs_multicue_process_range_device; count None: every
+        stream from `first` on): the foreground image, torch uint8 [count][rows][cols]; zeros for a stream whose model trains.  The streams
+        may be at different ages, and disjoint ranges may run on different HIP streams."""
         import torch
-        f = self._frames(frames)
-        out = torch.empty((self.n_streams, f.shape[1], f.shape[2]), dtype=torch.uint8, device=f.device)
-        capi.check(capi.lib().bgs_multicue_process_device(self._h, C.c_void_p(f.data_ptr()), f.shape[1], f.shape[2], C.c_void_p(out.data_ptr()), self._stream(hip_stream)))
+        if count is None:
+            count = self.n_streams - first
+        if frames.dim() == 3:
+            frames = frames[None]
+        assert (count < 1 or frames.shape[0] == count) and frames.shape[3] == 3 and frames.dtype.itemsize == 1  # a count below 1 is the library's to refuse
+        f = frames.contiguous()
+        out = torch.empty((max(count, 0), f.shape[1], f.shape[2]), dtype=torch.uint8, device=f.device)
+        capi.check(capi.lib().bgs_multicue_process_range_device(self._h, first, count, C.c_void_p(f.data_ptr()), f.shape[1], f.shape[2], C.c_void_p(out.data_ptr()),
+                                                                self._stream(hip_stream)))
+        return out
+
+    def reset_stream(self, stream):
+        """The stream's next frame is training frame 0 (bgs_multicue_reset_stream); the other streams go on."""
+        capi.check(capi.lib().bgs_multicue_reset_stream(self._h, stream))
+
+    def frames_seen(self, stream=0):
+        """The stream's g_iFrameCount: 0 before its frame 0, training_period + 2 after the last training frame."""
+        return int(self.state("count", stream)[0])
+
+    def process_host(self, frame, stream=0, channels=1):
+        """process() on one frame in host memory (bgs_multicue_process), synchronous: frame is a numpy uint8 [rows][cols][3] whose rows may be
+        padded (any positive row pitch, pixels contiguous within a row).  Returns numpy uint8 [rows][cols] or, channels == 3, [rows][cols][3]."""
+        assert frame.ndim == 3 and frame.shape[2] == 3 and frame.dtype.itemsize == 1
+        if frame.strides[2] != 1 or frame.strides[1] != 3 or frame.strides[0] <= 0:
+            frame = np.ascontiguousarray(frame)
+        rows, cols = frame.shape[:2]
+        out = np.empty((rows, cols) if channels == 1 else (rows, cols, channels), np.uint8)
+        capi.check(capi.lib().bgs_multicue_process(self._h, stream, C.c_void_p(frame.ctypes.data), rows, cols, frame.strides[0], out.ctypes.data_as(C.c_void_p),
+                                                   cols * channels, channels))
         return out
 
     def state(self, plane, stream=0):

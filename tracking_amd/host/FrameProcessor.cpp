@@ -33,6 +33,7 @@ FrameProcessor::FrameProcessor()
   vuMeter = nullptr, enableVuMeter = false;
   kde = nullptr, enableKDE = false;
   imbs = nullptr, enableIMBS = false;
+  mcbgs = nullptr, enableMultiCueBGS = false;
   multiLayerBGS = nullptr, enableMultiLayerBGS = false;
   sdbgs = nullptr, enableSigmaDeltaBGS = false;
   ssbgs = nullptr, enableSuBSENSEBGS = false;
@@ -75,6 +76,7 @@ void FrameProcessor::init() {  // FrameProcessor.cpp:35-155
   if (enableVuMeter) vuMeter = new VuMeter;  // :132
   if (enableKDE) kde = new KDE;  // after VuMeter, before IMBS (:135)
   if (enableIMBS) imbs = new IndependentMultimodalBGS;  // :138-139
+  if (enableMultiCueBGS) mcbgs = new SJN_MultiCueBGS;  // :141-142
   if (enableMultiLayerBGS) multiLayerBGS = new MultiLayerBGS;  // :126-127
   if (enableSigmaDeltaBGS) sdbgs = new SigmaDeltaBGS;
   if (enableSuBSENSEBGS) ssbgs = new SuBSENSEBGS;
@@ -156,6 +158,7 @@ void FrameProcessor::process(const Image& img_input) {  // :169-340
   if (enableVuMeter) process("VuMeter", vuMeter, img_prep, img_vumeter);  // :272
   if (enableKDE) process("KDE", kde, img_prep, img_kde);  // :275
   if (enableIMBS) process("IMBS", imbs, img_prep, img_imbs);  // :278-279
+  if (enableMultiCueBGS) process("MultiCueBGS", mcbgs, img_prep, img_mcbgs);  // :281-282
   if (enableMultiLayerBGS) {  // :262-266
     multiLayerBGS->setStatus(MultiLayerBGS::MLBGS_LEARN);
     process("MultiLayerBGS", multiLayerBGS, img_prep, img_mlbgs);
@@ -173,6 +176,7 @@ void FrameProcessor::finish() {  // :342-482 (reverse order of init)
   delete lobgs, lobgs = nullptr;
   delete ssbgs, ssbgs = nullptr;
   delete sdbgs, sdbgs = nullptr;
+  delete mcbgs, mcbgs = nullptr;  // :374-375
   delete imbs, imbs = nullptr;  // :377-378
   delete multiLayerBGS, multiLayerBGS = nullptr;
   delete kde, kde = nullptr;
@@ -250,6 +254,7 @@ void FrameProcessor::saveConfig() {  // :496-552 (keys of the classes this build
   fs.writeInt("enableVuMeter", enableVuMeter);  // :543
   fs.writeInt("enableKDE", enableKDE);  // :544
   fs.writeInt("enableIMBS", enableIMBS);  // :545
+  fs.writeInt("enableMultiCueBGS", enableMultiCueBGS);  // :546
   fs.writeInt("enableMultiLayerBGS", enableMultiLayerBGS);
   fs.writeInt("enableSigmaDeltaBGS", enableSigmaDeltaBGS);
   fs.writeInt("enableSuBSENSEBGS", enableSuBSENSEBGS);
@@ -291,6 +296,7 @@ void FrameProcessor::loadConfig() {  // :554-610 (defaults: PreProcessor and Fra
   enableVuMeter = fs.readInt("enableVuMeter", false);  // :601
   enableKDE = fs.readInt("enableKDE", false);  // :602
   enableIMBS = fs.readInt("enableIMBS", false);  // :603
+  enableMultiCueBGS = fs.readInt("enableMultiCueBGS", false);  // :604
   enableMultiLayerBGS = fs.readInt("enableMultiLayerBGS", false);
   enableSigmaDeltaBGS = fs.readInt("enableSigmaDeltaBGS", false);
   enableSuBSENSEBGS = fs.readInt("enableSuBSENSEBGS", false);

@@ -39,6 +39,7 @@ class FrameProcessor : public IFrameProcessor {
   Image img_gmg, img_adpmed, img_grigmm, img_zivgmm, img_tmpmean, img_wrenga, img_pramed, img_texbgs, img_kde, img_sdbgs, img_ssbgs, img_lobgs;  // FrameProcessor.h:120-236
   Image img_eigbkg;  // FrameProcessor.h (reference): img_eigbkg
   Image img_imbs;  // FrameProcessor.h:221 (reference): img_imbs
+  Image img_mcbgs;  // FrameProcessor.h:225 (reference): img_mcbgs, 8UC3 with equal channels
   Image img_mlbgs;  // FrameProcessor.h (reference): img_mlbgs
   Image img_t2fgmm_um, img_t2fgmm_uv;  // FrameProcessor.h (reference): img_t2fgmm_um / img_t2fgmm_uv
   Image img_fsi, img_fci;  // FrameProcessor.h (reference): FuzzySugenoIntegral / FuzzyChoquetIntegral masks
@@ -113,6 +114,8 @@ class FrameProcessor : public IFrameProcessor {
   bool enableKDE;
   IndependentMultimodalBGS* imbs;  // FrameProcessor.h:222-223
   bool enableIMBS;
+  SJN_MultiCueBGS* mcbgs;  // FrameProcessor.h:225-227
+  bool enableMultiCueBGS;
   MultiLayerBGS* multiLayerBGS;  // FrameProcessor.h (reference): multiLayerBGS / enableMultiLayerBGS
   bool enableMultiLayerBGS;
   SigmaDeltaBGS* sdbgs;

@@ -5,9 +5,9 @@
 //   AdaptiveBackgroundLearning, AdaptiveSelectiveBackgroundLearning, MixtureOfGaussianV1BGS, MixtureOfGaussianV2BGS, GMG,
 //   SigmaDeltaBGS, SuBSENSEBGS, LOBSTERBGS, DPZivkovicAGMMBGS, DPGrimsonGMMBGS, DPWrenGABGS, DPMeanBGS, DPAdaptiveMedianBGS, KDE,
 //   DPPratiMediodBGS, DPTextureBGS, LBSimpleGaussian, LBFuzzyGaussian, LBMixtureOfGaussians, LBAdaptiveSOM, LBFuzzyAdaptiveSOM, VuMeter,
-//   FuzzySugenoIntegral, FuzzyChoquetIntegral, T2FGMM_UM, T2FGMM_UV, DPEigenbackgroundBGS, IndependentMultimodalBGS, MultiLayerBGS
+//   FuzzySugenoIntegral, FuzzyChoquetIntegral, T2FGMM_UM, T2FGMM_UV, DPEigenbackgroundBGS, IndependentMultimodalBGS, MultiLayerBGS, SJN_MultiCueBGS
 // Each reads / writes the same ./config/<Class>.xml with the same keys and defaults as the class it stands in for
-// (the list is bgs_classes.inc + bgs_classes_kde.inc + bgs_classes_dp2.inc + bgs_classes_lb.inc + bgs_classes_vumeter.inc + bgs_classes_fuzzy.inc + bgs_classes_t2f.inc + bgs_classes_eigen.inc + bgs_classes_imbs.inc + bgs_classes_multilayer.inc, shared verbatim with this repository's tested host mirror, tracking_amd/host/bgs_host.h).
+// (the list is bgs_classes.inc + bgs_classes_kde.inc + bgs_classes_dp2.inc + bgs_classes_lb.inc + bgs_classes_vumeter.inc + bgs_classes_fuzzy.inc + bgs_classes_t2f.inc + bgs_classes_eigen.inc + bgs_classes_imbs.inc + bgs_classes_multilayer.inc + bgs_classes_multicue.inc, shared verbatim with this repository's tested host mirror, tracking_amd/host/bgs_host.h).
 //
 // Use:   mixtureOfGaussianV2BGS = new hipbgs::MixtureOfGaussianV2BGS;      // FrameProcessor.cpp:59-60
 //        if(i==36) bgs = new hipbgs::SuBSENSEBGS();                          // ustc_src/ustc_bgs.cpp:68
@@ -164,6 +164,13 @@ class HipBGSBase : public IBGS {
 #include "bgs_classes_eigen.inc"
 #include "bgs_classes_imbs.inc"
 #include "bgs_classes_multilayer.inc"
+#define BGS_HIP_MAT cv::Mat
+#define BGS_HIP_8UC3 CV_8UC3
+#define BGS_HIP_FAIL(code, what) CV_Error(CV_StsError, (what))  /* -> cv::Exception, caught at Main.cpp:63-72 */
+#include "bgs_classes_multicue.inc"
+#undef BGS_HIP_MAT
+#undef BGS_HIP_8UC3
+#undef BGS_HIP_FAIL
 #ifdef BGS_HIP_DEFINED_OVERRIDE
 #undef override
 #undef BGS_HIP_DEFINED_OVERRIDE

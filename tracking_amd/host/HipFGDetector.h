@@ -11,6 +11,7 @@
 // Type 15: hipbgs::DPEigenbackgroundBGS exists (HipBGS.h) but is not in the type table here, as in ustc_bgs.h (see there).
 // Type 33: hipbgs::IndependentMultimodalBGS likewise.
 // Type 23: hipbgs::MultiLayerBGS likewise.
+// Type 34: hipbgs::SJN_MultiCueBGS likewise.
 //
 // Needs OpenCV 2.4 with the legacy module (opencv2/legacy/blobtrack.hpp), which this repository's build image does not have:
 // checked for syntax against the declaration-only mock under tests/mock_opencv (tests/test_capi_cpu.py), as gnu++0x like the

@@ -3,8 +3,8 @@
 //     bgs_demo <frames.raw> <rows> <cols> <n_frames> <out_prefix> [ustc_type]
 // frames.raw = n_frames x rows x cols x 3 bytes (BGR).  For every class enabled in ./config/FrameProcessor.xml the mask of
 // each frame is appended to <out_prefix>.<ClassName>.raw (frames whose output the class leaves untouched are written as 0x07; of
-// the 8UC3 masks the lb/ classes hand out, whose channels are equal, the first channel is written, so every file holds one byte
-// per pixel).
+// the 8UC3 masks the lb/ classes and SJN_MultiCueBGS hand out, whose channels are equal, the first channel is written, so every file
+// holds one byte per pixel; SJN_MultiCueBGS's file is <out_prefix>.MultiCueBGS.raw, after its FrameProcessor name).
 // With a 6th argument the frames go through USTC_BGS(type) instead (ustc_src/ustc_bgs.cpp) and GetMask() of every frame is
 // written to <out_prefix>.ustc.raw.  With a 7th argument ("box" or "moments") the detector is a HipFGDetector and every frame's blob
 // list (GetBlobs) is printed like ustc_src/trackingMain.cpp:189-190 prints the tracker's: "pBlob x,y,w,h,id is ...".
@@ -76,10 +76,10 @@ int main(int argc, char** argv) {
                            "MixtureOfGaussianV1BGS", "MixtureOfGaussianV2BGS", "AdaptiveBackgroundLearning", "AdaptiveSelectiveBackgroundLearning",
                            "GMG", "DPAdaptiveMedianBGS", "DPGrimsonGMMBGS", "DPZivkovicAGMMBGS", "DPMeanBGS", "DPWrenGABGS", "SigmaDeltaBGS", "SuBSENSEBGS", "LOBSTERBGS", "KDE",
                            "DPPratiMediodBGS", "DPTextureBGS", "LBSimpleGaussian", "LBFuzzyGaussian", "LBMixtureOfGaussians", "LBAdaptiveSOM", "LBFuzzyAdaptiveSOM", "VuMeter",
-                           "FuzzySugenoIntegral", "FuzzyChoquetIntegral", "T2FGMM_UM", "T2FGMM_UV", "DPEigenbackgroundBGS", "IndependentMultimodalBGS", "MultiLayerBGS"};
+                           "FuzzySugenoIntegral", "FuzzyChoquetIntegral", "T2FGMM_UM", "T2FGMM_UV", "DPEigenbackgroundBGS", "IndependentMultimodalBGS", "MultiLayerBGS", "MultiCueBGS"};
     Image* masks[] = {&fp->img_framediff, &fp->img_staticfdiff, &fp->img_wmovmean, &fp->img_movvar, &fp->img_mog1, &fp->img_mog2, &fp->img_bkgl_fgmask, &fp->img_asbl,
                      &fp->img_gmg, &fp->img_adpmed, &fp->img_grigmm, &fp->img_zivgmm, &fp->img_tmpmean, &fp->img_wrenga, &fp->img_sdbgs, &fp->img_ssbgs, &fp->img_lobgs, &fp->img_kde,
-                     &fp->img_pramed, &fp->img_texbgs, &fp->img_lb_sg, &fp->img_lb_fg, &fp->img_lb_mog, &fp->img_lb_som, &fp->img_lb_fsom, &fp->img_vumeter, &fp->img_fsi, &fp->img_fci, &fp->img_t2fgmm_um, &fp->img_t2fgmm_uv, &fp->img_eigbkg, &fp->img_imbs, &fp->img_mlbgs};
+                     &fp->img_pramed, &fp->img_texbgs, &fp->img_lb_sg, &fp->img_lb_fg, &fp->img_lb_mog, &fp->img_lb_som, &fp->img_lb_fsom, &fp->img_vumeter, &fp->img_fsi, &fp->img_fci, &fp->img_t2fgmm_um, &fp->img_t2fgmm_uv, &fp->img_eigbkg, &fp->img_imbs, &fp->img_mlbgs, &fp->img_mcbgs};
     std::vector<std::ofstream> outs;
     for (const char* nm : names) outs.emplace_back((prefix + "." + nm + ".raw").c_str(), std::ios::binary);
     Image frame(rows, cols, 3);

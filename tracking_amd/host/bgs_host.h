@@ -292,6 +292,13 @@ class HipBGSBase : public IBGS {
 #define BGS_HIP_XML_HAS_STRINGS 1
 #include "bgs_classes_multilayer.inc"
 #undef BGS_HIP_XML_HAS_STRINGS
+#define BGS_HIP_MAT Image
+#define BGS_HIP_8UC3 3
+#define BGS_HIP_FAIL(code, what) throw Exception((code), (what))
+#include "bgs_classes_multicue.inc"
+#undef BGS_HIP_MAT
+#undef BGS_HIP_8UC3
+#undef BGS_HIP_FAIL
 
 #undef BGS_HIP_BANNER_DTOR
 

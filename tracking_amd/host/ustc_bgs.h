@@ -14,6 +14,8 @@
 // still throws for 33, which the suite pins as refused too.
 // Type 23 likewise: MultiLayerBGS exists (bgs_classes_multilayer.inc; FrameProcessor's enableMultiLayerBGS builds it) and the type
 // table still throws for 23, the suite's own example of a refused type.
+// Type 34 likewise: SJN_MultiCueBGS exists (bgs_classes_multicue.inc, on a bgs_multicue handle instead of an engine; FrameProcessor's
+// enableMultiCueBGS builds it) and the type table still throws for 34, which the suite pins as refused at run time.
 #pragma once
 #include "bgs_host.h"
 #include "blob.h"
