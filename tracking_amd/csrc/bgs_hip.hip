@@ -100,6 +100,8 @@ int d2h_staged(void* dst, const void* src, size_t bytes) {
 }
 inline unsigned blocks_for(size_t groups) { return (unsigned)((groups + bgs::kBlock - 1) / bgs::kBlock); }
 
+#include "host_path.h"
+
 }  // namespace
 
 namespace {
@@ -123,7 +125,7 @@ struct VmmRange {
 
 // What is here is what the generic code below uses itself.  A family's model - buffers, tables, per-stream counters - is the state
 // struct of its engine_*.h behind `model`; what stays is
-//  - geometry, the per-stream bookkeeping every family shares (seen, rpos, last_flags), staging, lanes, pins, timing, ingest, cc scratch, vmm;
+//  - geometry, the per-stream bookkeeping every family shares (seen, rpos, last_flags), the host path (HostPath), timing, ingest, cc scratch, vmm;
 //  - the frame history ring: process_clip_run, bgs_process and bgs_submit read and write it themselves, so it is a service of the
 //    generic code that the history classes use, not their private state;
 //  - `counter`: the families that have a learning phase counted in frames share it with that one meaning, and bgs_reset_stream clears it;
@@ -172,42 +174,14 @@ struct bgs_engine {
   // a model built from fixed-size physical chunks with the virtual memory API (model_allocate)
   VmmRange vmm;
 
-  // host staging (bgs_process)
-  uint8_t *h_in = nullptr, *h_fg = nullptr, *h_bg = nullptr;
-  uint8_t *d_in = nullptr, *d_fg = nullptr, *d_bg = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t band_ev[8] = {nullptr};  // bgs_process: one event per output band
-  // bgs_process: caller buffers that came back unchanged call after call are page-locked once and DMA'd directly (host_pin)
-  struct HostPin {
-    const void* ptr = nullptr;   // what the previous call passed for this role
-    size_t bytes = 0;
-    bool pinned = false, refused = false;
-  };
-  std::vector<HostPin> pin;       // [stream][3]: 0 input, 1 mask, 2 background (every camera has its own buffers)
-  std::vector<std::pair<const uint8_t*, size_t>> arenas;  // bgs_host_arena: caller memory page-locked as a whole; images inside it are DMA'd in place
-  // bgs_submit / bgs_wait: one lane per camera - its own HIP stream, staging and device images - so that the uploads, kernels and
-  // downloads of different cameras overlap; created at a stream's first bgs_submit
-  struct Lane {
-    hipStream_t hs = nullptr;
-    hipEvent_t done = nullptr;
-    uint8_t *h_in = nullptr, *h_fg = nullptr, *h_bg = nullptr, *d_in = nullptr, *d_fg = nullptr, *d_bg = nullptr;
-    bool pending = false, fg_direct = false, bg_direct = false;
-    uint8_t *fg = nullptr, *bg = nullptr;  // the caller's output images of the pending submission
-    size_t fg_step = 0, bg_step = 0;
-    uint32_t flags = 0;
-  };
-  std::vector<Lane> lanes;
-  // host-path diagnostics (bgs_get_state "hostpath"; bench.py host_path): what hipHostRegister cost and how often it ran, how long the
-  // CPU spent copying images into / out of pinned staging, bytes that crossed the bus each way
-  double diag_reg_ms = 0, diag_stage_in_ms = 0, diag_stage_out_ms = 0;
-  int64_t diag_reg_calls = 0, diag_unreg_calls = 0, diag_h2d_bytes = 0, diag_d2h_bytes = 0, diag_frames = 0;
+  HostPath host;                          // everything of the calls that take frames in host memory (host_path.h)
+  hipStream_t stream() const { return host.sync.hs; }  // the engine's own stream is its synchronous lane's; made by allocate(), where families enqueue their table uploads
   bool ingest_on = false;             // bgs_set_ingest: bgs_process takes raw frames
   bgs_ingest ingest{};
   int raw_rows = 0, raw_cols = 0;     // geometry of the raw frames (fixed by the first one)
-  uint8_t *h_raw = nullptr, *d_raw = nullptr, *d_ingest_ws = nullptr;  // raw staging for configurations that need device work
   uint8_t* pack_fg = nullptr;         // frames of rows*cols % 64 != 0 pixels: the byte masks a packed-only caller's bit masks are made from
   size_t pack_fg_bytes = 0;
-  int last_fg_stream = -1;            // bgs_last_mask_blobs: whose mask d_fg holds (-1: none valid)
+  int last_fg_stream = -1;            // bgs_last_mask_blobs: whose mask host.sync.fg.d holds (-1: none valid)
   void* cc_work = nullptr;            // its device scratch: workspace | boxes | moments | count
   int cc_cap = 0;                     // boxes the scratch has room for
 
@@ -226,7 +200,7 @@ namespace {
 struct Family {
   int (*check)(bgs_algo, const bgs_params&);                      // nullable; needs no device (bgs_create, bgs_set_params)
   int (*check_geometry)(bgs_algo, int rows, int cols, int ch);    // nullable; refusals made before the device is opened
-  int (*allocate)(bgs_engine*);                                   // rows / cols / ch / n are set, e->stream exists; makes e->model (make_state) and fills it; after a failure free_all destroys what there is of it
+  int (*allocate)(bgs_engine*);                                   // rows / cols / ch / n are set, e->stream() exists; makes e->model (make_state) and fills it; after a failure free_all destroys what there is of it
   uint64_t (*key)(const bgs_engine*, int stream);                 // streams whose next frame has the same key share a launch
   // one frame: launches on s, advances the family's own per-stream counters, *flags = BGS_FG_VALID / BGS_BG_VALID of the run
   int (*run)(bgs_engine*, int first, int count, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits, hipStream_t s, uint32_t* flags);
@@ -372,26 +346,13 @@ int64_t copy_host(const char* plane, void* dst, size_t cap, const void* src, siz
 }
 int64_t unknown_plane(const bgs_engine* e, const char* plane) { return fail(BGS_ERR_STATE, "unknown state plane '%s' for algorithm %d", plane, (int)e->algo); }
 
-void lane_release(bgs_engine::Lane& ln) {  // whatever of a lane came to be (bgs_submit's set-up may have failed half-way)
-  if (ln.hs) (void)hipStreamSynchronize(ln.hs);
-  void* host[] = {ln.h_in, ln.h_fg, ln.h_bg};
-  for (void* h : host)
-    if (h) (void)hipHostFree(h);
-  void* dv[] = {ln.d_in, ln.d_fg, ln.d_bg};
-  for (void* d : dv)
-    if (d) (void)hipFree(d);
-  if (ln.done) (void)hipEventDestroy(ln.done);
-  if (ln.hs) (void)hipStreamDestroy(ln.hs);
-  ln = bgs_engine::Lane();
-}
-
 // Every model / history / staging buffer of an engine comes from here.  Nothing may rely on what a fresh allocation holds:
 // each model is initialised at a stream's first frame ON THE LAUNCH STREAM (mog2_clear, mog1_clear_kernel, gmg_clear_kernel,
 // dp_gmm_clear_kernel, ss_init_streams, ...).  BGS_DEBUG_POISON=1 makes a violation deterministic instead of timing- and
 // allocator-dependent: the buffer is filled with 0xA5 (a NaN-free but wildly wrong float, a mode count of 165) before first use.
 int dmalloc(bgs_engine* e, void** p, size_t bytes) {
   HIP_TRY(hipMalloc(p, bytes));
-  if (e->knob.poison) HIP_TRY(hipMemsetAsync(*p, 0xA5, bytes, e->stream));  // allocate() drains e->stream before it returns
+  if (e->knob.poison) HIP_TRY(hipMemsetAsync(*p, 0xA5, bytes, e->stream()));  // allocate() drains e->stream() before it returns
   return BGS_OK;
 }
 template <class T>
@@ -481,7 +442,7 @@ int model_allocate(bgs_engine* e, void** out, size_t bytes) {
   if (e->knob.model_chunk_mb > 0 && bytes >= e->knob.model_chunk_min_bytes && !e->vmm.base) {
     if (vmm_allocate(e->vmm, e->device, out, bytes, (size_t)e->knob.model_chunk_mb << 20) == BGS_OK) {
       e->vmm.owner = out;
-      if (e->knob.poison) HIP_TRY(hipMemsetAsync(*out, 0xA5, e->vmm.bytes, e->stream));
+      if (e->knob.poison) HIP_TRY(hipMemsetAsync(*out, 0xA5, e->vmm.bytes, e->stream()));
       return BGS_OK;
     }
     (void)hipGetLastError();
@@ -592,25 +553,10 @@ void free_all(bgs_engine* e) {
   for (auto& r : e->ring) dfree(r);
   dfree(e->cc_work), e->cc_cap = 0;
   dfree(e->pack_fg), e->pack_fg_bytes = 0;
-  if (e->h_raw) (void)hipHostFree(e->h_raw), e->h_raw = nullptr;
-  dfree(e->d_raw), dfree(e->d_ingest_ws);
   e->last_fg_stream = -1;
-  dfree(e->d_in), dfree(e->d_fg), dfree(e->d_bg);
-  void* host[] = {e->h_in, e->h_fg, e->h_bg};
-  for (void* h : host)
-    if (h) (void)hipHostFree(h);
-  e->h_in = e->h_fg = e->h_bg = nullptr;
+  e->host.release();
   for (auto& ev : e->events) (void)hipEventDestroy(ev.first), (void)hipEventDestroy(ev.second);
   e->events.clear();
-  for (auto& ev : e->band_ev)
-    if (ev) (void)hipEventDestroy(ev), ev = nullptr;
-  for (auto& hp : e->pin) {
-    if (hp.pinned) (void)hipHostUnregister(const_cast<void*>(hp.ptr));
-    hp = bgs_engine::HostPin();
-  }
-  for (auto& a : e->arenas) (void)hipHostUnregister(const_cast<uint8_t*>(a.first));
-  e->arenas.clear();
-  for (auto& ln : e->lanes) lane_release(ln);
 }
 
 int check_params(bgs_algo algo, const bgs_params& p) {
@@ -627,62 +573,27 @@ int allocate(bgs_engine* e, int rows, int cols, int ch) {
   }
   HIP_TRY(hipSetDevice(e->device));
   e->rows = rows, e->cols = cols, e->ch = ch, e->n = (size_t)rows * cols;
-  if (!e->stream) HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+  HIP_TRY(e->host.sync.open());  // e->stream()
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, e->device) == hipSuccess && prop.multiProcessorCount > 0) e->n_cu = prop.multiProcessorCount;
   int rc = e->fam->allocate(e);
   if (rc) return rc;
-  // Whatever allocation enqueued on e->stream (statistics counters, poison fills) is complete before the caller's first
+  // Whatever allocation enqueued on e->stream() (statistics counters, poison fills) is complete before the caller's first
   // launch - which may come on ANOTHER stream (device path) that nothing else orders against this one.
-  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream()));
   return BGS_OK;
 }
 
-// OpenCV's capture loop hands IBGS::process the SAME frame buffer every frame (VideoCapture.cpp:158-218: cvQueryFrame's image,
-// wrapped by cv::Mat img_input(frame)), and a caller that keeps its mask / background images allocated does the same on the way
-// out.  A buffer that comes back with the same address and size as in the previous call is page-locked (hipHostRegister, once)
-// and from then on the DMA engine reads / writes it directly: no staging copy by the CPU.  A different buffer in that role drops
-// the registration; bgs_destroy drops them all.  Only contiguous images qualify (row step = row bytes).
-// OPT-IN per role (BGS_OPT_HOST_REGISTER): the engine cannot see a buffer being freed and another one mapped at the same address,
-// so the caller promises that a buffer it passes in an enabled role stays allocated until it passes a different one or destroys
-// the engine.
-bool host_pin(bgs_engine* e, int stream, int role, const void* ptr, size_t bytes, hipStream_t user = nullptr) {
-  if (!ptr || !bytes) return false;
-  for (const auto& a : e->arenas)  // inside an arena the caller registered as a whole: nothing to do per image
-    if ((const uint8_t*)ptr >= a.first && (const uint8_t*)ptr + bytes <= a.first + a.second) return true;
-  if (!((e->knob.host_register >> role) & 1)) return false;
-  bgs_engine::HostPin& hp = e->pin[(size_t)stream * 3 + role];
-  if (hp.ptr == ptr && hp.bytes == bytes) {
-    if (hp.pinned) return true;
-    if (hp.refused) return false;
-    const auto t0 = std::chrono::steady_clock::now();
-    const hipError_t er = hipHostRegister(const_cast<void*>(ptr), bytes, hipHostRegisterDefault);
-    e->diag_reg_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    e->diag_reg_calls++;
-    if (er == hipSuccess) return hp.pinned = true;
-    (void)hipGetLastError();  // not registrable (e.g. already registered by the caller, read-only mapping): keep staging
-    hp.refused = true;
-    return false;
-  }
-  if (hp.pinned) {
-    (void)hipStreamSynchronize(user ? user : e->stream);
-    (void)hipHostUnregister(const_cast<void*>(hp.ptr));
-    e->diag_unreg_calls++;
-  }
-  hp = bgs_engine::HostPin();
-  hp.ptr = ptr, hp.bytes = bytes;  // a candidate: registered when it comes back
-  return false;
-}
+bool host_pin(bgs_engine* e, int stream, int role, const void* ptr, size_t bytes, hipStream_t s) { return e->host.pinned(e->knob.host_register, stream, role, ptr, bytes, s); }
 
-int ensure_staging(bgs_engine* e) {
-  if (e->h_in) return BGS_OK;
-  const size_t fb = e->n * e->ch;
-  HIP_TRY(hipHostMalloc((void**)&e->h_in, fb, hipHostMallocDefault));
-  HIP_TRY(hipHostMalloc((void**)&e->h_fg, e->n, hipHostMallocDefault));
-  HIP_TRY(hipHostMalloc((void**)&e->h_bg, fb, hipHostMallocDefault));
-  DMALLOC(e->d_in, fb);
-  DMALLOC(e->d_fg, e->n);
-  DMALLOC(e->d_bg, fb);
+// The staging of a camera's lane (the synchronous one or a bgs_submit lane), sized by the geometry; made by the first call that needs it
+int lane_make(bgs_engine* e, Lane& ln, const char* fn, int stream) {
+  if (ln.done) return BGS_OK;
+  const size_t bytes[3] = {e->n * e->ch, e->n, e->n * bg_channels(e)};
+  const hipError_t er = ln.make(bytes[0], bytes[1], bytes[2]);
+  if (er != hipSuccess) return fail(BGS_ERR_HIP, "%s: setting up the lane of stream %d failed: %s", fn, stream, hipGetErrorString(er));
+  const Staging* st[3] = {&ln.in, &ln.fg, &ln.bg};
+  for (int i = 0; i < 3 && e->knob.poison; ++i) HIP_TRY(hipMemsetAsync(st[i]->d, 0xA5, bytes[i], ln.hs));  // see dmalloc
   return BGS_OK;
 }
 
@@ -1037,8 +948,7 @@ int bgs_create(bgs_algo algo, const bgs_params* params, int hip_device, int n_st
   e->S = n_streams;
   e->seen.assign(n_streams, 0);
   e->rpos.assign(n_streams, 0);
-  e->pin.assign((size_t)n_streams * 3, bgs_engine::HostPin());
-  e->lanes.assign(n_streams, bgs_engine::Lane());
+  e->host.set_streams(n_streams);
   e->last_flags.assign(n_streams, 0);
   e->counter.assign(n_streams, 0);
   for_each_block([e](const auto& b) { b.defaults(&(e->*b.member)); });  // a class with a block of its own starts from the constructor's values whatever bgs_params it was handed
@@ -1136,10 +1046,9 @@ int bgs_set_option(bgs_engine* e, int option, int64_t value) {
     case 6: e->knob.mog2_sparse = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 4); return BGS_OK;
     case 7: e->knob.clip_fuse = value != 0; return BGS_OK;
     case 8:
-      if (hipSetDevice(e->device) == hipSuccess && e->stream) (void)hipStreamSynchronize(e->stream);
+      if (hipSetDevice(e->device) == hipSuccess && e->stream()) (void)hipStreamSynchronize(e->stream());
       (void)hipDeviceSynchronize();
-      for (size_t i = 0; i < e->pin.size(); ++i)
-        if (!((value >> (i % 3)) & 1) && e->pin[i].pinned) (void)hipHostUnregister(const_cast<void*>(e->pin[i].ptr)), e->pin[i] = bgs_engine::HostPin();
+      e->host.unpin_roles_outside((int)(value & 7));
       e->knob.host_register = (int)(value & 7);
       return BGS_OK;
     case 5: return BGS_OK;  // BGS_OPT_PLACEMENT_PROBE of rounds 1-2: accepted and ignored (placement is deterministic since round 3: model_allocate)
@@ -1159,7 +1068,7 @@ int bgs_set_option(bgs_engine* e, int option, int64_t value) {
 // with it on that camera's model, ring slot and frame count.  The device entry points refuse instead (bgs_wait first).
 static int range_busy(const bgs_engine* e, int first, int count) {
   for (int i = std::max(first, 0); i < first + count && i < e->S; ++i)
-    if (e->lanes[i].pending) return fail(BGS_ERR_STATE, "stream %d has a bgs_submit in flight: bgs_wait before a device-path call that covers it", i);
+    if (e->host.sub[i].pending) return fail(BGS_ERR_STATE, "stream %d has a bgs_submit in flight: bgs_wait before a device-path call that covers it", i);
   return BGS_OK;
 }
 
@@ -1208,98 +1117,65 @@ int bgs_process(bgs_engine* e, int stream, const uint8_t* in, int rows, int cols
   const bool ingest_on_device = ingest && (pl.mode != 0 || e->ingest.equalize_hist || e->ingest.gaussian_blur);
   int rc = bgs_set_geometry(e, rows, cols, channels);
   if (rc) return rc;
-  if (e->lanes[stream].pending) {  // a bgs_submit of this stream is still in flight: its result is collected (and dropped) first
+  HostPath& hp = e->host;
+  Lane& ln = hp.sync;
+  if (hp.sub[stream].pending) {  // a bgs_submit of this stream is still in flight: its result is collected (and dropped) first
     rc = lane_wait(e, stream, nullptr);
     if (rc) return rc;
   }
-  rc = ensure_staging(e);
+  rc = lane_make(e, ln, "bgs_process", stream);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(e->device));
   const size_t rb = (size_t)cols * channels, fb = e->n * channels;
   // history-keeping algorithms receive the upload straight in their ring slot (zero-copy history)
-  uint8_t* dst = e->d_in;
+  uint8_t* dst = ln.in.d;
   if (e->nring) dst = e->ring[e->rpos[stream] % e->nring] + (size_t)stream * fb;
   if (ingest_on_device) {
     // resize / equalizeHist / GaussianBlur: the raw frame goes up as it is, the preparation runs between the upload and the model kernel
-    const size_t raw_rb = (size_t)raw_cols * channels, raw_bytes = raw_rb * raw_rows;
-    if (!e->h_raw) {
-      HIP_TRY(hipHostMalloc((void**)&e->h_raw, raw_bytes, hipHostMallocDefault));
-      HIP_TRY(hipMalloc((void**)&e->d_raw, raw_bytes));
-      const size_t ws = bgs_ingest_workspace(&e->ingest, 1, raw_rows, raw_cols, channels);
-      if (ws) HIP_TRY(hipMalloc((void**)&e->d_ingest_ws, ws));
+    const size_t raw_rb = (size_t)raw_cols * channels;
+    if (!hp.raw.h) {  // with its workspace, or not at all
+      hipError_t er = hp.ingest_ws.make(bgs_ingest_workspace(&e->ingest, 1, raw_rows, raw_cols, channels), /*host=*/false);
+      if (er == hipSuccess && (er = hp.raw.make(raw_rb * raw_rows)) != hipSuccess) hp.ingest_ws.release();
+      if (er != hipSuccess) return fail(BGS_ERR_HIP, "bgs_process: staging of the raw frame: %s", hipGetErrorString(er));
     }
-    const int bands = raw_rows >= 64 ? 8 : 1;
-    for (int b = 0; b < bands; ++b) {
-      const int y0 = (int)((int64_t)raw_rows * b / bands), y1 = (int)((int64_t)raw_rows * (b + 1) / bands);
-      for (int y = y0; y < y1; ++y) std::memcpy(e->h_raw + (size_t)y * raw_rb, in + (size_t)y * in_step, raw_rb);
-      HIP_TRY(hipMemcpyAsync(e->d_raw + (size_t)y0 * raw_rb, e->h_raw + (size_t)y0 * raw_rb, (size_t)(y1 - y0) * raw_rb, hipMemcpyHostToDevice, e->stream));
-    }
-    rc = bgs_ingest_device(e->device, &e->ingest, e->d_raw, 1, raw_rows, raw_cols, channels, raw_rb, dst, e->d_ingest_ws, e->stream);
+    HIP_TRY(upload_rows(hp.raw, hp.raw.d, ln.hs, in, in_step, raw_rb, raw_rows, band_count(raw_rows)));
+    rc = bgs_ingest_device(e->device, &e->ingest, hp.raw.d, 1, raw_rows, raw_cols, channels, raw_rb, dst, hp.ingest_ws.d, ln.hs);
     if (rc) return rc;
   } else {
-    // staging is pipelined: while the DMA engine moves band k, the CPU copies band k+1 of the caller's (pageable, possibly
-    // strided) image into the pinned buffer.  Flip (rows reversed) and ROI (a window of the raw frame) cost nothing extra: they
-    // only change which source row and column each staged row starts at.
-    e->diag_frames++, e->diag_h2d_bytes += (int64_t)fb;
-    if (!ingest && in_step == rb && host_pin(e, stream, 0, in, fb)) {
-      HIP_TRY(hipMemcpyAsync(dst, in, fb, hipMemcpyHostToDevice, e->stream));  // straight from the caller's page-locked frame buffer
+    // flip (rows reversed) and ROI (a window of the raw frame) cost nothing extra: the row map says where each staged row starts
+    hp.frames++, hp.h2d_bytes += (int64_t)fb;
+    if (!ingest && in_step == rb && host_pin(e, stream, 0, in, fb, ln.hs)) {
+      HIP_TRY(hipMemcpyAsync(dst, in, fb, hipMemcpyHostToDevice, ln.hs));  // straight from the caller's page-locked frame buffer
     } else {
       const auto st0 = std::chrono::steady_clock::now();
-      const int bands = rows >= 64 ? 8 : 1;
-      for (int b = 0; b < bands; ++b) {
-        const int y0 = (int)((int64_t)rows * b / bands), y1 = (int)((int64_t)rows * (b + 1) / bands);
-        for (int y = y0; y < y1; ++y) {
-          size_t sy = (size_t)y, sx = 0;
-          if (ingest) sy = (size_t)(e->ingest.flip ? pl.rh - 1 - (y + pl.y0) : y + pl.y0), sx = (size_t)pl.x0 * channels;
-          std::memcpy(e->h_in + (size_t)y * rb, in + sy * in_step + sx, rb);
-        }
-        HIP_TRY(hipMemcpyAsync(dst + (size_t)y0 * rb, e->h_in + (size_t)y0 * rb, (size_t)(y1 - y0) * rb, hipMemcpyHostToDevice, e->stream));
-      }
-      e->diag_stage_in_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - st0).count();
+      const RowMap map{e->ingest.flip != 0, pl.rh, pl.y0, (size_t)pl.x0 * channels};
+      HIP_TRY(upload_rows(ln.in, dst, ln.hs, in, in_step, rb, rows, band_count(rows), ingest ? &map : nullptr));
+      hp.stage_in_ms += ms_since(st0);
     }
   }
   uint32_t flags = 0;
   const bool saved_borrow = e->borrow;
   e->borrow = false;
   e->last_fg_stream = -1;
-  rc = process_range(e, stream, 1, dst, e->d_fg, bg ? e->d_bg : nullptr, nullptr, e->stream, &flags);  // the mask stays on the device for bgs_last_mask_blobs
+  rc = process_range(e, stream, 1, dst, ln.fg.d, bg ? ln.bg.d : nullptr, nullptr, ln.hs, &flags);  // the mask stays on the device for bgs_last_mask_blobs
   e->borrow = saved_borrow;
   if (rc) return rc;
   if (flags & BGS_FG_VALID) e->last_fg_stream = stream;
   const int bg_ch = bg_channels(e);
-  // the way back is pipelined the same way when there is a background image to return (6 MB at 1080p): band k is copied out to
-  // the caller's image while band k+1 is still on the bus; a mask alone (2 MB) is not worth the events
+  // the way back is banded when there is a background image to return (6 MB at 1080p); a mask alone (2 MB) is not worth the events
   bool out_fg = fg && (flags & BGS_FG_VALID), out_bg = bg && (flags & BGS_BG_VALID);
   // outputs the caller keeps allocated (same buffer as last call, contiguous rows) are written by the DMA engine directly
-  const bool fg_direct = out_fg && fg_step == (size_t)cols && host_pin(e, stream, 1, fg, e->n);
-  const bool bg_direct = out_bg && bg_step == (size_t)cols * bg_ch && host_pin(e, stream, 2, bg, e->n * bg_ch);
-  e->diag_d2h_bytes += (int64_t)((out_fg ? e->n : 0) + (out_bg ? e->n * bg_ch : 0));
-  if (fg_direct) HIP_TRY(hipMemcpyAsync(fg, e->d_fg, e->n, hipMemcpyDeviceToHost, e->stream));
-  if (bg_direct) HIP_TRY(hipMemcpyAsync(bg, e->d_bg, e->n * bg_ch, hipMemcpyDeviceToHost, e->stream));
+  const bool fg_direct = out_fg && fg_step == (size_t)cols && host_pin(e, stream, 1, fg, e->n, ln.hs);
+  const bool bg_direct = out_bg && bg_step == (size_t)cols * bg_ch && host_pin(e, stream, 2, bg, e->n * bg_ch, ln.hs);
+  hp.d2h_bytes += (int64_t)((out_fg ? e->n : 0) + (out_bg ? e->n * bg_ch : 0));
+  if (fg_direct) HIP_TRY(hipMemcpyAsync(fg, ln.fg.d, e->n, hipMemcpyDeviceToHost, ln.hs));
+  if (bg_direct) HIP_TRY(hipMemcpyAsync(bg, ln.bg.d, e->n * bg_ch, hipMemcpyDeviceToHost, ln.hs));
   if (fg_direct) out_fg = false;
   if (bg_direct) out_bg = false;
-  if (!out_fg && !out_bg) {
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (out_flags) *out_flags = flags;
-    return BGS_OK;
-  }
-  const int obands = out_bg ? (rows >= 64 ? 8 : 1) : 1;
-  for (int b = 0; b < obands; ++b) {
-    const int y0 = (int)((int64_t)rows * b / obands), y1 = (int)((int64_t)rows * (b + 1) / obands);
-    if (out_fg) HIP_TRY(hipMemcpyAsync(e->h_fg + (size_t)y0 * cols, e->d_fg + (size_t)y0 * cols, (size_t)(y1 - y0) * cols, hipMemcpyDeviceToHost, e->stream));
-    if (out_bg)
-      HIP_TRY(hipMemcpyAsync(e->h_bg + (size_t)y0 * cols * bg_ch, e->d_bg + (size_t)y0 * cols * bg_ch, (size_t)(y1 - y0) * cols * bg_ch, hipMemcpyDeviceToHost, e->stream));
-    if (!e->band_ev[b]) HIP_TRY(hipEventCreateWithFlags(&e->band_ev[b], hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(e->band_ev[b], e->stream));
-  }
-  for (int b = 0; b < obands; ++b) {
-    const int y0 = (int)((int64_t)rows * b / obands), y1 = (int)((int64_t)rows * (b + 1) / obands);
-    HIP_TRY(hipEventSynchronize(e->band_ev[b]));
-    if (out_fg)
-      for (int y = y0; y < y1; ++y) std::memcpy(fg + (size_t)y * fg_step, e->h_fg + (size_t)y * cols, (size_t)cols);
-    if (out_bg)
-      for (int y = y0; y < y1; ++y) std::memcpy(bg + (size_t)y * bg_step, e->h_bg + (size_t)y * cols * bg_ch, (size_t)cols * bg_ch);
-  }
+  if (!out_fg && !out_bg)
+    HIP_TRY(hipStreamSynchronize(ln.hs));
+  else
+    HIP_TRY(ln.download_banded(rows, out_bg ? band_count(rows) : 1, {&ln.fg, out_fg ? fg : nullptr, fg_step, (size_t)cols}, {&ln.bg, out_bg ? bg : nullptr, bg_step, (size_t)cols * bg_ch}));
   if (out_flags) *out_flags = flags;
   return BGS_OK;
 }
@@ -1309,21 +1185,19 @@ int bgs_process(bgs_engine* e, int stream, const uint8_t* in, int rows, int cols
 // kernel runs and camera C's mask comes back: the copy engines and the CUs work side by side instead of taking turns, which is all
 // a synchronous bgs_process per camera can do.  One submission per stream in flight; bgs_process on a stream first collects it.
 static int lane_wait(bgs_engine* e, int stream, uint32_t* out_flags) {
-  bgs_engine::Lane& ln = e->lanes[stream];
+  const Lane& ln = e->host.lanes[stream];
+  HostPath::Submission& sub = e->host.sub[stream];
   if (out_flags) *out_flags = 0;
-  if (!ln.pending) return BGS_OK;
+  if (!sub.pending) return BGS_OK;
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipEventSynchronize(ln.done));
-  ln.pending = false;
-  const int bg_ch = bg_channels(e);
-  const bool copy_fg = ln.fg && !ln.fg_direct && (ln.flags & BGS_FG_VALID), copy_bg = ln.bg && !ln.bg_direct && (ln.flags & BGS_BG_VALID);
+  sub.pending = false;
+  const bool copy_fg = sub.fg && !sub.fg_direct && (sub.flags & BGS_FG_VALID), copy_bg = sub.bg && !sub.bg_direct && (sub.flags & BGS_BG_VALID);
   const auto st0 = std::chrono::steady_clock::now();
-  if (copy_fg)
-    for (int y = 0; y < e->rows; ++y) std::memcpy(ln.fg + (size_t)y * ln.fg_step, ln.h_fg + (size_t)y * e->cols, (size_t)e->cols);
-  if (copy_bg)
-    for (int y = 0; y < e->rows; ++y) std::memcpy(ln.bg + (size_t)y * ln.bg_step, ln.h_bg + (size_t)y * e->cols * bg_ch, (size_t)e->cols * bg_ch);
-  if (copy_fg || copy_bg) e->diag_stage_out_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - st0).count();
-  if (out_flags) *out_flags = ln.flags;
+  if (copy_fg) unpack_rows(sub.fg, sub.fg_step, ln.fg.h, (size_t)e->cols, 0, e->rows);
+  if (copy_bg) unpack_rows(sub.bg, sub.bg_step, ln.bg.h, (size_t)e->cols * bg_channels(e), 0, e->rows);
+  if (copy_fg || copy_bg) e->host.stage_out_ms += ms_since(st0);
+  if (out_flags) *out_flags = sub.flags;
   return BGS_OK;
 }
 
@@ -1332,87 +1206,66 @@ int bgs_submit(bgs_engine* e, int stream, const uint8_t* in, int rows, int cols,
   if (!e) return fail(BGS_ERR_INVALID, "engine is NULL");
   if (stream < 0 || stream >= e->S) return fail(BGS_ERR_INVALID, "stream %d outside 0..%d", stream, e->S - 1);
   if (e->ingest_on) return fail(BGS_ERR_UNSUPPORTED, "bgs_submit takes prepared frames (bgs_set_ingest is served by bgs_process)");
-  if (e->lanes[stream].pending) return fail(BGS_ERR_STATE, "stream %d has a submission in flight: bgs_wait first", stream);
+  if (e->host.sub[stream].pending) return fail(BGS_ERR_STATE, "stream %d has a submission in flight: bgs_wait first", stream);
   if (!in || rows <= 0 || cols <= 0) return BGS_OK;  // if(img_input.empty()) return;
   if (channels != 1 && channels != 3) return fail(BGS_ERR_UNSUPPORTED, "channels must be 1 or 3");
   if (in_step < (size_t)cols * channels) return fail(BGS_ERR_INVALID, "in_step %zu < cols*channels", in_step);
   int rc = bgs_set_geometry(e, rows, cols, channels);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(e->device));
-  bgs_engine::Lane& ln = e->lanes[stream];
+  HostPath& hp = e->host;
+  Lane& ln = hp.lanes[stream];
+  HostPath::Submission& sub = hp.sub[stream];
   const size_t rb = (size_t)cols * channels, fb = e->n * channels;
   const int bg_ch = bg_channels(e);
-  if (!ln.hs) {
-    // all or nothing: a lane whose stream exists but whose buffers do not would send the next submission through null pointers
-    hipError_t er = hipStreamCreateWithFlags(&ln.hs, hipStreamNonBlocking);
-    if (er == hipSuccess) er = hipEventCreateWithFlags(&ln.done, hipEventDisableTiming);
-    if (er == hipSuccess) er = hipHostMalloc((void**)&ln.h_in, fb, hipHostMallocDefault);
-    if (er == hipSuccess) er = hipHostMalloc((void**)&ln.h_fg, e->n, hipHostMallocDefault);
-    if (er == hipSuccess) er = hipHostMalloc((void**)&ln.h_bg, e->n * bg_ch, hipHostMallocDefault);
-    if (er == hipSuccess) er = hipMalloc((void**)&ln.d_in, fb);
-    if (er == hipSuccess) er = hipMalloc((void**)&ln.d_fg, e->n);
-    if (er == hipSuccess) er = hipMalloc((void**)&ln.d_bg, e->n * bg_ch);
-    if (er != hipSuccess) {
-      (void)hipGetLastError();
-      lane_release(ln);
-      return fail(BGS_ERR_HIP, "bgs_submit: setting up the lane of stream %d failed: %s", stream, hipGetErrorString(er));
-    }
-  }
-  uint8_t* dst = ln.d_in;
+  rc = lane_make(e, ln, "bgs_submit", stream);
+  if (rc) return rc;
+  uint8_t* dst = ln.in.d;
   if (e->nring) dst = e->ring[e->rpos[stream] % e->nring] + (size_t)stream * fb;  // history classes: straight into their ring slot
-  e->diag_frames++, e->diag_h2d_bytes += (int64_t)fb;
+  hp.frames++, hp.h2d_bytes += (int64_t)fb;
   if (in_step == rb && host_pin(e, stream, 0, in, fb, ln.hs)) {
     HIP_TRY(hipMemcpyAsync(dst, in, fb, hipMemcpyHostToDevice, ln.hs));
   } else {
     const auto st0 = std::chrono::steady_clock::now();
-    const int bands = rows >= 64 ? 8 : 1;  // the CPU stages band k+1 while the DMA engine moves band k
-    for (int b = 0; b < bands; ++b) {
-      const int y0 = (int)((int64_t)rows * b / bands), y1 = (int)((int64_t)rows * (b + 1) / bands);
-      for (int y = y0; y < y1; ++y) std::memcpy(ln.h_in + (size_t)y * rb, in + (size_t)y * in_step, rb);
-      HIP_TRY(hipMemcpyAsync(dst + (size_t)y0 * rb, ln.h_in + (size_t)y0 * rb, (size_t)(y1 - y0) * rb, hipMemcpyHostToDevice, ln.hs));
-    }
-    e->diag_stage_in_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - st0).count();
+    HIP_TRY(upload_rows(ln.in, dst, ln.hs, in, in_step, rb, rows, band_count(rows)));
+    hp.stage_in_ms += ms_since(st0);
   }
   uint32_t flags = 0;
   const bool saved_borrow = e->borrow;
   e->borrow = false;
   if (e->last_fg_stream == stream) e->last_fg_stream = -1;  // bgs_last_mask_blobs serves the synchronous call's mask
-  rc = process_range(e, stream, 1, dst, ln.d_fg, bg ? ln.d_bg : nullptr, nullptr, ln.hs, &flags);
+  rc = process_range(e, stream, 1, dst, ln.fg.d, bg ? ln.bg.d : nullptr, nullptr, ln.hs, &flags);
   e->borrow = saved_borrow;
   if (rc) return rc;
-  ln.flags = flags, ln.fg = fg, ln.bg = bg, ln.fg_step = fg_step, ln.bg_step = bg_step;
-  ln.fg_direct = fg && (flags & BGS_FG_VALID) && fg_step == (size_t)cols && host_pin(e, stream, 1, fg, e->n, ln.hs);
-  ln.bg_direct = bg && (flags & BGS_BG_VALID) && bg_step == (size_t)cols * bg_ch && host_pin(e, stream, 2, bg, e->n * bg_ch, ln.hs);
-  e->diag_d2h_bytes += (int64_t)(((fg && (flags & BGS_FG_VALID)) ? e->n : 0) + ((bg && (flags & BGS_BG_VALID)) ? e->n * bg_ch : 0));
-  if (fg && (flags & BGS_FG_VALID)) HIP_TRY(hipMemcpyAsync(ln.fg_direct ? fg : ln.h_fg, ln.d_fg, e->n, hipMemcpyDeviceToHost, ln.hs));
-  if (bg && (flags & BGS_BG_VALID)) HIP_TRY(hipMemcpyAsync(ln.bg_direct ? bg : ln.h_bg, ln.d_bg, e->n * bg_ch, hipMemcpyDeviceToHost, ln.hs));
+  const bool out_fg = fg && (flags & BGS_FG_VALID), out_bg = bg && (flags & BGS_BG_VALID);
+  sub.flags = flags, sub.fg = fg, sub.bg = bg, sub.fg_step = fg_step, sub.bg_step = bg_step;
+  sub.fg_direct = out_fg && fg_step == (size_t)cols && host_pin(e, stream, 1, fg, e->n, ln.hs);
+  sub.bg_direct = out_bg && bg_step == (size_t)cols * bg_ch && host_pin(e, stream, 2, bg, e->n * bg_ch, ln.hs);
+  hp.d2h_bytes += (int64_t)((out_fg ? e->n : 0) + (out_bg ? e->n * bg_ch : 0));
+  if (out_fg) HIP_TRY(sub.fg_direct ? hipMemcpyAsync(fg, ln.fg.d, e->n, hipMemcpyDeviceToHost, ln.hs) : download_whole(ln.fg, e->n, ln.hs));
+  if (out_bg) HIP_TRY(sub.bg_direct ? hipMemcpyAsync(bg, ln.bg.d, e->n * bg_ch, hipMemcpyDeviceToHost, ln.hs) : download_whole(ln.bg, e->n * bg_ch, ln.hs));
   HIP_TRY(hipEventRecord(ln.done, ln.hs));
-  ln.pending = true;
+  sub.pending = true;
   return BGS_OK;
 }
 
 int bgs_host_arena(bgs_engine* e, void* ptr, size_t bytes, int on) {
   if (!e || !ptr || (on && !bytes)) return fail(BGS_ERR_INVALID, "bgs_host_arena: bad argument");
   HIP_TRY(hipSetDevice(e->device));
-  for (size_t i = 0; i < e->arenas.size(); ++i)
-    if (e->arenas[i].first == (const uint8_t*)ptr) {
-      if (on) return e->arenas[i].second == bytes ? BGS_OK : fail(BGS_ERR_INVALID, "bgs_host_arena: this address is registered with another size");
+  auto& arenas = e->host.arenas;
+  for (size_t i = 0; i < arenas.size(); ++i)
+    if (arenas[i].first == (const uint8_t*)ptr) {
+      if (on) return arenas[i].second == bytes ? BGS_OK : fail(BGS_ERR_INVALID, "bgs_host_arena: this address is registered with another size");
       (void)hipDeviceSynchronize();  // nothing may still be reading or writing it
       HIP_TRY(hipHostUnregister(ptr));
-      e->diag_unreg_calls++;
-      e->arenas.erase(e->arenas.begin() + (long)i);
+      e->host.unreg_calls++;
+      arenas.erase(arenas.begin() + (long)i);
       return BGS_OK;
     }
   if (!on) return fail(BGS_ERR_INVALID, "bgs_host_arena: no such arena");
-  const auto t0 = std::chrono::steady_clock::now();
-  const hipError_t er = hipHostRegister(ptr, bytes, hipHostRegisterDefault);
-  e->diag_reg_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  e->diag_reg_calls++;
-  if (er != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(BGS_ERR_HIP, "hipHostRegister of a %zu-byte arena failed: %s", bytes, hipGetErrorString(er));
-  }
-  e->arenas.emplace_back((const uint8_t*)ptr, bytes);
+  const hipError_t er = e->host.timed_register(ptr, bytes);
+  if (er != hipSuccess) return fail(BGS_ERR_HIP, "hipHostRegister of a %zu-byte arena failed: %s", bytes, hipGetErrorString(er));
+  arenas.emplace_back((const uint8_t*)ptr, bytes);
   return BGS_OK;
 }
 
@@ -1429,10 +1282,11 @@ int64_t bgs_get_state(bgs_engine* e, int stream, const char* plane, void* dst, s
   if (stream < 0 || stream >= e->S) return fail(BGS_ERR_INVALID, "stream %d outside 0..%d", stream, e->S - 1);
   if (hipSetDevice(e->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(BGS_ERR_HIP, "device sync failed");
   if (!strcmp(plane, "hostpath")) {  // diagnostics of bgs_process / bgs_submit since creation: 15 doubles (see bench.py host_path)
+    const HostPath& hp = e->host;
     double rec[15] = {0};
-    for (size_t i = 0; i < e->pin.size(); ++i) rec[i % 3] += e->pin[i].pinned, rec[3 + i % 3] += e->pin[i].refused;  // per role: input, mask, background
-    rec[6] = (double)e->diag_reg_calls, rec[7] = e->diag_reg_ms, rec[8] = (double)e->diag_unreg_calls, rec[9] = (double)e->diag_frames;
-    rec[10] = (double)e->diag_h2d_bytes, rec[11] = (double)e->diag_d2h_bytes, rec[12] = e->diag_stage_in_ms, rec[13] = e->diag_stage_out_ms, rec[14] = (double)e->arenas.size();
+    for (size_t i = 0; i < hp.pin.size(); ++i) rec[i % 3] += hp.pin[i].pinned, rec[3 + i % 3] += hp.pin[i].refused;  // per role: input, mask, background
+    rec[6] = (double)hp.reg_calls, rec[7] = hp.reg_ms, rec[8] = (double)hp.unreg_calls, rec[9] = (double)hp.frames;
+    rec[10] = (double)hp.h2d_bytes, rec[11] = (double)hp.d2h_bytes, rec[12] = hp.stage_in_ms, rec[13] = hp.stage_out_ms, rec[14] = (double)hp.arenas.size();
     return copy_host(plane, dst, cap, rec, sizeof(rec));
   }
   if (!strcmp(plane, "placement")) {  // diagnostics: [0] chunk size in MiB of the chunked model (0: one plain allocation), [1] number of chunks
@@ -1507,13 +1361,12 @@ int64_t bgs_kernel_timing_series(bgs_engine* e, float* ms, int64_t cap) {
 
 void bgs_destroy(bgs_engine* e) {
   if (!e) return;
-  if (e->n || e->stream) {
+  if (e->n || e->stream()) {
     (void)hipSetDevice(e->device);
     (void)hipDeviceSynchronize();
   }
   free_all(e);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
-  delete e;
+  delete e;  // ~HostPath closes the engine's stream
 }
 
 // ---- measurement aids (bench.py `calibration`): what THIS box's memory system and bus deliver, measured by the library that is being
@@ -1914,10 +1767,10 @@ int bgs_last_mask_blobs(bgs_engine* e, int stream, int connectivity, int min_w, 
     d_boxes = (bgs_box*)((char*)e->cc_work + ws);
     d_mom = (bgs_moments*)(d_boxes + e->cc_cap);
     int32_t* d_count = (int32_t*)(d_mom + e->cc_cap);
-    int rc = cc_run(e->device, e->d_fg, 1, e->rows, e->cols, connectivity, nullptr, d_boxes, e->cc_cap, d_count, nullptr, e->cc_work, e->stream, d_mom);
+    int rc = cc_run(e->device, e->host.sync.fg.d, 1, e->rows, e->cols, connectivity, nullptr, d_boxes, e->cc_cap, d_count, nullptr, e->cc_work, e->stream(), d_mom);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(&n, d_count, sizeof(n), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpyAsync(&n, d_count, sizeof(n), hipMemcpyDeviceToHost, e->stream()));
+    HIP_TRY(hipStreamSynchronize(e->stream()));
     if (n <= e->cc_cap) break;
     cap = n + n / 8 + 64;  // the true total is known now: one more pass with room for all of them
   }
@@ -2041,47 +1894,20 @@ int bgs_ingest_host(int hip_device, const bgs_ingest* c, const uint8_t* src, int
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(BGS_ERR_HIP, "no HIP device visible: libbgs_hip has no CPU path");
   HIP_TRY(hipSetDevice(hip_device));
   const size_t in_bytes = (size_t)src_rows * src_cols * channels, out_bytes = (size_t)pl.rows * out_row, ws = bgs_ingest_workspace(c, 1, src_rows, src_cols, channels);
-  uint8_t *d_in = nullptr, *d_out = nullptr, *d_ws = nullptr, *h_in = nullptr, *h_out = nullptr;
-  hipStream_t s = nullptr;
-  auto cleanup = [&]() {
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (d_ws) (void)hipFree(d_ws);
-    if (h_in) (void)hipHostFree(h_in);
-    if (h_out) (void)hipHostFree(h_out);
-    if (s) (void)hipStreamDestroy(s);
-  };
-  hipError_t er = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-  if (er == hipSuccess) er = hipMalloc((void**)&d_in, in_bytes);
-  if (er == hipSuccess) er = hipMalloc((void**)&d_out, out_bytes);
-  if (er == hipSuccess && ws) er = hipMalloc((void**)&d_ws, ws);
-  // the caller's images never go to hipMemcpy themselves (d2h_staged above: the runtime's by-address cache of pinned caller
-  // buffers): rows are packed into / unpacked from page-locked images of this call's own (the caller's step may exceed the row)
-  if (er == hipSuccess) er = hipHostMalloc((void**)&h_in, in_bytes, hipHostMallocDefault);
-  if (er == hipSuccess) er = hipHostMalloc((void**)&h_out, out_bytes, hipHostMallocDefault);
-  if (er == hipSuccess) {
-    const size_t in_row = (size_t)src_cols * channels;
-    for (int y = 0; y < src_rows; ++y) std::memcpy(h_in + (size_t)y * in_row, src + (size_t)y * src_step, in_row);
-    er = hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, s);
-  }
-  if (er != hipSuccess) {
-    (void)hipGetLastError();
-    cleanup();
-    return fail(BGS_ERR_HIP, "bgs_ingest_host: %s", hipGetErrorString(er));
-  }
-  rc = bgs_ingest_device(hip_device, c, d_in, 1, src_rows, src_cols, channels, (size_t)src_cols * channels, d_out, d_ws, s);
-  if (!rc) {
-    er = hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, s);
-    if (er == hipSuccess) er = hipStreamSynchronize(s);
-    if (er != hipSuccess)
-      rc = fail(BGS_ERR_HIP, "bgs_ingest_host: %s", hipGetErrorString(er));
-    else
-      for (int y = 0; y < pl.rows; ++y) std::memcpy(dst + (size_t)y * dst_step, h_out + (size_t)y * out_row, out_row);
-  } else {
-    (void)hipStreamSynchronize(s);
-  }
-  cleanup();
-  return rc;
+  const size_t in_row = (size_t)src_cols * channels;
+  Staging work;  // bgs_ingest_device's workspace; outlives the lane, whose destructor drains the stream
+  Lane ln;       // of this call alone: the raw frame as `in`, the prepared one as `fg`; released on every way out
+  hipError_t er = ln.make(in_bytes, out_bytes, 0);
+  if (er == hipSuccess) er = work.make(ws, /*host=*/false);
+  if (er == hipSuccess) er = upload_rows(ln.in, ln.in.d, ln.hs, src, src_step, in_row, src_rows, 1);
+  if (er != hipSuccess) return (void)hipGetLastError(), fail(BGS_ERR_HIP, "bgs_ingest_host: %s", hipGetErrorString(er));
+  rc = bgs_ingest_device(hip_device, c, ln.in.d, 1, src_rows, src_cols, channels, in_row, ln.fg.d, work.d, ln.hs);
+  if (rc) return rc;  // ~Lane drains the stream
+  er = download_whole(ln.fg, out_bytes, ln.hs);
+  if (er == hipSuccess) er = hipStreamSynchronize(ln.hs);
+  if (er != hipSuccess) return fail(BGS_ERR_HIP, "bgs_ingest_host: %s", hipGetErrorString(er));
+  unpack_rows(dst, dst_step, ln.fg.h, out_row, 0, pl.rows);
+  return BGS_OK;
 }
 
 

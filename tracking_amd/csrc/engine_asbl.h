@@ -18,10 +18,10 @@ int asbl_build_lut(bgs_engine* e) {
   if (!st.lut) HIP_TRY(hipMalloc((void**)&st.lut.p, 2 * one));
   const bgs_params& p = e->p;
   for (int learn = 1; learn >= 0; --learn)
-    hipLaunchKernelGGL(bgs::asbl_lut_kernel, dim3(bgs::kAsblLutRows), dim3(bgs::kBlock), 0, e->stream, st.lut + (learn ? 0 : one), learn, p.alpha_learn, 1 - p.alpha_learn,
+    hipLaunchKernelGGL(bgs::asbl_lut_kernel, dim3(bgs::kAsblLutRows), dim3(bgs::kBlock), 0, e->stream(), st.lut + (learn ? 0 : one), learn, p.alpha_learn, 1 - p.alpha_learn,
                        p.alpha_detection, 1 - p.alpha_detection);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream()));
   st.lut_alpha[0] = p.alpha_learn, st.lut_alpha[1] = p.alpha_detection, st.lut_valid = true;
   return BGS_OK;
 }

@@ -134,9 +134,9 @@ int64_t eig_get_state(bgs_engine* e, int stream, const char* plane, void* dst, s
   HIP_TRY(hipDeviceSynchronize());
   bgs::EigenArgs a = eig_args(e, stream, nullptr, nullptr, nullptr);
   a.result = r;
-  hipLaunchKernelGGL(bgs::eigen_reconstruct_kernel, dim3(blocks_for(e->n), 1), dim3(bgs::kBlock), 0, e->stream, a);
+  hipLaunchKernelGGL(bgs::eigen_reconstruct_kernel, dim3(blocks_for(e->n), 1), dim3(bgs::kBlock), 0, e->stream(), a);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream()));
   return fetch(dst, r, L * 4) ? BGS_ERR_HIP : (int64_t)(L * 4);
 }
 

@@ -74,8 +74,8 @@ int fz_allocate(bgs_engine* e) {
   DMALLOC(st.tab, 264 * sizeof(float));
   float tab[264];
   fz_table(tab);
-  HIP_TRY(hipMemcpyAsync(st.tab, tab, sizeof(tab), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));  // `tab` leaves scope
+  HIP_TRY(hipMemcpyAsync(st.tab, tab, sizeof(tab), hipMemcpyHostToDevice, e->stream()));
+  HIP_TRY(hipStreamSynchronize(e->stream()));  // `tab` leaves scope
   st.fn.assign(S, 0);
   st.detected.assign(S, 0);
   return BGS_OK;

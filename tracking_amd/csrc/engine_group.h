@@ -29,10 +29,10 @@ struct bgs_group {
   int64_t seen = 0, abl_counter = 0;
   int n_cu = 256;
   hipStream_t stream = nullptr;
-  // host staging (single-stream groups)
-  uint8_t *h_in = nullptr, *d_in = nullptr;
-  bool staged = false;  // bgs_group_process: the whole staging set exists
-  std::vector<uint8_t*> h_fg, h_bg, d_fg, d_bg;
+  // bgs_group_process (single-stream groups): staging of the frame and of every class's mask and background (host_path.h), made
+  // whole by the first call and released with the group
+  Staging in;
+  std::vector<Staging> fg, bg;
   // kernel timing of the fused launch
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -52,24 +52,11 @@ unsigned fan_bit_of(bgs_algo a) {
   }
 }
 
-void group_free_staging(bgs_group* g) {  // bgs_group_process's host staging, whatever of it came to be
-  if (g->d_in) (void)hipFree(g->d_in), g->d_in = nullptr;
-  if (g->h_in) (void)hipHostFree(g->h_in), g->h_in = nullptr;
-  for (auto* v : {&g->h_fg, &g->h_bg})
-    for (uint8_t*& p : *v)
-      if (p) (void)hipHostFree(p), p = nullptr;
-  for (auto* v : {&g->d_fg, &g->d_bg})
-    for (uint8_t*& p : *v)
-      if (p) (void)hipFree(p), p = nullptr;
-  g->staged = false;
-}
-
-void group_free(bgs_group* g) {
+void group_free(bgs_group* g) {  // the model; there is no staging before there is a model
   void* dev[] = {g->ring[0], g->ring[1], g->ring[2], g->sfd_bg, g->abl_state, g->abl_lut, g->sd_mt, g->sd_vt};
   for (void* d : dev)
     if (d) (void)hipFree(d);
   g->ring[0] = g->ring[1] = g->ring[2] = nullptr, g->sfd_bg = g->abl_state = g->abl_lut = g->sd_mt = g->sd_vt = nullptr;
-  group_free_staging(g);
   for (auto& ev : g->events) (void)hipEventDestroy(ev.first), (void)hipEventDestroy(ev.second);
   g->events.clear();
   g->abl_lut_valid = false;
@@ -295,7 +282,7 @@ int bgs_group_create(const bgs_algo* algos, const bgs_params* const* params, int
       return fail(BGS_ERR_HIP, "no HIP device visible: libbgs_hip has no CPU path");
     }
   }
-  g->h_fg.assign(n_algos, nullptr), g->h_bg.assign(n_algos, nullptr), g->d_fg.assign(n_algos, nullptr), g->d_bg.assign(n_algos, nullptr);
+  g->fg = std::vector<Staging>((size_t)n_algos), g->bg = std::vector<Staging>((size_t)n_algos);
   *out = g;
   return BGS_OK;
 }
@@ -370,46 +357,37 @@ int bgs_group_process(bgs_group* g, const uint8_t* in, int rows, int cols, int c
   int rc = bgs_group_set_geometry(g, rows, cols, channels);
   if (rc) return rc;
   const size_t fb = g->n * channels, row = (size_t)cols * channels;
-  if (!g->staged) {
+  auto bg_row = [&](int i) { return (size_t)cols * (g->algos[i] == BGS_ASBL ? 1 : channels); };  // bytes of a row of class i's background
+  if (!g->in.h) {
     // all or nothing: a staging set with some class's buffers missing would silently drop that class's outputs
-    hipError_t er = hipHostMalloc((void**)&g->h_in, fb, hipHostMallocDefault);
-    if (er == hipSuccess) er = hipMalloc((void**)&g->d_in, fb);
-    for (int i = 0; i < K && er == hipSuccess; ++i) {
-      const size_t bgb = g->n * (g->algos[i] == BGS_ASBL ? 1 : channels);
-      er = hipHostMalloc((void**)&g->h_fg[i], g->n, hipHostMallocDefault);
-      if (er == hipSuccess) er = hipHostMalloc((void**)&g->h_bg[i], bgb, hipHostMallocDefault);
-      if (er == hipSuccess) er = hipMalloc((void**)&g->d_fg[i], g->n);
-      if (er == hipSuccess) er = hipMalloc((void**)&g->d_bg[i], bgb);
-    }
+    hipError_t er = g->in.make(fb);
+    for (int i = 0; i < K && er == hipSuccess; ++i)
+      if ((er = g->fg[i].make(g->n)) == hipSuccess) er = g->bg[i].make(bg_row(i) * rows);
     if (er != hipSuccess) {
-      (void)hipGetLastError();
-      group_free_staging(g);
+      g->in.release();
+      for (int i = 0; i < K; ++i) g->fg[i].release(), g->bg[i].release();
       return fail(BGS_ERR_HIP, "bgs_group_process: staging buffers: %s", hipGetErrorString(er));
     }
-    g->staged = true;
   }
-  for (int y = 0; y < rows; ++y) std::memcpy(g->h_in + (size_t)y * row, in + (size_t)y * in_step, row);
-  HIP_TRY(hipMemcpyAsync(g->d_in, g->h_in, fb, hipMemcpyHostToDevice, g->stream));  // ONE upload for all the classes
+  HIP_TRY(upload_rows(g->in, g->in.d, g->stream, in, in_step, row, rows, 1));  // ONE upload for all the classes
   std::vector<uint8_t*> dfg((size_t)K), dbg((size_t)K);
-  for (int i = 0; i < K; ++i) dfg[i] = (fg && fg[i]) ? g->d_fg[i] : nullptr, dbg[i] = (bg && bg[i]) ? g->d_bg[i] : nullptr;
+  for (int i = 0; i < K; ++i) dfg[i] = (fg && fg[i]) ? g->fg[i].d : nullptr, dbg[i] = (bg && bg[i]) ? g->bg[i].d : nullptr;
   std::vector<uint32_t> flags((size_t)K, 0);
   const bool saved = g->borrow;
   g->borrow = false;  // the staging buffer is reused every frame: history must be a private copy
-  rc = group_process_device(g, g->d_in, dfg.data(), dbg.data(), g->stream, flags.data());
+  rc = group_process_device(g, g->in.d, dfg.data(), dbg.data(), g->stream, flags.data());
   g->borrow = saved;
   if (rc) return rc;
   for (int i = 0; i < K; ++i) {
-    const size_t bgc = g->algos[i] == BGS_ASBL ? 1 : channels;
-    if (dfg[i] && (flags[i] & BGS_FG_VALID)) HIP_TRY(hipMemcpyAsync(g->h_fg[i], g->d_fg[i], g->n, hipMemcpyDeviceToHost, g->stream));
-    if (dbg[i] && (flags[i] & BGS_BG_VALID)) HIP_TRY(hipMemcpyAsync(g->h_bg[i], g->d_bg[i], g->n * bgc, hipMemcpyDeviceToHost, g->stream));
+    if (!(flags[i] & BGS_FG_VALID)) dfg[i] = nullptr;  // from here on: what comes back
+    if (!(flags[i] & BGS_BG_VALID)) dbg[i] = nullptr;
+    if (dfg[i]) HIP_TRY(download_whole(g->fg[i], g->n, g->stream));
+    if (dbg[i]) HIP_TRY(download_whole(g->bg[i], bg_row(i) * rows, g->stream));
   }
   HIP_TRY(hipStreamSynchronize(g->stream));
   for (int i = 0; i < K; ++i) {
-    const size_t bgc = g->algos[i] == BGS_ASBL ? 1 : channels;
-    if (dfg[i] && (flags[i] & BGS_FG_VALID))
-      for (int y = 0; y < rows; ++y) std::memcpy(fg[i] + (size_t)y * (fg_step ? fg_step[i] : (size_t)cols), g->h_fg[i] + (size_t)y * cols, (size_t)cols);
-    if (dbg[i] && (flags[i] & BGS_BG_VALID))
-      for (int y = 0; y < rows; ++y) std::memcpy(bg[i] + (size_t)y * (bg_step ? bg_step[i] : (size_t)cols * bgc), g->h_bg[i] + (size_t)y * cols * bgc, (size_t)cols * bgc);
+    if (dfg[i]) unpack_rows(fg[i], fg_step ? fg_step[i] : (size_t)cols, g->fg[i].h, (size_t)cols, 0, rows);
+    if (dbg[i]) unpack_rows(bg[i], bg_step ? bg_step[i] : bg_row(i), g->bg[i].h, bg_row(i), 0, rows);
   }
   if (out_flags)
     for (int i = 0; i < K; ++i) out_flags[i] = flags[i];

@@ -94,10 +94,10 @@ int kde_allocate(bgs_engine* e) {
   kde_kernel_table(tab);
   int2 gate[256];
   kde_gate_table(p.kde_alpha, gate);
-  HIP_TRY(hipMemcpyAsync(st.lut, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(st.gate, gate, sizeof(gate), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemsetAsync(st.trips, 0, sizeof(unsigned long long), e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));  // `tab` and `gate` leave scope
+  HIP_TRY(hipMemcpyAsync(st.lut, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, e->stream()));
+  HIP_TRY(hipMemcpyAsync(st.gate, gate, sizeof(gate), hipMemcpyHostToDevice, e->stream()));
+  HIP_TRY(hipMemsetAsync(st.trips, 0, sizeof(unsigned long long), e->stream()));
+  HIP_TRY(hipStreamSynchronize(e->stream()));  // `tab` and `gate` leave scope
   return BGS_OK;
 }
 

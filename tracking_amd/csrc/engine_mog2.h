@@ -183,7 +183,7 @@ size_t mog2_state_bytes(const bgs_engine* e) {
 int mog2_allocate(bgs_engine* e) {
   Mog2State& st = make_state<Mog2State>(e);
   HIP_TRY(hipMalloc((void**)&st.d_stat.p, 3 * sizeof(unsigned)));
-  HIP_TRY(hipMemsetAsync(st.d_stat, 0, 3 * sizeof(unsigned), e->stream));  // ordered: allocate() drains e->stream before it returns
+  HIP_TRY(hipMemsetAsync(st.d_stat, 0, 3 * sizeof(unsigned), e->stream()));  // ordered: allocate() drains e->stream() before it returns
   HIP_TRY(hipHostMalloc((void**)&st.h_stat, 3 * Mog2State::kStatSlots * sizeof(unsigned), hipHostMallocDefault));
   for (hipEvent_t& ev : st.stat_ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   return model_allocate(e, st.model, mog2_state_bytes(e));

@@ -50,10 +50,7 @@ struct McModel {
   size_t n = 0;
   std::vector<int64_t> count;  // g_iFrameCount, one per stream; 0: the stream's next frame initialises its model (mc_reset_kernel)
   bool have_landmark = false;  // of the piecewise calls, which need every stream at the same age: one flag serves them all
-  // bgs_multicue_process: a HIP stream, page-locked staging and device buffers for one frame and one image, made by its first call
-  hipStream_t h_stream = nullptr;
-  uint8_t *h_pin = nullptr, *h_dev = nullptr;
-  size_t h_frame = 0;          // bytes of a frame, rounded up to 256: where the image starts in both buffers
+  Lane host;  // bgs_multicue_process: a HIP stream and the staging of one frame (in) and one image (fg), made by its first call (host_path.h)
   int taps[7] = {0};
   uint8_t* arena = nullptr;  // one allocation; everything below points into it
   uint8_t *red = nullptr, *gauss = nullptr, *xyz = nullptr, *landmark = nullptr;
@@ -65,9 +62,7 @@ struct McModel {
   bgs::McPlanes tb{}, tc{}, cb{}, cc{};
   int16_t *tref = nullptr, *tcnt = nullptr, *cref = nullptr, *ccnt = nullptr;
   ~McModel() {
-    if (h_stream) (void)hipStreamSynchronize(h_stream), (void)hipStreamDestroy(h_stream);
-    if (h_pin) (void)hipHostFree(h_pin);
-    if (h_dev) (void)hipFree(h_dev);
+    host.close();  // drains its stream before the model goes
     if (arena) (void)hipFree(arena);
   }
 };
@@ -351,24 +346,19 @@ int mc_process_host(McModel& m, int stream, const void* frame, int rows, int col
   int rc = mc_geometry(m, fn, frame, rows, cols, true);  // fixes the handle's geometry if nothing has yet: the staging below never changes size
   if (rc) return rc;
   HIP_TRY(hipSetDevice(m.device));
-  m.h_frame = (px * 3 + 255) & ~(size_t)255;
-  if (!m.h_pin) HIP_TRY(hipHostMalloc((void**)&m.h_pin, m.h_frame + px, hipHostMallocDefault));
-  if (!m.h_dev) HIP_TRY(hipMalloc((void**)&m.h_dev, m.h_frame + px));
-  if (!m.h_stream) HIP_TRY(hipStreamCreateWithFlags(&m.h_stream, hipStreamNonBlocking));
-  for (int y = 0; y < rows; ++y) std::memcpy(m.h_pin + (size_t)y * row, (const uint8_t*)frame + (size_t)y * step, row);
-  HIP_TRY(hipMemcpyAsync(m.h_dev, m.h_pin, px * 3, hipMemcpyHostToDevice, m.h_stream));
-  if ((rc = mc_process_range(m, fn, stream, 1, m.h_dev, rows, cols, m.h_dev + m.h_frame, m.h_stream))) return rc;
-  HIP_TRY(hipMemcpyAsync(m.h_pin + m.h_frame, m.h_dev + m.h_frame, px, hipMemcpyDeviceToHost, m.h_stream));
-  HIP_TRY(hipStreamSynchronize(m.h_stream));
-  const uint8_t* img = m.h_pin + m.h_frame;
-  for (int y = 0; y < rows; ++y) {
-    uint8_t* d = (uint8_t*)out + (size_t)y * out_step;
-    const uint8_t* q = img + (size_t)y * cols;
-    if (out_channels == 1)
-      std::memcpy(d, q, (size_t)cols);
-    else
-      for (int x = 0; x < cols; ++x) d[3 * x] = d[3 * x + 1] = d[3 * x + 2] = q[x];
+  Lane& ln = m.host;
+  if (!ln.done) {
+    const hipError_t er = ln.make(px * 3, px, 0);
+    if (er != hipSuccess) return fail(BGS_ERR_HIP, "%s: staging buffers: %s", fn, hipGetErrorString(er));
   }
+  HIP_TRY(upload_rows(ln.in, ln.in.d, ln.hs, (const uint8_t*)frame, step, row, rows, 1));
+  if ((rc = mc_process_range(m, fn, stream, 1, ln.in.d, rows, cols, ln.fg.d, ln.hs))) return rc;
+  HIP_TRY(download_whole(ln.fg, px, ln.hs));
+  HIP_TRY(hipStreamSynchronize(ln.hs));
+  if (out_channels == 1)
+    unpack_rows((uint8_t*)out, out_step, ln.fg.h, (size_t)cols, 0, rows);
+  else
+    unpack_rows_gray3((uint8_t*)out, out_step, ln.fg.h, cols, 0, rows);
   return BGS_OK;
 }
 

@@ -124,14 +124,14 @@ struct SbgState : FamilyState {
 };
 SbgState& sbg_of(const bgs_engine* e) { return state_of<SbgState>(e); }
 
-// (Re)build ABL's lookup table for the current alpha on e->stream.  Called when the geometry is set and when bgs_set_params
+// (Re)build ABL's lookup table for the current alpha on e->stream().  Called when the geometry is set and when bgs_set_params
 // changes alpha; both drain the device first / the stream after, so no launch on any stream sees a half-written table.
 int abl_build_lut(bgs_engine* e) {
   SbgState& st = sbg_of(e);
   if (!st.lut) HIP_TRY(hipMalloc((void**)&st.lut.p, 256 * 256));
-  hipLaunchKernelGGL(bgs::abl_lut_kernel, dim3(256), dim3(bgs::kBlock), 0, e->stream, st.lut.p, e->p.alpha, 1 - e->p.alpha);
+  hipLaunchKernelGGL(bgs::abl_lut_kernel, dim3(256), dim3(bgs::kBlock), 0, e->stream(), st.lut.p, e->p.alpha, 1 - e->p.alpha);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream()));
   st.lut_alpha = e->p.alpha, st.lut_valid = true;
   return BGS_OK;
 }

@@ -91,8 +91,8 @@ int ss_allocate(bgs_engine* e) {
     uint32_t m[bgs::kSsMagicN];
     for (uint32_t k = 0; k < (uint32_t)bgs::kSsMagicN; ++k) m[k] = bgs::ss_magic(k);
     DMALLOC(d->magic, sizeof(m));
-    HIP_TRY(hipMemcpyAsync(d->magic, m, sizeof(m), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));  // m is on this stack frame
+    HIP_TRY(hipMemcpyAsync(d->magic, m, sizeof(m), hipMemcpyHostToDevice, e->stream()));
+    HIP_TRY(hipStreamSynchronize(e->stream()));  // m is on this stack frame
   }
   DMALLOC(d->flood_flags, (size_t)e->S * bgs::kSsFloodFlags * sizeof(int));
   const size_t words = (size_t)e->S * e->rows * ((e->cols + 63) / 64);
