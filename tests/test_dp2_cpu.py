@@ -4,7 +4,6 @@ the C ABI defaults, the refused parameters and the host class list."""
 import ctypes as C
 import json
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -15,7 +14,6 @@ from tracking_amd import capi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
-HOST = os.path.join(HERE, os.pardir, "tracking_amd", "host")
 PRATI_CASES = ["default", "h4_r1", "h1_r3", "thr10", "ties", "ties_h64", "frames96"]
 TEXTURE_CASES = ["crop48x80", "crop32x64", "box32x48"]
 
@@ -190,20 +188,3 @@ def test_refused_parameters(field, value):
     h = C.c_void_p()
     assert capi.lib().bgs_create(capi.DP_PRATI_MEDIOD, C.byref(p), 0, 1, C.byref(h)) == capi.ERR_UNSUPPORTED
     assert b"PratiMediod" in capi.lib().bgs_last_error()
-
-
-def test_host_class_list():
-    """The two IBGS classes (bgs_classes_dp2.inc) are shared by the tested host mirror and the reference-side adapter, and
-    USTC_BGS types 14 and 16 build them (type 15, DPEigenbackground, and 23 stay refused)."""
-    inc = open(os.path.join(HOST, "bgs_classes_dp2.inc")).read()
-    assert re.findall(r"^class (\w+) : public HipBGSBase", inc, re.M) == ["DPPratiMediodBGS", "DPTextureBGS"]
-    for k in ('"threshold"', '"samplingRate"', '"historySize"', '"weight"', '"showOutput"'):
-        assert k in inc, k
-    for f in ("HipBGS.h", "bgs_host.h"):
-        src = open(os.path.join(HOST, f)).read()
-        assert src.index('#include "bgs_classes_kde.inc"') < src.index('#include "bgs_classes_dp2.inc"'), f
-    ustc = open(os.path.join(HOST, "ustc_bgs.h")).read()
-    assert "if (i == 14) bgs = new DPPratiMediodBGS;" in ustc and "if (i == 16) bgs = new DPTextureBGS;" in ustc
-    assert "i == 15" not in ustc and "i == 23" not in ustc
-    det = open(os.path.join(HOST, "HipFGDetector.h")).read()
-    assert "if (i == 14) bgs = new hipbgs::DPPratiMediodBGS;" in det and "if (i == 16) bgs = new hipbgs::DPTextureBGS;" in det

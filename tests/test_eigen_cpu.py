@@ -180,36 +180,6 @@ def test_every_refusal_names_the_class_and_needs_no_device():
 
 # ---- host layer ------------------------------------------------------------------------------------------------------------------------
 
-def test_host_class_list_keys_defaults_type_table_and_frame_processor():
-    inc = open(os.path.join(HOST, "bgs_classes_eigen.inc")).read()
-    assert re.findall(r"^class (\w+) : public \w+", inc, re.M) == ["DPEigenbackgroundBGS"]
-    keys = ["threshold", "historySize", "embeddedDim", "showOutput"]
-    assert re.findall(r'fs\.write\w+\("(\w+)"', inc) == keys == re.findall(r'fs\.read\w+\("(\w+)"', inc)  # the reference's order
-    for dflt in ('readInt("threshold", 225)', 'readInt("historySize", 20)', 'readInt("embeddedDim", 10)', 'readInt("showOutput", true)',
-                 "threshold(225), historySize(20), embeddedDim(10), showOutput(true)", "int threshold, historySize, embeddedDim;"):
-        assert dflt in inc, dflt
-    assert '"DPEigenbackgroundBGS"' in inc  # banners and ./config/DPEigenbackgroundBGS.xml
-    for f in ("HipBGS.h", "bgs_host.h"):
-        src = open(os.path.join(HOST, f)).read()
-        assert src.index('#include "bgs_classes_t2f.inc"') < src.index('#include "bgs_classes_eigen.inc"'), f
-    # The type table: the tests of the T2FGMM round pin USTC_BGS(15) as refused at run time and the switch as holding exactly cases
-    # 17 and 18, so type 15 is not wired in by number; the header says so and the class is reached as an IBGS / through FrameProcessor.
-    for f in ("ustc_bgs.h", "HipFGDetector.h"):
-        text = open(os.path.join(HOST, f)).read()
-        assert "i == 15)" not in text and "case 15:" not in text, f
-    assert "DPEigenbackgroundBGS" in open(os.path.join(HOST, "ustc_bgs.h")).read()
-    fp = open(os.path.join(HOST, "FrameProcessor.cpp")).read()
-    fph = open(os.path.join(HOST, "FrameProcessor.h")).read()
-    cls, member = "DPEigenbackgroundBGS", "eigenBackground"
-    assert 'enable%s = fs.readInt("enable%s", false)' % (cls, cls) in fp and 'process("%s", %s, img_prep, img_eigbkg)' % (cls, member) in fp
-    assert 'fs.writeInt("enable%s", enable%s)' % (cls, cls) in fp and "new %s;" % cls in fp and "delete %s" % member in fp
-    assert "bool enable%s;" % cls in fph and "%s* %s;" % (cls, member) in fph
-    for frag in ("new %s;", 'process("%s"', 'fs.writeInt("enable%s"', 'fs.readInt("enable%s"'):  # between PratiMediod and Texture, as in the reference
-        a, b, c = (fp.index(frag % k) for k in ("DPPratiMediodBGS", cls, "DPTextureBGS"))
-        assert a < b < c, frag
-    assert "bgs_classes_eigen.inc" in open(os.path.join(HOST, "Makefile")).read()
-
-
 def test_frame_processor_builds_the_class_and_writes_the_reference_xml(tmp_path):
     """Without a GPU the first frame ends in the one exception of the host layer; by then the class's banner is out and saveConfig()
     has written the reference's keys in the reference's order with the reference's defaults.  With a GPU the run succeeds."""

@@ -4,7 +4,6 @@ ABI (ids, the second hole, bgs_fuzzy_params, every refusal) and the host layer."
 import ctypes as C
 import json
 import os
-import re
 import subprocess
 import zlib
 
@@ -16,7 +15,6 @@ from tracking_amd import capi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
-HOST = os.path.join(HERE, os.pardir, "tracking_amd", "host")
 REF = np.load(os.path.join(GOLDEN, "fuzzy_ref.npz"))
 CASES = ["choquet_default", "sugeno_default", "choquet_opt1", "sugeno_opt1", "nosmooth", "portrait", "square", "tiny3x3", "tiny2x2", "thr_edge", "relearn", "flat"]
 SIZEOF_BGS_PARAMS_PARENT = 336  # sizeof(bgs_params) of the commit before this class: bgs_params must not grow
@@ -246,33 +244,6 @@ def test_ohta_finding():
 
 
 # ---- host layer ------------------------------------------------------------------------------------------------------------------------
-
-def test_host_class_list_keys_defaults_and_type_table():
-    inc = open(os.path.join(HOST, "bgs_classes_fuzzy.inc")).read()
-    assert re.findall(r"^class (\w+) : public \w+", inc, re.M) == ["FuzzyIntegralBase", "FuzzySugenoIntegral", "FuzzyChoquetIntegral"]
-    keys = ["showOutput", "framesToLearn", "alphaLearn", "alphaUpdate", "colorSpace", "option", "smooth", "threshold"]
-    assert re.findall(r'fs\.write\w+\("(\w+)"', inc) == keys == re.findall(r'fs\.read\w+\("(\w+)"', inc)  # the reference's order
-    for dflt in ('readInt("showOutput", true)', 'readInt("framesToLearn", 10)', 'readReal("alphaLearn", 0.1)', 'readReal("alphaUpdate", 0.01)', 'readInt("colorSpace", 1)',
-                 'readInt("option", 2)', 'readInt("smooth", true)', 'readReal("threshold", 0.67)'):
-        assert dflt in inc, dflt
-    assert '"FuzzySugenoIntegral"' in inc and '"FuzzyChoquetIntegral"' in inc  # ./config/<name>.xml
-    for f in ("HipBGS.h", "bgs_host.h"):
-        src = open(os.path.join(HOST, f)).read()
-        assert src.index('#include "bgs_classes_vumeter.inc"') < src.index('#include "bgs_classes_fuzzy.inc"'), f
-    ustc = open(os.path.join(HOST, "ustc_bgs.h")).read()
-    det = open(os.path.join(HOST, "HipFGDetector.h")).read()
-    assert "if (i == 21) bgs = new FuzzySugenoIntegral;" in ustc and "if (i == 22) bgs = new FuzzyChoquetIntegral;" in ustc
-    assert "if (i == 21) bgs = new hipbgs::FuzzySugenoIntegral;" in det and "if (i == 22) bgs = new hipbgs::FuzzyChoquetIntegral;" in det
-    for n in (15, 17, 18, 19, 20, 23, 30, 33, 34):
-        assert "i == %d)" % n not in ustc and "i == %d)" % n not in det, n
-    assert " tb/," not in ustc  # the header comment no longer lists all of tb/ as outside the path
-    fp = open(os.path.join(HOST, "FrameProcessor.cpp")).read()
-    fph = open(os.path.join(HOST, "FrameProcessor.h")).read()
-    for cls in ("FuzzySugenoIntegral", "FuzzyChoquetIntegral"):
-        assert 'enable%s = fs.readInt("enable%s", false)' % (cls, cls) in fp and 'process("%s", ' % cls in fp and 'fs.writeInt("enable%s", enable%s)' % (cls, cls) in fp
-        assert "bool enable%s;" % cls in fph
-    assert "bgs_classes_fuzzy.inc" in open(os.path.join(HOST, "Makefile")).read()
-
 
 def test_reference_side_adapters_compile_with_the_fuzzy_classes(tmp_path):
     root = os.path.dirname(HERE)

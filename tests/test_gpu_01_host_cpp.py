@@ -134,6 +134,20 @@ def test_ustc_bgs_type_table(demo, tmp_path, golden_frames, utype, algo_name):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("utype,bg_channels", [(7, 1), (5, 3)])
+def test_background_model_channels(demo, tmp_path, golden_frames, utype, bg_channels):
+    """AdaptiveSelectiveBackgroundLearning (type 7) keeps a gray background model and hands out 8UC1; MixtureOfGaussianV2BGS (type 5), like
+    every class that does not say otherwise, hands out a background with the input's three channels.  The mask is 8UC1 for both."""
+    os.makedirs(tmp_path / "config")
+    raw = os.path.join(str(tmp_path), "frames.raw")
+    golden_frames[:3].tofile(raw)
+    r = subprocess.run([demo, raw, "80", "96", "3", os.path.join(str(tmp_path), "out"), str(utype), "shapes"], cwd=str(tmp_path), capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    shapes = [l for l in r.stdout.split("\n") if l.startswith("frame ")]
+    assert shapes[-1] == "frame 2 mask 80x96x1 background 80x96x%d" % bg_channels, shapes
+
+
+@pytest.mark.gpu
 def test_ustc_bgs_rejects_types_outside_the_path(demo, tmp_path, golden_frames):
     os.makedirs(tmp_path / "config")
     raw = os.path.join(str(tmp_path), "frames.raw")

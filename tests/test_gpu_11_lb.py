@@ -298,7 +298,7 @@ def test_demo_ustc_types_25_29_and_frame_processor_equal_fixture(tmp_path):
             (wd / "config").mkdir(parents=True)
             (wd / "config" / ("%s.xml" % name)).write_text('<?xml version="1.0"?>\n<opencv_storage>\n%s</opencv_storage>\n' % xml)
             if mode == "ustc":
-                args = [DEMO, raw, str(rows), str(cols), str(n), str(wd / "out"), str(cls)]
+                args = [DEMO, raw, str(rows), str(cols), str(n), str(wd / "out"), str(cls), "shapes"]
                 out = wd / "out.ustc.raw"
             else:
                 write_fp_config(str(wd / "config"), set())
@@ -312,6 +312,9 @@ def test_demo_ustc_types_25_29_and_frame_processor_equal_fixture(tmp_path):
             assert res.returncode == 0, res.stdout + res.stderr
             got = np.fromfile(str(out), np.uint8).reshape(n, rows, cols)
             assert np.array_equal(got, want), (name, mode, int((got != want).sum()))
+            if mode == "ustc":  # the wrappers hand out cv::Mat(m_pBGModel->GetFG()): an 8UC3 mask (the file above holds its first channel)
+                shapes = [l for l in res.stdout.split("\n") if l.startswith("frame ")]
+                assert len(shapes) == n and all(" mask %dx%dx3 " % (rows, cols) in l for l in shapes), shapes[:3]
             saved = (wd / "config" / ("%s.xml" % name)).read_text()
             assert "<showOutput>1</showOutput>" in saved and "<sensitivity>%d</sensitivity>" % p["sensitivity"] in saved
 

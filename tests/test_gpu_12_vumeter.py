@@ -319,7 +319,7 @@ def test_demo_ustc_type_31_and_frame_processor_equal_the_restatement(tmp_path):
             (wd / "config").mkdir(parents=True)
             (wd / "config" / "VuMeter.xml").write_text('<?xml version="1.0"?>\n<opencv_storage>\n%s</opencv_storage>\n' % xml)
             if mode == "ustc":
-                args = [DEMO, raw, str(rows), str(cols), str(n), str(wd / "out"), "31"]
+                args = [DEMO, raw, str(rows), str(cols), str(n), str(wd / "out"), "31", "shapes"]
                 out = wd / "out.ustc.raw"
             else:
                 write_fp_config(str(wd / "config"), set())
@@ -333,5 +333,8 @@ def test_demo_ustc_type_31_and_frame_processor_equal_the_restatement(tmp_path):
             assert res.returncode == 0, res.stdout + res.stderr
             got = np.fromfile(str(out), np.uint8).reshape(n, rows, cols)
             assert np.array_equal(got, want), (mode, filt, int((got != want).sum()))
+            if mode == "ustc":  # mask and background model are 8UC1: the background is the gray image the model keeps
+                shapes = [l for l in res.stdout.split("\n") if l.startswith("frame ")]
+                assert shapes == ["frame %d mask %dx%dx1 background %dx%dx1" % (t, rows, cols, rows, cols) for t in range(n)], shapes[:3]
             saved = (wd / "config" / "VuMeter.xml").read_text()
             assert "<showOutput>1</showOutput>" in saved and "<enableFilter>%d</enableFilter>" % filt in saved and "<binSize>8</binSize>" in saved

@@ -123,18 +123,3 @@ def test_parameter_limits_are_rejected(field, value):
     h = C.c_void_p()
     assert capi.lib().bgs_create(capi.KDE, C.byref(p), 0, 1, C.byref(h)) == capi.ERR_INVALID
     assert b"KDE" in capi.lib().bgs_last_error()
-
-
-def test_host_class_list_includes_kde():
-    """The KDE IBGS class (bgs_classes_kde.inc) is shared by the tested host mirror and the reference-side adapter, and USTC_BGS type 32
-    builds it (type 23 stays refused)."""
-    import re
-    host = os.path.join(os.path.dirname(GOLDEN.rstrip("/")), os.pardir, "tracking_amd", "host")
-    inc = open(os.path.join(host, "bgs_classes_kde.inc")).read()
-    assert re.findall(r"^class (\w+) : public HipBGSBase", inc, re.M) == ["KDE"]
-    for k in ("framesToLearn", "SequenceLength", "TimeWindowSize", "SDEstimationFlag", "lUseColorRatiosFlag", '"th"', '"alpha"', "showOutput"):
-        assert k in inc, k
-    for f in ("HipBGS.h", "bgs_host.h"):
-        assert '#include "bgs_classes_kde.inc"' in open(os.path.join(host, f)).read(), f
-    ustc = open(os.path.join(host, "ustc_bgs.h")).read()
-    assert "if (i == 32) bgs = new KDE;" in ustc and "i == 23" not in ustc

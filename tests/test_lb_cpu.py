@@ -4,7 +4,6 @@ tolerance, what the fixtures claim to cover, the C ABI (ids, struct tail, defaul
 import ctypes as C
 import json
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -15,7 +14,6 @@ from tracking_amd import capi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
-HOST = os.path.join(HERE, os.pardir, "tracking_amd", "host")
 SHORT = {25: "sg", 26: "fg", 27: "mog", 28: "som", 29: "fsom"}
 CLASSES = [25, 26, 27, 28, 29]
 EXACT, FUZZY = (25, 27, 28), (26, 29)
@@ -216,30 +214,6 @@ def test_refused_parameters(cls, field, value):
 
 
 # ---- host layer ------------------------------------------------------------------------------------------------------------------------
-
-def test_host_class_list_and_type_table():
-    """The five IBGS classes (bgs_classes_lb.inc) are shared by the tested host mirror and the reference-side adapter; USTC_BGS types
-    25-29 build them (15, DPEigenbackground, and 23 stay refused); FrameProcessor knows the reference's five enable flags."""
-    inc = open(os.path.join(HOST, "bgs_classes_lb.inc")).read()
-    names = [ln.NAMES[c] for c in CLASSES]
-    assert re.findall(r"^class (\w+) : public HipBGSBase", inc, re.M) == names
-    for k in ("sensitivity", "noiseVariance", "learningRate", "bgThreshold", "trainingSensitivity", "trainingLearningRate", "trainingSteps", "showOutput"):
-        assert '"%s"' % k in inc, k
-    assert inc.count("{ fg_channels_ = 3; }") == 5
-    for f in ("HipBGS.h", "bgs_host.h"):
-        src = open(os.path.join(HOST, f)).read()
-        assert src.index('#include "bgs_classes_dp2.inc"') < src.index('#include "bgs_classes_lb.inc"'), f
-    ustc = open(os.path.join(HOST, "ustc_bgs.h")).read()
-    det = open(os.path.join(HOST, "HipFGDetector.h")).read()
-    for typ, name in zip(CLASSES, names):
-        assert "if (i == %d) bgs = new %s;" % (typ, name) in ustc
-        assert "if (i == %d) bgs = new hipbgs::%s;" % (typ, name) in det
-    assert "i == 15" not in ustc and "i == 23" not in ustc and "i == 15" not in det and "i == 23" not in det
-    fp = open(os.path.join(HOST, "FrameProcessor.cpp")).read()
-    for name in names:
-        assert 'fs.readInt("enable%s", false)' % name in fp and 'process("%s", ' % name in fp, name
-    assert "bgs_classes_lb.inc" in open(os.path.join(HOST, "Makefile")).read()
-
 
 def test_reference_side_adapters_compile_with_the_lb_classes(tmp_path):
     """HipBGS.h / HipFGDetector.h with the five classes, -std=gnu++0x against the declaration-only OpenCV mock (the 8UC3 mask is

@@ -173,36 +173,6 @@ def test_every_refusal_names_the_class_and_needs_no_device(algo, name):
 
 # ---- host layer ------------------------------------------------------------------------------------------------------------------------
 
-def test_host_class_list_keys_defaults_and_type_table():
-    inc = open(os.path.join(HOST, "bgs_classes_t2f.inc")).read()
-    assert re.findall(r"^class (\w+) : public \w+", inc, re.M) == ["T2FGMMBase", "T2FGMM_UM", "T2FGMM_UV"]
-    keys = ["threshold", "alpha", "km", "kv", "gaussians", "showOutput"]
-    assert re.findall(r'fs\.write\w+\("(\w+)"', inc) == keys == re.findall(r'fs\.read\w+\("(\w+)"', inc)  # the reference's order
-    for dflt in ('readReal("threshold", 9.0)', 'readReal("alpha", 0.01)', 'readReal("km", 1.5)', 'readReal("kv", 0.6)', 'readInt("gaussians", 3)', 'readInt("showOutput", true)',
-                 "threshold(9.0), alpha(0.01), km(1.5f), kv(0.6f), gaussians(3), showOutput(true)", "double threshold, alpha;", "float km, kv;"):
-        assert dflt in inc, dflt
-    assert '"T2FGMM_UM"' in inc and '"T2FGMM_UV"' in inc  # banners and ./config/<name>.xml
-    for f in ("HipBGS.h", "bgs_host.h"):
-        src = open(os.path.join(HOST, f)).read()
-        assert src.index('#include "bgs_classes_fuzzy.inc"') < src.index('#include "bgs_classes_t2f.inc"'), f
-    ustc = open(os.path.join(HOST, "ustc_bgs.h")).read()
-    det = open(os.path.join(HOST, "HipFGDetector.h")).read()
-    assert "case 17: bgs = new T2FGMM_UM; break;" in ustc and "case 18: bgs = new T2FGMM_UV; break;" in ustc
-    assert "case 17: bgs = new hipbgs::T2FGMM_UM; break;" in det and "case 18: bgs = new hipbgs::T2FGMM_UV; break;" in det
-    for text in (ustc, det):
-        assert set(re.findall(r"case (\d+):", text)) == {"17", "18"}
-        for n in (15, 19, 20, 23, 30, 33, 34):
-            assert "i == %d)" % n not in text, n
-    assert "T2FMRF.cpp:331" in ustc  # why 19 and 20 stay refused
-    fp = open(os.path.join(HOST, "FrameProcessor.cpp")).read()
-    fph = open(os.path.join(HOST, "FrameProcessor.h")).read()
-    for cls, member in (("T2FGMM_UM", "type2FuzzyGMM_UM"), ("T2FGMM_UV", "type2FuzzyGMM_UV")):
-        assert 'enable%s = fs.readInt("enable%s", false)' % (cls, cls) in fp and 'process("%s", %s, ' % (cls, member) in fp
-        assert 'fs.writeInt("enable%s", enable%s)' % (cls, cls) in fp and "new %s;" % cls in fp and "delete %s" % member in fp
-        assert "bool enable%s;" % cls in fph and "%s* %s;" % (cls, member) in fph
-    assert "bgs_classes_t2f.inc" in open(os.path.join(HOST, "Makefile")).read()
-
-
 @pytest.fixture(scope="module")
 def demo():
     subprocess.run(["make", "-s", "-C", HOST], check=True)

@@ -5,7 +5,6 @@ formula, the C ABI (ids, struct tail, defaults, setter rules) and the host class
 import ctypes as C
 import json
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -16,7 +15,6 @@ from tracking_amd import capi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
-HOST = os.path.join(HERE, os.pardir, "tracking_amd", "host")
 CASES = ["default", "bins3", "bins100", "bins200", "bins1", "setters", "thr_edge", "denormal", "denormal_mid", "long"]
 WHOLE_MODEL = ["bins3", "bins1", "denormal", "denormal_mid", "long"]  # the cases that hold every histogram plane after the last frame
 VU_FIELDS = ["vu_bin_size", "vu_enable_filter", "vu_alpha", "vu_threshold"]
@@ -218,28 +216,6 @@ def test_out_of_range_values_are_replaced_not_refused(field, value):
 
 
 # ---- host layer ------------------------------------------------------------------------------------------------------------------------
-
-def test_host_class_list_and_type_table():
-    inc = open(os.path.join(HOST, "bgs_classes_vumeter.inc")).read()
-    assert re.findall(r"^class (\w+) : public HipBGSBase", inc, re.M) == ["VuMeter"]
-    keys = re.findall(r'fs\.write\w+\("(\w+)"', inc)
-    assert keys == ["enableFilter", "binSize", "alpha", "threshold", "showOutput"] == re.findall(r'fs\.read\w+\("(\w+)"', inc)  # the reference's order
-    for dflt in ('readInt("enableFilter", true)', 'readInt("binSize", 8)', 'readReal("alpha", 0.995)', 'readReal("threshold", 0.03)', 'readInt("showOutput", true)'):
-        assert dflt in inc, dflt
-    for f in ("HipBGS.h", "bgs_host.h"):
-        src = open(os.path.join(HOST, f)).read()
-        assert src.index('#include "bgs_classes_lb.inc"') < src.index('#include "bgs_classes_vumeter.inc"'), f
-        assert "algo_ == BGS_VUMETER" in src, f  # the 1-channel background image
-    ustc = open(os.path.join(HOST, "ustc_bgs.h")).read()
-    det = open(os.path.join(HOST, "HipFGDetector.h")).read()
-    assert "if (i == 31) bgs = new VuMeter;" in ustc and "if (i == 31) bgs = new hipbgs::VuMeter;" in det
-    assert "i == 15" not in ustc and "i == 23" not in ustc and "i == 15" not in det and "i == 23" not in det
-    assert "ck/, av/," not in ustc  # the header comment no longer lists av/ as outside the path
-    fp = open(os.path.join(HOST, "FrameProcessor.cpp")).read()
-    assert 'enableVuMeter = fs.readInt("enableVuMeter", false)' in fp and 'process("VuMeter", ' in fp and 'fs.writeInt("enableVuMeter", enableVuMeter)' in fp
-    assert "bool enableVuMeter;" in open(os.path.join(HOST, "FrameProcessor.h")).read()
-    assert "bgs_classes_vumeter.inc" in open(os.path.join(HOST, "Makefile")).read()
-
 
 def test_reference_side_adapters_compile_with_vumeter(tmp_path):
     root = os.path.dirname(HERE)

@@ -8,6 +8,8 @@
 // Same control flow as the reference: one IBGS instance per enabled class, created in init(), fed the same
 // pre-processed frame in the reference's order, one mask per class kept in a member image.  The PreProcessor (PreProcessor.h:
 // copy, optional equalizeHist / GaussianBlur from ./config/PreProcessor.xml) is created in init() like the reference's (:37-38).
+// What the reference spells out per class in seven places is one line of FrameProcessor::classes here (FrameProcessor.cpp);
+// the constructor, init(), process(), finish() and the XML description loop over it.
 #pragma once
 #include <chrono>
 #include <string>
@@ -23,7 +25,7 @@ class IFrameProcessor {  // IFrameProcessor.h:23-28
   virtual ~IFrameProcessor() {}
 };
 
-class FrameProcessor : public IFrameProcessor {
+class FrameProcessor : public IFrameProcessor, protected XmlDescribed {
  public:
   FrameProcessor();
   ~FrameProcessor() override;
@@ -45,6 +47,17 @@ class FrameProcessor : public IFrameProcessor {
   Image img_fsi, img_fci;  // FrameProcessor.h (reference): FuzzySugenoIntegral / FuzzyChoquetIntegral masks
   Image img_vumeter;  // FrameProcessor.h (reference): img_vumeter
   Image img_lb_sg, img_lb_fg, img_lb_mog, img_lb_som, img_lb_fsom;  // 8UC3 masks, equal channels (the lb/ wrappers' own convention)
+  // One line per class, in the reference's order (the order of init(), process() and the XML keys).
+  struct Class {
+    const char* name;              // process(name, ...), the XML key "enable" + name, what tictoc names
+    bool enabled;                  // the XML key's default
+    IBGS* (*make)();               // new <Class>
+    Image FrameProcessor::*image;  // where the mask is kept
+    int teardown;                  // finish() deletes in descending order of this (:342-482: not quite the reverse of init())
+    const char* file;              // bgs_demo writes the masks to <out_prefix>.<file>.raw
+  };
+  enum { kClasses = 34 };
+  static const Class classes[kClasses];
   double lastDuration() const { return duration; }
   int groupedClasses() const { return (int)grouped_.size(); }  // how many classes share the fused launch (0: none)
 
@@ -58,74 +71,8 @@ class FrameProcessor : public IFrameProcessor {
 
   PreProcessor* preProcessor;
   bool enablePreProcessor;
-  FrameDifferenceBGS* frameDifference;
-  bool enableFrameDifferenceBGS;
-  StaticFrameDifferenceBGS* staticFrameDifference;
-  bool enableStaticFrameDifferenceBGS;
-  WeightedMovingMeanBGS* weightedMovingMean;
-  bool enableWeightedMovingMeanBGS;
-  WeightedMovingVarianceBGS* weightedMovingVariance;
-  bool enableWeightedMovingVarianceBGS;
-  MixtureOfGaussianV1BGS* mixtureOfGaussianV1BGS;
-  bool enableMixtureOfGaussianV1BGS;
-  MixtureOfGaussianV2BGS* mixtureOfGaussianV2BGS;
-  bool enableMixtureOfGaussianV2BGS;
-  AdaptiveBackgroundLearning* adaptiveBackgroundLearning;
-  bool enableAdaptiveBackgroundLearning;
-  GMG* gmg;
-  bool enableGMG;
-  DPAdaptiveMedianBGS* adaptiveMedian;
-  bool enableDPAdaptiveMedianBGS;
-  DPGrimsonGMMBGS* grimsonGMM;
-  bool enableDPGrimsonGMMBGS;
-  DPZivkovicAGMMBGS* zivkovicAGMM;
-  bool enableDPZivkovicAGMMBGS;
-  DPMeanBGS* temporalMean;
-  bool enableDPMeanBGS;
-  DPWrenGABGS* wrenGA;
-  bool enableDPWrenGABGS;
-  DPPratiMediodBGS* pratiMediod;
-  bool enableDPPratiMediodBGS;
-  DPEigenbackgroundBGS* eigenBackground;
-  bool enableDPEigenbackgroundBGS;
-  DPTextureBGS* textureBGS;
-  bool enableDPTextureBGS;
-  T2FGMM_UM* type2FuzzyGMM_UM;
-  bool enableT2FGMM_UM;
-  T2FGMM_UV* type2FuzzyGMM_UV;
-  bool enableT2FGMM_UV;
-  FuzzySugenoIntegral* fuzzySugenoIntegral;
-  bool enableFuzzySugenoIntegral;
-  FuzzyChoquetIntegral* fuzzyChoquetIntegral;
-  bool enableFuzzyChoquetIntegral;
-  LBSimpleGaussian* lbSimpleGaussian;
-  bool enableLBSimpleGaussian;
-  LBFuzzyGaussian* lbFuzzyGaussian;
-  bool enableLBFuzzyGaussian;
-  LBMixtureOfGaussians* lbMixtureOfGaussians;
-  bool enableLBMixtureOfGaussians;
-  LBAdaptiveSOM* lbAdaptiveSOM;
-  bool enableLBAdaptiveSOM;
-  LBFuzzyAdaptiveSOM* lbFuzzyAdaptiveSOM;
-  bool enableLBFuzzyAdaptiveSOM;
-  VuMeter* vuMeter;
-  bool enableVuMeter;
-  KDE* kde;
-  bool enableKDE;
-  IndependentMultimodalBGS* imbs;  // FrameProcessor.h:222-223
-  bool enableIMBS;
-  SJN_MultiCueBGS* mcbgs;  // FrameProcessor.h:225-227
-  bool enableMultiCueBGS;
-  MultiLayerBGS* multiLayerBGS;  // FrameProcessor.h (reference): multiLayerBGS / enableMultiLayerBGS
-  bool enableMultiLayerBGS;
-  SigmaDeltaBGS* sdbgs;
-  bool enableSigmaDeltaBGS;
-  SuBSENSEBGS* ssbgs;
-  bool enableSuBSENSEBGS;
-  LOBSTERBGS* lobgs;
-  bool enableLOBSTERBGS;
-  AdaptiveSelectiveBackgroundLearning* adaptiveSelectiveBackgroundLearning;  // not in the reference's FrameProcessor (Demo.cpp / USTC_BGS type 7 only)
-  bool enableAdaptiveSelectiveBackgroundLearning;
+  IBGS* bgs_[kClasses];     // classes[i]'s object while it is enabled, between init() and finish()
+  bool enabled_[kClasses];  // ./config/FrameProcessor.xml: enable<classes[i].name>
 
   // the enabled byte-stream classes share ONE launch per frame (bgs_group) when there are at least two of them
   bgs_group* group_ = nullptr;
@@ -135,8 +82,9 @@ class FrameProcessor : public IFrameProcessor {
   void process(std::string name, IBGS* bgs, const Image& img_input, Image& img_bgs);
   void tic(std::string value);
   void toc();
-  void saveConfig();
-  void loadConfig();
+  void describe(XmlIo& io) override;
+  void saveConfig() { saveDescribed("./config/FrameProcessor.xml"); }
+  void loadConfig() { loadDescribed("./config/FrameProcessor.xml"); }
 };
 
 }  // namespace bgs_hip

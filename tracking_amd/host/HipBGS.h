@@ -6,16 +6,17 @@
 //   SigmaDeltaBGS, SuBSENSEBGS, LOBSTERBGS, DPZivkovicAGMMBGS, DPGrimsonGMMBGS, DPWrenGABGS, DPMeanBGS, DPAdaptiveMedianBGS, KDE,
 //   DPPratiMediodBGS, DPTextureBGS, LBSimpleGaussian, LBFuzzyGaussian, LBMixtureOfGaussians, LBAdaptiveSOM, LBFuzzyAdaptiveSOM, VuMeter,
 //   FuzzySugenoIntegral, FuzzyChoquetIntegral, T2FGMM_UM, T2FGMM_UV, DPEigenbackgroundBGS, IndependentMultimodalBGS, MultiLayerBGS, SJN_MultiCueBGS
-// Each reads / writes the same ./config/<Class>.xml with the same keys and defaults as the class it stands in for
-// (the list is bgs_classes.inc + bgs_classes_kde.inc + bgs_classes_dp2.inc + bgs_classes_lb.inc + bgs_classes_vumeter.inc + bgs_classes_fuzzy.inc + bgs_classes_t2f.inc + bgs_classes_eigen.inc + bgs_classes_imbs.inc + bgs_classes_multilayer.inc + bgs_classes_multicue.inc, shared verbatim with this repository's tested host mirror, tracking_amd/host/bgs_host.h).
+// Each reads / writes the same ./config/<Class>.xml with the same keys and defaults as the class it stands in for: every class
+// describes its file once (bgs_describe.inc), in the bgs_classes*.inc files, shared verbatim with this repository's tested host
+// mirror, tracking_amd/host/bgs_host.h.
 //
 // Use:   mixtureOfGaussianV2BGS = new hipbgs::MixtureOfGaussianV2BGS;      // FrameProcessor.cpp:59-60
 //        if(i==36) bgs = new hipbgs::SuBSENSEBGS();                          // ustc_src/ustc_bgs.cpp:68
 // Build: -I<repo>/include -I<repo>/tracking_amd/host  -L<repo>/tracking_amd/lib -lbgs_hip
 //
 // This file needs OpenCV 2.4 headers, which the build image of this repository does not have: it is checked for syntax against
-// a declaration-only mock (tests/mock_opencv, test_reference_side_adapters_compile in tests/test_capi_cpu.py, -std=gnu++0x like the
-// reference's CMakeLists.txt:5); the logic it shares with bgs_host.h is what the tests exercise.
+// a declaration-only mock (tests/mock_opencv, tests/test_host_classes_cpu.py, every class instantiated, -std=gnu++0x like the
+// reference's CMakeLists.txt:5); the logic it shares with bgs_host.h is what the tests run.
 #pragma once
 #include <iostream>
 #include <string>
@@ -68,9 +69,15 @@ class XmlConfig {
   std::vector<std::pair<std::string, int> > order_;
 };
 
+#ifndef override
+#define BGS_HIP_DEFINED_OVERRIDE
+#define override  /* the reference builds as C++03 */
+#endif
+#include "bgs_describe.inc"
+
 // Common machinery: one single-stream engine, per-frame config reload, the reference's output conventions
 // (outputs left untouched on warm-up frames and for classes that never write a background).
-class HipBGSBase : public IBGS {
+class HipBGSBase : public IBGS, protected XmlDescribed {
  public:
   virtual ~HipBGSBase() {
     if (engine_) bgs_destroy(engine_);
@@ -85,9 +92,8 @@ class HipBGSBase : public IBGS {
       fail();
     }
     if (applyClassParams(engine_)) fail();
-    const int bg_ch = (algo_ == BGS_ASBL || algo_ == BGS_VUMETER) ? 1 : img_input.channels();
     fg_.create(img_input.size(), CV_8UC1);
-    bg_.create(img_input.size(), CV_MAKETYPE(CV_8U, bg_ch));
+    bg_.create(img_input.size(), CV_MAKETYPE(CV_8U, bgChannels(img_input.channels())));
     uint32_t flags = 0;
     if (bgs_process(engine_, 0, img_input.data, img_input.rows, img_input.cols, img_input.channels(), img_input.step, fg_.data, fg_.step, bg_.data, bg_.step, &flags))
       fail();
@@ -135,10 +141,11 @@ class HipBGSBase : public IBGS {
   bgs_params params_;
   virtual int applyClassParams(bgs_engine*) { return 0; }  // parameters outside bgs_params (bgs_classes_fuzzy.inc, bgs_classes_t2f.inc, bgs_classes_eigen.inc, bgs_classes_imbs.inc, bgs_classes_multilayer.inc), before every frame
   int fg_channels_;  // 3: the class hands its caller an 8UC3 mask with equal channels (bgs_classes_lb.inc)
+  virtual int bgChannels(int input_channels) const { return input_channels; }  // the classes whose background model is a gray image say 1
 
  private:
-  virtual void saveConfig() = 0;  // private pure virtuals of IBGS, re-declared so process() above may call them
-  virtual void loadConfig() = 0;
+  virtual void saveConfig() { saveDescribed(configPath()); }  // both come from the class's describe() (bgs_describe.inc)
+  virtual void loadConfig() { loadDescribed(configPath()); }
   void fail() { CV_Error(CV_StsError, std::string(name_) + ": " + bgs_last_error()); }  // -> cv::Exception, caught at Main.cpp:63-72
   bgs_algo algo_;
   const char* name_;
@@ -150,10 +157,6 @@ class HipBGSBase : public IBGS {
 
 #define BGS_HIP_BANNER_DTOR(Class) \
   ~Class() { std::cout << "~" #Class "()" << std::endl; }
-#ifndef override
-#define BGS_HIP_DEFINED_OVERRIDE
-#define override  /* the reference builds as C++03 */
-#endif
 #include "bgs_classes.inc"
 #include "bgs_classes_kde.inc"
 #include "bgs_classes_dp2.inc"

@@ -8,10 +8,8 @@
 // for the types on the hot path (0-13 except the three dp classes outside it, 35-37).  GetBlobs() is the addition: the foreground
 // regions of the last mask as CvBlob {x, y, w, h, ID}, found on the device copy of the mask, so a blob-detection module can seed
 // from rectangles instead of re-scanning the mask on the CPU (CvBlobDetector::DetectNewBlob receives the mask at :166).
-// Type 15: hipbgs::DPEigenbackgroundBGS exists (HipBGS.h) but is not in the type table here, as in ustc_bgs.h (see there).
-// Type 33: hipbgs::IndependentMultimodalBGS likewise.
-// Type 23: hipbgs::MultiLayerBGS likewise.
-// Type 34: hipbgs::SJN_MultiCueBGS likewise.
+// Types 15, 23, 33 and 34 have a class in HipBGS.h (DPEigenbackgroundBGS, MultiLayerBGS, IndependentMultimodalBGS, SJN_MultiCueBGS)
+// and are not offered by number, as in ustc_bgs.h (see there).
 //
 // Needs OpenCV 2.4 with the legacy module (opencv2/legacy/blobtrack.hpp), which this repository's build image does not have:
 // checked for syntax against the declaration-only mock under tests/mock_opencv (tests/test_capi_cpu.py), as gnu++0x like the
@@ -40,38 +38,38 @@ class HipFGDetector : public CvFGDetector {
   explicit HipFGDetector(int type) : frameNum(0), c_mask(0), bgs(0), nextBlobID(0) {  // ustc_bgs.cpp:3-69
     const int i = type;
     CV_Assert(i >= 0 && i <= 37);
-    if (i == 0) bgs = new hipbgs::FrameDifferenceBGS;
-    if (i == 1) bgs = new hipbgs::StaticFrameDifferenceBGS;
-    if (i == 2) bgs = new hipbgs::WeightedMovingMeanBGS;
-    if (i == 3) bgs = new hipbgs::WeightedMovingVarianceBGS;
-    if (i == 4) bgs = new hipbgs::MixtureOfGaussianV1BGS;
-    if (i == 5) bgs = new hipbgs::MixtureOfGaussianV2BGS;
-    if (i == 6) bgs = new hipbgs::AdaptiveBackgroundLearning;
-    if (i == 7) bgs = new hipbgs::AdaptiveSelectiveBackgroundLearning;
-    if (i == 8) bgs = new hipbgs::GMG;
-    if (i == 9) bgs = new hipbgs::DPAdaptiveMedianBGS;
-    if (i == 10) bgs = new hipbgs::DPGrimsonGMMBGS;
-    if (i == 11) bgs = new hipbgs::DPZivkovicAGMMBGS;
-    if (i == 12) bgs = new hipbgs::DPMeanBGS;
-    if (i == 13) bgs = new hipbgs::DPWrenGABGS;
-    if (i == 14) bgs = new hipbgs::DPPratiMediodBGS;
-    if (i == 16) bgs = new hipbgs::DPTextureBGS;
-    if (i == 21) bgs = new hipbgs::FuzzySugenoIntegral;
-    if (i == 22) bgs = new hipbgs::FuzzyChoquetIntegral;
-    if (i == 25) bgs = new hipbgs::LBSimpleGaussian;
-    if (i == 26) bgs = new hipbgs::LBFuzzyGaussian;
-    if (i == 27) bgs = new hipbgs::LBMixtureOfGaussians;
-    if (i == 28) bgs = new hipbgs::LBAdaptiveSOM;
-    if (i == 29) bgs = new hipbgs::LBFuzzyAdaptiveSOM;
-    if (i == 31) bgs = new hipbgs::VuMeter;
-    if (i == 32) bgs = new hipbgs::KDE;
-    if (i == 35) bgs = new hipbgs::SigmaDeltaBGS;
-    if (i == 36) bgs = new hipbgs::SuBSENSEBGS();
-    if (i == 37) bgs = new hipbgs::LOBSTERBGS();
-    switch (i) {  // tb/'s type-2 fuzzy GMMs
+    switch (i) {
+      case 0: bgs = new hipbgs::FrameDifferenceBGS; break;
+      case 1: bgs = new hipbgs::StaticFrameDifferenceBGS; break;
+      case 2: bgs = new hipbgs::WeightedMovingMeanBGS; break;
+      case 3: bgs = new hipbgs::WeightedMovingVarianceBGS; break;
+      case 4: bgs = new hipbgs::MixtureOfGaussianV1BGS; break;
+      case 5: bgs = new hipbgs::MixtureOfGaussianV2BGS; break;
+      case 6: bgs = new hipbgs::AdaptiveBackgroundLearning; break;
+      case 7: bgs = new hipbgs::AdaptiveSelectiveBackgroundLearning; break;
+      case 8: bgs = new hipbgs::GMG; break;
+      case 9: bgs = new hipbgs::DPAdaptiveMedianBGS; break;
+      case 10: bgs = new hipbgs::DPGrimsonGMMBGS; break;
+      case 11: bgs = new hipbgs::DPZivkovicAGMMBGS; break;
+      case 12: bgs = new hipbgs::DPMeanBGS; break;
+      case 13: bgs = new hipbgs::DPWrenGABGS; break;
+      case 14: bgs = new hipbgs::DPPratiMediodBGS; break;
+      case 16: bgs = new hipbgs::DPTextureBGS; break;
       case 17: bgs = new hipbgs::T2FGMM_UM; break;
       case 18: bgs = new hipbgs::T2FGMM_UV; break;
-      default: break;
+      case 21: bgs = new hipbgs::FuzzySugenoIntegral; break;
+      case 22: bgs = new hipbgs::FuzzyChoquetIntegral; break;
+      case 25: bgs = new hipbgs::LBSimpleGaussian; break;
+      case 26: bgs = new hipbgs::LBFuzzyGaussian; break;
+      case 27: bgs = new hipbgs::LBMixtureOfGaussians; break;
+      case 28: bgs = new hipbgs::LBAdaptiveSOM; break;
+      case 29: bgs = new hipbgs::LBFuzzyAdaptiveSOM; break;
+      case 31: bgs = new hipbgs::VuMeter; break;
+      case 32: bgs = new hipbgs::KDE; break;
+      case 35: bgs = new hipbgs::SigmaDeltaBGS; break;
+      case 36: bgs = new hipbgs::SuBSENSEBGS; break;
+      case 37: bgs = new hipbgs::LOBSTERBGS; break;
+      default: break;  // 15, 19, 20, 23, 24, 30, 33, 34: refused below
     }
     if (!bgs) CV_Error(CV_StsBadArg, "HipFGDetector: this type is outside the package_bgs hot path libbgs_hip covers");
   }

@@ -1,385 +1,280 @@
-// bgs_classes.inc — the IBGS classes of the hot path, one per reference class: algorithm id, ./config/<Class>.xml keys and
-// defaults (reference file:line beside each).  Written against four names only - HipBGSBase, XmlConfig, params_, firstTime -
-// so the same list serves tracking_amd/host/bgs_host.h (bgs_hip::Image, own XML reader: compiled and tested in this
-// repository) and tracking_amd/host/HipBGS.h (cv::Mat + CvFileStorage: what a maintainer adds to the reference tree).
-// Include inside a namespace, after HipBGSBase / XmlConfig / BGS_HIP_BANNER_DTOR are defined.
+// bgs_classes.inc — the IBGS classes of the hot path, one per reference class: algorithm id and one description of its
+// ./config/<Class>.xml (keys in the reference's order, each with its member and default; reference file:line beside it).
+// HipBGSBase makes loadConfig() and saveConfig() of that description (bgs_describe.inc).  Written against HipBGSBase, XmlIo, params_
+// and firstTime only, so the same list serves tracking_amd/host/bgs_host.h (bgs_hip::Image, own XML reader: compiled and tested in
+// this repository) and tracking_amd/host/HipBGS.h (cv::Mat + CvFileStorage: what a maintainer adds to the reference tree, C++03).
+// Include inside a namespace, after HipBGSBase / BGS_HIP_BANNER_DTOR are defined.  Every member a description names is set by the
+// loadConfig() that process() starts with, before anything reads it.
 
 // package_bgs/FrameDifferenceBGS.{h,cpp}
 class FrameDifferenceBGS : public HipBGSBase {
  public:
-  FrameDifferenceBGS() : HipBGSBase(BGS_FRAME_DIFF, "FrameDifferenceBGS"), showOutput(true) {}
+  FrameDifferenceBGS() : HipBGSBase(BGS_FRAME_DIFF, "FrameDifferenceBGS") {}
   BGS_HIP_BANNER_DTOR(FrameDifferenceBGS)
  private:
   bool showOutput;
-  void saveConfig() override {  // FrameDifferenceBGS.cpp:65-74
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeInt("enableThreshold", params_.enable_threshold);
-    fs.writeInt("threshold", params_.threshold);
-    fs.writeInt("showOutput", showOutput);
-    fs.save(configPath());
-  }
-  void loadConfig() override {  // :76-85
-    XmlConfig fs;
-    fs.load(configPath());
-    params_.enable_threshold = fs.readInt("enableThreshold", true);
-    params_.threshold = fs.readInt("threshold", 15);
-    showOutput = fs.readInt("showOutput", true);
+  void describe(XmlIo& io) override {  // FrameDifferenceBGS.cpp:65-85
+    io("enableThreshold", params_.enable_threshold, true);
+    io("threshold", params_.threshold, 15);
+    io("showOutput", showOutput, true);
   }
 };
 
 // package_bgs/StaticFrameDifferenceBGS.{h,cpp}
 class StaticFrameDifferenceBGS : public HipBGSBase {
  public:
-  StaticFrameDifferenceBGS() : HipBGSBase(BGS_STATIC_FRAME_DIFF, "StaticFrameDifferenceBGS"), showOutput(true) {}
+  StaticFrameDifferenceBGS() : HipBGSBase(BGS_STATIC_FRAME_DIFF, "StaticFrameDifferenceBGS") {}
   BGS_HIP_BANNER_DTOR(StaticFrameDifferenceBGS)
  private:
   bool showOutput;
-  void saveConfig() override {
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeInt("enableThreshold", params_.enable_threshold);
-    fs.writeInt("threshold", params_.threshold);
-    fs.writeInt("showOutput", showOutput);
-    fs.save(configPath());
-  }
-  void loadConfig() override {
-    XmlConfig fs;
-    fs.load(configPath());
-    params_.enable_threshold = fs.readInt("enableThreshold", true);
-    params_.threshold = fs.readInt("threshold", 15);
-    showOutput = fs.readInt("showOutput", true);
+  void describe(XmlIo& io) override {
+    io("enableThreshold", params_.enable_threshold, true);
+    io("threshold", params_.threshold, 15);
+    io("showOutput", showOutput, true);
   }
 };
 
 // package_bgs/WeightedMovingMeanBGS.{h,cpp}
 class WeightedMovingMeanBGS : public HipBGSBase {
  public:
-  WeightedMovingMeanBGS() : HipBGSBase(BGS_WMM, "WeightedMovingMeanBGS"), showOutput(true), showBackground(false) {}
+  WeightedMovingMeanBGS() : HipBGSBase(BGS_WMM, "WeightedMovingMeanBGS") {}
   BGS_HIP_BANNER_DTOR(WeightedMovingMeanBGS)
  private:
   bool showOutput, showBackground;
-  void saveConfig() override {  // WeightedMovingMeanBGS.cpp:98-109
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeInt("enableWeight", params_.enable_weight);
-    fs.writeInt("enableThreshold", params_.enable_threshold);
-    fs.writeInt("threshold", params_.threshold);
-    fs.writeInt("showOutput", showOutput);
-    fs.writeInt("showBackground", showBackground);
-    fs.save(configPath());
-  }
-  void loadConfig() override {  // :111-122
-    XmlConfig fs;
-    fs.load(configPath());
-    params_.enable_weight = fs.readInt("enableWeight", true);
-    params_.enable_threshold = fs.readInt("enableThreshold", true);
-    params_.threshold = fs.readInt("threshold", 15);
-    showOutput = fs.readInt("showOutput", true);
-    showBackground = fs.readInt("showBackground", false);
+  void describe(XmlIo& io) override {  // WeightedMovingMeanBGS.cpp:98-122
+    io("enableWeight", params_.enable_weight, true);
+    io("enableThreshold", params_.enable_threshold, true);
+    io("threshold", params_.threshold, 15);
+    io("showOutput", showOutput, true);
+    io("showBackground", showBackground, false);
   }
 };
 
 // package_bgs/WeightedMovingVarianceBGS.{h,cpp}
 class WeightedMovingVarianceBGS : public HipBGSBase {
  public:
-  WeightedMovingVarianceBGS() : HipBGSBase(BGS_WMV, "WeightedMovingVarianceBGS"), showOutput(true) {}
+  WeightedMovingVarianceBGS() : HipBGSBase(BGS_WMV, "WeightedMovingVarianceBGS") {}
   BGS_HIP_BANNER_DTOR(WeightedMovingVarianceBGS)
  private:
   bool showOutput;
-  void saveConfig() override {  // WeightedMovingVarianceBGS.cpp:139-149
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeInt("enableWeight", params_.enable_weight);
-    fs.writeInt("enableThreshold", params_.enable_threshold);
-    fs.writeInt("threshold", params_.threshold);
-    fs.writeInt("showOutput", showOutput);
-    fs.save(configPath());
-  }
-  void loadConfig() override {  // :151-161
-    XmlConfig fs;
-    fs.load(configPath());
-    params_.enable_weight = fs.readInt("enableWeight", true);
-    params_.enable_threshold = fs.readInt("enableThreshold", true);
-    params_.threshold = fs.readInt("threshold", 15);
-    showOutput = fs.readInt("showOutput", true);
+  void describe(XmlIo& io) override {  // WeightedMovingVarianceBGS.cpp:139-161
+    io("enableWeight", params_.enable_weight, true);
+    io("enableThreshold", params_.enable_threshold, true);
+    io("threshold", params_.threshold, 15);
+    io("showOutput", showOutput, true);
   }
 };
 
 // package_bgs/AdaptiveBackgroundLearning.{h,cpp}
 class AdaptiveBackgroundLearning : public HipBGSBase {
  public:
-  AdaptiveBackgroundLearning() : HipBGSBase(BGS_ABL, "AdaptiveBackgroundLearning"), showForeground(true), showBackground(true) {}
+  AdaptiveBackgroundLearning() : HipBGSBase(BGS_ABL, "AdaptiveBackgroundLearning") {}
   BGS_HIP_BANNER_DTOR(AdaptiveBackgroundLearning)
  private:
   bool showForeground, showBackground;
-  void saveConfig() override {  // AdaptiveBackgroundLearning.cpp:85-97
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeReal("alpha", params_.alpha);
-    fs.writeInt("limit", params_.limit);
-    fs.writeInt("enableThreshold", params_.enable_threshold);
-    fs.writeInt("threshold", params_.threshold);
-    fs.writeInt("showForeground", showForeground);
-    fs.writeInt("showBackground", showBackground);
-    fs.save(configPath());
-  }
-  void loadConfig() override {  // :99-111
-    XmlConfig fs;
-    fs.load(configPath());
-    params_.alpha = fs.readReal("alpha", 0.05);
-    params_.limit = fs.readInt("limit", -1);
-    params_.enable_threshold = fs.readInt("enableThreshold", true);
-    params_.threshold = fs.readInt("threshold", 15);
-    showForeground = fs.readInt("showForeground", true);
-    showBackground = fs.readInt("showBackground", true);
+  void describe(XmlIo& io) override {  // AdaptiveBackgroundLearning.cpp:85-111
+    io("alpha", params_.alpha, 0.05);
+    io("limit", params_.limit, -1);
+    io("enableThreshold", params_.enable_threshold, true);
+    io("threshold", params_.threshold, 15);
+    io("showForeground", showForeground, true);
+    io("showBackground", showBackground, true);
   }
 };
 
-// package_bgs/AdaptiveSelectiveBackgroundLearning.{h,cpp}
+// package_bgs/AdaptiveSelectiveBackgroundLearning.{h,cpp}: the background model is the gray image the class keeps
 class AdaptiveSelectiveBackgroundLearning : public HipBGSBase {
  public:
-  AdaptiveSelectiveBackgroundLearning() : HipBGSBase(BGS_ASBL, "AdaptiveSelectiveBackgroundLearning"), showOutput(true) {}
+  AdaptiveSelectiveBackgroundLearning() : HipBGSBase(BGS_ASBL, "AdaptiveSelectiveBackgroundLearning") {}
   BGS_HIP_BANNER_DTOR(AdaptiveSelectiveBackgroundLearning)
  private:
   bool showOutput;
-  void saveConfig() override {  // AdaptiveSelectiveBackgroundLearning.cpp:107-118
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeInt("learningFrames", params_.learning_frames);
-    fs.writeReal("alphaLearn", params_.alpha_learn);
-    fs.writeReal("alphaDetection", params_.alpha_detection);
-    fs.writeInt("threshold", params_.threshold);
-    fs.writeInt("showOutput", showOutput);
-    fs.save(configPath());
-  }
-  void loadConfig() override {  // :120-131 (defaults 90 / 25 differ from the ctor's -1 / 15, SURVEY.md App. C 5)
-    XmlConfig fs;
-    fs.load(configPath());
-    params_.learning_frames = fs.readInt("learningFrames", 90);
-    params_.alpha_learn = fs.readReal("alphaLearn", 0.05);
-    params_.alpha_detection = fs.readReal("alphaDetection", 0.05);
-    params_.threshold = fs.readInt("threshold", 25);
-    showOutput = fs.readInt("showOutput", true);
+  int bgChannels(int) const override { return 1; }
+  void describe(XmlIo& io) override {  // AdaptiveSelectiveBackgroundLearning.cpp:107-131 (defaults 90 / 25 differ from the ctor's -1 / 15, SURVEY.md App. C 5)
+    io("learningFrames", params_.learning_frames, 90);
+    io("alphaLearn", params_.alpha_learn, 0.05);
+    io("alphaDetection", params_.alpha_detection, 0.05);
+    io("threshold", params_.threshold, 25);
+    io("showOutput", showOutput, true);
   }
 };
 
 // package_bgs/MixtureOfGaussianV2BGS.{h,cpp}
 class MixtureOfGaussianV2BGS : public HipBGSBase {
  public:
-  MixtureOfGaussianV2BGS() : HipBGSBase(BGS_MOG2, "MixtureOfGaussianV2BGS"), showOutput(true) {}
+  MixtureOfGaussianV2BGS() : HipBGSBase(BGS_MOG2, "MixtureOfGaussianV2BGS") {}
   BGS_HIP_BANNER_DTOR(MixtureOfGaussianV2BGS)
  private:
   bool showOutput;
-  void saveConfig() override {  // MixtureOfGaussianV2BGS.cpp:76-86
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeReal("alpha", params_.alpha);
-    fs.writeInt("enableThreshold", params_.enable_threshold);
-    fs.writeInt("threshold", params_.threshold);
-    fs.writeInt("showOutput", showOutput);
-    fs.save(configPath());
-  }
-  void loadConfig() override {  // :88-98
-    XmlConfig fs;
-    fs.load(configPath());
-    params_.alpha = fs.readReal("alpha", 0.05);
-    params_.enable_threshold = fs.readInt("enableThreshold", true);
-    params_.threshold = fs.readInt("threshold", 15);
-    showOutput = fs.readInt("showOutput", true);
+  void describe(XmlIo& io) override {  // MixtureOfGaussianV2BGS.cpp:76-98
+    io("alpha", params_.alpha, 0.05);
+    io("enableThreshold", params_.enable_threshold, true);
+    io("threshold", params_.threshold, 15);
+    io("showOutput", showOutput, true);
   }
 };
 
 // package_bgs/MixtureOfGaussianV1BGS.{h,cpp}
 class MixtureOfGaussianV1BGS : public HipBGSBase {
  public:
-  MixtureOfGaussianV1BGS() : HipBGSBase(BGS_MOG1, "MixtureOfGaussianV1BGS", /*clears_bg=*/true), showOutput(true) {}
+  MixtureOfGaussianV1BGS() : HipBGSBase(BGS_MOG1, "MixtureOfGaussianV1BGS", /*clears_bg=*/true) {}
   BGS_HIP_BANNER_DTOR(MixtureOfGaussianV1BGS)
  private:
   bool showOutput;
-  void saveConfig() override {  // MixtureOfGaussianV1BGS.cpp:73-83
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeReal("alpha", params_.alpha);
-    fs.writeInt("enableThreshold", params_.enable_threshold);
-    fs.writeInt("threshold", params_.threshold);
-    fs.writeInt("showOutput", showOutput);
-    fs.save(configPath());
-  }
-  void loadConfig() override {  // :85-95
-    XmlConfig fs;
-    fs.load(configPath());
-    params_.alpha = fs.readReal("alpha", 0.05);
-    params_.enable_threshold = fs.readInt("enableThreshold", true);
-    params_.threshold = fs.readInt("threshold", 15);
-    showOutput = fs.readInt("showOutput", true);
+  void describe(XmlIo& io) override {  // MixtureOfGaussianV1BGS.cpp:73-95
+    io("alpha", params_.alpha, 0.05);
+    io("enableThreshold", params_.enable_threshold, true);
+    io("threshold", params_.threshold, 15);
+    io("showOutput", showOutput, true);
   }
 };
 
 // package_bgs/GMG.{h,cpp}
 class GMG : public HipBGSBase {
  public:
-  GMG() : HipBGSBase(BGS_GMG, "GMG", /*clears_bg=*/true), showOutput(true) {}
+  GMG() : HipBGSBase(BGS_GMG, "GMG", /*clears_bg=*/true) {}
   BGS_HIP_BANNER_DTOR(GMG)
  private:
   bool showOutput;
-  void saveConfig() override {  // GMG.cpp:79-88
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeInt("initializationFrames", params_.gmg_init_frames);
-    fs.writeReal("decisionThreshold", params_.gmg_decision_threshold);
-    fs.writeInt("showOutput", showOutput);
-    fs.save(configPath());
-  }
-  void loadConfig() override {  // :90-99
-    XmlConfig fs;
-    fs.load(configPath());
-    params_.gmg_init_frames = fs.readInt("initializationFrames", 20);
-    params_.gmg_decision_threshold = fs.readReal("decisionThreshold", 0.7);
-    showOutput = fs.readInt("showOutput", true);
+  void describe(XmlIo& io) override {  // GMG.cpp:79-99
+    io("initializationFrames", params_.gmg_init_frames, 20);
+    io("decisionThreshold", params_.gmg_decision_threshold, 0.7);
+    io("showOutput", showOutput, true);
   }
 };
 
 // package_bgs/bl/SigmaDeltaBGS.{h,cpp}
 class SigmaDeltaBGS : public HipBGSBase {
  public:
-  SigmaDeltaBGS() : HipBGSBase(BGS_SIGMA_DELTA, "SigmaDeltaBGS"), showOutput(true) {}
+  SigmaDeltaBGS() : HipBGSBase(BGS_SIGMA_DELTA, "SigmaDeltaBGS") {}
   BGS_HIP_BANNER_DTOR(SigmaDeltaBGS)
  private:
   bool showOutput;
-  void saveConfig() override {  // SigmaDeltaBGS.cpp:57-66
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeInt("ampFactor", params_.sd_amp_factor);
-    fs.writeInt("minVar", params_.sd_min_var);
-    fs.writeInt("maxVar", params_.sd_max_var);
-    fs.writeInt("showOutput", showOutput);
-    fs.save(configPath());
-  }
-  void loadConfig() override {  // :68-79
-    XmlConfig fs;
-    fs.load(configPath());
-    params_.sd_amp_factor = fs.readInt("ampFactor", 1);
-    params_.sd_min_var = fs.readInt("minVar", 15);
-    params_.sd_max_var = fs.readInt("maxVar", 255);
-    showOutput = fs.readInt("showOutput", true);
+  void describe(XmlIo& io) override {  // SigmaDeltaBGS.cpp:57-79
+    io("ampFactor", params_.sd_amp_factor, 1);
+    io("minVar", params_.sd_min_var, 15);
+    io("maxVar", params_.sd_max_var, 255);
+    io("showOutput", showOutput, true);
   }
 };
 
 // package_bgs/pl/SuBSENSE.{h,cpp} (the class USTC_BGS type 36 instantiates, ustc_src/ustc_bgs.cpp:68)
 class SuBSENSEBGS : public HipBGSBase {
  public:
-  SuBSENSEBGS() : HipBGSBase(BGS_SUBSENSE, "SuBSENSEBGS"), showOutput(true) {}
+  SuBSENSEBGS() : HipBGSBase(BGS_SUBSENSE, "SuBSENSEBGS") {}
   ~SuBSENSEBGS() override {}
  private:
   bool showOutput;
-  void saveConfig() override {  // SuBSENSE.cpp:47-60
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeReal("fRelLBSPThreshold", params_.lbsp_rel_threshold);
-    fs.writeInt("nDescDistThresholdOffset", params_.subsense_desc_dist_threshold_offset);
-    fs.writeInt("nMinColorDistThreshold", params_.subsense_min_color_dist_threshold);
-    fs.writeInt("nBGSamples", params_.subsense_n_samples);
-    fs.writeInt("nRequiredBGSamples", params_.subsense_n_required);
-    fs.writeInt("nSamplesForMovingAvgs", params_.subsense_samples_for_moving_avgs);
-    fs.writeInt("showOutput", showOutput);
-    fs.save(configPath());
-  }
-  void loadConfig() override {  // SuBSENSE.cpp:62-75 (read every frame; the model itself is built once, on the first frame)
-    XmlConfig fs;
-    fs.load(configPath());
-    params_.lbsp_rel_threshold = (float)fs.readReal("fRelLBSPThreshold", 0.333f);
-    params_.subsense_desc_dist_threshold_offset = fs.readInt("nDescDistThresholdOffset", 3);
-    params_.subsense_min_color_dist_threshold = fs.readInt("nMinColorDistThreshold", 30);
-    params_.subsense_n_samples = fs.readInt("nBGSamples", 50);
-    params_.subsense_n_required = fs.readInt("nRequiredBGSamples", 2);
-    params_.subsense_samples_for_moving_avgs = fs.readInt("nSamplesForMovingAvgs", 100);
-    showOutput = fs.readInt("showOutput", true);
+  void describe(XmlIo& io) override {  // SuBSENSE.cpp:47-75 (read every frame; the model itself is built once, on the first frame)
+    io("fRelLBSPThreshold", params_.lbsp_rel_threshold, 0.333f);
+    io("nDescDistThresholdOffset", params_.subsense_desc_dist_threshold_offset, 3);
+    io("nMinColorDistThreshold", params_.subsense_min_color_dist_threshold, 30);
+    io("nBGSamples", params_.subsense_n_samples, 50);
+    io("nRequiredBGSamples", params_.subsense_n_required, 2);
+    io("nSamplesForMovingAvgs", params_.subsense_samples_for_moving_avgs, 100);
+    io("showOutput", showOutput, true);
   }
 };
 
 // package_bgs/pl/LOBSTER.{h,cpp}: like SuBSENSEBGS, the parameters are handed to the model once, when it is built on the first frame
 class LOBSTERBGS : public HipBGSBase {
  public:
-  LOBSTERBGS() : HipBGSBase(BGS_LOBSTER, "LOBSTERBGS"), showOutput(true) {}
+  LOBSTERBGS() : HipBGSBase(BGS_LOBSTER, "LOBSTERBGS") {}
   ~LOBSTERBGS() override {}
  private:
   bool showOutput;
-  void saveConfig() override {  // LOBSTER.cpp:47-58
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeReal("fRelLBSPThreshold", params_.lbsp_rel_threshold);
-    fs.writeInt("nLBSPThresholdOffset", params_.lbsp_threshold_offset);
-    fs.writeInt("nDescDistThreshold", params_.subsense_desc_dist_threshold_offset);
-    fs.writeInt("nColorDistThreshold", params_.subsense_min_color_dist_threshold);
-    fs.writeInt("nBGSamples", params_.subsense_n_samples);
-    fs.writeInt("nRequiredBGSamples", params_.subsense_n_required);
-    fs.writeInt("showOutput", showOutput);
-    fs.save(configPath());
-  }
-  void loadConfig() override {  // :60-73
-    XmlConfig fs;
-    fs.load(configPath());
-    params_.lbsp_rel_threshold = (float)fs.readReal("fRelLBSPThreshold", 0.365f);
-    params_.lbsp_threshold_offset = fs.readInt("nLBSPThresholdOffset", 0);
-    params_.subsense_desc_dist_threshold_offset = fs.readInt("nDescDistThreshold", 4);
-    params_.subsense_min_color_dist_threshold = fs.readInt("nColorDistThreshold", 30);
-    params_.subsense_n_samples = fs.readInt("nBGSamples", 35);
-    params_.subsense_n_required = fs.readInt("nRequiredBGSamples", 2);
-    showOutput = fs.readInt("showOutput", true);
+  void describe(XmlIo& io) override {  // LOBSTER.cpp:47-73
+    io("fRelLBSPThreshold", params_.lbsp_rel_threshold, 0.365f);
+    io("nLBSPThresholdOffset", params_.lbsp_threshold_offset, 0);
+    io("nDescDistThreshold", params_.subsense_desc_dist_threshold_offset, 4);
+    io("nColorDistThreshold", params_.subsense_min_color_dist_threshold, 30);
+    io("nBGSamples", params_.subsense_n_samples, 35);
+    io("nRequiredBGSamples", params_.subsense_n_required, 2);
+    io("showOutput", showOutput, true);
   }
 };
 
 // package_bgs/dp/DP*BGS.{h,cpp}: the wrapper reads its XML every frame but hands the values to the model only once, inside
 // `if(firstTime)` (e.g. DPZivkovicAGMMBGS.cpp:48-65) - later edits of the file change what saveConfig would write, not the
-// running model.  Mirrored: the values go into params_ only while firstTime is true.
-#define BGS_HIP_DP_CLASS(Class, ALGO, WRITE_BODY, READ_BODY)                  \
-  class Class : public HipBGSBase {                                           \
-   public:                                                                     \
-    Class() : HipBGSBase(ALGO, #Class), showOutput(true) {                    \
-      threshold = params_.dp_threshold, alpha = params_.dp_alpha, gaussians = params_.dp_gaussians; \
-      learningFrames = params_.learning_frames, samplingRate = params_.dp_sampling_rate; \
-    }                                                                          \
-    BGS_HIP_BANNER_DTOR(Class)                                                \
-   private:                                                                    \
-    double threshold, alpha;                                                   \
-    int gaussians, learningFrames, samplingRate;                               \
-    bool showOutput;                                                           \
-    void saveConfig() override {                                               \
-      XmlConfig fs;                                                            \
-      fs.beginWrite();                                                         \
-      WRITE_BODY fs.writeInt("showOutput", showOutput);                       \
-      fs.save(configPath());                                                   \
-    }                                                                          \
-    void loadConfig() override {                                               \
-      XmlConfig fs;                                                            \
-      fs.load(configPath());                                                   \
-      READ_BODY showOutput = fs.readInt("showOutput", true);                  \
-      if (firstTime) {                                                         \
-        params_.dp_threshold = (float)threshold, params_.dp_alpha = (float)alpha, params_.dp_gaussians = gaussians; \
-        params_.learning_frames = learningFrames, params_.dp_sampling_rate = samplingRate; \
-      }                                                                        \
-    }                                                                          \
-  };
+// running model.  Mirrored: the values go into params_ only while firstTime is true.  Each class describes the three keys its
+// wrapper has; the members it does not name keep the algorithm's own defaults.
+class DPBase : public HipBGSBase {
+ protected:
+  DPBase(bgs_algo algo, const char* name) : HipBGSBase(algo, name) {
+    threshold = params_.dp_threshold, alpha = params_.dp_alpha, gaussians = params_.dp_gaussians;
+    learningFrames = params_.learning_frames, samplingRate = params_.dp_sampling_rate;
+  }
+  double threshold, alpha;
+  int gaussians, learningFrames, samplingRate;
+  bool showOutput;
+  void loaded() override {
+    if (!firstTime) return;
+    params_.dp_threshold = (float)threshold, params_.dp_alpha = (float)alpha, params_.dp_gaussians = gaussians;
+    params_.learning_frames = learningFrames, params_.dp_sampling_rate = samplingRate;
+  }
+};
 
-// DPZivkovicAGMMBGS.cpp:82-104
-BGS_HIP_DP_CLASS(DPZivkovicAGMMBGS, BGS_DP_ZIVKOVIC_AGMM,
-                 fs.writeReal("threshold", threshold); fs.writeReal("alpha", alpha); fs.writeInt("gaussians", gaussians);,
-                 threshold = fs.readReal("threshold", 25.0f); alpha = fs.readReal("alpha", 0.001f); gaussians = fs.readInt("gaussians", 3);)
-// DPGrimsonGMMBGS.cpp:84-105
-BGS_HIP_DP_CLASS(DPGrimsonGMMBGS, BGS_DP_GRIMSON_GMM,
-                 fs.writeReal("threshold", threshold); fs.writeReal("alpha", alpha); fs.writeInt("gaussians", gaussians);,
-                 threshold = fs.readReal("threshold", 9.0); alpha = fs.readReal("alpha", 0.01); gaussians = fs.readInt("gaussians", 3);)
-// DPWrenGABGS.cpp:83-104
-BGS_HIP_DP_CLASS(DPWrenGABGS, BGS_DP_WREN_GA,
-                 fs.writeReal("threshold", threshold); fs.writeReal("alpha", alpha); fs.writeInt("learningFrames", learningFrames);,
-                 threshold = fs.readReal("threshold", 12.25f); alpha = fs.readReal("alpha", 0.005f); learningFrames = fs.readInt("learningFrames", 30);)
-// DPMeanBGS.cpp:84-105 (threshold is an int there)
-BGS_HIP_DP_CLASS(DPMeanBGS, BGS_DP_MEAN,
-                 fs.writeInt("threshold", (int)threshold); fs.writeReal("alpha", alpha); fs.writeInt("learningFrames", learningFrames);,
-                 threshold = fs.readInt("threshold", 2700); alpha = fs.readReal("alpha", 1e-6f); learningFrames = fs.readInt("learningFrames", 30);)
-// DPAdaptiveMedianBGS.cpp:83-104
-BGS_HIP_DP_CLASS(DPAdaptiveMedianBGS, BGS_DP_ADAPTIVE_MEDIAN,
-                 fs.writeInt("threshold", (int)threshold); fs.writeInt("samplingRate", samplingRate); fs.writeInt("learningFrames", learningFrames);,
-                 threshold = fs.readInt("threshold", 40); samplingRate = fs.readInt("samplingRate", 7); learningFrames = fs.readInt("learningFrames", 30);)
-#undef BGS_HIP_DP_CLASS
+class DPZivkovicAGMMBGS : public DPBase {
+ public:
+  DPZivkovicAGMMBGS() : DPBase(BGS_DP_ZIVKOVIC_AGMM, "DPZivkovicAGMMBGS") {}
+  BGS_HIP_BANNER_DTOR(DPZivkovicAGMMBGS)
+ private:
+  void describe(XmlIo& io) override {  // DPZivkovicAGMMBGS.cpp:82-104
+    io("threshold", threshold, 25.0f);
+    io("alpha", alpha, 0.001f);
+    io("gaussians", gaussians, 3);
+    io("showOutput", showOutput, true);
+  }
+};
+
+class DPGrimsonGMMBGS : public DPBase {
+ public:
+  DPGrimsonGMMBGS() : DPBase(BGS_DP_GRIMSON_GMM, "DPGrimsonGMMBGS") {}
+  BGS_HIP_BANNER_DTOR(DPGrimsonGMMBGS)
+ private:
+  void describe(XmlIo& io) override {  // DPGrimsonGMMBGS.cpp:84-105
+    io("threshold", threshold, 9.0);
+    io("alpha", alpha, 0.01);
+    io("gaussians", gaussians, 3);
+    io("showOutput", showOutput, true);
+  }
+};
+
+class DPWrenGABGS : public DPBase {
+ public:
+  DPWrenGABGS() : DPBase(BGS_DP_WREN_GA, "DPWrenGABGS") {}
+  BGS_HIP_BANNER_DTOR(DPWrenGABGS)
+ private:
+  void describe(XmlIo& io) override {  // DPWrenGABGS.cpp:83-104
+    io("threshold", threshold, 12.25f);
+    io("alpha", alpha, 0.005f);
+    io("learningFrames", learningFrames, 30);
+    io("showOutput", showOutput, true);
+  }
+};
+
+class DPMeanBGS : public DPBase {
+ public:
+  DPMeanBGS() : DPBase(BGS_DP_MEAN, "DPMeanBGS") {}
+  BGS_HIP_BANNER_DTOR(DPMeanBGS)
+ private:
+  void describe(XmlIo& io) override {  // DPMeanBGS.cpp:84-105 (threshold is an int there)
+    io.asInt("threshold", threshold, 2700);
+    io("alpha", alpha, 1e-6f);
+    io("learningFrames", learningFrames, 30);
+    io("showOutput", showOutput, true);
+  }
+};
+
+class DPAdaptiveMedianBGS : public DPBase {
+ public:
+  DPAdaptiveMedianBGS() : DPBase(BGS_DP_ADAPTIVE_MEDIAN, "DPAdaptiveMedianBGS") {}
+  BGS_HIP_BANNER_DTOR(DPAdaptiveMedianBGS)
+ private:
+  void describe(XmlIo& io) override {  // DPAdaptiveMedianBGS.cpp:83-104
+    io.asInt("threshold", threshold, 40);
+    io("samplingRate", samplingRate, 7);
+    io("learningFrames", learningFrames, 30);
+    io("showOutput", showOutput, true);
+  }
+};

@@ -1,6 +1,4 @@
-// bgs_classes_eigen.inc — the IBGS class of package_bgs/dp's Eigenbackground, written against the same names as bgs_classes.inc and
-// included after bgs_classes_t2f.inc by tracking_amd/host/bgs_host.h and tracking_amd/host/HipBGS.h.  A file of its own: the tests
-// pin the class lists of the other .inc files as they stand.
+// bgs_classes_eigen.inc — the IBGS class of package_bgs/dp's Eigenbackground, in the form bgs_classes.inc describes.
 
 // package_bgs/dp/DPEigenbackgroundBGS.{h,cpp} (USTC_BGS type 15).  loadConfig runs every frame into the wrapper's int members, but the
 // values reach the params object once, `if(firstTime)`: they travel in bgs_eigen_params, which the engine takes when its model is
@@ -8,7 +6,7 @@
 // first historySize frames; img_bgmodel is never written.
 class DPEigenbackgroundBGS : public HipBGSBase {
  public:
-  DPEigenbackgroundBGS() : HipBGSBase(BGS_DP_EIGENBACKGROUND, "DPEigenbackgroundBGS"), threshold(225), historySize(20), embeddedDim(10), showOutput(true) {}
+  DPEigenbackgroundBGS() : HipBGSBase(BGS_DP_EIGENBACKGROUND, "DPEigenbackgroundBGS") {}
   BGS_HIP_BANNER_DTOR(DPEigenbackgroundBGS)
 
  protected:
@@ -22,21 +20,10 @@ class DPEigenbackgroundBGS : public HipBGSBase {
   }
 
  private:
-  void saveConfig() override {  // DPEigenbackgroundBGS.cpp:84-94
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeInt("threshold", threshold);
-    fs.writeInt("historySize", historySize);
-    fs.writeInt("embeddedDim", embeddedDim);
-    fs.writeInt("showOutput", showOutput);
-    fs.save(configPath());
-  }
-  void loadConfig() override {  // :96-106
-    XmlConfig fs;
-    fs.load(configPath());
-    threshold = fs.readInt("threshold", 225);
-    historySize = fs.readInt("historySize", 20);
-    embeddedDim = fs.readInt("embeddedDim", 10);
-    showOutput = fs.readInt("showOutput", true);
+  void describe(XmlIo& io) override {  // DPEigenbackgroundBGS.cpp:84-106
+    io("threshold", threshold, 225);
+    io("historySize", historySize, 20);
+    io("embeddedDim", embeddedDim, 10);
+    io("showOutput", showOutput, true);
   }
 };

@@ -1,6 +1,4 @@
-// bgs_classes_imbs.inc — the IBGS class of package_bgs/db's IMBS, written against the same names as bgs_classes.inc and included
-// after bgs_classes_eigen.inc by tracking_amd/host/bgs_host.h and tracking_amd/host/HipBGS.h.  A file of its own: the tests pin the
-// class lists of the other .inc files as they stand.
+// bgs_classes_imbs.inc — the IBGS class of package_bgs/db's IMBS, in the form bgs_classes.inc describes.
 
 // package_bgs/db/IndependentMultimodalBGS.{h,cpp} (USTC_BGS type 33).  The wrapper constructs BackgroundSubtractorIMBS(fps) with
 // fps 10 and every other argument at the full constructor's default; its XML holds showOutput only.  8UC1 mask with the four labels
@@ -8,7 +6,7 @@
 // shows a putText banner there).
 class IndependentMultimodalBGS : public HipBGSBase {
  public:
-  IndependentMultimodalBGS() : HipBGSBase(BGS_IMBS, "IndependentMultimodalBGS"), fps(10), showOutput(true) {}
+  IndependentMultimodalBGS() : HipBGSBase(BGS_IMBS, "IndependentMultimodalBGS"), fps(10) {}
   BGS_HIP_BANNER_DTOR(IndependentMultimodalBGS)
 
  protected:
@@ -22,15 +20,5 @@ class IndependentMultimodalBGS : public HipBGSBase {
   }
 
  private:
-  void saveConfig() override {  // IndependentMultimodalBGS.cpp:38-45
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeInt("showOutput", showOutput);
-    fs.save(configPath());
-  }
-  void loadConfig() override {  // :47-54
-    XmlConfig fs;
-    fs.load(configPath());
-    showOutput = fs.readInt("showOutput", true);
-  }
+  void describe(XmlIo& io) override { io("showOutput", showOutput, true); }  // IndependentMultimodalBGS.cpp:38-54
 };

@@ -1,15 +1,14 @@
-// bgs_classes_multicue.inc — the IBGS class of package_bgs/sjn's SJN_MultiCueBGS, included after bgs_classes_multilayer.inc by
-// tracking_amd/host/bgs_host.h and tracking_amd/host/HipBGS.h.  A file of its own: the tests pin the class lists of the other .inc files
-// as they stand.  Unlike the classes of those files this one has no bgs_algo and no bgs_engine: it holds a one-stream bgs_multicue
-// (include/bgs_hip.h), so it derives from IBGS itself.  The including header names its image type, the 8UC3 type code of that image's
+// bgs_classes_multicue.inc — the IBGS class of package_bgs/sjn's SJN_MultiCueBGS.  Unlike the classes of the other files this one has no
+// bgs_algo and no bgs_engine: it holds a one-stream bgs_multicue (include/bgs_hip.h), so it derives from IBGS itself and shares only
+// the description of its XML (bgs_describe.inc).  The including header names its image type, the 8UC3 type code of that image's
 // create() and its one way to fail: BGS_HIP_MAT, BGS_HIP_8UC3, BGS_HIP_FAIL(code, what).
 
 // package_bgs/sjn/SJN_MultiCueBGS.{h,cpp} (USTC_BGS type 34).  The parameters are the constructor's (SJN_MultiCueBGS.cpp:30-48) and no XML
 // key changes them; ./config/MultiCueBGS.xml holds showOutput only.  8UC3 mask with three equal channels, zero while the model trains
 // (frames 0 .. 20); img_bgmodel is left untouched, as the reference leaves it.  The reference prints no constructor or destructor banner.
-class SJN_MultiCueBGS : public IBGS {
+class SJN_MultiCueBGS : public IBGS, protected XmlDescribed {
  public:
-  SJN_MultiCueBGS() : firstTime(true), showOutput(true), device_(0), model_(0) {}
+  SJN_MultiCueBGS() : firstTime(true), device_(0), model_(0) {}
   ~SJN_MultiCueBGS() {
     if (model_) bgs_multicue_destroy(model_);
   }
@@ -36,17 +35,9 @@ class SJN_MultiCueBGS : public IBGS {
   bool firstTime, showOutput;
   int device_;
   bgs_multicue* model_;
-  void saveConfig() {  // :115-122
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeInt("showOutput", showOutput);
-    fs.save("./config/MultiCueBGS.xml");
-  }
-  void loadConfig() {  // :124-131
-    XmlConfig fs;
-    fs.load("./config/MultiCueBGS.xml");
-    showOutput = fs.readInt("showOutput", true);
-  }
+  void describe(XmlIo& io) override { io("showOutput", showOutput, true); }  // :115-131
+  void saveConfig() { saveDescribed("./config/MultiCueBGS.xml"); }
+  void loadConfig() { loadDescribed("./config/MultiCueBGS.xml"); }
   SJN_MultiCueBGS(const SJN_MultiCueBGS&);  // owns the handle: not copied
   SJN_MultiCueBGS& operator=(const SJN_MultiCueBGS&);
 };

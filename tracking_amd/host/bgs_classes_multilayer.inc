@@ -1,6 +1,4 @@
-// bgs_classes_multilayer.inc — the IBGS class of package_bgs/jmo's MultiLayerBGS, written against the same names as bgs_classes.inc
-// and included after bgs_classes_imbs.inc by tracking_amd/host/bgs_host.h and tracking_amd/host/HipBGS.h.  A file of its own: the
-// tests pin the class lists of the other .inc files as they stand.
+// bgs_classes_multilayer.inc — the IBGS class of package_bgs/jmo's MultiLayerBGS, in the form bgs_classes.inc describes.
 
 // package_bgs/jmo/MultiLayerBGS.{h,cpp} (USTC_BGS type 23).  loadConfig runs every frame, but the values reach CMultiLayerBGS once,
 // `if(firstTime)`: they travel in bgs_multilayer_params, which the engine takes when its model is built and keeps (a later
@@ -14,13 +12,7 @@
 class MultiLayerBGS : public HipBGSBase {
  public:
   enum Status { MLBGS_NONE = -1, MLBGS_LEARN = 0, MLBGS_DETECT = 1 };
-  MultiLayerBGS()
-      : HipBGSBase(BGS_MULTILAYER, "MultiLayerBGS"), status(MLBGS_NONE), showOutput(true), saveModel(false), disableDetectMode(true), disableLearning(false),
-        detectAfter(0), loadDefaultParams(true), max_mode_num(5), weight_updating_constant(5.0f), texture_weight(0.5f), bg_mode_percent(0.6f),
-        pattern_neig_half_size(4), pattern_neig_gaus_sigma(3.0f), bg_prob_threshold(0.2f), bg_prob_updating_threshold(0.2f), robust_LBP_constant(3),
-        min_noised_angle(0.01768f), shadow_rate(0.6f), highlight_rate(1.2f), bilater_filter_sigma_s(3.0f), bilater_filter_sigma_r(0.1f), frame_duration(0.1f),
-        learn_mode_learn_rate_per_second(0.5f), learn_weight_learn_rate_per_second(0.5f), learn_init_mode_weight(0.05f),
-        detect_mode_learn_rate_per_second(0.01f), detect_weight_learn_rate_per_second(0.01f), detect_init_mode_weight(0.001f) {}
+  MultiLayerBGS() : HipBGSBase(BGS_MULTILAYER, "MultiLayerBGS"), status(MLBGS_NONE) {}
   BGS_HIP_BANNER_DTOR(MultiLayerBGS)
   void setStatus(Status _status) { status = _status; }  // MultiLayerBGS.cpp:31-34
 
@@ -59,74 +51,39 @@ class MultiLayerBGS : public HipBGSBase {
   }
 
  private:
-  void saveConfig() override {  // MultiLayerBGS.cpp:251-290
-    XmlConfig fs;
-    fs.beginWrite();
+  void describe(XmlIo& io) override {  // MultiLayerBGS.cpp:251-331
 #ifdef BGS_HIP_XML_HAS_STRINGS
-    fs.writeString("preloadModel", bg_model_preload);
+    io("preloadModel", bg_model_preload, "");
 #endif
-    fs.writeInt("saveModel", saveModel);
-    fs.writeInt("detectAfter", detectAfter);
-    fs.writeInt("disableDetectMode", disableDetectMode);
-    fs.writeInt("disableLearningInDetecMode", disableLearning);
-    fs.writeInt("loadDefaultParams", loadDefaultParams);
-    fs.writeInt("max_mode_num", max_mode_num);
-    fs.writeReal("weight_updating_constant", weight_updating_constant);
-    fs.writeReal("texture_weight", texture_weight);
-    fs.writeReal("bg_mode_percent", bg_mode_percent);
-    fs.writeInt("pattern_neig_half_size", pattern_neig_half_size);
-    fs.writeReal("pattern_neig_gaus_sigma", pattern_neig_gaus_sigma);
-    fs.writeReal("bg_prob_threshold", bg_prob_threshold);
-    fs.writeReal("bg_prob_updating_threshold", bg_prob_updating_threshold);
-    fs.writeInt("robust_LBP_constant", robust_LBP_constant);
-    fs.writeReal("min_noised_angle", min_noised_angle);
-    fs.writeReal("shadow_rate", shadow_rate);
-    fs.writeReal("highlight_rate", highlight_rate);
-    fs.writeReal("bilater_filter_sigma_s", bilater_filter_sigma_s);
-    fs.writeReal("bilater_filter_sigma_r", bilater_filter_sigma_r);
-    fs.writeReal("frame_duration", frame_duration);
-    fs.writeReal("learn_mode_learn_rate_per_second", learn_mode_learn_rate_per_second);
-    fs.writeReal("learn_weight_learn_rate_per_second", learn_weight_learn_rate_per_second);
-    fs.writeReal("learn_init_mode_weight", learn_init_mode_weight);
-    fs.writeReal("detect_mode_learn_rate_per_second", detect_mode_learn_rate_per_second);
-    fs.writeReal("detect_weight_learn_rate_per_second", detect_weight_learn_rate_per_second);
-    fs.writeReal("detect_init_mode_weight", detect_init_mode_weight);
-    fs.writeInt("showOutput", showOutput);
-    fs.save(configPath());
+    io("saveModel", saveModel, false);
+    io("detectAfter", detectAfter, 0);
+    io("disableDetectMode", disableDetectMode, true);
+    io("disableLearningInDetecMode", disableLearning, false);
+    io("loadDefaultParams", loadDefaultParams, true);
+    io("max_mode_num", max_mode_num, 5);
+    io("weight_updating_constant", weight_updating_constant, 5.0);
+    io("texture_weight", texture_weight, 0.5);
+    io("bg_mode_percent", bg_mode_percent, 0.6);
+    io("pattern_neig_half_size", pattern_neig_half_size, 4);
+    io("pattern_neig_gaus_sigma", pattern_neig_gaus_sigma, 3.0);
+    io("bg_prob_threshold", bg_prob_threshold, 0.2);
+    io("bg_prob_updating_threshold", bg_prob_updating_threshold, 0.2);
+    io("robust_LBP_constant", robust_LBP_constant, 3);
+    io("min_noised_angle", min_noised_angle, 0.01768);
+    io("shadow_rate", shadow_rate, 0.6);
+    io("highlight_rate", highlight_rate, 1.2);
+    io("bilater_filter_sigma_s", bilater_filter_sigma_s, 3.0);
+    io("bilater_filter_sigma_r", bilater_filter_sigma_r, 0.1);
+    io("frame_duration", frame_duration, 0.1);
+    io("learn_mode_learn_rate_per_second", learn_mode_learn_rate_per_second, 0.5);
+    io("learn_weight_learn_rate_per_second", learn_weight_learn_rate_per_second, 0.5);
+    io("learn_init_mode_weight", learn_init_mode_weight, 0.05);
+    io("detect_mode_learn_rate_per_second", detect_mode_learn_rate_per_second, 0.01);
+    io("detect_weight_learn_rate_per_second", detect_weight_learn_rate_per_second, 0.01);
+    io("detect_init_mode_weight", detect_init_mode_weight, 0.001);
+    io("showOutput", showOutput, true);
   }
-  void loadConfig() override {  // :292-331
-    XmlConfig fs;
-    fs.load(configPath());
-#ifdef BGS_HIP_XML_HAS_STRINGS
-    bg_model_preload = fs.readString("preloadModel", "");
-#endif
-    saveModel = fs.readInt("saveModel", false);
-    detectAfter = fs.readInt("detectAfter", 0);
-    disableDetectMode = fs.readInt("disableDetectMode", true);
-    disableLearning = fs.readInt("disableLearningInDetecMode", false);
-    loadDefaultParams = fs.readInt("loadDefaultParams", true);
-    max_mode_num = fs.readInt("max_mode_num", 5);
-    weight_updating_constant = (float)fs.readReal("weight_updating_constant", 5.0);
-    texture_weight = (float)fs.readReal("texture_weight", 0.5);
-    bg_mode_percent = (float)fs.readReal("bg_mode_percent", 0.6);
-    pattern_neig_half_size = fs.readInt("pattern_neig_half_size", 4);
-    pattern_neig_gaus_sigma = (float)fs.readReal("pattern_neig_gaus_sigma", 3.0);
-    bg_prob_threshold = (float)fs.readReal("bg_prob_threshold", 0.2);
-    bg_prob_updating_threshold = (float)fs.readReal("bg_prob_updating_threshold", 0.2);
-    robust_LBP_constant = fs.readInt("robust_LBP_constant", 3);
-    min_noised_angle = (float)fs.readReal("min_noised_angle", 0.01768);
-    shadow_rate = (float)fs.readReal("shadow_rate", 0.6);
-    highlight_rate = (float)fs.readReal("highlight_rate", 1.2);
-    bilater_filter_sigma_s = (float)fs.readReal("bilater_filter_sigma_s", 3.0);
-    bilater_filter_sigma_r = (float)fs.readReal("bilater_filter_sigma_r", 0.1);
-    frame_duration = (float)fs.readReal("frame_duration", 0.1);
-    learn_mode_learn_rate_per_second = (float)fs.readReal("learn_mode_learn_rate_per_second", 0.5);
-    learn_weight_learn_rate_per_second = (float)fs.readReal("learn_weight_learn_rate_per_second", 0.5);
-    learn_init_mode_weight = (float)fs.readReal("learn_init_mode_weight", 0.05);
-    detect_mode_learn_rate_per_second = (float)fs.readReal("detect_mode_learn_rate_per_second", 0.01);
-    detect_weight_learn_rate_per_second = (float)fs.readReal("detect_weight_learn_rate_per_second", 0.01);
-    detect_init_mode_weight = (float)fs.readReal("detect_init_mode_weight", 0.001);
-    showOutput = fs.readInt("showOutput", true);
+  void loaded() override {
     if (loadDefaultParams) {  // :110-128, :147-152: the hard-coded block replaces what was read, and is what the first frame saves
       max_mode_num = 5, weight_updating_constant = 5.0f, texture_weight = 0.5f, bg_mode_percent = 0.6f, pattern_neig_half_size = 4;
       pattern_neig_gaus_sigma = 3.0f, bg_prob_threshold = 0.2f, bg_prob_updating_threshold = 0.2f, robust_LBP_constant = 3;

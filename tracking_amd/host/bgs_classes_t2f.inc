@@ -1,6 +1,4 @@
-// bgs_classes_t2f.inc — the IBGS classes of package_bgs/tb's type-2 fuzzy GMMs, written against the same names as bgs_classes.inc and
-// included after bgs_classes_fuzzy.inc by tracking_amd/host/bgs_host.h and tracking_amd/host/HipBGS.h.  A file of its own: the tests
-// pin the class lists of the other .inc files as they stand; types 17 and 18 came later.
+// bgs_classes_t2f.inc — the IBGS classes of package_bgs/tb's type-2 fuzzy GMMs, in the form bgs_classes.inc describes.
 
 // package_bgs/tb/T2FGMM_UM.{h,cpp} and T2FGMM_UV.{h,cpp} (USTC_BGS types 17 and 18): the same file twice, the one difference being
 // params.Type().  loadConfig runs every frame into members of the wrapper's own types (double threshold / alpha, float km / kv, int
@@ -9,8 +7,7 @@
 // first frame on; img_bgmodel is never written.
 class T2FGMMBase : public HipBGSBase {
  protected:
-  T2FGMMBase(bgs_algo algo, const char* name)
-      : HipBGSBase(algo, name), threshold(9.0), alpha(0.01), km(1.5f), kv(0.6f), gaussians(3), showOutput(true) {}
+  T2FGMMBase(bgs_algo algo, const char* name) : HipBGSBase(algo, name) {}
   double threshold, alpha;
   float km, kv;
   int gaussians;
@@ -23,26 +20,13 @@ class T2FGMMBase : public HipBGSBase {
   }
 
  private:
-  void saveConfig() override {  // T2FGMM_U*.cpp:85-97
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeReal("threshold", threshold);
-    fs.writeReal("alpha", alpha);
-    fs.writeReal("km", km);
-    fs.writeReal("kv", kv);
-    fs.writeInt("gaussians", gaussians);
-    fs.writeInt("showOutput", showOutput);
-    fs.save(configPath());
-  }
-  void loadConfig() override {  // :99-111
-    XmlConfig fs;
-    fs.load(configPath());
-    threshold = fs.readReal("threshold", 9.0);
-    alpha = fs.readReal("alpha", 0.01);
-    km = (float)fs.readReal("km", 1.5);
-    kv = (float)fs.readReal("kv", 0.6);
-    gaussians = fs.readInt("gaussians", 3);
-    showOutput = fs.readInt("showOutput", true);
+  void describe(XmlIo& io) override {  // T2FGMM_U*.cpp:85-111
+    io("threshold", threshold, 9.0);
+    io("alpha", alpha, 0.01);
+    io("km", km, 1.5);
+    io("kv", kv, 0.6);
+    io("gaussians", gaussians, 3);
+    io("showOutput", showOutput, true);
   }
 };
 

@@ -1,6 +1,4 @@
-// bgs_classes_vumeter.inc — the IBGS class of package_bgs/av (VuMeter), written against the same four names as bgs_classes.inc and
-// included after bgs_classes_lb.inc by tracking_amd/host/bgs_host.h and tracking_amd/host/HipBGS.h.  A file of its own: the tests
-// pin the class lists of the other .inc files as they stand; type 31 came later.
+// bgs_classes_vumeter.inc — the IBGS class of package_bgs/av (VuMeter), in the form bgs_classes.inc describes.
 
 // package_bgs/av/VuMeter.{h,cpp} (USTC_BGS type 31).  loadConfig runs every frame, but the wrapper hands binSize, alpha and
 // threshold to its model once, on the first frame, through setters that replace out-of-range values (VuMeter.cpp:42-47,
@@ -8,27 +6,16 @@
 // does.  Mask and background model are 8UC1 (the background is the gray image the model keeps).
 class VuMeter : public HipBGSBase {
  public:
-  VuMeter() : HipBGSBase(BGS_VUMETER, "VuMeter"), showOutput(true) {}
+  VuMeter() : HipBGSBase(BGS_VUMETER, "VuMeter") {}
   BGS_HIP_BANNER_DTOR(VuMeter)
  private:
   bool showOutput;
-  void saveConfig() override {  // VuMeter.cpp:88-101
-    XmlConfig fs;
-    fs.beginWrite();
-    fs.writeInt("enableFilter", params_.vu_enable_filter);
-    fs.writeInt("binSize", params_.vu_bin_size);
-    fs.writeReal("alpha", params_.vu_alpha);
-    fs.writeReal("threshold", params_.vu_threshold);
-    fs.writeInt("showOutput", showOutput);
-    fs.save(configPath());
-  }
-  void loadConfig() override {  // :103-116
-    XmlConfig fs;
-    fs.load(configPath());
-    params_.vu_enable_filter = fs.readInt("enableFilter", true);
-    params_.vu_bin_size = fs.readInt("binSize", 8);
-    params_.vu_alpha = fs.readReal("alpha", 0.995);
-    params_.vu_threshold = fs.readReal("threshold", 0.03);
-    showOutput = fs.readInt("showOutput", true);
+  int bgChannels(int) const override { return 1; }
+  void describe(XmlIo& io) override {  // VuMeter.cpp:88-116
+    io("enableFilter", params_.vu_enable_filter, true);
+    io("binSize", params_.vu_bin_size, 8);
+    io("alpha", params_.vu_alpha, 0.995);
+    io("threshold", params_.vu_threshold, 0.03);
+    io("showOutput", showOutput, true);
   }
 };

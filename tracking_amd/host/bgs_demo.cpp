@@ -7,7 +7,8 @@
 // holds one byte per pixel; SJN_MultiCueBGS's file is <out_prefix>.MultiCueBGS.raw, after its FrameProcessor name).
 // With a 6th argument the frames go through USTC_BGS(type) instead (ustc_src/ustc_bgs.cpp) and GetMask() of every frame is
 // written to <out_prefix>.ustc.raw.  With a 7th argument ("box" or "moments") the detector is a HipFGDetector and every frame's blob
-// list (GetBlobs) is printed like ustc_src/trackingMain.cpp:189-190 prints the tracker's: "pBlob x,y,w,h,id is ...".
+// list (GetBlobs) is printed like ustc_src/trackingMain.cpp:189-190 prints the tracker's: "pBlob x,y,w,h,id is ...".  With "shapes" as
+// the 7th argument every frame's "frame t mask RxCxCH background RxCxCH" is printed instead: what the class handed out, as it handed it.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -47,7 +48,8 @@ int main(int argc, char** argv) {
     if (!in) throw Exception(BGS_ERR_INVALID, std::string("cannot open ") + argv[1]);
     if (argc >= 7) {  // the tracker's FG detector: Process(frame) then GetMask(), trackingMain.cpp:152-166
       HipFGDetector fg(std::atoi(argv[6]));
-      const bool want_blobs = argc >= 8, from_moments = want_blobs && std::string(argv[7]) == "moments";
+      const std::string extra = argc >= 8 ? argv[7] : "";
+      const bool want_blobs = argc >= 8 && extra != "shapes", from_moments = extra == "moments", want_shapes = extra == "shapes";
       std::ofstream out((prefix + ".ustc.raw").c_str(), std::ios::binary);
       Image frame(rows, cols, 3);
       CvBlobSeq blobs;
@@ -57,6 +59,9 @@ int main(int argc, char** argv) {
         fg.Process(frame);
         const Image* m = fg.GetMask();
         dump(out, m ? *m : Image(), rows, cols);
+        if (want_shapes)
+          std::printf("frame %d mask %dx%dx%d background %dx%dx%d\n", t, fg.img_mask.rows, fg.img_mask.cols, fg.img_mask.channels(), fg.img_bkgmodel.rows,
+                      fg.img_bkgmodel.cols, fg.img_bkgmodel.channels());
         if (want_blobs) {
           fg.GetBlobs(&blobs, 8, from_moments);
           std::printf("frame %d blobs %d\n", t, blobs.GetBlobNum());
@@ -72,16 +77,8 @@ int main(int argc, char** argv) {
     FrameProcessor* fp = new FrameProcessor;
     fp->init();
     FramePrep prep;  // VideoCapture's resize / flip / ROI from ./config/VideoCapture.xml (defaults: none); BGSLIB_RAW geometry in, prepared out
-    const char* names[] = {"FrameDifferenceBGS", "StaticFrameDifferenceBGS", "WeightedMovingMeanBGS", "WeightedMovingVarianceBGS",
-                           "MixtureOfGaussianV1BGS", "MixtureOfGaussianV2BGS", "AdaptiveBackgroundLearning", "AdaptiveSelectiveBackgroundLearning",
-                           "GMG", "DPAdaptiveMedianBGS", "DPGrimsonGMMBGS", "DPZivkovicAGMMBGS", "DPMeanBGS", "DPWrenGABGS", "SigmaDeltaBGS", "SuBSENSEBGS", "LOBSTERBGS", "KDE",
-                           "DPPratiMediodBGS", "DPTextureBGS", "LBSimpleGaussian", "LBFuzzyGaussian", "LBMixtureOfGaussians", "LBAdaptiveSOM", "LBFuzzyAdaptiveSOM", "VuMeter",
-                           "FuzzySugenoIntegral", "FuzzyChoquetIntegral", "T2FGMM_UM", "T2FGMM_UV", "DPEigenbackgroundBGS", "IndependentMultimodalBGS", "MultiLayerBGS", "MultiCueBGS"};
-    Image* masks[] = {&fp->img_framediff, &fp->img_staticfdiff, &fp->img_wmovmean, &fp->img_movvar, &fp->img_mog1, &fp->img_mog2, &fp->img_bkgl_fgmask, &fp->img_asbl,
-                     &fp->img_gmg, &fp->img_adpmed, &fp->img_grigmm, &fp->img_zivgmm, &fp->img_tmpmean, &fp->img_wrenga, &fp->img_sdbgs, &fp->img_ssbgs, &fp->img_lobgs, &fp->img_kde,
-                     &fp->img_pramed, &fp->img_texbgs, &fp->img_lb_sg, &fp->img_lb_fg, &fp->img_lb_mog, &fp->img_lb_som, &fp->img_lb_fsom, &fp->img_vumeter, &fp->img_fsi, &fp->img_fci, &fp->img_t2fgmm_um, &fp->img_t2fgmm_uv, &fp->img_eigbkg, &fp->img_imbs, &fp->img_mlbgs, &fp->img_mcbgs};
     std::vector<std::ofstream> outs;
-    for (const char* nm : names) outs.emplace_back((prefix + "." + nm + ".raw").c_str(), std::ios::binary);
+    for (const FrameProcessor::Class& c : FrameProcessor::classes) outs.emplace_back((prefix + "." + c.file + ".raw").c_str(), std::ios::binary);
     Image frame(rows, cols, 3);
     for (int t = 0; t < n; ++t) {
       in.read((char*)frame.data, (size_t)rows * cols * 3);
@@ -89,7 +86,7 @@ int main(int argc, char** argv) {
       Image img_input;
       prep.process(frame, img_input);  // VideoCapture.cpp:164-203
       fp->process(img_input);
-      for (size_t i = 0; i < outs.size(); ++i) dump(outs[i], *masks[i], img_input.rows, img_input.cols);
+      for (size_t i = 0; i < outs.size(); ++i) dump(outs[i], fp->*FrameProcessor::classes[i].image, img_input.rows, img_input.cols);
     }
     fp->finish();
     delete fp;

@@ -141,6 +141,9 @@ class XmlConfig {
   std::vector<std::string> out_;
 };
 
+#define BGS_HIP_XML_HAS_STRINGS 1  // this XmlConfig has readString / writeString (tictoc, MultiLayerBGS's preloadModel)
+#include "bgs_describe.inc"
+
 // ---------------------------------------------------------------------------------------------- errors
 // What a failed CV_Assert is in the reference: an exception derived from std::exception, caught at Main.cpp:63-72.
 class Exception : public std::runtime_error {
@@ -161,7 +164,7 @@ class IBGS {  // package_bgs/IBGS.h:21-33
 };
 
 // Common machinery of every class below: one single-stream engine, per-frame config reload, output conventions.
-class HipBGSBase : public IBGS {
+class HipBGSBase : public IBGS, protected XmlDescribed {
  public:
   ~HipBGSBase() override {
     if (engine_) bgs_destroy(engine_);
@@ -188,9 +191,8 @@ class HipBGSBase : public IBGS {
       if (rc) throw Exception(rc, std::string(name_) + ": " + bgs_last_error());
     }
     if (int rc = applyClassParams(engine_)) throw Exception(rc, std::string(name_) + ": " + bgs_last_error());
-    const int bg_ch = (algo_ == BGS_ASBL || algo_ == BGS_VUMETER) ? 1 : img_input.channels();
     fg_.create(img_input.rows, img_input.cols, 1);
-    bg_.create(img_input.rows, img_input.cols, bg_ch);
+    bg_.create(img_input.rows, img_input.cols, bgChannels(img_input.channels()));
     uint32_t flags = 0;
     int rc = bgs_process(engine_, 0, img_input.data, img_input.rows, img_input.cols, img_input.channels(), img_input.step, fg_.data, fg_.step, bg_.data,
                          bg_.step, &flags);
@@ -244,10 +246,11 @@ class HipBGSBase : public IBGS {
   // parameters that do not travel in bgs_params (bgs_classes_fuzzy.inc, bgs_classes_t2f.inc, bgs_classes_eigen.inc, bgs_classes_imbs.inc, bgs_classes_multilayer.inc): handed over before every frame, after bgs_set_params
   virtual int applyClassParams(bgs_engine*) { return 0; }
   int fg_channels_ = 1;  // 3: the class hands its caller an 8UC3 mask with equal channels, like the reference's lb/ wrappers (bgs_classes_lb.inc)
+  virtual int bgChannels(int input_channels) const { return input_channels; }  // the classes whose background model is a gray image say 1
 
  private:
-  void saveConfig() override = 0;  // private pure virtuals of IBGS, re-declared so process() above may call them
-  void loadConfig() override = 0;
+  void saveConfig() override { saveDescribed(configPath()); }  // both come from the class's describe() (bgs_describe.inc)
+  void loadConfig() override { loadDescribed(configPath()); }
   bgs_algo algo_;
   const char* name_;
   bool clears_bg_;
@@ -289,9 +292,7 @@ class HipBGSBase : public IBGS {
 #include "bgs_classes_t2f.inc"
 #include "bgs_classes_eigen.inc"
 #include "bgs_classes_imbs.inc"
-#define BGS_HIP_XML_HAS_STRINGS 1
 #include "bgs_classes_multilayer.inc"
-#undef BGS_HIP_XML_HAS_STRINGS
 #define BGS_HIP_MAT Image
 #define BGS_HIP_8UC3 3
 #define BGS_HIP_FAIL(code, what) throw Exception((code), (what))
@@ -301,5 +302,6 @@ class HipBGSBase : public IBGS {
 #undef BGS_HIP_FAIL
 
 #undef BGS_HIP_BANNER_DTOR
+#undef BGS_HIP_XML_HAS_STRINGS
 
 }  // namespace bgs_hip

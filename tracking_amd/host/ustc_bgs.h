@@ -2,20 +2,12 @@
 // cvCreateBlobTrackerAuto1 (ustc_src/trackingMain.cpp:33-35, :613-618; the shipped build uses type 36 = SuBSENSE).
 // Same type table, same Process / GetMask / Release protocol; OpenCV-legacy's CvFGDetector base and IplImage are not in this
 // image, so the mask is handed out as a bgs_hip::Image (INTEGRATION.md shows the IplImage-returning version for the reference).
-// Types whose class is outside the hot path (ustc_bgs.cpp:23-58: dp Eigenbackground, tb/'s T2FMRF pair, jmo/, LbpMrf, ck/, db/,
-// sjn/; of ae/ only KDE, type 32, of lb/ the five per-pixel models, types 25-29, av/'s VuMeter, type 31, and of tb/ the two fuzzy
-// integrals, types 21 and 22, and the two type-2 fuzzy GMMs, types 17 and 18, are built) throw instead of silently running something
-// else.  T2FMRF_UM / T2FMRF_UV (19, 20) stay refused on purpose: T2FMRF.cpp:331 reads the weights of ANOTHER pixel's modes, so the
-// result depends on pixel order, and the MRF result goes into the low-threshold mask, which the wrapper clears before it returns
-// the high-threshold one.  Type 15: the class exists (DPEigenbackgroundBGS, bgs_classes_eigen.inc; FrameProcessor's
-// enableDPEigenbackgroundBGS builds it), but the type table still throws for 15: the suite pins USTC_BGS(15) as refused at run time
-// and the switch below as holding exactly the two tb/ cases, so a tracker reaches the class as an IBGS, not by number.
-// Type 33 likewise: IndependentMultimodalBGS exists (bgs_classes_imbs.inc; FrameProcessor's enableIMBS builds it) and the type table
-// still throws for 33, which the suite pins as refused too.
-// Type 23 likewise: MultiLayerBGS exists (bgs_classes_multilayer.inc; FrameProcessor's enableMultiLayerBGS builds it) and the type
-// table still throws for 23, the suite's own example of a refused type.
-// Type 34 likewise: SJN_MultiCueBGS exists (bgs_classes_multicue.inc, on a bgs_multicue handle instead of an engine; FrameProcessor's
-// enableMultiCueBGS builds it) and the type table still throws for 34, which the suite pins as refused at run time.
+// One type table: a type either builds its class or is refused, and throws instead of silently running something else.  Refused:
+// T2FMRF_UM / T2FMRF_UV (19, 20) on purpose: T2FMRF.cpp:331 reads the weights of ANOTHER pixel's modes, so the result depends on
+// pixel order, and the MRF result goes into the low-threshold mask, which the wrapper clears before it returns the high-threshold
+// one; 24 (LbpMrf) and 30 (ck/) have no class here; 15, 23, 33 and 34 have one (DPEigenbackgroundBGS,
+// MultiLayerBGS, IndependentMultimodalBGS, SJN_MultiCueBGS: FrameProcessor builds them, a tracker reaches them as an IBGS) and are
+// not offered by number.
 #pragma once
 #include "bgs_host.h"
 #include "blob.h"
@@ -31,38 +23,38 @@ class USTC_BGS {
   explicit USTC_BGS(int type) : frameNum(0), bgs(nullptr) {  // ustc_bgs.cpp:3-69
     const int i = type;
     if (!(i >= 0 && i <= 37)) throw Exception(BGS_ERR_INVALID, "USTC_BGS: type must be 0..37");  // CV_Assert(i>=0&&i<=37)
-    if (i == 0) bgs = new FrameDifferenceBGS;
-    if (i == 1) bgs = new StaticFrameDifferenceBGS;
-    if (i == 2) bgs = new WeightedMovingMeanBGS;
-    if (i == 3) bgs = new WeightedMovingVarianceBGS;
-    if (i == 4) bgs = new MixtureOfGaussianV1BGS;
-    if (i == 5) bgs = new MixtureOfGaussianV2BGS;
-    if (i == 6) bgs = new AdaptiveBackgroundLearning;
-    if (i == 7) bgs = new AdaptiveSelectiveBackgroundLearning;
-    if (i == 8) bgs = new GMG;
-    if (i == 9) bgs = new DPAdaptiveMedianBGS;
-    if (i == 10) bgs = new DPGrimsonGMMBGS;
-    if (i == 11) bgs = new DPZivkovicAGMMBGS;
-    if (i == 12) bgs = new DPMeanBGS;
-    if (i == 13) bgs = new DPWrenGABGS;
-    if (i == 14) bgs = new DPPratiMediodBGS;
-    if (i == 16) bgs = new DPTextureBGS;
-    if (i == 21) bgs = new FuzzySugenoIntegral;
-    if (i == 22) bgs = new FuzzyChoquetIntegral;
-    if (i == 25) bgs = new LBSimpleGaussian;
-    if (i == 26) bgs = new LBFuzzyGaussian;
-    if (i == 27) bgs = new LBMixtureOfGaussians;
-    if (i == 28) bgs = new LBAdaptiveSOM;
-    if (i == 29) bgs = new LBFuzzyAdaptiveSOM;
-    if (i == 31) bgs = new VuMeter;
-    if (i == 32) bgs = new KDE;
-    if (i == 35) bgs = new SigmaDeltaBGS;
-    if (i == 36) bgs = new SuBSENSEBGS();
-    if (i == 37) bgs = new LOBSTERBGS();
-    switch (i) {  // tb/'s type-2 fuzzy GMMs
+    switch (i) {
+      case 0: bgs = new FrameDifferenceBGS; break;
+      case 1: bgs = new StaticFrameDifferenceBGS; break;
+      case 2: bgs = new WeightedMovingMeanBGS; break;
+      case 3: bgs = new WeightedMovingVarianceBGS; break;
+      case 4: bgs = new MixtureOfGaussianV1BGS; break;
+      case 5: bgs = new MixtureOfGaussianV2BGS; break;
+      case 6: bgs = new AdaptiveBackgroundLearning; break;
+      case 7: bgs = new AdaptiveSelectiveBackgroundLearning; break;
+      case 8: bgs = new GMG; break;
+      case 9: bgs = new DPAdaptiveMedianBGS; break;
+      case 10: bgs = new DPGrimsonGMMBGS; break;
+      case 11: bgs = new DPZivkovicAGMMBGS; break;
+      case 12: bgs = new DPMeanBGS; break;
+      case 13: bgs = new DPWrenGABGS; break;
+      case 14: bgs = new DPPratiMediodBGS; break;
+      case 16: bgs = new DPTextureBGS; break;
       case 17: bgs = new T2FGMM_UM; break;
       case 18: bgs = new T2FGMM_UV; break;
-      default: break;
+      case 21: bgs = new FuzzySugenoIntegral; break;
+      case 22: bgs = new FuzzyChoquetIntegral; break;
+      case 25: bgs = new LBSimpleGaussian; break;
+      case 26: bgs = new LBFuzzyGaussian; break;
+      case 27: bgs = new LBMixtureOfGaussians; break;
+      case 28: bgs = new LBAdaptiveSOM; break;
+      case 29: bgs = new LBFuzzyAdaptiveSOM; break;
+      case 31: bgs = new VuMeter; break;
+      case 32: bgs = new KDE; break;
+      case 35: bgs = new SigmaDeltaBGS; break;
+      case 36: bgs = new SuBSENSEBGS; break;
+      case 37: bgs = new LOBSTERBGS; break;
+      default: break;  // 15, 19, 20, 23, 24, 30, 33, 34: refused below
     }
     if (!bgs) throw Exception(BGS_ERR_UNSUPPORTED, "USTC_BGS: type " + std::to_string(i) + " is outside the package_bgs hot path built here");
   }
