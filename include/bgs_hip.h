@@ -709,6 +709,29 @@ int bgs_mask_morph_device(int hip_device, const void* d_src, void* d_dst, int ro
 int bgs_canny_device(int hip_device, const void* d_src, void* d_dst, int images, int rows, int cols, int low, int high,
                      void* hip_stream);
 
+/* MotionDetection::GetMotionsMaskHU of LbpMrf (package_bgs/ck/MotionDetection.cpp:1256-1366) as a pure function, `images` maps at
+ * once: the background-rate map of the node grid in, the class's foreground mask out.  A = histogram_area
+ * (HUHistogramArea, 5), w = min_cut_weight (HUMinCutWeight, 8.0f); the node grid is NH = rows - A + 1 by NW = (cols - A + 1) / 2.
+ * Per node: source capacity 1, sink capacity (short)(w * (1 - rate)) clamped to [0, 32767]; edges of capacity 1 each way from node
+ * (x, y) to (x-1, y) and (x, y-1) only where x > 0 and y > 0 (row 0 has no horizontal edges, column 0 no vertical ones).  The exact
+ * minimum cut: a node is SOURCE iff the source reaches it in the residual graph of a maximum flow, as Graph::what_segment says.
+ * Then the mask of :1322-1342 (node row y on image row y + A - A / 2, node column on image column x + A / 2), cvFloodFill from
+ * (0, 0) with the holes becoming foreground, and one 3 x 3 erosion.
+ *   d_rate   f32 [images][NH][NW]      d_mask  u8 [images][rows][cols], 0 / 255
+ *   d_labels u8 [images][NH][NW] or NULL, 1 = SINK      d_flow  i32 [images] or NULL: the value Graph::maxflow() returns
+ * Asynchronous on hip_stream (its scratch memory is allocated and freed in stream order).  The cut converges through a fixed number
+ * of launches; a call that needed more raises the device's sticky counter (bgs_lbpmrf_mask_counters) and its outputs are not the cut.
+ * bgs_lbpmrf_mask_check states every refusal without a device, all BGS_ERR_UNSUPPORTED: an even A or A < 3, a frame with no node
+ * (NH < 1 or NW < 1), a weight that is not finite, and an odd cols - A + 1: the reference indexes its node array with x / 2 for x up
+ * to cols - A, past the array when that width is odd. */
+int bgs_lbpmrf_mask_check(int rows, int cols, int histogram_area, float min_cut_weight);
+int bgs_lbpmrf_mask_device(int hip_device, const void* d_rate, void* d_mask, void* d_labels, void* d_flow, int images, int rows,
+                           int cols, int histogram_area, float min_cut_weight, void* hip_stream);
+/* Waits for the device.  *not_converged: how many bgs_lbpmrf_mask_device calls on this device, since the library was loaded, were not
+ * finished by their launches (sticky; 0 is the only healthy value).  *last_launches: the relaxation launches the last call used.
+ * Either pointer may be NULL. */
+int bgs_lbpmrf_mask_counters(int hip_device, uint64_t* not_converged, uint64_t* last_launches);
+
 /* ---- the model stage of SJN_MultiCueBGS (package_bgs/sjn): everything the class does per pixel -------------
  * Frame reduction, the 7 x 7 blur, the HSV-cone conversion, the texture and colour codebooks with their cache-books, training,
  * the confidence and landmark maps and the model update with absorption, as SJN_MultiCueBGS.cpp's own functions define them.

@@ -26,6 +26,9 @@ Not the driver's bench line (bench.py is); the numbers go to DESIGN.md §6.
              to 160 x 120: us per train, landmark and update call, bytes of state per reduced pixel, the live bytes a call touches
              over this box's copy rate; the 32-stream step as two ranges on two HIP streams beside the one call; the host path of one
              1080p camera (upload + step + download)
+  --only lbpmrf_mask: bgs_lbpmrf_mask_device (the grid min-cut and the mask of LbpMrf) on 1, 8 and 32 rate maps of a 1080p frame
+             (1076 x 958 nodes): blob-like maps, uniform noise and an all-neutral map; us per call, the relaxation launches a call used,
+             and the max-flow / min-cut duality of every map as the leg's own check
 usage: bench_configs.py [--streams S] [--swizzle 0|1]"""
 import argparse
 import os
@@ -325,6 +328,42 @@ def run_canny(rows=120, cols=160, reps=50):
             us = a.elapsed_time(b) / reps * 1e3
             print("canny %dx%d %-14s %3d images: %8.1f us per call, %7.2f us per image, %d edge pixels  (numpy restatement %.1f ms per image)"
                   % (cols, rows, name, images, us, us / images, int((want == 255).sum()), cpu_ms))
+
+
+def run_lbpmrf_mask(rows=1080, cols=1920, reps=5):
+    """bgs_lbpmrf_mask_device: a fixed budget of step launches per call, of which the first `launches` work and the rest return at once.  The
+    reference is not needed: the labels describe a cut, and a cut whose capacity equals the flow value is a minimum cut of a maximum flow."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import lbpmrf_numpy as ln
+    import lbpmrf_scenes as sc
+    from tracking_amd.engine import lbpmrf_mask_counters, lbpmrf_mask_device
+    nh, nw = sc.nodes(rows, cols)
+    makers = (("blobs", lambda k: sc.blobs(nh, nw, 1 + k)), ("uniform noise", lambda k: sc.uniform(nh, nw, 2 + k)), ("all neutral", lambda k: sc.neutral(nh, nw)))
+    for name, make in makers:
+        distinct = [make(k) for k in range(4)]
+        for images in (1, 8, 32):
+            rates = np.stack([distinct[k % 4] for k in range(images)])
+            d = torch.from_numpy(rates).cuda()
+            mask, labels, flow = lbpmrf_mask_device(d, rows, cols)
+            torch.cuda.synchronize()
+            stuck, launches = lbpmrf_mask_counters()
+            assert stuck == 0, "the cut did not converge within its launches"
+            labels_h, flow_h = labels.cpu().numpy(), flow.cpu().numpy()
+            for k in range(min(images, 4)):
+                cut = ln.duality(ln.sink_weights(rates[k]), labels_h[k])
+                assert cut == int(flow_h[k]), ("duality", name, images, k, cut, int(flow_h[k]))
+            for k in range(4, images):  # the repeats of the batch
+                assert np.array_equal(labels_h[k], labels_h[k % 4]) and flow_h[k] == flow_h[k % 4]
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                mask, labels, flow = lbpmrf_mask_device(d, rows, cols)
+            b.record()
+            torch.cuda.synchronize()
+            us = a.elapsed_time(b) / reps * 1e3
+            print("lbpmrf_mask %dx%d (%d x %d nodes) %-14s %2d maps: %10.1f us per call, %9.1f us per map, %3d relaxation launches used, SINK nodes of map 0 %d, "
+                  "foreground pixels of map 0 %d, duality holds" % (cols, rows, nh, nw, name, images, us, us / images, launches, int(labels_h[0].sum()), int((mask[0] != 0).sum())))
+    assert lbpmrf_mask_counters()[0] == 0
 
 
 def run_multicue(rows=1080, cols=1920, reps=30):
@@ -1290,6 +1329,9 @@ def main():
         return
     if args.only == "canny":
         run_canny()
+        return
+    if args.only == "lbpmrf_mask":
+        run_lbpmrf_mask()
         return
     if args.only == "multicue":
         run_multicue()

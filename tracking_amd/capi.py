@@ -204,6 +204,9 @@ SYMBOLS = [
     ("bgs_lbsp_describe_batch_device", C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     ("bgs_mask_morph_device", C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ("bgs_canny_device", C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    ("bgs_lbpmrf_mask_check", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float]),
+    ("bgs_lbpmrf_mask_device", C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
+    ("bgs_lbpmrf_mask_counters", C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("bgs_multicue_default_params", C.c_int, [C.POINTER(BgsMulticueParams)]),
     ("bgs_multicue_check", C.c_int, [C.POINTER(BgsMulticueParams), C.c_int, C.c_int]),
     ("bgs_multicue_create", C.c_int, [C.c_int, C.c_int, C.POINTER(BgsMulticueParams), C.POINTER(_P)]),

@@ -41,6 +41,7 @@
 #include "kernel_imbs.h"
 #include "kernel_multilayer.h"
 #include "kernel_canny.h"
+#include "gridcut.h"
 #include "kernel_multicue.h"
 #include "multicue_box.h"
 #include "kernel_cc.h"
@@ -1563,6 +1564,99 @@ int bgs_canny_device(int hip_device, const void* d_src, void* d_dst, int images,
   if (low > high) std::swap(low, high);  // cvCanny orders its two thresholds itself
   hipLaunchKernelGGL(bgs::canny_kernel, dim3(images), dim3(bgs::kCannyBlock), 0, (hipStream_t)hip_stream, (const uint8_t*)d_src, (uint8_t*)d_dst, rows, cols, low, high);
   HIP_TRY(hipGetLastError());
+  return BGS_OK;
+}
+
+// ---- the LbpMrf mask stage (gridcut.h)
+int bgs_lbpmrf_mask_check(int rows, int cols, int histogram_area, float min_cut_weight) {
+  if (histogram_area < 3 || histogram_area % 2 == 0)
+    return fail(BGS_ERR_UNSUPPORTED, "LbpMrf: histogram_area %d: it must be odd and at least 3", histogram_area);
+  if (!std::isfinite(min_cut_weight)) return fail(BGS_ERR_UNSUPPORTED, "LbpMrf: min_cut_weight is not finite");
+  if (rows < histogram_area || cols - histogram_area + 1 < 2)
+    return fail(BGS_ERR_UNSUPPORTED, "LbpMrf: a %d x %d frame has no node for histogram_area %d", rows, cols, histogram_area);
+  if ((cols - histogram_area + 1) % 2)
+    return fail(BGS_ERR_UNSUPPORTED, "LbpMrf: cols - histogram_area + 1 = %d is odd (the reference reads past its node array there)", cols - histogram_area + 1);
+  return BGS_OK;
+}
+
+namespace {
+std::mutex g_lbpmrf_mu;
+unsigned long long* g_lbpmrf_stats[64];  // per device: [0] sticky "did not converge" counter, [1] launches of the last call; never freed
+
+int lbpmrf_stats(int hip_device, unsigned long long** out) {
+  if (hip_device < 0 || hip_device >= 64) return fail(BGS_ERR_INVALID, "LbpMrf: bad device %d", hip_device);
+  std::lock_guard<std::mutex> lock(g_lbpmrf_mu);
+  if (!g_lbpmrf_stats[hip_device]) {
+    unsigned long long* p = nullptr;
+    HIP_TRY(hipMalloc((void**)&p, 2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(p, 0, 2 * sizeof(unsigned long long)));
+    g_lbpmrf_stats[hip_device] = p;
+  }
+  *out = g_lbpmrf_stats[hip_device];
+  return BGS_OK;
+}
+}  // namespace
+
+int bgs_lbpmrf_mask_counters(int hip_device, uint64_t* not_converged, uint64_t* last_launches) {
+  HIP_TRY(hipSetDevice(hip_device));
+  unsigned long long* st = nullptr;
+  int rc = lbpmrf_stats(hip_device, &st);
+  if (rc) return rc;
+  unsigned long long h[2];
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(h, st, sizeof(h), hipMemcpyDeviceToHost));
+  if (not_converged) *not_converged = h[0];
+  if (last_launches) *last_launches = h[1];
+  return BGS_OK;
+}
+
+int bgs_lbpmrf_mask_device(int hip_device, const void* d_rate, void* d_mask, void* d_labels, void* d_flow, int images, int rows, int cols, int histogram_area,
+                           float min_cut_weight, void* hip_stream) {
+  if (!d_rate || !d_mask || images <= 0 || images > 65535 || rows <= 0 || cols <= 0) return fail(BGS_ERR_INVALID, "bgs_lbpmrf_mask_device: bad argument");
+  int rc = bgs_lbpmrf_mask_check(rows, cols, histogram_area, min_cut_weight);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(hip_device));
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int nh = rows - histogram_area + 1, nw = (cols - histogram_area + 1) / 2;
+  const size_t n = (size_t)images * nh * nw, px = (size_t)images * rows * cols;
+  if ((size_t)nh * nw > (size_t)INT32_MAX) return fail(BGS_ERR_UNSUPPORTED, "LbpMrf: too many nodes");
+  const int W64 = (cols + 63) / 64, tilesY = (rows + 63) / 64, budget = bgs::gc_launch_budget(nh, nw);
+  const size_t words = (size_t)images * rows * W64;
+  unsigned long long* stats = nullptr;
+  if ((rc = lbpmrf_stats(hip_device, &stats))) return rc;
+  // one stream-ordered allocation, carved up (256-byte pieces): nothing here waits for the device
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_int = up(n * sizeof(int)), b_ctl = up(bgs::gc_ctl_bytes(budget) + (size_t)images * sizeof(int)), b_lab = d_labels ? 0 : up(n), b_px = up(px),
+               b_bits = up(words * 8), b_fl = up((size_t)images * bgs::kSsFloodFlags * sizeof(int));
+  char* ws = nullptr;
+  HIP_TRY(hipMallocAsync((void**)&ws, 3 * b_int + b_ctl + b_lab + 2 * b_px + 2 * b_bits + b_fl, s));
+  char* at = ws;
+  auto take = [&](size_t b) { char* p = at; at += b; return p; };
+  bgs::GcArgs a{};
+  a.rate = (const float*)d_rate;
+  a.excess = (int*)take(b_int), a.height = (int*)take(b_int), a.resid = (int*)take(b_int);
+  a.ctl = (int*)take(b_ctl), a.negatives = a.ctl + 3 * (size_t)budget;
+  a.labels = d_labels ? (uint8_t*)d_labels : (uint8_t*)take(b_lab);
+  a.flow = (int*)d_flow, a.stats = stats;
+  a.images = images, a.nh = nh, a.nw = nw, a.budget = budget, a.weight = min_cut_weight;
+  uint8_t *nodes = (uint8_t*)take(b_px), *filled = (uint8_t*)take(b_px);
+  uint64_t *mb = (uint64_t*)take(b_bits), *rb = (uint64_t*)take(b_bits);
+  int* fl = (int*)take(b_fl);
+  (void)hipMemsetAsync(a.ctl, 0, b_ctl, s);
+  (void)hipMemsetAsync(fl, 0, b_fl, s);
+  bgs::gc_solve_launch(a, s);
+  bgs::lm_node_mask_launch(a.labels, nodes, images, rows, cols, histogram_area, nh, nw, s);
+  // cvFloodFill from (0, 0): SuBSENSE's device flood fill (the seed value is the corner's own, always 0 here)
+  hipLaunchKernelGGL(bgs::ss_flood_pack_kernel, dim3(blocks_for((size_t)rows * W64 * bgs::kWave), 1, images), dim3(bgs::kBlock), 0, s, (const uint8_t*)nodes, mb, rb, rows, cols, W64);
+  hipLaunchKernelGGL(bgs::ss_flood_seed_kernel, dim3(images), dim3(bgs::kBlock), 0, s, (const uint64_t*)mb, rb, rows, cols, W64);
+  const dim3 fgrid(blocks_for((size_t)tilesY * W64 * bgs::kWave), 1, images);
+  for (int k = 0; k < bgs::kSsFloodBatch; ++k) ss_launch_flood(fgrid, images, tilesY, s, mb, rb, rows, W64, fl, k);
+  hipLaunchKernelGGL(bgs::ss_flood_finish_kernel, dim3(images), dim3(256), 0, s, (const uint64_t*)mb, rb, rows, W64, fl, bgs::kSsFloodBatch);
+  bgs::lm_paint_launch(rb, filled, images, rows, cols, W64, s);
+  bgs::morph_launch(bgs::MorphArgs{filled, (uint8_t*)d_mask, rows, cols, 0, 3}, images, s);  // cvErode(…, NULL, 1)
+  hipError_t er = hipGetLastError();
+  hipError_t fr = hipFreeAsync(ws, s);
+  if (er != hipSuccess || fr != hipSuccess) return fail(BGS_ERR_HIP, "bgs_lbpmrf_mask_device: %s", hipGetErrorString(er != hipSuccess ? er : fr));
   return BGS_OK;
 }
 

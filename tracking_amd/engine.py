@@ -298,6 +298,39 @@ def canny_device(src, low, high, device=0, hip_stream=None):
     return dst
 
 
+LBPMRF_HISTOGRAM_AREA, LBPMRF_MIN_CUT_WEIGHT = 5, 8.0
+
+
+def lbpmrf_mask_device(rate, rows, cols, histogram_area=LBPMRF_HISTOGRAM_AREA, min_cut_weight=LBPMRF_MIN_CUT_WEIGHT, want_labels=True, want_flow=True,
+                       device=0, hip_stream=None):
+    """rate: torch CUDA float32 [NH][NW] or [images][NH][NW], the background-rate map of LbpMrf's node grid for rows x cols frames
+    (NH = rows - A + 1, NW = (cols - A + 1) / 2).  MotionDetection::GetMotionsMaskHU (bgs_lbpmrf_mask_device): returns (mask uint8
+    [..][rows][cols] of 0 / 255, labels uint8 like rate with 1 = SINK or None, flow int32 [images] or None)."""
+    import torch
+    capi.check(capi.lib().bgs_lbpmrf_mask_check(rows, cols, int(histogram_area), float(min_cut_weight)))
+    nh, nw = rows - histogram_area + 1, (cols - histogram_area + 1) // 2
+    if rate.dtype != torch.float32 or tuple(rate.shape[-2:]) != (nh, nw) or rate.dim() not in (2, 3):
+        raise ValueError("rate must be float32 [%d][%d] or [images][%d][%d]" % (nh, nw, nh, nw))
+    images = 1 if rate.dim() == 2 else rate.shape[0]
+    rate = rate.contiguous()
+    mask = torch.empty(tuple(rate.shape[:-2]) + (rows, cols), dtype=torch.uint8, device=rate.device)
+    labels = torch.empty(rate.shape, dtype=torch.uint8, device=rate.device) if want_labels else None
+    flow = torch.empty(images, dtype=torch.int32, device=rate.device) if want_flow else None
+    if hip_stream is None:
+        hip_stream = torch.cuda.current_stream().cuda_stream
+    capi.check(capi.lib().bgs_lbpmrf_mask_device(device, C.c_void_p(rate.data_ptr()), C.c_void_p(mask.data_ptr()), C.c_void_p(labels.data_ptr() if want_labels else None),
+                                                 C.c_void_p(flow.data_ptr() if want_flow else None), images, rows, cols, int(histogram_area), float(min_cut_weight),
+                                                 C.c_void_p(hip_stream)))
+    return mask, labels, flow
+
+
+def lbpmrf_mask_counters(device=0):
+    """(calls of lbpmrf_mask_device on this device that did not converge - sticky, 0 when healthy -, relaxation launches of the last call); waits for the device"""
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    capi.check(capi.lib().bgs_lbpmrf_mask_counters(device, C.byref(a), C.byref(b)))
+    return int(a.value), int(b.value)
+
+
 def multicue_xyz(bgr, device=0, hip_stream=None):
     """bgr: torch CUDA uint8 [..., 3].  BGR2HSVxyz_Par of SJN_MultiCueBGS on every pixel (bgs_multicue_xyz_device): uint8 of the same shape."""
     import torch
