@@ -1,6 +1,6 @@
-"""One adapter per model family for tools/fuzz_parity.py's `models` table (not a test module): the 15 classes that are pinned to
+"""One adapter per model family for tools/fuzz_parity.py's `models` table (not a test module): the 16 classes that are pinned to
 reference-built fixtures and restated in numpy (kde_numpy, dp2_numpy, lb_numpy, vumeter_numpy, fuzzy_numpy, t2f_numpy, eigen_numpy,
-imbs_numpy).
+imbs_numpy, multilayer_numpy).
 
 An adapter draws parameters (and, rarely, one the engine must refuse: `refusal()` is the table), names the
 input generators of its family, builds the restatement of one stream (`make_ref`: a fresh one per stream and after every
@@ -19,6 +19,8 @@ import imbs_masks as mk
 import imbs_numpy as im
 import kde_numpy as kn
 import lb_numpy as ln
+import multilayer_numpy as ml
+import multilayer_scenes as msc
 import t2f_numpy as tn
 import vumeter_numpy as vn
 from tracking_amd import capi
@@ -97,7 +99,9 @@ def _clip(kind, T, H, W, seed, quiet):
             "vu_box": lambda: vn.bgr(T, H, W, seed), "vu_leave": lambda: np.repeat(vn.leave(T, H, W, seed)[..., None], 3, axis=-1),
             "eigen_pca": lambda: en.pca_clip(T, H, W, seed, quiet), "imbs_box": lambda: im.clip("box", T, H, W, seed), "imbs_persist": lambda: im.clip("persist", T, H, W, seed),
             "imbs_shadow": lambda: _imbs_event("shadow", 2, T, H, W, seed, quiet), "imbs_holes": lambda: _imbs_event("holes", 2, T, H, W, seed, quiet),
-            "imbs_sudden": lambda: _imbs_event("sudden", 3, T, H, W, seed, quiet), "imbs_inject": lambda: mk.fuzz_clip(T, H, W, seed, quiet)}[kind]()
+            "imbs_sudden": lambda: _imbs_event("sudden", 3, T, H, W, seed, quiet), "imbs_inject": lambda: mk.fuzz_clip(T, H, W, seed, quiet),
+            "ml_scripted": lambda: msc.frames_of("scripted", H, W, T, seed), "ml_dark": lambda: msc.frames_of("dark", H, W, T, seed),
+            "ml_block": lambda: msc.frames_of("static_block", H, W, T, seed), "ml_scaled": lambda: msc.frames_of("scaled_block", H, W, T, seed)}[kind]()
 
 
 def _imbs_event(kind, part, T, H, W, seed, lead):
@@ -739,7 +743,115 @@ class Imbs(Adapter):
         return _ImbsRef(p, H, W, stats)
 
 
-ADAPTERS = [Kde(), Prati(), Texture(), Lb(), VuMeter(), Fuzzy(), T2f(), Eigen(), Imbs()]
+# -- MultiLayerBGS
+
+_ml_sine = []
+
+
+def _ml_min_sine_bits():
+    """m_fMinNoisedAngleSine as the reference's own constructor computed it: the committed fixture's bits (all 17 cases hold the same)."""
+    if not _ml_sine:
+        _ml_sine.append(int(ml.load()["defaults"]["consts"][0]))
+    return _ml_sine[0]
+
+
+class _MultiLayerRef:
+    def __init__(self, p, H, W, stats):
+        self.m, self.stats = ml.Model(p, H, W, _ml_min_sine_bits()), stats
+
+    def step(self, f):
+        before = dict(self.m.counts)
+        fg, bg = self.m.apply(f)
+        for k, v in self.m.counts.items():  # the branch counters, summed over the case's streams
+            self.stats[k] = self.stats.get(k, 0) + v - before[k]
+        return fg, bg, None  # every frame delivers both; a stream's first mask is the reference's zero mask
+
+    def switch(self, p):
+        pass
+
+    def planes(self):
+        order, modes, dist = self.m.state()
+        return {"order": order, "modes": modes, "dist": dist}
+
+
+class MultiLayer(Adapter):
+    """Everything is compared as raw bits: no tolerance, no redraw.  Parameters are frozen when the geometry is
+    set, so a switch must change nothing, and a stream reset after one still runs the old values.  An inverted clip is an ordinary
+    input."""
+    family, classes, has_bg, cut = "multilayer", {ml.CLASS_NAME: capi.MULTILAYER}, True, True
+    # static_block's 8 x 8 block is under 1 % of a big frame: scripted, dark and the block that scales with the frame come more often
+    kinds = ("ml_scripted", "ml_scripted", "ml_scripted", "ml_dark", "ml_dark", "ml_scaled", "ml_scaled", "ml_scaled", "ml_block")
+    # 1 x 1, one row, one column, 2 x 5, frames inside the largest halo (8) one or both ways, the smoothing tile's edges (32 x 8) from
+    # both sides, ragged 37 x 53, whole words 16 x 64
+    h_small, w_small = [1, 2, 7, 8, 9, 16, 33, 37], [1, 3, 5, 31, 32, 33, 37, 53, 64, 70, 33, 32, 31]
+    h_big, w_big = [33, 65, 97, 130], [64, 97, 131, 261]
+    # the mode learn rate of a stream in LEARN status, one float32 further (robust_LBP_constant 3 -> 4 lies under the MAX(., 5) clamp)
+    step_of = {ml.CLASS_NAME: ("learn_mode_learn_rate_per_second", lambda v: float(np.nextafter(np.float32(v), np.float32(np.inf))), None)}
+    FLOATS = [k for k in ml.FIELDS if k not in ml.INT_FIELDS]
+
+    def draw_params(self, rng, name, H, W, T):
+        c = lambda *v: v[int(rng.integers(0, len(v)))]
+        h = int(rng.integers(-1, 9))
+        sigma = c(3.0, 0.5, 1.0, 5.0, 0.0) if h < 0 else c(3.0, 0.5, 1.0, 5.0)
+        fast = rng.random() < 0.7  # with slow rates a short clip never creates a layer
+        p = dict(max_mode_num=int(rng.integers(1, 6)), weight_updating_constant=c(0.0, 0.0, 5.0, 1.0), texture_weight=c(0.5, 0.3, 1.0, 0.0, -1.0),
+                 bg_mode_percent=c(0.6, 0.3, 0.9), pattern_neig_half_size=h, pattern_neig_gaus_sigma=sigma, bg_prob_threshold=c(0.2, 0.1, 0.4),
+                 bg_prob_updating_threshold=c(0.2, 0.1, 0.35), robust_LBP_constant=c(3, 5, 6, 12), min_noised_angle=c(ml.DEFAULTS["min_noised_angle"], 0.05, 0.5),
+                 shadow_rate=c(0.6, 0.4, 1.0), highlight_rate=c(1.2, 1.0, 2.0), frame_duration=c(0.1, 0.1, 0.1, 0.04),
+                 learn_mode_learn_rate_per_second=c(5.0, 2.0) if fast else c(5.0, 0.5, 2.0), learn_weight_learn_rate_per_second=c(5.0, 5.0, 5.0, 2.0) if fast else c(5.0, 0.5, 2.0),
+                 learn_init_mode_weight=c(0.05, 0.2))
+        for k, v in (("detect_mode_learn_rate_per_second", (0.5, 2.0)), ("detect_weight_learn_rate_per_second", (0.5, 5.0)), ("detect_init_mode_weight", (0.05, 0.2))):
+            p[k] = c(*v) if rng.random() < 1 / 3 else ml.DEFAULTS[k]
+        flags = int(rng.integers(0, 8))
+        p.update(status=flags & 1, disable_detect_mode=flags >> 1 & 1, disable_learning=flags >> 2 & 1)
+        p["detect_after"] = [0, 0, 3, max(T, 8) // 2][int(rng.integers(0, 4))]  # draw_frames makes the last one T // 2
+        return {k: p[k] for k in ml.FIELDS}
+
+    def draw_frames(self, rng, p):
+        """8-30 frames (scripted changes its scene at frame 6; a layer that is not seen again is removed 14 frames later); a
+        detect_after above 3 falls on T // 2 of a clip of 8-22 frames."""
+        da, T = p["detect_after"], int(rng.integers(8, 31))
+        return T if da <= 3 else 2 * da + int(rng.integers(0, 2)) * (da < 11)
+
+    def draw_bad(self, rng, name, p):
+        bad = [("max_mode_num", 0), ("max_mode_num", 6), ("pattern_neig_half_size", 9), ("texture_weight", float("nan")), ("frame_duration", float("inf"))]
+        if p["pattern_neig_half_size"] >= 0:  # without smoothing the sigma is never read and not refused
+            bad += [("pattern_neig_gaus_sigma", 0.0), ("pattern_neig_gaus_sigma", -1.0)]
+        return bad[int(rng.integers(0, len(bad)))]
+
+    def refusal(self, name, p):  # ml_check, engine_multilayer.h
+        with np.errstate(over="ignore"):
+            finite = all(np.isfinite(np.float32(p[k])) for k in self.FLOATS)
+        h = p["pattern_neig_half_size"]
+        if not finite or not 1 <= p["max_mode_num"] <= ml.K or h > capi.MULTILAYER_MAX_HALF_SIZE or (h >= 0 and not p["pattern_neig_gaus_sigma"] > 0):
+            return capi.ERR_UNSUPPORTED
+        return None
+
+    def draw_switch(self, rng, name, p):  # a valid draw that an engine which wrongly took it would show
+        q = self.draw_params(rng, name, 0, 0, 8)
+        q.update(max_mode_num=p["max_mode_num"] % ml.K + 1, bg_prob_threshold=p["bg_prob_threshold"] + 0.15, pattern_neig_half_size=(p["pattern_neig_half_size"] + 2) % 9)
+        if not q["pattern_neig_gaus_sigma"] > 0:
+            q["pattern_neig_gaus_sigma"] = 3.0
+        return q
+
+    def make_engine(self, name, p, S):
+        from tracking_amd import Engine
+        eng = Engine(self.classes[name], n_streams=S)
+        try:
+            self.apply(eng, name, p)
+        except capi.BgsError:
+            eng.close()
+            raise
+        return eng
+
+    def apply(self, eng, name, p):
+        eng.set_multilayer_params(**p)
+
+    def make_ref(self, name, p, H, W, stats):
+        return _MultiLayerRef(p, H, W, stats)
+
+
+ADAPTERS = [Kde(), Prati(), Texture(), Lb(), VuMeter(), Fuzzy(), T2f(), Eigen(), Imbs(), MultiLayer()]
 BY_CLASS = {name: ad for ad in ADAPTERS for name in ad.classes}
 MODELS = sorted(BY_CLASS)
 FAMILIES = {ad.family: sorted(ad.classes) for ad in ADAPTERS}
@@ -841,15 +953,17 @@ def describe(case):
 # One class per slice, so that the restatement's side of a slice stays near 3 s on the CPU; tests/test_fuzz_models_cpu.py holds every
 # slice to the conditions a class needs (accepted cases, entry points, geometries, resets, switches, refusals, lively masks).
 
-IMBS_SLICE_INDEX = 14  # the 14 classes of the first table keep the index, and with it the seeds, of their place in their sorted list
+# The 14 classes of the first table keep the index, and with it the seeds, of their place in their sorted list; a class that joined
+# later takes the next free index, whatever its place in the alphabet
+LATE_JOINERS = {im.CLASS_NAME: 14, ml.CLASS_NAME: 15}
 
 
 def _slices():
     out = []
-    first14 = [n for n in MODELS if n != im.CLASS_NAME]
-    assert len(first14) == IMBS_SLICE_INDEX
+    first14 = [n for n in MODELS if n not in LATE_JOINERS]
+    assert len(first14) == 14 and sorted(LATE_JOINERS.values()) == list(range(14, len(MODELS)))
     for name in MODELS:
-        k = IMBS_SLICE_INDEX if name == im.CLASS_NAME else first14.index(name)
+        k = LATE_JOINERS[name] if name in LATE_JOINERS else first14.index(name)
         fam = BY_CLASS[name].family
         small, small_parts, big, big_parts = SLICE_CASES.get(name, SLICE_CASES["*"])
         for size, is_big, first, count, parts in (("small", False, 700000 + 1000 * k, small, small_parts), ("big", True, 800000 + 1000 * k, big, big_parts)):
@@ -861,7 +975,7 @@ def _slices():
 
 # class -> (small cases, slices they are cut into, big cases, slices they are cut into); cut where a restatement is slow
 SLICE_CASES = {"*": (36, 1, 8, 1), "DPTexture": (28, 4, 6, 3), "LBAdaptiveSOM": (36, 2, 8, 2), "LBFuzzyAdaptiveSOM": (36, 2, 8, 4), "LBMixtureOfGaussians": (36, 1, 8, 2),
-               "T2FGMM_UV": (36, 1, 8, 2), im.CLASS_NAME: (36, 1, 8, 4)}
+               "T2FGMM_UV": (36, 1, 8, 2), im.CLASS_NAME: (36, 1, 8, 4), ml.CLASS_NAME: (36, 1, 8, 2)}
 SLICES = _slices()
 
 

@@ -60,7 +60,23 @@ def dark(rows, cols, T, seed):
     return np.stack(out)
 
 
-GENERATORS = {"static_block": static_block, "scripted": scripted, "dark": dark}
+def scaled_block(rows, cols, T, seed):
+    """static_block's scene with a block of a third of the frame each way (at least one pixel) that moves half its size a frame: a
+    frame of any size shows foreground and background.  The first five frames show another scene, which never comes back: with fast
+    rates its mode becomes a layer and then decays until the first form of the layer removal takes it, 14 frames later.  Not in the reference fixture; the models fuzz draws it."""
+    rs = np.random.RandomState(seed)
+    first, base = _texture(rs, rows, cols, 140, 250), _texture(rs, rows, cols, 40, 120)
+    bh, bw = max(rows // 3, 1), max(cols // 3, 1)
+    out = []
+    for t in range(T):
+        f = _noisy(rs, first if t < 5 else base, 2)
+        y, x = (t * max(bh // 2, 1)) % (rows - bh + 1), (t * max(bw // 2, 1)) % (cols - bw + 1)
+        f[y:y + bh, x:x + bw] = _noisy(rs, np.full((bh, bw, 3), 230), 3)
+        out.append(f)
+    return np.stack(out)
+
+
+GENERATORS = {"static_block": static_block, "scripted": scripted, "dark": dark, "scaled_block": scaled_block}
 
 
 def frames_of(gen, rows, cols, T, seed):

@@ -1,4 +1,4 @@
-"""The fuzz of the 15 reference-pinned model classes (tools/fuzz_parity.py `models`, tests/model_refs.py), checked without a GPU: the
+"""The fuzz of the 16 reference-pinned model classes (tools/fuzz_parity.py `models`, tests/model_refs.py), checked without a GPU: the
 old table still draws the cases it always drew, a draw is pure and deterministic, the fixed slices of tests/test_gpu_20_fuzz_models.py
 cover what each class needs, the checkers report planted defects, and the slices' inputs tell a restatement from the same restatement
 one parameter step away."""
@@ -54,14 +54,17 @@ def test_a_draw_is_pure_and_deterministic(monkeypatch):
 # ---- the slices ----------------------------------------------------------------------------------------------------------------------
 
 def test_the_slices_of_the_first_14_classes_keep_their_seeds():
-    """IndependentMultimodalBGS sorts into the middle of the class list; it takes index 14, and the 41 slices that were there before
-    it are the tuples they were (tests/golden/fuzz_model_slices.json, recorded from the table of 14)."""
+    """IndependentMultimodalBGS and MultiLayerBGS sort into the middle of the class list; they take indices 14 and 15, and the 41
+    slices that were there before them are the tuples they were (tests/golden/fuzz_model_slices.json, recorded from the table of 14)."""
     rec = [tuple([r[0], tuple(r[1])] + r[2:]) for r in json.load(open(os.path.join(GOLDEN, "fuzz_model_slices.json")))]
     assert len(rec) == 41 and len({r[1] for r in rec}) == 14
-    assert [s for s in mr.SLICES if s[1] != (mr.im.CLASS_NAME,)] == rec
+    late = {(mr.im.CLASS_NAME,), (mr.ml.CLASS_NAME,)}
+    assert [s for s in mr.SLICES if s[1] not in late] == rec
     mine = [s for s in mr.SLICES if s[1] == (mr.im.CLASS_NAME,)]
     assert [(s[2], s[3], s[4]) for s in mine] == [(False, 714000, 36), (True, 814000, 2), (True, 814002, 2), (True, 814004, 2), (True, 814006, 2)]
-    assert len({s[0] for s in mr.SLICES}) == len(mr.SLICES) == 46
+    mine = [s for s in mr.SLICES if s[1] == (mr.ml.CLASS_NAME,)]
+    assert [(s[2], s[3], s[4]) for s in mine] == [(False, 715000, 36), (True, 815000, 4), (True, 815004, 4)]
+    assert len({s[0] for s in mr.SLICES}) == len(mr.SLICES) == 49
 
 
 @functools.lru_cache(maxsize=None)
@@ -144,6 +147,25 @@ def test_slices_cover_what_the_class_needs(name):
         assert any(min(c["H"], c["W"]) < 3 for c, _ in every) and any(c["W"] == 3 for c, _ in every) and any(c["params"]["morphologicalFiltering"] for c, _ in every)
         assert {r["kind"] for c, _ in every for r in c["inputs"]} == set(ad.kinds)
         assert any(c["H"] * c["W"] > 4 * 256 and c["H"] * c["W"] % 256 for c, _ in every) and max(c["H"] * c["W"] for c, _ in every) <= 65 * 131
+    if ad.family == "multilayer":
+        every = [(c, st) for sid in mr.slices_of(name, False) + mr.slices_of(name, True) for c, _, st in restated(sid)[1]]
+        half = lambda c: c["params"]["pattern_neig_half_size"]
+        assert {half(c) for c, _ in every} == set(range(-1, 9)), "every half size"
+        assert any(half(c) == 8 and min(c["H"], c["W"]) < 8 for c, _ in every), "the largest halo on a frame smaller than it"
+        assert any(half(c) == 8 and c["W"] in (31, 32, 33) for c, _ in every), "the largest halo at the smoothing tile's edge"
+        assert {c["params"]["max_mode_num"] for c, _ in every} == {1, 2, 3, 4, 5}
+        assert any(c["params"]["texture_weight"] <= 0 for c, _ in every)
+        assert any(c["H"] == 1 and c["W"] > 1 for c, _ in every) and any(c["W"] == 1 and c["H"] > 1 for c, _ in every) and any(c["H"] == c["W"] == 1 for c, _ in every)
+        after = lambda c: c["params"]["detect_after"]
+        # a reset past detect_after sends one stream back to learning beside detecting ones: a call holds different launch keys
+        assert sum(c["S"] >= 2 and after(c) > 0 and any(st["resets"] and st["t"] > after(c) for st in c["steps"]) for c, _ in every) >= 3
+        assert sum(any(st["m"] == "clip" and st["n"] >= 2 and st["t"] < after(c) < st["t"] + st["n"] for st in c["steps"]) for c, _ in every) >= 2, "the switch inside a clip call"
+        total = {k: sum(st.get(k, 0) for _, st in every) for k in mr.ml.COUNTERS}
+        assert all(v > 0 for v in total.values()), total
+        for k in ("removal_second", "stale_decay_matched"):
+            assert sum(st.get(k, 0) > 0 for _, st in every) >= 3, k
+        assert {r["kind"] for c, _ in every for r in c["inputs"]} == set(ad.kinds)
+        assert all(c["redraws"] == 0 for c, _ in every)  # no draw is redrawn: parity is claimed on every input
     print("%s: restatement side of each slice, seconds: %s" % (name, {k: round(v, 1) for k, v in secs.items()}))
 
 

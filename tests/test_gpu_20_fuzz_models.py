@@ -1,6 +1,6 @@
-"""Fixed slices of the randomised differential run of the 15 reference-pinned model classes (tools/fuzz_parity.py `models`) inside the
-GPU suite: KDE, DPPratiMediod, DPTexture, the five lb/ models, VuMeter, the fuzzy integrals, T2FGMM_UM / _UV, DPEigenbackground and
-IndependentMultimodalBGS against their numpy restatements, through random geometries (one-row, narrow, ragged, several tiles), parameters (one the engine must
+"""Fixed slices of the randomised differential run of the 16 reference-pinned model classes (tools/fuzz_parity.py `models`) inside the
+GPU suite: KDE, DPPratiMediod, DPTexture, the five lb/ models, VuMeter, the fuzzy integrals, T2FGMM_UM / _UV, DPEigenbackground,
+IndependentMultimodalBGS and MultiLayerBGS against their numpy restatements, through random geometries (one-row, narrow, ragged, several tiles), parameters (one the engine must
 refuse among them), 1-3 streams, every entry point (host frames, submit / wait, device batches, two ranges on two HIP streams, clips of
 1-11 frames, a mix), independent stream resets and parameter switches.  Masks, backgrounds, packed words and the model at the end,
 each under its class's written contract (tests/model_refs.py).  tests/test_fuzz_models_cpu.py holds the slices to what a class needs.

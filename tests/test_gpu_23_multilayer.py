@@ -1,6 +1,8 @@
 """MultiLayerBGS (BGS_MULTILAYER, USTC_BGS type 23's class) on the GPU against the outputs of the reference's own
 jmo/CMultiLayerBGS.cpp (tests/golden/multilayer_ref.npz, read through tests/multilayer_numpy.py; nothing here needs the reference
-tree).  Every comparison is byte for byte: masks, backgrounds, the three state planes, and every other path against the host path.
+tree), and - at half sizes, launch keys and an emptied mode list the fixture does not hold - against the restatement, which
+tests/test_multilayer_cpu.py pins to the reference's code there.  Every comparison is byte for byte: masks, backgrounds, the three
+state planes, and every other path against the host path.
 No tolerance anywhere (DESIGN.md 5.11 names the two places where the contract is the fixture's stand-in)."""
 import functools
 import os
@@ -156,6 +158,118 @@ def test_neighbour_reads_and_blur_halo_stay_inside_a_stream_s_image():
             assert np.array_equal(d_bg.cpu().numpy()[s], runs[s][1][t]), (t, s)
     for s in range(2):
         same_state(state_of(eng, H * W, stream=s), runs[s][2], "stream %d" % s)
+    eng.close()
+
+
+def test_every_half_size_at_the_smoothing_tile_s_edges():
+    """pattern_neig_half_size 1..8 with a narrow and a wide Gaussian on frames of one pixel, one row, and one pixel past, one pixel
+    short of and two tiles across the 32 x 8 smoothing tile, all smaller than the largest halo in at least one direction.  Masks,
+    backgrounds and the smoothed distance plane equal the restatement's bit for bit, and every half size changes the plane against
+    the half size below it somewhere, so a kernel that ignored it could not pass."""
+    T, bits = 12, int(ml.load()["defaults"]["consts"][0])
+    differs = dict.fromkeys(range(1, 9), False)
+    for g, (H, W) in enumerate(((1, 1), (1, 40), (9, 33), (17, 31), (7, 65))):
+        frames = sc.frames_of("scripted", H, W, T, 61 + g)
+        for sigma in (0.5, 3.0):
+            below = ml.run(dict(ml.DEFAULTS, **ml.FAST, pattern_neig_half_size=0, pattern_neig_gaus_sigma=sigma), frames, bits)[0].state()[2]
+            for h in range(1, 9):
+                p = dict(ml.DEFAULTS, **ml.FAST, pattern_neig_half_size=h, pattern_neig_gaus_sigma=sigma)
+                m, want_masks, want_bgs = ml.run(p, frames, bits)
+                masks, bgs, st = host_run(p, frames)
+                where = (H, W, sigma, h)
+                assert np.array_equal(masks, want_masks), (where, int((masks != want_masks).sum()))
+                assert np.array_equal(bgs, want_bgs), where
+                want = m.state()[2]
+                assert st["dist"].tobytes() == want.tobytes(), (where, int((st["dist"].view(np.uint32) != want.view(np.uint32)).sum()))
+                differs[h] = differs[h] or st["dist"].tobytes() != below.tobytes()
+                below = st["dist"]
+    assert all(differs.values()), differs
+
+
+EMPTIED = dict(dict(ml.DEFAULTS, **ml.FAST), weight_updating_constant=5.0, max_mode_num=4, pattern_neig_half_size=2, bg_prob_threshold=0.1, bg_prob_updating_threshold=0.35,
+               min_noised_angle=0.05, shadow_rate=0.4, highlight_rate=2.0)
+
+
+def test_a_frame_that_empties_the_last_pixel_s_list_is_a_first_frame():
+    """weight_updating_constant 5 with a weight rate of 0.5 a frame drives weights below zero; a layered mode below 1e-4 is removed
+    even when it is the list's only one, and when that happens to the last pixel the reference's bFirstFrame is true again: a zero
+    mask and a zero distance map in the middle of a stream (the models fuzz found it at seed 715035)."""
+    frames = sc.frames_of("dark", 9, 33, 8, 5005245)
+    m, want_masks, want_bgs = ml.run(EMPTIED, frames, int(ml.load()["defaults"]["consts"][0]))
+    assert want_masks[3].any() and not want_masks[4].any() and want_masks[5].any()  # frame 4 is the one
+    masks, bgs, st = host_run(EMPTIED, frames)
+    assert [t for t in range(len(frames)) if not np.array_equal(masks[t], want_masks[t])] == []
+    assert np.array_equal(bgs, want_bgs)
+    for pl, want in zip(("order", "modes", "dist"), m.state()):
+        assert st[pl].tobytes() == want.tobytes(), pl
+    # and the frame's zero map is what the state plane holds right after it
+    eng = engine(EMPTIED)
+    for f in frames[:5]:
+        eng.process(f)
+    assert not eng.get_state("dist", (9 * 33,), np.float32).any()
+    eng.close()
+
+
+def test_one_call_holds_first_learning_and_detecting_streams():
+    """Three 16 x 33 streams with detect_after 4 join at steps 0, 3 and 6, and stream 0 is reset at step 8 and fed its clip again: the
+    calls at steps 6 and 8 hold a stream on its first frame, a learning one and a detecting one (three launch keys).  Batches up to
+    step 8, then clips of 3 frames: stream 2 passes detect_after inside a clip call, stream 0 at the start of one.  Every mask, background and packed
+    word (528 pixels are no multiple of 64) and the final state of all three streams equal each stream's own single-stream host run."""
+    torch = _torch()
+    H, W, S, U = 16, 33, 3, 15
+    n, Wd = H * W, (H * W + 63) // 64
+    p = dict(ml.DEFAULTS, **ml.FAST, detect_after=4)
+    join, reset_at = (0, 3, 6), 8
+    frames = [sc.frames_of("scripted", H, W, U, 71 + s) for s in range(S)]
+    start = list(join)
+    lives = {0: host_run(p, frames[0][:reset_at]), 1: host_run(p, frames[1][:U - join[1]]), 2: host_run(p, frames[2][:U - join[2]])}
+    again = host_run(p, frames[0][:U - reset_at])  # stream 0 after its reset
+    assert any(r[0][5:].any() for r in lives.values())  # detecting frames with foreground
+    eng = engine(p, n_streams=S)
+    eng.set_geometry(H, W, 3)
+
+    def check(u, s, fg, bg, bits):
+        run = again if s == 0 and u >= reset_at else lives[s]
+        want, wbg = run[0][u - start[s]], run[1][u - start[s]]
+        assert np.array_equal(fg, want), (u, s, int((fg != want).sum()))
+        assert np.array_equal(bg, wbg), (u, s)
+        assert np.array_equal(bits, words_of(want, Wd)), (u, s)
+
+    u = 0
+    while u < U:
+        if u == reset_at:
+            eng.reset_stream(0)
+            start[0] = reset_at
+        k = sum(1 for s in range(S) if join[s] <= u)
+        if u < 9:
+            if u in (6, 8):  # (first frame, past detect_after) differs between all three streams
+                assert len({(u - start[s] == 0, u - start[s] >= 4) for s in range(k)}) == 3
+            d_frames = torch.from_numpy(np.stack([frames[s][u - start[s]] for s in range(k)])).cuda()
+            d_fg = torch.full((k, H, W), 9, dtype=torch.uint8, device="cuda")
+            d_bg = torch.full((k, H, W, 3), 9, dtype=torch.uint8, device="cuda")
+            d_bits = torch.full((k, Wd), -1, dtype=torch.int64, device="cuda")
+            assert eng.process_batch_device(d_frames, d_fg, d_bg, d_bits, first=0, count=k) == BOTH
+            torch.cuda.synchronize()
+            fg, bg, bits = d_fg.cpu().numpy(), d_bg.cpu().numpy(), d_bits.cpu().numpy().view(np.uint64)
+            for s in range(k):
+                check(u, s, fg[s], bg[s], bits[s])
+            u += 1
+        else:
+            c = 3
+            d_frames = torch.from_numpy(np.stack([np.stack([frames[s][u + j - start[s]] for s in range(S)]) for j in range(c)])).cuda()  # [c][S][H][W][3]
+            d_fg = torch.full((c, S, H, W), 9, dtype=torch.uint8, device="cuda")
+            d_bg = torch.full((c, S, H, W, 3), 9, dtype=torch.uint8, device="cuda")
+            d_bits = torch.full((c, S, Wd), -1, dtype=torch.int64, device="cuda")
+            assert eng.process_clip_device(d_frames, c, d_fg, d_bg, d_bits) == [BOTH] * c
+            torch.cuda.synchronize()
+            fg, bg, bits = d_fg.cpu().numpy(), d_bg.cpu().numpy(), d_bits.cpu().numpy().view(np.uint64)
+            for j in range(c):
+                for s in range(S):
+                    check(u + j, s, fg[j, s], bg[j, s], bits[j, s])
+            u += c
+    for s, run in ((0, again), (1, lives[1]), (2, lives[2])):
+        assert eng.frames_seen(s) == U - start[s]
+        same_state(state_of(eng, n, stream=s), run[2], "stream %d" % s)
     eng.close()
 
 

@@ -1,6 +1,7 @@
 """MultiLayerBGS (USTC_BGS type 23's class) without a GPU: the numpy restatement against the fixture made from the reference's own
 jmo/CMultiLayerBGS.cpp, the conditions that make the fixture a fair yardstick (every branch counter above 0, expf mismatch counts 0),
-the C ABI (ids, bgs_multilayer_params, the refusals, the host-computed constants) and the host layer."""
+the same restatement against the reference's code on every run of the fixed slices of the models fuzz
+(tests/golden/multilayer_fuzz_ref.npz), the C ABI (ids, bgs_multilayer_params, the refusals, the host-computed constants) and the host layer."""
 import ctypes as C
 import functools
 import os
@@ -42,6 +43,54 @@ def test_restatement_reproduces_the_reference_fixture(case):
         assert modes.tobytes() == r["modes"].tobytes()
     assert dist.tobytes() == r["dist"].tobytes()
     assert not r["masks"][0].any()  # a stream's first frame: the zero mask
+
+
+def _fuzz_slices():
+    import model_refs as mr
+    return [s for s in mr.SLICES if s[1] == (ml.CLASS_NAME,)]
+
+
+@pytest.mark.parametrize("classes,big,first,count", [s[1:] for s in _fuzz_slices()], ids=[s[0] for s in _fuzz_slices()])
+def test_restatement_reproduces_the_reference_where_the_fuzz_takes_it(classes, big, first, count):
+    """tests/golden/multilayer_fuzz_ref.npz: the reference's own code on every stream of every accepted case of the fixed slices of the
+    models fuzz, run straight through with the case's parameters (tools/ref_fixtures/multilayer/make_fixture.py), as CRCs of the
+    input, the masks, the backgrounds and the three state planes after the last frame."""
+    import model_refs as mr
+    z = np.load(os.path.join(HERE, "golden", "multilayer_fuzz_ref.npz"))
+    rec = {(int(seed), int(s)): [int(c) for c in crcs] for (seed, s), crcs in zip(z["runs"], z["crcs"])}
+    assert len(rec) == len(z["runs"]) and (z["expf"][:, 0] > 0).all()
+    ad = mr.BY_CLASS[ml.CLASS_NAME]
+    bits = int(ml.load()["defaults"]["consts"][0])
+    ran = 0
+    for case in mr.slice_cases(first, count, classes, big):
+        if ad.refusal(ml.CLASS_NAME, case["params"]) is not None:
+            assert not any(seed == case["seed"] for seed, _ in rec)
+            continue
+        for s, frames in enumerate(mr.build_inputs(case)):
+            want = rec[case["seed"], s]
+            assert ml.crc(frames) == want[0], (case["seed"], s, "the input")
+            m, masks, bgs = ml.run(case["params"], frames, bits)
+            got = [ml.crc(masks), ml.crc(bgs)] + [ml.crc(a) for a in m.state()]
+            assert got == want[1:], (case["seed"], s, "masks, backgrounds, order, modes, dist", [a == b for a, b in zip(got, want[1:])], case["params"])
+            ran += 1
+    assert ran >= count // 2
+    if (big, first) == (False, 715000):  # the file holds the runs of the three slices and nothing else
+        runs = sum(c["S"] for sl in _fuzz_slices() for c in mr.slice_cases(sl[3], sl[4], sl[1], sl[2]) if ad.refusal(ml.CLASS_NAME, c["params"]) is None)
+        assert runs == len(rec)
+
+
+def test_a_frame_that_empties_the_last_pixel_s_list_is_a_first_frame_again():
+    """weight_updating_constant 5 with a fast weight rate drives a layered mode's weight below zero, the
+    first form of the layer removal takes the list's only mode, and when the last pixel is among those pixels the frame gets the
+    zero mask in the middle of a stream.  Run (715035, stream 0) of the fuzz fixture is such a clip: the masks are the reference's."""
+    import model_refs as mr
+    case = mr.slice_cases(715035, 1, (ml.CLASS_NAME,), False)[0]
+    assert case["params"]["weight_updating_constant"] == 5.0 and not any(st["resets"] for st in case["steps"])
+    m, masks, _ = ml.run(case["params"], mr.build_inputs(case)[0], int(ml.load()["defaults"]["consts"][0]))
+    assert masks[3].any() and not masks[4].any() and masks[5].any()
+    z = np.load(os.path.join(HERE, "golden", "multilayer_fuzz_ref.npz"))
+    i = [tuple(r) for r in z["runs"].tolist()].index((715035, 0))
+    assert ml.crc(masks) == int(z["crcs"][i][1])
 
 
 def test_the_fixture_holds_the_cases_the_class_needs():

@@ -3,8 +3,8 @@ the engine accepts, number of streams, and a random mix of entry points (host fr
 mask, every background the class delivers and - where the helpers know the model - the state at the end must match.
 
 Two tables.  The default one (`ALL`) holds the classes oracle/bgs_oracle.c restates and compares the engine with that oracle.
-`models` holds the 15 classes that are pinned to reference-built fixtures (KDE, DPPratiMediod, DPTexture, the five lb/ models, VuMeter,
-the fuzzy integrals, T2FGMM_UM / _UV, DPEigenbackground, IndependentMultimodalBGS) and compares the engine with their numpy restatements through the adapters of
+`models` holds the 16 classes that are pinned to reference-built fixtures (KDE, DPPratiMediod, DPTexture, the five lb/ models, VuMeter,
+the fuzzy integrals, T2FGMM_UM / _UV, DPEigenbackground, IndependentMultimodalBGS, MultiLayerBGS) and compares the engine with their numpy restatements through the adapters of
 tests/model_refs.py, each under its class's written contract.
 
 A case is drawn without a GPU - draw_case(rng, seed, table) returns its description - and then run: run_case(case).

@@ -1,5 +1,7 @@
-"""Writes tests/golden/multilayer_ref.npz from the reference's own model code (README.md here).
-usage: make_fixture.py /path/to/libmlref.so [out.npz]"""
+"""Writes tests/golden/multilayer_ref.npz and tests/golden/multilayer_fuzz_ref.npz from the reference's own model code (README.md here).
+The second file pins the restatement where the models fuzz takes it: every stream of every accepted case of the fixed MultiLayerBGS
+slices of tests/model_refs.py, run straight through (no reset) with the case's parameters, as CRCs.
+usage: make_fixture.py /path/to/libmlref.so [out.npz [fuzz_out.npz]]"""
 import ctypes as C
 import os
 import sys
@@ -7,6 +9,7 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, ROOT)  # tests/model_refs.py names the class ids of tracking_amd.capi
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import multilayer_numpy as ml  # noqa: E402
 import multilayer_scenes as sc  # noqa: E402
@@ -47,6 +50,38 @@ def run_reference(lib, params, frames):
     return masks, bgs, order, modes, dist, consts, counts
 
 
+def fuzz_runs():
+    """(case, stream, frames) of every accepted case of the fixed slices; tests/test_multilayer_cpu.py draws the same."""
+    import model_refs as mr
+    ad = mr.BY_CLASS[ml.CLASS_NAME]
+    for _, classes, big, first, count in mr.SLICES:
+        if classes != (ml.CLASS_NAME,):
+            continue
+        for case in mr.slice_cases(first, count, classes, big):
+            if ad.refusal(ml.CLASS_NAME, case["params"]) is None:
+                for s, frames in enumerate(mr.build_inputs(case)):
+                    yield case, s, frames
+
+
+def write_fuzz_fixture(lib, out):
+    """Per run: (seed, stream), the CRC-32 of the input, the masks, the backgrounds, `order`, `modes` and `dist` after the last frame,
+    and the expf call / libm-differs counts.  The counts are recorded, not conditioned on: the model gets the correctly rounded value
+    either way."""
+    runs, crcs, expf, differ = [], [], [], 0
+    for case, s, frames in fuzz_runs():
+        masks, bgs, order, modes, dist, consts, counts = run_reference(lib, case["params"], frames)
+        ref = [ml.crc(frames), ml.crc(masks), ml.crc(bgs), ml.crc(order), ml.crc(modes), ml.crc(dist)]
+        m, rm, rb = ml.run(case["params"], frames, int(consts[0]))
+        mine = [ref[0], ml.crc(rm), ml.crc(rb)] + [ml.crc(a) for a in m.state()]
+        if mine != ref:
+            differ += 1
+            print("seed %d stream %d %dx%d T=%d: restatement differs (input masks bg order modes dist) %s %s" % (case["seed"], s, case["H"], case["W"], case["T"],
+                  [a == b for a, b in zip(mine, ref)], case["params"]))
+        runs.append((case["seed"], s)), crcs.append(ref), expf.append([int(counts[0]), int(counts[1])])
+    np.savez_compressed(out, runs=np.array(runs, np.int64), crcs=np.array(crcs, np.uint32), expf=np.array(expf, np.int64))
+    print("%s: %d runs, %d where the restatement differs, %d with an expf call where libm differs, %d bytes" % (out, len(runs), differ, sum(e[1] > 0 for e in expf), os.path.getsize(out)))
+
+
 def main():
     lib = C.CDLL(sys.argv[1])
     out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "tests", "golden", "multilayer_ref.npz")
@@ -83,6 +118,7 @@ def main():
     print("counters over the fixture:", total)
     np.savez_compressed(out, **z)
     print(out, os.path.getsize(out), "bytes")
+    write_fuzz_fixture(lib, sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "tests", "golden", "multilayer_fuzz_ref.npz"))
 
 
 if __name__ == "__main__":

@@ -9,6 +9,7 @@
 struct MlState : FamilyState {
   DevPtr<uint32_t> model;  // [S][kMlPlanes][n]
   DevPtr<float> raw, dist; // [S][n] each
+  DevPtr<uint32_t> empty_last;  // [S]: the reference's bFirstFrame of the stream's latest frame (kernel_multilayer.h)
   float k[2 * bgs::kMlMaxHalf + 1] = {1.f};
   int half = 0;
   float min_sine = 0.f;
@@ -66,6 +67,7 @@ int ml_allocate(bgs_engine* e) {
   if (rc) return rc;
   DMALLOC(st.raw, S * n * 4);
   DMALLOC(st.dist, S * n * 4);
+  DMALLOC(st.empty_last, S * 4);
   st.half = p.pattern_neig_half_size > 0 ? p.pattern_neig_half_size : 0;  // below 0: no smoothing; 0: GaussianBlur copies a 1 x 1 kernel
   st.k[0] = 1.f;  // either way the one tap 1.0f leaves every value as it is
   if (st.half > 0) gaussian_kernel_f32(2 * st.half + 1, p.pattern_neig_gaus_sigma, st.k);
@@ -84,7 +86,7 @@ bgs::MlArgs ml_args(const bgs_engine* e, int first, const uint8_t* d_frames, uin
   const size_t f = (size_t)first, n = e->n;
   bgs::MlArgs a{};
   a.cur = d_frames, a.fg = d_fg, a.bgout = d_bg;
-  a.model = st.model + f * bgs::kMlPlanes * n, a.raw = st.raw + f * n, a.dist = st.dist + f * n;
+  a.model = st.model + f * bgs::kMlPlanes * n, a.raw = st.raw + f * n, a.dist = st.dist + f * n, a.empty_last = st.empty_last + f;
   a.n = (uint32_t)n, a.rows = e->rows, a.cols = e->cols;
   a.max_modes = p.max_mode_num, a.first = e->seen[first] == 0, a.texture = p.texture_weight > 0;
   // the wrapper's status (MultiLayerBGS.cpp:71-108, :156-188) and the switch at detect_after (:200-218)

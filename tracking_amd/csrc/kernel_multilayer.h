@@ -33,9 +33,10 @@ struct MlArgs {
   uint8_t *fg, *bgout;  // [count][n], [count][n][3] (both nullable)
   uint32_t* model;      // [count][kMlPlanes][n]
   float *raw, *dist;    // [count][n]: this frame's distances, the smoothed map
+  uint32_t* empty_last; // [count]: bFirstFrame as the pixel loop leaves it, written by the model kernel, read by the smoothing kernel
   uint32_t n;
   int rows, cols;
-  int max_modes, learn, first, texture;  // m_nMaxLBPModeNum; !m_disableLearning; the streams' first frame; m_fTextureWeight > 0
+  int max_modes, learn, first, texture;  // m_nMaxLBPModeNum; !m_disableLearning; the streams' first frame (host side only); m_fTextureWeight > 0
   float tw, wc, percent, thr, upd_thr, offset, min_sine, min_angle, shadow, high;
   float mrate, m1, wrate, init_w;        // m_fModeUpdatingLearnRate, 1 - it, m_fWeightUpdatingLearnRate, m_fLowInitialModeWeight
   int half;                              // taps = 2 half + 1 (0: the map is copied)
@@ -253,6 +254,10 @@ __global__ __launch_bounds__(kBlock) void ml_model_kernel(const MlArgs a) {
     ml_renumber_layers(rank, lay);
   }
 
+  // bFirstFrame (:456, :754) is assigned per pixel and ends as "the last pixel's list was empty here".  That is every stream's
+  // first frame, and any later frame on which the removal above took the last pixel's only mode.
+  if (p == a.n - 1) a.empty_last[k] = num == 0 ? 1u : 0u;
+
   float raw = 0.f;
   int wslot = -1;  // the slot whose colour and pattern planes are rewritten
   float npat[6], nbg[3];
@@ -449,7 +454,7 @@ __global__ __launch_bounds__(kBlock) void ml_smooth_kernel(const MlArgs a) {
   const int bx = blockIdx.x * W, by = blockIdx.y * H, h = a.half, taps = 2 * h + 1, tid = threadIdx.x;
   const int tx = tid % W, ty = tid / W, x = bx + tx, y = by + ty;
   const bool inside = x < a.cols && y < a.rows;
-  if (a.first) {  // bFirstFrame: a zero mask and a zero map
+  if (a.empty_last[k]) {  // bFirstFrame: a zero mask and a zero map (uniform over the block)
     if (inside) {
       a.dist[k * n + (size_t)y * a.cols + x] = 0.f;
       if (a.fg) a.fg[k * n + (size_t)y * a.cols + x] = 0;
