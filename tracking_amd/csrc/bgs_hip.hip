@@ -25,6 +25,7 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <string>
 #include <atomic>
 #include <vector>
@@ -113,6 +114,100 @@ struct Family;  // below
 struct FamilyState {
   virtual ~FamilyState() = default;
 };
+
+template <class T>
+void dfree(T*& p) {
+  if (p) (void)hipFree(p), p = nullptr;
+}
+
+// A device buffer owned by a family's state struct: freed with the struct.  A chunked model (model_allocate) is not hipFree's to
+// release: free_all nulls `p` through VmmRange::owner and releases the range BEFORE the state is destroyed.
+template <class T>
+struct DevPtr {
+  T* p = nullptr;
+  DevPtr() = default;
+  DevPtr(DevPtr&& o) noexcept : p(o.p) { o.p = nullptr; }
+  DevPtr& operator=(DevPtr&& o) noexcept {
+    std::swap(p, o.p);
+    return *this;
+  }
+  DevPtr(const DevPtr&) = delete;
+  DevPtr& operator=(const DevPtr&) = delete;
+  ~DevPtr() { reset(); }
+  void reset() { dfree(p); }
+  operator T*() const { return p; }
+};
+
+#include "frame_history.h"
+
+// The frame history ring of FrameDifference (2 slots) and WeightedMovingMean / Variance (3): the frame a stream receives at position
+// `pos` lives in slot[pos % nring] + `off`, the stream's bytes into a slot (frame_history.h has the arithmetic).  Every engine has one
+// (its classes' ring; the generic clip and host paths drive it), every group ONE for its fused classes.
+struct FrameHistory {
+  DevPtr<uint8_t> slot[3];
+  int nring = 0;  // 0: the owner's classes keep no history
+  enum Mode { kPrivate, kBorrowed, kClip } mode = kPrivate;  // kBorrowed: BGS_OPT_BORROW_FRAMES, the caller's previous d_frames are the history, no copies
+  const uint8_t* lent[2] = {nullptr, nullptr};               // kBorrowed / kClip: frames t-1 and t-2
+
+  // For the length of one call, whatever the owner's mode: Scope(h) - the call keeps private copies (the host entry points: their staging
+  // buffer is reused every frame); Scope(h, h1, h2) - its history is these two frames (a clip call).  Restored on every return path.
+  struct Scope {
+    FrameHistory& h;
+    const Mode mode;
+    const uint8_t* const lent[2];
+    explicit Scope(FrameHistory& h_) : h(h_), mode(h_.mode), lent{h_.lent[0], h_.lent[1]} { h.mode = kPrivate; }
+    Scope(FrameHistory& h_, const uint8_t* h1, const uint8_t* h2) : Scope(h_) { h.mode = kClip, h.lent[0] = h1, h.lent[1] = h2; }
+    ~Scope() { h.mode = mode, h.lent[0] = lent[0], h.lent[1] = lent[1]; }
+    Scope(const Scope&) = delete;
+  };
+
+  void release() { slot[0].reset(), slot[1].reset(), slot[2].reset(); }
+  // the question of both lock-step refusals: the caller's buffers hold one frame of ALL streams, a launch must cover them all at one age
+  bool lockstep_only() const { return nring && mode == kBorrowed; }
+  uint8_t* at(int i, size_t off) const { return i == kNoSlot ? nullptr : slot[i] + off; }
+  // where the frame received at `pos` is kept; the k-th last frame before it of a stream that has seen t frames; the state planes
+  // prev1 / prev2.  Null where there is no such slot (no ring, warm-up, another plane)
+  uint8_t* keep_at(int64_t pos, size_t off) const { return at(nring ? history_cur(nring, pos) : kNoSlot, off); }
+  const uint8_t* prev(int64_t pos, int64_t t, int k, size_t off) const { return at(history_prev(nring, pos, t, k), off); }
+  const uint8_t* plane(int64_t pos, int64_t t, const char* name, size_t off) const { return at(history_plane(nring, pos, t, name), off); }
+  // The history of one launch over `bytes` of frames at d_frames, received at `pos` by streams that have seen t: the frame is copied
+  // into its slot unless it is there already (the host path uploads into it) or the history is lent; then the lent pair moves on.
+  struct Frames { const uint8_t *cur, *h1, *h2; };
+  hipError_t resolve(int64_t pos, int64_t t, size_t off, size_t bytes, const uint8_t* d_frames, hipStream_t s, Frames* f) {
+    *f = {d_frames, nring ? lent[0] : nullptr, nring ? lent[1] : nullptr};
+    if (!nring) return hipSuccess;
+    if (mode != kPrivate) return lent[1] = lent[0], lent[0] = d_frames, hipSuccess;
+    uint8_t* own = keep_at(pos, off);
+    *f = {own, prev(pos, t, 1, off), prev(pos, t, 2, off)};
+    return own == d_frames ? hipSuccess : hipMemcpyAsync(own, d_frames, bytes, hipMemcpyDeviceToDevice, s);
+  }
+};
+
+// Kernel timing: one event pair per timed launch (Timed, below).  Bounded: a caller that leaves this measurement aid on must not grow the list forever.
+struct LaunchTimer {
+  bool on = false;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+  bool full() const { return events.size() >= 16384; }
+  void enable(bool v) {
+    for (auto& ev : events) (void)hipEventDestroy(ev.first), (void)hipEventDestroy(ev.second);
+    events.clear(), on = v;
+  }
+  ~LaunchTimer() { enable(false); }
+  // ms of the first `cap` pairs: their number, their sum, each one into `each` when given.  wait: every pair's end event is waited for
+  // and a HIP error ends the walk (the engine's calls); else the device is drained and a pair that cannot be read counts as 0 ms
+  hipError_t read(bool wait, int64_t cap, float* each, int64_t* n, double* total) const {
+    for (*n = 0, *total = 0; *n < cap && *n < (int64_t)events.size(); ++*n) {
+      const auto& ev = events[(size_t)*n];
+      float ms = 0;
+      hipError_t er = wait ? hipEventSynchronize(ev.second) : hipSuccess;
+      if (er == hipSuccess) er = hipEventElapsedTime(&ms, ev.first, ev.second);
+      if (wait && er != hipSuccess) return er;
+      if (each) each[*n] = ms;
+      *total += ms;
+    }
+    return hipSuccess;
+  }
+};
 }
 
 // One virtual address range backed by separately created physical chunks (hipMemAddressReserve + hipMemCreate x n + hipMemMap): how
@@ -126,9 +221,10 @@ struct VmmRange {
 
 // What is here is what the generic code below uses itself.  A family's model - buffers, tables, per-stream counters - is the state
 // struct of its engine_*.h behind `model`; what stays is
-//  - geometry, the per-stream bookkeeping every family shares (seen, rpos, last_flags), the host path (HostPath), timing, ingest, cc scratch, vmm;
-//  - the frame history ring: process_clip_run, bgs_process and bgs_submit read and write it themselves, so it is a service of the
-//    generic code that the history classes use, not their private state;
+//  - geometry, the per-stream bookkeeping every family shares (seen, rpos, last_flags), the host path (HostPath), timing (LaunchTimer), ingest, cc scratch, vmm;
+//  - `hist`, the frame history ring (FrameHistory, above): process_clip_run and the host entry points say for the length of a call where its
+//    history comes from (FrameHistory::Scope) and upload into its slots, so it is a service of the generic code that the history classes
+//    use (ring_run asks it for the frames of a launch), not their private state; a group holds the same struct;
 //  - `counter`: the families that have a learning phase counted in frames share it with that one meaning, and bgs_reset_stream clears it;
 //  - p and the class parameter blocks (one member per ParamBlock constant of an engine_*.h, which says who owns it and whether it
 //    is live or frozen once the geometry is set): all may be set before the geometry is known, i.e. before there is a state;
@@ -149,15 +245,9 @@ struct bgs_engine {
   int rows = 0, cols = 0, ch = 0;
   size_t n = 0;  // pixels per stream; 0 until the geometry is known
   std::vector<int64_t> seen, counter;
-  std::vector<int64_t> rpos;         // frame history ring: where a stream's NEXT frame goes (ring[rpos % nring]); survives bgs_reset_stream, so that streams fed in the same calls keep sharing launches
+  std::vector<int64_t> rpos;         // frame history ring: the position of a stream's NEXT frame (hist); survives bgs_reset_stream, so that streams fed in the same calls keep sharing launches
   std::vector<uint32_t> last_flags;  // out_flags of each stream's last frame (bgs_stream_flags)
-
-  // frame history ring (FD: 2 slots, WMM/WMV: 3): frame t of stream s lives in ring[t % nring] + s*n*ch
-  uint8_t* ring[3] = {nullptr, nullptr, nullptr};
-  int nring = 0;
-  bool borrow = false;               // device path: history = the caller's previous d_frames, no copies
-  bool borrow_in_clip = false;       // set by process_clip: frames of the clip serve as history, for the range of that call
-  const uint8_t* borrowed[2] = {nullptr, nullptr};
+  FrameHistory hist;                 // FD: 2 slots, WMM / WMV: 3, every other class: none
 
   struct Knobs {
     int xcd_swizzle = 1;             // XCD-aware block order (kernel_mog2.h): 0 off, 1 model kernels (MOG2, MOG1, dp), 2 also the byte-stream kernels
@@ -186,9 +276,7 @@ struct bgs_engine {
   void* cc_work = nullptr;            // its device scratch: workspace | boxes | moments | count
   int cc_cap = 0;                     // boxes the scratch has room for
 
-  // dominant-kernel timing
-  bool timing = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+  LaunchTimer timer;                  // dominant-kernel timing
   const char* kernel_name = "";
 };
 
@@ -297,29 +385,6 @@ uint32_t any_flags(const bgs_engine* e, int first, int count) {
 
 bool always(const bgs_engine*) { return true; }  // needs_byte_mask of the classes whose mask is finished by a stencil pass
 
-template <class T>
-void dfree(T*& p) {
-  if (p) (void)hipFree(p), p = nullptr;
-}
-
-// A device buffer owned by a family's state struct: freed with the struct.  A chunked model (model_allocate) is not hipFree's to
-// release: free_all nulls `p` through VmmRange::owner and releases the range BEFORE the state is destroyed.
-template <class T>
-struct DevPtr {
-  T* p = nullptr;
-  DevPtr() = default;
-  DevPtr(DevPtr&& o) noexcept : p(o.p) { o.p = nullptr; }
-  DevPtr& operator=(DevPtr&& o) noexcept {
-    std::swap(p, o.p);
-    return *this;
-  }
-  DevPtr(const DevPtr&) = delete;
-  DevPtr& operator=(const DevPtr&) = delete;
-  ~DevPtr() { reset(); }
-  void reset() { dfree(p); }
-  operator T*() const { return p; }
-};
-
 // the state of e's family: made by its allocate, typed again by the one-line accessor of its engine_*.h
 template <class St>
 St& make_state(bgs_engine* e) {
@@ -366,19 +431,21 @@ void** raw_of(DevPtr<T>& d) { return (void**)&d.p; }
     if (rc__) return rc__;                                \
   } while (0)
 
+// the launches between its construction and its destruction on s, as one pair of the timer (an engine's: with the kernel's name)
 struct Timed {
-  bgs_engine* e;
+  LaunchTimer& tm;
   hipStream_t s;
   hipEvent_t a = nullptr, b = nullptr;
-  Timed(bgs_engine* e_, hipStream_t s_, const char* name, bool enable = true) : e(e_), s(s_) {
+  Timed(LaunchTimer& tm_, hipStream_t s_, bool enable = true) : tm(tm_), s(s_) {
+    if (enable && tm.on && !tm.full() && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) (void)hipEventRecord(a, s);
+  }
+  Timed(bgs_engine* e, hipStream_t s_, const char* name, bool enable = true) : Timed(e->timer, s_, enable) {
     if (enable) e->kernel_name = name;
-    // bounded: timing is a measurement aid, a caller that leaves it on must not grow the list forever
-    if (enable && e->timing && e->events.size() < 16384 && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) (void)hipEventRecord(a, s);
   }
   ~Timed() {
     if (a && b) {
       (void)hipEventRecord(b, s);
-      e->events.emplace_back(a, b);
+      tm.events.emplace_back(a, b);
     }
   }
 };
@@ -551,13 +618,11 @@ void free_all(bgs_engine* e) {
     vmm_free(e->vmm);
   }
   e->model.reset();
-  for (auto& r : e->ring) dfree(r);
+  e->hist.release();
   dfree(e->cc_work), e->cc_cap = 0;
   dfree(e->pack_fg), e->pack_fg_bytes = 0;
   e->last_fg_stream = -1;
   e->host.release();
-  for (auto& ev : e->events) (void)hipEventDestroy(ev.first), (void)hipEventDestroy(ev.second);
-  e->events.clear();
 }
 
 int check_params(bgs_algo algo, const bgs_params& p) {
@@ -565,19 +630,22 @@ int check_params(bgs_algo algo, const bgs_params& p) {
   return f->check ? f->check(algo, p) : BGS_OK;
 }
 
-int allocate(bgs_engine* e, int rows, int cols, int ch) {
+// the refusals of a geometry, made before the device is opened: those of every class, then the family's (an engine's own; a group's fused SigmaDelta)
+int check_geometry(const Family* fam, bgs_algo algo, int rows, int cols, int ch) {
   if (rows <= 0 || cols <= 0) return fail(BGS_ERR_INVALID, "bad geometry %dx%d", rows, cols);
   if (ch != 1 && ch != 3) return fail(BGS_ERR_UNSUPPORTED, "channels must be 1 or 3, got %d", ch);
-  if (e->fam->check_geometry) {
-    int rc = e->fam->check_geometry(e->algo, rows, cols, ch);
-    if (rc) return rc;
-  }
+  return fam && fam->check_geometry ? fam->check_geometry(algo, rows, cols, ch) : BGS_OK;
+}
+
+int allocate(bgs_engine* e, int rows, int cols, int ch) {
+  int rc = check_geometry(e->fam, e->algo, rows, cols, ch);
+  if (rc) return rc;
   HIP_TRY(hipSetDevice(e->device));
   e->rows = rows, e->cols = cols, e->ch = ch, e->n = (size_t)rows * cols;
   HIP_TRY(e->host.sync.open());  // e->stream()
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, e->device) == hipSuccess && prop.multiProcessorCount > 0) e->n_cu = prop.multiProcessorCount;
-  int rc = e->fam->allocate(e);
+  rc = e->fam->allocate(e);
   if (rc) return rc;
   // Whatever allocation enqueued on e->stream() (statistics counters, poison fills) is complete before the caller's first
   // launch - which may come on ANOTHER stream (device path) that nothing else orders against this one.
@@ -652,7 +720,7 @@ int process_range(bgs_engine* e, int first, int count, const uint8_t* d_frames, 
     int b = a + 1;
     const uint64_t key = launch_key(e, a);
     while (b < first + count && launch_key(e, b) == key) ++b;
-    if (e->borrow && (a != first || b != first + count) && e->nring && !e->borrow_in_clip)
+    if (e->hist.lockstep_only() && (a != first || b != first + count))
       return fail(BGS_ERR_INVALID, "borrowed frame history needs streams in lock-step (streams %d and %d are not)", a, b);
     const size_t o = (size_t)(a - first) * e->n;
     uint32_t fl = 0;
@@ -726,67 +794,55 @@ int process_clip(bgs_engine* e, int first, int count, int nframes, const uint8_t
   return BGS_OK;
 }
 
+// `fuse` frames of a clip as ONE launch of the family (Family::clip_fused), which needs the streams of the run in lock-step
+int clip_fused_run(bgs_engine* e, int first, int count, int fuse, size_t slab, const uint8_t* fr, uint8_t* fg, uint8_t* bg, uint64_t* bits, hipStream_t s, uint32_t* out_flags) {
+  const int64_t seen = e->seen[first];
+  for (int i = first; i < first + count; ++i)
+    if (e->seen[i] != seen) return fail(BGS_ERR_INVALID, "streams %d and %d are not in lock-step (%lld vs %lld frames)", first, i, (long long)seen, (long long)e->seen[i]);
+  HIP_TRY(hipSetDevice(e->device));
+  uint32_t fl = 0;
+  int rc = e->fam->clip_fused(e, first, count, fuse, slab, fr, fg, bg, bits, s, &fl);
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  for (int i = first; i < first + count; ++i) e->seen[i] += fuse, e->rpos[i] += fuse, e->last_flags[i] = fl;
+  for (int j = 0; j < fuse && out_flags; ++j) out_flags[j] = fl;
+  return BGS_OK;
+}
+
 // `count` streams of one age starting at `first`, inside a slab of `slab_count` streams per frame
 int process_clip_run(bgs_engine* e, int first, int count, int slab_count, int nframes, const uint8_t* d_frames, uint8_t* d_fg, uint8_t* d_bg, uint64_t* d_bits,
                      hipStream_t s, uint32_t* out_flags) {
-  const size_t npix = e->n * count, C = (size_t)e->ch;
+  const size_t npix = e->n * count, C = (size_t)e->ch, offb = e->n * (size_t)first * C;
   const size_t slab = e->n * slab_count;  // pixels from one frame of the clip to the next
   const size_t words = slab / 64;
   const Family& fam = *e->fam;
   const bool fuse_ok = e->knob.clip_fuse && fam.clip_fused && (!fam.clip_fusable || fam.clip_fusable(e));
   // FrameDifference / WeightedMoving*: frame t needs frames t-1 (t-2).  A per-frame call copies its frame into the engine's ring; inside
   // a clip the earlier frames of the clip ARE that history, so only the last one (two) are copied into the ring, once, at the end.
-  const bool ring_clip = e->nring > 0 && !e->borrow && nframes >= 2;
-  const uint8_t* saved_borrowed[2] = {e->borrowed[0], e->borrowed[1]};
-  const int64_t ring_t0 = e->seen[first], ring_p0 = e->rpos[first];
-  if (ring_clip) {
-    const int R = e->nring;
-    const size_t offb = e->n * (size_t)first * C;
-    e->borrow = true, e->borrow_in_clip = true;
-    e->borrowed[0] = ring_t0 >= 1 ? e->ring[(ring_p0 + R - 1) % R] + offb : nullptr;
-    e->borrowed[1] = (ring_t0 >= 2 && R == 3) ? e->ring[(ring_p0 + R - 2) % R] + offb : nullptr;
-  }
+  FrameHistory& h = e->hist;
+  const bool ring_clip = h.nring > 0 && h.mode == FrameHistory::kPrivate && nframes >= 2;
+  const int64_t t0 = e->seen[first], p0 = e->rpos[first];
+  std::optional<FrameHistory::Scope> lend;
+  if (ring_clip) lend.emplace(h, h.prev(p0, t0, 1, offb), h.prev(p0, t0, 2, offb));
   auto end_ring_clip = [&](int done) -> int {  // `done` frames of the clip went through: leave the ring as per-frame calls would have
-    if (!ring_clip) return BGS_OK;
-    e->borrow = false, e->borrow_in_clip = false;
-    e->borrowed[0] = saved_borrowed[0], e->borrowed[1] = saved_borrowed[1];
-    const int R = e->nring;
-    const size_t offb = e->n * (size_t)first * C;
-    for (int k = 1; k < R; ++k) {
-      const int j = done - k;  // clip frame j is the k-th last one
-      if (j < 0) break;        // older ones are in the ring already
-      HIP_TRY(hipMemcpyAsync(e->ring[(ring_p0 + j) % R] + offb, d_frames + (size_t)j * slab * C, npix * C, hipMemcpyDeviceToDevice, s));
-    }
+    HistoryCopy plan[2];
+    const int copies = ring_clip ? history_clip_plan(h.nring, p0, done, plan) : 0;
+    for (int i = 0; i < copies; ++i) HIP_TRY(hipMemcpyAsync(h.slot[plan[i].slot] + offb, d_frames + (size_t)plan[i].frame * slab * C, npix * C, hipMemcpyDeviceToDevice, s));
     return BGS_OK;
   };
-  int t = 0;
-  while (t < nframes) {
+  for (int t = 0, fuse; t < nframes; t += fuse) {
     const int left = nframes - t;
-    const int fuse = !fuse_ok ? 1 : left >= 8 ? 8 : left >= 4 ? 4 : left >= 2 ? 2 : 1;
+    fuse = !fuse_ok ? 1 : left >= 8 ? 8 : left >= 4 ? 4 : left >= 2 ? 2 : 1;
     const uint8_t* fr = d_frames + (size_t)t * slab * C;
     uint8_t* fg = d_fg ? d_fg + (size_t)t * slab : nullptr;
     uint8_t* bg = d_bg ? d_bg + (size_t)t * slab * (size_t)bg_channels(e) : nullptr;
     uint64_t* bits = d_bits ? d_bits + (size_t)t * words : nullptr;
-    if (fuse == 1) {
-      int rc = process_range(e, first, count, fr, fg, bg, bits, s, out_flags ? out_flags + t : nullptr);
-      if (rc) {
-        (void)end_ring_clip(t);
-        return rc;
-      }
-    } else {
-      const int64_t seen = e->seen[first];
-      for (int i = first; i < first + count; ++i)
-        if (e->seen[i] != seen) return fail(BGS_ERR_INVALID, "streams %d and %d are not in lock-step (%lld vs %lld frames)", first, i, (long long)seen, (long long)e->seen[i]);
-      HIP_TRY(hipSetDevice(e->device));
-      uint32_t fl = 0;
-      int rc = fam.clip_fused(e, first, count, fuse, slab, fr, fg, bg, bits, s, &fl);
-      if (rc) return rc;
-      HIP_TRY(hipGetLastError());
-      for (int i = first; i < first + count; ++i) e->seen[i] += fuse, e->rpos[i] += fuse, e->last_flags[i] = fl;
-      if (out_flags)
-        for (int j = 0; j < fuse; ++j) out_flags[t + j] = fl;
+    uint32_t* fl = out_flags ? out_flags + t : nullptr;
+    const int rc = fuse == 1 ? process_range(e, first, count, fr, fg, bg, bits, s, fl) : clip_fused_run(e, first, count, fuse, slab, fr, fg, bg, bits, s, fl);
+    if (rc) {
+      (void)end_ring_clip(t);
+      return rc;
     }
-    t += fuse;
   }
   return end_ring_clip(nframes);
 }
@@ -1040,7 +1096,7 @@ int bgs_set_geometry(bgs_engine* e, int rows, int cols, int channels) {
 int bgs_set_option(bgs_engine* e, int option, int64_t value) {
   if (!e) return fail(BGS_ERR_INVALID, "engine is NULL");
   switch (option) {
-    case 1: e->borrow = value != 0; return BGS_OK;
+    case 1: e->hist.mode = value ? FrameHistory::kBorrowed : FrameHistory::kPrivate; return BGS_OK;
     case 2:  // round-2 A/B knobs (pixels per lane, planar layout): accepted and ignored since the slot layout of round 3
     case 3: return BGS_OK;
     case 4: e->knob.xcd_swizzle = (int)std::min<int64_t>(std::max<int64_t>(value, 0), 2); return BGS_OK;
@@ -1095,6 +1151,33 @@ int bgs_process_batch_device(bgs_engine* e, const void* d_frames, void* d_fg, vo
 
 static int lane_wait(bgs_engine* e, int stream, uint32_t* out_flags);  // bgs_submit / bgs_wait, below
 
+// where the frame of a host call goes on the device: the history classes receive the upload straight in their ring slot (zero-copy history)
+static uint8_t* lane_dst(const bgs_engine* e, const Lane& ln, int stream) {
+  uint8_t* slot = e->hist.keep_at(e->rpos[stream], (size_t)stream * e->n * e->ch);
+  return slot ? slot : ln.in.d;
+}
+
+// What bgs_process and bgs_submit do with a frame on their lane: the upload - straight from the caller's page-locked buffer, or staged
+// (map: bgs_set_ingest's flip / ROI, free of charge: the row map says where each staged row starts); not when the ingest kernels wrote
+// the frame (in == NULL) - then the model's step with private history.  The mask stays on the device for bgs_last_mask_blobs.
+static int lane_frame(bgs_engine* e, Lane& ln, int stream, const uint8_t* in, size_t in_step, const RowMap* map, bool want_bg, uint32_t* flags) {
+  HostPath& hp = e->host;
+  const size_t rb = (size_t)e->cols * e->ch, fb = e->n * e->ch;
+  uint8_t* dst = lane_dst(e, ln, stream);
+  if (in) {
+    hp.frames++, hp.h2d_bytes += (int64_t)fb;
+    if (!map && in_step == rb && host_pin(e, stream, 0, in, fb, ln.hs)) {
+      HIP_TRY(hipMemcpyAsync(dst, in, fb, hipMemcpyHostToDevice, ln.hs));
+    } else {
+      const auto st0 = std::chrono::steady_clock::now();
+      HIP_TRY(upload_rows(ln.in, dst, ln.hs, in, in_step, rb, e->rows, band_count(e->rows), map));
+      hp.stage_in_ms += ms_since(st0);
+    }
+  }
+  FrameHistory::Scope own(e->hist);
+  return process_range(e, stream, 1, dst, ln.fg.d, want_bg ? ln.bg.d : nullptr, nullptr, ln.hs, flags);
+}
+
 int bgs_process(bgs_engine* e, int stream, const uint8_t* in, int rows, int cols, int channels, size_t in_step, uint8_t* fg, size_t fg_step, uint8_t* bg,
                 size_t bg_step, uint32_t* out_flags) {
   if (out_flags) *out_flags = 0;
@@ -1127,10 +1210,6 @@ int bgs_process(bgs_engine* e, int stream, const uint8_t* in, int rows, int cols
   rc = lane_make(e, ln, "bgs_process", stream);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(e->device));
-  const size_t rb = (size_t)cols * channels, fb = e->n * channels;
-  // history-keeping algorithms receive the upload straight in their ring slot (zero-copy history)
-  uint8_t* dst = ln.in.d;
-  if (e->nring) dst = e->ring[e->rpos[stream] % e->nring] + (size_t)stream * fb;
   if (ingest_on_device) {
     // resize / equalizeHist / GaussianBlur: the raw frame goes up as it is, the preparation runs between the upload and the model kernel
     const size_t raw_rb = (size_t)raw_cols * channels;
@@ -1140,26 +1219,13 @@ int bgs_process(bgs_engine* e, int stream, const uint8_t* in, int rows, int cols
       if (er != hipSuccess) return fail(BGS_ERR_HIP, "bgs_process: staging of the raw frame: %s", hipGetErrorString(er));
     }
     HIP_TRY(upload_rows(hp.raw, hp.raw.d, ln.hs, in, in_step, raw_rb, raw_rows, band_count(raw_rows)));
-    rc = bgs_ingest_device(e->device, &e->ingest, hp.raw.d, 1, raw_rows, raw_cols, channels, raw_rb, dst, hp.ingest_ws.d, ln.hs);
+    rc = bgs_ingest_device(e->device, &e->ingest, hp.raw.d, 1, raw_rows, raw_cols, channels, raw_rb, lane_dst(e, ln, stream), hp.ingest_ws.d, ln.hs);
     if (rc) return rc;
-  } else {
-    // flip (rows reversed) and ROI (a window of the raw frame) cost nothing extra: the row map says where each staged row starts
-    hp.frames++, hp.h2d_bytes += (int64_t)fb;
-    if (!ingest && in_step == rb && host_pin(e, stream, 0, in, fb, ln.hs)) {
-      HIP_TRY(hipMemcpyAsync(dst, in, fb, hipMemcpyHostToDevice, ln.hs));  // straight from the caller's page-locked frame buffer
-    } else {
-      const auto st0 = std::chrono::steady_clock::now();
-      const RowMap map{e->ingest.flip != 0, pl.rh, pl.y0, (size_t)pl.x0 * channels};
-      HIP_TRY(upload_rows(ln.in, dst, ln.hs, in, in_step, rb, rows, band_count(rows), ingest ? &map : nullptr));
-      hp.stage_in_ms += ms_since(st0);
-    }
   }
   uint32_t flags = 0;
-  const bool saved_borrow = e->borrow;
-  e->borrow = false;
+  const RowMap map{e->ingest.flip != 0, pl.rh, pl.y0, (size_t)pl.x0 * channels};
   e->last_fg_stream = -1;
-  rc = process_range(e, stream, 1, dst, ln.fg.d, bg ? ln.bg.d : nullptr, nullptr, ln.hs, &flags);  // the mask stays on the device for bgs_last_mask_blobs
-  e->borrow = saved_borrow;
+  rc = lane_frame(e, ln, stream, ingest_on_device ? nullptr : in, in_step, ingest ? &map : nullptr, bg != nullptr, &flags);
   if (rc) return rc;
   if (flags & BGS_FG_VALID) e->last_fg_stream = stream;
   const int bg_ch = bg_channels(e);
@@ -1217,26 +1283,12 @@ int bgs_submit(bgs_engine* e, int stream, const uint8_t* in, int rows, int cols,
   HostPath& hp = e->host;
   Lane& ln = hp.lanes[stream];
   HostPath::Submission& sub = hp.sub[stream];
-  const size_t rb = (size_t)cols * channels, fb = e->n * channels;
   const int bg_ch = bg_channels(e);
   rc = lane_make(e, ln, "bgs_submit", stream);
   if (rc) return rc;
-  uint8_t* dst = ln.in.d;
-  if (e->nring) dst = e->ring[e->rpos[stream] % e->nring] + (size_t)stream * fb;  // history classes: straight into their ring slot
-  hp.frames++, hp.h2d_bytes += (int64_t)fb;
-  if (in_step == rb && host_pin(e, stream, 0, in, fb, ln.hs)) {
-    HIP_TRY(hipMemcpyAsync(dst, in, fb, hipMemcpyHostToDevice, ln.hs));
-  } else {
-    const auto st0 = std::chrono::steady_clock::now();
-    HIP_TRY(upload_rows(ln.in, dst, ln.hs, in, in_step, rb, rows, band_count(rows)));
-    hp.stage_in_ms += ms_since(st0);
-  }
   uint32_t flags = 0;
-  const bool saved_borrow = e->borrow;
-  e->borrow = false;
   if (e->last_fg_stream == stream) e->last_fg_stream = -1;  // bgs_last_mask_blobs serves the synchronous call's mask
-  rc = process_range(e, stream, 1, dst, ln.fg.d, bg ? ln.bg.d : nullptr, nullptr, ln.hs, &flags);
-  e->borrow = saved_borrow;
+  rc = lane_frame(e, ln, stream, in, in_step, nullptr, bg != nullptr, &flags);
   if (rc) return rc;
   const bool out_fg = fg && (flags & BGS_FG_VALID), out_bg = bg && (flags & BGS_BG_VALID);
   sub.flags = flags, sub.fg = fg, sub.bg = bg, sub.fg_step = fg_step, sub.bg_step = bg_step;
@@ -1325,9 +1377,7 @@ int bgs_stream_flags(const bgs_engine* e, int stream, uint32_t* out_flags) {
 
 int bgs_enable_kernel_timing(bgs_engine* e, int on) {
   if (!e) return fail(BGS_ERR_INVALID, "engine is NULL");
-  e->timing = on != 0;
-  for (auto& ev : e->events) (void)hipEventDestroy(ev.first), (void)hipEventDestroy(ev.second);
-  e->events.clear();
+  e->timer.enable(on != 0);
   return BGS_OK;
 }
 
@@ -1335,14 +1385,10 @@ int bgs_kernel_timing(bgs_engine* e, double* avg_ms, int64_t* launches, const ch
   if (!e) return fail(BGS_ERR_INVALID, "engine is NULL");
   HIP_TRY(hipSetDevice(e->device));
   double total = 0;
-  for (auto& ev : e->events) {
-    HIP_TRY(hipEventSynchronize(ev.second));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ev.first, ev.second));
-    total += ms;
-  }
-  if (avg_ms) *avg_ms = e->events.empty() ? 0.0 : total / (double)e->events.size();
-  if (launches) *launches = (int64_t)e->events.size();
+  int64_t n = 0;
+  HIP_TRY(e->timer.read(true, INT64_MAX, nullptr, &n, &total));
+  if (avg_ms) *avg_ms = n ? total / (double)n : 0.0;
+  if (launches) *launches = n;
   if (kernel_name) *kernel_name = e->kernel_name;
   return BGS_OK;
 }
@@ -1350,13 +1396,9 @@ int bgs_kernel_timing(bgs_engine* e, double* avg_ms, int64_t* launches, const ch
 int64_t bgs_kernel_timing_series(bgs_engine* e, float* ms, int64_t cap) {
   if (!e || !ms || cap < 0) return fail(BGS_ERR_INVALID, "bad argument");
   HIP_TRY(hipSetDevice(e->device));
+  double total = 0;
   int64_t n = 0;
-  for (auto& ev : e->events) {
-    if (n >= cap) break;
-    HIP_TRY(hipEventSynchronize(ev.second));
-    HIP_TRY(hipEventElapsedTime(&ms[n], ev.first, ev.second));
-    ++n;
-  }
+  HIP_TRY(e->timer.read(true, cap, ms, &n, &total));
   return n;
 }
 

@@ -5,7 +5,9 @@
 // classes among them (FrameDifference, StaticFrameDifference, WeightedMovingMean, WeightedMovingVariance,
 // AdaptiveBackgroundLearning, SigmaDelta - at most one instance of each) as ONE kernel over one read of the frame and one
 // shared history ring (kernel_fanout.h); every other class (and a second instance of a fused one) is a member engine fed the
-// same device frame.  Outputs, warm-up conventions and states are those of the separate engines, bit for bit.
+// same device frame.  Outputs, warm-up conventions and states are those of the separate engines, bit for bit: the state of a fused
+// class IS its family's state struct (engine_pointwise.h), the ring the FrameHistory an engine has, and what acts on them (ABL's rule
+// and table, first frames, planes, geometry refusals, the persistent grid, the timer) the functions the engines call.
 // The streams of a group advance in lock-step (whole-batch calls); the host entry point serves single-stream groups, which is
 // what FrameProcessor is.
 #pragma once
@@ -19,23 +21,17 @@ struct bgs_group {
   std::vector<unsigned> fan_bit;        // per class: its kFan* bit, 0 = member engine
   std::vector<bgs_engine*> member;      // per class: own engine, or null when fused
   unsigned fused = 0;                   // union of the fan bits
-  uint8_t* ring[3] = {nullptr, nullptr, nullptr};
-  int nring = 0;
-  bool borrow = false;                  // BGS_OPT_BORROW_FRAMES: the caller's previous d_frames buffers are the history
-  const uint8_t* borrowed[2] = {nullptr, nullptr};
-  uint8_t *sfd_bg = nullptr, *abl_state = nullptr, *abl_lut = nullptr, *sd_mt = nullptr, *sd_vt = nullptr;
-  double abl_lut_alpha = 0;
-  bool abl_lut_valid = false;
-  int64_t seen = 0, abl_counter = 0;
+  FrameHistory hist;                    // ONE ring of 2 (FD alone) or 3 slots for all of them, at position `seen`: a group has no bgs_reset_stream
+  SbgState sfd, abl;                    // abl.lut follows params lazily: it is rebuilt by the next process call after bgs_group_set_params
+  SdState sd;
+  int64_t seen = 0, abl_counter = 0;    // ONE ABL counter for all the streams
   int n_cu = 256;
   hipStream_t stream = nullptr;
   // bgs_group_process (single-stream groups): staging of the frame and of every class's mask and background (host_path.h), made
   // whole by the first call and released with the group
   Staging in;
   std::vector<Staging> fg, bg;
-  // kernel timing of the fused launch
-  bool timing = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+  LaunchTimer timer;                    // of the fused launch
 };
 
 namespace {
@@ -52,16 +48,6 @@ unsigned fan_bit_of(bgs_algo a) {
   }
 }
 
-void group_free(bgs_group* g) {  // the model; there is no staging before there is a model
-  void* dev[] = {g->ring[0], g->ring[1], g->ring[2], g->sfd_bg, g->abl_state, g->abl_lut, g->sd_mt, g->sd_vt};
-  for (void* d : dev)
-    if (d) (void)hipFree(d);
-  g->ring[0] = g->ring[1] = g->ring[2] = nullptr, g->sfd_bg = g->abl_state = g->abl_lut = g->sd_mt = g->sd_vt = nullptr;
-  for (auto& ev : g->events) (void)hipEventDestroy(ev.first), (void)hipEventDestroy(ev.second);
-  g->events.clear();
-  g->abl_lut_valid = false;
-}
-
 int group_index_of(const bgs_group* g, unsigned bit) {
   for (size_t i = 0; i < g->fan_bit.size(); ++i)
     if (g->fan_bit[i] == bit) return (int)i;
@@ -70,38 +56,27 @@ int group_index_of(const bgs_group* g, unsigned bit) {
 
 int group_build_lut(bgs_group* g) {
   const int i = group_index_of(g, bgs::kFanABL);
-  if (i < 0) return BGS_OK;
-  const double alpha = g->params[i].alpha;
-  if (g->abl_lut_valid && alpha == g->abl_lut_alpha) return BGS_OK;
-  // a launch still in flight on some stream may be reading the table: let the device drain before it is rewritten
-  if (g->abl_lut_valid) HIP_TRY(hipDeviceSynchronize());
-  if (!g->abl_lut) HIP_TRY(hipMalloc((void**)&g->abl_lut, 256 * 256));
-  hipLaunchKernelGGL(bgs::abl_lut_kernel, dim3(256), dim3(bgs::kBlock), 0, g->stream, g->abl_lut, alpha, 1 - alpha);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(g->stream));
-  g->abl_lut_alpha = alpha, g->abl_lut_valid = true;
-  return BGS_OK;
+  return i < 0 ? BGS_OK : abl_table(g->abl, g->params[i].alpha, g->device, g->stream);
 }
 
 int group_allocate(bgs_group* g, int rows, int cols, int ch) {
-  if (rows <= 0 || cols <= 0) return fail(BGS_ERR_INVALID, "bad geometry %dx%d", rows, cols);
-  if (ch != 1 && ch != 3) return fail(BGS_ERR_UNSUPPORTED, "channels must be 1 or 3, got %d", ch);
-  if ((g->fused & bgs::kFanSD) && ch != 3) return fail(BGS_ERR_UNSUPPORTED, "SigmaDeltaBGS is 3-channel only (sdLaMa091AllocInit_8u_C3R, SigmaDeltaBGS.cpp:35)");
+  int rc = check_geometry((g->fused & bgs::kFanSD) ? &kSigmaDelta : nullptr, BGS_SIGMA_DELTA, rows, cols, ch);
+  if (rc) return rc;
   HIP_TRY(hipSetDevice(g->device));
   g->rows = rows, g->cols = cols, g->ch = ch, g->n = (size_t)rows * cols;
   const size_t fb = g->n * g->S * ch;
   if (!g->stream) HIP_TRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-  g->nring = (g->fused & (bgs::kFanWMM | bgs::kFanWMV)) ? 3 : (g->fused & bgs::kFanFD) ? 2 : 0;
-  for (int i = 0; i < g->nring; ++i) HIP_TRY(hipMalloc((void**)&g->ring[i], fb));
-  if (g->fused & bgs::kFanSFD) HIP_TRY(hipMalloc((void**)&g->sfd_bg, fb));
-  if (g->fused & bgs::kFanABL) HIP_TRY(hipMalloc((void**)&g->abl_state, fb));
+  g->hist.nring = (g->fused & (bgs::kFanWMM | bgs::kFanWMV)) ? 3 : (g->fused & bgs::kFanFD) ? 2 : 0;
+  for (int i = 0; i < g->hist.nring; ++i) HIP_TRY(hipMalloc((void**)&g->hist.slot[i].p, fb));
+  if (g->fused & bgs::kFanSFD) HIP_TRY(hipMalloc((void**)&g->sfd.bg.p, fb));
+  if (g->fused & bgs::kFanABL) HIP_TRY(hipMalloc((void**)&g->abl.bg.p, fb));
   if (g->fused & bgs::kFanSD) {
-    HIP_TRY(hipMalloc((void**)&g->sd_mt, fb));
-    HIP_TRY(hipMalloc((void**)&g->sd_vt, fb));
+    HIP_TRY(hipMalloc((void**)&g->sd.mt.p, fb));
+    HIP_TRY(hipMalloc((void**)&g->sd.vt.p, fb));
   }
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, g->device) == hipSuccess && prop.multiProcessorCount > 0) g->n_cu = prop.multiProcessorCount;
-  int rc = group_build_lut(g);
+  rc = group_build_lut(g);
   if (rc) return rc;
   for (size_t i = 0; i < g->member.size(); ++i)
     if (g->member[i]) {
@@ -113,17 +88,9 @@ int group_allocate(bgs_group* g, int rows, int cols, int ch) {
 
 template <int G, int C>
 void group_launch_fan(bgs_group* g, const bgs::FanArgs& a, hipStream_t s) {
-  const bool lut = (a.mask & bgs::kFanABL) && a.abl_update;
-  if (lut) {
-    static std::atomic<int> per_cu_cache{0};  // a property of the code object; atomic because groups may be driven from several host threads
-    int per_cu = per_cu_cache.load(std::memory_order_relaxed);
-    if (!per_cu) {
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bgs::fan_kernel<G, C, true>, bgs::kAblBlock, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-      per_cu_cache.store(per_cu, std::memory_order_relaxed);
-    }
+  if ((a.mask & bgs::kFanABL) && a.abl_update) {  // the table form is persistent, like abl_kernel
     const size_t per_tile = (size_t)bgs::kAblBlock * G, ntiles = (a.npix + per_tile - 1) / per_tile;
-    const dim3 grid((unsigned)std::min<size_t>(ntiles, (size_t)per_cu * g->n_cu));
-    hipLaunchKernelGGL((bgs::fan_kernel<G, C, true>), grid, dim3(bgs::kAblBlock), 0, s, a, (const uint8_t*)g->abl_lut);
+    hipLaunchKernelGGL((bgs::fan_kernel<G, C, true>), (resident_grid<bgs::fan_kernel<G, C, true>>(ntiles, g->n_cu)), dim3(bgs::kAblBlock), 0, s, a, (const uint8_t*)g->abl.lut.p);
   } else {
     hipLaunchKernelGGL((bgs::fan_kernel<G, C, false>), dim3(blocks_for((a.npix + G - 1) / G)), dim3(bgs::kBlock), 0, s, a, (const uint8_t*)nullptr);
   }
@@ -146,83 +113,50 @@ int group_process_device(bgs_group* g, const uint8_t* d_frames, uint8_t* const* 
     if (rc) return rc;
     bgs::FanArgs a{};
     a.npix = npix;
-    const uint8_t *cur = d_frames, *h1 = nullptr, *h2 = nullptr;
-    if (g->nring) {
-      const int R = g->nring;
-      if (g->borrow) {
-        h1 = g->borrowed[0], h2 = g->borrowed[1];
-        g->borrowed[1] = g->borrowed[0], g->borrowed[0] = d_frames;
-      } else {
-        uint8_t* slot = g->ring[t % R];
-        HIP_TRY(hipMemcpyAsync(slot, cur, fb, hipMemcpyDeviceToDevice, s));  // a private copy as history
-        cur = slot;
-        if (t >= 1) h1 = g->ring[(t - 1) % R];
-        if (t >= 2 && R == 3) h2 = g->ring[(t - 2) % R];
-      }
-    }
-    a.cur = cur, a.p1 = h1, a.p2 = h2;
-    auto out_of = [&](unsigned bit, bgs::FanOut& o, bool with_bg) -> int {
+    FrameHistory::Frames f;
+    HIP_TRY(g->hist.resolve(t, t, 0, fb, d_frames, s, &f));
+    a.cur = f.cur, a.p1 = f.h1, a.p2 = f.h2;
+    auto out_of = [&](unsigned bit, bgs::FanOut& o, bool with_bg, uint32_t fl) -> const bgs_params& {  // class `bit` takes part in this launch
       const int i = group_index_of(g, bit);
       const bgs_params& p = g->params[i];
       o.fg = d_fg ? d_fg[i] : nullptr, o.bg = (with_bg && d_bg) ? d_bg[i] : nullptr, o.bits = nullptr;
       o.thr = p.threshold, o.enable_thr = p.enable_threshold, o.enable_weight = p.enable_weight;
-      return i;
+      a.mask |= bit, flags[i] = fl;
+      return p;
     };
-    if ((g->fused & bgs::kFanFD) && t >= 1) {
-      const int i = out_of(bgs::kFanFD, a.fd, false);
-      a.mask |= bgs::kFanFD, flags[i] = BGS_FG_VALID;
-    }
+    if ((g->fused & bgs::kFanFD) && t >= 1) out_of(bgs::kFanFD, a.fd, false, BGS_FG_VALID);
     if (g->fused & bgs::kFanSFD) {
-      const int i = out_of(bgs::kFanSFD, a.sfd, false);
-      if (t == 0) HIP_TRY(hipMemcpyAsync(g->sfd_bg, d_frames, fb, hipMemcpyDeviceToDevice, s));  // img_input.copyTo(img_background)
-      a.sfd_bg = g->sfd_bg, a.mask |= bgs::kFanSFD, flags[i] = BGS_FG_VALID | BGS_BG_VALID;
-      if (d_bg && d_bg[i]) HIP_TRY(hipMemcpyAsync(d_bg[i], g->sfd_bg, fb, hipMemcpyDeviceToDevice, s));
+      out_of(bgs::kFanSFD, a.sfd, false, BGS_FG_VALID | BGS_BG_VALID);
+      uint8_t* bg = d_bg ? d_bg[group_index_of(g, bgs::kFanSFD)] : nullptr;
+      HIP_TRY(sbg_first_frame(g->sfd, t, 0, d_frames, fb, s));
+      a.sfd_bg = g->sfd.bg;
+      if (bg) HIP_TRY(hipMemcpyAsync(bg, a.sfd_bg, fb, hipMemcpyDeviceToDevice, s));
     }
-    if ((g->fused & bgs::kFanWMM) && t >= 2) {
-      const int i = out_of(bgs::kFanWMM, a.wmm, true);
-      a.mask |= bgs::kFanWMM, flags[i] = BGS_FG_VALID | BGS_BG_VALID;
-    }
-    if ((g->fused & bgs::kFanWMV) && t >= 2) {
-      const int i = out_of(bgs::kFanWMV, a.wmv, false);
-      a.mask |= bgs::kFanWMV, flags[i] = BGS_FG_VALID;
-    }
+    if ((g->fused & bgs::kFanWMM) && t >= 2) out_of(bgs::kFanWMM, a.wmm, true, BGS_FG_VALID | BGS_BG_VALID);
+    if ((g->fused & bgs::kFanWMV) && t >= 2) out_of(bgs::kFanWMV, a.wmv, false, BGS_FG_VALID);
     if (g->fused & bgs::kFanABL) {
-      const int i = out_of(bgs::kFanABL, a.abl, true);
-      const bgs_params& p = g->params[i];
-      if (t == 0) HIP_TRY(hipMemcpyAsync(g->abl_state, d_frames, fb, hipMemcpyDeviceToDevice, s));
-      a.abl_state = g->abl_state;
-      a.abl_update = ((p.limit > 0 && p.limit < g->abl_counter) || p.limit == -1) ? 1 : 0;
-      if (a.abl_update && p.limit > 0 && p.limit < g->abl_counter) g->abl_counter++;
-      a.mask |= bgs::kFanABL, flags[i] = BGS_FG_VALID | BGS_BG_VALID;
+      const bgs_params& p = out_of(bgs::kFanABL, a.abl, true, BGS_FG_VALID | BGS_BG_VALID);
+      HIP_TRY(sbg_first_frame(g->abl, t, 0, d_frames, fb, s));
+      a.abl_state = g->abl.bg, a.abl_update = abl_updates(p, g->abl_counter);
+      abl_count(p, g->abl_counter);
     }
     if (g->fused & bgs::kFanSD) {
-      const int i = out_of(bgs::kFanSD, a.sd, false);
-      const bgs_params& p = g->params[i];
-      if (t == 0) {  // SigmaDeltaBGS.cpp:33-39: allocate + initialise, return without output
-        HIP_TRY(hipMemcpyAsync(g->sd_mt, d_frames, fb, hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(bgs::sigmadelta_init_vt_kernel, dim3(blocks_for(fb)), dim3(bgs::kBlock), 0, s, g->sd_vt, fb, g->cols, (int)(uint8_t)p.sd_min_var);
-      } else {
-        a.sd_mt = g->sd_mt, a.sd_vt = g->sd_vt, a.sd_N = (uint32_t)p.sd_amp_factor, a.sd_vmin = (uint8_t)p.sd_min_var, a.sd_vmax = (uint8_t)p.sd_max_var;
-        a.mask |= bgs::kFanSD, flags[i] = BGS_FG_VALID;
-      }
+      const bgs_params& p = g->params[group_index_of(g, bgs::kFanSD)];
+      if (t == 0 && (rc = sd_first_frame(g->sd, 0, d_frames, fb, g->cols, p, s))) return rc;
+      if (t >= 1) out_of(bgs::kFanSD, a.sd, false, BGS_FG_VALID);
+      a.sd_mt = g->sd.mt, a.sd_vt = g->sd.vt, a.sd_N = (uint32_t)p.sd_amp_factor, a.sd_vmin = (uint8_t)p.sd_min_var, a.sd_vmax = (uint8_t)p.sd_max_var;
     }
     if (a.mask) {
       const void* ptrs[] = {a.cur, a.p1, a.p2, a.fd.fg, a.sfd.fg, a.wmm.fg, a.wmm.bg, a.wmv.fg, a.abl.fg, a.abl.bg, a.sd.fg};
       int G = npix % 4 ? 1 : 4;
       for (const void* q : ptrs)
         if (q && !aligned(q, 4)) G = 1;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (g->timing && g->events.size() < 16384 && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) (void)hipEventRecord(e0, s);
-      if (C == 3) {
-        if (G == 4) group_launch_fan<4, 3>(g, a, s);
-        else group_launch_fan<1, 3>(g, a, s);
-      } else {
-        if (G == 4) group_launch_fan<4, 1>(g, a, s);
+      {
+        Timed tm(g->timer, s);
+        if (C == 3 && G == 4) group_launch_fan<4, 3>(g, a, s);
+        else if (C == 3) group_launch_fan<1, 3>(g, a, s);
+        else if (G == 4) group_launch_fan<4, 1>(g, a, s);
         else group_launch_fan<1, 1>(g, a, s);
-      }
-      if (e0 && e1) {
-        (void)hipEventRecord(e1, s);
-        g->events.emplace_back(e0, e1);
       }
       HIP_TRY(hipGetLastError());
     }
@@ -293,9 +227,8 @@ void bgs_group_destroy(bgs_group* g) {
   (void)hipDeviceSynchronize();
   for (bgs_engine* e : g->member)
     if (e) bgs_destroy(e);
-  group_free(g);
   if (g->stream) (void)hipStreamDestroy(g->stream);
-  delete g;
+  delete g;  // the states, the ring, the timer and the staging release themselves
 }
 
 int bgs_group_size(const bgs_group* g) { return g ? (int)g->algos.size() : BGS_ERR_INVALID; }
@@ -318,7 +251,7 @@ int bgs_group_set_params(bgs_group* g, int index, const bgs_params* params) {
 int bgs_group_set_option(bgs_group* g, int option, int64_t value) {
   if (!g) return fail(BGS_ERR_INVALID, "group is NULL");
   if (option == BGS_OPT_BORROW_FRAMES) {
-    g->borrow = value != 0;
+    g->hist.mode = value ? FrameHistory::kBorrowed : FrameHistory::kPrivate;
     for (bgs_engine* e : g->member)
       if (e && (e->algo == BGS_FRAME_DIFF || e->algo == BGS_WMM || e->algo == BGS_WMV)) (void)bgs_set_option(e, option, value);
     return BGS_OK;
@@ -335,7 +268,7 @@ int bgs_group_set_geometry(bgs_group* g, int rows, int cols, int channels) {
     return fail(BGS_ERR_GEOMETRY, "a group keeps its geometry (%dx%dx%d); create a new one for %dx%dx%d", g->rows, g->cols, g->ch, rows, cols, channels);
   }
   int rc = group_allocate(g, rows, cols, channels);
-  if (rc) group_free(g), g->n = 0;
+  if (rc) g->hist.release(), g->sfd = SbgState(), g->abl = SbgState(), g->sd = SdState(), g->n = 0;  // everything, whatever part of it came to be
   return rc;
 }
 
@@ -373,10 +306,10 @@ int bgs_group_process(bgs_group* g, const uint8_t* in, int rows, int cols, int c
   std::vector<uint8_t*> dfg((size_t)K), dbg((size_t)K);
   for (int i = 0; i < K; ++i) dfg[i] = (fg && fg[i]) ? g->fg[i].d : nullptr, dbg[i] = (bg && bg[i]) ? g->bg[i].d : nullptr;
   std::vector<uint32_t> flags((size_t)K, 0);
-  const bool saved = g->borrow;
-  g->borrow = false;  // the staging buffer is reused every frame: history must be a private copy
-  rc = group_process_device(g, g->in.d, dfg.data(), dbg.data(), g->stream, flags.data());
-  g->borrow = saved;
+  {
+    FrameHistory::Scope own(g->hist);  // the staging buffer is reused every frame: private history, whatever BGS_OPT_BORROW_FRAMES says
+    rc = group_process_device(g, g->in.d, dfg.data(), dbg.data(), g->stream, flags.data());
+  }
   if (rc) return rc;
   for (int i = 0; i < K; ++i) {
     if (!(flags[i] & BGS_FG_VALID)) dfg[i] = nullptr;  // from here on: what comes back
@@ -401,31 +334,24 @@ int64_t bgs_group_get_state(bgs_group* g, int index, int stream, const char* pla
   if (!g->n) return fail(BGS_ERR_STATE, "no model yet");
   if (stream < 0 || stream >= g->S) return fail(BGS_ERR_INVALID, "stream %d outside 0..%d", stream, g->S - 1);
   if (hipSetDevice(g->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(BGS_ERR_HIP, "device sync failed");
-  const size_t nb = g->n * g->ch, off = nb * stream;
+  const size_t nb = g->n * g->ch;
   const uint8_t* src = nullptr;
-  const unsigned bit = g->fan_bit[index];
   const int64_t t = g->seen;
-  if (!strcmp(plane, "bg") && bit == bgs::kFanSFD) src = g->sfd_bg;
-  if (!strcmp(plane, "bg") && bit == bgs::kFanABL) src = g->abl_state;
-  if (!strcmp(plane, "mt") && bit == bgs::kFanSD && t >= 1) src = g->sd_mt;
-  if (!strcmp(plane, "vt") && bit == bgs::kFanSD && t >= 1) src = g->sd_vt;
-  if (!g->borrow && (bit & (bgs::kFanFD | bgs::kFanWMM | bgs::kFanWMV)) && g->nring) {
-    if (!strcmp(plane, "prev1") && t >= 1) src = g->ring[(t - 1) % g->nring];
-    if (!strcmp(plane, "prev2") && t >= 2 && g->nring == 3) src = g->ring[(t - 2) % g->nring];
+  switch (g->fan_bit[index]) {  // the planes of the class's family; a fused SigmaDelta answers mt / vt only, not the engine's "bg"
+    case bgs::kFanSFD: src = sbg_plane(g->sfd, t, nb, stream, plane); break;
+    case bgs::kFanABL: src = sbg_plane(g->abl, t, nb, stream, plane); break;
+    case bgs::kFanSD: src = sd_plane(g->sd, t, nb, stream, plane); break;
+    default: src = g->hist.mode == FrameHistory::kBorrowed ? nullptr : g->hist.plane(t, t, plane, nb * stream);  // lent history: the ring holds nothing
   }
   if (!src) return fail(BGS_ERR_STATE, "unknown state plane '%s' for class %d of the group", plane, index);
-  if (cap < nb) return fail(BGS_ERR_STATE, "buffer too small for plane %s", plane);
-  if (d2h_staged(dst, src + off, nb) != BGS_OK) return fail(BGS_ERR_HIP, "hipMemcpy failed");
-  return (int64_t)nb;
+  return copy_plane(plane, dst, cap, src, nb);
 }
 
 int64_t bgs_group_frames_seen(const bgs_group* g) { return g ? g->seen : BGS_ERR_INVALID; }
 
 int bgs_group_enable_kernel_timing(bgs_group* g, int on) {
   if (!g) return fail(BGS_ERR_INVALID, "group is NULL");
-  g->timing = on != 0;
-  for (auto& ev : g->events) (void)hipEventDestroy(ev.first), (void)hipEventDestroy(ev.second);
-  g->events.clear();
+  g->timer.enable(on != 0);
   return BGS_OK;
 }
 
@@ -434,14 +360,9 @@ int bgs_group_kernel_timing(bgs_group* g, double* avg_ms, int64_t* launches) {
   if (!g || !avg_ms || !launches) return fail(BGS_ERR_INVALID, "NULL argument");
   HIP_TRY(hipSetDevice(g->device));
   HIP_TRY(hipDeviceSynchronize());
-  double tot = 0;
-  for (auto& ev : g->events) {
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ev.first, ev.second);
-    tot += ms;
-  }
-  *launches = (int64_t)g->events.size();
-  *avg_ms = g->events.empty() ? 0.0 : tot / (double)g->events.size();
+  double total = 0;
+  (void)g->timer.read(false, INT64_MAX, nullptr, launches, &total);
+  *avg_ms = *launches ? total / (double)*launches : 0.0;
   return BGS_OK;
 }
 
